@@ -1,5 +1,6 @@
 """The driver's contract with bench.py: one JSON line on stdout with the agreed keys (GPU box only; a reduced
-layer so the check takes seconds -- the numbers of record come from the default invocation)."""
+layer so the check takes seconds -- the numbers of record come from the default invocation), and the sample
+--dump-outputs keeps of a wide layer (on the host)."""
 import json
 import os
 import subprocess
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
            "--n", "256", "--c", "512", "--m", "512", "--cpu-sample", "32", "--numpy-sample", "16"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -45,6 +46,70 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     npb = out["cpu_baseline_numpy"]
     assert npb["value"] > 0 and npb["cores"] >= 1 and npb["neurons_with_index_mismatch_vs_gpu"] == 0 and "process" in npb["kind"]
     assert 0 < roof["frac_call"] <= roof["frac"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_prints_the_headline_alone_and_dumps_its_last_step(tmp_path, oracle_mod):
+    """Without --full the line holds the headline and none of the secondary records; --steps sets the timed steps; --dump-outputs
+    writes the last timed step's Q, indices and residual norms -- the oracle's on the same seeded layer."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    N, C, m = 256, 512, 512
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--n", str(N), "--c", str(C), "--m", str(m), "--dump-outputs", str(tmp_path)]
+    res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "weights_quantized_per_sec" and out["unit"] == "weights/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f64" and out["steps"] == 3 and out["warmup"] == 1 and out["deferred_status_nonzero_steps"] == 0
+    assert out["ms_per_step"] > 0 and abs(out["value"] - N * C / (out["ms_per_step"] / 1e3)) <= 1e-6 * out["value"]
+    for key in ["roofline", "cpu_baseline", "cpu_baseline_numpy", "parity_sample", "long_rows", "ms_per_step_medians_prefetched"]:
+        assert key not in out, key
+    Q, idx, resid = (np.load(os.path.join(tmp_path, name + ".npy")) for name in ("Q", "idx", "resid"))
+    assert Q.dtype == np.float32 and idx.dtype == np.float32 and resid.dtype == np.float64
+    assert Q.shape == idx.shape == (N, C) and resid.shape == (C,)
+    X, Xq = bench.synthetic_layer(N, m, C, 0, 0)
+    W = bench.weight_block(N, 0, C)
+    alphabet, _ = oracle_mod.layer_alphabet(W, np.linspace(-1, 1, 3), 3.0)
+    Qo, io, ro = oracle_mod.layer(W, X, Xq, alphabet)
+    assert np.array_equal(idx, io.T.astype(np.float32)), "alphabet indices differ from the oracle"
+    assert np.array_equal(Q, Qo.T.astype(np.float32))
+    np.testing.assert_allclose(resid, ro, rtol=1e-5)
+
+
+def test_dump_outputs_keeps_a_fixed_column_sample_under_64_mb(tmp_path):
+    """bench.py --dump-outputs on the north-star layer's shape (CPU tensors): whole columns of Q and of the indices, the same ones on every
+    run, in layer order, all files float32 / float64 and under 64 MB together; a layer that fits is written whole."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    N, C = 4096, 4096
+    g = torch.Generator().manual_seed(0)
+    Q = torch.randn(N, C, generator=g)
+    idx = torch.randint(0, 3, (N, C), dtype=torch.int8, generator=g)
+    resid = torch.rand(C, dtype=torch.float64, generator=g)
+    runs = []
+    for name in ("a", "b"):
+        d = os.path.join(tmp_path, name)
+        bench._dump_outputs(d, Q, idx, resid)
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64e6
+        runs.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    a, b = runs
+    assert sorted(a) == ["Q", "idx", "resid"] and all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    k = a["Q"].shape[1]
+    assert 0 < k < C and a["idx"].shape == (N, k) and np.array_equal(a["resid"], resid.numpy())
+    Qn = Q.numpy()
+    cols = np.array([np.flatnonzero(Qn[0] == v)[0] for v in a["Q"][0]])
+    assert np.all(np.diff(cols) > 0)
+    assert np.array_equal(a["Q"], Qn[:, cols]) and np.array_equal(a["idx"], idx.numpy()[:, cols].astype(np.float32))
+    small = os.path.join(tmp_path, "small")
+    bench._dump_outputs(small, Q[:8, :5], idx[:8, :5], resid[:5])
+    assert np.array_equal(np.load(os.path.join(small, "Q.npy")), Qn[:8, :5])
 
 
 @pytest.mark.gpu
@@ -92,7 +157,7 @@ def test_bench_two_ranks_over_gloo_split_the_fixed_layer():
         port = sock.getsockname()[1]
     env = dict(os.environ, GPFQ_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
            "--fan-in", "256", "--neurons", "512", "--samples", "512"]      # (the launcher's parser would take "--n" for its own)
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -123,7 +188,7 @@ def test_bench_eight_ranks_over_gloo_strong_and_weak():
         port = sock.getsockname()[1]
     env = dict(os.environ, GPFQ_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--full",
            "--fan-in", "256", "--neurons", "520", "--samples", "512"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=1500, env=env)
     assert res.returncode == 0, res.stderr[-3000:]

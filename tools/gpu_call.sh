@@ -3,7 +3,7 @@
 #     gpurun --timeout 2400 -- 'bash tools/gpu_call.sh <step> [<step> ...]'
 # runs the named steps in order on the GPU box, from the repository root, everything it writes under gpurun_out/r06/ (merged back by gpurun).
 #   suite [pytest -k expr]   the whole -m gpu test suite (or a -k selection), tail of the report -> gpu_suite.txt
-#   bench [args]             python bench.py [args] -> bench.json (+ the line's headline figures printed)
+#   bench [args]             python bench.py --full [args] -> bench.json (+ the line's headline figures printed)
 #   ab                       bench.py of this tree against the same command in _base_r05/ (a git worktree of the round's base), twice each
 #   guard                    tools/bench_configs.py --skip-fc1 --shapes --check profiles/r05/configs.json (the perf guard) -> configs_check.txt
 #   configs                  tools/bench_configs.py --resnet --shapes -> gpurun_out/configs.json
@@ -44,11 +44,11 @@ while [ $# -gt 0 ]; do
       if [ ${#args[@]} -gt 0 ]; then timeout 3000 python -m pytest tests -x -q -m gpu -k "${args[*]}" 2>&1 | tail -12 | tee $OUT/gpu_suite.txt
       else timeout 3000 python -m pytest tests -x -q -m gpu 2>&1 | tail -12 | tee $OUT/gpu_suite.txt; fi ;;
     bench)
-      timeout 900 python bench.py "${args[@]}" > $OUT/bench.json.tmp 2> $OUT/bench.err && mv $OUT/bench.json.tmp $OUT/bench.json; tail -2 $OUT/bench.err; show $OUT/bench.json ;;
+      timeout 900 python bench.py --full "${args[@]}" > $OUT/bench.json.tmp 2> $OUT/bench.err && mv $OUT/bench.json.tmp $OUT/bench.json; tail -2 $OUT/bench.err; show $OUT/bench.json ;;
     ab)
       for rep in 1 2; do
         (cd _base_r05 && timeout 600 python bench.py --steps 20 --warmup 3 --numpy-sample 0 --long-rows 0) > $OUT/bench_base_$rep.json 2> $OUT/bench_base_$rep.err
-        timeout 600 python bench.py --steps 20 --warmup 3 --numpy-sample 0 --long-rows 0 > $OUT/bench_new_$rep.json 2> $OUT/bench_new_$rep.err
+        timeout 600 python bench.py --full --steps 20 --warmup 3 --numpy-sample 0 --long-rows 0 > $OUT/bench_new_$rep.json 2> $OUT/bench_new_$rep.err
       done
       show $OUT/bench_base_1.json $OUT/bench_new_1.json $OUT/bench_base_2.json $OUT/bench_new_2.json ;;
     guard)

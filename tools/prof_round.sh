@@ -2,7 +2,7 @@
 # usage (GPU box, from the repository root):  [ROUND=r04] bash tools/prof_round.sh
 # A round's profile set (rounds 2-4 ran it as prof_r02.sh / prof_r03.sh / prof_r04.sh: git history).  Everything lands in
 # gpurun_out/prof_$ROUND; what is committed under profiles/$ROUND/ is copied from there.
-#  1. rocprofv3 --kernel-trace --stats of `python3 bench.py` (the headline line) -> bench_kernel_stats.csv
+#  1. rocprofv3 --kernel-trace --stats of `python3 bench.py --full` (the headline line and its secondary steps) -> bench_kernel_stats.csv
 #  2. the same for tools/bench_configs.py (cfg1, cfg3 fc2 / fc1 / predictions, cfg4 all layers) -> configs_kernel_stats.csv
 #  (round 4: + the matrix-instruction counters of the headline kernel, whose dot products moved to v_mfma_f64_4x4x4_4b_f64;
 #   bench_configs.py runs with --resnet so that cfg5's layers are in the trace and in configs.json)
@@ -15,7 +15,7 @@ OUT=$ROOT/gpurun_out/prof_$ROUND
 mkdir -p $OUT
 export PYTHONPATH=$ROOT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 $ROOT/bench.py > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 $ROOT/bench.py --full > $OUT/bench.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/configs -o configs -- python3 $ROOT/tools/bench_configs.py --resnet > $OUT/configs.log 2>&1
 cd $ROOT
 find $OUT/bench -name "bench_kernel_stats.csv" -exec cp {} $OUT/bench_kernel_stats.csv \;

@@ -17,7 +17,7 @@ def main():
     if len(mains) < 3:
         print("fewer than three launches of", key)
         return
-    k = int(sys.argv[3]) if len(sys.argv) > 3 else -2           # (bench.py: warm-up steps, the timed steps, then the same steps with the medians prefetched)
+    k = int(sys.argv[3]) if len(sys.argv) > 3 else -2           # (bench.py --full: warm-up steps, the timed steps, then the same steps with the medians prefetched)
     a, b = mains[k - 1], mains[k]
     t0 = rows[a][1]
     print(f"microseconds from the end of the previous step's kernel; queue = HIP stream\n{'start':>9} {'end':>9} {'dur':>8}  queue  kernel")
