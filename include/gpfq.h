@@ -236,7 +236,8 @@ int gpfq_quantize_neurons(const float *X, const float *Xq, int64_t ld, const flo
  * gpfq_layer_alphabet_device forms, ON THE DEVICE, rad = float64(alphabet_scalar) * float64(*median32) (the reference's legacy-NumPy
  * typing of :544), the members rad * unit_alphabet[k] (float64 products, :545) and what the block-pipelined kernel derives from them,
  * into `dev_alphabet` (GPFQ_DEVICE_ALPHABET_BYTES of device memory, 16-byte aligned; float64 rad at byte 0, the M float64 members from
- * byte 128) -- no launch of the layer waits for the radius to reach the host.
+ * byte 128, int32 ok at byte 68: 1 where the block-pipelined kernel runs the alphabet, see gpfq_device_alphabet_ok) -- no launch of the
+ * layer waits for the radius to reach the host.
  *   median32       [device] f32 [1]   from gpfq_median_abs (or the sharded protocol)
  *   unit_alphabet  [host]   f64 [M]   linspace(-1, 1, M) (:396), 1 <= M <= 64
  *
@@ -265,6 +266,11 @@ int gpfq_layer_alphabet_device(const float *median32, double alphabet_scalar, co
 int gpfq_layer_alphabet_from_kernel(const float *W, int64_t n, double alphabet_scalar, const double *unit_alphabet, int M,
                                     void *dev_alphabet, float *median_out, void *workspace, size_t workspace_bytes, void *stream);
 int gpfq_dense_layer_supported(int64_t N, int64_t m, int64_t C, const double *unit_alphabet, int M);
+/* ... and whether the alphabet gpfq_layer_alphabet_device forms from a float32 median is one the block-pipelined kernel takes: 1, or 0
+ * where the kernel would write nothing and raise GPFQ_ERR_ALPHABET (a radius of 0, infinity or NaN, but also a finite radius whose
+ * members do not survive float32 -- a symmetric alphabet whose float32 radius is 0 -- or whose progression step overflows).  Host only:
+ * the same code the device runs, for a caller that holds the median on the host and wants no deferred status to wait for. */
+int gpfq_device_alphabet_ok(float median32, double alphabet_scalar, const double *unit_alphabet, int M);
 /* ... and whether the kernel of that shape writes GPFQ_LAYOUT_KERAS outputs itself (the 16-neuron four-step shapes: layers wider than 2048
  * neurons on rows of up to 1024 samples -- the decision wavefront has the slack there); elsewhere gpfq_quantize_dense_layer takes
  * GPFQ_LAYOUT_NEURON_MAJOR only (GPFQ_ERR_UNSUPPORTED otherwise) and gpfq_assemble_kernel_device lays the result out in one pass */

@@ -471,6 +471,15 @@ int gpfq_layer_alphabet_device(const float *median32, double alphabet_scalar, co
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_layer_alphabet_device");
 }
 
+// Whether the alphabet gpfq_layer_alphabet_device would form from this median is one the block-pipelined kernel runs (DevAlphabet::ok):
+// the same __host__ __device__ code on the host, no launch.  A caller that read the median back knows without the call's status.
+int gpfq_device_alphabet_ok(float median32, double alphabet_scalar, const double *unit_alphabet, int M)
+{
+    HostAlphabet H;
+    if (unit_alphabet_arg(unit_alphabet, M, &H) != GPFQ_OK || H.is_big) return 0;
+    return gpfq::device_alphabet_of(median32, alphabet_scalar, H.A, gpfq::blk_unit_wants_sym(H.A) ? 1 : 0).ok;
+}
+
 // median(|W|) and the layer alphabet in one go: the last workgroup of the median's second pass forms the alphabet (no launch of its
 // own between the two).  Needs the two-pass form: a 16-byte aligned kernel and gpfq_median_abs_workspace_bytes_for(n) of workspace.
 int gpfq_layer_alphabet_from_kernel(const float *W, int64_t n, double alphabet_scalar, const double *unit_alphabet, int M,
@@ -668,6 +677,9 @@ int gpfq_quantize_neurons_gram(const float *X, const float *Xq, int64_t ld, floa
     a.nrm32_out = compute_norms ? nrm32 : nullptr;
     a.slack = std::ldexp(1.0, g_gram_slack_log2);
     a.variant = g_variant;
+    // (noted like every other dense launch: a caller that asks gpfq_last_dense_kernel whether a deferred status exists -- the cluster
+    //  form's -- must not see the name of an earlier call's kernel)
+    gpfq::note_dense_kernel("gpfq_gram_* (Gram records + certified scalar recurrence)");
     hipError_t e = gpfq::launch_gram(a, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_quantize_neurons_gram");
 }

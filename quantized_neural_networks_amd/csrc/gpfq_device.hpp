@@ -14,6 +14,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace gpfq {
@@ -228,7 +229,8 @@ struct DevAlphabet {
     double pad[6];
     double a[64];                        // the members (float64), a[k] = rad * unit[k]
 };
-static_assert(sizeof(DevAlphabet) == 128 + 64 * 8, "DevAlphabet layout (include/gpfq.h documents the offsets of rad and a[])");
+static_assert(sizeof(DevAlphabet) == 128 + 64 * 8, "DevAlphabet layout (include/gpfq.h documents the offsets of rad, ok and a[])");
+static_assert(offsetof(DevAlphabet, rad) == 0 && offsetof(DevAlphabet, ok) == 68 && offsetof(DevAlphabet, a) == 128, "DevAlphabet offsets");
 
 // an alphabet by reference (members in device memory): the kernels templated on their alphabet argument index it like AlphabetT
 struct AlphabetRef {
@@ -290,8 +292,9 @@ __host__ __device__ inline float blk_sym_of(const double *a, int M)
 // product (:544: python scalar times np.float32 is a float64 product) --, members rad * unit[k] (:545: float64 products), and the
 // progression the chain of decisions indexes.  `want_sym`: the caller will launch the symmetric-form instantiations (the unit alphabet is
 // {-1, 0, 1} / {-1, 1}): an alphabet that is then not exactly symmetric is not ok.  One thread (gpfq_alphabet_device_kernel; the last
-// workgroup of the one-GPU median, gpfq_median2_kernel).
-__device__ inline void form_device_alphabet(DevAlphabet *out, float median32, double alphabet_scalar, const AlphabetArg &unit, int want_sym)
+// workgroup of the one-GPU median, gpfq_median2_kernel).  The host evaluates the same code (device_alphabet_of; gpfq_device_alphabet_ok):
+// a caller that holds the median on the host knows D.ok without reading the call's status.
+__host__ __device__ inline DevAlphabet device_alphabet_of(float median32, double alphabet_scalar, const AlphabetArg &unit, int want_sym)
 {
     DevAlphabet D{};
     D.M = unit.M; D.zero_idx = unit.zero_idx;
@@ -303,7 +306,12 @@ __device__ inline void form_device_alphabet(DevAlphabet *out, float median32, do
     // (the literal zero of rule (i) and the member 0: the caller's zero_idx is the unit alphabet's -- rad * 0 = 0 for every finite rad)
     if (ok && D.zero_idx >= 0 && D.a[D.zero_idx] != 0.0) ok = false;
     D.ok = ok ? 1 : 0;
-    *out = D;
+    return D;
+}
+
+__device__ inline void form_device_alphabet(DevAlphabet *out, float median32, double alphabet_scalar, const AlphabetArg &unit, int want_sym)
+{
+    *out = device_alphabet_of(median32, alphabet_scalar, unit, want_sym);
 }
 
 __device__ __forceinline__ double alphabet_lane(const AlphabetArg &A, int lane)

@@ -898,11 +898,14 @@ gpfq_median2_kernel(const float *__restrict__ W, int64_t n, int64_t per_block, S
 #ifdef GPFQ_MEDIAN_STAMPS
     if (blockIdx.x == 0 && tid == 0) stamps[0] = __builtin_amdgcn_s_memrealtime() - ts0;          // workgroup 0: zeroing + reads + merge
 #endif
-    // ---- the last workgroup to get here picks (each wavefront waits for its own merges -- agent-scope atomics -- to be acknowledged: a
-    // workgroup-scope release, no cache maintenance; an agent-scope fence per thread writes the L2 back thousands of times per pass) ----
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    // ---- the last workgroup to get here picks.  Each wavefront first waits for its own merges -- agent-scope atomics -- to be acknowledged:
+    // an explicit vmcnt(0) (s_waitcnt with expcnt and lgkmcnt left at their maxima).  A workgroup-scope release fence is NOT that wait: on
+    // gfx950 it emits no instruction at all, and the barrier does not wait for memory either (tests/test_median_handoff_isa.py checks the
+    // generated code).  An agent-scope fence per thread would write the L2 back thousands of times per pass; the ticket below is the one
+    // agent-scope release of the workgroup ----
+    __builtin_amdgcn_s_waitcnt(0x0f70);                            // vmcnt(0) expcnt(7) lgkmcnt(15) (gfx9: vmcnt in bits 3:0 and 15:14, expcnt 6:4, lgkmcnt 11:8)
     __syncthreads();
-    if (tid == 0) is_last = __hip_atomic_fetch_add(&ctl->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1 : 0;
+    if (tid == 0) is_last = __hip_atomic_fetch_add(&ctl->done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1 : 0;
     __syncthreads();
     if (!is_last) return;
 #ifdef GPFQ_MEDIAN_STAMPS

@@ -40,6 +40,7 @@ SYMBOLS = {
     "gpfq_layer_alphabet_device": (_int, [_vp, ctypes.c_double, _dp, _int, _vp, _vp]),
     "gpfq_layer_alphabet_from_kernel": (_int, [_vp, _i64, ctypes.c_double, _dp, _int, _vp, _vp, _vp, _sz, _vp]),
     "gpfq_dense_layer_supported": (_int, [_i64, _i64, _i64, _dp, _int]),
+    "gpfq_device_alphabet_ok": (_int, [ctypes.c_float, ctypes.c_double, _dp, _int]),
     "gpfq_dense_layer_keras_out_supported": (_int, [_i64, _i64, _i64, _dp, _int]),
     "gpfq_dense_layer_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "gpfq_quantize_dense_layer": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _dp, _int, _i64, _i64,
@@ -627,6 +628,14 @@ def dense_layer_supported(N, m, C, unit_alphabet):
     """Whether quantize_dense_layer (device-resident alphabet, the block-pipelined kernel) takes this shape and unit alphabet."""
     arr = (ctypes.c_double * len(unit_alphabet))(*[float(v) for v in unit_alphabet])
     return bool(load().gpfq_dense_layer_supported(int(N), int(m), int(C), arr, len(unit_alphabet)))
+
+
+def device_alphabet_ok(median32, unit_alphabet, alphabet_scalar):
+    """Whether the device alphabet formed from the float32 median (layer_alphabet_device) is one the block-pipelined kernel runs -- the
+    device's own predicate (DevAlphabet::ok) evaluated on the host: a finite positive radius is not enough (float32 members, the step)."""
+    import numpy as np
+    arr = (ctypes.c_double * len(unit_alphabet))(*[float(v) for v in unit_alphabet])
+    return bool(load().gpfq_device_alphabet_ok(float(np.float32(median32)), float(alphabet_scalar), arr, len(unit_alphabet)))
 
 
 def _dense_layer_args(X, Xq, W, unit, lo, hi):

@@ -8,6 +8,8 @@ process group (one process per GPU, backend "nccl" = RCCL over xGMI).  Every ran
 activation matrices and the full analog kernel, quantizes its shard, and ONE all-gather per layer
 reassembles the quantized kernel; there is no other communication.
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -238,6 +240,7 @@ def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, ch
     world, rank = _group_info(group)
     lo, hi = shard_bounds(C, world, rank)
     dalpha = alphabet if isinstance(alphabet, hip.DeviceAlphabet) else None
+    no_cluster = False                                            # (a timed-out exchange of the device alphabet's launch: the host path without the cluster form)
     if dalpha is not None and not (X.shape[1] > 0 and hip.dense_layer_supported(N, X.shape[1], max(hi - lo, 1), dalpha.unit)):
         alphabet, dalpha = dalpha.values(), None                   # (no block-pipelined kernel for this shape: the host alphabet's paths)
     Wc = W.contiguous()
@@ -249,12 +252,23 @@ def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, ch
         need = check and not (getattr(dalpha, "radius_ok", False) and "cluster form" not in hip.last_dense_kernel())
         st = hip.call_status(r) if need else 0
         if st == hip.GPFQ_ERR_CLUSTER_TIMEOUT:
-            _log_failure(log, f"Dense layer {N} x {C}: the cluster form's exchange timed out; rerunning the layer through the classic kernels")
             with hip.option("blk_cluster", 0):
-                r = hip.quantize_dense_layer(X, Xq, Wc, dalpha, lo, hi, keras_out=(world == 1), want_values=(world == 1), want_resid=want_resid)
-                st = hip.call_status(r)
+                classic = hip.dense_layer_supported(N, X.shape[1], max(hi - lo, 1), dalpha.unit)
+                if classic:
+                    _log_failure(log, f"Dense layer {N} x {C}: the cluster form's exchange timed out; rerunning the layer through the classic kernels")
+                    r = hip.quantize_dense_layer(X, Xq, Wc, dalpha, lo, hi, keras_out=(world == 1), want_values=(world == 1), want_resid=want_resid)
+                    st = hip.call_status(r)
+            if not classic:
+                # rows beyond the classic block shapes (more than 5120 samples): only the cluster form reads a device alphabet there --
+                # the host alphabet's kernels (several wavefronts per neuron, the streaming kernel) take the layer, with the cluster form off
+                _log_failure(log, f"Dense layer {N} x {C}: the cluster form's exchange timed out and no classic block kernel takes rows of "
+                                  f"{X.shape[1]} samples; rerunning the layer with the host alphabet without the cluster form")
+                alphabet, dalpha, st, no_cluster = dalpha.values(), None, 0, True
         if st == hip.GPFQ_ERR_ALPHABET:
-            # radius 0 / infinite / NaN (the median of a kernel that is mostly zeros): only the host alphabet's kernels take such a one
+            # radius 0 / infinite / NaN (the median of a kernel that is mostly zeros), or members the kernel cannot index (a float32 radius
+            # of 0, a step that overflows): only the host alphabet's kernels take such a one
+            _log_failure(log, f"Dense layer {N} x {C}: the device alphabet (radius {float(dalpha.rad())!r}) is not one the block kernel "
+                              f"runs; rerunning the layer with the host alphabet")
             alphabet, dalpha = dalpha.values(), None
         elif st != 0:
             raise hip.GpfqError(f"quantize_dense: status {st} after the fallback")
@@ -272,20 +286,21 @@ def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, ch
         return out
     Wt = hip.neuron_major(Wc, lo, hi)                            # neuron-major shard [C_local][N]
     deferred = None
-    if hi > lo:
-        if world > 1:
-            # (a rank whose exchange timed out repairs its shard BEFORE the all-gather: the other ranks never see garbage and nobody
-            #  has to agree on anything)
-            r = quantize_neurons_checked(X, Xq, Wt, alphabet, log=log, want_values=False, want_resid=want_resid)
+    with (hip.option("blk_cluster", 0) if no_cluster else contextlib.nullcontext()):
+        if hi > lo:
+            if world > 1:
+                # (a rank whose exchange timed out repairs its shard BEFORE the all-gather: the other ranks never see garbage and nobody
+                #  has to agree on anything)
+                r = quantize_neurons_checked(X, Xq, Wt, alphabet, log=log, want_values=False, want_resid=want_resid)
+            else:
+                # one GPU: the assembly pass is queued behind the kernel first and the status read after it -- the host's wait then costs no
+                # bubble between the two (cfg4's Dense(128 -> 10): 0.06 ms of a 0.15 ms layer); nothing is RETURNED unchecked
+                r = hip.quantize_neurons(X, Xq, Wt, alphabet, want_values=False, want_resid=want_resid)
+                deferred = r if "cluster form" in hip.last_dense_kernel() else None
+            i_loc, res_loc = r["idx"], r["resid"]
         else:
-            # one GPU: the assembly pass is queued behind the kernel first and the status read after it -- the host's wait then costs no
-            # bubble between the two (cfg4's Dense(128 -> 10): 0.06 ms of a 0.15 ms layer); nothing is RETURNED unchecked
-            r = hip.quantize_neurons(X, Xq, Wt, alphabet, want_values=False, want_resid=want_resid)
-            deferred = r if "cluster form" in hip.last_dense_kernel() else None
-        i_loc, res_loc = r["idx"], r["resid"]
-    else:
-        i_loc = torch.empty((0, N), dtype=hip.index_dtype(len(alphabet)), device=W.device)
-        res_loc = torch.empty((0,), dtype=torch.float64, device=W.device)
+            i_loc = torch.empty((0, N), dtype=hip.index_dtype(len(alphabet)), device=W.device)
+            res_loc = torch.empty((0,), dtype=torch.float64, device=W.device)
     # only the indices travel over xGMI -- packed to 2 or 4 bits per weight when the alphabet allows;
     # values are looked up while transposing to the Keras layout
     if world > 1:

@@ -584,7 +584,7 @@ class QuantizedNeuralNetwork:
     def _prefetch_medians(self, layer_indices):
         """median(|W|) of the given layers' analog kernels, all queued before the first host wait (layers whose kernel is on the
         GPU and small enough for the one-GPU select; the others compute theirs when their turn comes)."""
-        self._medians, self._medians_dev = {}, {}
+        self._medians, self._medians_dev, self._medians_host = {}, {}, {}
         todo = []
         for k in layer_indices:
             Wd = self._kernel_on_device(self.trained_net.layers[k])
@@ -592,7 +592,7 @@ class QuantizedNeuralNetwork:
             if Wd.is_cuda and Wd.numel() > 0 and (world == 1 or Wd.numel() < _layer._SHARDED_MEDIAN_MIN):
                 todo.append((k, hip.median_abs(Wd.detach().reshape(-1), on_device=True)))
         for (k, t), v in zip(todo, hip.medians_to_host([t for _, t in todo])):
-            self._medians[k] = v
+            self._medians[k] = self._medians_host[k] = v
             self._medians_dev[k] = t
 
     def _layer_alphabet_device(self, layer_idx, rad):
@@ -604,7 +604,10 @@ class QuantizedNeuralNetwork:
             return None
         d = hip.layer_alphabet_device(t, self.alphabet, self.alphabet_scalar)
         d._rad = np.float64(rad)
-        d.radius_ok = bool(np.isfinite(rad) and rad > 0)          # known good on the host: no deferred alphabet status to wait for
+        # known good on the host -- the device's own predicate on the median read back (a finite positive rad is not enough: a float32
+        # radius of 0, a step that overflows): no deferred alphabet status to wait for
+        med = getattr(self, "_medians_host", {}).pop(layer_idx, None)
+        d.radius_ok = med is not None and hip.device_alphabet_ok(med, self.alphabet, self.alphabet_scalar)
         return d
 
     # -- Dense layer (reference :523-574) ---------------------------------------------------

@@ -24,8 +24,10 @@ def _free_port():
 
 def _inputs(case, dev):
     g = torch.Generator(device=dev).manual_seed(11)
-    if case in ("dense", "dense_8bit", "dense_long", "dense_device", "dense_device_long", "dense_device_wide"):
+    if case in ("dense", "dense_8bit", "dense_long", "dense_device", "dense_device_long", "dense_device_wide", "dense_device_timeout"):
         N, m, C = (120, 3100, 70) if case in ("dense_long", "dense_device_long") else ((40, 1024, 4500) if case == "dense_device_wide" else (300, 1024, 70))   # 70 neurons: uneven shards; dense_long: rows of the block kernel's cluster form (four slices per rank's launch)
+        if case == "dense_device_timeout":
+            N, m, C = 16, 6000, 30                               # rows only the cluster form takes among the block kernels (no classic twin)
         W = torch.randn((N, C), device=dev, generator=g) / np.sqrt(N)
         G = torch.randn((N, m), device=dev, generator=g)
         return dict(W=W, X=torch.relu(G), Xq=torch.relu(G + 0.1 * torch.randn((N, m), device=dev, generator=g)),
@@ -147,6 +149,26 @@ def _run(case, dev, group):
     unit = np.linspace(-1, 1, int(round(2 ** d["bits"])))
     if case == "dense_big_median":
         layer._SHARDED_MEDIAN_MIN = 1 << 22                      # (the sharded counting protocol at a test's size: the default threshold is 32 M weights since round 6)
+    if case == "dense_device_timeout":
+        # every rank's cluster exchange is forced to time out (one slice never publishes; 40 ms): each rank logs, repairs its shard with
+        # the host alphabet without the cluster form (no classic block shape takes rows of 6000 samples) BEFORE the all-gather
+        import oracle
+        from quantized_neural_networks_amd import hip
+        hip.set_option("blk_cluster_fault", 1)
+        hip.set_option("blk_cluster_timeout_ms", 40)
+        logged = []
+        try:
+            out = layer.quantize_dense_layer(d["W"], d["X"], d["Xq"], unit, 3, group=group, log=logged.append)
+        finally:
+            hip.set_option("blk_cluster_fault", 0)
+            hip.set_option("blk_cluster_timeout_ms", 3000)
+        assert any("timed out" in msg for msg in logged), logged
+        W, X, Xq = (d[k].cpu().numpy() for k in ("W", "X", "Xq"))
+        Q, idx, resid = oracle.layer(W, X, Xq, oracle.layer_alphabet(W, unit, 3)[0])
+        res = {k: out[k].cpu().numpy() for k in ("Q", "idx", "resid")}
+        assert np.array_equal(res["idx"], idx.T) and np.array_equal(res["Q"], Q.T.astype(np.float32))
+        np.testing.assert_allclose(res["resid"], resid, rtol=1e-5)
+        return res
     if case.startswith("dense_device"):
         # round 6: the layer driver with the alphabet formed and kept on the device (median -> rad * alphabet -> shard's kernel reading the
         # Keras kernel -> all-gather of packed indices -> assembly from the device alphabet), the pre-pass on a second stream; _wide: shards
@@ -187,6 +209,7 @@ def _worker(rank, world, port, case, result_dir):
 
 @pytest.mark.parametrize("case,world", [("dense", 2), ("dense", 3), ("dense_long", 2), ("dense_big_median", 2), ("conv3x3", 2), ("conv5x5", 3),
                                         ("dense_device", 2), ("dense_device", 8), ("dense_device_long", 2), ("dense_device_wide", 2),
+                                        ("dense_device_timeout", 2),
                                         ("dense_8bit", 3), ("conv3x3_8bit", 2), ("conv_filters_8bit", 2),
                                         ("network_mlp", 2), ("network_cnn", 2), ("network_cnn", 3), ("network_mlp_grid", 2),
                                         ("conv_filters", 2), ("conv_columns7", 3),    # fewer channels than ranks: image shards
