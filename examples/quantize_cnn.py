@@ -21,7 +21,7 @@ from time import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from quantized_network import CIFAR10Sequence, QuantizedCNN, msq_quantize  # noqa: E402
+from quantized_network import CIFAR10Sequence, QuantizedCNN, msq_quantize, msq_quantize_channels  # noqa: E402
 from quantized_neural_networks_amd import keras_shim as keras  # noqa: E402
 
 ParamConfig = namedtuple("ParamConfig", "pretrained_model, data_set, q_train_size, ignore_layers, bits, alphabet_scalar")
@@ -69,6 +69,8 @@ def main():
     ap.add_argument("--samples", type=int, default=5000, help="q_train_size (reference: 5000)")
     ap.add_argument("--bits", type=float, nargs="+", default=[np.log2(3)])
     ap.add_argument("--scalars", type=float, nargs="+", default=[2, 3, 4])
+    ap.add_argument("--radius", choices=["layer", "channel"], default="layer",
+                    help="one alphabet radius per layer (the reference's rule) or one per output channel, for GPFQ and MSQ alike")
     ap.add_argument("--csv", default=None, help="append the metrics rows here (reference schema and append semantics)")
     ap.add_argument("--save-dir", default=None, help="save every quantized model there (quantize_pretrained_cnn.py:97-100)")
     ap.add_argument("--test-samples", type=int, default=2000)
@@ -87,7 +89,7 @@ def main():
     for idx, params in enumerate(ParamConfig(*c) for c in grid):
         get_data = CIFAR10Sequence(X_train[0:params.q_train_size], y_train[0:params.q_train_size], batch_size=16)
         my_quant_net = QuantizedCNN(network=model, batch_size=params.q_train_size, get_data=get_data, logger=quiet,
-                                    bits=params.bits, alphabet_scalar=params.alphabet_scalar)
+                                    bits=params.bits, alphabet_scalar=params.alphabet_scalar, radius=args.radius)
         tic = time()
         my_quant_net.quantize_network()
         quantization_time = time() - tic
@@ -99,8 +101,12 @@ def main():
         for layer_idx, layer in enumerate(model.layers):
             if layer.__class__.__name__ in ("Dense", "Conv2D"):
                 W, b = layer.get_weights()
-                rad = params.alphabet_scalar * np.median(np.abs(W.flatten()))
-                MSQ_model.layers[layer_idx].set_weights([msq_quantize(W, rad * my_quant_net.alphabet), b])
+                if args.radius == "channel":
+                    Q = msq_quantize_channels(W, my_quant_net.alphabet, params.alphabet_scalar)
+                else:
+                    rad = params.alphabet_scalar * np.median(np.abs(W.flatten()))
+                    Q = msq_quantize(W, rad * my_quant_net.alphabet)
+                MSQ_model.layers[layer_idx].set_weights([Q, b])
         MSQ_accuracy = agreement(MSQ_model, y_test, X_test)
 
         import pandas as pd

@@ -8,7 +8,7 @@ what this image has: no TensorFlow and no MNIST files, so the network (the refer
 with BatchNormalization, train_mnist_mlp.py:60-73) is built with the torch-backed Keras shim, weights are
 random, data are synthetic, and "accuracy" is agreement with the analog network's own predictions.
 
-    python examples/quantize_mlp.py [--samples 25000] [--scalars 2 3 4]
+    python examples/quantize_mlp.py [--samples 25000] [--scalars 2 3 4] [--radius layer|channel]
 """
 import argparse
 import os
@@ -20,7 +20,7 @@ from time import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from quantized_network import MNISTSequence, QuantizedNeuralNetwork, msq_quantize  # noqa: E402
+from quantized_network import MNISTSequence, QuantizedNeuralNetwork, msq_quantize, msq_quantize_channels  # noqa: E402
 from quantized_neural_networks_amd import keras_shim as keras  # noqa: E402
 
 ParamConfig = namedtuple("ParamConfig", "data_set, bits, alphabet_scalar")
@@ -52,6 +52,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=25000, help="calibration samples (the reference's quant_train_size)")
     ap.add_argument("--scalars", type=float, nargs="+", default=[2, 3, 4])
+    ap.add_argument("--radius", choices=["layer", "channel"], default="layer",
+                    help="one alphabet radius per layer (the reference's rule) or one per output channel, for GPFQ and MSQ alike")
     ap.add_argument("--save-dir", default=None, help="save every quantized model there (the reference's serialized_models/)")
     ap.add_argument("--csv", default=None, help="append one metrics row per setting there, the reference's schema and "
                                                 "append semantics (quantize_pretrained_mlp.py:119-153)")
@@ -70,7 +72,7 @@ def main():
         get_data = MNISTSequence(X_train, y_train, batch_size=args.samples)
         my_quant_net = QuantizedNeuralNetwork(network=model, batch_size=args.samples, get_data=get_data,
                                               logger=type("Quiet", (), {"info": staticmethod(lambda m: None)})(),
-                                              bits=params.bits, alphabet_scalar=params.alphabet_scalar)
+                                              bits=params.bits, alphabet_scalar=params.alphabet_scalar, radius=args.radius)
         tic = time()
         my_quant_net.quantize_network()
         quantization_time = time() - tic
@@ -86,8 +88,12 @@ def main():
         for layer_idx, layer in enumerate(model.layers):
             if layer.__class__.__name__ in ("Dense", "Conv2D"):
                 W, b = model.layers[layer_idx].get_weights()
-                rad = params.alphabet_scalar * np.median(np.abs(W.flatten()))
-                MSQ_model.layers[layer_idx].set_weights([msq_quantize(W, rad * my_quant_net.alphabet), b])
+                if args.radius == "channel":
+                    Q = msq_quantize_channels(W, my_quant_net.alphabet, params.alphabet_scalar)
+                else:
+                    rad = params.alphabet_scalar * np.median(np.abs(W.flatten()))
+                    Q = msq_quantize(W, rad * my_quant_net.alphabet)
+                MSQ_model.layers[layer_idx].set_weights([Q, b])
         msq_acc = agreement(MSQ_model, y_test, X_test)
         if args.csv:                                    # one row per setting, header with the first (:138-153)
             import pandas as pd

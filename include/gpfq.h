@@ -358,6 +358,30 @@ int gpfq_assemble_kernel_device(const void *qidx, int bits, const void *dev_alph
                                 float *Q, void *qidx_t, void *stream);
 
 /*
+ * Per-output-channel radius (radius = "channel"; the reference has one radius per layer, :544-545 / :831-832).  An output
+ * channel is a column j of a row-major f32 matrix [R][C]: a Dense kernel [N][C], a Conv2D kernel viewed as [kh*kw*Cin][F], a
+ * DepthwiseConv2D kernel viewed as [kh*kw][Cin*mult].
+ *   radii[j] = float64(alphabet_scalar) * float64(median(|W[:, j]|))   (float32 median with NumPy's semantics, as gpfq_median_abs)
+ * replaced, when it is not a finite positive number, by float64(alphabet_scalar) * float64(*layer_median) (layer_median: a
+ * [device] f32 scalar such as gpfq_median_abs writes; may be NULL), and by 0 when that is not one either.  For the columns
+ * [c_lo, c_hi) it also writes W_scaled[i][j] = float32(float64(W[i][j]) / radii[j]) (0 where radii[j] == 0): the kernel the walk
+ * runs on with the unit alphabet linspace(-1, 1, M); nothing else of W_scaled is written.  One launch, no host synchronisation;
+ * a column never spans workgroups, so the call needs no workspace (gpfq_column_radii_workspace_bytes returns 0; NULL is accepted).
+ *   W [device] f32 [R][ld]; radii [device] f64 [C]; W_scaled [device] f32 [R][ldo] (may be NULL when c_lo == c_hi).
+ *   R = 0: every radius is 0.
+ *
+ * gpfq_assemble_kernel_colrad: Q[t][j] = (float)(radii[j] * unit_alphabet[k]) for the index k of weight t of column j (0.0f for
+ * the literal-zero index -1).  layout GPFQ_LAYOUT_NEURON_MAJOR: qidx [C][N] as gpfq_assemble_kernel takes it (bits 2 / 4 / 8 / 16;
+ * qidx_t [N][C] may be NULL); GPFQ_LAYOUT_KERAS: qidx is already [N][C] (bits 8 / 16), qidx_t is ignored.  Q [device] f32 [N][C].
+ */
+size_t gpfq_column_radii_workspace_bytes(int64_t R, int64_t C);
+int gpfq_column_radii(const float *W, int64_t R, int64_t C, int64_t ld, double alphabet_scalar, const float *layer_median,
+                      double *radii, float *W_scaled, int64_t ldo, int64_t c_lo, int64_t c_hi,
+                      void *workspace, size_t workspace_bytes, void *stream);
+int gpfq_assemble_kernel_colrad(const void *qidx, int bits, int layout, const double *unit_alphabet, int M, const double *radii,
+                                int64_t N, int64_t C, float *Q, void *qidx_t, void *stream);
+
+/*
  * median(|W|) of n float32 weights with NumPy's semantics (float32 result; even n -> float32 mean of
  * the two middle values).  Replaces `median(abs(W.flatten()))` of the alphabet radius
  * (scripts/quantized_network.py:544, :831).  Exact radix select, no sort.

@@ -9,4 +9,5 @@ from quantized_neural_networks_amd.quantized_network import (  # noqa: F401
     SegmentedData,
     _bit_round_parallel,
     msq_quantize,
+    msq_quantize_channels,
 )

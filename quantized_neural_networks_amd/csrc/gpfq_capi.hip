@@ -731,6 +731,55 @@ int gpfq_assemble_kernel(const void *qidx, int bits, const double *alphabet, int
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_assemble_kernel");
 }
 
+size_t gpfq_column_radii_workspace_bytes(int64_t R, int64_t C)
+{
+    (void)R; (void)C;
+    return 0;                                  // a column never spans workgroups: nothing is handed between them
+}
+
+int gpfq_column_radii(const float *W, int64_t R, int64_t C, int64_t ld, double alphabet_scalar, const float *layer_median,
+                      double *radii, float *W_scaled, int64_t ldo, int64_t c_lo, int64_t c_hi,
+                      void *workspace, size_t workspace_bytes, void *stream)
+{
+    (void)workspace; (void)workspace_bytes;
+    if (R < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size R=%lld C=%lld", (long long)R, (long long)C);
+    if (R > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "columns of more than 2^31 - 1 rows");
+    if (!(c_lo >= 0 && c_lo <= c_hi && c_hi <= C))
+        return fail(GPFQ_ERR_INVALID_ARG, "scaled column range [%lld, %lld) outside [0, %lld]", (long long)c_lo, (long long)c_hi, (long long)C);
+    if (C == 0) return GPFQ_OK;
+    if (!radii) return fail(GPFQ_ERR_INVALID_ARG, "radii is NULL");
+    if (R > 0 && !W) return fail(GPFQ_ERR_INVALID_ARG, "W is NULL");
+    if (R > 0 && ld < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ld=%lld < C=%lld", (long long)ld, (long long)C);
+    if (R > 0 && c_hi > c_lo) {
+        if (!W_scaled) return fail(GPFQ_ERR_INVALID_ARG, "W_scaled is NULL with a column range to scale");
+        if (ldo < C) return fail(GPFQ_ERR_INVALID_ARG, "W_scaled pitch ldo=%lld < C=%lld", (long long)ldo, (long long)C);
+    }
+    hipError_t e = gpfq::launch_column_radii(W, R, C, ld, alphabet_scalar, layer_median, radii, c_hi > c_lo ? W_scaled : nullptr, ldo,
+                                             c_lo, c_hi, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_column_radii");
+}
+
+int gpfq_assemble_kernel_colrad(const void *qidx, int bits, int layout, const double *unit_alphabet, int M, const double *radii,
+                                int64_t N, int64_t C, float *Q, void *qidx_t, void *stream)
+{
+    if (N < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size");
+    if (bits != 2 && bits != 4 && bits != 8 && bits != 16) return fail(GPFQ_ERR_INVALID_ARG, "bits must be 2, 4, 8 or 16");
+    if (layout != GPFQ_LAYOUT_NEURON_MAJOR && layout != GPFQ_LAYOUT_KERAS) return fail(GPFQ_ERR_INVALID_ARG, "unknown index layout %d", layout);
+    if (layout == GPFQ_LAYOUT_KERAS && bits < 8) return fail(GPFQ_ERR_INVALID_ARG, "packed indices are neuron-major rows (GPFQ_LAYOUT_NEURON_MAJOR)");
+    HostAlphabet H;
+    int rc = make_alphabet(unit_alphabet, M, -1, &H);
+    if (rc != GPFQ_OK) return rc;
+    if (bits < 8 && M + 1 > (1 << bits)) return fail(GPFQ_ERR_INVALID_ARG, "%d-bit codes cannot hold an alphabet of %d", bits, M);
+    if ((bits == 16) != H.is_big)
+        return fail(GPFQ_ERR_INVALID_ARG, "alphabets of %d members have %s indices (gpfq_index_bits)", M, H.is_big ? "int16" : "int8 or packed");
+    if (N == 0 || C == 0) return GPFQ_OK;
+    if (!qidx || !radii || !Q) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (N > 2147483647LL * 32) return fail(GPFQ_ERR_UNSUPPORTED, "kernel too large to assemble in one call");
+    hipError_t e = gpfq::launch_assemble_colrad(qidx, bits, layout == GPFQ_LAYOUT_KERAS ? 1 : 0, H.A, H.big(), radii, N, C, Q,
+                                                layout == GPFQ_LAYOUT_KERAS ? nullptr : qidx_t, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_assemble_kernel_colrad");
+}
+
 size_t gpfq_median_abs_workspace_bytes(void) { return gpfq::median_workspace_bytes() + 64; }
 size_t gpfq_median_abs_workspace_bytes_for(int64_t n) { return n > 0 ? gpfq::median_workspace_bytes_fast(n) : gpfq::median_workspace_bytes() + 64; }
 

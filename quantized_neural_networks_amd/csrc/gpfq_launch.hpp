@@ -282,6 +282,12 @@ hipError_t launch_assemble(const int8_t *qidx, const AlphabetArg &A, int64_t N, 
                            hipStream_t stream, const AlphabetBig *big = nullptr, const DevAlphabet *dev = nullptr);
 // dev != NULL: the members are read from a DevAlphabet in device memory (A: its size only)
 hipError_t launch_pack(const int8_t *qidx, int64_t N, int64_t C, int bits, uint8_t *packed, hipStream_t stream);
+// gpfq_colrad.hip (radius = "channel"): per-column radii of a row-major [R][C] matrix (+ W' for columns [c_lo, c_hi)), and
+// Q[t][j] = float32(radii[j] * unit[k]) from neuron-major (keras_layout = 0) or Keras-layout (1) indices
+hipError_t launch_column_radii(const float *W, int64_t R, int64_t C, int64_t ld, double alphabet_scalar, const float *layer_median,
+                               double *radii, float *Wp, int64_t ldo, int64_t c_lo, int64_t c_hi, hipStream_t stream);
+hipError_t launch_assemble_colrad(const void *qidx, int bits, int keras_layout, const AlphabetArg &A, const AlphabetBig *big,
+                                  const double *radii, int64_t N, int64_t C, float *Q, void *idxT, hipStream_t stream);
 size_t median_workspace_bytes();
 size_t median_workspace_bytes_fast(int64_t n);   // ... with room for the one-GPU form's candidate list (gpfq_median_abs_workspace_bytes_for)
 size_t channel_sumsq_workspace_bytes(int64_t Cin);

@@ -49,6 +49,9 @@ SYMBOLS = {
     "gpfq_dense_layer_run": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _dp, _int, _i64, _i64,
                                     _vp, _vp, _int, _i64, _vp, _vp, _sz, _vp]),
     "gpfq_assemble_kernel_device": (_int, [_vp, _int, _vp, _int, _i64, _i64, _vp, _vp, _vp]),
+    "gpfq_column_radii_workspace_bytes": (_sz, [_i64, _i64]),
+    "gpfq_column_radii": (_int, [_vp, _i64, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
+    "gpfq_assemble_kernel_colrad": (_int, [_vp, _int, _int, _dp, _int, _vp, _i64, _i64, _vp, _vp, _vp]),
     "gpfq_gram_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "gpfq_quantize_neurons_gram": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _i64, _dp, _int, _int, _i64, _i64, _i64,
                                           _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -757,6 +760,66 @@ def assemble_kernel_device(qidx, dalpha, want_idx=True, bits=8, N=None):
                                                   idx_t.data_ptr() if idx_t is not None else None, _stream()),
                "gpfq_assemble_kernel_device")
     return Q, idx_t
+
+
+def column_radii(W2d, alphabet_scalar, layer_median=None, scale=None):
+    """Per-output-channel radii of a row-major f32 [R][C'] matrix (gpfq_column_radii): r f64 [C'], r[j] = float64(alphabet_scalar) *
+    float64(median(|W2d[:, j]|)), a radius that is not finite and positive replaced by alphabet_scalar * layer_median (f32 device scalar
+    [1], e.g. median_abs(..., on_device=True); None: no fallback) and then by 0.  scale=(lo, hi): also W' f32 [R][C'] with columns
+    lo..hi = float32(float64(W2d) / r) (the rest of it unwritten), else None.  Returns (r, W').  One launch, no sync."""
+    _dev(W2d, torch.float32, "W2d")
+    if W2d.dim() != 2:
+        raise GpfqError("column_radii needs a 2-D [R][C'] matrix")
+    Wc = W2d.contiguous()
+    R, C = Wc.shape
+    lo, hi = (0, 0) if scale is None else (int(scale[0]), int(scale[1]))
+    if layer_median is not None:
+        _dev(layer_median, torch.float32, "layer_median")
+    dev = W2d.device
+    r = torch.empty(C, dtype=torch.float64, device=dev)
+    Wp = torch.empty((R, C), dtype=torch.float32, device=dev) if scale is not None else None
+    lib = load()
+    nbytes = lib.gpfq_column_radii_workspace_bytes(R, C)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        _check(lib.gpfq_column_radii(Wc.data_ptr(), R, C, max(C, 1), float(alphabet_scalar),
+                                     layer_median.data_ptr() if layer_median is not None else None, r.data_ptr(),
+                                     Wp.data_ptr() if Wp is not None else None, max(C, 1), lo, hi,
+                                     ws.data_ptr() if ws is not None else None, nbytes, _stream()), "gpfq_column_radii")
+    return r, Wp
+
+
+def assemble_kernel_colrad(qidx, unit_alphabet, radii, bits=None, N=None, layout=GPFQ_LAYOUT_NEURON_MAJOR, want_idx=True):
+    """Q[t][j] = float32(radii[j] * unit_alphabet[k]) of the index k of weight t of column j (gpfq_assemble_kernel_colrad).
+    layout GPFQ_LAYOUT_NEURON_MAJOR: qidx [C][N] int8 / int16, or rows packed by pack_indices (bits = 2 / 4, pass N) -> (Q f32 [N][C],
+    idx [N][C]); GPFQ_LAYOUT_KERAS: qidx is already [N][C] -> (Q f32 [N][C], qidx).  No sync."""
+    M = len(unit_alphabet)
+    if bits is None:
+        bits = 16 if M > 64 else 8
+    _dev(qidx, torch.int16 if bits == 16 else torch.int8 if bits == 8 else torch.uint8, "qidx")
+    _dev(radii, torch.float64, "radii")
+    if qidx.dim() != 2 or not qidx.is_contiguous():
+        raise GpfqError("qidx must be a contiguous 2-D tensor")
+    if layout == GPFQ_LAYOUT_KERAS:
+        N, C = qidx.shape
+    else:
+        C = qidx.shape[0]
+        if bits >= 8:
+            N = qidx.shape[1]
+        elif N is None or qidx.shape[1] != (N * bits + 7) // 8:
+            raise GpfqError("packed indices need N, with ceil(N*bits/8) bytes per row")
+    if radii.numel() != C or not radii.is_contiguous():
+        raise GpfqError(f"radii must be a contiguous [{C}] tensor")
+    arr, M, _ = _alphabet(unit_alphabet)
+    Q = torch.empty((N, C), dtype=torch.float32, device=qidx.device)
+    idx_t = None
+    if layout != GPFQ_LAYOUT_KERAS and want_idx:
+        idx_t = torch.empty((N, C), dtype=index_dtype(M), device=qidx.device)
+    with torch.cuda.device(qidx.device):
+        _check(load().gpfq_assemble_kernel_colrad(qidx.data_ptr(), bits, layout, arr, M, radii.data_ptr(), N, C, Q.data_ptr(),
+                                                  idx_t.data_ptr() if idx_t is not None else None, _stream()),
+               "gpfq_assemble_kernel_colrad")
+    return Q, (qidx if layout == GPFQ_LAYOUT_KERAS else idx_t)
 
 
 def last_dense_kernel():

@@ -520,3 +520,96 @@ def quantize_conv2d(W, act_w, act_q, alphabet, strides, padding, rate, group=Non
     Q = Qc.reshape(Cin, F, kh, kw).permute(2, 3, 0, 1).contiguous()
     idx = Ic.reshape(Cin, F, kh, kw).permute(2, 3, 0, 1).contiguous()
     return dict(Q=Q, idx=idx, resid=Rc.contiguous(), reruns=torch.tensor(reruns))
+
+
+# ------------------------------------------------------------------------------------------
+# radius = "channel": one alphabet radius per output channel
+# ------------------------------------------------------------------------------------------
+_unit_alphabets = {}
+
+
+def _unit_alphabet_device(unit, device):
+    """DeviceAlphabet of radius exactly 1 (1.0 * float64(1.0f)) over the unit alphabet, one per device and alphabet: what the
+    block-pipelined kernel reads when it walks a scaled kernel W'.  Known good on the host, so no deferred alphabet status is waited for."""
+    key = (device.index, tuple(float(v) for v in unit))
+    d = _unit_alphabets.get(key)
+    if d is None:
+        one = torch.ones(1, dtype=torch.float32, device=device)
+        d = hip.layer_alphabet_device(one, unit, 1.0)
+        d._rad = np.float64(1.0)
+        d.radius_ok = hip.device_alphabet_ok(np.float32(1.0), unit, 1.0)
+        _unit_alphabets[key] = d
+    return d
+
+
+def _channel_radii(W2d, alphabet_scalar, scale):
+    """(layer median f32 device scalar or None, radii f64 [C'], W') of a row-major [R][C'] view of a kernel: two launches, no sync."""
+    med = hip.median_abs(W2d.reshape(-1), on_device=True) if W2d.numel() else None
+    r, Wp = hip.column_radii(W2d, alphabet_scalar, layer_median=med, scale=scale)
+    return med, r, Wp
+
+
+def quantize_dense_channels(W, X, Xq, unit_alphabet, alphabet_scalar, group=None, overlap=False, kernel_ready=None, want_resid=True,
+                            log=None, check=True):
+    """quantize_dense with one radius per neuron (radius="channel"): r_j = alphabet_scalar * median(|W[:, j]|) (the layer radius
+    where that is not a finite positive number, then 0), the walk run by quantize_dense -- every kernel, fallback and repair as there --
+    on W' = float32(W / r_j) with the unit alphabet (a device alphabet of radius 1 up to 64 members), and
+    Q = float32(r_j * unit[idx]), resid_j = r_j * the walk's residual norm.
+
+    Sharded (group): every rank computes all radii itself (deterministic, no collective) and scales only its own neurons; the one
+    all-gather still carries packed indices only.  overlap=True: the median and the radii / W' launch go to a side stream beside the row
+    norms and the record pre-pass (kernel_ready as for quantize_dense_layer).
+
+    Returns quantize_dense's dict with Q, resid as above + "radii" (f64 [C]) and "layer_median" (f32 device scalar)."""
+    N, C = W.shape
+    world, rank = _group_info(group)
+    lo, hi = shard_bounds(C, world, rank)
+    m = X.shape[1]
+    unit = np.asarray(unit_alphabet, dtype=np.float64)
+    Wc = W.detach().contiguous()
+    dalpha = _unit_alphabet_device(unit, W.device) if len(unit) <= 64 else None
+    alphabet = dalpha if dalpha is not None else unit
+    if not (overlap and dalpha is not None and Wc.numel() and m > 0 and hi > lo and hip.dense_layer_supported(N, m, hi - lo, unit)):
+        med, r, Wp = _channel_radii(Wc, alphabet_scalar, (lo, hi))
+        out = quantize_dense(Wp, X, Xq, alphabet, group=group, want_resid=want_resid, log=log, check=check)
+    else:
+        main = torch.cuda.current_stream(W.device)
+        side = _side_stream(W.device)
+        if kernel_ready is None:
+            side.wait_stream(main)
+        elif kernel_ready is not True:
+            side.wait_event(kernel_ready)
+        with torch.cuda.stream(side):
+            med, r, Wp = _channel_radii(Wc, alphabet_scalar, (lo, hi))
+        Wc.record_stream(side)                                    # (the allocator's bookkeeping, as in quantize_dense_layer)
+        for t in (med, r, Wp):
+            t.record_stream(main)
+        ws = hip.dense_layer_workspace(N, m, hi - lo, W.device)
+        hip.dense_layer_prepare(X, Xq, unit, hi - lo, ws)
+        main.wait_stream(side)
+        out = quantize_dense(Wp, X, Xq, dalpha, group=group, want_resid=want_resid, log=log, check=check, prepared=ws)
+    out["Q"], _ = hip.assemble_kernel_colrad(out["idx"], unit, r, layout=hip.GPFQ_LAYOUT_KERAS)
+    if "resid" in out:
+        out["resid"] = out["resid"] * r
+    out["radii"], out["layer_median"] = r, med
+    return out
+
+
+def quantize_conv2d_channels(W, act_w, act_q, unit_alphabet, alphabet_scalar, strides, padding, rate, group=None, want_resid=True,
+                             depthwise=False):
+    """quantize_conv2d with one radius per output channel (radius="channel"): filter f of a Conv2D kernel -- column f of the view
+    [kh*kw*Cin][F] -- or output channel (c, d) of a DepthwiseConv2D kernel -- column c*mult + d of [kh*kw][Cin*mult].  The
+    (channel, filter) pairs walk on W' = float32(W / r) with the unit alphabet through quantize_conv2d (its reruns and sharding
+    included); Q = float32(r * unit[idx]), resid scaled by the pair's radius.  Every rank computes all radii itself.
+    Returns quantize_conv2d's dict + "radii" (f64 [F] or [Cin*mult]) and "layer_median"."""
+    kh, kw, Cin, F = W.shape
+    unit = np.asarray(unit_alphabet, dtype=np.float64)
+    Wc = W.detach().contiguous()
+    W2 = Wc.reshape(kh * kw, Cin * F) if depthwise else Wc.reshape(kh * kw * Cin, F)
+    med, r, Wp = _channel_radii(W2, alphabet_scalar, (0, W2.shape[1]))
+    out = quantize_conv2d(Wp.reshape(kh, kw, Cin, F), act_w, act_q, unit, strides, padding, rate, group=group, want_resid=want_resid)
+    Q, _ = hip.assemble_kernel_colrad(out["idx"].reshape(W2.shape), unit, r, layout=hip.GPFQ_LAYOUT_KERAS)
+    out["Q"] = Q.reshape(kh, kw, Cin, F)
+    out["resid"] = out["resid"] * (r.reshape(Cin, F) if depthwise else r.reshape(1, F))
+    out["radii"], out["layer_median"] = r, med
+    return out

@@ -15,7 +15,9 @@ The network object is only touched through the Keras attribute set of SURVEY A.4
 Extra keyword-only constructor arguments (not in the reference): ``device`` (torch device of this
 process' GPU) and ``process_group`` (a ``torch.distributed`` group over which the neurons of every
 layer -- and the samples of the activation capture in between -- are sharded), and ``fix_partial_batch`` to opt out of the reference's
-partial-last-batch layout quirk (:491-495).
+partial-last-batch layout quirk (:491-495).  ``radius="channel"`` gives every output channel (Dense neuron, conv filter, depthwise
+output channel) an alphabet radius of its own instead of the reference's one per layer; the default
+``radius="layer"`` is the reference's rule.
 """
 import logging
 from collections import namedtuple
@@ -54,6 +56,21 @@ def msq_quantize(W, alphabet, device=None):
     Wd = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float32)).to(dev)
     Q, _ = hip.msq_round(Wd, np.asarray(alphabet, dtype=np.float64))
     return Q.cpu().numpy()
+
+
+def msq_quantize_channels(W, unit_alphabet, alphabet_scalar, device=None, depthwise=False):
+    """The MSQ baseline with one radius per output channel (radius="channel"): the nearest unit member of W' = float32(W / r_j),
+    assembled as float32(r_j * unit[idx]).  Output channels are the columns of W viewed as [-1][W.shape[-1]] (Dense, Conv2D) or,
+    with depthwise=True, as [kh*kw][Cin*mult]; r_j as layer.quantize_dense_channels forms them.  Returns Q (float32, W's shape)."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    W2 = W.reshape(W.shape[0] * W.shape[1], -1) if (depthwise and W.ndim == 4) else W.reshape(-1, W.shape[-1])
+    Wd = torch.from_numpy(np.ascontiguousarray(W2)).to(dev)
+    unit = np.asarray(unit_alphabet, dtype=np.float64)
+    _, r, Wp = _layer._channel_radii(Wd, alphabet_scalar, (0, Wd.shape[1]))
+    _, idx = hip.msq_round(Wp, unit)
+    Q, _ = hip.assemble_kernel_colrad(idx, unit, r, layout=hip.GPFQ_LAYOUT_KERAS)
+    return Q.cpu().numpy().reshape(W.shape)
 
 
 # ------------------------------------------------------------------------------------------
@@ -105,6 +122,22 @@ class ImageNetSequence(_SliceSequence):
 
 
 # ------------------------------------------------------------------------------------------
+def _check_radius(radius):
+    if radius not in ("layer", "channel"):
+        raise ValueError(f"radius must be 'layer' (one alphabet radius per layer, the reference's rule) or 'channel' (one per output "
+                         f"channel), got {radius!r}")
+    return radius
+
+
+def _channel_stats(out, alphabet, alphabet_scalar, **extra):
+    """last_layer_stats of a radius="channel" layer: rad = the radii (f64 [channels]), layer_rad = alphabet_scalar * median(|W|), both
+    left on the device until read; alphabet = the unit alphabet the walk used."""
+    med = out["layer_median"]
+    layer_rad = (med.reshape(()).double() * float(alphabet_scalar) if med is not None else np.float64(np.nan))
+    return _LazyStats(rad=out["radii"], layer_rad=layer_rad, alphabet=np.asarray(alphabet, dtype=np.float64), resid=out["resid"],
+                      idx=out["idx"], **extra)
+
+
 class _LazyStats(dict):
     """last_layer_stats[layer]: rad, alphabet, resid, idx (, reruns).  The index tensor and the residual norms stay on the GPU until
     someone reads them (they are diagnostics: 103 MB of indices for VGG16's fc1 crossed PCIe after every layer until round 3);
@@ -114,6 +147,8 @@ class _LazyStats(dict):
         v = dict.__getitem__(self, key)
         if isinstance(v, torch.Tensor):
             v = v.detach().cpu().numpy()
+            if v.ndim == 0:
+                v = v[()]                                  # (a scalar -- layer_rad of radius="channel" -- reads as a NumPy scalar)
             dict.__setitem__(self, key, v)
         return v
 
@@ -148,9 +183,10 @@ class QuantizedNeuralNetwork:
     """Wrapper around a Keras-style model that quantizes its Dense layers (reference :331-590)."""
 
     def __init__(self, network, batch_size, get_data, mini_batch_size=32, logger=None, ignore_layers=[],
-                 bits=np.log2(3), alphabet_scalar=1, *, device=None, process_group=None, fix_partial_batch=False):
+                 bits=np.log2(3), alphabet_scalar=1, *, device=None, process_group=None, fix_partial_batch=False, radius="layer"):
         # batch_size and mini_batch_size are accepted and ignored, as in the reference (:371-400):
         # the sample count comes from get_data alone.
+        self.radius = _check_radius(radius)
         self.get_data = get_data
         self.trained_net = network
         self.quantized_net = clone_model(network)
@@ -619,6 +655,9 @@ class QuantizedNeuralNetwork:
         wX, qX = self._get_layer_data_generator(layer_idx, transpose=True)
         self._log(f"\tdone. {time()-tic:2f} seconds.")
 
+        if self.radius == "channel":
+            self._quantize_layer_channels(layer_idx, Wd, wX, qX)
+            return
         layer_alphabet, rad = self._layer_alphabet(Wd, layer_idx)
         dalpha = self._layer_alphabet_device(layer_idx, rad)
 
@@ -639,6 +678,23 @@ class QuantizedNeuralNetwork:
         self._log(f"\tdone. {time()-tic:.2f} seconds.")
         self.last_layer_stats[layer_idx] = _LazyStats(rad=rad, alphabet=layer_alphabet, resid=out["resid"], idx=out["idx"])
 
+    def _quantize_layer_channels(self, layer_idx, Wd, wX, qX):
+        """radius="channel": the radii, the scaled kernel and the walk all queued on the device (layer.quantize_dense_channels); no
+        host wait for the radii."""
+        N_ell_plus_1 = Wd.shape[1]
+        self._log("\tQuantizing neurons (in parallel)...")
+        tic = time()
+        try:
+            out = _layer.quantize_dense_channels(Wd, wX, qX, self.alphabet, self.alphabet_scalar, group=self.process_group, want_resid=None,
+                                                 log=lambda msg: self._log(f"\t\tLayer {layer_idx}: {msg}"))
+        except Exception as exc:
+            self._log(f"\t\tLayer {layer_idx} generated an exception: {exc}")
+            raise exc
+        self._log_units("\t\tNeuron {} of " + f"{N_ell_plus_1} quantized successfully.", N_ell_plus_1)
+        self._update_weights(layer_idx, out["Q"])
+        self._log(f"\tdone. {time()-tic:.2f} seconds.")
+        self.last_layer_stats[layer_idx] = _channel_stats(out, self.alphabet, self.alphabet_scalar)
+
     # The reference logs one record per neuron / filter as its futures complete (:567, :716).  Here all of a layer's units complete
     # together; the records still go out ONE PER UNIT (handlers and formatters that count or prefix records see what they saw), unless
     # the logger has INFO disabled (then nothing is formatted at all: 4096 logger calls cost about as much as the kernel that
@@ -658,8 +714,9 @@ class QuantizedNeuralNetwork:
     def quantize_network(self):
         """Quantizes all Dense layers that are not in ``ignore_layers``, in order (:576-590)."""
         num_layers = len(self.trained_net.layers)
-        self._prefetch_medians([k for k, layer in enumerate(self.trained_net.layers)
-                                if layer.__class__.__name__ == "Dense" and k not in self.ignore_layers])
+        if self.radius == "layer":
+            self._prefetch_medians([k for k, layer in enumerate(self.trained_net.layers)
+                                    if layer.__class__.__name__ == "Dense" and k not in self.ignore_layers])
         for layer_idx, layer in enumerate(self.trained_net.layers):
             if layer.__class__.__name__ == "Dense" and layer_idx not in self.ignore_layers:
                 tic = time()
@@ -674,7 +731,8 @@ class QuantizedCNN(QuantizedNeuralNetwork):
 
     def __init__(self, network, batch_size, get_data, mini_batch_size=32, logger=None, bits=np.log2(3),
                  alphabet_scalar=1, patch_mini_batch_size=5000, is_quantize_conv2d=True, *,
-                 device=None, process_group=None, fix_partial_batch=False):
+                 device=None, process_group=None, fix_partial_batch=False, radius="layer"):
+        self.radius = _check_radius(radius)
         self.get_data = get_data
         self.trained_net = network
         self.quantized_net = clone_model(network)
@@ -709,29 +767,38 @@ class QuantizedCNN(QuantizedNeuralNetwork):
         except Exception:
             rate = None
         Wd = self._kernel_on_device(layer)
-        alphabet, rad = self._layer_alphabet(Wd, layer_idx)                        # (:831-832)
+        channels = self.radius == "channel"
+        if not channels:
+            alphabet, rad = self._layer_alphabet(Wd, layer_idx)                    # (:831-832)
         num_channels = Wd.shape[-2]
         tic = time()
         self._log(f"\t\tBuilding patch arrays and quantizing channel filters for {num_channels} channels...")
         try:
-            out = _layer.quantize_conv2d(Wd, wX, qX, alphabet, strides=tuple(layer.strides),
-                                         padding=layer.padding.upper(), rate=tuple(rate) if rate else None,
-                                         group=self.process_group,
-                                         want_resid=False)      # residual norms are diagnostics: skip their replay
+            conv = dict(strides=tuple(layer.strides), padding=layer.padding.upper(), rate=tuple(rate) if rate else None,
+                        group=self.process_group, want_resid=False)      # residual norms are diagnostics: skip their replay
+            if channels:
+                out = _layer.quantize_conv2d_channels(Wd, wX, qX, self.alphabet, self.alphabet_scalar,
+                                                      depthwise=layer.__class__.__name__ == "DepthwiseConv2D", **conv)
+            else:
+                out = _layer.quantize_conv2d(Wd, wX, qX, alphabet, **conv)
             Q = out["Q"]
         except Exception as exc:
             self._log(f"\t\t\tLayer {layer_idx} generated an exception: {exc}")
             raise Exception
         self._log(f"\t\tdone. {time()-tic:.2f} seconds.")
         self._update_weights(layer_idx, Q)
+        if channels:
+            self.last_layer_stats[layer_idx] = _channel_stats(out, self.alphabet, self.alphabet_scalar, reruns=int(out.get("reruns", 0)))
+            return
         self.last_layer_stats[layer_idx] = _LazyStats(rad=rad, alphabet=alphabet, resid=out["resid"], idx=out["idx"],
                                                       reruns=int(out.get("reruns", 0)))
 
     def quantize_network(self):
         num_layers = len(self.trained_net.layers)
-        self._prefetch_medians([k for k, layer in enumerate(self.trained_net.layers)
-                                if layer.__class__.__name__ == "Dense"
-                                or (layer.__class__.__name__ in {"Conv2D", "DepthwiseConv2D"} and self.is_quantize_conv2d)])
+        if self.radius == "layer":
+            self._prefetch_medians([k for k, layer in enumerate(self.trained_net.layers)
+                                    if layer.__class__.__name__ == "Dense"
+                                    or (layer.__class__.__name__ in {"Conv2D", "DepthwiseConv2D"} and self.is_quantize_conv2d)])
         for layer_idx, layer in enumerate(self.trained_net.layers):
             if layer.__class__.__name__ == "Dense":
                 self._log(f"Quantizing (Dense) layer {layer_idx} of {num_layers}...")
