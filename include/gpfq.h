@@ -113,80 +113,95 @@ int gpfq_set_main_kernel_events(void *start_event, void *stop_event);
 /*
  * Process-wide tuning/test hooks; results never depend on them, only which kernel family runs.  Each option is one atomic
  * integer: a call running on another thread sees the old or the new value of each, never a torn one -- the calls stay
- * re-entrant per stream whatever is set while they run.
- *   "onchip_mode"  1 (default) certified-prediction mode, 0 verbatim reference flow
- *   "tile_steps"   LDS tile height in steps (power of two <= 64), 0 = heuristic
- *   "group_waves"  neurons (wavefronts) per workgroup 1..16 of the wave-per-neuron kernel, 0 = heuristic
- *   "lanes_per_neuron"  0 = heuristic, 16/32/64 = row-group kernel with that many lanes per neuron,
- *                  1 = wave-per-neuron kernel
- *   "variant"      bit 0: row-group kernel without the float64 copy of Xq in LDS; bit 1: wide kernel with
+ * re-entrant per stream whatever is set while they run.  Every exported function reads the options ONCE, at its top: its support
+ * check, its workspace size and its launches agree with each other whatever is set meanwhile (gpfq_dense_layer_prepare and
+ * gpfq_dense_layer_run are two calls and read them twice: keep the options still between the two).
+ * A value outside an option's set is rejected with GPFQ_ERR_INVALID_ARG (the message names the key and the set) where the line says
+ * "else rejected"; the other options map whatever they are given onto their set as the line says.  The options, in the order of the
+ * library's table (csrc/gpfq_options.hpp):
+ *   "onchip_mode"  default 1: certified-prediction mode; 0 verbatim reference flow (any other value: 1)
+ *   "tile_steps"   default 0 = heuristic; LDS tile height in steps, a power of two <= 64 (else rejected)
+ *   "group_waves"  default 0 = heuristic; neurons (wavefronts) per workgroup 1..16 of the wave-per-neuron kernel (else rejected)
+ *   "lanes_per_neuron"  default 0 = heuristic; 16/32/64 = row-group kernel with that many lanes per neuron,
+ *                  1 = wave-per-neuron kernel (else rejected)
+ *   "waves_per_neuron"  default 0 = heuristic (rows longer than 2048 samples, and layers too narrow to fill the chip);
+ *                  2..16: force the wide kernel (one neuron over that many wavefronts); outside 0..16 rejected
+ *   "variant"      default 0; stored as given.  bit 0: row-group kernel without the float64 copy of Xq in LDS; bit 1: wide kernel with
  *                  LDS-staged rows instead of register prefetch; bit 2: Gram records of walks longer than 64
  *                  steps on the vector units instead of the matrix cores (v_mfma_f64_16x16x4_f64);
- *                  bit 4: pipelined kernel issues its LDS-DMA spread over the steps of a tile
- *   "pipe"         role-split dense kernels (alphabets <= 64): -1 (default) the block form (gpfq_blk.hip; rows of 257..28672
+ *                  bit 4: pipelined kernel issues its LDS-DMA spread over the steps of a tile; bit 5: the block form keeps the general
+ *                  form for symmetric alphabets
+ *   "pipe"         default -1; role-split dense kernels (alphabets <= 64): -1 the block form (gpfq_blk.hip; rows of 257..28672
  *                  samples) where measured faster -- layers of 512+ neurons, and any width for rows of 769+ samples --,
  *                  0 never, 1 one step per slot (gpfq_pipe.hip, rows up to 2048) whenever it applies, 2 the block form
- *                  whenever it applies
- *   "blk_sweep_waves"   0 (default: by shape -- eleven for rows of 769..1024 samples, eight for shorter rows), 8 or 11: sweep
- *                  wavefronts per workgroup of the block form's 16-neuron four-step shapes (with the decision wavefront two or
- *                  three wavefronts per SIMD; same bits: DESIGN.md)
- *   "blk_quad_waves"    0 (default: by shape), 7 or 8: sweep wavefronts per workgroup of the four-group narrow shapes on rows of at most
- *                  768 samples (seven = two wavefronts per SIMD with the decision wavefront; the default for layers of at most 1024 neurons)
- *   "blk_quad_groups"   2 (default): layers of at most 2048 neurons on rows of 257..1024 samples take four neuron groups per sweep
- *                  wavefront with one or two neurons per lane (4 / 8 neurons per workgroup, dot products on the matrix unit);
- *                  1: only layers of 129..2048 neurons; 0: the one- / two-group shapes of round 3
- *   "blk_cluster"       the block form's CLUSTER FORM (a row cut into 1024-sample slices, one workgroup each, partial dot products exchanged
- *                  once per slot; rows of up to GPFQ_ONCHIP_MAX_M samples): 1 (default) by shape -- every row beyond 3072 samples, rows of 1537..3072
- *                  samples in layers that are one round of the chip --, 0 off (rows beyond 5120 samples then take the wide kernel), a row
- *                  length >= 1024: every row beyond it (tests)
- *   "blk_cluster_nl"    that form's neurons per workgroup: 0 (default) 8 where the layer is then one round, else 16; 1 / 2 / 4 force 4 / 8 / 16
- *   "blk_cluster_map"   its workgroup id -> (cluster, slice) map: 0 a cluster's slices side by side in one XCD's queue, 1 consecutive ids
- *                  (the slices go round the XCDs), -1 (default) = 1: the chip holds 256 / slices whole clusters per round under map 1 and
- *                  8 x (32 / slices) under map 0, never more (and where the slice count divides 8 an XCD streams one slice's records
- *                  instead of all of them); map 0 only when forced (tests, A/B); same bits
- *   "blk_four_groups"   1 (default): layers of at most 1024 neurons on rows of 769..2048 samples take 4 neurons per workgroup; 0: 8
- *   "blk_wide_groups"   1 (default): rows of 1025..2048 samples in layers of more than 2048 neurons take 16 neurons per workgroup
- *                  (eleven sweep wavefronts, one round of workgroups); 0: 8 neurons per workgroup as narrower layers do
- *   "waves_per_neuron"  2..16: force the wide kernel (one neuron over that many wavefronts), 0 = heuristic
- *                  (rows longer than 2048 samples, and layers too narrow to fill the chip)
- *   "gram_slack_log2"   Gram paths: error bounds multiplied by 2^value (tests force the repair/rerun branches)
- *   "conv_s2"      1 (default): 7x7 / stride 2 / VALID conv layers form their Gram records from shift sums of the parity classes of the
- *                  channel planes (gpfq_gram_s2.hip); 0: the matrix-core kernel
- *   "auto_gram"    1 (default): GPFQ_PATH_AUTO may divert long rows to the Gram path (one stream synchronisation inside the call);
+ *                  whenever it applies (else rejected)
+ *   "auto_gram"    default 1: GPFQ_PATH_AUTO may divert long rows to the Gram path (one stream synchronisation inside the call);
  *                  0: AUTO only picks between the asynchronous on-chip and streaming kernels
- *   "conv_fused"   1 (default): conv layers read their patch rows from the channel planes; 0: per-channel patch matrices
- *   "conv_nhwc"    1 (default): 3x3 / stride 1 / SAME layers read the NHWC activations directly (shards of 32+ channels, and of 8 to 31 where 2, 4 or 8 divides the image count: see "conv_nhwc_halves")
- *                  (gpfq_quantize_conv3x3_nhwc); 0: channel planes first
- *   "conv_nhwc_slots"   that form's workgroups per launch (default 8192: many short one-wavefront workgroups balance themselves)
- *   "conv_nhwc_halves"  1 (default): in shards of at most 32 / 16 / 8 channels the lanes the shard leaves idle walk further
- *                  halves / quarters / eighths of the images (where that count divides the number of images); 0: they idle
- *   "conv_planes_free"  1 (default): 7x7 / stride 2 / VALID layers read the NHWC activations themselves
- *                  (gpfq_quantize_conv_channels_nhwc); 0: channel planes first
- *   "blk_pair_groups", "blk_single_groups"  1 (default): the block form takes two neurons per workgroup in layers of at most 512
- *                  neurons, one in layers of at most 128; 0: four / two
- *   "conv_strip"   plane-correlation kernel: output positions per lane (0 = heuristic, 1, 2 or 4)
- *   "conv_shift"   1 (default): 3x3 / stride 1 / SAME layers on images of 20 x 20 or more (shards of 8+ channels) accumulate shift sums (27 FMAs per
- *                  position, border classes apart); 0: the per-output-position records (99 FMAs) that VALID layers and small
- *                  images use; 2: the shift form for every image of 4 x 4 or more (tests)
- */
-int gpfq_set_option(const char *key, int value);
-/* Round 6 additions to the option list above:
- *   "blk_prep_run"  1 (default): the block kernel's record pre-pass takes runs of 4 .. 16 records per workgroup (each row read about four
+ *   "gram_slack_log2"   default 0; stored as given.  Gram paths: error bounds multiplied by 2^value (tests force the repair/rerun branches)
+ *   "sync_errors"  default 0: asynchronous, the caller checks gpfq_call_status itself; 1: gpfq_quantize_neurons (block-pipelined
+ *                  kernel) and gpfq_quantize_dense_layer wait for their launches and return gpfq_call_status() of the call
+ *   "blk_single_groups"  default 1: the block form takes one neuron per workgroup in layers of at most 128 neurons (needs
+ *                  the pair option below too); 0: two
+ *   "blk_pair_groups"    default 1: the block form takes two neurons per workgroup in layers of at most 512 neurons; 0: four
+ *   "blk_four_groups"   default 1: layers of at most 1024 neurons on rows of 769..2048 samples take 4 neurons per workgroup; 0: 8
+ *   "blk_wide_groups"   default 1: rows of 1025..2048 samples in layers of more than 2048 neurons take 16 neurons per workgroup
+ *                  (eleven sweep wavefronts, one round of workgroups); 0: 8 neurons per workgroup as narrower layers do
+ *   "blk_quad_groups"   default 2: layers of at most 2048 neurons on rows of 257..1024 samples take four neuron groups per sweep
+ *                  wavefront with one or two neurons per lane (4 / 8 neurons per workgroup, dot products on the matrix unit);
+ *                  1: only layers of 129..2048 neurons; 0: the one- / two-group shapes of round 3 (other values: clamped to 0..2)
+ *   "blk_quad_waves"    default 0 = by shape; 7 or 8: sweep wavefronts per workgroup of the four-group narrow shapes on rows of at most
+ *                  768 samples (seven = two wavefronts per SIMD with the decision wavefront; the default for layers of at most 1024
+ *                  neurons); else rejected
+ *   "blk_sweep_waves"   default 0 = by shape -- eleven for rows of 769..1024 samples, eight for shorter rows; 8 or 11: sweep
+ *                  wavefronts per workgroup of the block form's 16-neuron four-step shapes (with the decision wavefront two or
+ *                  three wavefronts per SIMD; same bits: DESIGN.md); else rejected
+ *   "blk_prep_run"  default 1: the block kernel's record pre-pass takes runs of 4 .. 16 records per workgroup (each row read about four
  *                  times instead of eighteen) for walks of 2048+ steps, the run length by the number of records; 0: one record per
- *                  workgroup (the same records); 4 .. 16: runs of that many records whatever the walk's length (tests, A/B)
- *   "blk_prep_norms"  1 (default): gpfq_quantize_dense_layer / _prepare called without the caller's row norms form them INSIDE the record
+ *                  workgroup (the same records); 4 .. 16: runs of that many records whatever the walk's length (tests, A/B); any
+ *                  other value: 1
+ *   "blk_prep_norms"  default 1: gpfq_quantize_dense_layer / _prepare called without the caller's row norms form them INSIDE the record
  *                  pre-pass where that reproduces gpfq_row_norms' sums bit for bit (runs of records, rows of 769 .. 1024 samples,
  *                  m a multiple of four) -- one launch less; 0: always by the row-norm kernel in front of the pre-pass (tests, A/B)
- *   "blk_cluster768"  -1 (default): rows of 2049..3072 samples in layers wider than 2048 neurons run as FOUR 768-sample slices of the cluster
+ *   "blk_cluster"       default 1; the block form's CLUSTER FORM (a row cut into 1024-sample slices, one workgroup each, partial dot products
+ *                  exchanged once per slot; rows of up to GPFQ_ONCHIP_MAX_M samples): 1 by shape -- every row beyond 3072 samples, rows of
+ *                  1537..3072 samples in layers that are one round of the chip --, 0 off (rows beyond 5120 samples then take the wide
+ *                  kernel), a row length >= 1024: every row beyond it (tests); else rejected
+ *   "blk_cluster_nl"    default 0: that form's neurons per workgroup 8 where the layer is then one round, else 16; 1 / 2 / 4 force
+ *                  4 / 8 / 16 (any other value: 0)
+ *   "blk_cluster_map"   default -1; its workgroup id -> (cluster, slice) map: 0 a cluster's slices side by side in one XCD's queue,
+ *                  1 consecutive ids (the slices go round the XCDs), -1 (any negative value) = 1: the chip holds 256 / slices whole
+ *                  clusters per round under map 1 and 8 x (32 / slices) under map 0, never more (and where the slice count divides 8
+ *                  an XCD streams one slice's records instead of all of them); map 0 only when forced (tests, A/B); same bits
+ *   "blk_cluster768"  default -1: rows of 2049..3072 samples in layers wider than 2048 neurons run as FOUR 768-sample slices of the cluster
  *                  form (64 clusters per round: whole rounds), eleven sweep wavefronts for symmetric alphabets, eight otherwise; 8 / 11 force
- *                  the count; 0: the classic one-step shape of rounds 4-5
- *   "blk_chip_ok"   -1 (default): the cluster form asks the device whether it is the whole chip its workgroup maps assume (256 compute
- *                  units = 8 XCDs x 32, no compute-unit mask in the environment) and is not used otherwise; 0 / 1 force the answer (tests)
- *   "blk_cluster_timeout_ms"  how long an exchange of the cluster form waits for a slice that does not arrive (default 3000)
- *   "blk_cluster_fault"       tests: 1 = one slice of the first cluster never publishes -- every exchange of that cluster times out
- *   "sync_errors"   1: gpfq_quantize_neurons (block-pipelined kernel) and gpfq_quantize_dense_layer wait for their launches and return
- *                  gpfq_call_status() of the call; 0 (default): asynchronous, the caller checks gpfq_call_status itself
+ *                  the count; 0: the classic one-step shape of rounds 4-5 (any other value: -1)
+ *   "blk_chip_ok"   default -1 (any negative value): the cluster form asks the device whether it is the whole chip its workgroup maps
+ *                  assume (256 compute units = 8 XCDs x 32, no compute-unit mask in the environment) and is not used otherwise;
+ *                  0 / 1 force the answer (tests)
+ *   "blk_cluster_timeout_ms"  default 3000: how long an exchange of the cluster form waits for a slice that does not arrive;
+ *                  1..60000 (else rejected)
+ *   "blk_cluster_fault"       default 0; tests: 1 = one slice of the first cluster never publishes -- every exchange of that cluster times out
+ *   "conv_fused"   default 1: conv layers read their patch rows from the channel planes; 0: per-channel patch matrices
+ *   "conv_planes_free"  default 1: 7x7 / stride 2 / VALID layers read the NHWC activations themselves
+ *                  (gpfq_quantize_conv_channels_nhwc); 0: channel planes first
+ *   "conv_nhwc"    default 1: 3x3 / stride 1 / SAME layers read the NHWC activations directly (shards of 32+ channels, and of 8 to 31
+ *                  where 2, 4 or 8 divides the image count: see the halves option below) (gpfq_quantize_conv3x3_nhwc); 0: channel planes first
+ *   "conv_strip"   default 0 = heuristic; plane-correlation kernel: output positions per lane 1, 2 or 4 (else rejected)
+ *   "conv_shift"   default 1: 3x3 / stride 1 / SAME layers on images of 20 x 20 or more (shards of 8+ channels) accumulate shift sums (27 FMAs per
+ *                  position, border classes apart); 0: the per-output-position records (99 FMAs) that VALID layers and small
+ *                  images use; 2: the shift form for every image of 4 x 4 or more (tests); else rejected
+ *   "conv_s2"      default 1: 7x7 / stride 2 / VALID conv layers form their Gram records from shift sums of the parity classes of the
+ *                  channel planes (gpfq_gram_s2.hip); 0: the matrix-core kernel
+ *   "conv_nhwc_halves"  default 1: in shards of at most 32 / 16 / 8 channels the lanes the shard leaves idle walk further
+ *                  halves / quarters / eighths of the images (where that count divides the number of images); 0: they idle
+ *   "conv_nhwc_slots"   default 8192: the NHWC 3x3 form's workgroups per launch (many short one-wavefront workgroups balance
+ *                  themselves); clamped to 256..65536
+ * (The 0 / 1 switches store any non-zero value as 1.)
  */
+int gpfq_set_option(const char *key, int value);
+/* The stored (normalised) value of an option: what the last accepted gpfq_set_option left there, or the default.  Setting an option to
+ * what this returned changes nothing.  Unknown or NULL key, NULL value: GPFQ_ERR_INVALID_ARG. */
+int gpfq_get_option(const char *key, int *value);
 
 /*
  * Deferred errors of an asynchronous dense call (gpfq_quantize_neurons on the on-chip path, gpfq_quantize_dense_layer): waits for

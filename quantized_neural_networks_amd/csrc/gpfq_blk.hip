@@ -1998,52 +1998,19 @@ gpfq_blk_kernel(BlkK K)
 
 // ---- host side ------------------------------------------------------------------------------------
 struct BlkShape { int G, S, B, mp, NW, NL, NS; };  // NL: neurons per lane (4 G or 2 G neurons per workgroup); NS: 0 = classic; >= 2: slices of the cluster form (mp = samples of a slice)
-static std::atomic<int> g_blk_single{1};  // one neuron per workgroup for layers of at most 128 neurons (blk_set_single_groups)
-void blk_set_single_groups(int on) { g_blk_single.store(on ? 1 : 0, std::memory_order_relaxed); }
-static std::atomic<int> g_blk_nw{0};      // sweep wavefronts of the 16-neuron B = 4 shapes: 8, 11, or 0 = by shape (blk_set_sweep_waves)
-static std::atomic<int> g_blk_four{1};    // 4-neuron workgroups for layers of at most 1024 neurons on rows of 769..2048 samples
-void blk_set_four_groups(int on) { g_blk_four.store(on ? 1 : 0, std::memory_order_relaxed); }
-static std::atomic<int> g_blk_wide{1};    // 16-neuron workgroups for rows beyond 1024 samples in layers wider than 2048 neurons
-void blk_set_wide_groups(int on) { g_blk_wide.store(on ? 1 : 0, std::memory_order_relaxed); }
-void blk_set_sweep_waves(int nw) { g_blk_nw.store(nw == 11 ? 11 : (nw == 8 ? 8 : 0), std::memory_order_relaxed); }
-
-// C: neurons of the call.  Rows of 769..1024 samples are the one shape whose slot is bound by the sweeps (nine sample pairs
-// on three of the SIMDs), not by the chain of decisions: up to 2048 neurons -- one round of 256 workgroups with 8 neurons
-// each -- the sweeps are halved by giving a workgroup 8 neurons instead of 16 (4096 x 2048, m = 1024: 4.0 -> 2.9 ms).
-static std::atomic<int> g_blk_quad{2};    // four neuron groups x 1 / 2 neurons per lane for layers of at most 2048 neurons on rows of 257..1024 samples (1: 129..2048 only)
-void blk_set_quad_groups(int on) { g_blk_quad.store(on < 0 ? 0 : (on > 2 ? 2 : on), std::memory_order_relaxed); }
-static std::atomic<int> g_blk_quad_nw{0}; // sweep wavefronts of the four-group narrow shapes on rows of at most 768 samples: 7, 8, or 0 = by shape
-void blk_set_quad_waves(int nw) { g_blk_quad_nw.store(nw == 7 ? 7 : (nw == 8 ? 8 : 0), std::memory_order_relaxed); }
-static std::atomic<int> g_blk_pairs{1};   // two-neuron workgroups for layers of at most 512 neurons
-void blk_set_pair_groups(int on) { g_blk_pairs.store(on ? 1 : 0, std::memory_order_relaxed); }
+// (the options that steer the shapes -- blk_* -- are rows of gpfq_options.hpp; a call's snapshot of them arrives in PipeArgs::opt)
 
 // Cluster form (round 5): long rows -- up to 28672 samples -- are cut into slices of 1024 samples, one workgroup of the headline shape
 // <4,32,4> x 11 each, that exchange their partial dot products once per slot (cl_publish / cl_gather).  Option blk_cluster: 1 (default)
 // = by row length and width (blk_shape), 0 = off (rows beyond 5120 samples then keep the several-wavefronts-per-neuron kernel), a value
-// from 1024 up = every row beyond that many samples (tests, A/B).
-static std::atomic<int> g_blk_cluster_nl{0};      // cluster form: neurons per lane, 0 = by width; 1 / 2 / 4 force it (option blk_cluster_nl)
-void blk_set_cluster_nl(int v) { g_blk_cluster_nl.store(v == 1 || v == 2 || v == 4 ? v : 0, std::memory_order_relaxed); }
-static std::atomic<int> g_blk_prep_run{1};         // 1 (default): the record pre-pass takes runs of 4 .. 16 records per workgroup for walks of 2048+ steps; 0: one record per workgroup; 4 .. 16: runs of that many at any length (option blk_prep_run: A/B, tests)
-void blk_set_prep_run(int v) { g_blk_prep_run.store(v >= 4 && v <= 16 ? v : (v ? 1 : 0), std::memory_order_relaxed); }
-static std::atomic<int> g_blk_prep_norms{1};       // 1 (default): gpfq_quantize_dense_layer's row norms inside the record pre-pass where that is bit-identical; 0: always the row-norm kernel (option blk_prep_norms: A/B, tests)
-void blk_set_prep_norms(int v) { g_blk_prep_norms.store(v ? 1 : 0, std::memory_order_relaxed); }
-static std::atomic<int> g_blk_chip{-1};            // -1: ask the device; 0 / 1 force the answer of blk_chip_ok (option blk_chip_ok: tests)
-void blk_set_chip_ok(int v) { g_blk_chip.store(v < 0 ? -1 : (v ? 1 : 0), std::memory_order_relaxed); }
-static std::atomic<int> g_blk_cl_timeout_ms{3000};  // how long an exchange of the cluster form waits for a slice before it gives up (option blk_cluster_timeout_ms)
-void blk_set_cluster_timeout_ms(int v) { g_blk_cl_timeout_ms.store(v < 1 ? 1 : v, std::memory_order_relaxed); }
-static std::atomic<int> g_blk_cl_fault{0};         // tests: 1 = slice 1 of cluster 0 never publishes (forces the exchange's timeout; option blk_cluster_fault)
-void blk_set_cluster_fault(int v) { g_blk_cl_fault.store(v ? 1 : 0, std::memory_order_relaxed); }
-static std::atomic<int> g_blk_cluster768{-1};      // rows of 2049..3072 samples in wide layers as four 768-sample slices: -1 (default) yes, 0 off, 8 / 11 force the sweep wavefronts (option blk_cluster768)
-void blk_set_cluster768(int v) { g_blk_cluster768.store(v == 0 ? 0 : (v == 8 ? 8 : (v == 11 ? 11 : -1)), std::memory_order_relaxed); }
-static std::atomic<int> g_blk_cluster{1};
-void blk_set_cluster(int v) { g_blk_cluster.store(v <= 0 ? 0 : (v < 1024 ? 1 : v), std::memory_order_relaxed); }
+// from 1024 up = every row beyond that many samples (tests, A/B).  (The options themselves: gpfq_options.hpp.)
 constexpr int64_t kClusterMaxM = 28672;      // = GPFQ_ONCHIP_MAX_M: 28 slices, still inside one XCD's 32 CUs
 // The cluster form's co-residency argument (gpfq_blk_kernel) is about THIS chip: 256 compute units in 8 XCDs of 32, the workgroups of a
 // launch handed to the XCDs round-robin and started in order.  A device that shows anything else -- a partition of the chip (CPX / DPX / QPX
 // modes: 32 / 128 / 64 compute units), a compute-unit mask from the environment -- does not get the cluster shapes: its long rows keep the
 // classic shapes and the several-wavefronts-per-neuron kernel.  Asked once per device; no device (the CPU build container
 // sizing a workspace): the full chip is assumed.
-static bool blk_chip_ok()
+static bool blk_chip_ok(const Options &opt)
 {
     static std::atomic<int> cache[64];                       // per device: 0 unknown, 1 ok, 2 not
     int dev = 0;
@@ -2058,19 +2025,16 @@ static bool blk_chip_ok()
         v = ok ? 1 : 2;
         cache[dev].store(v, std::memory_order_relaxed);
     }
-    const int forced = g_blk_chip.load(std::memory_order_relaxed);      // (tests: option blk_chip_ok = 0 pretends the chip is partitioned)
+    const int forced = opt.blk_chip_ok;                                 // (tests: option blk_chip_ok = 0 pretends the chip is partitioned)
     return forced >= 0 ? forced != 0 : v == 1;
 }
 // Workgroup id -> (cluster, slice).  Workgroups go to the XCDs round-robin by id and every XCD starts its own in order.  Map 0 puts the
 // slices of a cluster side by side in ONE XCD's queue (the exchange stays inside that XCD's L2 domain); but an XCD's 32 CUs then hold
 // 32 / nsl whole clusters and 32 % nsl slices of the next one, which wait a whole round for their mates -- and so does every round after
 // (three slices: four rounds' time for three rounds of work).  Map 1, consecutive ids, strands at most one cluster of the whole chip.
-static std::atomic<int> g_blk_cluster_map{-1};     // -1: by the number of slices (blk_cluster_map below); 0 / 1 force a map (option blk_cluster_map)
-void blk_set_cluster_map(int v) { g_blk_cluster_map.store(v < 0 ? -1 : (v ? 1 : 0), std::memory_order_relaxed); }
-static int blk_cluster_map(int nsl, int64_t clusters)
+static int blk_cluster_map(int nsl, int64_t clusters, const Options &opt)
 {
-    const int v = g_blk_cluster_map.load(std::memory_order_relaxed);
-    if (v >= 0) return v;
+    if (opt.blk_cluster_map >= 0) return opt.blk_cluster_map;      // (0 / 1 force a map; -1: by the number of slices)
     // The two maps take the same time at every slice count measured (profiles/r05/cluster_form.txt) -- the exchange hides behind the chain of
     // decisions across XCDs as well as inside one.  But where the slice count divides 8 (or is 16), consecutive ids put slice s of EVERY
     // cluster on XCD s mod 8: an XCD's 32 workgroups then stream one or two record streams instead of all of them, and the launch's HBM
@@ -2086,7 +2050,10 @@ static int blk_cluster_map(int nsl, int64_t clusters)
     return 1;
 }
 
-static BlkShape blk_shape(int64_t m, int64_t C)
+// C: neurons of the call.  Rows of 769..1024 samples are the one shape whose slot is bound by the sweeps (nine sample pairs
+// on three of the SIMDs), not by the chain of decisions: up to 2048 neurons -- one round of 256 workgroups with 8 neurons
+// each -- the sweeps are halved by giving a workgroup 8 neurons instead of 16 (4096 x 2048, m = 1024: 4.0 -> 2.9 ms).
+static BlkShape blk_shape(int64_t m, int64_t C, const Options &opt)
 {
     if (m <= 0 || C <= 0) return {0, 0, 0, 0, 0, 0};               // (an empty calibration set has no shape: the slice count below would divide by zero)
     {
@@ -2094,21 +2061,21 @@ static BlkShape blk_shape(int64_t m, int64_t C)
         // chain of decisions), the classic shapes lose a third of that rate from 2049 samples up --, and rows of 1537..3072 samples
         // wherever the layer is ONE round of the chip (an XCD holds 32 / slices clusters at a time: up to 2048 neurons at two slices,
         // 1280 at three): profiles/r05/cluster_form.txt.
-        const int clm = g_blk_cluster.load(std::memory_order_relaxed);
+        const int clm = opt.blk_cluster;
         const int ns_ = (int)((m + 1023) / 1024);
         const bool one_round = ns_ <= 32 && ((C + 15) / 16 + 7) / 8 <= 32 / ns_;      // with 16 neurons per workgroup
-        const bool take = blk_chip_ok() && (clm == 1 ? (m > 3072 || (m > 1536 && one_round && (m > 2048 || C > 128))) : (clm > 1 && m > clm));   // (at most 128 neurons on rows of at most 2048 samples: the one-neuron workgroups stay ahead, 1.98 / 2.07 ms)
+        const bool take = blk_chip_ok(opt) && (clm == 1 ? (m > 3072 || (m > 1536 && one_round && (m > 2048 || C > 128))) : (clm > 1 && m > clm));   // (at most 128 neurons on rows of at most 2048 samples: the one-neuron workgroups stay ahead, 1.98 / 2.07 ms)
         // Round 6: rows of 2049..3072 samples in layers wider than 2048 neurons -- three 1024-sample slices would be 85 clusters per round
         // (four rounds for 3.01 rounds of work: 12.6 ms at 4096 x 4096 on 3000 samples, behind the classic one-step shape's 11.5) -- as FOUR
         // slices of 768 samples: 64 clusters per round, four whole rounds of a shorter slot.  (Other ragged lengths gain nothing from
         // shorter slices: a 768-sample slot takes 0.875 of a 1024-sample one)
-        if (clm == 1 && blk_chip_ok() && m > 2048 && m <= 3072 && C > 2048 && g_blk_cluster768.load(std::memory_order_relaxed) != 0)
+        if (clm == 1 && blk_chip_ok(opt) && m > 2048 && m <= 3072 && C > 2048 && opt.blk_cluster768 != 0)
             return {4, 24, 4, 768, 11, 4, 4};                      // (eight or eleven sweep wavefronts: launch_blk, by the alphabet's form)
         if (take && m <= kClusterMaxM) {
             // neurons per workgroup: the fewest (4, 8, 16) with which the layer is still ONE round of the chip -- a slot of the 4- and
             // 8-neuron shapes is the decision wavefront's (with the exchange's flight exposed), a slot of the 16-neuron shape the sweeps'
             const int ns = (int)((m + 1023) / 1024);
-            const int cn = g_blk_cluster_nl.load(std::memory_order_relaxed);
+            const int cn = opt.blk_cluster_nl;
             // (measured, profiles/r05/cluster_form.txt: 8 neurons per workgroup wherever the layer is then still one round -- an XCD holds
             //  32 / ns clusters at a time --, 16 otherwise; 4 per workgroup never beat 8)
             int nl = 4;
@@ -2120,7 +2087,7 @@ static BlkShape blk_shape(int64_t m, int64_t C)
     // Round 4 (dot products on the matrix unit, fused with the updates pair by pair): rows of 769..1024 samples take ELEVEN sweep wavefronts
     // (three per SIMD: 2.97 against 3.13 ms at 4096 x 4096 x 1024 -- the per-wavefront fold that made eleven lose until round 3 is gone);
     // shorter rows keep eight (768 samples: 2.53 against 2.63 ms; 512: 1.96 against 1.98)
-    const int nw_opt = g_blk_nw.load(std::memory_order_relaxed);
+    const int nw_opt = opt.blk_sweep_waves;
     const int nw4 = nw_opt ? nw_opt : 8, nw4_long = nw_opt ? nw_opt : 11;
     // Layers of at most 512 neurons: TWO neurons per workgroup (two per lane of the sweep wavefronts).  A narrow layer is bound by
     // the time of one slot, a slot by the instructions its workgroup issues (profiles/r03/blk_phase_stamps.txt): half the neurons
@@ -2135,16 +2102,16 @@ static BlkShape blk_shape(int64_t m, int64_t C)
     // on 512 samples 1.96 -> 1.38 (profiles/r04/latency_shapes.txt).  At most 128 neurons: 1.57 both ways at first; with the pair split of
     // BlkSplitQuad32 the four-group form is ahead there too (4096 x 128 on 1024 samples 1.58 -> 1.40 ms, on 768 1.62 -> 1.39, on 512 1.37 ->
     // 1.33; 4096 x 10 1.62 -> 1.50; cfg1's Dense(784 -> 128) 0.279 -> 0.271) and is the default for every layer of at most 2048 neurons.
-    const int quad = g_blk_quad.load(std::memory_order_relaxed);         // 2 (default): every layer of at most 2048 neurons; 1: 129..2048 only; 0: off
+    const int quad = opt.blk_quad_groups; // 2 (default): every layer of at most 2048 neurons; 1: 129..2048 only; 0: off
     if (quad && C <= 2048 && (quad >= 2 || C > 128) && m > 256 && m <= 1024) {
         const int nl = C > 1024 ? 2 : 1;
-        const int qw = g_blk_quad_nw.load(std::memory_order_relaxed);
+        const int qw = opt.blk_quad_waves;
         const int qnw = qw ? qw : (nl == 1 ? 7 : 8);                  // (seven sweep wavefronts: see BlkSplit7; rows beyond 768 samples keep eight)
         if (m <= 512) return {4, 16, 4, 512, qnw, nl};
         if (m <= 768) return {4, 24, 4, 768, qnw, nl};
         return {4, 32, 4, 1024, qw == 7 ? 7 : 8, nl};                 // (rows of 769..1024 samples: seven only when the option forces it)
     }
-    if (C <= 128 && g_blk_pairs.load(std::memory_order_relaxed) != 0 && g_blk_single.load(std::memory_order_relaxed) != 0) {
+    if (C <= 128 && opt.blk_pair_groups && opt.blk_single_groups) {
         if (m > 256 && m <= 512) return {1, 4, 4, 512, 4, 1};
         if (m > 512 && m <= 1024) return {1, 8, 4, 1024, 8, 1};
         if (m > 1024 && m <= 1536) return {1, 12, 2, 1536, 8, 1};
@@ -2153,7 +2120,7 @@ static BlkShape blk_shape(int64_t m, int64_t C)
         if (m > 3072 && m <= 4096) return {1, 32, 1, 4096, 8, 1};
         if (m > 4096 && m <= 5120) return {1, 40, 1, 5120, 8, 1};    // (eleven sweep wavefronts of 2-4 pairs: 2.17 against 2.06 ms at 2048 x 128 on 5008 samples)
     }
-    if (C <= 512 && g_blk_pairs.load(std::memory_order_relaxed) != 0) {
+    if (C <= 512 && opt.blk_pair_groups) {
         if (m > 256 && m <= 512) return {1, 4, 4, 512, 4, 2};
         if (m > 512 && m <= 1024) return {1, 8, 4, 1024, 8, 2};
         if (m > 1024 && m <= 1536) return {1, 12, 2, 1536, 8, 2};
@@ -2166,7 +2133,7 @@ static BlkShape blk_shape(int64_t m, int64_t C)
     if (m > 512 && m <= 768) return {4, 24, 4, 768, nw4, 4};
     // layers of at most 1024 neurons on rows of 769+ samples: FOUR neurons per workgroup (a quarter of the 16-neuron sweep per slot;
     // 256 workgroups hold 1024 neurons) -- the slot is then the chain of decisions
-    const bool four = C <= 1024 && g_blk_four.load(std::memory_order_relaxed) != 0;
+    const bool four = C <= 1024 && opt.blk_four_groups;
     if (four && m > 768 && m <= 1024) return {1, 8, 4, 1024, 8, 4};
     if (four && m > 1024 && m <= 1536) return {1, 12, 2, 1536, 8, 4};
     if (four && m > 1536 && m <= 2048) return {1, 16, 2, 2048, 8, 4};
@@ -2175,7 +2142,7 @@ static BlkShape blk_shape(int64_t m, int64_t C)
     // that takes two rounds of workgroups), 16 neurons over eleven sweep wavefronts: one round, half the decisions and folds per weight
     // (a 16-neuron workgroup takes 1.6 x as long as an 8-neuron one: 6.5 against 4.1 ms for 4096 steps of 2048 samples; rounds of 256)
     const int64_t rounds16 = (C + 4095) / 4096, rounds8 = (C + 2047) / 2048;
-    const bool wide = C > 2048 && 8 * rounds16 <= 5 * rounds8 && g_blk_wide.load(std::memory_order_relaxed) != 0;
+    const bool wide = C > 2048 && 8 * rounds16 <= 5 * rounds8 && opt.blk_wide_groups;
     if (m > 1024 && m <= 1536) return wide ? BlkShape{4, 48, 2, 1536, 11, 4} : BlkShape{2, 24, 2, 1536, 8, 4};
     if (m > 1536 && m <= 2048) return wide ? BlkShape{4, 64, 2, 2048, 11, 4} : BlkShape{2, 32, 2, 2048, 8, 4};
     // rows of 2049..4096 samples: a record is 48 / 64 KiB, so a slot is ONE step (B = 1) -- 8 neurons over eleven sweep wavefronts
@@ -2222,15 +2189,15 @@ static size_t blk_hdrs_off(int64_t nblk, const BlkShape &sh) { return blk_recs_b
 static size_t blk_mbox_off(int64_t nblk, const BlkShape &sh) { return blk_hdrs_off(nblk, sh) + ((blk_hdrs_bytes(nblk, sh.B, sh.NS != 0) + 255) & ~(size_t)255); }
 
 // Whether the kernel itself writes Keras-layout outputs for this shape (the 16-neuron four-step shapes: blk_kout_shape)
-bool blk_keras_out_supported(int64_t m, int64_t C)
+bool blk_keras_out_supported(int64_t m, int64_t C, const Options &opt)
 {
-    const BlkShape sh = blk_shape(m, C);
+    const BlkShape sh = blk_shape(m, C, opt);
     return sh.G == 4 && sh.B == 4 && sh.NL == 4 && sh.NS == 0;
 }
 
 bool blk_supported(const PipeArgs &a)
 {
-    const BlkShape sh = blk_shape(a.m, a.C);
+    const BlkShape sh = blk_shape(a.m, a.C, a.opt);
     if (sh.G == 0 || a.N < 1 || a.m < 1) return false;
     if (a.A.M > 64 || !a.A.ascending) return false;
     DevAlphabet D{};
@@ -2243,13 +2210,13 @@ bool blk_supported(const PipeArgs &a)
 constexpr size_t kAlphaBlock = 1024;        // the call's DevAlphabet, in front of the records (a host alphabet is stored there; a device alphabet is the caller's block)
 static_assert(sizeof(DevAlphabet) <= kAlphaBlock, "alphabet block");
 
-size_t blk_workspace_bytes(int64_t N, int64_t m, int64_t Cn)
+size_t blk_workspace_bytes(int64_t N, int64_t m, int64_t Cn, const Options &opt)
 {
     if (m <= 0 || N < 0) return 0;          // (an empty calibration set: blk_shape has no shape for it -- and must not be asked)
     // (the record layout depends on the row length and, through the steps per slot, on the width class of the layer: the largest)
     size_t need = 0;
     for (int64_t C : {(int64_t)1 << 30, (int64_t)2048, (int64_t)1024, (int64_t)512, Cn > 0 ? Cn : (int64_t)1}) {   // (and the call's own width: the cluster form's neurons per workgroup)
-        const BlkShape sh = blk_shape(m, C);
+        const BlkShape sh = blk_shape(m, C, opt);
         if (!sh.G) continue;
         const int64_t nblk = (N + sh.B - 1) / sh.B;
         // (cluster form: a record stream per slice, the compact headers once, the exchange buffers + the error word)
@@ -2259,11 +2226,11 @@ size_t blk_workspace_bytes(int64_t N, int64_t m, int64_t Cn)
     return need ? need + kAlphaBlock : 0;
 }
 
-// a32 of a symmetric alphabet {-a, 0, a} or {-a, a} (DevAlphabet::sym_a), else 0.  PipeArgs::variant bit 1 (option "variant" bit 5) keeps the general form (A/B timing).
+// a32 of a symmetric alphabet {-a, 0, a} or {-a, a} (DevAlphabet::sym_a), else 0.  Option "variant" bit 5 keeps the general form (A/B timing).
 // (device alphabets: a.A is the UNIT alphabet linspace(-1, 1, M) -- symmetric exactly when rad * unit is, for a finite rad > 0)
 static float blk_sym_a(const PipeArgs &a)
 {
-    if (a.variant & 2) return 0.f;
+    if ((a.opt.variant >> 4) & 2) return 0.f;
     return blk_sym_of(a.A.a, a.A.M);
 }
 
@@ -2290,9 +2257,9 @@ static hipError_t launch_blk_sym(const PipeArgs &a, const BlkShape &sh, const De
     K.hdrs = K.recs + blk_hdrs_off(nblk_, sh);
     K.alpha = alpha;
     K.alpha_err = a.fallback_count ? reinterpret_cast<int *>(a.fallback_count + 1) + 1 : nullptr;   // (fourth 32-bit word of the call's counter block, zeroed with it)
-    K.nsl = CL ? sh.NS : 0; K.cl_map = blk_cluster_map(sh.NS, (a.C + NB - 1) / NB); K.slice_bytes = (int64_t)blk_recs_bytes(nblk_, sh); K.mbox = nullptr; K.cl_err = nullptr;
+    K.nsl = CL ? sh.NS : 0; K.cl_map = blk_cluster_map(sh.NS, (a.C + NB - 1) / NB, a.opt); K.slice_bytes = (int64_t)blk_recs_bytes(nblk_, sh); K.mbox = nullptr; K.cl_err = nullptr;
     K.u_ld = a.m; K.slack = 0x1p-43 * (double)(sh.NS > 1 ? sh.NS : 1);
-    K.cl_timeout = 100000ull * (unsigned long long)g_blk_cl_timeout_ms.load(std::memory_order_relaxed); K.cl_fault = g_blk_cl_fault.load(std::memory_order_relaxed);
+    K.cl_timeout = 100000ull * (unsigned long long)a.opt.blk_cluster_timeout_ms; K.cl_fault = a.opt.blk_cluster_fault;
     if constexpr (CLM == 1) {
         char *mb = wbase + blk_mbox_off(nblk_, sh);
         const size_t mbytes = blk_mbox_bytes(a.C, sh);
@@ -2318,16 +2285,11 @@ static hipError_t launch_blk_sym(const PipeArgs &a, const BlkShape &sh, const De
     return hipGetLastError();
 }
 
-// (the eleven-wavefront variants of the shapes that also exist with eight are kept in the general form only: an experiment switch)
-constexpr bool blk_has_sym(int S, int NSW) { (void)S; (void)NSW; return true; }
-
 template <int G, int S, int B, int NSW = 8, int NL = 4>
 static hipError_t launch_blk_inst(const PipeArgs &a, const BlkShape &sh, const DevAlphabet *alpha, hipStream_t stream)
 {
     // (sweep-bound shapes gain 3-4 %, the others nothing)
-    if constexpr (blk_has_sym(S, NSW)) {
-        if (blk_sym_a(a) != 0.f) return launch_blk_sym<G, S, B, NSW, true, NL>(a, sh, alpha, stream);
-    }
+    if (blk_sym_a(a) != 0.f) return launch_blk_sym<G, S, B, NSW, true, NL>(a, sh, alpha, stream);
     return launch_blk_sym<G, S, B, NSW, false, NL>(a, sh, alpha, stream);
 }
 
@@ -2400,7 +2362,7 @@ hipError_t launch_alphabet_device(const float *median32, double alphabet_scalar,
 
 hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
 {
-    const BlkShape sh = blk_shape(a.m, a.C);
+    const BlkShape sh = blk_shape(a.m, a.C, a.opt);
     if (!sh.G) return hipErrorInvalidValue;
     const int64_t nblk = (a.N + sh.B - 1) / sh.B;
     const int64_t nrec = (nblk + 1) * sh.B + 1;
@@ -2412,7 +2374,7 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
     hipError_t e = do_run ? blk_alphabet(a, &alpha, stream) : hipSuccess;
     if (e != hipSuccess) return e;
     char *const wbase = static_cast<char *>(a.workspace) + kAlphaBlock;
-    const int sym_shape = (sh.NS || blk_has_sym(sh.S, sh.NW)) && blk_sym_a(a) != 0.f ? 1 : 0;
+    const int sym_shape = blk_sym_a(a) != 0.f ? 1 : 0;
     const int sym_prep = a.phase == 0 ? sym_shape : 0;            // (two-phase calls: the scaling follows in phase 2)
     if (a.phase == 2 && sym_shape) {
         const int mps = sh.mp;
@@ -2422,7 +2384,9 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
         if (e != hipSuccess) return e;
     }
     const bool vec_rows = (a.ld % 4 == 0) && (((uintptr_t)a.X | (uintptr_t)a.Xq) % 16 == 0);
-    const bool run_form = !sh.NS && vec_rows && (g_blk_prep_run.load(std::memory_order_relaxed) > 1 || (g_blk_prep_run.load(std::memory_order_relaxed) == 1 && nrec >= 2048));
+    // the record pre-pass in runs of records per workgroup (gpfq_blk_prep_run_kernel): the classic shapes, rows it can read 16 bytes at a time
+    const int prep_run = a.opt.blk_prep_run;
+    const bool run_form = !sh.NS && vec_rows && (prep_run > 1 || (prep_run == 1 && nrec >= 2048));
     // (the row norms, when the caller left them to this call: inside the pre-pass where it forms the row-norm kernel's very sums, else by that kernel)
     const float *nrm32 = a.nrm32;
     unsigned *zero16 = nullptr;
@@ -2430,7 +2394,7 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
         zero16 = reinterpret_cast<unsigned *>(a.fallback_count);
         // (mp == 1024 exactly: every thread of the pre-pass's workgroups then holds one 16-byte piece of a row -- with fewer, whole wavefronts sit
         //  the loop out and the wavefront sum would read lanes that never ran: tools/fuzz_parity.py found that at 292 samples)
-        const bool fuse = run_form && sh.mp == 1024 && a.m % 4 == 0 && g_blk_prep_norms.load(std::memory_order_relaxed) != 0;
+        const bool fuse = run_form && sh.mp == 1024 && a.m % 4 == 0 && a.opt.blk_prep_norms;
         if (!fuse) {
             e = launch_row_norms(a.Xq, a.N, a.m, a.ld, a.nrm32_out, stream, zero16);
             if (e != hipSuccess) return e;
@@ -2454,7 +2418,7 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
         if (sh.S == 24) {
             // four 768-sample slices (blk_shape).  Sweep wavefronts, measured at 4096 x 4096 on 3000 samples (tools/c768_probe.py): the symmetric
             // form 10.29 ms with eleven against 10.68 with eight, the general form 11.02 with eight against 11.25 with eleven
-            const int forced = g_blk_cluster768.load(std::memory_order_relaxed);
+            const int forced = a.opt.blk_cluster768;
             const int nw = forced == 8 || forced == 11 ? forced : (sym ? 11 : 8);
             return nw == 8 ? GPFQ_BLK_CL(24, 8, 4, 1) : GPFQ_BLK_CL(24, 11, 4, 1);
         }
@@ -2465,18 +2429,16 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
     auto *prep = sh.B == 4 ? (r64 ? gpfq_blk_prep_kernel<4, true> : gpfq_blk_prep_kernel<4, false>)
                            : (sh.B == 2 ? (r64 ? gpfq_blk_prep_kernel<2, true> : gpfq_blk_prep_kernel<2, false>) : gpfq_blk_prep_kernel<1, false>);
     const int sym = sym_prep;   // (exactly the launches launch_blk_inst gives the symmetric form)
-    const bool vec = (a.ld % 4 == 0) && (((uintptr_t)a.X | (uintptr_t)a.Xq) % 16 == 0);
     if (!do_prep) {
-    } else if (vec && (g_blk_prep_run.load(std::memory_order_relaxed) > 1 || (g_blk_prep_run.load(std::memory_order_relaxed) == 1 && nrec >= 2048))) {
+    } else if (run_form) {
         // (walks of fewer than 2048 steps: runs of records would be fewer workgroups than the chip has compute units, each a chain of eight
         //  records -- a Dense(128 -> 10) layer's pre-pass 0.08 ms longer; those keep one record per workgroup)
         // runs of 4 .. 16 records per workgroup (gpfq_blk_prep_run_kernel); the one-record form keeps the rows it cannot read 16 bytes at a time.
         // The kernel holds four workgroups per compute unit (116 registers): 1024 at a time.  A workgroup is a chain of 1 + run round trips to
         // memory, so the run length is the one in 4 .. 16 under which the launch is the fewest rounds x (1 + run) -- the SHORTEST run that
         // still fits one round where there is one (4101 records of the headline layer: runs of five, 821 workgroups).
-        const int opt = g_blk_prep_run.load(std::memory_order_relaxed);
         int run = 8;
-        if (opt >= 4 && opt <= kPrepRunMax) run = opt;
+        if (prep_run >= 4 && prep_run <= kPrepRunMax) run = prep_run;
         else {
             int64_t best = -1;
             for (int rl = 4; rl <= kPrepRunMax; ++rl) {

@@ -71,9 +71,39 @@ int make_alphabet(const double *alphabet, int M, int zero_idx, HostAlphabet *H)
     return GPFQ_OK;
 }
 
+// The options (gpfq_options.hpp): the table's rows, and the process-wide store -- one relaxed atomic per row, in the table's order.
+struct OptionRow {
+    const char *key;
+    int gpfq::Options::*member;
+    bool (*accepts)(int);
+    int (*stores)(int);
+    const char *domain;
+};
+#define GPFQ_OPTION_ROW(key, def, accepts, stores, domain) \
+    {#key, &gpfq::Options::key, [](int v) { (void)v; return (bool)(accepts); }, [](int v) { return (int)(stores); }, domain},
+const OptionRow kOptionRows[] = {GPFQ_OPTIONS(GPFQ_OPTION_ROW)};
+#undef GPFQ_OPTION_ROW
+#define GPFQ_OPTION_DEFAULT(key, def, accepts, stores, domain) {def},
+std::atomic<int> option_store[] = {GPFQ_OPTIONS(GPFQ_OPTION_DEFAULT)};
+#undef GPFQ_OPTION_DEFAULT
+constexpr int kOptionCount = (int)(sizeof(kOptionRows) / sizeof(kOptionRows[0]));
+
+int option_index(const char *key)
+{
+    for (int i = 0; i < kOptionCount; ++i)
+        if (!std::strcmp(key, kOptionRows[i].key)) return i;
+    return -1;
+}
+
 }  // namespace
 
 namespace gpfq {
+Options options_snapshot()
+{
+    Options o;
+    for (int i = 0; i < kOptionCount; ++i) o.*kOptionRows[i].member = option_store[i].load(std::memory_order_relaxed);
+    return o;
+}
 void note_dense_kernel(const char *name) { g_dense_kernel = name; }
 bool main_kernel_events(hipEvent_t *start, hipEvent_t *stop)
 {
@@ -154,9 +184,9 @@ static bool auto_wants_gram(int64_t N, int64_t m, int64_t C, bool want_u)
 // on-chip workspace: [fallback counter, 64 B][RowStats x N][iteration records of the pipelined kernel]
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 static size_t onchip_stats_bytes(int64_t N) { return al256(64 + (size_t)N * sizeof(gpfq::RowStats)); }
-static size_t onchip_workspace_bytes(int64_t N, int64_t m, int64_t C)
+static size_t onchip_workspace_bytes(int64_t N, int64_t m, int64_t C, const gpfq::Options &o)
 {
-    const size_t p = gpfq::pipe_workspace_bytes(N, m), b = gpfq::blk_workspace_bytes(N, m, C);
+    const size_t p = gpfq::pipe_workspace_bytes(N, m), b = gpfq::blk_workspace_bytes(N, m, C, o);
     return onchip_stats_bytes(N) + (p > b ? p : b);
 }
 
@@ -170,7 +200,8 @@ static size_t auto_gram_workspace_bytes(int64_t N, int64_t m, int64_t C)
 size_t gpfq_workspace_bytes(int64_t N, int64_t m, int64_t C, int path)
 {
     if (N < 0 || m < 0 || C < 0) return 0;
-    size_t need = resolve_path(m, path) == GPFQ_PATH_ONCHIP ? onchip_workspace_bytes(N, m, C)
+    const gpfq::Options o = gpfq::options_snapshot();
+    size_t need = resolve_path(m, path) == GPFQ_PATH_ONCHIP ? onchip_workspace_bytes(N, m, C, o)
                                                              : gpfq::stream_workspace_bytes(N, m, C, /*need_u=*/true);
     if (path == GPFQ_PATH_AUTO && auto_wants_gram(N, m, C, false)) {
         const size_t g = auto_gram_workspace_bytes(N, m, C);
@@ -179,99 +210,24 @@ size_t gpfq_workspace_bytes(int64_t N, int64_t m, int64_t C, int path)
     return need;
 }
 
-// Tuning / test hooks (process-wide, atomics: a call on another thread sees either the old or the new value of each).
-// Results never depend on them.
-static std::atomic<int> g_onchip_mode{1};      // 1 = certified (default), 0 = exact flow
-static std::atomic<int> g_tile_steps{0};       // 0 = heuristic
-static std::atomic<int> g_group_waves{0};      // 0 = heuristic
-static std::atomic<int> g_lpn{0};              // 0 = heuristic, 1 = wave-per-neuron kernel, 16/32/64 = row-group kernel
-static std::atomic<int> g_gram_slack_log2{0};  // Gram path: error bounds multiplied by 2^this (tests force the uncertified branch)
-static std::atomic<int> g_wpn{0};              // wide kernel: wavefronts per neuron (0 = heuristic: only for rows > 2048)
-static std::atomic<int> g_variant{0};          // bit 0: row-group kernel without the float64 copy of Xq in LDS; bit 1: wide kernel with LDS-staged rows
-static std::atomic<int> g_pipe{-1};            // pipelined dense kernels: -1 = heuristic, 0 = never, 1 = one step per slot (gpfq_pipe.hip) whenever it
-                                   // applies, 2 = blocks of steps per slot (gpfq_blk.hip) whenever it applies
-static std::atomic<int> g_auto_gram{1};        // GPFQ_PATH_AUTO may take the Gram path (one stream synchronisation inside the call); 0: AUTO stays asynchronous
-static std::atomic<int> g_conv_fused{1};       // conv channel loop: 3x3/stride-1 Gram matrices straight from the planes
-static std::atomic<int> g_conv_planes_free{1}; // 7x7 / 2 layers read the NHWC activations themselves (gpfq_quantize_conv_channels_nhwc; 0: channel planes first)
-static std::atomic<int> g_conv_nhwc{1};        // 3x3 / stride 1 / SAME layers straight from the NHWC activations (no channel-major copy)
-static std::atomic<int> g_conv_strip{0};
-static std::atomic<int> g_sync_errors{0};      // 1: gpfq_quantize_neurons / gpfq_quantize_dense_layer wait for their launches and return the call's status words as an error code
-static std::atomic<int> g_conv_shift{1};    // fused 3x3 conv kernel with SAME padding: the shift form (0 = the per-output-position form)       // fused conv kernel: forced strip length (0 = heuristic)
-
 int gpfq_set_option(const char *key, int value)
 {
     if (!key) return fail(GPFQ_ERR_INVALID_ARG, "option key is NULL");
-    if (!std::strcmp(key, "onchip_mode")) { g_onchip_mode = value ? 1 : 0; return GPFQ_OK; }
-    if (!std::strcmp(key, "tile_steps")) {
-        if (value < 0 || value > 64 || (value & (value - 1))) return fail(GPFQ_ERR_INVALID_ARG, "tile_steps must be 0 or a power of two <= 64");
-        g_tile_steps = value; return GPFQ_OK;
-    }
-    if (!std::strcmp(key, "group_waves")) {
-        if (value < 0 || value > 16) return fail(GPFQ_ERR_INVALID_ARG, "group_waves must be in [0, 16]");
-        g_group_waves = value; return GPFQ_OK;
-    }
-    if (!std::strcmp(key, "variant")) { g_variant = value; return GPFQ_OK; }
-    if (!std::strcmp(key, "pipe")) {
-        if (value != -1 && value != 0 && value != 1 && value != 2)
-            return fail(GPFQ_ERR_INVALID_ARG, "pipe must be -1, 0, 1 or 2");
-        g_pipe = value; return GPFQ_OK;
-    }
-    if (!std::strcmp(key, "blk_four_groups")) { gpfq::blk_set_four_groups(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_wide_groups")) { gpfq::blk_set_wide_groups(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_pair_groups")) { gpfq::blk_set_pair_groups(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_single_groups")) { gpfq::blk_set_single_groups(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_quad_groups")) { gpfq::blk_set_quad_groups(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_cluster_map")) { gpfq::blk_set_cluster_map(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_cluster768")) { gpfq::blk_set_cluster768(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_prep_run")) { gpfq::blk_set_prep_run(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_prep_norms")) { gpfq::blk_set_prep_norms(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_chip_ok")) { gpfq::blk_set_chip_ok(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_cluster_fault")) { gpfq::blk_set_cluster_fault(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_cluster_timeout_ms")) {
-        if (value < 1 || value > 60000) return fail(GPFQ_ERR_INVALID_ARG, "blk_cluster_timeout_ms must be in [1, 60000]");
-        gpfq::blk_set_cluster_timeout_ms(value); return GPFQ_OK;
-    }
-    if (!std::strcmp(key, "sync_errors")) { g_sync_errors = value ? 1 : 0; return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_cluster_nl")) { gpfq::blk_set_cluster_nl(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "blk_cluster")) {
-        if (value < 0 || (value > 1 && value < 1024)) return fail(GPFQ_ERR_INVALID_ARG, "blk_cluster must be 0 (off), 1 (default: by row length and width) or a row length >= 1024");
-        gpfq::blk_set_cluster(value); return GPFQ_OK;
-    }
-    if (!std::strcmp(key, "blk_quad_waves")) {
-        if (value != 0 && value != 7 && value != 8) return fail(GPFQ_ERR_INVALID_ARG, "blk_quad_waves must be 0 (by shape), 7 or 8");
-        gpfq::blk_set_quad_waves(value); return GPFQ_OK;
-    }
-    if (!std::strcmp(key, "blk_sweep_waves")) {
-        if (value != 0 && value != 8 && value != 11) return fail(GPFQ_ERR_INVALID_ARG, "blk_sweep_waves must be 0 (by shape), 8 or 11");
-        gpfq::blk_set_sweep_waves(value); return GPFQ_OK;
-    }
-    if (!std::strcmp(key, "waves_per_neuron")) {
-        if (value < 0 || value > 16) return fail(GPFQ_ERR_INVALID_ARG, "waves_per_neuron must be in [0, 16]");
-        g_wpn = value; return GPFQ_OK;
-    }
-    if (!std::strcmp(key, "gram_slack_log2")) { g_gram_slack_log2 = value; return GPFQ_OK; }
-    if (!std::strcmp(key, "auto_gram")) { g_auto_gram = value ? 1 : 0; return GPFQ_OK; }
-    if (!std::strcmp(key, "conv_fused")) { g_conv_fused = value ? 1 : 0; return GPFQ_OK; }
-    if (!std::strcmp(key, "conv_nhwc")) { g_conv_nhwc = value ? 1 : 0; return GPFQ_OK; }
-    if (!std::strcmp(key, "conv_planes_free")) { g_conv_planes_free = value ? 1 : 0; return GPFQ_OK; }
-    if (!std::strcmp(key, "conv_s2")) { gpfq::conv_set_s2(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "conv_nhwc_slots")) { gpfq::image_set_nhwc_slots(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "conv_nhwc_halves")) { gpfq::image_set_nhwc_halves(value); return GPFQ_OK; }
-    if (!std::strcmp(key, "conv_shift")) {
-        if (value < 0 || value > 2) return fail(GPFQ_ERR_INVALID_ARG, "conv_shift must be 0, 1 or 2");
-        g_conv_shift = value; return GPFQ_OK;
-    }
-    if (!std::strcmp(key, "conv_strip")) {
-        if (value != 0 && value != 1 && value != 2 && value != 4)
-            return fail(GPFQ_ERR_INVALID_ARG, "conv_strip must be 0, 1, 2 or 4");
-        g_conv_strip = value; return GPFQ_OK;
-    }
-    if (!std::strcmp(key, "lanes_per_neuron")) {
-        if (value != 0 && value != 1 && value != 16 && value != 32 && value != 64)
-            return fail(GPFQ_ERR_INVALID_ARG, "lanes_per_neuron must be 0, 1, 16, 32 or 64");
-        g_lpn = value; return GPFQ_OK;
-    }
-    return fail(GPFQ_ERR_INVALID_ARG, "unknown option '%s'", key);
+    const int i = option_index(key);
+    if (i < 0) return fail(GPFQ_ERR_INVALID_ARG, "unknown option '%s'", key);
+    if (!kOptionRows[i].accepts(value)) return fail(GPFQ_ERR_INVALID_ARG, "%s must be %s", key, kOptionRows[i].domain);
+    option_store[i].store(kOptionRows[i].stores(value), std::memory_order_relaxed);
+    return GPFQ_OK;
+}
+
+int gpfq_get_option(const char *key, int *value)
+{
+    if (!key) return fail(GPFQ_ERR_INVALID_ARG, "option key is NULL");
+    const int i = option_index(key);
+    if (i < 0) return fail(GPFQ_ERR_INVALID_ARG, "unknown option '%s'", key);
+    if (!value) return fail(GPFQ_ERR_INVALID_ARG, "option '%s': value is NULL", key);
+    *value = option_store[i].load(std::memory_order_relaxed);
+    return GPFQ_OK;
 }
 
 int gpfq_call_status(const void *workspace, void *stream)
@@ -319,9 +275,10 @@ int gpfq_quantize_neurons(const float *X, const float *Xq, int64_t ld, const flo
         return fail(GPFQ_ERR_INVALID_ARG, "unknown path %d", path);
     const int p = resolve_path(m, path);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const gpfq::Options o = gpfq::options_snapshot();
 
     // (alphabets beyond 64 members have no wavefront-per-neuron chain for walks beyond 64 steps: those stay on the element-wise paths)
-    if (path == GPFQ_PATH_AUTO && g_auto_gram && N > 0 && m > 0 && auto_wants_gram(N, m, C, u_out != nullptr) && !(H.is_big && N > 64) && workspace &&
+    if (path == GPFQ_PATH_AUTO && o.auto_gram && N > 0 && m > 0 && auto_wants_gram(N, m, C, u_out != nullptr) && !(H.is_big && N > 64) && workspace &&
         (uintptr_t)workspace % 16 == 0 && workspace_bytes >= auto_gram_workspace_bytes(N, m, C)) {
         // Long rows, short walks: Gram records once per layer, the recurrence on scalars with every decision certified,
         // uncertifiable chains repaired on the device; whatever is still flagged afterwards (practically never) is rerun
@@ -334,8 +291,8 @@ int gpfq_quantize_neurons(const float *X, const float *Xq, int64_t ld, const flo
         g.X = X; g.Xq = Xq; g.ld = ld; g.nrm32 = nrm32; g.Wt = Wt; g.ldw = ldw; g.A = A; g.big = H.big();
         g.N = N; g.m = m; g.C = C; g.qidx = qidx; g.Qt = Qt; g.resid = resid; g.uncertified = unc;
         g.workspace = gram_ws;
-        g.slack = std::ldexp(1.0, g_gram_slack_log2);
-        g.variant = g_variant;
+        g.slack = std::ldexp(1.0, o.gram_slack_log2);
+        g.opt = o;
         gpfq::note_dense_kernel("gpfq_gram_* (Gram records + certified scalar recurrence), reruns through gpfq_stream_*");
         hipError_t e = gpfq::launch_gram(g, s);
         if (e != hipSuccess) return hip_fail(e, "gpfq_quantize_neurons(auto: gram)");
@@ -362,11 +319,8 @@ int gpfq_quantize_neurons(const float *X, const float *Xq, int64_t ld, const flo
         gpfq::OnchipArgs a;
         a.X = X; a.Xq = Xq; a.ld = ld; a.nrm32 = nrm32; a.Wt = Wt; a.ldw = ldw; a.A = A; a.big = H.big();
         a.N = N; a.m = m; a.C = C; a.qidx = qidx; a.Qt = Qt; a.resid = resid; a.u_out = u_out;
-        a.ts_override = g_tile_steps; a.nw_override = g_group_waves;
-        a.mode = g_onchip_mode;
-        a.lpn = g_lpn;
-        a.wpn = g_wpn;
-        a.variant = g_variant;
+        a.mode = o.onchip_mode;
+        a.opt = o;
         // certified mode needs the per-row statistics in the workspace; without one, run the exact flow
         const bool have_ws = workspace && workspace_bytes >= onchip_stats_bytes(N) && (uintptr_t)workspace % 16 == 0;
         bool counters_zeroed = false;
@@ -381,8 +335,8 @@ int gpfq_quantize_neurons(const float *X, const float *Xq, int64_t ld, const flo
             gpfq::PipeArgs pa;
             pa.X = X; pa.Xq = Xq; pa.ld = ld; pa.nrm32 = nrm32; pa.Wt = Wt; pa.ldw = ldw; pa.A = A;
             pa.N = N; pa.m = m; pa.C = C; pa.qidx = qidx; pa.Qt = Qt; pa.resid = resid; pa.u_out = u_out;
-            pa.ts_override = g_tile_steps; pa.variant = g_variant >> 4;
-            const bool forced_old = g_lpn != 0 || g_wpn != 0 || g_onchip_mode != 1 || g_pipe == 0;
+            pa.opt = o;
+            const bool forced_old = o.lanes_per_neuron != 0 || o.waves_per_neuron != 0 || o.onchip_mode != 1 || o.pipe == 0;
             // measured (tools/blk_ab.sh shapes): the block-pipelined kernel is ahead of the row-group and wavefront-per-neuron kernels
             // for rows of 257..4096 samples (2049+: one step per slot; 4096 x 4096 x 4096: 16.6 vs 38 ms) whenever the layer has 512 neurons or more (4096 x 4096, m = 1024: 4.1 vs 5.4 ms;
             // m = 2048, 16 levels: 8.7 vs 10.0; m = 512: 3.2 vs 3.9; 4096 x 1024, m = 1536: 3.7 vs 6.8; 784 x 4096, m = 512: 0.68
@@ -395,19 +349,19 @@ int gpfq_quantize_neurons(const float *X, const float *Xq, int64_t ld, const flo
             // Round 5: rows of 5121..28672 samples too -- the cluster form (gpfq_blk.hip: slices of 1024 samples over several workgroups;
             // blk_supported() says no when the option blk_cluster switches it off)
             const bool fits = m > 256 && M <= 64 && m <= GPFQ_ONCHIP_MAX_M;
-            const bool want = g_pipe == 1;
-            if ((g_pipe == 2 || (g_pipe < 0 && !forced_old && fits)) && N > 0 && m > 0 && gpfq::blk_supported(pa) && workspace &&
-                (uintptr_t)workspace % 16 == 0 && workspace_bytes >= onchip_workspace_bytes(N, m, C)) {
+            const bool want = o.pipe == 1;
+            if ((o.pipe == 2 || (o.pipe < 0 && !forced_old && fits)) && N > 0 && m > 0 && gpfq::blk_supported(pa) && workspace &&
+                (uintptr_t)workspace % 16 == 0 && workspace_bytes >= onchip_workspace_bytes(N, m, C, o)) {
                 pa.workspace = static_cast<char *>(workspace) + onchip_stats_bytes(N);
                 pa.fallback_count = static_cast<unsigned long long *>(workspace);
                 pa.zero_counters = 1;                              // (the kernel that stores the alphabet zeroes the counter block as well: one launch, no memset)
                 gpfq::note_dense_kernel("gpfq_blk_kernel (4 to 11 sweep wavefronts + 1 decision wavefront per workgroup, blocks of steps per slot)");
                 hipError_t e = gpfq::launch_blk(pa, s);
                 if (e != hipSuccess) return hip_fail(e, "gpfq_quantize_neurons(block-pipelined)");
-                return g_sync_errors ? gpfq_call_status(workspace, stream) : GPFQ_OK;
+                return o.sync_errors ? gpfq_call_status(workspace, stream) : GPFQ_OK;
             }
             if (want && N > 0 && m > 0 && gpfq::pipe_supported(pa) && workspace && (uintptr_t)workspace % 16 == 0 &&
-                workspace_bytes >= onchip_workspace_bytes(N, m, C)) {
+                workspace_bytes >= onchip_workspace_bytes(N, m, C, o)) {
                 hipError_t ez = zero_counters();
                 if (ez != hipSuccess) return hip_fail(ez, "gpfq_quantize_neurons(workspace)");
                 pa.workspace = static_cast<char *>(workspace) + onchip_stats_bytes(N);
@@ -500,33 +454,40 @@ int gpfq_layer_alphabet_from_kernel(const float *W, int64_t n, double alphabet_s
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_layer_alphabet_from_kernel");
 }
 
-static gpfq::PipeArgs dense_layer_probe(int64_t N, int64_t m, int64_t C, const HostAlphabet &H)
+// The answers of gpfq_dense_layer_supported / _workspace_bytes under the caller's snapshot (dense_layer_impl: one call, one reading)
+static bool dense_layer_supported(int64_t N, int64_t m, int64_t C, const double *unit_alphabet, int M, const gpfq::Options &o)
 {
+    if (N < 1 || m < 1 || C < 1 || !unit_alphabet || M < 1 || M > 64) return false;
+    HostAlphabet H;
+    if (unit_alphabet_arg(unit_alphabet, M, &H) != GPFQ_OK) return false;
+    // exactly the rows and alphabets gpfq_quantize_neurons gives the block-pipelined kernel by default
+    const bool forced_old = o.lanes_per_neuron != 0 || o.waves_per_neuron != 0 || o.onchip_mode != 1 || o.pipe == 0 || o.pipe == 1;
+    if (forced_old || !(m > 256 && m <= GPFQ_ONCHIP_MAX_M)) return false;
     gpfq::PipeArgs pa{};
-    pa.A = H.A; pa.N = N; pa.m = m; pa.C = C;
-    return pa;
+    pa.A = H.A; pa.N = N; pa.m = m; pa.C = C; pa.opt = o;
+    return gpfq::blk_supported(pa);
+}
+
+static size_t dense_layer_workspace_bytes(int64_t N, int64_t m, int64_t C, const gpfq::Options &o)
+{
+    if (N < 0 || m < 0 || C < 0) return 0;
+    return onchip_workspace_bytes(N, m, C, o) + al256((size_t)N * sizeof(float));      // (+ the row norms when the caller passes none)
 }
 
 int gpfq_dense_layer_supported(int64_t N, int64_t m, int64_t C, const double *unit_alphabet, int M)
 {
-    if (N < 1 || m < 1 || C < 1 || !unit_alphabet || M < 1 || M > 64) return 0;
-    HostAlphabet H;
-    if (unit_alphabet_arg(unit_alphabet, M, &H) != GPFQ_OK) return 0;
-    // exactly the rows and alphabets gpfq_quantize_neurons gives the block-pipelined kernel by default
-    const bool forced_old = g_lpn != 0 || g_wpn != 0 || g_onchip_mode != 1 || g_pipe == 0 || g_pipe == 1;
-    if (forced_old || !(m > 256 && m <= GPFQ_ONCHIP_MAX_M)) return 0;
-    return gpfq::blk_supported(dense_layer_probe(N, m, C, H)) ? 1 : 0;
+    return dense_layer_supported(N, m, C, unit_alphabet, M, gpfq::options_snapshot()) ? 1 : 0;
 }
 
 int gpfq_dense_layer_keras_out_supported(int64_t N, int64_t m, int64_t C, const double *unit_alphabet, int M)
 {
-    return gpfq_dense_layer_supported(N, m, C, unit_alphabet, M) && gpfq::blk_keras_out_supported(m, C) ? 1 : 0;
+    const gpfq::Options o = gpfq::options_snapshot();
+    return dense_layer_supported(N, m, C, unit_alphabet, M, o) && gpfq::blk_keras_out_supported(m, C, o) ? 1 : 0;
 }
 
 size_t gpfq_dense_layer_workspace_bytes(int64_t N, int64_t m, int64_t C)
 {
-    if (N < 0 || m < 0 || C < 0) return 0;
-    return onchip_workspace_bytes(N, m, C) + al256((size_t)N * sizeof(float));      // (+ the row norms when the caller passes none)
+    return dense_layer_workspace_bytes(N, m, C, gpfq::options_snapshot());
 }
 
 // phase 0: the whole layer call; 1: the alphabet-independent half (status block, row norms, record pre-pass); 2: the alphabet-dependent half
@@ -546,19 +507,20 @@ static int dense_layer_impl(int phase, const float *X, const float *Xq, int64_t 
     if (!X || !Xq) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (phase != 1 && (!W || !dev_alphabet)) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (ld < m) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ld=%lld < m=%lld", (long long)ld, (long long)m);
+    const gpfq::Options o = gpfq::options_snapshot();
     if (phase != 1) {
         if (ldc < c_lo + C) return fail(GPFQ_ERR_INVALID_ARG, "kernel pitch ldc=%lld < c_lo + C=%lld", (long long)ldc, (long long)(c_lo + C));
         if (out_layout != GPFQ_LAYOUT_NEURON_MAJOR && out_layout != GPFQ_LAYOUT_KERAS) return fail(GPFQ_ERR_INVALID_ARG, "unknown output layout %d", out_layout);
         if (out_layout == GPFQ_LAYOUT_KERAS && ldo < c_lo + C) return fail(GPFQ_ERR_INVALID_ARG, "output pitch ldo=%lld < c_lo + C=%lld", (long long)ldo, (long long)(c_lo + C));
-        if (out_layout == GPFQ_LAYOUT_KERAS && ldo != 1 && !gpfq::blk_keras_out_supported(m, C))
+        if (out_layout == GPFQ_LAYOUT_KERAS && ldo != 1 && !gpfq::blk_keras_out_supported(m, C, o))
             return fail(GPFQ_ERR_UNSUPPORTED, "the kernel of this shape (m=%lld, C=%lld) writes neuron-major outputs only (gpfq_dense_layer_keras_out_supported): "
                                               "ask for GPFQ_LAYOUT_NEURON_MAJOR and lay them out with gpfq_assemble_kernel_device", (long long)m, (long long)C);
     }
-    if (!gpfq_dense_layer_supported(N, m, C, unit_alphabet, M))
+    if (!dense_layer_supported(N, m, C, unit_alphabet, M, o))
         return fail(GPFQ_ERR_UNSUPPORTED, "no block-pipelined kernel for N=%lld m=%lld C=%lld M=%d (gpfq_dense_layer_supported): use gpfq_quantize_neurons with a host alphabet",
                     (long long)N, (long long)m, (long long)C, M);
-    if (!workspace || (uintptr_t)workspace % 16 != 0 || workspace_bytes < gpfq_dense_layer_workspace_bytes(N, m, C))
-        return fail(GPFQ_ERR_WORKSPACE, "%s needs %zu aligned workspace bytes", what, gpfq_dense_layer_workspace_bytes(N, m, C));
+    if (!workspace || (uintptr_t)workspace % 16 != 0 || workspace_bytes < dense_layer_workspace_bytes(N, m, C, o))
+        return fail(GPFQ_ERR_WORKSPACE, "%s needs %zu aligned workspace bytes", what, dense_layer_workspace_bytes(N, m, C, o));
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = hipSuccess;
     float *n32_out = nullptr;
@@ -566,7 +528,7 @@ static int dense_layer_impl(int phase, const float *X, const float *Xq, int64_t 
         // the call's counter block (exact fallbacks, cluster timeout, alphabet word) is zeroed with the row norms when they are formed here
         // (launch_blk: inside the record pre-pass, or by the row-norm kernel in front of it)
         if (!nrm32) {
-            n32_out = reinterpret_cast<float *>(static_cast<char *>(workspace) + onchip_workspace_bytes(N, m, C));
+            n32_out = reinterpret_cast<float *>(static_cast<char *>(workspace) + onchip_workspace_bytes(N, m, C, o));
         } else {
             e = hipMemsetAsync(workspace, 0, 64, s);
             if (e != hipSuccess) return hip_fail(e, what);
@@ -577,7 +539,7 @@ static int dense_layer_impl(int phase, const float *X, const float *Xq, int64_t 
     pa.Wt = W ? W + c_lo : nullptr; pa.ldw = 1; pa.ldt = ldc;     // the Keras kernel itself: neuron j's weight of step t is W[t][c_lo + j]
     pa.A = H.A; pa.N = N; pa.m = m; pa.C = C;
     pa.resid = resid; pa.u_out = nullptr;
-    pa.ts_override = g_tile_steps; pa.variant = g_variant >> 4;
+    pa.opt = o;
     if (out_layout == GPFQ_LAYOUT_KERAS) {
         pa.qidx = qidx ? qidx + c_lo : nullptr; pa.Qt = Q ? Q + c_lo : nullptr;
         pa.o_sj = 1; pa.o_st = ldo;
@@ -592,7 +554,7 @@ static int dense_layer_impl(int phase, const float *X, const float *Xq, int64_t 
     if (phase != 1) gpfq::note_dense_kernel("gpfq_blk_kernel (4 to 11 sweep wavefronts + 1 decision wavefront per workgroup, blocks of steps per slot)");
     e = gpfq::launch_blk(pa, s);
     if (e != hipSuccess) return hip_fail(e, what);
-    return (g_sync_errors && phase != 1) ? gpfq_call_status(workspace, stream) : GPFQ_OK;
+    return (o.sync_errors && phase != 1) ? gpfq_call_status(workspace, stream) : GPFQ_OK;
 }
 
 int gpfq_quantize_dense_layer(const float *X, const float *Xq, int64_t ld, const float *nrm32,
@@ -675,8 +637,8 @@ int gpfq_quantize_neurons_gram(const float *X, const float *Xq, int64_t ld, floa
     a.N = N; a.m = m; a.C = C; a.qidx = static_cast<int8_t *>(qidx); a.Qt = Qt; a.resid = resid; a.uncertified = uncertified;
     a.workspace = workspace;
     a.nrm32_out = compute_norms ? nrm32 : nullptr;
-    a.slack = std::ldexp(1.0, g_gram_slack_log2);
-    a.variant = g_variant;
+    a.opt = gpfq::options_snapshot();
+    a.slack = std::ldexp(1.0, a.opt.gram_slack_log2);
     // (noted like every other dense launch: a caller that asks gpfq_last_dense_kernel whether a deferred status exists -- the cluster
     //  form's -- must not see the name of an earlier call's kernel)
     gpfq::note_dense_kernel("gpfq_gram_* (Gram records + certified scalar recurrence)");
@@ -934,22 +896,28 @@ int gpfq_quantize_conv1x1(const float *act_q, int64_t n, int64_t H, int64_t W, i
 
 static size_t al256c(size_t x) { return (x + 255) & ~(size_t)255; }
 
-size_t gpfq_conv_channels_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw,
-                                          int rh, int rw, int same_padding, int64_t F, int want_resid)
+static size_t conv_channels_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw,
+                                           int rh, int rw, int same_padding, int64_t F, int want_resid, const gpfq::Options &o)
 {
     const int64_t oh = gpfq_patch_out_dim(H, kh, sh, rh, same_padding), ow = gpfq_patch_out_dim(W, kw, sw, rw, same_padding);
     const int64_t cols = n * oh * ow;
     const int64_t K = (int64_t)kh * kw;
     if (cols <= 0 || K <= 0 || F < 0 || nch < 0) return 0;
-    if (!want_resid && g_conv_fused && gpfq::gram_image_supported(n, H, W, kh, kw, sh, sw, rh, rw, same_padding))
+    if (!want_resid && o.conv_fused && gpfq::gram_image_supported(n, H, W, kh, kw, sh, sw, rh, rw, same_padding))
         return gpfq::gram_image_workspace_bytes(nch, F);
-    if (!want_resid && g_conv_fused && gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow)) {
+    if (!want_resid && o.conv_fused && gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow)) {
         size_t b = al256c(gpfq::gram_conv_workspace_bytes(K, nch, F, cols));
         if (!same_padding && gpfq::gram_s2_supported(n, H, W, kh, kw, sh, sw, rh, rw, 0, 0, nch)) b += gpfq::gram_s2_workspace_bytes(n, H, W, nch);
         return b;
     }
     const int64_t ldp = (cols + 3) & ~(int64_t)3;
     return 2 * al256c((size_t)K * ldp * sizeof(float)) + al256c((size_t)K * sizeof(float)) + gpfq::gram_workspace_bytes(K, cols, F);
+}
+
+size_t gpfq_conv_channels_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw,
+                                          int rh, int rw, int same_padding, int64_t F, int want_resid)
+{
+    return conv_channels_workspace_bytes(n, H, W, nch, kh, kw, sh, sw, rh, rw, same_padding, F, want_resid, gpfq::options_snapshot());
 }
 
 // phase 0: the whole channel loop; 1: Gram records only (-> records, negflags); 2: decide from given records
@@ -977,21 +945,21 @@ static int conv_channels_impl(int phase, double *records, int32_t *negflags,
     if (!act_w || !act_q) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (phase != 1 && (!Wt || !qidx || !Qt || !uncertified)) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (phase && resid) return fail(GPFQ_ERR_UNSUPPORTED, "residual norms need the whole call");
-    const size_t need = gpfq_conv_channels_workspace_bytes(n, H, W, nch, kh, kw, sh, sw, rh, rw, same_padding, F, resid != nullptr);
+    const gpfq::Options o = gpfq::options_snapshot();
+    const size_t need = conv_channels_workspace_bytes(n, H, W, nch, kh, kw, sh, sw, rh, rw, same_padding, F, resid != nullptr, o);
     if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16 != 0)
         return fail(GPFQ_ERR_WORKSPACE, "conv channel loop needs %zu aligned workspace bytes", need);
-    if (pix > 1 && !(same_padding == 0 && !resid && !phase && g_conv_fused && gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow) &&
+    if (pix > 1 && !(same_padding == 0 && !resid && !phase && o.conv_fused && gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow) &&
                      gpfq::gram_s2_supported(n, H, W, kh, kw, sh, sw, rh, rw, 0, 0, nch)))
         return fail(GPFQ_ERR_UNSUPPORTED, "NHWC activations: only the 7x7 / stride 2 / VALID shift-sum form reads them (gpfq_conv_channels_nhwc_supported)");
-    if (pix == 1 && !resid && g_conv_fused && gpfq::gram_image_supported(n, H, W, kh, kw, sh, sw, rh, rw, same_padding)) {
+    if (pix == 1 && !resid && o.conv_fused && gpfq::gram_image_supported(n, H, W, kh, kw, sh, sw, rh, rw, same_padding)) {
         // 3x3 / stride 1: Gram matrices of every channel straight from the planes, one batched decide launch
         gpfq::ImageGramArgs g;
         g.act_w = act_w; g.act_q = act_q; g.n = n; g.H = H; g.W = W; g.nch = nch; g.pad = same_padding ? 1 : 0;
         g.Wt = Wt; g.A = A; g.big = HA.big(); g.F = F; g.qidx = qidx; g.Qt = Qt; g.uncertified = uncertified;
         g.workspace = workspace;
-        g.slack = std::ldexp(1.0, g_gram_slack_log2);
-        g.variant = g_conv_strip;
-        g.shift_form = g_conv_shift;
+        g.slack = std::ldexp(1.0, o.gram_slack_log2);
+        g.opt = o;
         g.phase = phase; g.records = records; g.negflags = negflags;
         hipError_t e = gpfq::launch_gram_image(g, static_cast<hipStream_t>(stream));
         return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_quantize_conv_channels(fused)");
@@ -1004,15 +972,15 @@ static int conv_channels_impl(int phase, double *records, int32_t *negflags,
         pad_top = (int)(th / 2);
         pad_left = (int)(tw / 2);
     }
-    if (!resid && g_conv_fused && gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow)) {
+    if (!resid && o.conv_fused && gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow)) {
         // any other shape: the tile kernel gathers its patch rows from the planes (implicit im2col)
         gpfq::ConvGramArgs g;
         g.act_w = act_w; g.act_q = act_q; g.n = n; g.H = H; g.W = W; g.nch = nch;
         g.kh = kh; g.kw = kw; g.sh = sh; g.sw = sw; g.rh = rh; g.rw = rw; g.pt = pad_top; g.pl = pad_left; g.oh = oh; g.ow = ow;
         g.Wt = Wt; g.A = A; g.big = HA.big(); g.F = F; g.qidx = qidx; g.Qt = Qt; g.uncertified = uncertified;
         g.workspace = workspace;
-        g.slack = std::ldexp(1.0, g_gram_slack_log2);
-        g.variant = g_variant;
+        g.slack = std::ldexp(1.0, o.gram_slack_log2);
+        g.opt = o;
         g.phase = phase; g.records = records; g.negflags = negflags; g.pix = pix;
         if (pad_top == 0 && pad_left == 0 && gpfq::gram_s2_supported(n, H, W, kh, kw, sh, sw, rh, rw, pad_top, pad_left, nch))
             g.s2_part = reinterpret_cast<double *>(static_cast<char *>(workspace) + al256c(gpfq::gram_conv_workspace_bytes(K, nch, F, cols)));
@@ -1041,8 +1009,8 @@ static int conv_channels_impl(int phase, double *records, int32_t *negflags,
         a.qidx = HA.at(qidx, c * F * K); a.Qt = Qt + c * F * K; a.resid = resid ? resid + c * F : nullptr;
         a.uncertified = uncertified + c * F;
         a.workspace = ws;
-        a.slack = std::ldexp(1.0, g_gram_slack_log2);
-        a.variant = g_variant;
+        a.slack = std::ldexp(1.0, o.gram_slack_log2);
+        a.opt = o;
         e = gpfq::launch_gram(a, s);
         if (e != hipSuccess) return hip_fail(e, "gpfq_quantize_conv_channels(gram)");
     }
@@ -1051,13 +1019,15 @@ static int conv_channels_impl(int phase, double *records, int32_t *negflags,
 
 int gpfq_conv3x3_nhwc_supported(int64_t n, int64_t H, int64_t W, int64_t nch)
 {
-    return g_conv_fused && g_conv_nhwc && gpfq::gram_image_nhwc_supported(n, H, W, nch) ? 1 : 0;
+    const gpfq::Options o = gpfq::options_snapshot();
+    return o.conv_fused && o.conv_nhwc && gpfq::gram_image_nhwc_supported(n, H, W, nch, o) ? 1 : 0;
 }
 
 size_t gpfq_conv3x3_nhwc_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch, int64_t F)
 {
-    if (!gpfq::gram_image_nhwc_supported(n, H, W, nch) || F < 0) return 0;
-    return gpfq::gram_image_nhwc_workspace_bytes(n, H, W, nch, F);
+    const gpfq::Options o = gpfq::options_snapshot();
+    if (!gpfq::gram_image_nhwc_supported(n, H, W, nch, o) || F < 0) return 0;
+    return gpfq::gram_image_nhwc_workspace_bytes(n, H, W, nch, F, o);
 }
 
 int gpfq_quantize_conv3x3_nhwc(const float *act_w, const float *act_q, int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t c_lo, int64_t nch,
@@ -1069,9 +1039,10 @@ int gpfq_quantize_conv3x3_nhwc(const float *act_w, const float *act_q, int64_t n
     int rc = make_alphabet(alphabet, M, zero_idx, &HA);
     if (rc != GPFQ_OK) return rc;
     if (nch == 0 || F == 0) return GPFQ_OK;
-    if (!gpfq::gram_image_nhwc_supported(n, H, W, nch)) return fail(GPFQ_ERR_UNSUPPORTED, "NHWC form needs images of 4 x 4 or more and 32+ channels");
+    const gpfq::Options o = gpfq::options_snapshot();
+    if (!gpfq::gram_image_nhwc_supported(n, H, W, nch, o)) return fail(GPFQ_ERR_UNSUPPORTED, "NHWC form needs images of 4 x 4 or more and 32+ channels");
     if (!act_w || !act_q || !Wt || !qidx || !Qt || !uncertified) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
-    const size_t need = gpfq_conv3x3_nhwc_workspace_bytes(n, H, W, nch, F);
+    const size_t need = gpfq::gram_image_nhwc_workspace_bytes(n, H, W, nch, F, o);
     if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16 != 0)
         return fail(GPFQ_ERR_WORKSPACE, "NHWC conv call needs %zu aligned workspace bytes", need);
     gpfq::ImageGramArgs g;
@@ -1079,7 +1050,8 @@ int gpfq_quantize_conv3x3_nhwc(const float *act_w, const float *act_q, int64_t n
     g.n = n; g.H = H; g.W = W; g.nch = nch; g.pad = 1;
     g.Wt = Wt; g.A = HA.A; g.big = HA.big(); g.F = F; g.qidx = static_cast<int8_t *>(qidx); g.Qt = Qt; g.uncertified = uncertified;
     g.workspace = workspace;
-    g.slack = std::ldexp(1.0, g_gram_slack_log2);
+    g.slack = std::ldexp(1.0, o.gram_slack_log2);
+    g.opt = o;
     hipError_t e = gpfq::launch_gram_image_nhwc(g, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_quantize_conv3x3_nhwc");
 }
@@ -1090,7 +1062,7 @@ int gpfq_conv_records_supported(int64_t n, int64_t H, int64_t W, int64_t nch, in
     if (n <= 0 || H <= 0 || W <= 0 || nch <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || rh <= 0 || rw <= 0) return 0;
     const int64_t oh = gpfq_patch_out_dim(H, kh, sh, rh, same_padding), ow = gpfq_patch_out_dim(W, kw, sw, rw, same_padding);
     const int64_t cols = n * oh * ow, K = (int64_t)kh * kw;
-    if (cols <= 0 || K > GPFQ_GRAM_MAX_N || cols >= (1LL << 30) || !g_conv_fused) return 0;
+    if (cols <= 0 || K > GPFQ_GRAM_MAX_N || cols >= (1LL << 30) || !gpfq::options_snapshot().conv_fused) return 0;
     return (gpfq::gram_image_supported(n, H, W, kh, kw, sh, sw, rh, rw, same_padding) ||
             gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow)) ? 1 : 0;
 }
@@ -1107,7 +1079,8 @@ int gpfq_quantize_conv_channels(const float *act_w, const float *act_q, int64_t 
 
 int gpfq_conv_channels_nhwc_supported(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding)
 {
-    if (n <= 0 || H <= 0 || W <= 0 || nch <= 0 || same_padding || !g_conv_fused || !g_conv_planes_free) return 0;
+    const gpfq::Options o = gpfq::options_snapshot();
+    if (n <= 0 || H <= 0 || W <= 0 || nch <= 0 || same_padding || !o.conv_fused || !o.conv_planes_free) return 0;
     const int64_t oh = gpfq_patch_out_dim(H, kh, sh, rh, 0), ow = gpfq_patch_out_dim(W, kw, sw, rw, 0);
     if ((int64_t)kh * kw > GPFQ_GRAM_MAX_N || n * oh * ow >= (1LL << 30)) return 0;
     return gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow) && gpfq::gram_s2_supported(n, H, W, kh, kw, sh, sw, rh, rw, 0, 0, nch) ? 1 : 0;

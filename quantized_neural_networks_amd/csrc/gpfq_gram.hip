@@ -1000,7 +1000,7 @@ hipError_t launch_gram_decide(const double *gram, const float *nrm32, const floa
 hipError_t launch_gram(const GramArgs &a, hipStream_t stream)
 {
     const int64_t nchunks = (a.m + kGramCH - 1) / kGramCH;
-    const bool mfma = gram_mfma_supported(a.X, a.Xq, a.ld, a.N) && !(a.variant & 4);     // long walks: matrix cores
+    const bool mfma = gram_mfma_supported(a.X, a.Xq, a.ld, a.N) && !(a.opt.variant & 4);     // long walks: matrix cores
     const int64_t nblocks = gram_blocks(a.N, a.m), nparts = mfma ? gram_mfma_walkers(a.N, a.m) : gram_parts(a.N, a.m);
     const int64_t rchunks = (a.m + 1023) / 1024;
     const int64_t rec = gram_record(a.N);

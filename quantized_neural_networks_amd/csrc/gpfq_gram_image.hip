@@ -17,7 +17,6 @@
 // consecutive output positions of one row from a 3 x (S+2) register window, and the two wavefronts of a
 // pair own the columns s in {0,3,5,7,8} and {1,2,4,6} of the record (49 + 50 sums), which keeps a wavefront
 // under 128 accumulator registers and two of them resident per SIMD.
-#include <atomic>
 #include <type_traits>
 
 #include "gpfq_device.hpp"
@@ -762,9 +761,9 @@ hipError_t launch_gram_image(const ImageGramArgs &a, hipStream_t stream)
     // images (tools/conv3x3_probe.py, whole layer): 32 x 32, 32 channels: 1.93 -> 1.49 ms; 24 x 24: 1.70 -> 1.50; 20 x 20: 2.24 ->
     // 2.02; 16 x 16 loses; 3 channels at 32 x 32 (hundreds of short workgroups per channel, each with its class sums to reduce):
     // 0.34 -> 0.50.  So: from 20 x 20 up, with 8 channels or more in the shard.
-    // shift_form = 2 forces it for every size it can take (tests).
-    const bool shift = a.shift_form && (a.shift_form == 2 || (a.H >= 20 && a.W >= 20 && a.nch >= 8)) && image_plan(a.n, a.H, a.W, a.pad, a.variant, &p, &S, &lds, true);
-    if (!shift && !image_plan(a.n, a.H, a.W, a.pad, a.variant, &p, &S, &lds)) return hipErrorInvalidValue;
+    // option conv_shift = 2 forces it for every size it can take (tests).
+    const bool shift = a.opt.conv_shift && (a.opt.conv_shift == 2 || (a.H >= 20 && a.W >= 20 && a.nch >= 8)) && image_plan(a.n, a.H, a.W, a.pad, a.opt.conv_strip, &p, &S, &lds, true);
+    if (!shift && !image_plan(a.n, a.H, a.W, a.pad, a.opt.conv_strip, &p, &S, &lds)) return hipErrorInvalidValue;
     p.act_w = a.act_w; p.act_q = a.act_q; p.same_act = a.act_w == a.act_q;
     // one round of the chip: as many workgroups as are co-resident
     const void *fn = shift ? (S == 4 ? (const void *)gpfq_gram_shift_kernel<4, false> : S == 2 ? (const void *)gpfq_gram_shift_kernel<2, false>
@@ -846,20 +845,17 @@ hipError_t launch_gram_image(const ImageGramArgs &a, hipStream_t stream)
 }
 
 // ---- NHWC entry: 3 x 3, stride 1, SAME, all channels of the shard in one launch chain ----
-static std::atomic<int> g_nhwc_halves{1};              // shards of <= 32 channels: lanes 32-63 walk the second half of the images (option conv_nhwc_halves)
-void image_set_nhwc_halves(int on) { g_nhwc_halves.store(on ? 1 : 0, std::memory_order_relaxed); }
-static std::atomic<int> g_nhwc_slots{8192};            // workgroups of a launch (option conv_nhwc_slots: experiment switch)
-void image_set_nhwc_slots(int n) { g_nhwc_slots.store(n < 256 ? 256 : (n > 65536 ? 65536 : n), std::memory_order_relaxed); }
-// Image groups of a shard of nch channels over n images: the largest G in {16, 8, 4, 2} with nch <= 64 / G that divides n (1: none)
-static int nhwc_image_groups(int64_t n, int64_t nch)
+// Image groups of a shard of nch channels over n images: the largest G in {16, 8, 4, 2} with nch <= 64 / G that divides n (1: none, or
+// option conv_nhwc_halves = 0)
+static int nhwc_image_groups(int64_t n, int64_t nch, const Options &opt)
 {
-    if (!g_nhwc_halves.load(std::memory_order_relaxed)) return 1;
+    if (!opt.conv_nhwc_halves) return 1;
     for (int g = 16; g >= 2; g >>= 1)
         if (nch * g <= 64 && n % g == 0 && n >= g) return g;
     return 1;
 }
 
-static void nhwc_slots(int64_t n, int64_t H, int64_t W, int64_t nch, NhwcParams &p)
+static void nhwc_slots(int64_t n, int64_t H, int64_t W, int64_t nch, const Options &opt, NhwcParams &p)
 {
     // Slots per class in proportion to its work (items x row steps per item x requests per step), about 8192 one-wavefront
     // workgroups in the launch -- four times what the chip holds at once: a workgroup belongs to one class and the classes' costs
@@ -868,7 +864,7 @@ static void nhwc_slots(int64_t n, int64_t H, int64_t W, int64_t nch, NhwcParams 
     // slots, 2.36 / 1.27 / 0.84 / 0.65 with 4096, 1.93 / 1.08 / 0.69 / 0.49 with 8192, 2.14 / 1.06 / 0.65 / 0.43 with 16384); the
     // partial sums -- 27 doubles per slot and channel, 113 MB per launch -- are what more slots cost (two-stage combine below)
     const int64_t groups = (nch + 63) / 64;
-    int64_t total = g_nhwc_slots.load(std::memory_order_relaxed) / groups;
+    int64_t total = opt.conv_nhwc_slots / groups;
     if (total < 256) total = 256;
     const int64_t ns_mid = (W - 2 + kNhwcStrip - 1) / kNhwcStrip;
     double work[9];
@@ -893,21 +889,21 @@ static void nhwc_slots(int64_t n, int64_t H, int64_t W, int64_t nch, NhwcParams 
     p.nslots = p.slot_off[9];
 }
 
-bool gram_image_nhwc_supported(int64_t n, int64_t H, int64_t W, int64_t nch)
+bool gram_image_nhwc_supported(int64_t n, int64_t H, int64_t W, int64_t nch, const Options &opt)
 {
     // (64 channels fill the lanes of a wavefront; with 32 -- half of them idle -- this form still beats planes + the LDS-staged kernel since
     //  round 3: the CIFAR10 CNN's 32 -> 32 @32x32 layer on 5008 images 1.55 -> 0.95 ms, 32 -> 64 @16x16 0.66 -> 0.46)
     // narrower shards: only where the image groups put their lanes to work (an image count the group count divides)
     // (and from 8 channels up: 3 -> 32 @32x32 on 5008 images takes 0.45 ms here against 0.34 through planes -- sixteen groups' partials and
     //  4-byte requests 12 bytes apart --, 8 -> 8 @56x56 0.74 against 0.96, 16 -> 32 @32x32 0.56 against 0.89)
-    if (nch < 32 && (nch < 8 || nhwc_image_groups(n, nch) * nch < 32)) return false;
+    if (nch < 32 && (nch < 8 || nhwc_image_groups(n, nch, opt) * nch < 32)) return false;
     return n > 0 && H >= 4 && W >= 4 && nch >= 1 && n * H * W < (1LL << 30) && H < 32768 && W < 32768;
 }
 
-size_t gram_image_nhwc_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch, int64_t F)
+size_t gram_image_nhwc_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch, int64_t F, const Options &opt)
 {
     NhwcParams p{};
-    nhwc_slots(n, H, W, nch, p);
+    nhwc_slots(n, H, W, nch, opt, p);
     size_t b = 0;
     b += al256i((size_t)nch * p.nslots * (nch <= 4 ? 16 : nch <= 8 ? 8 : nch <= 16 ? 4 : nch <= 32 ? 2 : 1) * kShiftN * sizeof(double));
     b += al256i((size_t)nch * kRec9 * sizeof(double));
@@ -922,16 +918,16 @@ size_t gram_image_nhwc_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t 
 hipError_t launch_gram_image_nhwc(const ImageGramArgs &a, hipStream_t stream)
 {
     if (a.nch == 0 || a.F == 0) return hipSuccess;
-    if (!gram_image_nhwc_supported(a.n, a.H, a.W, a.nch) || a.pad != 1 || a.nhwc_cin < a.nch) return hipErrorInvalidValue;
+    if (!gram_image_nhwc_supported(a.n, a.H, a.W, a.nch, a.opt) || a.pad != 1 || a.nhwc_cin < a.nch) return hipErrorInvalidValue;
     NhwcParams p{};
     p.act_w = a.act_w; p.act_q = a.act_q; p.cin = a.nhwc_cin;
     p.n = (int)a.n; p.H = (int)a.H; p.W = (int)a.W; p.nch = (int)a.nch;
     // narrow shards: the lanes a shard of at most 32 / 16 / 8 / 4 channels leaves idle walk further G-ths of the images
-    p.halves = nhwc_image_groups(a.n, a.nch);
+    p.halves = nhwc_image_groups(a.n, a.nch, a.opt);
     if ((uint64_t)a.n * a.H * a.W * a.nhwc_cin * sizeof(float) >= (1ull << 32)) p.halves = 1;      // (the group offset is a 32-bit lane offset)
     p.n_walk = (int)(a.n / p.halves);
     p.half_off = p.halves > 1 ? (unsigned)((uint64_t)p.n_walk * a.H * a.W * a.nhwc_cin * sizeof(float)) : 0u;
-    nhwc_slots(p.n_walk, a.H, a.W, a.nch, p);
+    nhwc_slots(p.n_walk, a.H, a.W, a.nch, a.opt, p);
     char *ws = static_cast<char *>(a.workspace);
     p.part = reinterpret_cast<double *>(ws);        ws += al256i((size_t)a.nch * p.nslots * (a.nch <= 4 ? 16 : a.nch <= 8 ? 8 : a.nch <= 16 ? 4 : a.nch <= 32 ? 2 : 1) * kShiftN * sizeof(double));
     double *gram = reinterpret_cast<double *>(ws);  ws += al256i((size_t)a.nch * kRec9 * sizeof(double));

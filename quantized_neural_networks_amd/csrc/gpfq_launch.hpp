@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "gpfq_device.hpp"
+#include "gpfq_options.hpp"
 
 namespace gpfq {
 
@@ -25,8 +26,6 @@ struct OnchipArgs {
     const RowStats *stats = nullptr;
     unsigned long long *fallback_count = nullptr;
     int mode = 0;          // 0 = exact flow, 1 = certified (needs stats)
-    int lpn = 0;           // lanes per neuron of the row-group kernel: 16/32/64, 1 = wave kernel, 0 = heuristic
-    int wpn = 0;           // wavefronts per neuron of the wide kernel (forced split), 0 = heuristic
     const float *Wt;
     int64_t ldw;
     AlphabetArg A;
@@ -36,9 +35,7 @@ struct OnchipArgs {
     float *Qt;
     double *resid;
     double *u_out;
-    int ts_override = 0;   // tuning hooks (bench/tests); 0 = heuristic
-    int nw_override = 0;
-    int variant = 0;
+    Options opt;           // the call's snapshot (tile_steps, group_waves, lanes_per_neuron, waves_per_neuron, variant)
 };
 
 struct StreamArgs {
@@ -73,8 +70,7 @@ struct PipeArgs {
     double *u_out;
     void *workspace;                       // pipe_workspace_bytes(N, m), 16-byte aligned
     unsigned long long *fallback_count = nullptr;
-    int ts_override = 0;                   // tuning hook (bench/tests); 0 = heuristic
-    int variant = 0;                       // tuning / timing experiments (PipeK::flags)
+    Options opt;                           // the call's snapshot (tile_steps; variant >> 4: PipeK::flags / the block kernel's general form; blk_*)
     // Block form only (round 6, gpfq_quantize_dense_layer): the weights and the outputs in the layer's own (Keras) layout, the alphabet in
     // device memory.  Weight of neuron j at step t: Wt[j ldw + t ldt]; output element (j, t) at j o_sj + t o_st (o_st == 1: neuron-major
     // [C][N] whatever o_sj says).  dev_alpha != NULL: a DevAlphabet formed on the device (launch_alphabet_device) -- A then holds the UNIT
@@ -94,25 +90,9 @@ struct PipeArgs {
 // rad * unit[k]; dev_alphabet: GPFQ_DEVICE_ALPHABET_BYTES of device memory (a DevAlphabet).
 hipError_t launch_alphabet_device(const float *median32, double alphabet_scalar, const AlphabetArg &unit, void *dev_alphabet, hipStream_t stream);
 bool blk_supported(const PipeArgs &a);
-bool blk_keras_out_supported(int64_t m, int64_t C);   // PipeArgs::o_st != 1 is taken (the 16-neuron four-step shapes; elsewhere neuron-major + one assembly pass)
-size_t blk_workspace_bytes(int64_t N, int64_t m, int64_t C);   // (C: the cluster form's exchange buffers are per 16 neurons)
+bool blk_keras_out_supported(int64_t m, int64_t C, const Options &opt);   // PipeArgs::o_st != 1 is taken (the 16-neuron four-step shapes; elsewhere neuron-major + one assembly pass)
+size_t blk_workspace_bytes(int64_t N, int64_t m, int64_t C, const Options &opt);   // (C: the cluster form's exchange buffers are per 16 neurons)
 hipError_t launch_blk(const PipeArgs &a, hipStream_t stream);
-void blk_set_four_groups(int on);   // 4-neuron workgroups for layers of at most 1024 neurons (speed only)
-void blk_set_single_groups(int on); // 1-neuron workgroups for layers of at most 128 neurons (speed only)
-void blk_set_pair_groups(int on);   // 2-neuron workgroups for layers of at most 512 neurons (speed only)
-void blk_set_wide_groups(int on);   // 16-neuron workgroups for rows beyond 1024 samples (speed only)
-void blk_set_quad_groups(int on);   // four neuron groups x 1 / 2 neurons per lane for layers of at most 2048 neurons on rows of 257..1024 samples; 2 (default): every such layer, 1: 129..2048 neurons only, 0: off (speed only)
-void blk_set_quad_waves(int nw);    // sweep wavefronts of the four-group narrow shapes on rows of at most 768 samples: 0 (default) = by shape (seven for layers of at most 1024 neurons, else eight), 7 or 8 force it (speed only)
-void blk_set_cluster_nl(int v);     // cluster form: neurons per lane of a workgroup, 0 (default) = by width, 1 / 2 / 4 force it (speed only)
-void blk_set_cluster_map(int v);    // cluster form: workgroup id -> (cluster, slice): -1 (default) by the slice count, 0 = a cluster inside one XCD, 1 = consecutive ids (speed only)
-void blk_set_cluster(int v);        // cluster form (rows cut into 1024-sample slices over several workgroups, up to 16384 samples): 1 (default) = by shape, 0 = off, v >= 1024 = every row beyond v samples (speed only)
-void blk_set_prep_norms(int v);     // 1 (default): the dense-layer call's row norms formed inside the record pre-pass where bit-identical; 0: always by the row-norm kernel
-void blk_set_prep_run(int v);       // 1 (default): the record pre-pass in runs of eight records per workgroup; 0: one record per workgroup (same records)
-void blk_set_cluster768(int v);     // rows of 2049..3072 samples in layers wider than 2048 neurons as four 768-sample slices: -1 (default) yes, 8 / 11 force the sweep wavefronts, 0 = the classic one-step shape (speed only)
-void blk_set_chip_ok(int v);        // -1 (default): the cluster form asks the device whether it is the whole 8 x 32-CU chip; 0 / 1: forced (tests)
-void blk_set_cluster_timeout_ms(int v);  // cluster form: how long an exchange waits for a missing slice (default 3000 ms)
-void blk_set_cluster_fault(int v);  // tests: 1 = one slice never publishes (forces the timeout and the caller's fallback)
-void blk_set_sweep_waves(int nw);   // sweep wavefronts of the 16-neuron four-step shapes: 0 (default) = by shape (eleven for rows of 769..1024 samples, eight below), 8 or 11 force it (speed only)
 bool pipe_supported(const PipeArgs &a);
 size_t pipe_workspace_bytes(int64_t N, int64_t m);
 hipError_t launch_pipe(const PipeArgs &a, hipStream_t stream);
@@ -154,7 +134,7 @@ struct GramArgs {
     int32_t *uncertified;   // [C]: 1 = decision chain not certified, rerun through the exact path
     void *workspace;
     double slack = 1.0;     // multiplies the error bounds (tests)
-    int variant = 0;        // bit 2: records of long walks on the vector units instead of the matrix cores
+    Options opt;            // the call's snapshot (variant bit 2: records of long walks on the vector units instead of the matrix cores)
 };
 
 size_t gram_workspace_bytes(int64_t N, int64_t m, int64_t C);
@@ -218,9 +198,8 @@ struct ImageGramArgs {
     int32_t *uncertified;         // [nch][F]
     void *workspace;
     double slack = 1.0;
-    int variant = 0;              // tuning hook: forces the strip length (1, 2, 4)
+    Options opt;                  // the call's snapshot (conv_strip, conv_shift; conv_nhwc_halves, conv_nhwc_slots)
     int64_t nhwc_cin = 0;         // launch_gram_image_nhwc: act_w / act_q are NHWC tensors (offset to the shard's first channel) of this many channels
-    int shift_form = 1;           // SAME padding: shift sums (27 FMAs per position) instead of per-output-position records (99); 0 = never
     // phase 1: stop after the Gram records (written to `records` [nch][171] f64 and `negflags` [nch] i32);
     // phase 2: take the records from there instead of forming them (column-sharded multi-GPU runs sum them in between)
     int phase = 0;
@@ -243,7 +222,7 @@ struct ConvGramArgs {
     int32_t *uncertified;         // [nch][F]
     void *workspace;
     double slack = 1.0;
-    int variant = 0;        // bit 2: vector-unit tiles instead of the matrix cores for 16 < kh*kw <= 64
+    Options opt;            // the call's snapshot (variant bit 2: vector-unit tiles instead of the matrix cores for 16 < kh*kw <= 64; conv_s2)
     int phase = 0;          // as ImageGramArgs: 1 = records only, 2 = from records ([nch][K*K*2 + K] f64, [nch] i32)
     double *records = nullptr;
     int32_t *negflags = nullptr;
@@ -258,16 +237,13 @@ bool gram_s2_supported(int64_t n, int64_t H, int64_t W, int kh, int kw, int sh, 
 size_t gram_s2_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch);
 hipError_t launch_gram_s2(const float *act_w, const float *act_q, int64_t n, int64_t H, int64_t W, int64_t nch, double *part,
                           double *gram, float *nrm32, int *negflag, hipStream_t stream, int64_t pix = 1);
-void image_set_nhwc_halves(int on);  // NHWC 3x3 form, <= 32 channels: the idle half of a wavefront walks the second half of the images (speed only)
-void image_set_nhwc_slots(int n);    // NHWC 3x3 form: workgroups per launch (speed only)
-void conv_set_s2(int on);           // the shift-sum form for 7x7 / 2 layers (speed only; 0: the matrix-core kernel)
 
 bool gram_image_supported(int64_t n, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding);
 size_t gram_image_workspace_bytes(int64_t nch, int64_t F);
 hipError_t launch_gram_image(const ImageGramArgs &a, hipStream_t stream);
 // The same from NHWC activations (ImageGramArgs::nhwc_cin; 3 x 3 / stride 1 / SAME, phase 0 only): no channel-major copy
-bool gram_image_nhwc_supported(int64_t n, int64_t H, int64_t W, int64_t nch);
-size_t gram_image_nhwc_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch, int64_t F);
+bool gram_image_nhwc_supported(int64_t n, int64_t H, int64_t W, int64_t nch, const Options &opt);
+size_t gram_image_nhwc_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch, int64_t F, const Options &opt);
 hipError_t launch_gram_image_nhwc(const ImageGramArgs &a, hipStream_t stream);
 
 hipError_t launch_row_stats(const float *X, const float *Xq, int64_t N, int64_t m, int64_t ld, const float *nrm32,

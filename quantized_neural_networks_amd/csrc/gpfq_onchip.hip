@@ -268,8 +268,8 @@ static hipError_t launch_epl_ar(const OnchipArgs &a, const AlphabetT<64 * AR> &A
     // tile: as many steps as fit ~64 KiB of LDS for both matrices, a divisor of 64
     int ts = 64;
     while (ts > 1 && (size_t)2 * ts * MP * sizeof(float) > 64 * 1024) ts >>= 1;
-    if (a.ts_override > 0) ts = a.ts_override;
-    if (a.nw_override > 0) nw = a.nw_override;
+    if (a.opt.tile_steps > 0) ts = a.opt.tile_steps;
+    if (a.opt.group_waves > 0) nw = a.opt.group_waves;
     const size_t lds_bytes = (size_t)2 * ts * MP * sizeof(float);
     const bool vec4 = (a.ld % 4 == 0) && (a.m % 4 == 0) && ((uintptr_t)a.X % 16 == 0) && ((uintptr_t)a.Xq % 16 == 0);
     const unsigned grid = (unsigned)((a.C + nw - 1) / nw);
@@ -305,16 +305,16 @@ hipError_t launch_onchip(const OnchipArgs &a, hipStream_t stream)
     // ... or a layer too narrow to fill the chip with one or two neurons per wavefront: its steps are
     // latency-bound, and splitting a neuron over 2-4 wavefronts shortens them (round-1 sweep:
     // C = 512, m = 1024: 1.41 -> 1.11 ms per 1024 steps; m = 2048: 2.57 -> 1.45 ms)
-    const bool narrow = a.wpn == 0 && a.lpn == 0 && a.m >= 512 && a.C <= 1024;
-    if (a.wpn > 1 || a.m > 2048 || narrow) {
-        int W = a.wpn > 1 ? a.wpn : (int)((a.m + 1023) / 1024);
+    const bool narrow = a.opt.waves_per_neuron == 0 && a.opt.lanes_per_neuron == 0 && a.m >= 512 && a.C <= 1024;
+    if (a.opt.waves_per_neuron > 1 || a.m > 2048 || narrow) {
+        int W = a.opt.waves_per_neuron > 1 ? a.opt.waves_per_neuron : (int)((a.m + 1023) / 1024);
         if (narrow && a.m <= 2048) {
             // 4 (8 above 512 neurons) elements per lane, 2..4 wavefronts: multiples of 4 elements per lane keep the
             // register-prefetch mode of the wide kernel (round-1 sweep: m = 512, C = 128: 0.92 -> 0.77 us/step)
             W = (int)(a.m / (64 * (a.C > 512 ? 8 : 4)));
             W = W < 2 ? 2 : W > 4 ? 4 : W;
         }
-        if (a.wpn == 0 && a.m > 2048 && a.m <= 8192 && a.C <= 512) {
+        if (a.opt.waves_per_neuron == 0 && a.m > 2048 && a.m <= 8192 && a.C <= 512) {
             // few neurons on long rows leave most of the chip idle and a step is bound by the instructions each wavefront
             // spends around its sweep: 8 elements per lane over 8..16 wavefronts instead of 16 over half as many
             // (tools/wide_probe.py, one deciding wavefront per step: 2048 x 128, m = 5008: 3.29 -> 2.76 ms; m = 3000: 2.79 -> 2.32)
@@ -327,7 +327,7 @@ hipError_t launch_onchip(const OnchipArgs &a, hipStream_t stream)
         return launch_wide(a, W, stream);
     }
     if (a.mode == MODE_CERTIFIED && a.stats) {
-        int lpn = a.big ? 1 : a.lpn;         // 65..256 members: the wavefront-per-neuron kernel (4 alphabet registers per lane)
+        int lpn = a.big ? 1 : a.opt.lanes_per_neuron;         // 65..256 members: the wavefront-per-neuron kernel (4 alphabet registers per lane)
         if (lpn == 0) lpn = 32;                      // measured best on cfg2/cfg3-like layers (round-1 sweep over shapes)
         while (lpn >= 16 && lpn <= 64 && !rows_supported(a, lpn)) lpn *= 2;
         if (lpn >= 16 && lpn <= 64) {

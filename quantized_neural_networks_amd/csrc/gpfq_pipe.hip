@@ -571,7 +571,7 @@ static hipError_t launch_pipe_inst(const PipeArgs &a, const PipeShape &sh, hipSt
 {
     constexpr int NB = 4 * G;
     int ts = pipe_tile_steps(sh, a.N);
-    if (a.ts_override > 0 && a.ts_override < ts) ts = a.ts_override;
+    if (a.opt.tile_steps > 0 && a.opt.tile_steps < ts) ts = a.opt.tile_steps;
     const PipeLds L = pipe_lds(sh.mp, NB, ts);
     const unsigned grid = (unsigned)((a.C + NB - 1) / NB);
     auto *kern = gpfq_pipe_kernel<G, S>;
@@ -579,7 +579,7 @@ static hipError_t launch_pipe_inst(const PipeArgs &a, const PipeShape &sh, hipSt
     if (e != hipSuccess) return e;
     PipeK K;
     K.recs = static_cast<const char *>(a.workspace); K.X = a.X; K.Xq = a.Xq; K.ld = a.ld; K.Wt = a.Wt; K.ldw = a.ldw;
-    K.N = a.N; K.C = a.C; K.m = (int)a.m; K.TS = ts; K.M = a.A.M; K.zero_idx = a.A.zero_idx; K.flags = a.variant & 1;
+    K.N = a.N; K.C = a.C; K.m = (int)a.m; K.TS = ts; K.M = a.A.M; K.zero_idx = a.A.zero_idx; K.flags = (a.opt.variant >> 4) & 1;
     K.qidx = a.qidx; K.Qt = a.Qt; K.resid = a.resid; K.u_out = a.u_out; K.fallback_count = a.fallback_count;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * (kSweepWaves + 1)), (size_t)L.total, stream, K, a.A);
     return hipGetLastError();

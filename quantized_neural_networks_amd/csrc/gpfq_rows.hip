@@ -337,13 +337,13 @@ static hipError_t launch_rows_xqd(const OnchipArgs &a, hipStream_t stream)
     constexpr size_t per_elem = XQD ? 16 : 8;              // LDS bytes per staged element
     int ts = 64;
     while (ts > 1 && (size_t)ts * MP * per_elem > 128 * 1024) ts >>= 1;
-    if (a.ts_override > 0) ts = a.ts_override;
+    if (a.opt.tile_steps > 0) ts = a.opt.tile_steps;
     while (ts > 1 && (size_t)ts * MP * per_elem > 150 * 1024) ts >>= 1;
     const size_t lds_bytes = (size_t)ts * MP * per_elem + (size_t)kMaxGroupNeurons * ts * sizeof(float) + 16 * sizeof(double);
     // neurons per workgroup: 16 (smaller groups re-stage the same rows more often and measured slower
     // even on narrow layers; the tuning hook can still lower it)
     int gs = kMaxGroupNeurons;
-    if (a.nw_override > 0 && a.nw_override <= 16 && a.nw_override >= 64 / LPN && !(a.nw_override & (a.nw_override - 1))) gs = a.nw_override;
+    if (a.opt.group_waves > 0 && a.opt.group_waves <= 16 && a.opt.group_waves >= 64 / LPN && !(a.opt.group_waves & (a.opt.group_waves - 1))) gs = a.opt.group_waves;
     const bool vec4 = (a.ld % 4 == 0) && (a.m % 4 == 0) && ((uintptr_t)a.X % 16 == 0) && ((uintptr_t)a.Xq % 16 == 0);
     const unsigned grid = (unsigned)((a.C + gs - 1) / gs);
     hipError_t e = ensure_dynamic_lds((const void *)gpfq_rows_kernel<LPN, EPL, XQD>, lds_bytes);
@@ -357,7 +357,7 @@ static hipError_t launch_rows_xqd(const OnchipArgs &a, hipStream_t stream)
 template <int LPN, int EPL>
 static hipError_t launch_rows_inst(const OnchipArgs &a, hipStream_t stream)
 {
-    if (a.variant & 1) return launch_rows_xqd<LPN, EPL, false>(a, stream);
+    if (a.opt.variant & 1) return launch_rows_xqd<LPN, EPL, false>(a, stream);
     return launch_rows_xqd<LPN, EPL, true>(a, stream);
 }
 

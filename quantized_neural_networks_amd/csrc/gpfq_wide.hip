@@ -439,7 +439,7 @@ static hipError_t launch_wide_epl_ar(const OnchipArgs &a, const AlphabetT<64 * A
         // register-prefetch mode, one neuron per workgroup: faster than sharing LDS-staged rows between the
         // neurons of a workgroup at every shape measured (round-1 sweep of narrow layers), the rows come from L2 anyway
         const bool aligned = (a.ld % 4 == 0) && (a.m % 4 == 0) && ((uintptr_t)a.X % 16 == 0) && ((uintptr_t)a.Xq % 16 == 0);
-        if (aligned && !(a.variant & 2) && (EPL < 16 || W <= 8)) {
+        if (aligned && !(a.opt.variant & 2) && (EPL < 16 || W <= 8)) {
             hipLaunchKernelGGL((gpfq_wide_direct_kernel<EPL, true, AR>), dim3((unsigned)a.C), dim3(64 * W), 0, stream,
                                a.X, a.Xq, a.ld, a.nrm32, a.Wt, a.ldw, A, a.N, (int)a.m, a.C, W, 1,
                                qidx, a.Qt, a.resid, a.u_out);
@@ -448,7 +448,7 @@ static hipError_t launch_wide_epl_ar(const OnchipArgs &a, const AlphabetT<64 * A
     }
     int ts = 16;
     while (ts > 1 && (size_t)2 * ts * MP * sizeof(float) > 96 * 1024) ts >>= 1;
-    if (a.ts_override > 0 && (size_t)2 * a.ts_override * MP * sizeof(float) <= 150 * 1024) ts = a.ts_override;
+    if (a.opt.tile_steps > 0 && (size_t)2 * a.opt.tile_steps * MP * sizeof(float) <= 150 * 1024) ts = a.opt.tile_steps;
     const size_t lds_bytes = (size_t)2 * ts * MP * sizeof(float) + (size_t)2 * G * W * 2 * sizeof(double);
     const bool vec4 = (a.ld % 4 == 0) && (a.m % 4 == 0) && ((uintptr_t)a.X % 16 == 0) && ((uintptr_t)a.Xq % 16 == 0);
     const unsigned grid = (unsigned)((a.C + G - 1) / G);

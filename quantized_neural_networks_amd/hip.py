@@ -34,6 +34,7 @@ SYMBOLS = {
     "gpfq_last_dense_kernel": (ctypes.c_char_p, []),
     "gpfq_set_main_kernel_events": (_int, [_vp, _vp]),
     "gpfq_set_option": (_int, [ctypes.c_char_p, _int]),
+    "gpfq_get_option": (_int, [ctypes.c_char_p, ctypes.POINTER(_int)]),
     "gpfq_quantize_neurons": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _dp, _int, _int, _i64, _i64, _i64,
                                      _vp, _vp, _vp, _vp, _vp, _sz, _int, _vp]),
     "gpfq_call_status": (_int, [_vp, _vp]),
@@ -857,33 +858,45 @@ def cluster_timeouts(result):
     return 0 if ws is None or ws.numel() < 16 else int(ws[8:12].view(torch.int32).item())
 
 
-_OPTION_DEFAULTS = {"blk_cluster768": -1, "blk_prep_run": 1, "blk_prep_norms": 1, "blk_cluster": 1, "blk_cluster_nl": 0, "blk_cluster_map": -1, "blk_chip_ok": -1, "blk_cluster_timeout_ms": 3000,
-                    "blk_cluster_fault": 0, "sync_errors": 0}
-_options = {}
-
-
 def set_option(key, value):
     _check(load().gpfq_set_option(key.encode(), int(value)), f"gpfq_set_option({key})")
-    _options[key] = int(value)
 
 
-class option:
-    """`with hip.option(key, value):` -- a process-wide library option for the duration of a block, then back to what this binding last
-    set it to (or the library's default).  Results never depend on options, only which kernel runs."""
+def get_option(key):
+    """The library's stored (normalised) value of an option; setting it again changes nothing."""
+    v = ctypes.c_int()
+    _check(load().gpfq_get_option(key.encode(), ctypes.byref(v)), f"gpfq_get_option({key})")
+    return v.value
 
-    def __init__(self, key, value):
-        self.key, self.value = key, int(value)
+
+class options:
+    """`with hip.options(key=value, ...):` -- process-wide library options for the duration of a block, then back (in reverse order) to
+    what the library held on entry, whoever set that.  Results never depend on options, only which kernel runs."""
+
+    def __init__(self, **kv):
+        self.kv = {k: int(v) for k, v in kv.items()}
 
     def __enter__(self):
-        self.prev = _options.get(self.key, _OPTION_DEFAULTS.get(self.key))
-        if self.prev is None:
-            raise GpfqError(f"hip.option: no known default for '{self.key}'")
-        set_option(self.key, self.value)
+        self.prev = []
+        try:
+            for key, value in self.kv.items():
+                prev = get_option(key)
+                set_option(key, value)
+                self.prev.append((key, prev))
+        except BaseException:
+            self.__exit__()
+            raise
         return self
 
     def __exit__(self, *exc):
-        set_option(self.key, self.prev)
+        while self.prev:
+            set_option(*self.prev.pop())
         return False
+
+
+def option(key, value):
+    """`with hip.option(key, value):` -- hip.options for one key."""
+    return options(**{key: value})
 
 
 def msq_round(W, alphabet):

@@ -305,3 +305,139 @@ def test_round6_options_and_median_workspace(lib):
     fine = 4 * (2 * (1 << 15) + 2 * (1 << 16))
     assert int(lib.gpfq_median_abs_workspace_bytes_for(1 << 24)) == 128 + fine + 4 * 3 * 1024
     assert int(lib.gpfq_median_abs_workspace_bytes_for(1 << 24)) == int(lib.gpfq_median_abs_workspace_bytes_for(1000))   # (any kernel: a function of nothing but the form)
+
+
+# ---- the option surface (csrc/gpfq_options.hpp), stated here independently of the library's table ------------------------------------
+_FLAGS = ("onchip_mode", "blk_four_groups", "blk_wide_groups", "blk_pair_groups", "blk_single_groups", "blk_prep_norms", "blk_cluster_fault",
+          "sync_errors", "auto_gram", "conv_fused", "conv_nhwc", "conv_planes_free", "conv_s2", "conv_nhwc_halves")
+_OPTION_DEFAULTS = dict(
+    {k: 1 for k in ("onchip_mode", "auto_gram", "conv_fused", "conv_planes_free", "conv_nhwc", "conv_shift", "conv_s2", "conv_nhwc_halves",
+                    "blk_single_groups", "blk_four_groups", "blk_wide_groups", "blk_pair_groups", "blk_prep_run", "blk_prep_norms", "blk_cluster")},
+    blk_quad_groups=2, pipe=-1, blk_chip_ok=-1, blk_cluster768=-1, blk_cluster_map=-1, blk_cluster_timeout_ms=3000, conv_nhwc_slots=8192,
+    **{k: 0 for k in ("tile_steps", "group_waves", "lanes_per_neuron", "waves_per_neuron", "variant", "gram_slack_log2", "sync_errors",
+                      "blk_quad_waves", "blk_sweep_waves", "blk_cluster_nl", "blk_cluster_fault", "conv_strip")})
+# keys that reject: (values taken as given, values refused)
+_OPTION_SETS = {
+    "tile_steps": ((0, 1, 2, 4, 8, 16, 32, 64), (-1, 3, 48, 65, 128)),
+    "group_waves": ((0, 1, 16), (-1, 17)),
+    "pipe": ((-1, 0, 1, 2), (-2, 3)),
+    "blk_cluster_timeout_ms": ((1, 3000, 60000), (0, -5, 60001)),
+    "blk_cluster": ((0, 1, 1024, 4096, 1 << 20), (-1, 2, 500, 1023)),
+    "blk_quad_waves": ((0, 7, 8), (-1, 1, 6, 9, 11)),
+    "blk_sweep_waves": ((0, 8, 11), (-1, 7, 9, 10, 12)),
+    "waves_per_neuron": ((0, 2, 16), (-1, 17)),
+    "conv_shift": ((0, 1, 2), (-1, 3)),
+    "conv_strip": ((0, 1, 2, 4), (-1, 3, 8)),
+    "lanes_per_neuron": ((0, 1, 16, 32, 64), (-1, 2, 8, 48, 128)),
+}
+# keys that take anything: {given: stored}
+_OPTION_MAPS = dict(
+    {k: {0: 0, 1: 1, 2: 1, -1: 1, 77: 1} for k in _FLAGS},
+    variant={0: 0, 1: 1, 36: 36, -3: -3, 1 << 20: 1 << 20},
+    gram_slack_log2={0: 0, 40: 40, -60: -60},
+    blk_quad_groups={-1: 0, 0: 0, 1: 1, 2: 2, 3: 2, 7: 2},
+    blk_cluster_map={-1: -1, -9: -1, 0: 0, 1: 1, 5: 1},
+    blk_cluster768={-1: -1, 0: 0, 8: 8, 11: 11, 1: -1, 7: -1, -4: -1, 12: -1},
+    blk_prep_run={0: 0, 1: 1, 2: 1, 3: 1, 4: 4, 9: 9, 16: 16, 17: 1, -1: 1},
+    blk_chip_ok={-1: -1, -2: -1, 0: 0, 1: 1, 9: 1},
+    blk_cluster_nl={0: 0, 1: 1, 2: 2, 4: 4, 3: 0, 8: 0, -1: 0},
+    conv_nhwc_slots={1: 256, 255: 256, 256: 256, 8192: 8192, 65536: 65536, 65537: 65536, -7: 256})
+
+
+def _get(lib, key):
+    v = ctypes.c_int(-12345)
+    assert lib.gpfq_get_option(key.encode(), ctypes.byref(v)) == 0, key
+    return v.value
+
+
+def _assert_options_at_defaults(lib):
+    assert {k: _get(lib, k) for k in _OPTION_DEFAULTS} == _OPTION_DEFAULTS
+
+
+def test_option_table_is_complete():
+    assert len(_OPTION_DEFAULTS) == 34 and set(_OPTION_SETS) | set(_OPTION_MAPS) == set(_OPTION_DEFAULTS) and not set(_OPTION_SETS) & set(_OPTION_MAPS)
+
+
+def test_option_defaults_rules_and_get(lib):
+    """Every key: its default on a library nobody has set anything in; what it rejects (non-zero, the key in the message, the stored
+    value untouched); what it maps; and set(key, get(key)) changing nothing for every value it accepts (hip.option relies on it)."""
+    _assert_options_at_defaults(lib)
+    try:
+        for key, (taken, refused) in _OPTION_SETS.items():
+            for v in taken:
+                assert lib.gpfq_set_option(key.encode(), v) == 0 and _get(lib, key) == v, (key, v)
+                assert lib.gpfq_set_option(key.encode(), _get(lib, key)) == 0 and _get(lib, key) == v, (key, v)
+                for bad in refused:
+                    assert lib.gpfq_set_option(key.encode(), bad) != 0, (key, bad)
+                    assert key.encode() in lib.gpfq_last_error() and _get(lib, key) == v, (key, bad)
+        for key, mapping in _OPTION_MAPS.items():
+            for given, stored in mapping.items():
+                assert lib.gpfq_set_option(key.encode(), given) == 0 and _get(lib, key) == stored, (key, given)
+                assert lib.gpfq_set_option(key.encode(), stored) == 0 and _get(lib, key) == stored, (key, given)
+    finally:
+        for key, v in _OPTION_DEFAULTS.items():
+            lib.gpfq_set_option(key.encode(), v)
+    _assert_options_at_defaults(lib)
+    # unknown / NULL key, NULL value: invalid argument, the unknown key by name
+    v = ctypes.c_int(7)
+    assert lib.gpfq_get_option(b"blk_prep_norm", ctypes.byref(v)) == -1 and b"unknown option 'blk_prep_norm'" in lib.gpfq_last_error() and v.value == 7
+    assert lib.gpfq_set_option(b"blk_prep_norm", 1) == -1 and b"unknown option 'blk_prep_norm'" in lib.gpfq_last_error()
+    assert lib.gpfq_get_option(None, ctypes.byref(v)) == -1 and lib.gpfq_set_option(None, 1) == -1 and b"NULL" in lib.gpfq_last_error()
+    assert lib.gpfq_get_option(b"pipe", None) == -1
+
+
+def test_header_lists_every_option_once(lib):
+    """The option comment of include/gpfq.h names exactly the keys the library accepts, each once."""
+    header = open(os.path.join(ROOT, "include", "gpfq.h")).read()
+    block = header[header.index("Process-wide tuning/test hooks"):header.index("int gpfq_set_option")]
+    keys = re.findall(r'"([a-z0-9_]+)"', block)
+    assert sorted(keys) == sorted(_OPTION_DEFAULTS), set(keys) ^ set(_OPTION_DEFAULTS)
+    for k in keys:
+        assert lib.gpfq_set_option(k.encode(), _get(lib, k)) == 0
+    _assert_options_at_defaults(lib)
+
+
+def test_hip_option_contexts_restore(lib):
+    from quantized_neural_networks_amd import hip
+    with pytest.raises(RuntimeError, match="boom"):
+        with hip.options(blk_cluster=4096, pipe=2):                          # ("pipe": a key the binding never kept a default for)
+            assert (hip.get_option("blk_cluster"), hip.get_option("pipe")) == (4096, 2)
+            with hip.option("blk_cluster", 0):
+                with hip.option("blk_quad_groups", 9):
+                    assert (hip.get_option("blk_cluster"), hip.get_option("blk_quad_groups")) == (0, 2)
+                assert hip.get_option("blk_quad_groups") == 2
+            assert hip.get_option("blk_cluster") == 4096
+            raise RuntimeError("boom")
+    _assert_options_at_defaults(lib)
+    # a value set behind the binding's back, through the raw handle, is what the block comes back to
+    assert lib.gpfq_set_option(b"blk_cluster_nl", 4) == 0
+    try:
+        with hip.option("blk_cluster_nl", 1):
+            assert hip.get_option("blk_cluster_nl") == 1
+        assert hip.get_option("blk_cluster_nl") == 4
+        # a refused value inside a several-key block: the keys already set go back, the error comes out
+        with pytest.raises(hip.GpfqError):
+            with hip.options(blk_cluster_nl=2, blk_cluster=7):
+                pass
+        assert hip.get_option("blk_cluster_nl") == 4 and hip.get_option("blk_cluster") == 1
+    finally:
+        lib.gpfq_set_option(b"blk_cluster_nl", 0)
+    _assert_options_at_defaults(lib)
+
+
+def test_dispatch_answers_match_golden(lib):
+    """Host sizing and support answers over the grid of tools/gen_dispatch_golden.py equal, element for element, what the commit named
+    in that script answered (tests/golden/dispatch.npz -- never regenerated from the code under test); afterwards every option is at
+    its default."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_dispatch_golden", os.path.join(ROOT, "tools", "gen_dispatch_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    want = np.load(os.path.join(ROOT, "tests", "golden", "dispatch.npz"))
+    assert list(want["settings"]) == list(gen.setting_names())
+    assert (tuple(want["N"]), tuple(want["m"]), tuple(want["C"])) == (gen.N_AXIS, gen.M_AXIS, gen.C_AXIS)
+    got = gen.answers(lib)
+    assert got.shape == want["answers"].shape == (15, 2, 25, 13, 10) and got.dtype == want["answers"].dtype
+    differ = np.argwhere(got != want["answers"])
+    assert differ.size == 0, differ[:10]
+    _assert_options_at_defaults(lib)

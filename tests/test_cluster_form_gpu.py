@@ -46,14 +46,9 @@ def test_cluster_form_vs_oracle(hip, oracle_mod, threshold, m, C, levels, nl):
     Xq[N - 2] = 0                                                 # a dead row: rule (i)
     alphabet, _ = oracle_mod.layer_alphabet(W, np.linspace(-1, 1, levels), 2)
     Q, idx, resid = oracle_mod.layer(W, X, Xq, alphabet)
-    try:
-        hip.set_option("blk_cluster", threshold)
-        hip.set_option("blk_cluster_nl", nl)                       # neurons per lane of a workgroup: by width (0: 4 neurons per workgroup here), 1, 2, 4
+    with hip.options(blk_cluster=threshold, blk_cluster_nl=nl):   # neurons per lane of a workgroup: by width (0: 4 neurons per workgroup here), 1, 2, 4
         r, out = _run(hip, W, X, Xq, alphabet)
         name = hip.last_dense_kernel()
-    finally:
-        hip.set_option("blk_cluster", 1)
-        hip.set_option("blk_cluster_nl", 0)
     assert "cluster form" in name, name
     assert np.array_equal(out["idx"], idx)
     assert np.array_equal(out["Q"], Q.astype(np.float32))
@@ -68,13 +63,10 @@ def test_cluster_form_off_keeps_the_wide_kernel(hip, oracle_mod):
     W, X, Xq = _synthetic(N, m, C, seed=5)
     alphabet, _ = oracle_mod.layer_alphabet(W, np.linspace(-1, 1, 3), 3)
     _, idx, _ = oracle_mod.layer(W, X, Xq, alphabet)
-    try:
-        hip.set_option("blk_cluster", 0)
+    with hip.options(blk_cluster=0):
         _, out = _run(hip, W, X, Xq, alphabet, want_u=False)
         assert "cluster form" not in hip.last_dense_kernel()
         assert np.array_equal(out["idx"], idx)
-    finally:
-        hip.set_option("blk_cluster", 1)
     _, out = _run(hip, W, X, Xq, alphabet, want_u=False)
     assert "cluster form" in hip.last_dense_kernel()
     assert np.array_equal(out["idx"], idx)
@@ -136,14 +128,9 @@ def test_cluster_form_both_workgroup_maps(hip, oracle_mod, cmap, m):
     W, X, Xq = _synthetic(N, m, C, seed=m + cmap)
     alphabet, _ = oracle_mod.layer_alphabet(W, np.linspace(-1, 1, 3), 3)
     _, idx, resid = oracle_mod.layer(W, X, Xq, alphabet)
-    try:
-        hip.set_option("blk_cluster", 1024)
-        hip.set_option("blk_cluster_map", cmap)
+    with hip.options(blk_cluster=1024, blk_cluster_map=cmap):
         _, out = _run(hip, W, X, Xq, alphabet, want_u=False)
         assert "cluster form" in hip.last_dense_kernel()
-    finally:
-        hip.set_option("blk_cluster", 1)
-        hip.set_option("blk_cluster_map", -1)
     assert np.array_equal(out["idx"], idx)
     np.testing.assert_allclose(out["resid"], resid, rtol=RESID_RTOL)
 
@@ -160,15 +147,12 @@ def test_four_slices_of_768_samples_vs_oracle(hip, oracle_mod, m, levels, waves)
     Xq[N - 3] = 0                                                 # a dead row: rule (i)
     alphabet, _ = oracle_mod.layer_alphabet(W, np.linspace(-1, 1, levels), 2)
     Q, idx, resid = oracle_mod.layer(W, X, Xq, alphabet)
-    try:
-        hip.set_option("blk_cluster768", waves)
+    with hip.options(blk_cluster768=waves):
         r, out = _run(hip, W, X, Xq, alphabet)
         name = hip.last_dense_kernel()
-        hip.set_option("blk_cluster768", 0)
+    with hip.options(blk_cluster768=0):
         r0, out0 = _run(hip, W, X, Xq, alphabet, want_u=False)
         name0 = hip.last_dense_kernel()
-    finally:
-        hip.set_option("blk_cluster768", -1)
     assert "cluster form" in name and "cluster form" not in name0
     assert np.array_equal(out["idx"], idx) and np.array_equal(out0["idx"], idx)
     assert np.array_equal(out["Q"], Q.astype(np.float32))

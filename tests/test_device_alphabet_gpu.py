@@ -155,12 +155,8 @@ def test_shapes_without_a_block_kernel_fall_back_to_the_host_alphabet(hip, layer
 @pytest.fixture
 def faulty_cluster(hip):
     """One slice of the first cluster never publishes: every exchange of that cluster times out (after 40 ms instead of 3 s)."""
-    hip.set_option("blk_cluster_fault", 1)
-    hip.set_option("blk_cluster_timeout_ms", 40)
-    yield
-    hip.set_option("blk_cluster_fault", 0)
-    hip.set_option("blk_cluster_timeout_ms", 3000)
-    hip.set_option("sync_errors", 0)
+    with hip.options(blk_cluster_fault=1, blk_cluster_timeout_ms=40, sync_errors=0):      # (sync_errors: what a test body sets goes back too)
+        yield
 
 
 def test_forced_exchange_timeout_is_reported_by_the_c_abi(hip, oracle_mod, faulty_cluster):
@@ -251,13 +247,10 @@ def test_partitioned_chip_keeps_the_classic_shapes(hip, oracle_mod):
     W, X, Xq = _synthetic(N, m, C, seed=8)
     alphabet, _ = oracle_mod.layer_alphabet(W, np.linspace(-1, 1, 3), 3)
     _, idx, _ = oracle_mod.layer(W, X, Xq, alphabet)
-    try:
-        hip.set_option("blk_chip_ok", 0)
+    with hip.options(blk_chip_ok=0):
         r = hip.quantize_neurons(_dev(X), _dev(Xq), _dev(W.T), alphabet, path=1)
         assert "cluster form" not in hip.last_dense_kernel()
         assert np.array_equal(r["idx"].cpu().numpy(), idx)
-    finally:
-        hip.set_option("blk_chip_ok", -1)
     r = hip.quantize_neurons(_dev(X), _dev(Xq), _dev(W.T), alphabet, path=1)
     assert "cluster form" in hip.last_dense_kernel()
     assert np.array_equal(r["idx"].cpu().numpy(), idx)
@@ -293,15 +286,12 @@ def test_record_prepass_in_runs_equals_one_record_per_workgroup(hip, oracle_mod,
     alphabet, _ = oracle_mod.layer_alphabet(W, np.linspace(-1, 1, levels), 3)
     Q, idx, resid = oracle_mod.layer(W, X, Xq, alphabet)
     outs = []
-    try:
-        for run in (0, 8, 4, 13):                                  # (4 .. 16: runs of that many records whatever the walk's length; 1, the default, only from 2048 steps)
-            hip.set_option("blk_prep_run", run)
+    for run in (0, 8, 4, 13):                                  # (4 .. 16: runs of that many records whatever the walk's length; 1, the default, only from 2048 steps)
+        with hip.options(blk_prep_run=run):
             with hip.option("blk_cluster", 0):
                 r = hip.quantize_neurons(_dev(X), _dev(Xq), _dev(W.T), alphabet, want_u=True, path=1)
             assert "gpfq_blk_kernel" in hip.last_dense_kernel()
             outs.append((r["idx"].cpu().numpy(), r["Q"].cpu().numpy(), r["u"].cpu().numpy(), r["resid"].cpu().numpy(), hip.exact_fallbacks(r)))
-    finally:
-        hip.set_option("blk_prep_run", 1)
     for other in outs[1:]:
         for a, b in zip(outs[0][:3], other[:3]):
             assert np.array_equal(a, b)
@@ -393,19 +383,15 @@ def test_row_norms_inside_the_record_prepass(hip, layer, oracle_mod, N, C, m, le
     Wd, Xd, Xqd = _dev(W), _dev(X), _dev(Xq)
     dalpha = layer.layer_alphabet_device(Wd, unit, 2.5)
     outs = []
-    try:
-        hip.set_option("blk_prep_run", run)
+    with hip.options(blk_prep_run=run):
         for norms in (1, 0, 1):
-            hip.set_option("blk_prep_norms", norms)
-            r = hip.quantize_dense_layer(Xd, Xqd, Wd, dalpha, keras_out=False, want_values=True)
+            with hip.options(blk_prep_norms=norms):
+                r = hip.quantize_dense_layer(Xd, Xqd, Wd, dalpha, keras_out=False, want_values=True)
             assert hip.call_status(r) == 0
             outs.append((r["idx"].cpu().numpy(), r["Q"].cpu().numpy(), r["resid"].cpu().numpy(), hip.exact_fallbacks(r)))
         # the caller's own norms (gpfq_row_norms): the third way to the same records
         r = hip.quantize_dense_layer(Xd, Xqd, Wd, dalpha, nrm32=hip.row_norms(Xqd), keras_out=False, want_values=True)
         outs.append((r["idx"].cpu().numpy(), r["Q"].cpu().numpy(), r["resid"].cpu().numpy(), hip.exact_fallbacks(r)))
-    finally:
-        hip.set_option("blk_prep_run", 1)
-        hip.set_option("blk_prep_norms", 1)
     for o in outs:
         assert np.array_equal(o[0], idx) and np.array_equal(o[1], Q.astype(np.float32))
         np.testing.assert_allclose(o[2], resid, rtol=RESID_RTOL)

@@ -140,9 +140,8 @@ def _check_against_oracle(out, Q, idx, resid):
 
 @pytest.fixture
 def fault_options(hip):
-    yield
-    hip.set_option("blk_cluster_fault", 0)
-    hip.set_option("blk_cluster_timeout_ms", 3000)
+    with hip.options(blk_cluster_fault=0, blk_cluster_timeout_ms=3000):       # (what a test body sets goes back when it ends, however it ends)
+        yield
 
 
 def _cells():

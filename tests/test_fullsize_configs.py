@@ -213,14 +213,11 @@ def _conv_slack_ab(hip, layer, W, act_w, act_q, alphabet, base, kw):
     doubled (`gram_slack_log2` = 1: wider than any bound the path ever shipped with) and multiplied by 8: a decision the
     production bound certified wrongly would have to survive bounds 2x and 8x as wide too, or show up here as a
     difference -- a chain flagged under the wider bound is decided from its exact dot products."""
-    try:
-        for s in (1, 3):
-            hip.set_option("gram_slack_log2", s)
+    for s in (1, 3):
+        with hip.options(gram_slack_log2=s):
             wide = layer.quantize_conv2d(W, act_w, act_q, alphabet, **kw)
             assert torch.equal(wide["idx"], base["idx"]), f"gram_slack_log2 = {s}: the index tensor moved"
             assert torch.equal(wide["Q"], base["Q"])
-    finally:
-        hip.set_option("gram_slack_log2", 0)
 
 
 def _conv_properties(layer, W, act_w, act_q, alphabet, base, M, kw):

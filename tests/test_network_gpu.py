@@ -376,12 +376,9 @@ def test_conv_layer_gram_fast_path(oracle_mod, slack, members):
     Wd = torch.from_numpy(W).cuda()
     alphabet, _ = layer.layer_alphabet(Wd, np.linspace(-1, 1, members), 4)
     assert 36 * 24 * 24 > hip.GPFQ_GRAM_MIN_M
-    try:
-        hip.set_option("gram_slack_log2", slack)
+    with hip.options(gram_slack_log2=slack):
         out = layer.quantize_conv2d(Wd, torch.from_numpy(act_w).cuda(), torch.from_numpy(act_q).cuda(), alphabet,
                                     strides=(1, 1), padding="SAME", rate=(1, 1))
-    finally:
-        hip.set_option("gram_slack_log2", 0)
     Q = out["Q"].cpu().numpy()
     idx = out["idx"].cpu().numpy()
     assert idx.dtype == (np.int8 if members <= 64 else np.int16)
@@ -416,16 +413,11 @@ def test_conv_3x3_from_nhwc(oracle_mod, n, H, W, Cin, F, first):
     aq = aw if first else torch.from_numpy(act_q).cuda()
     assert hip.conv3x3_nhwc_supported(n, H, W, Cin)
     out = layer.quantize_conv2d(Wd, aw, aq, alphabet, strides=(1, 1), padding="SAME", rate=(1, 1), want_resid=False)
-    try:
-        hip.set_option("conv_nhwc", 0)
+    with hip.options(conv_nhwc=0):
         assert not hip.conv3x3_nhwc_supported(n, H, W, Cin)
         planes = layer.quantize_conv2d(Wd, aw, aq, alphabet, strides=(1, 1), padding="SAME", rate=(1, 1), want_resid=False)
-        hip.set_option("conv_nhwc", 1)
-        hip.set_option("conv_nhwc_halves", 0)                            # (<= 32 channels, an even number of images: one image per wavefront)
+    with hip.options(conv_nhwc_halves=0):                                # (<= 32 channels, an even number of images: one image per wavefront)
         whole = layer.quantize_conv2d(Wd, aw, aq, alphabet, strides=(1, 1), padding="SAME", rate=(1, 1), want_resid=False)
-    finally:
-        hip.set_option("conv_nhwc", 1)
-        hip.set_option("conv_nhwc_halves", 1)
     assert torch.equal(out["Q"], planes["Q"]) and torch.equal(out["idx"], planes["idx"])
     assert torch.equal(out["Q"], whole["Q"]) and torch.equal(out["idx"], whole["idx"])
     Q = out["Q"].cpu().numpy()
@@ -478,24 +470,18 @@ def test_conv_fused_3x3(oracle_mod, n, H, W, Cin, F, padding, strip, first):
     alphabet, _ = layer.layer_alphabet(Wd, np.linspace(-1, 1, 8), 4)
     aw = torch.from_numpy(act_w).cuda()
     aq = aw if first else torch.from_numpy(act_q).cuda()
-    try:
-        hip.set_option("conv_strip", strip)
+    with hip.options(conv_strip=strip):
         out = layer.quantize_conv2d(Wd, aw, aq, alphabet, strides=(1, 1), padding=padding, rate=(1, 1), want_resid=False)
-        hip.set_option("conv_fused", 0)
-        old = layer.quantize_conv2d(Wd, aw, aq, alphabet, strides=(1, 1), padding=padding, rate=(1, 1), want_resid=False)
-        hip.set_option("conv_fused", 1)
+        with hip.options(conv_fused=0):
+            old = layer.quantize_conv2d(Wd, aw, aq, alphabet, strides=(1, 1), padding=padding, rate=(1, 1), want_resid=False)
         # SAME layers take the shift form (27 FMAs per position + border classes); conv_shift = 0 is the per-output-position form
-        hip.set_option("conv_shift", 0)
-        direct = layer.quantize_conv2d(Wd, aw, aq, alphabet, strides=(1, 1), padding=padding, rate=(1, 1), want_resid=False)
-        pw, pq = hip.channel_planes(aw, 0, Cin), hip.channel_planes(aq, 0, Cin)
-        rec0, neg0 = hip.conv_channel_records(pw, pq, (3, 3), (1, 1), (1, 1), padding)
-        hip.set_option("conv_shift", 2)                                 # the shift form whatever the image size
-        forced = layer.quantize_conv2d(Wd, aw, aq, alphabet, strides=(1, 1), padding=padding, rate=(1, 1), want_resid=False)
-        rec1, neg1 = hip.conv_channel_records(pw, pq, (3, 3), (1, 1), (1, 1), padding)
-    finally:
-        hip.set_option("conv_fused", 1)
-        hip.set_option("conv_strip", 0)
-        hip.set_option("conv_shift", 1)
+        with hip.options(conv_shift=0):
+            direct = layer.quantize_conv2d(Wd, aw, aq, alphabet, strides=(1, 1), padding=padding, rate=(1, 1), want_resid=False)
+            pw, pq = hip.channel_planes(aw, 0, Cin), hip.channel_planes(aq, 0, Cin)
+            rec0, neg0 = hip.conv_channel_records(pw, pq, (3, 3), (1, 1), (1, 1), padding)
+        with hip.options(conv_shift=2):                                 # the shift form whatever the image size
+            forced = layer.quantize_conv2d(Wd, aw, aq, alphabet, strides=(1, 1), padding=padding, rate=(1, 1), want_resid=False)
+            rec1, neg1 = hip.conv_channel_records(pw, pq, (3, 3), (1, 1), (1, 1), padding)
     assert torch.equal(out["Q"], old["Q"]) and torch.equal(out["idx"], old["idx"])
     assert torch.equal(out["Q"], direct["Q"]) and torch.equal(out["idx"], direct["idx"])
     assert torch.equal(out["Q"], forced["Q"]) and torch.equal(out["idx"], forced["idx"])
@@ -517,14 +503,11 @@ def test_conv_fused_3x3(oracle_mod, n, H, W, Cin, F, padding, strip, first):
         # inflated error bounds: some (2^14) or all (2^60) chains stop and are repaired on the device from the
         # exact dot products (two rounds), the rest by the caller's exact rerun -- results never change
         counts = []
-        try:
-            for slack in (14, 60):
-                hip.set_option("gram_slack_log2", slack)
+        for slack in (14, 60):
+            with hip.options(gram_slack_log2=slack):
                 rep = layer.quantize_conv2d(Wd, aw, aq, alphabet, strides=(1, 1), padding=padding, rate=(1, 1), want_resid=False)
                 assert torch.equal(rep["Q"], out["Q"]) and torch.equal(rep["idx"], out["idx"]), slack
                 counts.append(int(rep["reruns"]))
-        finally:
-            hip.set_option("gram_slack_log2", 0)
         assert counts[0] <= counts[1] == Cin * F, counts
 
 
@@ -555,20 +538,13 @@ def test_conv_implicit_im2col(oracle_mod, n, H, W, Cin, F, kh, kw, stride, rate,
     aw = torch.from_numpy(act_w).cuda()
     aq = aw if first else torch.from_numpy(act_q).cuda()
     kwargs = dict(strides=(stride, stride), padding=padding, rate=(rate, rate), want_resid=False)
-    try:
-        out = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
-        hip.set_option("conv_fused", 0)
+    out = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
+    with hip.options(conv_fused=0):
         old = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
-        hip.set_option("conv_fused", 1)
-        hip.set_option("variant", 4)                        # 16 < kh*kw <= 64: vector-unit tiles instead of the matrix cores
+    with hip.options(variant=4):                            # 16 < kh*kw <= 64: vector-unit tiles instead of the matrix cores
         vec = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
-        hip.set_option("variant", 0)
-        hip.set_option("gram_slack_log2", 14)               # some chains repaired on the device, from the planes
+    with hip.options(gram_slack_log2=14):                   # some chains repaired on the device, from the planes
         rep = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
-    finally:
-        hip.set_option("conv_fused", 1)
-        hip.set_option("variant", 0)
-        hip.set_option("gram_slack_log2", 0)
     assert torch.equal(out["Q"], old["Q"]) and torch.equal(out["idx"], old["idx"])
     assert torch.equal(out["Q"], vec["Q"]) and torch.equal(out["idx"], vec["idx"])
     assert torch.equal(out["Q"], rep["Q"]) and torch.equal(out["idx"], rep["idx"])
@@ -620,22 +596,16 @@ def test_conv7x7_stride2_shift_sums(oracle_mod, n, H, W, Cin, F, kind):
     aw = torch.from_numpy(act_w).cuda()
     aq = aw if kind == "first" else torch.from_numpy(act_q).cuda()
     kwargs = dict(strides=(2, 2), padding="VALID", rate=(1, 1), want_resid=False)
-    try:
-        out = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
-        hip.set_option("conv_s2", 0)
+    out = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
+    with hip.options(conv_s2=0):
         mfma = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
-        hip.set_option("conv_s2", 1)
-        hip.set_option("gram_slack_log2", 14)               # some chains repaired on the device, from the NHWC tensors
+    with hip.options(gram_slack_log2=14):                   # some chains repaired on the device, from the NHWC tensors
         rep = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
-        hip.set_option("conv_planes_free", 0)               # ... and from channel planes, the kernel fed from planes as well
-        assert not hip.conv_channels_nhwc_supported(n, H, W, Cin, (7, 7), (2, 2), (1, 1), "VALID")
-        rep_planes = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
-        hip.set_option("gram_slack_log2", 0)
+        with hip.options(conv_planes_free=0):               # ... and from channel planes, the kernel fed from planes as well
+            assert not hip.conv_channels_nhwc_supported(n, H, W, Cin, (7, 7), (2, 2), (1, 1), "VALID")
+            rep_planes = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
+    with hip.options(conv_planes_free=0):
         planes = layer.quantize_conv2d(Wd, aw, aq, alphabet, **kwargs)
-    finally:
-        hip.set_option("conv_s2", 1)
-        hip.set_option("conv_planes_free", 1)
-        hip.set_option("gram_slack_log2", 0)
     assert hip.conv_channels_nhwc_supported(n, H, W, Cin, (7, 7), (2, 2), (1, 1), "VALID")
     assert torch.equal(out["Q"], mfma["Q"]) and torch.equal(out["idx"], mfma["idx"])
     assert torch.equal(out["Q"], rep["Q"]) and torch.equal(out["idx"], rep["idx"])

@@ -17,16 +17,15 @@ for (N, C, m, M) in ((4096, 4096, 3000, 16), (4096, 4096, 3000, 3), (4096, 2560,
     ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
     ref = None
     for opt in (0, 8, 11):
-        hip.set_option("blk_cluster768", opt)
-        ks = []
-        for _ in range(4):
-            hip.set_main_kernel_events(*ev)
-            r = hip.quantize_neurons(X, Xq, Wt, alphabet, nrm32=nrm)
-            torch.cuda.synchronize()
-            hip.set_main_kernel_events(None, None)
-            ks.append(ev[0].elapsed_time(ev[1]))
-        same = "" if ref is None else (f"  indices equal to option 0: {bool(torch.equal(ref['idx'], r['idx']))}, values: {bool(torch.equal(ref['Q'], r['Q']))}, "
-                                       f"residual norms max rel diff {float(((ref['resid'] - r['resid']).abs() / ref['resid']).max()):.1e}")
-        ref = r if ref is None else ref
-        print(f"{N} x {C} on {m} samples, M={M}, blk_cluster768={opt:2d}: kernel {np.median(ks):.3f} ms  status {hip.call_status(r)}  fallbacks {hip.exact_fallbacks(r)}{same}  [{hip.last_dense_kernel()[:40]}]")
-hip.set_option("blk_cluster768", 11)
+        with hip.option("blk_cluster768", opt):
+            ks = []
+            for _ in range(4):
+                hip.set_main_kernel_events(*ev)
+                r = hip.quantize_neurons(X, Xq, Wt, alphabet, nrm32=nrm)
+                torch.cuda.synchronize()
+                hip.set_main_kernel_events(None, None)
+                ks.append(ev[0].elapsed_time(ev[1]))
+            same = "" if ref is None else (f"  indices equal to option 0: {bool(torch.equal(ref['idx'], r['idx']))}, values: {bool(torch.equal(ref['Q'], r['Q']))}, "
+                                           f"residual norms max rel diff {float(((ref['resid'] - r['resid']).abs() / ref['resid']).max()):.1e}")
+            ref = r if ref is None else ref
+            print(f"{N} x {C} on {m} samples, M={M}, blk_cluster768={opt:2d}: kernel {np.median(ks):.3f} ms  status {hip.call_status(r)}  fallbacks {hip.exact_fallbacks(r)}{same}  [{hip.last_dense_kernel()[:40]}]")

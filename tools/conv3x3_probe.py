@@ -29,14 +29,13 @@ for n, H, W, cin, cout in shapes:
     alphabet, rad = layer.layer_alphabet(Wk, np.linspace(-1, 1, 3), 3)
     ref = None
     for shift in ((1,) if SHIFT_ONLY else (0, 1)):
-        hip.set_option("conv_shift", shift)
-        best = 1e9
-        for it in range(4):
-            torch.cuda.synchronize(); t0 = time.time()
-            out = layer.quantize_conv2d(Wk, act_w, act_q, alphabet, strides=(1, 1), padding="SAME", rate=(1, 1), want_resid=False)
-            torch.cuda.synchronize(); best = min(best, time.time() - t0)
-        same = "" if ref is None else f", equal to the other form: {bool(torch.equal(ref, out['Q']))}"
-        ref = out["Q"] if ref is None else ref
-        print(f"3x3 {cin}->{cout} @{H}x{W} n={n} conv_shift={shift}: {best*1e3:.2f} ms, host reruns {int(out['reruns'])}{same}")
+        with hip.option("conv_shift", shift):
+            best = 1e9
+            for it in range(4):
+                torch.cuda.synchronize(); t0 = time.time()
+                out = layer.quantize_conv2d(Wk, act_w, act_q, alphabet, strides=(1, 1), padding="SAME", rate=(1, 1), want_resid=False)
+                torch.cuda.synchronize(); best = min(best, time.time() - t0)
+            same = "" if ref is None else f", equal to the other form: {bool(torch.equal(ref, out['Q']))}"
+            ref = out["Q"] if ref is None else ref
+            print(f"3x3 {cin}->{cout} @{H}x{W} n={n} conv_shift={shift}: {best*1e3:.2f} ms, host reruns {int(out['reruns'])}{same}")
     del act_w, act_q
-hip.set_option("conv_shift", 1)

@@ -73,14 +73,9 @@ while time.time() < t_end:
         elif path == 1:
             opts = dict(lanes_per_neuron=int(rng.choice([0, 1, 16, 32, 64])), waves_per_neuron=int(rng.choice([0, 0, 2, 4, 8, 16])),
                         onchip_mode=int(rng.integers(0, 2)))
-        try:
-            for k, v in opts.items():
-                hip.set_option(k, v)
+        with hip.options(**opts):
             r = hip.quantize_neurons(torch.from_numpy(X).to(dev), torch.from_numpy(Xq).to(dev), torch.from_numpy(W.T.copy()).to(dev),
                                      alphabet, path=path)
-        finally:
-            for k in opts:
-                hip.set_option(k, {"onchip_mode": 1, "pipe": -1, "blk_sweep_waves": 0, "blk_quad_waves": 0, "blk_wide_groups": 1, "blk_four_groups": 1, "blk_pair_groups": 1, "blk_single_groups": 1, "blk_quad_groups": 2, "blk_cluster": 1, "blk_cluster_map": -1, "blk_cluster_nl": 0, "blk_cluster768": -1}.get(k, 0))
         ok = np.array_equal(r["idx"].cpu().numpy(), io) and np.allclose(r["resid"].cpu().numpy(), ro, rtol=1e-5, atol=0)
         n_dense += 1
         if not ok:
@@ -90,13 +85,9 @@ while time.time() < t_end:
         # without a block-pipelined kernel fall back to the host alphabet inside
         if M <= 64 and rng.random() < 0.6:
             popts = dict(blk_prep_run=int(rng.choice([1, 1, 0, 4, 8])), blk_cluster=int(rng.choice([1, 1, 0, 1024])))
-            try:
-                for k, v in popts.items():
-                    hip.set_option(k, v)
+            with hip.options(**popts):
                 out = layer.quantize_dense_layer(torch.from_numpy(W).to(dev), torch.from_numpy(X).to(dev), torch.from_numpy(Xq).to(dev),
                                                  np.linspace(-1, 1, M), scalar, overlap=bool(rng.random() < 0.5), kernel_ready=[None, True][int(rng.random() < 0.5)])
-            finally:
-                hip.set_option("blk_prep_run", 1); hip.set_option("blk_cluster", 1)
             ok = (np.array_equal(out["idx"].cpu().numpy(), io.T) and np.array_equal(out["Q"].cpu().numpy(), Qo.T.astype(np.float32))
                   and np.allclose(out["resid"].cpu().numpy(), ro, rtol=1e-5, atol=0) and hip.call_status(out) == 0)
             n_dense += 1

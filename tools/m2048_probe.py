@@ -21,17 +21,16 @@ for (N, C, m, M) in shapes:
         e.record()
     ref = None
     for opt in (1, 1024, 1, 1024):
-        hip.set_option("blk_cluster", opt)
-        for _ in range(6):
-            r = hip.quantize_neurons(X, Xq, Wt, alphabet, nrm32=nrm)
-        ks = []
-        for _ in range(5):
-            hip.set_main_kernel_events(*ev)
-            r = hip.quantize_neurons(X, Xq, Wt, alphabet, nrm32=nrm)
-            hip.set_main_kernel_events(None, None)
-            torch.cuda.synchronize()
-            ks.append(ev[0].elapsed_time(ev[1]))
-        same = "" if ref is None else f"  indices equal: {bool(torch.equal(ref['idx'], r['idx']))}, values: {bool(torch.equal(ref['Q'], r['Q']))}"
-        ref = r if ref is None else ref
-        print(f"{N} x {C} on {m} samples, M={M}, blk_cluster={opt:4d}: kernel {np.median(ks):.3f} ms (min {np.min(ks):.3f})  status {hip.call_status(r)}{same}  [{hip.last_dense_kernel()[:28]}]")
-hip.set_option("blk_cluster", 1)
+        with hip.option("blk_cluster", opt):
+            for _ in range(6):
+                r = hip.quantize_neurons(X, Xq, Wt, alphabet, nrm32=nrm)
+            ks = []
+            for _ in range(5):
+                hip.set_main_kernel_events(*ev)
+                r = hip.quantize_neurons(X, Xq, Wt, alphabet, nrm32=nrm)
+                hip.set_main_kernel_events(None, None)
+                torch.cuda.synchronize()
+                ks.append(ev[0].elapsed_time(ev[1]))
+            same = "" if ref is None else f"  indices equal: {bool(torch.equal(ref['idx'], r['idx']))}, values: {bool(torch.equal(ref['Q'], r['Q']))}"
+            ref = r if ref is None else ref
+            print(f"{N} x {C} on {m} samples, M={M}, blk_cluster={opt:4d}: kernel {np.median(ks):.3f} ms (min {np.min(ks):.3f})  status {hip.call_status(r)}{same}  [{hip.last_dense_kernel()[:28]}]")

@@ -40,15 +40,14 @@ d = layer.layer_alphabet_device(W, unit, 3.0)
 nrm = hip.row_norms(Xq)
 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
 for run in (0, 4, 5, 6, 8, 9, 12, 16, 1):
-    hip.set_option("blk_prep_run", run)
-    ks, cs = [], []
-    for _ in range(8):
-        hip.set_main_kernel_events(*ev)
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        r = hip.quantize_dense_layer(X, Xq, W, d, nrm32=nrm)
-        b.record(); torch.cuda.synchronize()
-        hip.set_main_kernel_events(None, None)
-        ks.append(ev[0].elapsed_time(ev[1])); cs.append(a.elapsed_time(b))
-    print(f"blk_prep_run={run}: call - kernel = {1e3 * (np.median(cs) - np.median(ks)):7.1f} us   (kernel {np.median(ks):.4f} ms, status {hip.call_status(r)})")
-hip.set_option("blk_prep_run", 1)
+    with hip.option("blk_prep_run", run):
+        ks, cs = [], []
+        for _ in range(8):
+            hip.set_main_kernel_events(*ev)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            r = hip.quantize_dense_layer(X, Xq, W, d, nrm32=nrm)
+            b.record(); torch.cuda.synchronize()
+            hip.set_main_kernel_events(None, None)
+            ks.append(ev[0].elapsed_time(ev[1])); cs.append(a.elapsed_time(b))
+        print(f"blk_prep_run={run}: call - kernel = {1e3 * (np.median(cs) - np.median(ks)):7.1f} us   (kernel {np.median(ks):.4f} ms, status {hip.call_status(r)})")
