@@ -824,7 +824,8 @@ def assemble_kernel_colrad(qidx, unit_alphabet, radii, bits=None, N=None, layout
 
 
 def last_dense_kernel():
-    """Name of the dense kernel family the last quantize_neurons() call dispatched (diagnostics)."""
+    """Name of the dense kernel family the last quantize_neurons() / quantize_dense_layer() call of the process dispatched (diagnostics;
+    layer._can_defer asks it right after a launch whether that was the block kernel's cluster form)."""
     return load().gpfq_last_dense_kernel().decode()
 
 

@@ -8,8 +8,6 @@ process group (one process per GPU, backend "nccl" = RCCL over xGMI).  Every ran
 activation matrices and the full analog kernel, quantizes its shard, and ONE all-gather per layer
 reassembles the quantized kernel; there is no other communication.
 """
-import contextlib
-
 import numpy as np
 import torch
 
@@ -24,6 +22,13 @@ from . import hip
 # (tens of microseconds EACH over RCCL, and every one waits for the slowest rank): the break-even moved from 4 M to about 32 M weights --
 # the north-star layer (16.8 M) selects locally on every rank, VGG16's fc1 (102.8 M) shards its counting.
 _SHARDED_MEDIAN_MIN = 1 << 25
+
+
+def _median_slice(flat, world, rank):
+    """The slice of the flattened kernel that `rank` counts for the sharded median: slices start on multiples of 4 elements."""
+    n = flat.numel()
+    per = -(-n // (4 * world)) * 4
+    return flat[min(rank * per, n):min((rank + 1) * per, n)]
 
 
 def median_abs(W, group=None, meanwhile=None):
@@ -42,9 +47,7 @@ def median_abs(W, group=None, meanwhile=None):
     if world == 1 or n < _SHARDED_MEDIAN_MIN or not flat.is_cuda:
         return hip.median_abs(flat, meanwhile)
     import torch.distributed as dist
-    per = -(-n // (4 * world)) * 4                       # slices start on multiples of 4 elements
-    lo, hi = min(rank * per, n), min((rank + 1) * per, n)
-    return hip.median_abs_sharded(flat[lo:hi], n, lambda t: dist.all_reduce(t, group=group), meanwhile)
+    return hip.median_abs_sharded(_median_slice(flat, world, rank), n, lambda t: dist.all_reduce(t, group=group), meanwhile)
 
 
 def layer_alphabet_device(W, alphabet, alphabet_scalar, group=None):
@@ -58,11 +61,8 @@ def layer_alphabet_device(W, alphabet, alphabet_scalar, group=None):
     world, rank = _group_info(group)
     if world == 1 or n < _SHARDED_MEDIAN_MIN:
         return hip.layer_alphabet_from_kernel(flat, alphabet, alphabet_scalar)      # median + alphabet: one call, two launches
-    else:
-        import torch.distributed as dist
-        per = -(-n // (4 * world)) * 4
-        lo, hi = min(rank * per, n), min((rank + 1) * per, n)
-        med = hip.median_abs_sharded(flat[lo:hi], n, lambda t: dist.all_reduce(t, group=group), on_device=True)
+    import torch.distributed as dist
+    med = hip.median_abs_sharded(_median_slice(flat, world, rank), n, lambda t: dist.all_reduce(t, group=group), on_device=True)
     return hip.layer_alphabet_device(med, alphabet, alphabet_scalar)
 
 
@@ -139,32 +139,70 @@ def all_gather_units(local, n_units, group=None):
 # ------------------------------------------------------------------------------------------
 def _log_failure(log, msg):
     import warnings
-    warnings.warn(msg, RuntimeWarning, stacklevel=3)
+    warnings.warn(msg, RuntimeWarning, stacklevel=4)             # (the caller of the driver that ran the ladder)
     if log is not None:
         log(msg)
 
 
+def _can_defer(r, alphabet):
+    """Whether the launch that has just returned `r` can still fail late -- asked once, right after it (hip.last_dense_kernel names the
+    process's last launch): an exchange of the block kernel's CLUSTER FORM (several workgroups per group of neurons, which rests on their
+    being co-resident) can time out, and a device alphabet nobody vouched for (DeviceAlphabet.radius_ok) can be one the block kernel does
+    not run.  Every other launch has no status word and costs no host wait."""
+    if r.get("workspace") is None:                               # (nothing launched -- an empty shard -- or a kernel without status words)
+        return False
+    return (isinstance(alphabet, hip.DeviceAlphabet) and not alphabet.radius_ok) or "cluster form" in hip.last_dense_kernel()
+
+
+def _neurons_timed_out(rows, m, st):
+    return (f"quantize_neurons: the cluster form's exchange timed out on {rows} neurons x {m} samples (status {st}); rerunning them "
+            f"through the classic kernels")
+
+
+def _launch_repaired(launch, finish, alphabet, log, line, block_kernel=None, check=True, status_first=False):
+    """The repair ladder of every dense launch, at the reference's granularity (it logs the failing unit and re-raises at once,
+    scripts/quantized_network.py:563-565): launch(alphabet) -> the status word where the launch can have one (_can_defer; one host wait)
+    -> GPFQ_ERR_CLUSTER_TIMEOUT: logged once, rerun with the cluster form off -- on the device alphabet while block_kernel(dalpha) holds,
+    else (rows of more than 5120 samples: only the cluster form reads a device alphabet there) on the host alphabet's kernels
+    -> GPFQ_ERR_ALPHABET (radius 0 / infinite / NaN, or members the kernel cannot index): logged once, rerun on the host alphabet, the
+    cluster form allowed again -> any other status, or a second timeout, raises.  A device alphabet whose shape block_kernel() never took
+    goes to the host alphabet unlogged (one read-back).  line(what, alphabet, status): the caller's wording of "timeout" / "no classic" /
+    "alphabet".  finish(r, alphabet) queues what follows the kernel and returns the driver's result.  status_first=False (one GPU): it
+    is queued BEHIND the kernel before the status is read -- the host's wait then costs no bubble between the two (cfg4's
+    Dense(128 -> 10): 0.06 ms of a 0.15 ms layer); nothing is RETURNED unchecked.  status_first=True (a process group): the status is read
+    and the shard repaired BEFORE finish() packs and gathers it -- the other ranks never see garbage and nobody has to agree on anything.
+    A rerun's status is always read, and ahead of finish().  check=False (device alphabets): no status is read; the caller owes it."""
+    cluster, timed_out = True, 0
+    while True:
+        with (hip.options() if cluster else hip.option("blk_cluster", 0)):
+            if isinstance(alphabet, hip.DeviceAlphabet) and not block_kernel(alphabet):
+                if timed_out:
+                    _log_failure(log, line("no classic", alphabet, timed_out))
+                alphabet, timed_out = alphabet.values(), 0
+            elif timed_out:
+                _log_failure(log, line("timeout", alphabet, timed_out))
+            on_device = isinstance(alphabet, hip.DeviceAlphabet)
+            r = launch(alphabet)
+            wait = bool(timed_out) or ((check or not on_device) and _can_defer(r, alphabet))
+            out = None if (status_first or timed_out) else finish(r, alphabet)
+            st = hip.call_status(r) if wait else 0
+        if st == 0:
+            return finish(r, alphabet) if out is None else out
+        if st == hip.GPFQ_ERR_CLUSTER_TIMEOUT and cluster:
+            cluster, timed_out = False, st
+        elif st == hip.GPFQ_ERR_ALPHABET and on_device:
+            _log_failure(log, line("alphabet", alphabet, st))
+            alphabet, cluster, timed_out = alphabet.values(), True, 0
+        else:
+            raise hip.GpfqError(f"dense launch failed with status {st}" + ("" if cluster else " again without the cluster form"))
+
+
 def quantize_neurons_checked(X, Xq, Wt, alphabet, log=None, **kw):
-    """hip.quantize_neurons with the block kernel's deferred failure handled at the reference's granularity (the reference logs the
-    failing unit and re-raises at once, scripts/quantized_network.py:563-565): when the call went through the CLUSTER FORM -- several
-    workgroups per group of neurons that exchange partial dot products, which rests on their being co-resident -- its status word is read
-    (one host wait) BEFORE the result is used; a timed-out exchange is logged and the same neurons are rerun at once through the classic
-    kernels (option blk_cluster = 0), and only a failure of that run raises.  Every other kernel family has no deferred failure and no wait."""
-    r = hip.quantize_neurons(X, Xq, Wt, alphabet, **kw)
-    if "cluster form" not in hip.last_dense_kernel():
-        return r
-    st = hip.call_status(r)
-    if st == 0:
-        return r
-    _log_failure(log, f"quantize_neurons: the cluster form's exchange timed out on {Wt.shape[0]} neurons x {X.shape[1]} samples "
-                      f"(status {st}); rerunning them through the classic kernels")
-    with hip.option("blk_cluster", 0):
-        r = hip.quantize_neurons(X, Xq, Wt, alphabet, **kw)
-        st = hip.call_status(r)
-    if st != 0:
-        raise hip.GpfqError(f"quantize_neurons failed again without the cluster form (status {st})")
-    r["cluster_fallback"] = True
-    return r
+    """hip.quantize_neurons through the repair ladder (_launch_repaired): where the call went through the cluster form its status word
+    is read (one host wait) BEFORE the result is used; a timed-out exchange is logged and the same neurons are rerun at once through the
+    classic kernels, and only a failure of that run raises.  Every other kernel family has no deferred failure and no wait."""
+    return _launch_repaired(lambda a: hip.quantize_neurons(X, Xq, Wt, a, **kw), lambda r, a: r, alphabet, log,
+                            lambda what, a, st: _neurons_timed_out(Wt.shape[0], X.shape[1], st))
 
 
 _side_streams = {}
@@ -177,19 +215,40 @@ def _side_stream(device):
     return st
 
 
+def _beside_prepare(W, from_kernel, kernel_ready, X, Xq, unit_alphabet, rows):
+    """The two independent halves of a Dense layer on two HIP streams: from_kernel() -- what depends on the kernel W alone (the median,
+    the alphabet, the radii) -- on the side stream; the row norms and the record pre-pass, which depend on the activations alone, on the
+    caller's (gpfq_dense_layer_prepare for `rows` neurons); ONE join.  kernel_ready says when W was complete: None -- unknown, the side
+    stream first waits for everything outstanding on the caller's (always safe; the wait then sits on the longer of the two chains and the
+    overlap buys little); a torch.cuda.Event -- the side stream waits for that; True -- W was complete before anything now outstanding
+    here was queued (a trained network's analog kernel: the reference never writes it), no wait at all.
+    Returns (from_kernel()'s tuple of tensors / DeviceAlphabets, the prepared workspace)."""
+    main = torch.cuda.current_stream(W.device)
+    side = _side_stream(W.device)
+    if kernel_ready is None:
+        side.wait_stream(main)
+    elif kernel_ready is not True:
+        side.wait_event(kernel_ready)
+    with torch.cuda.stream(side):
+        made = from_kernel()
+    W.record_stream(side)                                         # (the allocator's bookkeeping: both streams use W and what was made of it)
+    for t in made:
+        getattr(t, "buf", t).record_stream(main)
+    ws = hip.dense_layer_workspace(X.shape[0], X.shape[1], rows, W.device)
+    hip.dense_layer_prepare(X, Xq, unit_alphabet, rows, ws)
+    main.wait_stream(side)
+    return made, ws
+
+
 def quantize_dense_layer(W, X, Xq, unit_alphabet, alphabet_scalar, group=None, want_resid=True, log=None, check=True, overlap=False,
                          kernel_ready=None):
     """The body of _quantize_layer_parallel (scripts/quantized_network.py:523-574) from "the activations are there" to the tensors
     set_weights takes, with nothing crossing to the host: median of |W| -> rad * alphabet on the device (:544-545), row norms, record
     pre-pass, the recurrence reading the Keras kernel in place.
 
-    overlap=True runs its two independent halves on two HIP streams: the median and the alphabet depend on the kernel W alone and go to a
-    side stream; the row norms and the record pre-pass depend on the activations alone and stay on this one (gpfq_dense_layer_prepare);
-    ONE join, then the alphabet-dependent rest (gpfq_dense_layer_run).  kernel_ready says when W was complete: None -- unknown, the side
-    stream first waits for everything outstanding on this one (always safe; the wait then sits on the longer of the two chains and the
-    overlap buys little); a torch.cuda.Event -- the side stream waits for that; True -- W was complete before anything now outstanding
-    here was queued (a trained network's analog kernel: the reference never writes it), no wait at all: the median of layer k + 1 then
-    also fills the tail of layer k.  Measured at the north-star layer: 3.05 -> 3.00 ms per layer (profiles/r06/overlap_ab.txt).
+    overlap=True runs the median and the alphabet on a side stream beside the row norms and the record pre-pass (_beside_prepare, which
+    also explains kernel_ready), then the alphabet-dependent rest (gpfq_dense_layer_run); with kernel_ready=True the median of layer
+    k + 1 also fills the tail of layer k.  Measured at the north-star layer: 3.05 -> 3.00 ms per layer (profiles/r06/overlap_ab.txt).
     (Round 6's first scheme -- the pre-pass on the side stream behind a fork wait -- measured a wash and is gone.)
 
     Same tensors as quantize_dense(W, X, Xq, rad * unit_alphabet), bit for bit.  Returns its dict + "alphabet" (the hip.DeviceAlphabet)."""
@@ -198,24 +257,11 @@ def quantize_dense_layer(W, X, Xq, unit_alphabet, alphabet_scalar, group=None, w
     lo, hi = shard_bounds(C, world, rank)
     m = X.shape[1]
     side_ok = world == 1 or W.numel() < _SHARDED_MEDIAN_MIN      # (the sharded median's collectives stay on the caller's stream)
-    if not (overlap and side_ok and W.numel() and m > 0 and hi > lo and hip.dense_layer_supported(N, m, hi - lo, unit_alphabet)):
-        dalpha = layer_alphabet_device(W, unit_alphabet, alphabet_scalar, group)
-        out = quantize_dense(W, X, Xq, dalpha, group=group, want_resid=want_resid, log=log, check=check)
-        out["alphabet"] = dalpha
-        return out
-    main = torch.cuda.current_stream(W.device)
-    side = _side_stream(W.device)
-    if kernel_ready is None:
-        side.wait_stream(main)
-    elif kernel_ready is not True:
-        side.wait_event(kernel_ready)
-    with torch.cuda.stream(side):
-        dalpha = layer_alphabet_device(W, unit_alphabet, alphabet_scalar, None)
-    W.record_stream(side)                                         # (the allocator's bookkeeping: both streams use W and the alphabet block)
-    dalpha.buf.record_stream(main)
-    ws = hip.dense_layer_workspace(N, m, hi - lo, W.device)
-    hip.dense_layer_prepare(X, Xq, unit_alphabet, hi - lo, ws)
-    main.wait_stream(side)
+    if overlap and side_ok and W.numel() and m > 0 and hi > lo and hip.dense_layer_supported(N, m, hi - lo, unit_alphabet):
+        (dalpha,), ws = _beside_prepare(W, lambda: (layer_alphabet_device(W, unit_alphabet, alphabet_scalar, None),), kernel_ready,
+                                        X, Xq, unit_alphabet, hi - lo)
+    else:
+        dalpha, ws = layer_alphabet_device(W, unit_alphabet, alphabet_scalar, group), None
     out = quantize_dense(W, X, Xq, dalpha, group=group, want_resid=want_resid, log=log, check=check, prepared=ws)
     out["alphabet"] = dalpha
     return out
@@ -233,94 +279,60 @@ def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, ch
 
     Returns dict(Q f32 [N][C], idx i8 [N][C], resid f64 [C]) on every rank.  want_resid=None: residual norms only
     where the kernel holds the residual anyway (NaN from the Gram path, which would replay it in an extra pass).
+    Deferred failures are logged and repaired before anything is returned or sent to another rank (_launch_repaired).
     check=False (device alphabets; benchmarks): the deferred status of the launch is NOT read here -- no host wait at all; the result
     carries "workspace" and the caller owes hip.call_status(result) before it trusts Q.
     """
     N, C = W.shape
+    m = X.shape[1]
     world, rank = _group_info(group)
     lo, hi = shard_bounds(C, world, rank)
-    dalpha = alphabet if isinstance(alphabet, hip.DeviceAlphabet) else None
-    no_cluster = False                                            # (a timed-out exchange of the device alphabet's launch: the host path without the cluster form)
-    if dalpha is not None and not (X.shape[1] > 0 and hip.dense_layer_supported(N, X.shape[1], max(hi - lo, 1), dalpha.unit)):
-        alphabet, dalpha = dalpha.values(), None                   # (no block-pipelined kernel for this shape: the host alphabet's paths)
     Wc = W.contiguous()
-    if dalpha is not None:
-        r = hip.quantize_dense_layer(X, Xq, Wc, dalpha, lo, hi, keras_out=(world == 1), want_values=(world == 1), want_resid=want_resid,
-                                     prepared=prepared)           # (prepared: quantize_dense_layer's side stream has run the pre-pass into this workspace)
-        # (the status costs one host wait: skipped where nothing deferred can have happened -- the caller knows the radius is a finite
-        #  positive number, DeviceAlphabet.radius_ok, and the launch was not the cluster form)
-        need = check and not (getattr(dalpha, "radius_ok", False) and "cluster form" not in hip.last_dense_kernel())
-        st = hip.call_status(r) if need else 0
-        if st == hip.GPFQ_ERR_CLUSTER_TIMEOUT:
-            with hip.option("blk_cluster", 0):
-                classic = hip.dense_layer_supported(N, X.shape[1], max(hi - lo, 1), dalpha.unit)
-                if classic:
-                    _log_failure(log, f"Dense layer {N} x {C}: the cluster form's exchange timed out; rerunning the layer through the classic kernels")
-                    r = hip.quantize_dense_layer(X, Xq, Wc, dalpha, lo, hi, keras_out=(world == 1), want_values=(world == 1), want_resid=want_resid)
-                    st = hip.call_status(r)
-            if not classic:
-                # rows beyond the classic block shapes (more than 5120 samples): only the cluster form reads a device alphabet there --
-                # the host alphabet's kernels (several wavefronts per neuron, the streaming kernel) take the layer, with the cluster form off
-                _log_failure(log, f"Dense layer {N} x {C}: the cluster form's exchange timed out and no classic block kernel takes rows of "
-                                  f"{X.shape[1]} samples; rerunning the layer with the host alphabet without the cluster form")
-                alphabet, dalpha, st, no_cluster = dalpha.values(), None, 0, True
-        if st == hip.GPFQ_ERR_ALPHABET:
-            # radius 0 / infinite / NaN (the median of a kernel that is mostly zeros), or members the kernel cannot index (a float32 radius
-            # of 0, a step that overflows): only the host alphabet's kernels take such a one
-            _log_failure(log, f"Dense layer {N} x {C}: the device alphabet (radius {float(dalpha.rad())!r}) is not one the block kernel "
-                              f"runs; rerunning the layer with the host alphabet")
-            alphabet, dalpha = dalpha.values(), None
-        elif st != 0:
-            raise hip.GpfqError(f"quantize_dense: status {st} after the fallback")
-    if dalpha is not None:
-        if world == 1:
-            out = dict(Q=r["Q"], idx=r["idx"], workspace=r["workspace"], cluster_err=torch.zeros(1, dtype=torch.int32, device=W.device))
-            if want_resid is not False:
-                out["resid"] = r["resid"]
-            return out
-        packed, bits = hip.pack_indices(r["idx"], len(dalpha))
-        Q, idx = hip.assemble_kernel_device(all_gather_units(packed, C, group).contiguous(), dalpha, bits=bits, N=N)
-        out = dict(Q=Q, idx=idx, workspace=r["workspace"], cluster_err=torch.zeros(1, dtype=torch.int32, device=W.device))
+    shard = []                                                    # neuron-major shard [C_local][N], laid out when a host alphabet first needs it
+
+    def launch(a):
+        nonlocal prepared
+        if isinstance(a, hip.DeviceAlphabet):
+            ws, prepared = prepared, None                         # (quantize_dense_layer's side stream has run the pre-pass into it: the first launch's only)
+            return hip.quantize_dense_layer(X, Xq, Wc, a, lo, hi, keras_out=(world == 1), want_values=(world == 1), want_resid=want_resid,
+                                            prepared=ws)
+        if not shard:
+            shard.append(hip.neuron_major(Wc, lo, hi))
+        if hi == lo:
+            return dict(idx=torch.empty((0, N), dtype=hip.index_dtype(len(a)), device=W.device),
+                        resid=torch.empty((0,), dtype=torch.float64, device=W.device), workspace=None)
+        return hip.quantize_neurons(X, Xq, shard[0], a, want_values=False, want_resid=want_resid)
+
+    def finish(r, a):
+        on_device = isinstance(a, hip.DeviceAlphabet)
+        if world > 1:
+            # only the indices travel over xGMI -- packed to 2 or 4 bits per weight when the alphabet allows; values are looked up while
+            # transposing to the Keras layout
+            packed, bits = hip.pack_indices(r["idx"], len(a))
+            assemble = hip.assemble_kernel_device if on_device else hip.assemble_kernel
+            Q, idx = assemble(all_gather_units(packed, C, group).contiguous(), a, bits=bits, N=N)
+        else:
+            Q, idx = (r["Q"], r["idx"]) if on_device else hip.assemble_kernel(r["idx"], a)
+        out = dict(Q=Q, idx=idx)
+        if on_device:
+            out["workspace"] = r["workspace"]
         if want_resid is not False:
             out["resid"] = all_gather_units(r["resid"], C, group)
         return out
-    Wt = hip.neuron_major(Wc, lo, hi)                            # neuron-major shard [C_local][N]
-    deferred = None
-    with (hip.option("blk_cluster", 0) if no_cluster else contextlib.nullcontext()):
-        if hi > lo:
-            if world > 1:
-                # (a rank whose exchange timed out repairs its shard BEFORE the all-gather: the other ranks never see garbage and nobody
-                #  has to agree on anything)
-                r = quantize_neurons_checked(X, Xq, Wt, alphabet, log=log, want_values=False, want_resid=want_resid)
-            else:
-                # one GPU: the assembly pass is queued behind the kernel first and the status read after it -- the host's wait then costs no
-                # bubble between the two (cfg4's Dense(128 -> 10): 0.06 ms of a 0.15 ms layer); nothing is RETURNED unchecked
-                r = hip.quantize_neurons(X, Xq, Wt, alphabet, want_values=False, want_resid=want_resid)
-                deferred = r if "cluster form" in hip.last_dense_kernel() else None
-            i_loc, res_loc = r["idx"], r["resid"]
-        else:
-            i_loc = torch.empty((0, N), dtype=hip.index_dtype(len(alphabet)), device=W.device)
-            res_loc = torch.empty((0,), dtype=torch.float64, device=W.device)
-    # only the indices travel over xGMI -- packed to 2 or 4 bits per weight when the alphabet allows;
-    # values are looked up while transposing to the Keras layout
-    if world > 1:
-        packed, bits = hip.pack_indices(i_loc, len(alphabet))
-        Q, idx = hip.assemble_kernel(all_gather_units(packed, C, group).contiguous(), alphabet, bits=bits, N=N)
-    else:
-        Q, idx = hip.assemble_kernel(i_loc, alphabet)
-        if deferred is not None and hip.call_status(deferred) != 0:
-            _log_failure(log, f"Dense layer {N} x {C}: the cluster form's exchange timed out; rerunning the layer through the classic kernels")
-            with hip.option("blk_cluster", 0):
-                r = hip.quantize_neurons(X, Xq, Wt, alphabet, want_values=False, want_resid=want_resid)
-                if hip.call_status(r) != 0:
-                    raise hip.GpfqError("quantize_dense failed again without the cluster form")
-            res_loc = r["resid"]
-            Q, idx = hip.assemble_kernel(r["idx"], alphabet)
-    # (cluster_err: kept for callers of round 5's interface -- a timed-out exchange no longer leaves this function, see quantize_neurons_checked)
-    out = dict(Q=Q, idx=idx, cluster_err=torch.zeros(1, dtype=torch.int32, device=W.device))
-    if want_resid is not False:
-        out["resid"] = all_gather_units(res_loc, C, group)
-    return out
+
+    def line(what, a, st):
+        if world > 1 and not isinstance(a, hip.DeviceAlphabet):
+            return _neurons_timed_out(hi - lo, m, st)
+        if what == "alphabet":
+            return (f"Dense layer {N} x {C}: the device alphabet (radius {float(a.rad())!r}) is not one the block kernel runs; rerunning "
+                    f"the layer with the host alphabet")
+        if what == "no classic":
+            return (f"Dense layer {N} x {C}: the cluster form's exchange timed out and no classic block kernel takes rows of {m} samples; "
+                    f"rerunning the layer with the host alphabet without the cluster form")
+        return f"Dense layer {N} x {C}: the cluster form's exchange timed out; rerunning the layer through the classic kernels"
+
+    return _launch_repaired(launch, finish, alphabet, log, line, check=check, status_first=world > 1,
+                            block_kernel=lambda a: m > 0 and hip.dense_layer_supported(N, m, max(hi - lo, 1), a.unit))
 
 
 # ------------------------------------------------------------------------------------------
@@ -558,7 +570,7 @@ def quantize_dense_channels(W, X, Xq, unit_alphabet, alphabet_scalar, group=None
 
     Sharded (group): every rank computes all radii itself (deterministic, no collective) and scales only its own neurons; the one
     all-gather still carries packed indices only.  overlap=True: the median and the radii / W' launch go to a side stream beside the row
-    norms and the record pre-pass (kernel_ready as for quantize_dense_layer).
+    norms and the record pre-pass (_beside_prepare, which explains kernel_ready).
 
     Returns quantize_dense's dict with Q, resid as above + "radii" (f64 [C]) and "layer_median" (f32 device scalar)."""
     N, C = W.shape
@@ -569,25 +581,11 @@ def quantize_dense_channels(W, X, Xq, unit_alphabet, alphabet_scalar, group=None
     Wc = W.detach().contiguous()
     dalpha = _unit_alphabet_device(unit, W.device) if len(unit) <= 64 else None
     alphabet = dalpha if dalpha is not None else unit
-    if not (overlap and dalpha is not None and Wc.numel() and m > 0 and hi > lo and hip.dense_layer_supported(N, m, hi - lo, unit)):
-        med, r, Wp = _channel_radii(Wc, alphabet_scalar, (lo, hi))
-        out = quantize_dense(Wp, X, Xq, alphabet, group=group, want_resid=want_resid, log=log, check=check)
+    if overlap and dalpha is not None and Wc.numel() and m > 0 and hi > lo and hip.dense_layer_supported(N, m, hi - lo, unit):
+        (med, r, Wp), ws = _beside_prepare(Wc, lambda: _channel_radii(Wc, alphabet_scalar, (lo, hi)), kernel_ready, X, Xq, unit, hi - lo)
     else:
-        main = torch.cuda.current_stream(W.device)
-        side = _side_stream(W.device)
-        if kernel_ready is None:
-            side.wait_stream(main)
-        elif kernel_ready is not True:
-            side.wait_event(kernel_ready)
-        with torch.cuda.stream(side):
-            med, r, Wp = _channel_radii(Wc, alphabet_scalar, (lo, hi))
-        Wc.record_stream(side)                                    # (the allocator's bookkeeping, as in quantize_dense_layer)
-        for t in (med, r, Wp):
-            t.record_stream(main)
-        ws = hip.dense_layer_workspace(N, m, hi - lo, W.device)
-        hip.dense_layer_prepare(X, Xq, unit, hi - lo, ws)
-        main.wait_stream(side)
-        out = quantize_dense(Wp, X, Xq, dalpha, group=group, want_resid=want_resid, log=log, check=check, prepared=ws)
+        (med, r, Wp), ws = _channel_radii(Wc, alphabet_scalar, (lo, hi)), None
+    out = quantize_dense(Wp, X, Xq, alphabet, group=group, want_resid=want_resid, log=log, check=check, prepared=ws)
     out["Q"], _ = hip.assemble_kernel_colrad(out["idx"], unit, r, layout=hip.GPFQ_LAYOUT_KERAS)
     if "resid" in out:
         out["resid"] = out["resid"] * r
