@@ -397,6 +397,47 @@ int gpfq_assemble_kernel_colrad(const void *qidx, int bits, int layout, const do
                                 int64_t N, int64_t C, float *Q, void *qidx_t, void *stream);
 
 /*
+ * Search over the alphabet scalar (a sequence as alphabet_scalar).  K candidate scalars s_0 .. s_{K-1}
+ * (1 <= K <= GPFQ_SEARCH_MAX_CANDIDATES, each a finite positive number) are K * C independent columns of one walk with the unit
+ * alphabet: candidate k of output channel j is column k * C + j (k-major: candidate k is a contiguous block of C columns).
+ *
+ * gpfq_candidate_kernels: with the base radius b_j = base_radii[j] (a [device] f64 [C] array such as gpfq_column_radii writes with
+ * alphabet_scalar 1.0: per = "channel") or, when base_radii is NULL, b_j = float64(*layer_median) for every j, 0 where that is not
+ * a finite positive number (layer_median: a [device] f32 scalar such as gpfq_median_abs writes: per = "layer") -- exactly one of the
+ * two is given --
+ *   radii[k * C + j] = float64(s_k) * b_j                                          for all K * C columns, and
+ *   W_cand[i][k * C + j] = float32(float64(W[i][j]) / radii[k * C + j])            (0 where the radius is 0)
+ * for the columns [c_lo, c_hi) of the K * C; nothing else of W_cand is written.  One launch, no host synchronisation, no workspace;
+ * the scalars travel as kernel arguments.  W is read once and written K times.
+ *   W [device] f32 [R][ld], ld >= C; scalars [host] f64 [K]; radii [device] f64 [K * C];
+ *   W_cand [device] f32 [R][ldo], ldo >= K * C (may be NULL when c_lo == c_hi or R == 0).
+ *
+ * gpfq_select_candidates: from the walk's Keras-layout indices and residual norms rho [T][K * C] (T = 1 for a Dense layer, one row
+ * per input channel for a Conv2D layer),
+ *   scores[k * C + j] = sum_t (radii[k * C + j] * rho[t][k * C + j])^2             float64, t ascending;
+ *   per_layer == 0: best[j] = the first k with the smallest scores[k * C + j];
+ *   per_layer != 0: best[j] = the first k with the smallest total_k = sum_j scores[k * C + j] for every j, the sum taken by thread
+ *     x = 0 .. 255 of one workgroup over j = x, x + 256, ... ascending, then p[x] += p[x + s] for s = 128, 64, .. 1;
+ *   a NaN never wins against a number, and k = 0 wins when all K are NaN;
+ *   Q[t][j] = (float)(radii[e] * unit_alphabet[qidx[t][e]]), e = best[j] * C + j    (0.0f for the literal-zero index -1),
+ *   qidx_sel[t][j] = qidx[t][e],  radii_sel[j] = radii[e],  resid_sel[t][j] = radii[e] * rho[t][e].
+ * Two ordinary launches (scores and totals; selection and gather), no host synchronisation; only the winners' indices are read.
+ *   qidx [device] [N][K * C], i8 (bits = 8, M <= 64) or i16 (bits = 16, M > 64); may be NULL when Q and qidx_sel are;
+ *   resid [device] f64 [T][K * C]; radii [device] f64 [K * C]; unit_alphabet [host] f64 [M];
+ *   best [device] i32 [C]; scores [device] f64 [K * C]; Q [device] f32 [N][C], qidx_sel [device] [N][C] of qidx's type,
+ *   radii_sel [device] f64 [C], resid_sel [device] f64 [T][C]: each of the last four may be NULL;
+ *   workspace [device], 8-byte aligned, >= gpfq_select_candidates_workspace_bytes(K, C): needed when per_layer != 0, else may be NULL.
+ */
+#define GPFQ_SEARCH_MAX_CANDIDATES 16
+int gpfq_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii, const float *layer_median,
+                           const double *scalars, int K, double *radii, float *W_cand, int64_t ldo, int64_t c_lo, int64_t c_hi,
+                           void *stream);
+size_t gpfq_select_candidates_workspace_bytes(int K, int64_t C);
+int gpfq_select_candidates(const void *qidx, int bits, int64_t N, int64_t C, int K, int64_t T, const double *resid, const double *radii,
+                           const double *unit_alphabet, int M, int per_layer, int32_t *best, double *scores, float *Q, void *qidx_sel,
+                           double *radii_sel, double *resid_sel, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * median(|W|) of n float32 weights with NumPy's semantics (float32 result; even n -> float32 mean of
  * the two middle values).  Replaces `median(abs(W.flatten()))` of the alphabet radius
  * (scripts/quantized_network.py:544, :831).  Exact radix select, no sort.

@@ -742,6 +742,72 @@ int gpfq_assemble_kernel_colrad(const void *qidx, int bits, int layout, const do
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_assemble_kernel_colrad");
 }
 
+int gpfq_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii, const float *layer_median,
+                           const double *scalars, int K, double *radii, float *W_cand, int64_t ldo, int64_t c_lo, int64_t c_hi,
+                           void *stream)
+{
+    if (R < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size R=%lld C=%lld", (long long)R, (long long)C);
+    if (K < 1 || K > GPFQ_SEARCH_MAX_CANDIDATES)
+        return fail(GPFQ_ERR_INVALID_ARG, "K=%d candidate scalars: must be 1..%d", K, GPFQ_SEARCH_MAX_CANDIDATES);
+    if (!scalars) return fail(GPFQ_ERR_INVALID_ARG, "scalars is NULL");
+    gpfq::SearchScalars S;
+    std::memset(&S, 0, sizeof(S));
+    S.K = K;
+    for (int k = 0; k < K; ++k) {
+        if (!(std::isfinite(scalars[k]) && scalars[k] > 0.0))
+            return fail(GPFQ_ERR_INVALID_ARG, "candidate scalar %d is %g: every candidate must be a finite positive number", k, scalars[k]);
+        S.s[k] = scalars[k];
+    }
+    if (!(c_lo >= 0 && c_lo <= c_hi && c_hi <= (int64_t)K * C))
+        return fail(GPFQ_ERR_INVALID_ARG, "candidate column range [%lld, %lld) outside [0, %lld]", (long long)c_lo, (long long)c_hi,
+                    (long long)((int64_t)K * C));
+    if (C == 0) return GPFQ_OK;
+    if (!radii) return fail(GPFQ_ERR_INVALID_ARG, "radii is NULL");
+    if ((base_radii != nullptr) == (layer_median != nullptr))
+        return fail(GPFQ_ERR_INVALID_ARG, "exactly one of base_radii (one per channel) and layer_median (one for the layer) must be given");
+    const bool scale = R > 0 && c_hi > c_lo;
+    if (scale) {
+        if (!W) return fail(GPFQ_ERR_INVALID_ARG, "W is NULL");
+        if (ld < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ld=%lld < C=%lld", (long long)ld, (long long)C);
+        if (!W_cand) return fail(GPFQ_ERR_INVALID_ARG, "W_cand is NULL with a column range to write");
+        if (ldo < (int64_t)K * C) return fail(GPFQ_ERR_INVALID_ARG, "W_cand pitch ldo=%lld < K * C=%lld", (long long)ldo, (long long)((int64_t)K * C));
+    }
+    hipError_t e = gpfq::launch_candidate_kernels(W, R, C, ld, base_radii, layer_median, S, radii, scale ? W_cand : nullptr, ldo, c_lo, c_hi,
+                                                  static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_candidate_kernels");
+}
+
+size_t gpfq_select_candidates_workspace_bytes(int K, int64_t C)
+{
+    (void)K; (void)C;
+    return GPFQ_SEARCH_MAX_CANDIDATES * sizeof(double);      // the K totals of per_layer, handed from the first launch to the second
+}
+
+int gpfq_select_candidates(const void *qidx, int bits, int64_t N, int64_t C, int K, int64_t T, const double *resid, const double *radii,
+                           const double *unit_alphabet, int M, int per_layer, int32_t *best, double *scores, float *Q, void *qidx_sel,
+                           double *radii_sel, double *resid_sel, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (N < 0 || C < 0 || T < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size N=%lld C=%lld T=%lld", (long long)N, (long long)C, (long long)T);
+    if (K < 1 || K > GPFQ_SEARCH_MAX_CANDIDATES)
+        return fail(GPFQ_ERR_INVALID_ARG, "K=%d candidate scalars: must be 1..%d", K, GPFQ_SEARCH_MAX_CANDIDATES);
+    if (bits != 8 && bits != 16) return fail(GPFQ_ERR_INVALID_ARG, "bits=%d: candidate indices are plain int8 (8) or int16 (16)", bits);
+    HostAlphabet H;
+    int rc = make_alphabet(unit_alphabet, M, -1, &H);
+    if (rc != GPFQ_OK) return rc;
+    if ((bits == 16) != H.is_big)
+        return fail(GPFQ_ERR_INVALID_ARG, "alphabets of %d members have %s indices (gpfq_index_bits)", M, H.is_big ? "int16" : "int8");
+    if (C == 0) return GPFQ_OK;
+    if (!radii || !best || !scores) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer (radii, best and scores are required)");
+    if (T > 0 && !resid) return fail(GPFQ_ERR_INVALID_ARG, "resid is NULL");
+    if (N > 0 && (Q || qidx_sel) && !qidx) return fail(GPFQ_ERR_INVALID_ARG, "qidx is NULL with Q or qidx_sel to gather");
+    if (per_layer && (!workspace || workspace_bytes < gpfq_select_candidates_workspace_bytes(K, C) || (uintptr_t)workspace % 8 != 0))
+        return fail(GPFQ_ERR_WORKSPACE, "per-layer selection needs %zu aligned workspace bytes", gpfq_select_candidates_workspace_bytes(K, C));
+    hipError_t e = gpfq::launch_select_candidates(qidx, bits, N, C, K, T, resid, radii, H.A, H.big(), per_layer ? 1 : 0, best, scores, Q,
+                                                  qidx_sel, radii_sel, resid_sel, static_cast<double *>(workspace),
+                                                  static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_select_candidates");
+}
+
 size_t gpfq_median_abs_workspace_bytes(void) { return gpfq::median_workspace_bytes() + 64; }
 size_t gpfq_median_abs_workspace_bytes_for(int64_t n) { return n > 0 ? gpfq::median_workspace_bytes_fast(n) : gpfq::median_workspace_bytes() + 64; }
 

@@ -264,6 +264,22 @@ hipError_t launch_column_radii(const float *W, int64_t R, int64_t C, int64_t ld,
                                double *radii, float *Wp, int64_t ldo, int64_t c_lo, int64_t c_hi, hipStream_t stream);
 hipError_t launch_assemble_colrad(const void *qidx, int bits, int keras_layout, const AlphabetArg &A, const AlphabetBig *big,
                                   const double *radii, int64_t N, int64_t C, float *Q, void *idxT, hipStream_t stream);
+// gpfq_search.hip (a sequence as alphabet_scalar): the K candidate scalars travel by value
+constexpr int kSearchMaxK = 16;
+struct SearchScalars {
+    double s[kSearchMaxK];
+    int K;
+};
+// radii[k * C + j] = s_k * b_j (b_j = base_radii[j], or the layer median for every j when base_radii is NULL) and, for the columns
+// [c_lo, c_hi) of [R][K * C], Wc[i][k * C + j] = float32(float64(W[i][j]) / radii[k * C + j]) (0 where the radius is 0)
+hipError_t launch_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii,
+                                    const float *layer_median, const SearchScalars &S, double *radii, float *Wc, int64_t ldo,
+                                    int64_t c_lo, int64_t c_hi, hipStream_t stream);
+// two launches: scores (+ the K totals of per_layer) and select + gather; totals [device] f64 [K] (per_layer only)
+hipError_t launch_select_candidates(const void *qidx, int bits, int64_t N, int64_t C, int K, int64_t T, const double *resid,
+                                    const double *radii, const AlphabetArg &A, const AlphabetBig *big, int per_layer, int32_t *best,
+                                    double *scores, float *Q, void *qsel, double *radii_sel, double *resid_sel, double *totals,
+                                    hipStream_t stream);
 size_t median_workspace_bytes();
 size_t median_workspace_bytes_fast(int64_t n);   // ... with room for the one-GPU form's candidate list (gpfq_median_abs_workspace_bytes_for)
 size_t channel_sumsq_workspace_bytes(int64_t Cin);

@@ -21,6 +21,7 @@ GPFQ_GRAM_MIN_M = 16384
 GPFQ_DEVICE_ALPHABET_BYTES = 1024
 GPFQ_LAYOUT_NEURON_MAJOR, GPFQ_LAYOUT_KERAS = 0, 1
 GPFQ_ERR_CLUSTER_TIMEOUT, GPFQ_ERR_ALPHABET = -6, -7
+GPFQ_SEARCH_MAX_CANDIDATES = 16    # candidate scalars of one search (include/gpfq.h)
 
 # every symbol include/gpfq.h declares: (restype, argtypes)
 _i64, _int, _vp, _sz = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
@@ -53,6 +54,10 @@ SYMBOLS = {
     "gpfq_column_radii_workspace_bytes": (_sz, [_i64, _i64]),
     "gpfq_column_radii": (_int, [_vp, _i64, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
     "gpfq_assemble_kernel_colrad": (_int, [_vp, _int, _int, _dp, _int, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "gpfq_candidate_kernels": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dp, _int, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "gpfq_select_candidates_workspace_bytes": (_sz, [_int, _i64]),
+    "gpfq_select_candidates": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _dp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                      _vp]),
     "gpfq_gram_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "gpfq_quantize_neurons_gram": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _i64, _dp, _int, _int, _i64, _i64, _i64,
                                           _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -821,6 +826,68 @@ def assemble_kernel_colrad(qidx, unit_alphabet, radii, bits=None, N=None, layout
                                                   idx_t.data_ptr() if idx_t is not None else None, _stream()),
                "gpfq_assemble_kernel_colrad")
     return Q, (qidx if layout == GPFQ_LAYOUT_KERAS else idx_t)
+
+
+def candidate_kernels(W2d, base, scalars, scale=None):
+    """The K candidate kernels of a search over the alphabet scalar (gpfq_candidate_kernels): radii f64 [K * C'] with
+    radii[k * C' + j] = float64(scalars[k]) * b_j and, with scale=(lo, hi), W'' f32 [R][K * C'] whose columns lo..hi of the K * C' hold
+    float32(float64(W2d[:, j]) / radii[k * C' + j]) (0 where the radius is 0; the rest of it unwritten), else None.  base: the base radii
+    b as an f64 [C'] device tensor (column_radii with scalar 1), or the layer median as an f32 device scalar [1] (b_j = the median for
+    every j, 0 where it is not finite and positive).  Returns (radii, W'').  One launch, no sync."""
+    _dev(W2d, torch.float32, "W2d")
+    if W2d.dim() != 2:
+        raise GpfqError("candidate_kernels needs a 2-D [R][C'] matrix")
+    Wc = W2d.contiguous()
+    R, C = Wc.shape
+    s = [float(v) for v in scalars]
+    K = len(s)
+    per_channel = base.dtype == torch.float64
+    _dev(base, torch.float64 if per_channel else torch.float32, "base")
+    if per_channel and (base.numel() != C or not base.is_contiguous()):
+        raise GpfqError(f"base radii must be a contiguous [{C}] tensor")
+    lo, hi = (0, 0) if scale is None else (int(scale[0]), int(scale[1]))
+    dev = W2d.device
+    radii = torch.empty(K * C, dtype=torch.float64, device=dev)
+    Wpp = torch.empty((R, K * C), dtype=torch.float32, device=dev) if scale is not None else None
+    with torch.cuda.device(dev):
+        _check(load().gpfq_candidate_kernels(Wc.data_ptr(), R, C, max(C, 1), base.data_ptr() if per_channel else None,
+                                             None if per_channel else base.data_ptr(), (ctypes.c_double * max(K, 1))(*s), K,
+                                             radii.data_ptr(), Wpp.data_ptr() if Wpp is not None else None, max(K * C, 1), lo, hi,
+                                             _stream()), "gpfq_candidate_kernels")
+    return radii, Wpp
+
+
+def select_candidates(qidx, resid, radii, unit_alphabet, K, per_layer=False, want_values=True):
+    """Scores, selection and gather of a search over the alphabet scalar (gpfq_select_candidates).  qidx [N][K * C] Keras-layout
+    indices of the K * C candidate columns (int8, int16 beyond 64 members), resid f64 [T][K * C] the walk's residual norms, radii f64
+    [K * C] (candidate_kernels).  Returns dict(best i32 [C], scores f64 [K][C], Q f32 [N][C], idx [N][C], radii f64 [C],
+    resid f64 [T][C] = radius * norm); per_layer: one candidate for the whole layer (the smallest sum of scores).  Two launches, no
+    sync."""
+    arr, M, _ = _alphabet(unit_alphabet)
+    bits = 16 if M > 64 else 8
+    _dev(qidx, index_dtype(M), "qidx"); _dev(resid, torch.float64, "resid"); _dev(radii, torch.float64, "radii")
+    if qidx.dim() != 2 or not qidx.is_contiguous() or resid.dim() != 2 or not resid.is_contiguous() or not radii.is_contiguous():
+        raise GpfqError("qidx and resid must be contiguous 2-D tensors, radii contiguous")
+    K = int(K)
+    N, KC = qidx.shape
+    if K < 1 or KC % K or radii.numel() != KC or resid.shape[1] != KC:
+        raise GpfqError(f"qidx {tuple(qidx.shape)}, resid {tuple(resid.shape)} and radii {tuple(radii.shape)} do not hold K={K} candidates")
+    C, T = KC // K, resid.shape[0]
+    dev = qidx.device
+    out = dict(best=torch.empty(C, dtype=torch.int32, device=dev), scores=torch.empty((K, C), dtype=torch.float64, device=dev),
+               Q=torch.empty((N, C), dtype=torch.float32, device=dev) if want_values else None,
+               idx=torch.empty((N, C), dtype=qidx.dtype, device=dev), radii=torch.empty(C, dtype=torch.float64, device=dev),
+               resid=torch.empty((T, C), dtype=torch.float64, device=dev))
+    lib = load()
+    nbytes = lib.gpfq_select_candidates_workspace_bytes(K, C) if per_layer else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        _check(lib.gpfq_select_candidates(qidx.data_ptr(), bits, N, C, K, T, resid.data_ptr(), radii.data_ptr(), arr, M,
+                                          1 if per_layer else 0, out["best"].data_ptr(), out["scores"].data_ptr(),
+                                          out["Q"].data_ptr() if want_values else None, out["idx"].data_ptr(), out["radii"].data_ptr(),
+                                          out["resid"].data_ptr(), ws.data_ptr() if ws is not None else None, nbytes, _stream()),
+               "gpfq_select_candidates")
+    return out
 
 
 def last_dense_kernel():

@@ -611,3 +611,156 @@ def quantize_conv2d_channels(W, act_w, act_q, unit_alphabet, alphabet_scalar, st
     out["resid"] = out["resid"] * (r.reshape(Cin, F) if depthwise else r.reshape(1, F))
     out["radii"], out["layer_median"] = r, med
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# a sequence as alphabet_scalar: search the scalar on the device
+# ------------------------------------------------------------------------------------------
+# One walk call takes whole candidates while its kernel W'' [rows][g * C] stays below this many elements (8 GiB of float32, and every
+# element offset of the passes around the walk within 32 bits); beyond it the candidates are split into groups of g.
+_SEARCH_MAX_ELEMS = (1 << 31) - 1
+
+
+def check_scalars(alphabet_scalar):
+    """The candidates of a search as a list of floats: 1..16 finite positive numbers (ValueError names the offender otherwise)."""
+    if isinstance(alphabet_scalar, (str, bytes)):
+        raise ValueError(f"alphabet_scalar must be a number or a sequence of 1..{hip.GPFQ_SEARCH_MAX_CANDIDATES} numbers, got "
+                         f"{alphabet_scalar!r}")
+    try:
+        raw = list(alphabet_scalar)
+    except TypeError:
+        raise ValueError(f"alphabet_scalar candidates must be a sequence of numbers, got {alphabet_scalar!r}")
+    if not 1 <= len(raw) <= hip.GPFQ_SEARCH_MAX_CANDIDATES:
+        raise ValueError(f"alphabet_scalar holds {len(raw)} candidates: a search takes 1..{hip.GPFQ_SEARCH_MAX_CANDIDATES}")
+    out = []
+    for v in raw:
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"alphabet_scalar candidate {v!r} is not a number")
+        if not (np.isfinite(f) and f > 0):
+            raise ValueError(f"alphabet_scalar candidate {v!r} is not a finite positive number")
+        out.append(f)
+    return out
+
+
+def _check_per(per):
+    if per not in ("channel", "layer"):
+        raise ValueError(f"per must be 'channel' or 'layer', got {per!r}")
+    return per == "layer"
+
+
+def _candidate_groups(K, rows, C):
+    """[k_lo, k_hi) of the groups of whole candidates one walk call takes: the fewest equal-sized groups whose kernel
+    [rows][g * C] stays within _SEARCH_MAX_ELEMS elements (one candidate per group at the least)."""
+    g = max(1, min(K, _SEARCH_MAX_ELEMS // max(rows * C, 1)))
+    n = -(-K // g)
+    g = -(-K // n)
+    return [(k, min(k + g, K)) for k in range(0, K, g)]
+
+
+def _search_base(W2d, per_layer):
+    """(layer median f32 device scalar, the base radii of a search): per="channel" the radii of scalar 1 (f64 [C'], two launches), per="layer" the
+    median itself (the candidate kernel broadcasts it).  No sync."""
+    if W2d.numel() == 0:
+        return None, torch.zeros(W2d.shape[1], dtype=torch.float64, device=W2d.device)
+    med = hip.median_abs(W2d.reshape(-1), on_device=True)
+    return med, (med if per_layer else hip.column_radii(W2d, 1.0, layer_median=med)[0])
+
+
+def quantize_dense_search(W, X, Xq, unit_alphabet, alphabet_scalars, per="channel", group=None, overlap=False, kernel_ready=None,
+                          log=None, check=True):
+    """quantize_dense with the alphabet scalar SEARCHED over the candidates alphabet_scalars = (s_0 .. s_{K-1}), 1 <= K <= 16: base
+    radius b_j = median(|W[:, j]|) (per="channel"; the layer median where that is not finite and positive, then 0) or median(|W|) for
+    every j (per="layer"), r_{k,j} = s_k * b_j, and ONE quantize_dense call -- every kernel, fallback and repair as there -- walks the
+    K * C columns W''[:, k * C + j] = float32(W[:, j] / r_{k,j}) with the unit alphabet (a device alphabet of radius 1 up to 64 members).
+    Candidate k of neuron j scores (r_{k,j} * its residual norm)^2; per="channel" keeps, for every neuron, the first candidate with
+    the smallest score, per="layer" the first candidate with the smallest sum over the neurons (hip.select_candidates: on the device,
+    in a fixed order).  The search ALWAYS walks the rescaled kernel, also for per="layer" and for K = 1: [s] with per="channel" is
+    quantize_dense_channels(.., s) bit for bit, [s] with per="layer" is the reference's un-rescaled walk only up to the rounding of W''
+    (DESIGN.md section 8 measured 0.006-0.04 % of the indices).
+
+    Candidates are split into groups of whole candidates where one call cannot take all K * C columns (_candidate_groups); the columns
+    are independent, the result is the same.  Sharded (group): every rank forms all radii, quantize_dense shards the K * C columns and
+    its one all-gather brings every candidate's indices and norms to every rank (K times the traffic of one candidate); every rank
+    selects for itself.  overlap=True: the median, the radii and the candidate launch go to a side stream beside the row norms and the
+    record pre-pass for the K * C columns (_beside_prepare, which explains kernel_ready).  check=False holds for a single group only.
+
+    Returns dict(Q f32 [N][C], idx [N][C], resid f64 [C] = r * norm, radii f64 [C] -- all of the selected candidates --, best i32 [C],
+    scores f64 [K][C], layer_median f32 device scalar)."""
+    scalars = check_scalars(alphabet_scalars)
+    per_layer = _check_per(per)
+    K = len(scalars)
+    N, C = W.shape
+    world, rank = _group_info(group)
+    m = X.shape[1]
+    unit = np.asarray(unit_alphabet, dtype=np.float64)
+    Wc = W.detach().contiguous()
+    dalpha = _unit_alphabet_device(unit, W.device) if len(unit) <= 64 else None
+    alphabet = dalpha if dalpha is not None else unit
+    groups = _candidate_groups(K, N, C)
+    base = {}
+    parts = []
+    for k_lo, k_hi in groups:
+        gC = (k_hi - k_lo) * C
+        lo, hi = shard_bounds(gC, world, rank)
+
+        def from_kernel():
+            if not base:
+                base["med"], base["b"] = _search_base(Wc, per_layer)
+            return (base["med"], base["b"]) + hip.candidate_kernels(Wc, base["b"], scalars[k_lo:k_hi], scale=(lo, hi))
+
+        if overlap and dalpha is not None and Wc.numel() and m > 0 and hi > lo and hip.dense_layer_supported(N, m, hi - lo, unit):
+            made, ws = _beside_prepare(Wc, from_kernel, kernel_ready, X, Xq, unit, hi - lo)
+        else:
+            made, ws = from_kernel(), None
+        r, Wpp = made[2], made[3]
+        out = quantize_dense(Wpp, X, Xq, alphabet, group=group, want_resid=True, log=log, check=check or len(groups) > 1, prepared=ws)
+        parts.append((out, r))
+    if len(parts) == 1:
+        idx, resid, r = parts[0][0]["idx"], parts[0][0]["resid"], parts[0][1]
+    else:                                                         # (k-major blocks: the groups' columns back to back)
+        idx = torch.cat([p[0]["idx"] for p in parts], dim=1)
+        resid = torch.cat([p[0]["resid"] for p in parts])
+        r = torch.cat([p[1] for p in parts])
+    sel = hip.select_candidates(idx.contiguous(), resid.reshape(1, K * C).contiguous(), r, unit, K, per_layer)
+    res = dict(Q=sel["Q"], idx=sel["idx"], resid=sel["resid"].reshape(C), radii=sel["radii"], best=sel["best"], scores=sel["scores"],
+               layer_median=base["med"])
+    if len(parts) == 1 and "workspace" in parts[0][0]:
+        res["workspace"] = parts[0][0]["workspace"]
+    return res
+
+
+def quantize_conv2d_search(W, act_w, act_q, unit_alphabet, alphabet_scalars, strides, padding, rate, per="channel", group=None):
+    """quantize_conv2d with the alphabet scalar searched per filter (per="channel") or for the layer (per="layer"), as
+    quantize_dense_search: the output channels are the columns f of the view [kh*kw*Cin][F], the candidates the K * F columns of
+    W'' viewed as (kh, kw, Cin, K * F), walked by ONE quantize_conv2d(.., want_resid=True) call per group of candidates (its reruns and
+    sharding included).  Candidate k of filter f scores sum_c (r_{k,f} * norm[c][k * F + f])^2 over the input channels c, ascending.
+    1 x 1 kernels go through the same call and the same formula.  DepthwiseConv2D kernels are not searched (their output channels
+    are (c, d) pairs, which the k-major blocks of (kh, kw, Cin, K * mult) do not hold).
+
+    Returns dict(Q f32 [kh][kw][Cin][F], idx same shape, resid f64 [Cin][F] = r * norm, radii f64 [F], best i32 [F],
+    scores f64 [K][F], layer_median, reruns)."""
+    scalars = check_scalars(alphabet_scalars)
+    per_layer = _check_per(per)
+    K = len(scalars)
+    kh, kw, Cin, F = W.shape
+    R = kh * kw * Cin
+    unit = np.asarray(unit_alphabet, dtype=np.float64)
+    W2 = W.detach().contiguous().reshape(R, F)
+    med, b = _search_base(W2, per_layer)
+    idx, resid, radii, reruns = [], [], [], 0
+    for k_lo, k_hi in _candidate_groups(K, R, F):
+        g = k_hi - k_lo
+        r, Wpp = hip.candidate_kernels(W2, b, scalars[k_lo:k_hi], scale=(0, g * F))
+        out = quantize_conv2d(Wpp.reshape(kh, kw, Cin, g * F), act_w, act_q, unit, strides, padding, rate, group=group, want_resid=True)
+        idx.append(out["idx"].reshape(R, g * F))
+        resid.append(out["resid"])
+        radii.append(r)
+        reruns = out["reruns"] + reruns
+    one = len(idx) == 1
+    sel = hip.select_candidates((idx[0] if one else torch.cat(idx, dim=1)).contiguous(),
+                                (resid[0] if one else torch.cat(resid, dim=1)).contiguous(), radii[0] if one else torch.cat(radii),
+                                unit, K, per_layer)
+    return dict(Q=sel["Q"].reshape(kh, kw, Cin, F), idx=sel["idx"].reshape(kh, kw, Cin, F), resid=sel["resid"], radii=sel["radii"],
+                best=sel["best"], scores=sel["scores"], layer_median=med, reruns=reruns)

@@ -17,7 +17,9 @@ process' GPU) and ``process_group`` (a ``torch.distributed`` group over which th
 layer -- and the samples of the activation capture in between -- are sharded), and ``fix_partial_batch`` to opt out of the reference's
 partial-last-batch layout quirk (:491-495).  ``radius="channel"`` gives every output channel (Dense neuron, conv filter, depthwise
 output channel) an alphabet radius of its own instead of the reference's one per layer; the default
-``radius="layer"`` is the reference's rule.
+``radius="layer"`` is the reference's rule.  A sequence of 1..16 numbers as ``alphabet_scalar`` searches the scalar on the device:
+every candidate is walked in the same launch and each output channel (``radius="channel"``) or the layer (``radius="layer"``) keeps
+the candidate with the smallest output error on the calibration data; a plain number is today's behaviour.
 """
 import logging
 from collections import namedtuple
@@ -129,6 +131,24 @@ def _check_radius(radius):
     return radius
 
 
+def _scalar_candidates(alphabet_scalar):
+    """None for a plain number (the reference's alphabet_scalar, used as it is), else the validated candidates of a search
+    (layer.check_scalars: 1..16 finite positive numbers, ValueError otherwise)."""
+    try:
+        plain = np.ndim(alphabet_scalar) == 0 and not isinstance(alphabet_scalar, (str, bytes))
+    except Exception:
+        plain = False
+    return None if plain else _layer.check_scalars(alphabet_scalar)
+
+
+def _search_stats(out, alphabet, **extra):
+    """last_layer_stats of a searched layer: rad = the selected radii (f64 per output channel), scalar_idx = the selected candidate per
+    channel (constant for radius="layer"), scores [K][channels], layer_rad = NaN (there is not a single one); all left on the device
+    until read.  The search always walks the rescaled kernel: alphabet = the unit alphabet."""
+    return _LazyStats(rad=out["radii"], scalar_idx=out["best"], scores=out["scores"], layer_rad=np.float64(np.nan),
+                      alphabet=np.asarray(alphabet, dtype=np.float64), resid=out["resid"], idx=out["idx"], **extra)
+
+
 def _channel_stats(out, alphabet, alphabet_scalar, **extra):
     """last_layer_stats of a radius="channel" layer: rad = the radii (f64 [channels]), layer_rad = alphabet_scalar * median(|W|), both
     left on the device until read; alphabet = the unit alphabet the walk used."""
@@ -187,6 +207,7 @@ class QuantizedNeuralNetwork:
         # batch_size and mini_batch_size are accepted and ignored, as in the reference (:371-400):
         # the sample count comes from get_data alone.
         self.radius = _check_radius(radius)
+        self.alphabet_scalars = _scalar_candidates(alphabet_scalar)      # a sequence: search the scalar
         self.get_data = get_data
         self.trained_net = network
         self.quantized_net = clone_model(network)
@@ -655,7 +676,7 @@ class QuantizedNeuralNetwork:
         wX, qX = self._get_layer_data_generator(layer_idx, transpose=True)
         self._log(f"\tdone. {time()-tic:2f} seconds.")
 
-        if self.radius == "channel":
+        if self.alphabet_scalars is not None or self.radius == "channel":
             self._quantize_layer_channels(layer_idx, Wd, wX, qX)
             return
         layer_alphabet, rad = self._layer_alphabet(Wd, layer_idx)
@@ -680,20 +701,28 @@ class QuantizedNeuralNetwork:
 
     def _quantize_layer_channels(self, layer_idx, Wd, wX, qX):
         """radius="channel": the radii, the scaled kernel and the walk all queued on the device (layer.quantize_dense_channels); no
-        host wait for the radii."""
+        host wait for the radii.  A sequence as alphabet_scalar: the same with every candidate walked in one call and the selection
+        on the device (layer.quantize_dense_search, either radius)."""
         N_ell_plus_1 = Wd.shape[1]
+        search = self.alphabet_scalars is not None
         self._log("\tQuantizing neurons (in parallel)...")
         tic = time()
         try:
-            out = _layer.quantize_dense_channels(Wd, wX, qX, self.alphabet, self.alphabet_scalar, group=self.process_group, want_resid=None,
-                                                 log=lambda msg: self._log(f"\t\tLayer {layer_idx}: {msg}"))
+            log = lambda msg: self._log(f"\t\tLayer {layer_idx}: {msg}")
+            if search:
+                out = _layer.quantize_dense_search(Wd, wX, qX, self.alphabet, self.alphabet_scalars, per=self.radius,
+                                                   group=self.process_group, log=log)
+            else:
+                out = _layer.quantize_dense_channels(Wd, wX, qX, self.alphabet, self.alphabet_scalar, group=self.process_group,
+                                                     want_resid=None, log=log)
         except Exception as exc:
             self._log(f"\t\tLayer {layer_idx} generated an exception: {exc}")
             raise exc
         self._log_units("\t\tNeuron {} of " + f"{N_ell_plus_1} quantized successfully.", N_ell_plus_1)
         self._update_weights(layer_idx, out["Q"])
         self._log(f"\tdone. {time()-tic:.2f} seconds.")
-        self.last_layer_stats[layer_idx] = _channel_stats(out, self.alphabet, self.alphabet_scalar)
+        self.last_layer_stats[layer_idx] = (_search_stats(out, self.alphabet) if search
+                                            else _channel_stats(out, self.alphabet, self.alphabet_scalar))
 
     # The reference logs one record per neuron / filter as its futures complete (:567, :716).  Here all of a layer's units complete
     # together; the records still go out ONE PER UNIT (handlers and formatters that count or prefix records see what they saw), unless
@@ -714,7 +743,7 @@ class QuantizedNeuralNetwork:
     def quantize_network(self):
         """Quantizes all Dense layers that are not in ``ignore_layers``, in order (:576-590)."""
         num_layers = len(self.trained_net.layers)
-        if self.radius == "layer":
+        if self.radius == "layer" and self.alphabet_scalars is None:
             self._prefetch_medians([k for k, layer in enumerate(self.trained_net.layers)
                                     if layer.__class__.__name__ == "Dense" and k not in self.ignore_layers])
         for layer_idx, layer in enumerate(self.trained_net.layers):
@@ -733,6 +762,7 @@ class QuantizedCNN(QuantizedNeuralNetwork):
                  alphabet_scalar=1, patch_mini_batch_size=5000, is_quantize_conv2d=True, *,
                  device=None, process_group=None, fix_partial_batch=False, radius="layer"):
         self.radius = _check_radius(radius)
+        self.alphabet_scalars = _scalar_candidates(alphabet_scalar)
         self.get_data = get_data
         self.trained_net = network
         self.quantized_net = clone_model(network)
@@ -756,6 +786,10 @@ class QuantizedCNN(QuantizedNeuralNetwork):
         """Every (input channel, filter) pair of the kernel is quantized as an independent neuron of
         kh*kw weights against that channel's patch matrix (:815-867, :652-727).  The reference's
         (1,1)-filter shortcut is dead code (:835-842), so 1x1 kernels take the general path too."""
+        search = self.alphabet_scalars is not None
+        if search and self.trained_net.layers[layer_idx].__class__.__name__ == "DepthwiseConv2D":
+            raise NotImplementedError(f"layer {layer_idx} ({getattr(self.trained_net.layers[layer_idx], 'name', 'DepthwiseConv2D')}): a "
+                                      f"sequence as alphabet_scalar (the search over the scalar) does not take DepthwiseConv2D layers")
         self._log("\tFeeding input data through hidden layers...")
         tic = time()
         wX, qX = self._get_layer_data_generator(layer_idx)
@@ -767,8 +801,8 @@ class QuantizedCNN(QuantizedNeuralNetwork):
         except Exception:
             rate = None
         Wd = self._kernel_on_device(layer)
-        channels = self.radius == "channel"
-        if not channels:
+        channels = self.radius == "channel" and not search
+        if not channels and not search:
             alphabet, rad = self._layer_alphabet(Wd, layer_idx)                    # (:831-832)
         num_channels = Wd.shape[-2]
         tic = time()
@@ -776,7 +810,10 @@ class QuantizedCNN(QuantizedNeuralNetwork):
         try:
             conv = dict(strides=tuple(layer.strides), padding=layer.padding.upper(), rate=tuple(rate) if rate else None,
                         group=self.process_group, want_resid=False)      # residual norms are diagnostics: skip their replay
-            if channels:
+            if search:
+                out = _layer.quantize_conv2d_search(Wd, wX, qX, self.alphabet, self.alphabet_scalars, conv["strides"], conv["padding"],
+                                                    conv["rate"], per=self.radius, group=self.process_group)
+            elif channels:
                 out = _layer.quantize_conv2d_channels(Wd, wX, qX, self.alphabet, self.alphabet_scalar,
                                                       depthwise=layer.__class__.__name__ == "DepthwiseConv2D", **conv)
             else:
@@ -787,6 +824,9 @@ class QuantizedCNN(QuantizedNeuralNetwork):
             raise Exception
         self._log(f"\t\tdone. {time()-tic:.2f} seconds.")
         self._update_weights(layer_idx, Q)
+        if search:
+            self.last_layer_stats[layer_idx] = _search_stats(out, self.alphabet, reruns=int(out.get("reruns", 0)))
+            return
         if channels:
             self.last_layer_stats[layer_idx] = _channel_stats(out, self.alphabet, self.alphabet_scalar, reruns=int(out.get("reruns", 0)))
             return
@@ -795,7 +835,7 @@ class QuantizedCNN(QuantizedNeuralNetwork):
 
     def quantize_network(self):
         num_layers = len(self.trained_net.layers)
-        if self.radius == "layer":
+        if self.radius == "layer" and self.alphabet_scalars is None:
             self._prefetch_medians([k for k, layer in enumerate(self.trained_net.layers)
                                     if layer.__class__.__name__ == "Dense"
                                     or (layer.__class__.__name__ in {"Conv2D", "DepthwiseConv2D"} and self.is_quantize_conv2d)])
