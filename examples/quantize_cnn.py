@@ -71,6 +71,9 @@ def main():
     ap.add_argument("--scalars", type=float, nargs="+", default=[2, 3, 4])
     ap.add_argument("--radius", choices=["layer", "channel"], default="layer",
                     help="one alphabet radius per layer (the reference's rule) or one per output channel, for GPFQ and MSQ alike")
+    ap.add_argument("--conv-walk", choices=["channel", "filter"], default="channel",
+                    help="Conv2D layers: one walk per (input channel, filter) pair (the reference's rule) or one per whole filter")
+    ap.add_argument("--conv-columns", type=int, default=8192, help="patch columns sampled per Conv2D layer with --conv-walk filter")
     ap.add_argument("--csv", default=None, help="append the metrics rows here (reference schema and append semantics)")
     ap.add_argument("--save-dir", default=None, help="save every quantized model there (quantize_pretrained_cnn.py:97-100)")
     ap.add_argument("--test-samples", type=int, default=2000)
@@ -89,7 +92,8 @@ def main():
     for idx, params in enumerate(ParamConfig(*c) for c in grid):
         get_data = CIFAR10Sequence(X_train[0:params.q_train_size], y_train[0:params.q_train_size], batch_size=16)
         my_quant_net = QuantizedCNN(network=model, batch_size=params.q_train_size, get_data=get_data, logger=quiet,
-                                    bits=params.bits, alphabet_scalar=params.alphabet_scalar, radius=args.radius)
+                                    bits=params.bits, alphabet_scalar=params.alphabet_scalar, radius=args.radius,
+                                    conv_walk=args.conv_walk, conv_columns=args.conv_columns)
         tic = time()
         my_quant_net.quantize_network()
         quantization_time = time() - tic

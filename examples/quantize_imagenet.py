@@ -100,7 +100,7 @@ def preprocess(x):
     return (np.asarray(x, dtype=np.float32) - np.array([103.939, 116.779, 123.68], dtype=np.float32)) / 64.0
 
 
-def quantize_network(parameters, dir_data, dir_processed_images, logger, save_dir, classes):
+def quantize_network(parameters, dir_data, dir_processed_images, logger, save_dir, classes, conv_walk="channel", conv_columns=8192):
     import pandas as pd
     model, model_name_analog = parameters.pretrained_model
     np.random.seed(np_seed)                                               # the seeds for splitting training and testing (:104-106)
@@ -122,7 +122,8 @@ def quantize_network(parameters, dir_data, dir_processed_images, logger, save_di
     quantization_train_generator = ImageNetSequence(train_paths, y_train, batch_size=16, preprocess_func=parameters.preprocess_func)
     my_quant_net = QuantizedCNN(network=model, batch_size=parameters.q_train_size, get_data=quantization_train_generator,
                                 logger=logger, bits=parameters.bits, alphabet_scalar=parameters.alphabet_scalar,
-                                patch_mini_batch_size=1000, is_quantize_conv2d=parameters.is_quantize_conv2d)
+                                patch_mini_batch_size=1000, is_quantize_conv2d=parameters.is_quantize_conv2d,
+                                conv_walk=conv_walk, conv_columns=conv_columns)
     tic = time()
     my_quant_net.quantize_network()
     quantization_time = time() - tic
@@ -169,6 +170,9 @@ def main():
     ap.add_argument("--q-train-size", type=int, default=64, help="reference: 1500")
     ap.add_argument("--valid-size", type=int, default=128, help="reference: 20000")
     ap.add_argument("--quantize-conv2d", action="store_true", help="is_quantize_conv2d (reference default: Dense layers only)")
+    ap.add_argument("--conv-walk", choices=["channel", "filter"], default="channel",
+                    help="Conv2D layers: one walk per (input channel, filter) pair (the reference's rule) or one per whole filter")
+    ap.add_argument("--conv-columns", type=int, default=8192, help="patch columns sampled per Conv2D layer with --conv-walk filter")
     ap.add_argument("--bits", type=float, nargs="+", default=[np.log2(3)])
     ap.add_argument("--scalars", type=float, nargs="+", default=[2.0])
     ap.add_argument("--csv", default=None, help="append the metrics rows here (reference schema and append semantics)")
@@ -191,7 +195,8 @@ def main():
                    [bool(args.quantize_conv2d)])
     n_rows = 0
     for idx, params in enumerate(ParamConfig(*c) for c in grid):
-        trial_metrics = quantize_network(params, dir_data, dir_processed, quiet, args.save_dir, args.classes)
+        trial_metrics = quantize_network(params, dir_data, dir_processed, quiet, args.save_dir, args.classes,
+                                         conv_walk=args.conv_walk, conv_columns=args.conv_columns)
         if args.csv:                                    # header with the first row only, rows appended (:283-291)
             trial_metrics.to_csv(args.csv, mode="a", header=(idx == 0))
         n_rows += 1

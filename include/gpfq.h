@@ -481,6 +481,24 @@ int gpfq_extract_patches(const float *act, int64_t n, int64_t H, int64_t W, int6
                          float *P, int64_t ldp, void *stream);
 
 /*
+ * Whole-filter im2col of a sample of the patch columns: the data of a Conv2D layer whose filters are walked as
+ * neurons of N = kh*kw*Cin weights -- the rows of the Keras kernel [kh][kw][Cin][F] viewed as [N][F].
+ *   X[t][j] = act[b][oy*sh + ky*rh - pad_top][ox*sw + kx*rw - pad_left][c], 0 outside the image, t = (ky*kw + kx)*Cin + c,
+ *   (b, oy, ox) = patch column gpfq_patch_column(total, S, seed, j) of the total = n*oh*ow columns of gpfq_extract_patches (same oh, ow,
+ *   padding rule and column order).
+ * The column rule: S <= 0 or S >= total takes every column in order (m = total).  Otherwise m = S and column i is
+ * lo_i + splitmix64(seed, i) mod (hi_i - lo_i) with the strata lo_i = floor(i*total/S), hi_i = floor((i+1)*total/S) (strictly
+ * ascending), splitmix64(seed, i): z = seed + (i+1)*0x9E3779B97F4A7C15; z = (z ^ z>>30)*0xBF58476D1CE4E5B9;
+ * z = (z ^ z>>27)*0x94D049BB133111EB; z ^ z>>31, all mod 2^64.  Sampling takes S < 2^31.
+ * One asynchronous launch for both matrices, no workspace: the device evaluates the rule itself.
+ */
+int64_t gpfq_patch_column(int64_t total, int64_t S, uint64_t seed, int64_t i);      /* host: the rule above; i for S <= 0 or S >= total */
+int gpfq_gather_patch_columns(const float *act_w, const float *act_q,               /* NHWC [n][H][W][Cin]; act_q NULL or == act_w: one matrix */
+                              int64_t n, int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw,
+                              int same_padding, int64_t S, uint64_t seed,
+                              float *Xw, float *Xq, int64_t ld, void *stream);      /* [kh*kw*Cin][ld], ld >= m; entries [m, ld) written as 0 */
+
+/*
  * Channel planes of NHWC activations: planes[c][p] = act[p][c_lo + c] for p < npos = n*H*W, c < nch -- the
  * `[..., channel_idx]` slices of scripts/quantized_network.py:769-770 for a shard of channels in one pass
  * (the input layout of gpfq_quantize_conv_channels).  act [device] f32 [npos][Cin]; planes [device] f32 [nch][npos].

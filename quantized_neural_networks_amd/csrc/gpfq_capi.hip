@@ -896,6 +896,41 @@ int gpfq_extract_patches(const float *act, int64_t n, int64_t H, int64_t W, int6
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_extract_patches");
 }
 
+int64_t gpfq_patch_column(int64_t total, int64_t S, uint64_t seed, int64_t i) { return gpfq::patch_column(total, S, seed, i); }
+
+int gpfq_gather_patch_columns(const float *act_w, const float *act_q, int64_t n, int64_t H, int64_t W, int64_t Cin, int kh, int kw,
+                              int sh, int sw, int rh, int rw, int same_padding, int64_t S, uint64_t seed,
+                              float *Xw, float *Xq, int64_t ld, void *stream)
+{
+    if (n < 0 || H <= 0 || W <= 0 || Cin <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad activation shape");
+    if (kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || rh <= 0 || rw <= 0)
+        return fail(GPFQ_ERR_INVALID_ARG, "bad kernel/stride/rate");
+    const int64_t oh = gpfq_patch_out_dim(H, kh, sh, rh, same_padding);
+    const int64_t ow = gpfq_patch_out_dim(W, kw, sw, rw, same_padding);
+    const int64_t total = n * oh * ow, N = (int64_t)kh * kw * Cin;
+    const bool sampled = S > 0 && S < total;
+    const int64_t m = sampled ? S : total;
+    if (ld < m) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ld=%lld < %lld columns", (long long)ld, (long long)m);
+    if (ld == 0) return GPFQ_OK;
+    if (sampled && S > 0x7fffffffll) return fail(GPFQ_ERR_UNSUPPORTED, "S=%lld sampled columns: the column rule takes S < 2^31", (long long)S);
+    const bool two = act_q != nullptr && act_q != act_w;
+    if (!act_w || !Xw || (two && !Xq)) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (((N + 63) / 64) * ((ld + 63) / 64) > 0x7fffffffll)
+        return fail(GPFQ_ERR_UNSUPPORTED, "%lld rows x %lld columns: more tiles than one launch takes", (long long)N, (long long)ld);
+    int pad_top = 0, pad_left = 0;
+    if (same_padding) {
+        // TF SAME, as gpfq_extract_patches
+        const int64_t keh = kh + (int64_t)(kh - 1) * (rh - 1), kew = kw + (int64_t)(kw - 1) * (rw - 1);
+        int64_t th = (oh - 1) * sh + keh - H; if (th < 0) th = 0;
+        int64_t tw = (ow - 1) * sw + kew - W; if (tw < 0) tw = 0;
+        pad_top = (int)(th / 2);
+        pad_left = (int)(tw / 2);
+    }
+    hipError_t e = gpfq::launch_gather_patch_columns(act_w, two ? act_q : nullptr, n, H, W, Cin, kh, kw, sh, sw, rh, rw, pad_top, pad_left,
+                                                     oh, ow, S, seed, Xw, two ? Xq : nullptr, ld, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_gather_patch_columns");
+}
+
 int gpfq_channel_planes(const float *act, int64_t npos, int64_t Cin, int64_t c_lo, int64_t nch, float *planes, void *stream)
 {
     if (npos < 0 || Cin <= 0 || c_lo < 0 || nch < 0 || c_lo + nch > Cin)

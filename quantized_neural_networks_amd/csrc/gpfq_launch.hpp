@@ -302,5 +302,10 @@ hipError_t launch_channel_planes(const float *act, int64_t npos, int64_t Cin, in
 hipError_t launch_extract_patches(const float *act, int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t c,
                                   int kh, int kw, int sh, int sw, int rh, int rw, int pad_top, int pad_left,
                                   int64_t oh, int64_t ow, float *P, int64_t ldp, hipStream_t stream);
+// gpfq_gather.hip: the column rule of gpfq_patch_column, and the whole-filter im2col of the sampled columns (act_q NULL: one matrix)
+int64_t patch_column(int64_t total, int64_t S, uint64_t seed, int64_t i);
+hipError_t launch_gather_patch_columns(const float *act_w, const float *act_q, int64_t n, int64_t H, int64_t W, int64_t Cin, int kh, int kw,
+                                       int sh, int sw, int rh, int rw, int pad_top, int pad_left, int64_t oh, int64_t ow, int64_t S,
+                                       uint64_t seed, float *Xw, float *Xq, int64_t ld, hipStream_t stream);
 
 }  // namespace gpfq

@@ -96,6 +96,9 @@ SYMBOLS = {
     "gpfq_patch_out_dim": (_i64, [_i64, _i64, _i64, _i64, _int]),
     "gpfq_extract_patches": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
                                     _vp, _i64, _vp]),
+    "gpfq_patch_column": (_i64, [_i64, _i64, ctypes.c_uint64, _i64]),
+    "gpfq_gather_patch_columns": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _i64, ctypes.c_uint64,
+                                         _vp, _vp, _i64, _vp]),
 }
 
 _lib = None
@@ -1125,3 +1128,51 @@ def extract_patches(act, channel, kernel_size, strides, rate, padding, out=None)
         _check(load().gpfq_extract_patches(act.data_ptr(), n, H, W, Cin, channel, kh, kw, sh, sw, rh, rw,
                                            1 if same else 0, out.data_ptr(), ldp, _stream()), "gpfq_extract_patches")
     return out
+
+
+def patch_column(total, S, seed, i):
+    """Patch column i of a sample of S out of `total` (gpfq_patch_column, the rule of include/gpfq.h): i itself for S <= 0 or
+    S >= total, else one column of the i-th stratum chosen by splitmix64(seed, i).  Host arithmetic only."""
+    return int(load().gpfq_patch_column(int(total), int(S), int(seed) & 0xFFFFFFFFFFFFFFFF, int(i)))
+
+
+def gather_patch_columns(act_w, act_q, ksize, strides, rate, padding, columns=None, seed=0):
+    """The whole-filter im2col rows of a sample of the patch columns (gpfq_gather_patch_columns): NHWC f32 [n][H][W][Cin] ->
+    X f32 [kh*kw*Cin][m], row (ky*kw + kx)*Cin + c, columns (image, oy, ox) as extract_patches orders them -- all of them
+    (columns=None or >= total = n*oh*ow) or the `columns` that patch_column(total, columns, seed, .) names.
+
+    Returns (X, Xq, m, total): views [:, :m] of [N][ld] buffers, ld = m rounded up to a multiple of 4, the pad columns zero;
+    Xq is X when act_q is act_w (one matrix is formed).  One asynchronous launch."""
+    _dev(act_w, torch.float32, "act_w")
+    same_t = act_q is None or act_q is act_w
+    if not same_t:
+        _dev(act_q, torch.float32, "act_q")
+        if act_q.shape != act_w.shape or act_q.device != act_w.device:
+            raise GpfqError(f"act_q {tuple(act_q.shape)} does not match act_w {tuple(act_w.shape)}")
+    if act_w.dim() != 4 or not act_w.is_contiguous() or not (same_t or act_q.is_contiguous()):
+        raise GpfqError("gather_patch_columns needs contiguous NHWC tensors")
+    n, H, W, Cin = act_w.shape
+    kh, kw = ksize
+    sh, sw = strides
+    rh, rw = rate if rate else (1, 1)
+    same = str(padding).upper() == "SAME"
+    if not same and str(padding).upper() != "VALID":
+        raise GpfqError(f"unknown padding {padding!r}")
+    total = n * patch_out_dim(H, kh, sh, rh, same) * patch_out_dim(W, kw, sw, rw, same)
+    S = 0 if columns is None else int(columns)
+    if columns is not None and S < 1:
+        raise ValueError(f"columns must be None or an int >= 1, got {columns!r}")
+    m = total if (S <= 0 or S >= total) else S
+    N, ld = kh * kw * Cin, -(-m // 4) * 4
+    if N * ld >= 1 << 31:
+        raise ValueError(f"the gathered matrix of {N} rows x {ld} columns has 2^31 elements or more: lower conv_columns "
+                         f"(the number of sampled patch columns)")
+    X = torch.empty((N, ld), dtype=torch.float32, device=act_w.device)
+    Xq = X if same_t else torch.empty((N, ld), dtype=torch.float32, device=act_w.device)
+    with torch.cuda.device(act_w.device):
+        rc = load().gpfq_gather_patch_columns(act_w.data_ptr(), None if same_t else act_q.data_ptr(), n, H, W, Cin, kh, kw, sh, sw, rh, rw,
+                                              1 if same else 0, S, int(seed) & 0xFFFFFFFFFFFFFFFF, X.data_ptr(),
+                                              None if same_t else Xq.data_ptr(), ld, _stream())
+    _check(rc, "gpfq_gather_patch_columns")
+    Xv = X[:, :m]
+    return Xv, (Xv if same_t else Xq[:, :m]), m, total

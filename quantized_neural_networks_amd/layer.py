@@ -764,3 +764,60 @@ def quantize_conv2d_search(W, act_w, act_q, unit_alphabet, alphabet_scalars, str
                                 unit, K, per_layer)
     return dict(Q=sel["Q"].reshape(kh, kw, Cin, F), idx=sel["idx"].reshape(kh, kw, Cin, F), resid=sel["resid"], radii=sel["radii"],
                 best=sel["best"], scores=sel["scores"], layer_median=med, reruns=reruns)
+
+
+# ------------------------------------------------------------------------------------------
+# conv_walk = "filter": a Conv2D filter walked as ONE neuron of kh*kw*Cin weights
+# ------------------------------------------------------------------------------------------
+def _filter_rows(W, act_w, act_q, strides, padding, rate, columns, seed):
+    """(W2 [N][F] -- the Keras kernel viewed with row (ky*kw + kx)*Cin + c --, X, Xq [N][m], m, total): the Dense problem whose neurons
+    are the layer's filters, on a sample of the patch columns (hip.gather_patch_columns: one launch; every rank of a group forms the
+    same rows itself, no collective)."""
+    kh, kw, Cin, F = W.shape
+    act_w = act_w.contiguous()
+    act_q = act_w if (act_q is None or act_q is act_w) else act_q.contiguous()
+    X, Xq, m, total = hip.gather_patch_columns(act_w, act_q, (kh, kw), tuple(strides), tuple(rate) if rate else None, padding,
+                                               columns=columns, seed=seed)
+    return W.detach().contiguous().reshape(kh * kw * Cin, F), X, Xq, m, total
+
+
+def _as_filters(out, W, m, total):
+    """A dense driver's [N][F] results in the Keras kernel's shape (views), + the sample's size."""
+    for key in ("Q", "idx"):
+        if out.get(key) is not None:
+            out[key] = out[key].reshape(W.shape)
+    out["columns"], out["total"] = m, total
+    return out
+
+
+def quantize_conv2d_filters(W, act_w, act_q, alphabet, strides, padding, rate, columns=8192, seed=0, group=None, want_resid=True, log=None):
+    """Quantize a Conv2D kernel filter by filter: filter f is neuron f of the Dense problem (W2, X, Xq) of _filter_rows -- a walk of
+    kh*kw*Cin steps over the im2col rows of ALL input channels, where quantize_conv2d walks every (channel, filter) pair on its own.
+
+    W          f32 [kh][kw][Cin][F]   Keras kernel layout
+    act_w/q    f32 NHWC [n][H][W][Cin] analog / quantized layer inputs (act_q is act_w: one matrix)
+    alphabet   f64 [M] or a hip.DeviceAlphabet, as quantize_dense takes
+    columns    the patch columns sampled out of total = n*oh*ow (hip.patch_column with `seed`); None or >= total: all of them
+
+    The walk is quantize_dense's: its kernels, repairs and fallbacks, its sharding (filters over the ranks, one all-gather of packed
+    indices).  Returns dict(Q f32 [kh][kw][Cin][F], idx same shape, resid f64 [F], columns=m, total=total) (+ quantize_dense's
+    "workspace" for a device alphabet)."""
+    W2, X, Xq, m, total = _filter_rows(W, act_w, act_q, strides, padding, rate, columns, seed)
+    return _as_filters(quantize_dense(W2, X, Xq, alphabet, group=group, want_resid=want_resid, log=log), W, m, total)
+
+
+def quantize_conv2d_filters_channels(W, act_w, act_q, unit_alphabet, alphabet_scalar, strides, padding, rate, columns=8192, seed=0,
+                                     group=None, want_resid=True, log=None):
+    """quantize_conv2d_filters with one radius per filter (radius="channel"): quantize_dense_channels on the rows of _filter_rows (the
+    columns of W2 are the filters).  Returns its dict with Q, idx in the kernel's shape + columns, total."""
+    W2, X, Xq, m, total = _filter_rows(W, act_w, act_q, strides, padding, rate, columns, seed)
+    return _as_filters(quantize_dense_channels(W2, X, Xq, unit_alphabet, alphabet_scalar, group=group, want_resid=want_resid, log=log),
+                       W, m, total)
+
+
+def quantize_conv2d_filters_search(W, act_w, act_q, unit_alphabet, alphabet_scalars, strides, padding, rate, per="channel", columns=8192,
+                                   seed=0, group=None, log=None):
+    """quantize_conv2d_filters with the alphabet scalar searched per filter (per="channel") or for the layer (per="layer"):
+    quantize_dense_search on the rows of _filter_rows.  Returns its dict with Q, idx in the kernel's shape + columns, total."""
+    W2, X, Xq, m, total = _filter_rows(W, act_w, act_q, strides, padding, rate, columns, seed)
+    return _as_filters(quantize_dense_search(W2, X, Xq, unit_alphabet, alphabet_scalars, per=per, group=group, log=log), W, m, total)

@@ -20,6 +20,9 @@ output channel) an alphabet radius of its own instead of the reference's one per
 ``radius="layer"`` is the reference's rule.  A sequence of 1..16 numbers as ``alphabet_scalar`` searches the scalar on the device:
 every candidate is walked in the same launch and each output channel (``radius="channel"``) or the layer (``radius="layer"``) keeps
 the candidate with the smallest output error on the calibration data; a plain number is today's behaviour.
+``QuantizedCNN(..., conv_walk="filter")`` walks every Conv2D filter as one neuron of kh*kw*Cin weights over a sample of
+``conv_columns`` patch columns; the default ``conv_walk="channel"`` is the reference's walk per (input channel,
+filter) pair.
 """
 import logging
 from collections import namedtuple
@@ -129,6 +132,21 @@ def _check_radius(radius):
         raise ValueError(f"radius must be 'layer' (one alphabet radius per layer, the reference's rule) or 'channel' (one per output "
                          f"channel), got {radius!r}")
     return radius
+
+
+def _check_conv_walk(conv_walk, conv_columns, conv_columns_seed):
+    """(conv_walk, conv_columns, conv_columns_seed) validated: "channel" / "filter"; None or an int >= 1; a uint64."""
+    if conv_walk not in ("channel", "filter"):
+        raise ValueError(f"conv_walk must be 'channel' (one walk per (input channel, filter) pair, the reference's rule) or 'filter' (one "
+                         f"walk per filter over all input channels), got {conv_walk!r}")
+    if conv_columns is not None:
+        if isinstance(conv_columns, bool) or not isinstance(conv_columns, (int, np.integer)) or conv_columns < 1:
+            raise ValueError(f"conv_columns must be None (all patch columns) or an int >= 1, got {conv_columns!r}")
+        conv_columns = int(conv_columns)
+    if (isinstance(conv_columns_seed, bool) or not isinstance(conv_columns_seed, (int, np.integer))
+            or not 0 <= int(conv_columns_seed) < 1 << 64):
+        raise ValueError(f"conv_columns_seed must be an int in [0, 2^64), got {conv_columns_seed!r}")
+    return conv_walk, conv_columns, int(conv_columns_seed)
 
 
 def _scalar_candidates(alphabet_scalar):
@@ -760,9 +778,11 @@ class QuantizedCNN(QuantizedNeuralNetwork):
 
     def __init__(self, network, batch_size, get_data, mini_batch_size=32, logger=None, bits=np.log2(3),
                  alphabet_scalar=1, patch_mini_batch_size=5000, is_quantize_conv2d=True, *,
-                 device=None, process_group=None, fix_partial_batch=False, radius="layer"):
+                 device=None, process_group=None, fix_partial_batch=False, radius="layer", conv_walk="channel", conv_columns=8192,
+                 conv_columns_seed=0):
         self.radius = _check_radius(radius)
         self.alphabet_scalars = _scalar_candidates(alphabet_scalar)
+        self.conv_walk, self.conv_columns, self.conv_columns_seed = _check_conv_walk(conv_walk, conv_columns, conv_columns_seed)
         self.get_data = get_data
         self.trained_net = network
         self.quantized_net = clone_model(network)
@@ -801,6 +821,10 @@ class QuantizedCNN(QuantizedNeuralNetwork):
         except Exception:
             rate = None
         Wd = self._kernel_on_device(layer)
+        if self.conv_walk == "filter" and layer.__class__.__name__ == "Conv2D":
+            # (a DepthwiseConv2D output channel depends on one input channel: its whole-filter walk IS the per-channel one below)
+            self._quantize_conv2D_layer_filters(layer_idx, layer, Wd, wX, qX, rate)
+            return
         channels = self.radius == "channel" and not search
         if not channels and not search:
             alphabet, rad = self._layer_alphabet(Wd, layer_idx)                    # (:831-832)
@@ -832,6 +856,42 @@ class QuantizedCNN(QuantizedNeuralNetwork):
             return
         self.last_layer_stats[layer_idx] = _LazyStats(rad=rad, alphabet=alphabet, resid=out["resid"], idx=out["idx"],
                                                       reruns=int(out.get("reruns", 0)))
+
+    def _quantize_conv2D_layer_filters(self, layer_idx, layer, Wd, wX, qX, rate):
+        """conv_walk="filter": every filter of the Conv2D kernel is ONE neuron of kh*kw*Cin weights, walked over the im2col rows of a
+        sample of conv_columns patch columns (layer.quantize_conv2d_filters and its radius="channel" / search forms): the layer runs
+        as a Dense layer [kh*kw*Cin][F] does, device alphabet included.  The alphabet is the one the layer has in channel mode."""
+        kh, kw, Cin, F = Wd.shape
+        search = self.alphabet_scalars is not None
+        channels = self.radius == "channel" and not search
+        conv = dict(strides=tuple(layer.strides), padding=layer.padding.upper(), rate=tuple(rate) if rate else None,
+                    columns=self.conv_columns, seed=self.conv_columns_seed, group=self.process_group,
+                    log=lambda msg: self._log(f"\t\tLayer {layer_idx}: {msg}"))
+        if not channels and not search:
+            alphabet, rad = self._layer_alphabet(Wd, layer_idx)                    # (:831-832)
+            dalpha = self._layer_alphabet_device(layer_idx, rad)
+        tic = time()
+        try:
+            # (residual norms are diagnostics: kept where the kernel holds the residual anyway, as for a Dense layer)
+            if search:
+                out = _layer.quantize_conv2d_filters_search(Wd, wX, qX, self.alphabet, self.alphabet_scalars, per=self.radius, **conv)
+            elif channels:
+                out = _layer.quantize_conv2d_filters_channels(Wd, wX, qX, self.alphabet, self.alphabet_scalar, want_resid=None, **conv)
+            else:
+                out = _layer.quantize_conv2d_filters(Wd, wX, qX, alphabet if dalpha is None else dalpha, want_resid=None, **conv)
+        except Exception as exc:
+            self._log(f"\t\t\tLayer {layer_idx} generated an exception: {exc}")
+            raise exc
+        self._log(f"\t\tGathered {out['columns']} of {out['total']} patch columns; quantized {F} filters of {kh * kw * Cin} weights each. "
+                  f"{time()-tic:.2f} seconds.")
+        self._update_weights(layer_idx, out["Q"])
+        extra = dict(conv_walk="filter", columns=out["columns"], total=out["total"])
+        if search:
+            self.last_layer_stats[layer_idx] = _search_stats(out, self.alphabet, **extra)
+        elif channels:
+            self.last_layer_stats[layer_idx] = _channel_stats(out, self.alphabet, self.alphabet_scalar, **extra)
+        else:
+            self.last_layer_stats[layer_idx] = _LazyStats(rad=rad, alphabet=alphabet, resid=out["resid"], idx=out["idx"], **extra)
 
     def quantize_network(self):
         num_layers = len(self.trained_net.layers)
