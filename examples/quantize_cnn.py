@@ -77,6 +77,9 @@ def main():
     ap.add_argument("--csv", default=None, help="append the metrics rows here (reference schema and append semantics)")
     ap.add_argument("--save-dir", default=None, help="save every quantized model there (quantize_pretrained_cnn.py:97-100)")
     ap.add_argument("--test-samples", type=int, default=2000)
+    ap.add_argument("--export-packed", default=None, metavar="PATH",
+                    help="also write the quantized network in the packed low-bit form (deploy.export_packed; with several settings the "
+                         "file holds the last one's)")
     args = ap.parse_args()
 
     rng = np.random.default_rng(0)
@@ -98,6 +101,10 @@ def main():
         my_quant_net.quantize_network()
         quantization_time = time() - tic
         q_accuracy = agreement(my_quant_net.quantized_net, y_test, X_test)
+
+        if args.export_packed:
+            from quantized_neural_networks_amd import deploy
+            print(f"packed network written to {deploy.export_packed(my_quant_net, args.export_packed)}")
 
         # MSQ net: same radius as the corresponding layer of the greedy network (quantize_pretrained_cnn.py:104-117)
         MSQ_model = keras.clone_model(model)

@@ -58,6 +58,9 @@ def main():
     ap.add_argument("--csv", default=None, help="append one metrics row per setting there, the reference's schema and "
                                                 "append semantics (quantize_pretrained_mlp.py:119-153)")
     ap.add_argument("--widths", type=int, nargs="+", default=[500, 300], help="hidden layer widths")
+    ap.add_argument("--export-packed", default=None, metavar="PATH",
+                    help="also write the quantized network in the packed low-bit form (deploy.export_packed; with several settings the "
+                         "file holds the last one's)")
     args = ap.parse_args()
 
     rng = np.random.default_rng(0)
@@ -81,6 +84,10 @@ def main():
             os.makedirs(args.save_dir, exist_ok=True)
             keras.save_model(my_quant_net.quantized_net,
                              os.path.join(args.save_dir, f"Quantized_MLP_scaler{params.alphabet_scalar}_bits{params.bits:.3f}"))
+
+        if args.export_packed:
+            from quantized_neural_networks_amd import deploy
+            print(f"packed network written to {deploy.export_packed(my_quant_net, args.export_packed)}")
 
         # MSQ baseline: same radius as the corresponding GPFQ layer (quantize_pretrained_mlp.py:97-112)
         MSQ_model = keras.clone_model(model)

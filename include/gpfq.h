@@ -397,6 +397,45 @@ int gpfq_assemble_kernel_colrad(const void *qidx, int bits, int layout, const do
                                 int64_t N, int64_t C, float *Q, void *qidx_t, void *stream);
 
 /*
+ * The packed low-bit form of a quantized kernel, and a Dense forward pass that runs from it.  The kernel is the
+ * row-major matrix [R][C] of the output channels above (Dense [N][C]; Conv2D [kh*kw*Cin][F]; DepthwiseConv2D [kh*kw][Cin*mult]) with
+ *   radii [device] f64 [C] (a layer radius: the same number C times), unit_alphabet [host] f64 [M], 1 <= M <= 64,
+ *   zero_code in {0, 1}: 1 when the kernel holds the literal zero (index -1: an even alphabet on a dead input),
+ *   bits = gpfq_packed_bits(M, zero_code): the smallest of 2 / 4 / 8 with 2^bits >= M + zero_code (0 for M < 1 or M > 64),
+ *   code = index + zero_code (code 0 = the literal zero when zero_code is 1),
+ *   packed [device] u8 [C][pitch], channel-major: code t of channel j at bit t * bits of row j, little-endian within a byte as
+ *   gpfq_pack_indices lays its codes; pitch = gpfq_packed_row_bytes(R, bits) = ceil(R * bits / 8) rounded up to 16 bytes (0 for R = 0);
+ *   pad bits are zero.
+ * The value of a code is (float)(radii[j] * unit_alphabet[index]), 0.0f for the literal zero: what gpfq_assemble_kernel and
+ * gpfq_assemble_kernel_colrad install.
+ *
+ * gpfq_encode_kernel: idx[t][j] = the first k with (float)(radii[j] * unit_alphabet[k]) == Q[t][j]; where there is none, -1 when
+ * Q[t][j] == 0 (a literal zero) and otherwise -2 (a miss: the element is not on its alphabet; a NaN always is one).  counters[0] / [1]
+ * count the literal zeros / the misses.  One kernel launch behind an asynchronous 16-byte clear of the counters, no host
+ * synchronisation, no workspace.
+ *   Q [device] f32 [R][ld], ld >= C; idx [device] i8 [R][C]; counters [device] u64 [2].
+ * gpfq_pack_codes: idx [device] i8 [R][C] (every index in [-zero_code, 2^bits - zero_code)) -> packed, pad bits included.
+ * gpfq_unpack_kernel: packed -> Q [device] f32 [R][ldq] (may be NULL) and idx [device] i8 [R][C] (may be NULL); a code no member
+ * has decodes to 0.0f / -1.
+ * gpfq_packed_dense_forward: y[b][j] = sum_t x[b][t] * q[t][j] (+ bias[j]) for the Dense layer q [N][C] held as packed rows, without
+ * the float kernel ever existing: float32 products and sums (fused multiply-adds) in an order the kernel chooses, the same for every
+ * call of one shape.  Any B >= 1, N >= 0, C; the kernel walks the batch in tiles itself.  Weights t >= N (the pad codes; code 0 is
+ * the first member when zero_code is 0) meet zeros, and x is not read beyond column N.
+ *   x [device] f32 [B][ldx], ldx >= N; packed 16-byte aligned; bias [device] f32 [C] or NULL; y [device] f32 [B][ldy], ldy >= C.
+ * All four are asynchronous on `stream` and take no workspace.
+ */
+int    gpfq_packed_bits(int M, int zero_code);
+size_t gpfq_packed_row_bytes(int64_t R, int bits);
+int gpfq_encode_kernel(const float *Q, int64_t R, int64_t C, int64_t ld, const double *radii, const double *unit_alphabet, int M,
+                       int8_t *idx, uint64_t *counters, void *stream);
+int gpfq_pack_codes(const int8_t *idx, int64_t R, int64_t C, int bits, int zero_code, uint8_t *packed, void *stream);
+int gpfq_unpack_kernel(const uint8_t *packed, int bits, int zero_code, const double *radii, const double *unit_alphabet, int M,
+                       int64_t R, int64_t C, float *Q, int64_t ldq, int8_t *idx, void *stream);
+int gpfq_packed_dense_forward(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int bits, int zero_code,
+                              const double *radii, const double *unit_alphabet, int M, const float *bias, int64_t N, int64_t C,
+                              float *y, int64_t ldy, void *stream);
+
+/*
  * Search over the alphabet scalar (a sequence as alphabet_scalar).  K candidate scalars s_0 .. s_{K-1}
  * (1 <= K <= GPFQ_SEARCH_MAX_CANDIDATES, each a finite positive number) are K * C independent columns of one walk with the unit
  * alphabet: candidate k of output channel j is column k * C + j (k-major: candidate k is a contiguous block of C columns).

@@ -742,6 +742,97 @@ int gpfq_assemble_kernel_colrad(const void *qidx, int bits, int layout, const do
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_assemble_kernel_colrad");
 }
 
+// ---- the packed low-bit form (gpfq_packed.hip) ----
+
+int gpfq_packed_bits(int M, int zero_code) { return gpfq::packed_bits(M, zero_code); }
+
+size_t gpfq_packed_row_bytes(int64_t R, int bits) { return gpfq::packed_row_bytes(R, bits); }
+
+// The unit alphabet of a packed layer (1..64 members) and its (bits, zero_code) pair.
+static int packed_alphabet(const double *unit_alphabet, int M, HostAlphabet *H)
+{
+    if (M > 64) return fail(GPFQ_ERR_UNSUPPORTED, "the packed form holds alphabets of at most 64 members, got M=%d", M);
+    return make_alphabet(unit_alphabet, M, -1, H);
+}
+
+static int packed_width_ok(int bits, int zero_code, int M)
+{
+    if (bits != 2 && bits != 4 && bits != 8) return fail(GPFQ_ERR_INVALID_ARG, "bits must be 2, 4 or 8");
+    if (zero_code != 0 && zero_code != 1) return fail(GPFQ_ERR_INVALID_ARG, "zero_code must be 0 or 1");
+    if (M + zero_code > (1 << bits)) return fail(GPFQ_ERR_INVALID_ARG, "%d-bit codes cannot hold %d members%s", bits, M, zero_code ? " and the literal zero" : "");
+    return GPFQ_OK;
+}
+
+int gpfq_encode_kernel(const float *Q, int64_t R, int64_t C, int64_t ld, const double *radii, const double *unit_alphabet, int M,
+                       int8_t *idx, uint64_t *counters, void *stream)
+{
+    if (R < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size R=%lld C=%lld", (long long)R, (long long)C);
+    HostAlphabet H;
+    int rc = packed_alphabet(unit_alphabet, M, &H);
+    if (rc != GPFQ_OK) return rc;
+    if (!counters) return fail(GPFQ_ERR_INVALID_ARG, "counters is NULL");
+    if (R > 0 && C > 0) {
+        if (!Q || !radii || !idx) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+        if (ld < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ld=%lld < C=%lld", (long long)ld, (long long)C);
+    }
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counter width");
+    hipError_t e = gpfq::launch_encode_kernel(Q, R, C, ld, radii, H.A, idx, reinterpret_cast<unsigned long long *>(counters),
+                                              static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_encode_kernel");
+}
+
+int gpfq_pack_codes(const int8_t *idx, int64_t R, int64_t C, int bits, int zero_code, uint8_t *packed, void *stream)
+{
+    if (R < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size R=%lld C=%lld", (long long)R, (long long)C);
+    int rc = packed_width_ok(bits, zero_code, 1);
+    if (rc != GPFQ_OK) return rc;
+    if (R == 0 || C == 0) return GPFQ_OK;
+    if (!idx || !packed) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (reinterpret_cast<uintptr_t>(packed) % 4 != 0) return fail(GPFQ_ERR_INVALID_ARG, "packed must be 4-byte aligned (16 for the forward pass)");
+    hipError_t e = gpfq::launch_pack_codes(idx, R, C, bits, zero_code, packed, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_pack_codes");
+}
+
+int gpfq_unpack_kernel(const uint8_t *packed, int bits, int zero_code, const double *radii, const double *unit_alphabet, int M,
+                       int64_t R, int64_t C, float *Q, int64_t ldq, int8_t *idx, void *stream)
+{
+    if (R < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size R=%lld C=%lld", (long long)R, (long long)C);
+    HostAlphabet H;
+    int rc = packed_alphabet(unit_alphabet, M, &H);
+    if (rc != GPFQ_OK) return rc;
+    rc = packed_width_ok(bits, zero_code, M);
+    if (rc != GPFQ_OK) return rc;
+    if (R == 0 || C == 0 || (!Q && !idx)) return GPFQ_OK;
+    if (!packed || !radii) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (Q && ldq < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldq=%lld < C=%lld", (long long)ldq, (long long)C);
+    hipError_t e = gpfq::launch_unpack_kernel(packed, bits, zero_code, radii, H.A, R, C, Q, ldq, idx, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_unpack_kernel");
+}
+
+int gpfq_packed_dense_forward(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int bits, int zero_code,
+                              const double *radii, const double *unit_alphabet, int M, const float *bias, int64_t N, int64_t C,
+                              float *y, int64_t ldy, void *stream)
+{
+    if (B < 0 || N < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size B=%lld N=%lld C=%lld", (long long)B, (long long)N, (long long)C);
+    HostAlphabet H;
+    int rc = packed_alphabet(unit_alphabet, M, &H);
+    if (rc != GPFQ_OK) return rc;
+    rc = packed_width_ok(bits, zero_code, M);
+    if (rc != GPFQ_OK) return rc;
+    if (B == 0 || C == 0) return GPFQ_OK;
+    if (!y || !radii) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (ldy < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldy=%lld < C=%lld", (long long)ldy, (long long)C);
+    if (N > 0) {
+        if (!x || !packed) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+        if (ldx < N) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldx=%lld < N=%lld", (long long)ldx, (long long)N);
+        if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "packed must be 16-byte aligned");
+    }
+    if (C > 2147483647LL * 8) return fail(GPFQ_ERR_UNSUPPORTED, "layer too wide for one launch");
+    hipError_t e = gpfq::launch_packed_dense_forward(x, B, ldx, packed, bits, zero_code, radii, H.A, bias, N, C, y, ldy,
+                                                     static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_packed_dense_forward");
+}
+
 int gpfq_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii, const float *layer_median,
                            const double *scalars, int K, double *radii, float *W_cand, int64_t ldo, int64_t c_lo, int64_t c_hi,
                            void *stream)

@@ -54,6 +54,12 @@ SYMBOLS = {
     "gpfq_column_radii_workspace_bytes": (_sz, [_i64, _i64]),
     "gpfq_column_radii": (_int, [_vp, _i64, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
     "gpfq_assemble_kernel_colrad": (_int, [_vp, _int, _int, _dp, _int, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "gpfq_packed_bits": (_int, [_int, _int]),
+    "gpfq_packed_row_bytes": (_sz, [_i64, _int]),
+    "gpfq_encode_kernel": (_int, [_vp, _i64, _i64, _i64, _vp, _dp, _int, _vp, _vp, _vp]),
+    "gpfq_pack_codes": (_int, [_vp, _i64, _i64, _int, _int, _vp, _vp]),
+    "gpfq_unpack_kernel": (_int, [_vp, _int, _int, _vp, _dp, _int, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "gpfq_packed_dense_forward": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _dp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
     "gpfq_candidate_kernels": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dp, _int, _vp, _vp, _i64, _i64, _i64, _vp]),
     "gpfq_select_candidates_workspace_bytes": (_sz, [_int, _i64]),
     "gpfq_select_candidates": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _dp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
@@ -1176,3 +1182,98 @@ def gather_patch_columns(act_w, act_q, ksize, strides, rate, padding, columns=No
     _check(rc, "gpfq_gather_patch_columns")
     Xv = X[:, :m]
     return Xv, (Xv if same_t else Xq[:, :m]), m, total
+
+
+# ---- the packed low-bit form of a quantized kernel (include/gpfq.h) ------------------------------------------
+
+def packed_bits(M, zero_code):
+    """Code width of a packed layer: the smallest of 2 / 4 / 8 with 2^bits >= M + zero_code; 0 for M < 1 or M > 64.  Host only."""
+    return int(load().gpfq_packed_bits(int(M), int(zero_code)))
+
+
+def packed_row_bytes(R, bits):
+    """Bytes of one output channel's packed row: ceil(R * bits / 8) rounded up to 16 (0 for R = 0).  Host only."""
+    return int(load().gpfq_packed_row_bytes(int(R), int(bits)))
+
+
+def _unit64(unit_alphabet):
+    arr, M, _ = _alphabet(unit_alphabet)
+    if M > 64:
+        raise GpfqError(f"the packed form holds alphabets of at most 64 members, got {M}")
+    return arr, M
+
+
+def encode_kernel(Q2d, radii, unit_alphabet):
+    """Indices of an on-alphabet kernel (gpfq_encode_kernel): Q2d f32 [R][C] (rows contiguous), radii f64 [C] ->
+    (idx i8 [R][C], counters i64 [2] = literal zeros, misses; both on the device).  One launch, no sync."""
+    _dev(Q2d, torch.float32, "Q2d"); _dev(radii, torch.float64, "radii")
+    qp, R, C, ld = _rows(Q2d, "Q2d")
+    if radii.numel() != C or not radii.is_contiguous():
+        raise GpfqError(f"radii must be a contiguous [{C}] tensor")
+    arr, M = _unit64(unit_alphabet)
+    idx = torch.empty((R, C), dtype=torch.int8, device=Q2d.device)
+    counters = torch.empty(2, dtype=torch.int64, device=Q2d.device)
+    with torch.cuda.device(Q2d.device):
+        _check(load().gpfq_encode_kernel(qp, R, C, ld, radii.data_ptr(), arr, M, idx.data_ptr(), counters.data_ptr(), _stream()),
+               "gpfq_encode_kernel")
+    return idx, counters
+
+
+def pack_codes(idx, bits, zero_code):
+    """idx i8 [R][C] -> packed u8 [C][packed_row_bytes(R, bits)] (gpfq_pack_codes), pad bits zero.  No sync."""
+    _dev(idx, torch.int8, "idx")
+    if idx.dim() != 2 or not idx.is_contiguous():
+        raise GpfqError("idx must be a contiguous [R][C] tensor")
+    R, C = idx.shape
+    packed = torch.empty((C, packed_row_bytes(R, bits)), dtype=torch.uint8, device=idx.device)
+    with torch.cuda.device(idx.device):
+        _check(load().gpfq_pack_codes(idx.data_ptr(), R, C, int(bits), int(zero_code), packed.data_ptr(), _stream()), "gpfq_pack_codes")
+    return packed
+
+
+def _packed_args(packed, bits, zero_code, radii, R):
+    _dev(packed, torch.uint8, "packed"); _dev(radii, torch.float64, "radii")
+    C = radii.numel()
+    if packed.dim() != 2 or not packed.is_contiguous() or tuple(packed.shape) != (C, packed_row_bytes(R, bits)) or not radii.is_contiguous():
+        raise GpfqError(f"packed must be a contiguous [{C}][{packed_row_bytes(R, bits)}] tensor for {R} rows of {bits}-bit codes, "
+                        f"got {tuple(packed.shape)}")
+    return C
+
+
+def unpack_kernel(packed, bits, zero_code, radii, unit_alphabet, R, want_values=True, want_idx=False):
+    """packed u8 [C][pitch] -> (Q f32 [R][C], idx i8 [R][C]) (gpfq_unpack_kernel); either may be None.  No sync."""
+    C = _packed_args(packed, bits, zero_code, radii, R)
+    arr, M = _unit64(unit_alphabet)
+    Q = torch.empty((R, C), dtype=torch.float32, device=packed.device) if want_values else None
+    idx = torch.empty((R, C), dtype=torch.int8, device=packed.device) if want_idx else None
+    with torch.cuda.device(packed.device):
+        _check(load().gpfq_unpack_kernel(packed.data_ptr(), int(bits), int(zero_code), radii.data_ptr(), arr, M, int(R), C,
+                                         Q.data_ptr() if Q is not None else None, max(C, 1), idx.data_ptr() if idx is not None else None,
+                                         _stream()), "gpfq_unpack_kernel")
+    return Q, idx
+
+
+def packed_dense_forward(x, packed, bits, zero_code, radii, unit_alphabet, N, bias=None, out=None):
+    """y f32 [B][C] = x [B][N] . q (+ bias) with the Dense kernel q [N][C] held as packed rows (gpfq_packed_dense_forward): the float
+    kernel is never formed.  x: rows contiguous (any row pitch); out: an optional [B][C] tensor with contiguous rows.  No sync."""
+    _dev(x, torch.float32, "x")
+    xp, B, Nx, ldx = _rows(x, "x")
+    if Nx != int(N):
+        raise GpfqError(f"x {tuple(x.shape)} does not have the layer's {N} input features")
+    C = _packed_args(packed, bits, zero_code, radii, N)
+    if bias is not None:
+        _dev(bias, torch.float32, "bias")
+        if bias.numel() != C or not bias.is_contiguous():
+            raise GpfqError(f"bias must be a contiguous [{C}] tensor")
+    arr, M = _unit64(unit_alphabet)
+    if out is None:
+        out = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    _dev(out, torch.float32, "out")
+    yp, By, Cy, ldy = _rows(out, "out")
+    if (By, Cy) != (B, C):
+        raise GpfqError(f"out {tuple(out.shape)} must be [{B}][{C}]")
+    with torch.cuda.device(x.device):
+        _check(load().gpfq_packed_dense_forward(xp, B, ldx, packed.data_ptr(), int(bits), int(zero_code), radii.data_ptr(), arr, M,
+                                                bias.data_ptr() if bias is not None else None, int(N), C, yp, ldy, _stream()),
+               "gpfq_packed_dense_forward")
+    return out

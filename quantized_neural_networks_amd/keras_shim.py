@@ -211,6 +211,69 @@ class Dense(Layer):
         return _activation(self.activation)(y)
 
 
+# Largest batch (rows of x) a PackedDense layer runs through gpfq_packed_dense_forward; beyond it the layer decodes its kernel and
+# multiplies (torch.matmul).  The rule: the largest measured batch at which the packed kernel beat both x @ Q on the float32 kernel and
+# decode + matmul on both 4096 x 4096 shapes (tools/packed_forward_probe.py -> profiles/packed_forward.txt).  Measured: it wins at 1, 2
+# and 4 rows (0.37, 0.50 and 0.81 of the float kernel's time, ternary) and loses at 8 (1.43).
+PACKED_FORWARD_MAX_BATCH = 4
+
+
+class PackedDense(Dense):
+    """A Dense layer that holds its quantized kernel as packed low-bit codes (deploy.load_packed): only the
+    codes, the radii and the bias live in device memory.  ``get_weights()`` decodes on demand; the weights cannot be set."""
+
+    def __init__(self, units, activation=None, use_bias=True, input_shape=None, name=None):
+        super().__init__(units, activation, use_bias, input_shape, name)
+        self.packed = None
+
+    def build(self, input_shape, device, rng):
+        Layer.build(self, input_shape, device, rng)
+        self.fan_in = int(input_shape[-1])
+        self._weights = [torch.zeros(self.units, device=device)] if self.use_bias else []      # (the bias alone)
+
+    def set_packed(self, packed, bias=None):
+        """packed: a deploy.pack_kernel result for a [fan_in][units] kernel, on this layer's device."""
+        if tuple(packed["shape"]) != (self.fan_in, self.units):
+            raise ValueError(f"packed kernel of shape {tuple(packed['shape'])}, layer {self.name} expects {(self.fan_in, self.units)}")
+        self.packed = packed
+        if self.use_bias and bias is not None:
+            Layer.set_weights(self, [bias])
+
+    def _kernel(self):
+        from . import deploy
+        if self.packed is None:
+            raise RuntimeError(f"PackedDense layer {self.name} holds no packed kernel (deploy.load_packed installs one)")
+        return deploy.unpack_kernel(self.packed)
+
+    def get_weights(self):
+        return [self._kernel().cpu().numpy()] + Layer.get_weights(self)
+
+    def set_weights(self, weights):
+        raise NotImplementedError("a PackedDense layer holds codes, not floats: its weights cannot be set")
+
+    def clone(self):
+        """A Dense layer of the same configuration (clone_model: fresh float weights, as for every other layer)."""
+        c = Dense(**self.config())
+        c.name = self.name
+        return c
+
+    def call(self, x):
+        from . import hip
+        if self.packed is None:
+            raise RuntimeError(f"PackedDense layer {self.name} holds no packed kernel (deploy.load_packed installs one)")
+        x2 = x.reshape(-1, self.fan_in)
+        bias = self._weights[0] if self.use_bias else None
+        if 0 < x2.shape[0] <= PACKED_FORWARD_MAX_BATCH:
+            p = self.packed
+            y = hip.packed_dense_forward(x2.contiguous(), p["codes"], p["bits"], p["zero_code"], p["radii"], p["alphabet"], self.fan_in,
+                                         bias=bias)
+        else:
+            y = x2 @ self._kernel()
+            if bias is not None:
+                y = y + bias
+        return _activation(self.activation)(y.reshape(tuple(x.shape[:-1]) + (self.units,)))
+
+
 class Conv2D(Layer):
     def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", dilation_rate=(1, 1),
                  activation=None, use_bias=True, input_shape=None, name=None):
@@ -733,16 +796,14 @@ def _layer_classes():
     return _LAYER_CLASSES
 
 
-def save_model(model, filepath):
-    """Stand-in for ``tf.keras.models.save_model`` as the reference's drivers call it on ``quantized_net``
-    (quantize_pretrained_mlp.py:87-95, _imagenet.py:180-191): architecture (layer classes + configs, and for graph
-    networks every layer's inbound layers) and weights in ONE ``.npz`` file (no pickling; ``load_model`` rebuilds the
-    network on the current device)."""
+def _arch_arrays(model):
+    """The architecture record of save_model / deploy.export_packed: {"__arch__": the JSON text as uint8}."""
     import json
     functional = isinstance(model, Model)
     specs = []
     for l in model.layers:
-        spec = dict(cls=l.__class__.__name__, name=l.name, config=l.config())
+        # (a PackedDense layer is recorded as the Dense layer it decodes to: save_model writes its float kernel, load_model reads it)
+        spec = dict(cls="Dense" if isinstance(l, PackedDense) else l.__class__.__name__, name=l.name, config=l.config())
         if functional:
             inbound = l.inbound_nodes[0].inbound_layers
             spec["inbound"] = [p.name for p in inbound] if isinstance(inbound, (list, tuple)) else [inbound.name]
@@ -752,57 +813,72 @@ def save_model(model, filepath):
     if functional:
         arch["outputs"] = [t.layer.name for t in model.outputs]
         arch["single"] = model._single
-    arrays = {"__arch__": np.frombuffer(json.dumps(arch).encode("utf-8"), dtype=np.uint8)}
-    for k, layer in enumerate(model.layers):
-        for j, w in enumerate(layer.get_weights()):
-            arrays[f"w{k}_{j}"] = w
+    return {"__arch__": np.frombuffer(json.dumps(arch).encode("utf-8"), dtype=np.uint8)}
+
+
+def _write_npz(arrays, filepath):
     path = str(filepath)
     with open(path if path.endswith(".npz") else path + ".npz", "wb") as f:
         np.savez(f, **arrays)
+
+
+def save_model(model, filepath):
+    """Stand-in for ``tf.keras.models.save_model`` as the reference's drivers call it on ``quantized_net``
+    (quantize_pretrained_mlp.py:87-95, _imagenet.py:180-191): architecture (layer classes + configs, and for graph
+    networks every layer's inbound layers) and weights in ONE ``.npz`` file (no pickling; ``load_model`` rebuilds the
+    network on the current device)."""
+    arrays = _arch_arrays(model)
+    for k, layer in enumerate(model.layers):
+        for j, w in enumerate(layer.get_weights()):
+            arrays[f"w{k}_{j}"] = w
+    _write_npz(arrays, filepath)
+
+
+def _network_from_arch(arch, device, classes=None):
+    """The network an architecture record describes, weights as built (random).  classes: {position in layers: layer class} to build
+    in place of the recorded class (deploy.load_packed: PackedDense for Dense)."""
+    classes = classes or {}
+
+    def tup(v):
+        return tuple(tup(e) for e in v) if isinstance(v, list) else v
+
+    known = _layer_classes()
+
+    def make(k, spec):
+        if spec["cls"] not in known:
+            raise ValueError(f"load_model: unknown layer class {spec['cls']!r}")
+        layer = classes.get(k, known[spec["cls"]])(**{key: tup(v) for key, v in spec["config"].items()})
+        layer.name = spec["name"]
+        return layer
+
+    if arch.get("functional"):
+        tensors, layers = {}, []
+        for k, spec in enumerate(arch["layers"]):
+            if spec["cls"] == "InputLayer":
+                tensors[spec["name"]] = Input(tup(spec["config"]["input_shape"]), name=spec["name"])
+                layers.append(tensors[spec["name"]].layer)
+                continue
+            layer = make(k, spec)
+            ins = [tensors[n] for n in spec["inbound"]]
+            tensors[spec["name"]] = layer(ins if spec["multi"] else ins[0])
+            layers.append(layer)
+        outs = [tensors[n] for n in arch["outputs"]]
+        net = Model(layers[0].output, outs[0] if arch["single"] else outs, device=device)
+        assert [l.name for l in net.layers] == [s["name"] for s in arch["layers"]]
+        return net
+    net = Sequential(input_shape=tuple(arch["input_shape"]), device=device)
+    for k, spec in enumerate(arch["layers"]):
+        net.add(make(k, spec))
+    return net
 
 
 def load_model(filepath, device=None):
     """Inverse of ``save_model``."""
     import json
     path = str(filepath)
-
-    def tup(v):
-        return tuple(tup(e) for e in v) if isinstance(v, list) else v
-
     with np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False) as z:
-        arch = json.loads(bytes(z["__arch__"]).decode("utf-8"))
-        known = _layer_classes()
-        if arch.get("functional"):
-            tensors, layers = {}, []
-            for spec in arch["layers"]:
-                cfg = {key: tup(v) for key, v in spec["config"].items()}
-                if spec["cls"] == "InputLayer":
-                    tensors[spec["name"]] = Input(cfg["input_shape"], name=spec["name"])
-                    layers.append(tensors[spec["name"]].layer)
-                    continue
-                if spec["cls"] not in known:
-                    raise ValueError(f"load_model: unknown layer class {spec['cls']!r}")
-                layer = known[spec["cls"]](**cfg)
-                layer.name = spec["name"]
-                ins = [tensors[n] for n in spec["inbound"]]
-                tensors[spec["name"]] = layer(ins if spec["multi"] else ins[0])
-                layers.append(layer)
-            outs = [tensors[n] for n in arch["outputs"]]
-            net = Model(layers[0].output, outs[0] if arch["single"] else outs, device=device)
-            assert [l.name for l in net.layers] == [s["name"] for s in arch["layers"]]
-            for k, layer in enumerate(net.layers):
-                n = len(layer._weights)
-                if n:
-                    layer.set_weights([z[f"w{k}_{j}"] for j in range(n)])
-            return net
-        net = Sequential(input_shape=tuple(arch["input_shape"]), device=device)
-        for k, spec in enumerate(arch["layers"]):
-            if spec["cls"] not in known:
-                raise ValueError(f"load_model: unknown layer class {spec['cls']!r}")
-            cfg = {key: tup(v) for key, v in spec["config"].items()}
-            layer = known[spec["cls"]](**cfg)
-            layer.name = spec["name"]
-            net.add(layer)
+        net = _network_from_arch(json.loads(bytes(z["__arch__"]).decode("utf-8")), device)
+        for k, layer in enumerate(net.layers):
             n = len(layer._weights)
             if n:
                 layer.set_weights([z[f"w{k}_{j}"] for j in range(n)])

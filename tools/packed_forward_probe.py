@@ -1,0 +1,166 @@
+"""Measures a Dense layer run three ways at small batches -> profiles/packed_forward.txt:
+
+    packed    gpfq_packed_dense_forward on the packed rows
+    float     x @ Q on the float32 kernel (torch.matmul)
+    decode    gpfq_unpack_kernel + torch.matmul
+
+Shapes 4096 x 4096 (ternary, 16 levels) and 25088 x 4096 (ternary), batches 1 .. 128.  Every figure is device time per call: the
+call is captured `--chain` times into a graph (a launch from Python costs more host time than these kernels run), the graph is
+replayed, the replays are timed with device events and the three ways alternate; median (min) over the replays.  Two cache states:
+"same" -- every call reads the same weights (what a repeated loop sees: a 64 MB float kernel stays in the 256 MiB last-level cache) --
+and "rotated" -- the calls of a chain walk over copies of the layer that together exceed that cache in float32 (what a network of
+many layers sees).  The switch-over constant keras_shim.PACKED_FORWARD_MAX_BATCH follows from the "same" table, the state that
+favours the float kernel: the largest measured batch at which the packed kernel beat both other ways on both 4096 x 4096 shapes
+(1 if there is none).  Also the file sizes of a VGG16-shaped Dense stack written by save_model and by export_packed.
+
+    python tools/packed_forward_probe.py [--out profiles/packed_forward.txt] [--quick]
+"""
+import argparse
+import os
+import sys
+import tempfile
+import types
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from quantized_neural_networks_amd import deploy, hip, keras_shim as ks  # noqa: E402
+
+BATCHES = (1, 2, 4, 8, 16, 32, 64, 128)
+
+
+def on_alphabet(rng, N, C, M, dev):
+    """A random kernel on the alphabet radius * linspace(-1, 1, M), one radius per channel, built on the device."""
+    unit = np.linspace(-1, 1, M)
+    radii = torch.from_numpy(rng.uniform(0.5, 1.5, C)).to(dev)
+    idx = torch.randint(0, M, (N, C), device=dev, dtype=torch.int8)
+    Q, _ = hip.assemble_kernel_colrad(idx, unit, radii, layout=hip.GPFQ_LAYOUT_KERAS)
+    return unit, radii, Q
+
+
+def timed(graphs, replays):
+    """Median and minimum device time (ms) of one replay of each graph, the graphs alternating."""
+    times = [[] for _ in graphs]
+    for _ in range(replays):
+        for i, g in enumerate(graphs):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            g.replay()
+            b.record()
+            b.synchronize()
+            times[i].append(a.elapsed_time(b))
+    return [(float(np.median(t)), float(np.min(t))) for t in times]
+
+
+def capture(fn, chain):
+    for i in range(3):
+        fn(i)                                           # warm up outside the capture (code objects, LDS limits, library heuristics)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for i in range(chain):
+            fn(i)
+    g.replay()
+    torch.cuda.synchronize()
+    return g
+
+
+def measure(label, N, C, M, args, dev, out):
+    rng = np.random.default_rng(N + M)
+    copies_rot = max(2, -(-(512 << 20) // (N * C * 4)))
+    layers = []
+    for _ in range(copies_rot):
+        unit, radii, Q = on_alphabet(rng, N, C, M, dev)
+        layers.append((deploy.pack_kernel(Q, radii, unit), Q))
+    p0 = layers[0][0]
+    out(f"{label}: N={N} C={C} M={M}: {p0['bits']}-bit codes, {p0['codes'].numel() / 1e6:.1f} MB packed against "
+        f"{N * C * 4 / 1e6:.1f} MB float32; rotated = {copies_rot} copies")
+    wins = {}
+    for state, ncopies in (("same", 1), ("rotated", copies_rot)):
+        out(f"  weights {state}; us per call, median (min):   B    packed          float           decode+matmul   packed/float  packed/decode")
+        for B in BATCHES:
+            x = torch.randn((B, N), device=dev)
+            y = [torch.empty((B, C), device=dev) for _ in range(3)]
+
+            def f_packed(i):
+                p = layers[i % ncopies][0]
+                hip.packed_dense_forward(x, p["codes"], p["bits"], p["zero_code"], p["radii"], p["alphabet"], N, out=y[0])
+
+            def f_float(i):
+                torch.matmul(x, layers[i % ncopies][1], out=y[1])
+
+            def f_decode(i):
+                p = layers[i % ncopies][0]
+                Qd, _ = hip.unpack_kernel(p["codes"], p["bits"], p["zero_code"], p["radii"], p["alphabet"], N)
+                torch.matmul(x, Qd, out=y[2])
+
+            graphs = [capture(f, args.chain) for f in (f_packed, f_float, f_decode)]
+            res = timed(graphs, args.replays)
+            us = [(1e3 * m / args.chain, 1e3 * lo / args.chain) for m, lo in res]
+            ref64 = x.double() @ layers[(args.chain - 1) % ncopies][1].double()
+            err = [float((t.double() - ref64).abs().max() / ref64.abs().max()) for t in y]
+            assert max(err) < 1e-4, err
+            out(f"                                              {B:4d}  {us[0][0]:7.2f} ({us[0][1]:6.2f})  {us[1][0]:7.2f} ({us[1][1]:6.2f})  "
+                f"{us[2][0]:7.2f} ({us[2][1]:6.2f})     {us[0][0] / us[1][0]:5.2f}        {us[0][0] / us[2][0]:5.2f}")
+            wins[(state, B)] = us[0][0] < us[1][0] and us[0][0] < us[2][0]
+            del graphs
+    return wins
+
+
+def file_sizes(dev, out):
+    """save_model against export_packed for the Dense stack of VGG16 (25088 -> 4096 -> 4096 -> 1000), ternary, put on the alphabet by hand."""
+    net = ks.Sequential([ks.Dense(4096, activation="relu", input_shape=(25088,)), ks.Dense(4096, activation="relu"),
+                         ks.Dense(1000, activation="softmax")], device=dev)
+    rng = np.random.default_rng(0)
+    stats = {}
+    for k, layer in enumerate(net.layers):
+        N, C = layer._weights[0].shape
+        unit, radii, Q = on_alphabet(rng, N, C, 3, dev)
+        layer.set_weights([Q, layer._weights[1]])
+        stats[k] = dict(rad=radii.cpu().numpy())
+    quantizer = types.SimpleNamespace(quantized_net=net, alphabet=np.linspace(-1, 1, 3), last_layer_stats=stats,
+                                      _will_quantize=lambda k: True)
+    with tempfile.TemporaryDirectory() as d:
+        ks.save_model(net, os.path.join(d, "float"))
+        path = deploy.export_packed(quantizer, os.path.join(d, "packed"))
+        a, b = os.path.getsize(os.path.join(d, "float.npz")), os.path.getsize(path)
+        back = deploy.load_packed(path, device=dev)
+        same = all(torch.equal(l._kernel(), m._weights[0]) for l, m in zip(back.layers, net.layers))
+    out(f"VGG16-shaped Dense stack 25088 -> 4096 -> 4096 -> 1000, ternary, one radius per output channel: save_model {a / 1e6:.1f} MB, "
+        f"export_packed {b / 1e6:.1f} MB ({a / b:.1f}x smaller); loaded kernels equal: {same}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--chain", type=int, default=32, help="calls captured into one graph")
+    ap.add_argument("--replays", type=int, default=15)
+    ap.add_argument("--quick", action="store_true", help="4096 x 4096 ternary only, no file sizes")
+    args = ap.parse_args()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    lines = []
+
+    def out(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    out(f"# {torch.cuda.get_device_name(dev)}; device time per call: {args.chain} calls captured into one graph, {args.replays} timed replays "
+        f"per form, the three forms alternating; median (min); us")
+    shapes = [("fc 4096 x 4096 ternary", 4096, 4096, 3)]
+    if not args.quick:
+        shapes += [("fc 4096 x 4096 16 levels", 4096, 4096, 16), ("VGG16 fc1 25088 x 4096 ternary", 25088, 4096, 3)]
+    wins = [measure(*s, args, dev, out) for s in shapes]
+    square = wins[:2]
+    both = [B for B in BATCHES if all(w[("same", B)] for w in square)]
+    out(f"# switch-over: batches at which the packed kernel beat both other ways on {'both' if len(square) == 2 else 'the'} 4096 x 4096 "
+        f"shape{'s' if len(square) == 2 else ''}, weights same: {both or 'none'} -> PACKED_FORWARD_MAX_BATCH = {max(both) if both else 1}")
+    if not args.quick:
+        file_sizes(dev, out)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
