@@ -84,6 +84,11 @@ int         gpfq_device_count(void);
  * Replaces the two scipy.linalg.norm(X_tilde, 2) calls made per weight at
  * scripts/quantized_network.py:83 and :89 (BLAS snrm2 -> float32-rounded norm); the value only
  * depends on t, so it is computed once per layer instead of 2*C times.
+ * This is the correctly rounded norm and depends on no BLAS.  The reference's value is its BLAS's: under the
+ * interpreter that wrote tests/golden (scipy 1.7 on MKL) it equals this one on every recorded row of up to
+ * 16000 samples and is 1 float32 ulp away on some longer rows (10 of 48 at 20000 samples; regimes.npz).  No
+ * recorded decision depends on the difference (numerics); a caller who has the reference's norms
+ * may pass them as nrm32 wherever one is taken.
  *   Xq [device] f32 [N][ld], nrm32 [device] f32 [N].
  */
 int gpfq_row_norms(const float *Xq, int64_t N, int64_t m, int64_t ld, float *nrm32, void *stream);

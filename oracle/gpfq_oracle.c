@@ -7,7 +7,8 @@
  *
  * Parity status: PINNED.  tests/test_oracle_golden.py checks every function below against
  * the .npz files under tests/golden, which tools/gen_golden.py produced by running the reference's own
- * functions (scripts/quantized_network.py) under its era interpreter (numpy 1.26 legacy casting).
+ * functions (scripts/quantized_network.py) under its era interpreter (numpy 1.26 legacy casting);
+ * tests/test_regime_golden.py does the same on long rows, alphabets of up to 256 members, signed and sparse data.
  *
  * The reference is Python; every mixed f32/f64 step of its NumPy expressions is spelled out
  * here as an explicit C cast so the result does not depend on any interpreter's promotion
@@ -55,7 +56,12 @@ static int zero_index(const double *alphabet, int M)
 }
 
 /* scipy.linalg.norm(x_f32, 2) (:83, :89): BLAS snrm2 -> f32-rounded Euclidean norm handed back
- * as a Python float.  Verified against the oracle interpreter: equals float32(sqrt(sum_f64 x^2)). */
+ * as a Python float.  RESTATED as float32(sqrt(sum_f64 x^2)), the correctly rounded norm.  Under the
+ * interpreter that wrote the golden files (scipy 1.7 on MKL) the reference's value equals this on every
+ * recorded row of up to 16000 samples; from 17000 samples on MKL's snrm2 is 1 float32 ulp away on some
+ * rows (tests/golden/regimes.npz: nrm_scan_*, nrm_diff_rows -- 10 of 48 rows at m = 20000).  The
+ * definition here does not depend on a BLAS and is the product's; callers that replay the reference on
+ * such rows pass its recorded norms in (nrm32 below). */
 float gpfq_oracle_norm32(const float *x, long m)
 {
     double s = 0.0;
@@ -70,12 +76,11 @@ void gpfq_oracle_row_norms(const float *Xq, long N, long m, long ld, float *nrm3
 
 /* One weight (:59-89) followed by the residual update (:119).  Returns the alphabet index
  * (or zero_idx for the literal 0) and stores the f64 value in *qval. */
-static int gpfq_oracle_step(float w, double *u, const float *X, const float *Xq, long m,
+static int gpfq_oracle_step(float w, double *u, const float *X, const float *Xq, long m, float nrm,
                             const double *alphabet, int M, int zero_idx, double *qval)
 {
     int k;
     double q;
-    float nrm = gpfq_oracle_norm32(Xq, m);
     if ((double)nrm < 1e-16) {                         /* :83-84 */
         k = zero_idx;
         q = 0.0;
@@ -111,16 +116,18 @@ static int gpfq_oracle_step(float w, double *u, const float *X, const float *Xq,
 
 /* One neuron / one (channel, filter) pair.  w has stride wstride (a column of the Keras
  * [N][C] kernel has stride C).  X, Xq: feature-major [N][ld] f32 rows of length m.
+ * nrm32: f32[N] norms of the rows of Xq to use at :83 and :89, or NULL for gpfq_oracle_norm32 of each row.
  * Outputs (any may be NULL): q f64[N], idx i16[N] (alphabets of up to 2^15 members), u f64[m] final residual. */
 void gpfq_oracle_neuron(const float *w, long wstride, const float *X, const float *Xq,
-                        long N, long m, long ld, const double *alphabet, int M,
+                        long N, long m, long ld, const float *nrm32, const double *alphabet, int M,
                         double *q, int16_t *idx, double *u_out)
 {
     int zi = zero_index(alphabet, M);
     double *u = (double *)calloc((size_t)(m > 0 ? m : 1), sizeof(double));   /* zeros(m) (:115) */
     for (long t = 0; t < N; ++t) {
         double qv;
-        int k = gpfq_oracle_step(w[t * wstride], u, X + t * ld, Xq + t * ld, m, alphabet, M, zi, &qv);
+        float nrm = nrm32 ? nrm32[t] : gpfq_oracle_norm32(Xq + t * ld, m);
+        int k = gpfq_oracle_step(w[t * wstride], u, X + t * ld, Xq + t * ld, m, nrm, alphabet, M, zi, &qv);
         if (q) q[t] = qv;
         if (idx) idx[t] = (int16_t)k;
     }
@@ -130,9 +137,9 @@ void gpfq_oracle_neuron(const float *w, long wstride, const float *X, const floa
 
 /* Neurons [j0, j1) of a Dense layer, W in Keras layout [N][C].  Outputs are neuron-major
  * ([j1-j0][N]) so each task writes one contiguous row; resid[j] = ||u_final||_2 (f64).
- * nthreads <= 0 -> all available cores.  Mirrors the process-pool fan-out (:549-567). */
+ * nrm32 as in gpfq_oracle_neuron (NULL: the restated norm).  nthreads <= 0 -> all available cores.  Mirrors the process-pool fan-out (:549-567). */
 void gpfq_oracle_layer(const float *W, long N, long C, long j0, long j1,
-                       const float *X, const float *Xq, long m, long ld,
+                       const float *X, const float *Xq, long m, long ld, const float *nrm32,
                        const double *alphabet, int M,
                        double *Q, int16_t *idx, double *resid, int nthreads)
 {
@@ -144,7 +151,7 @@ void gpfq_oracle_layer(const float *W, long N, long C, long j0, long j1,
 #pragma omp parallel for schedule(dynamic, 1)
     for (long j = j0; j < j1; ++j) {
         double *u = (double *)malloc((size_t)(m > 0 ? m : 1) * sizeof(double));
-        gpfq_oracle_neuron(W + j, C, X, Xq, N, m, ld, alphabet, M,
+        gpfq_oracle_neuron(W + j, C, X, Xq, N, m, ld, nrm32, alphabet, M,
                            Q ? Q + (j - j0) * N : NULL, idx ? idx + (j - j0) * N : NULL, u);
         if (resid) {
             double s = 0.0;
@@ -190,8 +197,8 @@ float gpfq_oracle_median_abs(const float *W, long n)
 
 /* Plain memoryless scalar quantization of a whole kernel (drivers' MSQ baseline,
  * quantize_pretrained_mlp.py:109): nearest(alphabet, (double)w) per weight. */
-/* Interface revision of this file (2: int16 index outputs); oracle/__init__.py rebuilds a library that reports another. */
-int gpfq_oracle_abi(void) { return 2; }
+/* Interface revision of this file (2: int16 index outputs; 3: nrm32 argument of neuron and layer); oracle/__init__.py rebuilds a library that reports another. */
+int gpfq_oracle_abi(void) { return 3; }
 
 void gpfq_oracle_msq(const float *W, long n, const double *alphabet, int M, double *Q, int16_t *idx)
 {

@@ -94,6 +94,37 @@ def test_gather_equals_restatement(hip, n, H, W, Cin, k, stride, rate, padding, 
         assert Xq2 is X2 and torch.equal(X2, X)
 
 
+GATHER_NON_SQUARE = [
+    # n, H, W, Cin, (kh, kw), (sh, sw), (rh, rw), padding: kh != kw and one of the stride / rate pairs unequal, so that a kernel which
+    # exchanged rh / rw, sh / sw or pad_top / pad_left would give other rows
+    (2, 10, 13, 4, (3, 5), (2, 1), (1, 1), "SAME"),
+    (2, 12, 9, 3, (2, 3), (1, 1), (2, 1), "VALID"),
+    (2, 9, 15, 8, (1, 7), (1, 2), (1, 1), "VALID"),
+    (3, 7, 6, 4, (2, 4), (1, 1), (1, 1), "SAME"),     # even kernels: TF's SAME pads one more at the bottom and right
+]
+
+
+@pytest.mark.parametrize("n,H,W,Cin,ksize,strides,rates,padding", GATHER_NON_SQUARE)
+def test_gather_non_square_geometry(hip, n, H, W, Cin, ksize, strides, rates, padding):
+    act_w, act_q = _acts(6, n, H, W, Cin)
+    geo = (*ksize, *strides, *rates, padding)
+    want_w, want_q = ref.rows(act_w, *geo), ref.rows(act_q, *geo)
+    total = ref.total_columns(act_w, *geo)
+    # (the restatement's own rows change when the two axes are exchanged: the case can tell them apart)
+    swapped = (ksize[1], ksize[0], strides[1], strides[0], rates[1], rates[0], padding)
+    other = ref.rows(act_w, *swapped)
+    assert other.shape != want_w.shape or not np.array_equal(other, want_w)
+    dw, dq = _cuda(act_w, act_q)
+    X, Xq, m, tot = hip.gather_patch_columns(dw, dq, ksize, strides, rates, padding)
+    assert tot == total == m and X.shape == Xq.shape == (ksize[0] * ksize[1] * Cin, m) == want_w.shape
+    ld = X.stride(0)
+    assert ld % 4 == 0 and m <= ld < m + 4 and Xq.stride(0) == ld
+    assert np.array_equal(X.cpu().numpy(), want_w)
+    assert np.array_equal(Xq.cpu().numpy(), want_q)
+    for buf in (_buffer(X, ld), _buffer(Xq, ld)):
+        assert (buf[:, m:] == 0).all()                                   # the pad columns
+
+
 @pytest.mark.parametrize("Cin,offset", [(3, 0), (4, 0), (8, 1)])
 def test_gather_raw_abi_odd_pitch_and_unaligned_tensor(hip, Cin, offset):
     """Through the C ABI with what the binding never passes: an odd row pitch (4-byte stores; Cin = 4: 16-byte loads beside them) and
@@ -149,13 +180,15 @@ WALKS = {
     "1x1": (6, 8, 8, 32, 16, 1, None, False),        # N = 32, m = 384
     "sampled": (8, 12, 12, 8, 8, 3, 300, False),     # 300 of 1152
     "classic": (2, 6, 6, 4, 8, 3, None, False),      # m = 72 < 257: the classic kernels
+    "cluster": (8, 12, 12, 8, 8, 3, None, False),    # N = 72, m = 1152: beyond 1024 columns, where the default conv_columns (8192) puts every walk
 }
 
 
 @pytest.mark.parametrize("case,levels,device_alphabet", [("block", 3, False), ("block", 3, True), ("block", 16, False), ("block", 16, True),
                                                          ("first", 3, False), ("first", 16, True), ("1x1", 3, False), ("1x1", 16, True),
                                                          ("sampled", 3, True), ("sampled", 16, False), ("classic", 3, False),
-                                                         ("classic", 16, True)])
+                                                         ("classic", 16, True),
+                                                         ("cluster", 3, False), ("cluster", 3, True), ("cluster", 16, False), ("cluster", 16, True)])
 def test_walk_equals_oracle(hip, layer, oracle_mod, case, levels, device_alphabet):
     n, H, Wd, Cin, F, k, S, first = WALKS[case]
     act_w, act_q = _acts(2, n, H, Wd, Cin, first)
@@ -164,7 +197,7 @@ def test_walk_equals_oracle(hip, layer, oracle_mod, case, levels, device_alphabe
     geo = (k, k, 1, 1, 1, 1, "SAME")
     X = ref.rows(act_w, *geo, S=S, seed=5)
     Xq = X if first else ref.rows(act_q, *geo, S=S, seed=5)
-    assert X.shape == (k * k * Cin, {"block": 384, "first": 320, "1x1": 384, "sampled": 300, "classic": 72}[case])
+    assert X.shape == (k * k * Cin, {"block": 384, "first": 320, "1x1": 384, "sampled": 300, "classic": 72, "cluster": 1152}[case])
     alphabet_o, rad_o = oracle_mod.layer_alphabet(W, unit, scalar)
     Wt, dw = _cuda(W, act_w)
     dq = dw if first else _cuda(act_q)[0]

@@ -161,6 +161,52 @@ def test_forward_against_float64(hip, deploy, M, zeros):
     print(f"M={M} zeros={zeros}: worst error / bound = {worst:.3g}")
 
 
+# The kernel walks a row in chunks of 64 sixteen-byte groups (4096 weights at 2 bits, 2048 at 4, 1024 at 8) and re-stages x in LDS between
+# two barriers per chunk: N on a chunk boundary and just past it, where the second chunk (the third at 8 bits) is a ragged tail of a few
+# weights behind the second pair of barriers.  (M, literal zeros, N)
+CHUNK_CASES = [(3, False, 4096), (3, False, 4100), (2, True, 4096), (2, True, 4100), (16, False, 2048), (16, False, 2050),
+               (4, True, 2048), (4, True, 2050), (64, False, 2050), (16, True, 2050)]
+
+
+@pytest.mark.parametrize("M,zeros,N", CHUNK_CASES)
+def test_forward_second_and_later_chunks(hip, deploy, M, zeros, N):
+    """test_forward_against_float64 at row lengths of more than one chunk at every width (2 bits is what VGG16's fc1, N = 25088, is
+    exported at).  C = 9: two workgroups, the second ragged; B = 5: two batch tiles of 4.  The same derived bound, NaN-padded ldx and
+    sentinel-padded ldy."""
+    rng = np.random.default_rng(1000 * M + 2 * N + zeros)
+    C = 9
+    unit, radii, Q = _layer(rng, N, C, M, zeros)
+    p = deploy.pack_kernel(Q, radii, unit)
+    bits = p["bits"]
+    assert (bits, p["zero_code"]) == (ref.packed_bits(M, int(zeros)), int(zeros))
+    per_chunk = 64 * (128 // bits)
+    assert N >= per_chunk * (2 if bits == 8 else 1)                     # a whole chunk, or the chunk loop turns again
+    bias = rng.standard_normal(C).astype(np.float32)
+    bias_d = torch.from_numpy(bias).cuda()
+    W = 128 // bits
+    tail = ((N - 1) // W) * W
+    worst = 0.0
+    for B in (1, 2, 5):
+        x = rng.standard_normal((B, N)).astype(np.float32)
+        x[:, tail:] *= 64.0                                             # the largest entries sit where an unmasked tail would show
+        xbuf = torch.full((B, N + 5), float("nan"), dtype=torch.float32, device="cuda")
+        xbuf[:, :N] = torch.from_numpy(x).cuda()
+        exact = x.astype(np.float64) @ Q.astype(np.float64)
+        S = np.abs(x).astype(np.float64) @ np.abs(Q).astype(np.float64)
+        for b_d, b_h in ((None, np.zeros(C)), (bias_d, bias.astype(np.float64))):
+            ybuf = torch.full((B, C + 2), -7.0, dtype=torch.float32, device="cuda")
+            out = hip.packed_dense_forward(xbuf[:, :N], p["codes"], bits, p["zero_code"], p["radii"], unit, N, bias=b_d, out=ybuf[:, :C])
+            assert out.data_ptr() == ybuf.data_ptr()
+            y = ybuf.cpu().numpy()
+            assert np.all(y[:, C:] == -7.0)
+            err = np.abs(y[:, :C].astype(np.float64) - (exact + b_h))
+            bound = (N + 8) * U24 * (S + np.abs(b_h))
+            ratio = float(np.max(err / np.maximum(bound, 1e-300)))
+            worst = max(worst, ratio)
+            assert np.all(err <= bound), (N, C, B, b_d is not None, ratio)
+    print(f"M={M} zeros={zeros} N={N}: worst error / bound = {worst:.3g}")
+
+
 class _Quiet:
     def info(self, msg):
         pass

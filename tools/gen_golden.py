@@ -19,8 +19,15 @@ own functions are executed on seeded inputs:
     activation layout, the partial-last-batch quirk and bias carry-over.
 
 Only data (inputs + expected outputs) is written, to tests/golden/*.npz.
+
+``--only regimes`` writes tests/golden/regimes.npz alone (long rows, alphabets of up to 256 members, signed
+and sparse activations; the inputs come from tests/_regime_inputs.py and only their sha256 is stored) and
+leaves every other golden file untouched.
 """
+import argparse
+import contextlib
 import importlib.util
+import io
 import os
 import sys
 import tempfile
@@ -193,8 +200,8 @@ def replay_residual(w, X, Xq, q):
 
 def to_index(q, alphabet):
     """Alphabet index of each reference output value; -1 = the literal 0 of rule (i) when 0 is
-    not an alphabet member."""
-    idx = np.full(q.shape, -1, dtype=np.int8)
+    not an alphabet member.  int16 for alphabets whose indices do not fit int8."""
+    idx = np.full(q.shape, -1, dtype=np.int16 if len(alphabet) > 127 else np.int8)
     for k, a in enumerate(alphabet):
         idx[q == a] = k
     bad = (idx < 0) & (q != 0.0)
@@ -473,22 +480,120 @@ def known_answer_settings():
                 out=net.forward_upto(data, 1))
 
 
+# --------------------------------------------------------------------------------------
+# regimes: what the product runs beyond the corner the groups above cover
+# --------------------------------------------------------------------------------------
+def _blas_name():
+    import scipy
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        scipy.show_config()
+    text = buf.getvalue()
+    libs = []
+    for line in text.splitlines():
+        if "libraries" in line and "=" in line:
+            libs.append(line.split("=", 1)[1].strip())
+    low = text.lower()
+    kind = "mkl" if "mkl" in low else "openblas" if "openblas" in low else "unknown"
+    return kind + ": " + (libs[0] if libs else "?")
+
+
+def _walk(name, d, alphabet, workdir):
+    """Q [N][C] from the reference's own function for the case's kind."""
+    import _regime_inputs as ri
+    N, C = d["W"].shape
+    Q = np.zeros((N, C))
+    for j in range(C):
+        if name in ri.CONV:
+            Q[:, j] = run_filter(d["Wc"][:, :, j], d["X"], d["Xq"], alphabet, workdir).reshape(-1)
+        else:
+            Q[:, j] = run_neuron(d["W"][:, j], d["X"], d["Xq"], alphabet, workdir)
+    return Q
+
+
+def regime_cases(workdir):
+    import scipy
+    import scipy.linalg
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import _regime_inputs as ri
+    out = {}
+    for name in ri.CASES:
+        d = ri.inputs(name)
+        W, X, Xq = d["W"], d["X"], d["Xq"]
+        N, C = W.shape
+        m = X.shape[1]
+        # the alphabet from the tensor the reference hands to np.median: the [N][C] kernel, or the conv layer's [kh][kw][F] block
+        alphabet, rad = layer_alphabet(d.get("Wc", W), d["bits"], d["scalar"])
+        assert len(alphabet) == d["M"]
+        Q = _walk(name, d, alphabet, workdir)
+        U = np.stack([replay_residual(W[:, j], X, Xq, Q[:, j]) for j in range(C)])
+        nrm_ref = np.array([np.float32(scipy.linalg.norm(Xq[t], 2)) for t in range(N)], dtype=np.float32)
+        own = ri.restated_norms(Xq)
+        diff_rows = np.flatnonzero(nrm_ref != own).astype(np.int64)
+        max_ulps = np.int64(ri.ulps(nrm_ref, own).max())
+        # the same walk with float32(sqrt(sum_f64 x^2)) in place of the reference's norm: the decisions that the restated
+        # definition changes, as (t, j) pairs
+        saved = ref.norm
+        ref.norm = lambda x, ord=None: np.float32(np.sqrt(np.cumsum(np.asarray(x, np.float64) ** 2)[-1])) if len(x) else np.float32(0)
+        try:
+            Q_own = _walk(name, d, alphabet, workdir)
+        finally:
+            ref.norm = saved
+        flips = np.argwhere(Q_own != Q).astype(np.int64).reshape(-1, 2)
+        case = dict(sha256=ri.digest(d), alphabet=alphabet, rad=np.float64(rad), bits=np.float64(d["bits"]),
+                    scalar=np.float64(d["scalar"]), Q=Q, idx=to_index(Q, alphabet), resid=np.linalg.norm(U, axis=1),
+                    nrm_ref=nrm_ref, nrm_diff_rows=diff_rows, nrm_max_ulps=max_ulps, own_norm_flips=flips)
+        if flips.size:
+            case["Q_own"] = Q_own
+        if m <= 1024:
+            case["U"] = U
+        if m <= 8192:
+            assert diff_rows.size == 0, (name, diff_rows)
+        print(f"  {name}: N={N} m={m} M={d['M']} norm rows differing {diff_rows.size}/{N} (max {int(max_ulps)} ulp), "
+              f"own-norm flips {len(flips)}")
+        out[name] = case
+    assert any(out[c]["nrm_diff_rows"].size for c in ri.LONG), "no long case shows the reference's norm leaving the restatement"
+    scan = []
+    for m in ri.SCAN_M:
+        rows = ri.scan_rows(m)
+        refn = np.array([np.float32(scipy.linalg.norm(r, 2)) for r in rows], dtype=np.float32)
+        scan.append(int((refn != ri.restated_norms(rows)).sum()))
+    print("  norm scan:", dict(zip(ri.SCAN_M, scan)))
+    out["meta"] = dict(nrm_scan_m=np.array(ri.SCAN_M, dtype=np.int64), nrm_scan_diff=np.array(scan, dtype=np.int64),
+                       nrm_scan_rows=np.int64(ri.SCAN_ROWS), numpy_version=np.array(np.__version__),
+                       scipy_version=np.array(scipy.__version__), blas=np.array(_blas_name()))
+    return out
+
+
+def _write_group(gname, cases):
+    flat = {}
+    for cname, arrays in cases.items():
+        for k, v in arrays.items():
+            flat[f"{cname}__{k}"] = v
+    np.savez_compressed(os.path.join(OUT, f"{gname}.npz"), **flat)
+    print(gname, sorted(cases))
+
+
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--only", choices=["regimes"], help="write this group alone and leave the other golden files as they are")
+    args = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
+    if args.only == "regimes":
+        with tempfile.TemporaryDirectory() as workdir:
+            _write_group("regimes", regime_cases(workdir))
+        print("numpy", np.__version__, "-> wrote", os.path.join(OUT, "regimes.npz"))
+        return
     with tempfile.TemporaryDirectory() as workdir:
         groups = {
             "dense": dense_cases(workdir),
             "edge": edge_cases(workdir),
             "conv": conv_cases(workdir),
             "network": network_cases(workdir),
+            "regimes": regime_cases(workdir),
         }
     for gname, cases in groups.items():
-        flat = {}
-        for cname, arrays in cases.items():
-            for k, v in arrays.items():
-                flat[f"{cname}__{k}"] = v
-        np.savez_compressed(os.path.join(OUT, f"{gname}.npz"), **flat)
-        print(gname, sorted(cases))
+        _write_group(gname, cases)
     np.savez_compressed(os.path.join(OUT, "bit_round.npz"), **bit_round_cases())
     np.savez_compressed(os.path.join(OUT, "settings_known_answer.npz"), **known_answer_settings())
     print("numpy", np.__version__, "-> wrote", OUT)
