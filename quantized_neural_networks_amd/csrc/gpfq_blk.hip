@@ -717,6 +717,11 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
     //  the form measured slower than the one- / two-group shapes: DESIGN_HISTORY.md, "gpfq_blk.hip notes" 4)
     constexpr bool kMfmaD = G == 4 && B == 4 && blk_row64(G, B) && !kNoMfmaD;
     constexpr bool kFused = kMfmaD && !kNoFused;
+    // The 16-neuron shapes with eleven sweep wavefronts (the headline layer, the cluster form's slices): the first operands of a slot
+    // in one round trip -- see the slot loop.  Not the eight-wavefront 16-neuron shapes (four and five pairs per lane: no register to
+    // spare, hipcc spills more of the sweep's loop with it) and not the narrow shapes (their slot is the decision wavefront's chain,
+    // whose first reads of a slot queue behind the sweeps' burst: 4-5 % slower with it, profiles/slot_top/README.md).
+    constexpr bool kBatchTop = kFused && NL == 4 && NSW == 11;
     constexpr bool kPreloadAll = PW * B <= 8 && PW <= 5 && !kFused;
     // ... where the registers allow it (u and the operands of a slot together): otherwise they are requested at the top of
     // phase U as in round 2
@@ -803,9 +808,15 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
             if (writer) lds_st<double2>(lds, o_x2, make_double2(vu, vw));
             slot_barrier();                                       // partials published
             slot_barrier();                                       // chains resumed, control word rewritten
-            ctl = lds_ld<int>(lds, L.off_ctl + 4 * (b & 1));
+            if constexpr (kBatchTop) ctl = lds_read_now(lds + L.off_ctl + 4 * (b & 1));
+            else ctl = lds_ld<int>(lds, L.off_ctl + 4 * (b & 1));
         }
     };
+    // (kBatchTop) Nothing is outstanding where the slot loop is entered -- and hipcc has to KNOW it (the builtin: its waitcnt pass reads
+    // that and not an asm statement).  A kernel argument's scalar load and the prologue's alphabet load, still "pending" at the loop
+    // header on paper, made the slot's first wait for an LDS read a full lgkmcnt(0) where a count would do (scalar loads answer out of
+    // order) and put a vmcnt(0) between the slot's first requests that waits for the LDS-DMA pieces issued just before them.
+    if constexpr (kBatchTop) __builtin_amdgcn_s_waitcnt(0);
     for (int b = 0; b < nslots; ++b) {
         STAMP(st0);
         STAMP_DO(if (b) acc_t += st0 - st5;)   // from the barrier to the top of the next slot: control word, next operands
@@ -888,7 +899,28 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                     if (i < NPS) { xbuf[i] = lds_ld<float2>(lds, row_off(i, false)); qbuf[i] = lds_ld<float2>(lds, row_off(i, true)); }
                 dcur = lds_ld<double2>(lds, rbm);
             };
-            first_requests();
+            if constexpr (kBatchTop) {
+                // What pair-step 0 consumes -- its rows and the (w, q) of steps 0 and 1 -- as ONE asm region with its wait inside: one
+                // round trip of six requests.  The rest (steps 2 and 3, the first row of the dot products) is requested behind it with
+                // plain reads and lands under pair-step 0's arithmetic.  Left to hipcc the slot's top was two round trips in sequence
+                // behind the control word's: all sixteen (w, q) drained with lgkmcnt(0) before the rows were requested, a second
+                // lgkmcnt(0) before the first product -- its waitcnt pass kept the control word's register pending at the loop header
+                // (the slow path's re-read on the back edge) and drained the queue in front of every instruction that reuses it.
+                static_assert(!kBatchTop || (B == 4 && NL == 4), "lds_read_slot_top reads four neurons' steps 0 and 1: 16 bytes at a stride of 4 steps x 8 bytes");
+                nf2 x0, q0;
+                nf4 w01[4];
+                lds_read_slot_top(x0, q0, w01, lds + row_off(0, false), lds + row_off(0, true), lds + o_wq + pbq);
+                xbuf[0] = make_float2(x0.x, x0.y); qbuf[0] = make_float2(q0.x, q0.y);
+#pragma unroll
+                for (int n = 0; n < NL; ++n) { fwq[0][n] = make_float2(w01[n].x, w01[n].y); fwq[1][n] = make_float2(w01[n].z, w01[n].w); }
+#pragma unroll
+                for (int s = 2; s < B; ++s)
+#pragma unroll
+                    for (int n = 0; n < NL; ++n) fwq[s][n] = lds_ld<float2>(lds, o_wq + pbq + (n * B + s) * 8);
+                dcur = lds_ld<double2>(lds, rbm);
+            } else {
+                first_requests();
+            }
             double2 dprev = make_double2(0.0, 0.0);
             double acc[NL];
 #pragma unroll
@@ -1141,7 +1173,9 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
 
         // ---- slow path: neurons of block b stopped at an uncertifiable step (rare) ----
         {
-        int ctl = lds_ld<int>(lds, L.off_ctl + 4 * (b & 1));      // (requested first: it is waited for alone)
+        int ctl;                                                  // (requested first: it is waited for alone)
+        if constexpr (kBatchTop) ctl = lds_read_now(lds + L.off_ctl + 4 * (b & 1));     // (a read hipcc does not track: see the slot's first requests)
+        else ctl = lds_ld<int>(lds, L.off_ctl + 4 * (b & 1));
         if constexpr (kHoist) {
             if (b + 1 < nslots) { preload_wq(b + 1); preload_rows(b + 1); }
         }

@@ -223,5 +223,24 @@ template <typename T> __device__ __forceinline__ void lds_st(lchar *base, int of
     *reinterpret_cast<__attribute__((address_space(3))) NT *>(base + off) = nv;
 }
 
+// LDS reads as ONE asm region: requests and the wait for them in a single statement, so every output is a landed value where hipcc
+// first sees it (it can spill or copy them as it likes) and its waitcnt pass never holds one of their registers "pending".  The
+// outputs are early-clobber: an answer may arrive while the statement's later requests still read their address registers.
+// lds_read_slot_top: the first operands of a fused slot of the 16-neuron block kernel (gpfq_blk.hip) -- the rows x, xq of pair-step 0
+// and, per neuron of the lane, the (w, q) of steps 0 and 1 (16 bytes at wq + 32 n: four steps of eight bytes per neuron).
+__device__ __forceinline__ void lds_read_slot_top(nf2 &x, nf2 &q, nf4 (&w)[4], lchar *px, lchar *pq, lchar *pwq)
+{
+    asm volatile("ds_read_b64 %0, %6\n\tds_read_b64 %1, %7\n\tds_read_b128 %2, %8\n\tds_read_b128 %3, %8 offset:32\n\t"
+                 "ds_read_b128 %4, %8 offset:64\n\tds_read_b128 %5, %8 offset:96\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(x), "=&v"(q), "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]), "=&v"(w[3])
+                 : "v"((unsigned)(uintptr_t)px), "v"((unsigned)(uintptr_t)pq), "v"((unsigned)(uintptr_t)pwq) : "memory");
+}
+__device__ __forceinline__ int lds_read_now(lchar *p)
+{
+    int v;
+    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"((unsigned)(uintptr_t)p) : "memory");
+    return v;
+}
+
 }  // namespace
 }  // namespace gpfq
