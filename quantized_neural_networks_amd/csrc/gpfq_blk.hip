@@ -722,6 +722,8 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
     // spare, hipcc spills more of the sweep's loop with it) and not the narrow shapes (their slot is the decision wavefront's chain,
     // whose first reads of a slot queue behind the sweeps' burst: 4-5 % slower with it, profiles/slot_top/README.md).
     constexpr bool kBatchTop = kFused && NL == 4 && NSW == 11;
+    // ... and with a symmetric alphabet the first two pair-steps of a slot inside the same asm region (slot_top_sym)
+    constexpr bool kTopSym = kBatchTop && SYM;
     constexpr bool kPreloadAll = PW * B <= 8 && PW <= 5 && !kFused;
     // ... where the registers allow it (u and the operands of a slot together): otherwise they are requested at the top of
     // phase U as in round 2
@@ -899,7 +901,31 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                     if (i < NPS) { xbuf[i] = lds_ld<float2>(lds, row_off(i, false)); qbuf[i] = lds_ld<float2>(lds, row_off(i, true)); }
                 dcur = lds_ld<double2>(lds, rbm);
             };
-            if constexpr (kBatchTop) {
+            if constexpr (kTopSym) {
+                // Symmetric alphabets: the slot's fifteen first requests AND the arithmetic of pair-steps 0 and 1 as one asm region
+                // (slot_top_sym) -- pair-step 0 starts when its own six answers are in, pair-step 1 when its rows are, while the later
+                // requests are still out; the region ends with a full wait, so every register the compiler sees has landed.  With the
+                // pair-steps left to hipcc (the general form below) pair-step 0 sits behind a drain of the region's six requests and
+                // pair-step 1 behind a second lgkmcnt(0) -- once per slot, just when the three wavefronts of a SIMD leave the barrier.
+                static_assert(!kTopSym || (B == 4 && NL == 4 && PF == 1), "slot_top_sym: four neurons per lane, pair-steps 0..2 are pair 0's steps 0..2");
+                nf4 w01[4], w23[4];
+                nf2 x2n, q2n;
+                nd2 d0;
+                __builtin_amdgcn_s_setprio(2);                 // (pair 0's priority, as below: the region holds the pair's first two steps)
+                slot_top_sym<RB>(w01, w23, x2n, q2n, d0, u[0][0], u[0][1], u[1][0], u[1][1], u[2][0], u[2][1], u[3][0], u[3][1],
+                                 lds + row_off(0, false), lds + row_off(0, true), lds + o_wq + pbq, lds + rbm);
+                // (the region ends with lgkmcnt(0); the builtin says so to hipcc's waitcnt pass, which does not read an asm statement and
+                //  otherwise drains the queue at its own first wait of the slot, right behind the requests of the pair-step after:
+                //  0xC07F = lgkmcnt(0) alone, vmcnt and expcnt left at their maxima -- the LDS-DMA pieces stay in flight)
+                __builtin_amdgcn_s_waitcnt(0xC07F);
+                xbuf[0] = make_float2(x2n.x, x2n.y); qbuf[0] = make_float2(q2n.x, q2n.y);      // the rows of pair-step 2
+                dcur = make_double2(d0.x, d0.y);
+#pragma unroll
+                for (int n = 0; n < NL; ++n) {
+                    fwq[0][n] = make_float2(w01[n].x, w01[n].y); fwq[1][n] = make_float2(w01[n].z, w01[n].w);
+                    fwq[2][n] = make_float2(w23[n].x, w23[n].y); fwq[3][n] = make_float2(w23[n].z, w23[n].w);
+                }
+            } else if constexpr (kBatchTop) {
                 // What pair-step 0 consumes -- its rows and the (w, q) of steps 0 and 1 -- as ONE asm region with its wait inside: one
                 // round trip of six requests.  The rest (steps 2 and 3, the first row of the dot products) is requested behind it with
                 // plain reads and lands under pair-step 0's arithmetic.  Left to hipcc the slot's top was two round trips in sequence
@@ -946,12 +972,22 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
 #pragma unroll
                 for (int st = 0; st < B; ++st) {
                     const int ips = p * B + st;                                  // this pair-step; its operands sit in buffer ips % PF
+                    if (kTopSym && ips < 2) continue;                            // (done inside slot_top_sym)
                     const float2 x2 = xbuf[ips % PF], q2 = qbuf[ips % PF];
                     const int pn = (ips + 1) / B, sn = (ips + 1) % B;            // (the GPFQ_BLK_X_LDS2 experiment re-reads the next one)
                     (void)pn; (void)sn;
                     if (ips + PF < NPS) {
                         xbuf[ips % PF] = lds_ld<float2>(lds, row_off(ips + PF, false));
                         qbuf[ips % PF] = lds_ld<float2>(lds, row_off(ips + PF, true));
+                    }
+                    // (kTopSym: the pieces of pair-steps 0 and 1 -- M0 and scalar address stepping cannot sit inside the region -- go out at
+                    //  pair-steps 2 and 3, in front of those pair-steps' own: two back to back at the most, never a burst)
+                    if (kTopSym && ips < 4) {
+#pragma unroll
+                        for (int i = 0; i < PPP; ++i) {
+                            const int k = (PTS * (ips - 2)) * PPP + i;
+                            if (PTS * B * PPP <= PER_MIN || k < PER_MIN) issue_piece(bn, k);
+                        }
                     }
                     if (p < PTS) {
 #pragma unroll

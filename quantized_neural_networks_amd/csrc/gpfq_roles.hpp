@@ -235,6 +235,68 @@ __device__ __forceinline__ void lds_read_slot_top(nf2 &x, nf2 &q, nf4 (&w)[4], l
                  : "=&v"(x), "=&v"(q), "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]), "=&v"(w[3])
                  : "v"((unsigned)(uintptr_t)px), "v"((unsigned)(uintptr_t)pq), "v"((unsigned)(uintptr_t)pwq) : "memory");
 }
+// slot_top_sym: the top of a fused slot for SYMMETRIC alphabets in the same shapes, requests AND the first two pair-steps in one region.
+// All fifteen reads of the slot's head are requested at once, in the order of their use -- pair-step 0's rows and the (w, q) of steps
+// 0 and 1 (16 bytes per neuron at aw + 32 n), the rows of pair-step 1 (RB bytes behind pair-step 0's), the (w, q) of steps 2 and 3
+// (aw + 32 n + 16), the first row of the dot products, the rows of pair-step 2 (2 RB) -- and the arithmetic of pair-steps 0 and 1 (pair 0,
+// steps 0 and 1) runs
+// under counted waits: the LDS answers in order, so lgkmcnt(n) with n requests behind the wanted one still out is exact, and any other
+// request the wavefront may have outstanding only makes the wait longer.  Per pair-step and neuron: pr = {w, w} * x (v_pk_mul_f32),
+// dd = {-sg, -sg} * f32(a xq) + pr (v_pk_fma_f32: one rounding), two conversions, two float64 additions into u -- update_pair's
+// instructions in the order hipcc gives them (stage by stage: no instruction consumes the result of the one in front of it, and no
+// s_nop is needed where hipcc places none).  The last wait is lgkmcnt(0): every output has landed where the compiler first sees it.
+// A 32-bit half of a 64-bit operand and a 64-bit half of a 128-bit one cannot be named through an asm operand, so the values the
+// arithmetic takes apart sit in named registers: the (w, q) of steps 0 and 1 in v[22:37] (outputs), the rows of pair-steps 0 and 1,
+// the products and the conversions in v[148:167] (clobbered; above what the sweep's loop uses, inside the kernel's 168).
+template <int RB>
+__device__ __forceinline__ void slot_top_sym(nf4 (&w01)[4], nf4 (&w23)[4], nf2 &x2, nf2 &q2, nd2 &d,
+                                             double &u00, double &u01, double &u10, double &u11, double &u20, double &u21, double &u30, double &u31,
+                                             lchar *px, lchar *pq, lchar *pwq, lchar *pd)
+{
+    static_assert(2 * RB + 8 <= 65536, "the rows of pair-steps 1 and 2 are reached through the 16-bit offset field");
+#define GPFQ_TOP_PAIR_STEP(W0, W1, W2, W3, X, XL, XH, Q)                                                           \
+    "v_pk_fma_f32 v[152:153], " W0 ", " Q ", v[152:153] op_sel:[1,0,0]\n\t"                                        \
+    "v_pk_fma_f32 v[154:155], " W1 ", " Q ", v[154:155] op_sel:[1,0,0]\n\t"                                        \
+    "v_pk_fma_f32 v[156:157], " W2 ", " Q ", v[156:157] op_sel:[1,0,0]\n\t"                                        \
+    "v_pk_fma_f32 " X ", " W3 ", " Q ", " X " op_sel:[1,0,0]\n\t"                                                  \
+    "v_cvt_f64_f32 " Q ", v152\n\tv_cvt_f64_f32 v[152:153], v153\n\t"                                              \
+    "v_cvt_f64_f32 v[158:159], v154\n\tv_cvt_f64_f32 v[154:155], v155\n\t"                                         \
+    "v_cvt_f64_f32 v[160:161], v156\n\tv_cvt_f64_f32 v[156:157], v157\n\t"                                         \
+    "v_cvt_f64_f32 v[162:163], " XL "\n\tv_cvt_f64_f32 " X ", " XH "\n\t"                                          \
+    "v_add_f64 %[u01], %[u01], v[152:153]\n\tv_add_f64 %[u10], %[u10], v[158:159]\n\t"                             \
+    "v_add_f64 %[u11], %[u11], v[154:155]\n\tv_add_f64 %[u20], %[u20], v[160:161]\n\t"                             \
+    "v_add_f64 %[u21], %[u21], v[156:157]\n\tv_add_f64 %[u30], %[u30], v[162:163]\n\t"                             \
+    "v_add_f64 %[u00], %[u00], " Q "\n\tv_add_f64 %[u31], %[u31], " X "\n\t"
+    asm volatile("ds_read_b64 v[148:149], %[ax]\n\tds_read_b64 v[150:151], %[aq]\n\t"
+                 "ds_read_b128 v[34:37], %[aw]\n\tds_read_b128 v[30:33], %[aw] offset:32\n\t"
+                 "ds_read_b128 v[26:29], %[aw] offset:64\n\tds_read_b128 v[22:25], %[aw] offset:96\n\t"
+                 "ds_read_b64 v[164:165], %[ax] offset:%[r1]\n\tds_read_b64 v[166:167], %[aq] offset:%[r1]\n\t"
+                 "ds_read_b128 %[w2], %[aw] offset:16\n\tds_read_b128 %[w3], %[aw] offset:48\n\t"
+                 "ds_read_b128 %[w4], %[aw] offset:80\n\tds_read_b128 %[w5], %[aw] offset:112\n\t"
+                 "ds_read_b128 %[d], %[ad]\n\t"
+                 "ds_read_b64 %[x2], %[ax] offset:%[r2]\n\tds_read_b64 %[q2], %[aq] offset:%[r2]\n\t"
+                 // pair-step 0: fifteen requests out; its rows and neuron n's (w, q) are the first 3 + n of them
+                 "s_waitcnt lgkmcnt(12)\n\tv_pk_mul_f32 v[152:153], v[148:149], v[34:35] op_sel_hi:[1,0]\n\t"
+                 "s_waitcnt lgkmcnt(11)\n\tv_pk_mul_f32 v[154:155], v[148:149], v[30:31] op_sel_hi:[1,0]\n\t"
+                 "s_waitcnt lgkmcnt(10)\n\tv_pk_mul_f32 v[156:157], v[148:149], v[26:27] op_sel_hi:[1,0]\n\t"
+                 "s_waitcnt lgkmcnt(9)\n\tv_pk_mul_f32 v[148:149], v[148:149], v[22:23] op_sel_hi:[1,0]\n\t"
+                 GPFQ_TOP_PAIR_STEP("v[34:35]", "v[30:31]", "v[26:27]", "v[22:23]", "v[148:149]", "v148", "v149", "v[150:151]")
+                 // pair-step 1: its rows are requests 7 and 8; the seven behind them may still be out
+                 "s_waitcnt lgkmcnt(7)\n\tv_pk_mul_f32 v[152:153], v[164:165], v[36:37] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[154:155], v[164:165], v[32:33] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[156:157], v[164:165], v[28:29] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[164:165], v[164:165], v[24:25] op_sel_hi:[1,0]\n\t"
+                 GPFQ_TOP_PAIR_STEP("v[36:37]", "v[32:33]", "v[28:29]", "v[24:25]", "v[164:165]", "v164", "v165", "v[166:167]")
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&{v[34:37]}"(w01[0]), "=&{v[30:33]}"(w01[1]), "=&{v[26:29]}"(w01[2]), "=&{v[22:25]}"(w01[3]),
+                   [w2] "=&v"(w23[0]), [w3] "=&v"(w23[1]), [w4] "=&v"(w23[2]), [w5] "=&v"(w23[3]), [d] "=&v"(d), [x2] "=&v"(x2), [q2] "=&v"(q2),
+                   [u00] "+v"(u00), [u01] "+v"(u01), [u10] "+v"(u10), [u11] "+v"(u11), [u20] "+v"(u20), [u21] "+v"(u21), [u30] "+v"(u30), [u31] "+v"(u31)
+                 : [ax] "v"((unsigned)(uintptr_t)px), [aq] "v"((unsigned)(uintptr_t)pq), [aw] "v"((unsigned)(uintptr_t)pwq), [ad] "v"((unsigned)(uintptr_t)pd),
+                   [r1] "i"(RB), [r2] "i"(2 * RB)
+                 : "memory", "v148", "v149", "v150", "v151", "v152", "v153", "v154", "v155", "v156", "v157", "v158", "v159", "v160", "v161", "v162",
+                   "v163", "v164", "v165", "v166", "v167");
+#undef GPFQ_TOP_PAIR_STEP
+}
 __device__ __forceinline__ int lds_read_now(lchar *p)
 {
     int v;
