@@ -238,6 +238,14 @@ int gpfq_call_status(const void *workspace, void *stream);
  *   nrm32    [device] from gpfq_row_norms.
  *   qidx, Qt, resid [device] outputs; any of them may be NULL.  u_out [device] optional.
  *   workspace [device], workspace_bytes >= gpfq_workspace_bytes(N, m, C, path).
+ *
+ * Layouts (this call, gpfq_row_norms, gpfq_quantize_neurons_gram and the gpfq_quantize_dense_layer family; pinned down by
+ * tests/test_operand_layouts_gpu.py): a pitch (ld, ldw, ldc, ldo) is any value >= the row length, and a device pointer needs only the
+ * natural alignment of its element (4 bytes for float32, 8 for float64, 2 for int16 indices, none for int8) -- the 16-byte loads and
+ * stores are taken where pitch and address allow them and never change a result.  The exceptions are the workspaces and dev_alphabet
+ * (16 bytes, checked) and gpfq_layer_alphabet_from_kernel's W (16 bytes, GPFQ_ERR_UNSUPPORTED otherwise).  Padding -- the elements
+ * between a row's end and the next row, and whatever surrounds a matrix -- is never written, and its contents (NaN included) never
+ * influence a result.
  */
 int gpfq_quantize_neurons(const float *X, const float *Xq, int64_t ld, const float *nrm32,
                           const float *Wt, int64_t ldw,

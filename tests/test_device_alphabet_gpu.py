@@ -109,10 +109,38 @@ def test_dense_layer_shard_of_a_layer_neuron_major(hip, layer, oracle_mod):
             assert b == 2
         Qk, Ik = hip.assemble_kernel_device(gathered.contiguous(), d, bits=bits, N=N)
         assert np.array_equal(Ik.cpu().numpy(), idx.T) and np.array_equal(Qk.cpu().numpy(), Q.T.astype(np.float32))
-    # a shard written straight into the whole layer's Keras-layout tensors leaves the other columns alone
+    # a shard asked for in the whole layer's Keras layout: its columns of whole-layer tensors
     r = hip.quantize_dense_layer(Xd, Xqd, Wd, d, 64, 128)
     assert np.array_equal(r["idx"][:, 64:128].cpu().numpy(), idx[64:128].T)
     assert np.array_equal(r["Q"][:, 64:128].cpu().numpy(), Q[64:128].T.astype(np.float32))
+    # ... and written by the kernel itself (GPFQ_LAYOUT_KERAS through the C ABI, in the 16-neuron four-step shape -- which this width only
+    # has on rows of at most 768 samples with the narrow shapes switched off: the first 600 samples of the rows above, at their pitch of
+    # 800) straight into whole-layer tensors that hold a sentinel everywhere: the shard's columns are the oracle's, every other element
+    # still holds the sentinel.  (More shards, pitches and offsets: tests/test_operand_layouts_gpu.py.)
+    import ctypes
+    lib = hip.load()
+    m6 = 600
+    Q6, idx6, resid6 = oracle_mod.layer(W, np.ascontiguousarray(X[:, :m6]), np.ascontiguousarray(Xq[:, :m6]), alphabet)
+    arr = (ctypes.c_double * 3)(*[float(v) for v in unit])
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    with hip.options(blk_quad_groups=0, blk_pair_groups=0):
+        for lo, hi in ((64, 128), (128, 150), (3, 4)):
+            assert lib.gpfq_dense_layer_keras_out_supported(N, m6, hi - lo, arr, 3) == 1
+            Ik = torch.full((N, C), 77, dtype=torch.int8, device="cuda")
+            Qk = torch.full((N, C), -7.0, dtype=torch.float32, device="cuda")
+            rs = torch.empty(hi - lo, dtype=torch.float64, device="cuda")
+            ws = hip.dense_layer_workspace(N, m6, hi - lo, "cuda")
+            rc = lib.gpfq_quantize_dense_layer(Xd.data_ptr(), Xqd.data_ptr(), m, None, Wd.data_ptr(), C, lo, hi - lo, d.buf.data_ptr(), arr, 3,
+                                               N, m6, Ik.data_ptr(), Qk.data_ptr(), hip.GPFQ_LAYOUT_KERAS, C, rs.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), stream)
+            assert rc == 0, lib.gpfq_last_error()
+            assert hip.call_status(ws) == 0
+            Ih, Qh = Ik.cpu().numpy(), Qk.cpu().numpy()
+            assert np.array_equal(Ih[:, lo:hi], idx6[lo:hi].T) and np.array_equal(Qh[:, lo:hi], Q6[lo:hi].T.astype(np.float32))
+            other = np.ones(C, dtype=bool)
+            other[lo:hi] = False
+            assert (Ih[:, other] == 77).all() and (Qh[:, other] == -7.0).all(), (lo, hi)
+            np.testing.assert_allclose(rs.cpu().numpy(), resid6[lo:hi], rtol=RESID_RTOL)
 
 
 def test_degenerate_radius_is_caught_on_the_device_and_the_layer_rerun(hip, layer, oracle_mod):
