@@ -435,7 +435,12 @@ int gpfq_assemble_kernel_colrad(const void *qidx, int bits, int layout, const do
  * call of one shape.  Any B >= 1, N >= 0, C; the kernel walks the batch in tiles itself.  Weights t >= N (the pad codes; code 0 is
  * the first member when zero_code is 0) meet zeros, and x is not read beyond column N.
  *   x [device] f32 [B][ldx], ldx >= N; packed 16-byte aligned; bias [device] f32 [C] or NULL; y [device] f32 [B][ldy], ldy >= C.
- * All four are asynchronous on `stream` and take no workspace.
+ * gpfq_packed_dense_forward_tiled: the same product, arguments, checks and status codes, for batches beyond a few rows: a workgroup
+ * holds 16 output channels against 16, 32 or 64 batch rows per pass of the codes, on the exact-f32 matrix instruction.  float32
+ * products and sums (fused multiply-adds: per wavefront a chain in the order of the weights it owns, the four chains of a workgroup
+ * added in a fixed order) in an order the kernel chooses, the same for every call of one shape; row b of y depends on row b of x
+ * alone.  Any B >= 1, N >= 0 (N = 0: y = bias, or 0), C; x is not read beyond column N or row B.
+ * All five are asynchronous on `stream` and take no workspace.
  */
 int    gpfq_packed_bits(int M, int zero_code);
 size_t gpfq_packed_row_bytes(int64_t R, int bits);
@@ -447,6 +452,9 @@ int gpfq_unpack_kernel(const uint8_t *packed, int bits, int zero_code, const dou
 int gpfq_packed_dense_forward(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int bits, int zero_code,
                               const double *radii, const double *unit_alphabet, int M, const float *bias, int64_t N, int64_t C,
                               float *y, int64_t ldy, void *stream);
+int gpfq_packed_dense_forward_tiled(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int bits, int zero_code,
+                                    const double *radii, const double *unit_alphabet, int M, const float *bias, int64_t N, int64_t C,
+                                    float *y, int64_t ldy, void *stream);
 
 /*
  * Search over the alphabet scalar (a sequence as alphabet_scalar).  K candidate scalars s_0 .. s_{K-1}

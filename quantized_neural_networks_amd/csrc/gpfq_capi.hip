@@ -809,9 +809,13 @@ int gpfq_unpack_kernel(const uint8_t *packed, int bits, int zero_code, const dou
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_unpack_kernel");
 }
 
-int gpfq_packed_dense_forward(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int bits, int zero_code,
-                              const double *radii, const double *unit_alphabet, int M, const float *bias, int64_t N, int64_t C,
-                              float *y, int64_t ldy, void *stream)
+// Both forward entries: one set of argument checks, and the launcher of the kernel family named.
+typedef hipError_t (*PackedForwardLaunch)(const float *, int64_t, int64_t, const uint8_t *, int, int, const double *, const gpfq::AlphabetArg &,
+                                          const float *, int64_t, int64_t, float *, int64_t, hipStream_t);
+
+static int packed_forward_entry(const char *name, PackedForwardLaunch launch, const float *x, int64_t B, int64_t ldx, const uint8_t *packed,
+                                int bits, int zero_code, const double *radii, const double *unit_alphabet, int M, const float *bias,
+                                int64_t N, int64_t C, float *y, int64_t ldy, void *stream)
 {
     if (B < 0 || N < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size B=%lld N=%lld C=%lld", (long long)B, (long long)N, (long long)C);
     HostAlphabet H;
@@ -828,9 +832,24 @@ int gpfq_packed_dense_forward(const float *x, int64_t B, int64_t ldx, const uint
         if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "packed must be 16-byte aligned");
     }
     if (C > 2147483647LL * 8) return fail(GPFQ_ERR_UNSUPPORTED, "layer too wide for one launch");
-    hipError_t e = gpfq::launch_packed_dense_forward(x, B, ldx, packed, bits, zero_code, radii, H.A, bias, N, C, y, ldy,
-                                                     static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_packed_dense_forward");
+    hipError_t e = launch(x, B, ldx, packed, bits, zero_code, radii, H.A, bias, N, C, y, ldy, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
+}
+
+int gpfq_packed_dense_forward(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int bits, int zero_code,
+                              const double *radii, const double *unit_alphabet, int M, const float *bias, int64_t N, int64_t C,
+                              float *y, int64_t ldy, void *stream)
+{
+    return packed_forward_entry("gpfq_packed_dense_forward", gpfq::launch_packed_dense_forward, x, B, ldx, packed, bits, zero_code, radii,
+                                unit_alphabet, M, bias, N, C, y, ldy, stream);
+}
+
+int gpfq_packed_dense_forward_tiled(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int bits, int zero_code,
+                                    const double *radii, const double *unit_alphabet, int M, const float *bias, int64_t N, int64_t C,
+                                    float *y, int64_t ldy, void *stream)
+{
+    return packed_forward_entry("gpfq_packed_dense_forward_tiled", gpfq::launch_packed_dense_forward_tiled, x, B, ldx, packed, bits,
+                                zero_code, radii, unit_alphabet, M, bias, N, C, y, ldy, stream);
 }
 
 int gpfq_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii, const float *layer_median,

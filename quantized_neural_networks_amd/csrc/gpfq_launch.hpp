@@ -277,6 +277,10 @@ hipError_t launch_unpack_kernel(const uint8_t *packed, int bits, int zero_code, 
 hipError_t launch_packed_dense_forward(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int bits, int zero_code,
                                        const double *radii, const AlphabetArg &U, const float *bias, int64_t N, int64_t C, float *y,
                                        int64_t ldy, hipStream_t stream);
+// gpfq_packed_tiled.hip: the same product on exact-f32 MFMA tiles, 16 neurons x 16 / 32 / 64 batch rows per pass of the codes
+hipError_t launch_packed_dense_forward_tiled(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int bits, int zero_code,
+                                             const double *radii, const AlphabetArg &U, const float *bias, int64_t N, int64_t C, float *y,
+                                             int64_t ldy, hipStream_t stream);
 // gpfq_search.hip (a sequence as alphabet_scalar): the K candidate scalars travel by value
 constexpr int kSearchMaxK = 16;
 struct SearchScalars {

@@ -60,6 +60,7 @@ SYMBOLS = {
     "gpfq_pack_codes": (_int, [_vp, _i64, _i64, _int, _int, _vp, _vp]),
     "gpfq_unpack_kernel": (_int, [_vp, _int, _int, _vp, _dp, _int, _i64, _i64, _vp, _i64, _vp, _vp]),
     "gpfq_packed_dense_forward": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _dp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "gpfq_packed_dense_forward_tiled": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _dp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
     "gpfq_candidate_kernels": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dp, _int, _vp, _vp, _i64, _i64, _i64, _vp]),
     "gpfq_select_candidates_workspace_bytes": (_sz, [_int, _i64]),
     "gpfq_select_candidates": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _dp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
@@ -1253,9 +1254,8 @@ def unpack_kernel(packed, bits, zero_code, radii, unit_alphabet, R, want_values=
     return Q, idx
 
 
-def packed_dense_forward(x, packed, bits, zero_code, radii, unit_alphabet, N, bias=None, out=None):
-    """y f32 [B][C] = x [B][N] . q (+ bias) with the Dense kernel q [N][C] held as packed rows (gpfq_packed_dense_forward): the float
-    kernel is never formed.  x: rows contiguous (any row pitch); out: an optional [B][C] tensor with contiguous rows.  No sync."""
+def _packed_forward(entry, x, packed, bits, zero_code, radii, unit_alphabet, N, bias, out):
+    """The checks and the call of both forward entries (the same parameter list)."""
     _dev(x, torch.float32, "x")
     xp, B, Nx, ldx = _rows(x, "x")
     if Nx != int(N):
@@ -1273,7 +1273,18 @@ def packed_dense_forward(x, packed, bits, zero_code, radii, unit_alphabet, N, bi
     if (By, Cy) != (B, C):
         raise GpfqError(f"out {tuple(out.shape)} must be [{B}][{C}]")
     with torch.cuda.device(x.device):
-        _check(load().gpfq_packed_dense_forward(xp, B, ldx, packed.data_ptr(), int(bits), int(zero_code), radii.data_ptr(), arr, M,
-                                                bias.data_ptr() if bias is not None else None, int(N), C, yp, ldy, _stream()),
-               "gpfq_packed_dense_forward")
+        _check(getattr(load(), entry)(xp, B, ldx, packed.data_ptr(), int(bits), int(zero_code), radii.data_ptr(), arr, M,
+                                      bias.data_ptr() if bias is not None else None, int(N), C, yp, ldy, _stream()), entry)
     return out
+
+
+def packed_dense_forward(x, packed, bits, zero_code, radii, unit_alphabet, N, bias=None, out=None):
+    """y f32 [B][C] = x [B][N] . q (+ bias) with the Dense kernel q [N][C] held as packed rows (gpfq_packed_dense_forward): the float
+    kernel is never formed.  x: rows contiguous (any row pitch); out: an optional [B][C] tensor with contiguous rows.  No sync."""
+    return _packed_forward("gpfq_packed_dense_forward", x, packed, bits, zero_code, radii, unit_alphabet, N, bias, out)
+
+
+def packed_dense_forward_tiled(x, packed, bits, zero_code, radii, unit_alphabet, N, bias=None, out=None):
+    """The same product, arguments and checks on the tiled kernel (gpfq_packed_dense_forward_tiled): 16 output channels against up to
+    64 batch rows per pass of the codes, for batches beyond the few rows packed_dense_forward is for.  No sync."""
+    return _packed_forward("gpfq_packed_dense_forward_tiled", x, packed, bits, zero_code, radii, unit_alphabet, N, bias, out)

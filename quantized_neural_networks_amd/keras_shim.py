@@ -217,6 +217,13 @@ class Dense(Layer):
 # and 4 rows (0.37, 0.50 and 0.81 of the float kernel's time, ternary) and loses at 8 (1.43).
 PACKED_FORWARD_MAX_BATCH = 4
 
+# Largest batch a PackedDense layer runs through gpfq_packed_dense_forward_tiled (above PACKED_FORWARD_MAX_BATCH rows); beyond it the
+# layer decodes its kernel and multiplies.  The rule: the largest probed batch such that at it, and at every smaller probed batch above
+# 4, the tiled kernel's median is at most 0.95 of decode + matmul's on both 4096 x 4096 shapes with the weights "same"
+# (tools/packed_forward_probe.py -> profiles/packed_forward_tiled.txt); 4 -- nothing routed -- if there is none.  Measured: 0.29 - 0.70 of decode + matmul's time from 5 to 64
+# rows, 0.82 (ternary) and 0.92 (16 levels) at 128 rows, 1.50 and 1.68 at 256.
+PACKED_TILED_MAX_BATCH = 128
+
 
 class PackedDense(Dense):
     """A Dense layer that holds its quantized kernel as packed low-bit codes (deploy.load_packed): only the
@@ -263,10 +270,10 @@ class PackedDense(Dense):
             raise RuntimeError(f"PackedDense layer {self.name} holds no packed kernel (deploy.load_packed installs one)")
         x2 = x.reshape(-1, self.fan_in)
         bias = self._weights[0] if self.use_bias else None
-        if 0 < x2.shape[0] <= PACKED_FORWARD_MAX_BATCH:
+        if 0 < x2.shape[0] <= max(PACKED_FORWARD_MAX_BATCH, PACKED_TILED_MAX_BATCH):
             p = self.packed
-            y = hip.packed_dense_forward(x2.contiguous(), p["codes"], p["bits"], p["zero_code"], p["radii"], p["alphabet"], self.fan_in,
-                                         bias=bias)
+            forward = hip.packed_dense_forward if x2.shape[0] <= PACKED_FORWARD_MAX_BATCH else hip.packed_dense_forward_tiled
+            y = forward(x2.contiguous(), p["codes"], p["bits"], p["zero_code"], p["radii"], p["alphabet"], self.fan_in, bias=bias)
         else:
             y = x2 @ self._kernel()
             if bias is not None:

@@ -1,19 +1,28 @@
-"""Measures a Dense layer run three ways at small batches -> profiles/packed_forward.txt:
+"""Measures a Dense layer run four ways at small batches -> profiles/packed_forward_tiled.txt
+(profiles/packed_forward.txt is the record of the first three, taken before the fourth existed):
 
     packed    gpfq_packed_dense_forward on the packed rows
     float     x @ Q on the float32 kernel (torch.matmul)
     decode    gpfq_unpack_kernel + torch.matmul
+    tiled     gpfq_packed_dense_forward_tiled on the packed rows
 
-Shapes 4096 x 4096 (ternary, 16 levels) and 25088 x 4096 (ternary), batches 1 .. 128.  Every figure is device time per call: the
-call is captured `--chain` times into a graph (a launch from Python costs more host time than these kernels run), the graph is
-replayed, the replays are timed with device events and the three ways alternate; median (min) over the replays.  Two cache states:
-"same" -- every call reads the same weights (what a repeated loop sees: a 64 MB float kernel stays in the 256 MiB last-level cache) --
-and "rotated" -- the calls of a chain walk over copies of the layer that together exceed that cache in float32 (what a network of
-many layers sees).  The switch-over constant keras_shim.PACKED_FORWARD_MAX_BATCH follows from the "same" table, the state that
-favours the float kernel: the largest measured batch at which the packed kernel beat both other ways on both 4096 x 4096 shapes
-(1 if there is none).  Also the file sizes of a VGG16-shaped Dense stack written by save_model and by export_packed.
+Shapes 4096 x 4096 (ternary, 16 levels) and 25088 x 4096 (ternary), and 4096 x 1000 (ternary) for what a layer of few column tiles
+costs the tiled kernel (63 workgroups on 256 compute units); batches 1 .. 256.  Every figure is device time per call: the call is
+captured `--chain` times into a graph (a launch from Python costs more host time than these kernels run), the graph is replayed, the
+replays are timed with device events and the four ways alternate; median (min) over the replays.  Two cache states: "same" -- every
+call reads the same weights (what a repeated loop sees: a 64 MB float kernel stays in the 256 MiB last-level cache) -- and "rotated"
+-- the calls of a chain walk over copies of the layer that together exceed that cache in float32 (what a network of many layers
+sees).
 
-    python tools/packed_forward_probe.py [--out profiles/packed_forward.txt] [--quick]
+The switch-over constant keras_shim.PACKED_FORWARD_MAX_BATCH follows from the "same" table, the state that favours the float kernel:
+the largest measured batch at which the packed kernel beat both other ways on both 4096 x 4096 shapes (1 if there is none).
+keras_shim.PACKED_TILED_MAX_BATCH follows from the same table: the largest probed batch such that at it, and at every smaller probed
+batch above 4, the tiled kernel's median is at most 0.95 of decode + matmul's -- the only other way a layer that holds no float kernel
+has -- on both 4096 x 4096 shapes (4 if there is none: nothing is routed).
+
+Also the file sizes of a VGG16-shaped Dense stack written by save_model and by export_packed.
+
+    python tools/packed_forward_probe.py [--out profiles/packed_forward_tiled.txt] [--quick]
 """
 import argparse
 import os
@@ -27,7 +36,8 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from quantized_neural_networks_amd import deploy, hip, keras_shim as ks  # noqa: E402
 
-BATCHES = (1, 2, 4, 8, 16, 32, 64, 128)
+BATCHES = (1, 2, 4, 5, 8, 16, 32, 64, 128, 256)
+TILED_MARGIN = 0.95                                 # tiled / (decode + matmul) at or below this: the tiled kernel is routed
 
 
 def on_alphabet(rng, N, C, M, dev):
@@ -76,12 +86,13 @@ def measure(label, N, C, M, args, dev, out):
     p0 = layers[0][0]
     out(f"{label}: N={N} C={C} M={M}: {p0['bits']}-bit codes, {p0['codes'].numel() / 1e6:.1f} MB packed against "
         f"{N * C * 4 / 1e6:.1f} MB float32; rotated = {copies_rot} copies")
-    wins = {}
+    wins, tiled = {}, {}
     for state, ncopies in (("same", 1), ("rotated", copies_rot)):
-        out(f"  weights {state}; us per call, median (min):   B    packed          float           decode+matmul   packed/float  packed/decode")
+        out(f"  weights {state}; us per call, median (min):   B    packed          float           decode+matmul   tiled           "
+            f"packed/float  packed/decode  tiled/decode  tiled/packed")
         for B in BATCHES:
             x = torch.randn((B, N), device=dev)
-            y = [torch.empty((B, C), device=dev) for _ in range(3)]
+            y = [torch.empty((B, C), device=dev) for _ in range(4)]
 
             def f_packed(i):
                 p = layers[i % ncopies][0]
@@ -95,17 +106,23 @@ def measure(label, N, C, M, args, dev, out):
                 Qd, _ = hip.unpack_kernel(p["codes"], p["bits"], p["zero_code"], p["radii"], p["alphabet"], N)
                 torch.matmul(x, Qd, out=y[2])
 
-            graphs = [capture(f, args.chain) for f in (f_packed, f_float, f_decode)]
+            def f_tiled(i):
+                p = layers[i % ncopies][0]
+                hip.packed_dense_forward_tiled(x, p["codes"], p["bits"], p["zero_code"], p["radii"], p["alphabet"], N, out=y[3])
+
+            graphs = [capture(f, args.chain) for f in (f_packed, f_float, f_decode, f_tiled)]
             res = timed(graphs, args.replays)
             us = [(1e3 * m / args.chain, 1e3 * lo / args.chain) for m, lo in res]
             ref64 = x.double() @ layers[(args.chain - 1) % ncopies][1].double()
             err = [float((t.double() - ref64).abs().max() / ref64.abs().max()) for t in y]
             assert max(err) < 1e-4, err
             out(f"                                              {B:4d}  {us[0][0]:7.2f} ({us[0][1]:6.2f})  {us[1][0]:7.2f} ({us[1][1]:6.2f})  "
-                f"{us[2][0]:7.2f} ({us[2][1]:6.2f})     {us[0][0] / us[1][0]:5.2f}        {us[0][0] / us[2][0]:5.2f}")
+                f"{us[2][0]:7.2f} ({us[2][1]:6.2f})  {us[3][0]:7.2f} ({us[3][1]:6.2f})     {us[0][0] / us[1][0]:5.2f}        "
+                f"{us[0][0] / us[2][0]:5.2f}         {us[3][0] / us[2][0]:5.2f}         {us[3][0] / us[0][0]:5.2f}")
             wins[(state, B)] = us[0][0] < us[1][0] and us[0][0] < us[2][0]
+            tiled[(state, B)] = us[3][0] <= TILED_MARGIN * us[2][0]
             del graphs
-    return wins
+    return wins, tiled
 
 
 def file_sizes(dev, out):
@@ -146,15 +163,24 @@ def main():
         lines.append(s)
 
     out(f"# {torch.cuda.get_device_name(dev)}; device time per call: {args.chain} calls captured into one graph, {args.replays} timed replays "
-        f"per form, the three forms alternating; median (min); us")
+        f"per form, the four forms alternating; median (min); us")
     shapes = [("fc 4096 x 4096 ternary", 4096, 4096, 3)]
     if not args.quick:
-        shapes += [("fc 4096 x 4096 16 levels", 4096, 4096, 16), ("VGG16 fc1 25088 x 4096 ternary", 25088, 4096, 3)]
-    wins = [measure(*s, args, dev, out) for s in shapes]
-    square = wins[:2]
+        shapes += [("fc 4096 x 4096 16 levels", 4096, 4096, 16), ("VGG16 fc1 25088 x 4096 ternary", 25088, 4096, 3),
+                   ("fc 4096 x 1000 ternary (63 column tiles)", 4096, 1000, 3)]
+    results = [measure(*s, args, dev, out) for s in shapes]
+    square, square_tiled = [w for w, _ in results[:2]], [t for _, t in results[:2]]
     both = [B for B in BATCHES if all(w[("same", B)] for w in square)]
     out(f"# switch-over: batches at which the packed kernel beat both other ways on {'both' if len(square) == 2 else 'the'} 4096 x 4096 "
         f"shape{'s' if len(square) == 2 else ''}, weights same: {both or 'none'} -> PACKED_FORWARD_MAX_BATCH = {max(both) if both else 1}")
+    routed = 4
+    for B in (b for b in BATCHES if b > 4):
+        if not all(t[("same", B)] for t in square_tiled):
+            break
+        routed = B
+    out(f"# tiled kernel: the largest probed batch with tiled <= {TILED_MARGIN} x (decode + matmul) at it and at every smaller probed batch "
+        f"above 4, on {'both' if len(square) == 2 else 'the'} 4096 x 4096 shape{'s' if len(square) == 2 else ''}, weights same "
+        f"-> PACKED_TILED_MAX_BATCH = {routed}")
     if not args.quick:
         file_sizes(dev, out)
     if args.out:
