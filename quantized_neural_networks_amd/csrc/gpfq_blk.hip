@@ -477,10 +477,14 @@ struct BlkK {
 
 // Diagnostic builds only (GPFQ_DIAG="-DGPFQ_BLK_DIAG -DGPFQ_BLK_STAMPS ...", quantized_neural_networks_amd/build.py): gpfq_blk_diag.hpp holds
 // the in-kernel phase stamps and the two A/B switches of round 4's matrix form.  The shipped translation unit compiles without it.
+// kTop3Ship: which of the slot-top pieces of the symmetric eleven-wavefront shapes are issued from inside the pair loop (blk_sweep_role,
+// kLateHdr / kLateW): bit 0 the header piece, bit 1 the weight piece.  A diagnostic build can choose another set (-DGPFQ_BLK_TOP3=n).
+constexpr int kTop3Ship = 3;
 #ifdef GPFQ_BLK_DIAG
 #include "gpfq_blk_diag.hpp"
 #else
 constexpr bool kNoMfmaD = false, kNoFused = false;
+constexpr int kTop3 = kTop3Ship;
 #define STAMP(var) do { } while (0)
 #define STAMP_DO(...)
 #endif
@@ -724,6 +728,34 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
     constexpr bool kBatchTop = kFused && NL == 4 && NSW == 11;
     // ... and with a symmetric alphabet the first two pair-steps of a slot inside the same asm region (slot_top_sym)
     constexpr bool kTopSym = kBatchTop && SYM;
+    // ... and the two LDS-DMA pieces a slot owes besides its record pieces -- the header piece of tile b + 2, the weight piece of block
+    // b + 1 -- issued from inside the pair loop instead of between the slot's barrier and its first LDS request, where every wavefront
+    // of the CU waits for the same thing and nothing hides their address arithmetic (kLateHdr, kLateW: see the pair loop).  With two
+    // issue points per step a three-pair wavefront's record pieces are out by pair-step 7: 8 and 10 are free.  A two-pair wavefront has
+    // pair-steps 6 and 7: free where such wavefronts own the pieces (the 24- and 16-pair splits, wavefronts 0 and 1: at most five pieces
+    // per tile, the last at pair-step 5).  In the 32-pair split a tile is 66 pieces, six per wavefront, and the two-pair wavefront --
+    // wavefront 7, which owns neither piece and issues both with no lane enabled -- sends its sixth record piece at pair-step 6 as
+    // well.  Never more than two pieces back to back either way.
+    constexpr bool kLateHdr = kTopSym && PW >= 2 && (kTop3 & 1) != 0, kLateW = kTopSym && PW >= 2 && (kTop3 & 2) != 0;
+    constexpr int kHdrStep = PW >= 3 ? 8 : 6, kWStep = PW >= 3 ? 10 : 7;
+    static_assert(!(kLateHdr || kLateW) || (PW <= 3 && B == 4 && PTS == 2 && PER_MIN <= 6), "the free pair-steps of a two- or three-pair wavefront");
+    // (kLateW) The weight piece's source, stepped by B ldt per slot instead of rebuilt from (jn, t) with 64-bit multiplies: lane =
+    // (neuron, step) of the block, one piece per block, wavefront 0's.  Both layouts: neuron-major (ldt = 1) and the Keras kernel (ldw = 1).
+    static_assert(!kLateW || NB * B == 64, "one 256-byte weight piece per block");
+    // The predicates are load_weights' -- wavefront 0, jn < C, t < N -- as lane masks in SCALAR registers, formed here once: the lanes of
+    // the workgroup's neurons for a whole block (w_lanes), of those the steps inside the walk for the partial block that ends it (w_tail:
+    // lane % B < N % B), no lane for a block behind the walk's end.  At pair-step 10 the sweep has no vector register to spare for a
+    // 64-bit comparison: hipcc spilled operands of the pair loop for one.
+    unsigned long long w_lanes = 0ull, w_tail = 0ull;
+    int w_whole = 0;                                              // blocks 0 .. w_whole - 1 are whole; block w_whole is the partial one, if any
+    const float *wsrc = nullptr;
+    if constexpr (kLateW) {                                       // (every other shape keeps its code)
+        w_lanes = wave == 0 ? __builtin_amdgcn_ballot_w64(jbase + lane / B < K.C) : 0ull;
+        w_tail = w_lanes & (0x1111111111111111ull * ((1ull << (int)(N % B)) - 1ull));
+        w_whole = (int)(N / B);
+        wsrc = K.Wt + (jbase + lane / B) * K.ldw + (int64_t)(B + lane % B) * K.ldt;               // block 1's, for slot 0 to request
+    }
+    (void)w_lanes; (void)w_tail; (void)w_whole; (void)wsrc;
     constexpr bool kPreloadAll = PW * B <= 8 && PW <= 5 && !kFused;
     // ... where the registers allow it (u and the operands of a slot together): otherwise they are requested at the top of
     // phase U as in round 2
@@ -833,8 +865,10 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                 if (K.Qt) K.Qt[jn * N + t] = __int_as_float(v.y);
             }
         }
-        if (b + 1 < nslots) load_weights(b + 1);                  // the block's weights: one piece
-        load_headers(b + 2, hbuf); hbuf = hbuf == 2 ? 0 : hbuf + 1;
+        if constexpr (!kLateW) {
+            if (b + 1 < nslots) load_weights(b + 1);              // the block's weights: one piece
+        }
+        if constexpr (!kLateHdr) { load_headers(b + 2, hbuf); hbuf = hbuf == 2 ? 0 : hbuf + 1; }
         const int bn = b + 1 < nslots ? b + 1 : b;                // (the last slot rewrites its own tile with the same bytes)
         STAMP(st1);
         const int tbase = (b & 1) * L.tile_pitch;
@@ -995,6 +1029,33 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                             const int k = (PTS * st + p) * PPP + i;
                             if (PTS * B * PPP <= PER_MIN || k < PER_MIN) issue_piece(bn, k);
                         }
+                    }
+                    // (kLateHdr) The header piece of tile b + 2.  The ring of three: it goes into the buffer that held tile b - 1, which the
+                    // decision wavefront last read at the end of slot b - 2 (cluster form: at the top of slot b - 1) -- free during all
+                    // of slot b; it is read at the end of slot b + 1 at the earliest, and the vmcnt(0) in front of THIS slot's barrier
+                    // (dma_wait) covers it.
+                    // (Both pieces go out under a lane mask formed in scalar registers, all lanes or none for this one, and not under a
+                    //  branch: a branch inside the unrolled pair loop splits it for hipcc's register allocation, which then spilled the
+                    //  matrix instructions' accumulators around it.)
+                    // (The slot's number is made opaque at each issue point: the scalar arithmetic of a piece -- its mask, its addresses --
+                    //  stays there instead of being hoisted to the top of the slot, which this is about.)
+                    if (kLateHdr && ips == kHdrStep) {
+                        int b2 = b + 2;
+                        asm volatile("" : "+s"(b2));
+                        // load_headers' own condition, wave < NHP && b2 <= nblk, as sign bits: scalar arithmetic, where a bool costs a vector select
+                        const unsigned on = ((unsigned)(wave - NHP) & (unsigned)(b2 - K.nblk - 1)) >> 31;
+                        glds16_s_lanes(K.hdrs + (int64_t)b2 * B * HDR + ((int64_t)wave << 10), lane16,
+                                       lds_addr(lds_generic + L.off_hr) + (unsigned)hbuf * (unsigned)L.hr_pitch + ((unsigned)wave << 10), 0ull - (unsigned long long)on);
+                        hbuf = hbuf == 2 ? 0 : hbuf + 1;
+                    }
+                    // (kLateW) The weight piece of block b + 1 goes into the parity buffer of block b - 1, which the decision wavefront
+                    // read in slot b - 1: free since that slot's barrier, and landed by the barrier that ends this one (the same vmcnt(0)).
+                    // No piece in the last slot, as before: b + 1 = nblk + 1 there, a block behind the walk's end like any other.
+                    if (kLateW && ips == kWStep) {
+                        int b1 = b + 1;
+                        asm volatile("" : "+s"(b1));
+                        glds4_lanes(wsrc, ldsW_addr + (unsigned)((b1 & 1) * NB * B * 4), b1 < w_whole ? w_lanes : b1 == w_whole ? w_tail : 0ull);
+                        wsrc += (int64_t)B * K.ldt;
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     float wv[NL], qv[NL];

@@ -3,6 +3,8 @@
 //                        per slot and left in the unused row-statistics area behind the call's counter block (tools/pipe_probe.py prints them)
 //   -DGPFQ_BLK_NO_MFMA   phase D (the block dot products) on the vector unit in every shape: the A/B of round 4's matrix form
 //   -DGPFQ_BLK_NO_FUSED  matrix-unit phase D as a phase of its own behind the updates: round 4's first form
+//   -DGPFQ_BLK_TOP3=n    which slot-top pieces of the symmetric eleven-wavefront shapes go out from inside the pair loop (kTop3Ship in
+//                        gpfq_blk.hip is the shipped set): bit 0 the header piece, bit 1 the weight piece; 0 = both at the top of the slot
 // The marginal-cost experiments of rounds 4-5 (every matrix / vector / LDS / DMA instruction issued twice, the barrier removed, pair splits
 // from the environment, the flush forced to one side) were removed in round 6; their numbers are in profiles/r04 and profiles/r05, their
 // code in the history (commit 1050215 and before).
@@ -17,6 +19,11 @@ constexpr bool kNoMfmaD = false;
 constexpr bool kNoFused = true;
 #else
 constexpr bool kNoFused = false;
+#endif
+#ifdef GPFQ_BLK_TOP3
+constexpr int kTop3 = GPFQ_BLK_TOP3;
+#else
+constexpr int kTop3 = kTop3Ship;
 #endif
 
 #ifdef GPFQ_BLK_STAMPS

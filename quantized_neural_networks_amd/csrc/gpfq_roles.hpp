@@ -55,6 +55,31 @@ __device__ __forceinline__ void glds4(const void *g, unsigned lds_dst_uniform)
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(g), "s"(lds_dst) : "memory");
 }
+// glds4 for the lanes of a wave-uniform mask only (EXEC is narrowed and restored inside the statement): a predicated piece whose
+// predicate is scalar arithmetic costs the surrounding loop no vector register, no vector comparison and no branch.  An empty mask is
+// allowed: a vector-memory load issued with EXEC = 0 moves nothing (hipcc itself leaves such loads in short skipped blocks).  The mask
+// goes into the statement as it is ("s"): one that hipcc cannot prove wave-uniform does not compile.
+__device__ __forceinline__ void glds4_lanes(const void *g, unsigned lds_dst_uniform, unsigned long long lanes_uniform)
+{
+    const unsigned lds_dst = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_dst_uniform);
+    unsigned keep;
+    unsigned long long keep_exec;
+    asm volatile("s_mov_b64 %1, exec\n\ts_and_b64 exec, exec, %4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                 "global_load_lds_dword %2, off\n\ts_mov_b32 m0, %0\n\ts_mov_b64 exec, %1"
+                 : "=&s"(keep), "=&s"(keep_exec) : "v"(g), "s"(lds_dst), "s"(lanes_uniform) : "memory", "scc");
+}
+__device__ __forceinline__ void glds16_s_lanes(const void *base_uniform, unsigned lane_off, unsigned lds_dst_uniform, unsigned long long lanes_uniform)
+{
+    const unsigned lds_dst = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_dst_uniform);
+    const unsigned long long a = (unsigned long long)(uintptr_t)base_uniform;
+    const unsigned long long sa = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
+                                  (unsigned)__builtin_amdgcn_readfirstlane((int)a);
+    unsigned keep;
+    unsigned long long keep_exec;
+    asm volatile("s_mov_b64 %1, exec\n\ts_and_b64 exec, exec, %5\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0\n\ts_mov_b64 exec, %1"
+                 : "=&s"(keep), "=&s"(keep_exec) : "v"(lane_off), "s"(sa), "s"(lds_dst), "s"(lanes_uniform) : "memory", "scc");
+}
 // The same with a wave-uniform base address in scalar registers and a 32-bit per-lane byte offset (global_load_lds ..., v, s[..]):
 // stepping the base from piece to piece is scalar arithmetic, so an LDS-DMA piece in the middle of a vector-bound loop costs
 // the loop one vector-memory issue and no vector ALU work.
