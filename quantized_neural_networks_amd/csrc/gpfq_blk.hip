@@ -613,8 +613,14 @@ template <int S> struct BlkSplit7;
 template <> struct BlkSplit7<32> { static constexpr int pw[7] = {5, 5, 5, 2, 5, 5, 5}; };
 template <> struct BlkSplit7<24> { static constexpr int pw[7] = {4, 4, 4, 1, 4, 4, 3}; };
 template <> struct BlkSplit7<16> { static constexpr int pw[7] = {3, 3, 2, 1, 3, 2, 2}; };
+// Eight neuron groups (G = 8, two neurons per lane: the lane map of blk_sweep_role's kMfmaD note), rows of 769..1024 samples: a pair is 16
+// samples, 64 of them to a row, and a lane updates two adjacent ones per pair-step -- BlkSplit<32, 11>'s proportions, the four-pair
+// wavefront being wavefront 7, on the decision wavefront's SIMD.
+struct BlkSplitOct64 { static constexpr int pw[11] = {6, 6, 6, 6, 6, 6, 6, 4, 6, 6, 6}; };
 template <int G, int S, int NSW, int NL> constexpr const int *blk_split()
 {
+    if constexpr (G == 8) { static_assert(S == 64 && NSW == 11 && NL == 2, "the eight-group map: 1024-sample rows over eleven sweep wavefronts"); return BlkSplitOct64::pw; }
+    else
     if constexpr (NSW == 7) return BlkSplit7<S>::pw;
     else
     if constexpr (G == 4 && NL < 4 && S == 32 && NSW == 8) return BlkSplitQuad32::pw;
@@ -647,13 +653,19 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
     const unsigned ldsT_addr = lds_addr(lds_generic), ldsW_addr = lds_addr(lds_generic + L.off_w);
     const int64_t N = K.N;
     const int nslots = K.nblk + 1;
-    const int o_x  = HDR + 8 * (pbase + kq);                      // float2 x   [pair]  (row t - B of record t)
+    // PU sample pairs of a lane sit side by side in a row and are updated together, one UNIT per pair-step (eight neuron groups: two --
+    // four consecutive samples, one 16-byte read per row; everywhere else a unit is a pair).  Pair p of the lane is pair pair_off(p) + PU kq
+    // of the wavefront's samples.
+    constexpr int PU = G == 8 ? 2 : 1;
+    static_assert(PW % PU == 0, "whole units per wavefront");
+    auto pair_off = [](int p) { return PU * (p / PU) * KQ + p % PU; };
+    const int o_x  = HDR + 8 * (pbase + PU * kq);                 // float2 x   [pair]  (row t - B of record t)
     int o_q = o_x + 4 * MP;                                       // float2 xq  [pair]
     // (opaque to the compiler: it would fuse the x and xq reads of a pair -- 4 MP bytes apart -- into ONE ds_read2st64_b64, which the
     //  LDS serves as two 32-bank accesses in 8 cycles; two ds_read_b64 take 2 cycles each: MI355X_MICROARCH.md, LDS)
     asm volatile("" : "+v"(o_q));
     constexpr int DB = blk_row64(G, B) ? 16 : 8;                  // bytes of a sample pair of row t + B
-    const int o_d  = HDR + 8 * MP + DB * (pbase + kq);           // double2 (float2) xqd[pair]  (row t + B)
+    const int o_d  = HDR + 8 * MP + DB * (pbase + PU * kq);      // double2 (float2) xqd[pair]  (row t + B)
     using DRaw = std::conditional_t<blk_row64(G, B), double2, float2>;   // as it sits in the record; converted where it is consumed
     auto ld_d = [&](int off) -> DRaw { return lds_ld<DRaw>(lds, off); };
     auto to_d2 = [](const DRaw &v) -> double2 { return make_double2((double)v.x, (double)v.y); };
@@ -719,13 +731,16 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
     // the two phases FUSED pair by pair (kFused): see the slot loop.
     // (NL = 4, 2 or 1 neurons per lane: 16, 8 or 4 per workgroup; four steps per slot only -- with two, half of every 4 x 4 x 4 block idles and
     //  the form measured slower than the one- / two-group shapes: DESIGN_HISTORY.md, "gpfq_blk.hip notes" 4)
-    constexpr bool kMfmaD = G == 4 && B == 4 && blk_row64(G, B) && !kNoMfmaD;
-    constexpr bool kFused = kMfmaD && !kNoFused;
+    // (eight neuron groups x two neurons per lane: the same 16 neurons under the second lane map of the kMfmaD note below; that map exists
+    //  in the fused form only, so the diagnostic switches leave it alone)
+    constexpr bool kMfmaD = (G == 4 || (G == 8 && NL == 2)) && B == 4 && blk_row64(G, B) && (!kNoMfmaD || G == 8);
+    constexpr bool kFused = kMfmaD && (!kNoFused || G == 8);
+    static_assert(G != 8 || kFused, "the eight-group lane map exists in the fused form only");
     // The 16-neuron shapes with eleven sweep wavefronts (the headline layer, the cluster form's slices): the first operands of a slot
     // in one round trip -- see the slot loop.  Not the eight-wavefront 16-neuron shapes (four and five pairs per lane: no register to
     // spare, hipcc spills more of the sweep's loop with it) and not the narrow shapes (their slot is the decision wavefront's chain,
     // whose first reads of a slot queue behind the sweeps' burst: 4-5 % slower with it, profiles/slot_top/README.md).
-    constexpr bool kBatchTop = kFused && NL == 4 && NSW == 11;
+    constexpr bool kBatchTop = kFused && (NL == 4 || G == 8) && NSW == 11;
     // ... and with a symmetric alphabet the first two pair-steps of a slot inside the same asm region (slot_top_sym)
     constexpr bool kTopSym = kBatchTop && SYM;
     // ... and the two LDS-DMA pieces a slot owes besides its record pieces -- the header piece of tile b + 2, the weight piece of block
@@ -736,9 +751,11 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
     // per tile, the last at pair-step 5).  In the 32-pair split a tile is 66 pieces, six per wavefront, and the two-pair wavefront --
     // wavefront 7, which owns neither piece and issues both with no lane enabled -- sends its sixth record piece at pair-step 6 as
     // well.  Never more than two pieces back to back either way.
-    constexpr bool kLateHdr = kTopSym && PW >= 2 && (kTop3 & 1) != 0, kLateW = kTopSym && PW >= 2 && (kTop3 & 2) != 0;
-    constexpr int kHdrStep = PW >= 3 ? 8 : 6, kWStep = PW >= 3 ? 10 : 7;
-    static_assert(!(kLateHdr || kLateW) || (PW <= 3 && B == 4 && PTS == 2 && PER_MIN <= 6), "the free pair-steps of a two- or three-pair wavefront");
+    // (eight neuron groups: a pair-step is a UNIT of two pairs in one step, so a six-pair wavefront has the pair-steps of a three-pair one)
+    constexpr int NUW = PW / PU;
+    constexpr bool kLateHdr = kTopSym && NUW >= 2 && (kTop3 & 1) != 0, kLateW = kTopSym && NUW >= 2 && (kTop3 & 2) != 0;
+    constexpr int kHdrStep = NUW >= 3 ? 8 : 6, kWStep = NUW >= 3 ? 10 : 7;
+    static_assert(!(kLateHdr || kLateW) || (NUW <= 3 && B == 4 && PTS == 2 && PER_MIN <= 6), "the free pair-steps of a two- or three-pair wavefront");
     // (kLateW) The weight piece's source, stepped by B ldt per slot instead of rebuilt from (jn, t) with 64-bit multiplies: lane =
     // (neuron, step) of the block, one piece per block, wavefront 0's.  Both layouts: neuron-major (ldt = 1) and the Keras kernel (ldw = 1).
     static_assert(!kLateW || NB * B == 64, "one 256-byte weight piece per block");
@@ -810,7 +827,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                     for (int pp = 1; pp < PW; ++pp) { t0 = (p == pp) ? u[n][2 * pp] : t0; t1 = (p == pp) ? u[n][2 * pp + 1] : t1; }
                     for (int j = 0; j < S; ++j) {
                         const int rb = nb_ + j * RB;
-                        const float2 x2 = lds_ld<float2>(lds, rb + o_x + 8 * p * KQ), q2 = lds_ld<float2>(lds, rb + o_q + 8 * p * KQ);
+                        const float2 x2 = lds_ld<float2>(lds, rb + o_x + 8 * pair_off(p)), q2 = lds_ld<float2>(lds, rb + o_q + 8 * pair_off(p));
                         const float2 wq = lds_ld<float2>(lds, o_wq + cbq + (n * B + j) * 8);
                         if constexpr (SYM) {
                             t0 += (double)__fmaf_rn(wq.y, q2.x, __fmul_rn(wq.x, x2.x));
@@ -821,16 +838,16 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                         }
                     }
                     const int rb = nb_ + S * RB;
-                    const float2 x2 = lds_ld<float2>(lds, rb + o_x + 8 * p * KQ);
+                    const float2 x2 = lds_ld<float2>(lds, rb + o_x + 8 * pair_off(p));
                     float2 q2;
                     if constexpr (SYM) {                              // the record holds a32 * Xq_t: the row itself from memory (rare path)
-                        const int i0 = 2 * (pbase + p * KQ + kq);
+                        const int i0 = 2 * (pbase + pair_off(p) + PU * kq);
                         const float *xr = K.Xq + ((int64_t)b * B + S) * K.ldx + (CL ? (int64_t)cs.slice * MP : (int64_t)0);   // (cluster form: the slice's samples)
                         const int mrow = CL ? cs.m_sl : K.m;
                         q2.x = i0 < mrow ? xr[i0] : 0.f;
                         q2.y = i0 + 1 < mrow ? xr[i0 + 1] : 0.f;
                     } else {
-                        q2 = lds_ld<float2>(lds, rb + o_q + 8 * p * KQ);
+                        q2 = lds_ld<float2>(lds, rb + o_q + 8 * pair_off(p));
                     }
                     eu[n] = fma((double)q2.x, t0, eu[n]);
                     eu[n] = fma((double)q2.y, t1, eu[n]);
@@ -900,6 +917,41 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
 #pragma unroll
             for (int n = 0; n < NL; ++n) { u[n][2 * p] += c0[n]; u[n][2 * p + 1] += c1[n]; }
         };
+        // (eight neuron groups) a unit of two adjacent pairs, pairs 2 P and 2 P + 1 of the lane, in one step: the same stages over
+        // (pair, neuron) -- four independent products per stage, as update_pair has over four neurons
+        auto update_unit2 = [&](int P, const float4 &x4, const float4 &q4, const float (&wv)[NL], const float (&qv)[NL]) {
+            const pk2 xv[2] = {{x4.x, x4.y}, {x4.z, x4.w}}, qx[2] = {{q4.x, q4.y}, {q4.z, q4.w}};
+            pk2 pr[2][NL], rr[2][NL], dd[2][NL];
+            double c0[2][NL], c1[2][NL];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int n = 0; n < NL; ++n) pr[h][n] = pk2{wv[n], wv[n]} * xv[h];
+            if constexpr (SYM) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int n = 0; n < NL; ++n) dd[h][n] = __builtin_elementwise_fma(pk2{qv[n], qv[n]}, qx[h], pr[h][n]);
+            } else {
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int n = 0; n < NL; ++n) rr[h][n] = pk2{qv[n], qv[n]} * qx[h];
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int n = 0; n < NL; ++n) dd[h][n] = pr[h][n] - rr[h][n];
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int n = 0; n < NL; ++n) { c0[h][n] = (double)dd[h][n].x; c1[h][n] = (double)dd[h][n].y; }
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int n = 0; n < NL; ++n) { u[n][4 * P + 2 * h] += c0[h][n]; u[n][4 * P + 2 * h + 1] += c1[h][n]; }
+        };
+        (void)update_unit2;
         // ---- phase U: the B updates of block b-1, in order: u += f32(w x) - f32(q xq)  (:119) ----
         // Software-pipelined by hand: the operands of the NEXT pair (and the next step's four (w, q)) are requested before
         // the arithmetic of the current one (sched_barrier keeps hipcc from sinking the requests to their first use,
@@ -915,16 +967,33 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
             // (The slot's first requests stay BEHIND the wait for the slow path's control word: hoisted in front of it -- with the slow
             //  path inlined, round 4, or as an out-of-line call without a spill, round 5 -- the kernel is 10-20 % slower:
             //  DESIGN_HISTORY.md, "gpfq_blk.hip notes" 5; profiles/r05/blk_variants_ab.txt.)
-            const int rbm = tbase + ng * RB + o_d;
+            const int rbm = tbase + (G == 8 ? lane & 3 : ng) * RB + o_d;  // (the matrix instruction's column j: the row of step lane & 3 -- which is ng where G = 4)
             // Operand rows are requested PF pair-steps ahead of their use: one everywhere -- except in the seven-sweep-wavefront shapes (two
             // wavefronts per SIMD, 256 registers), where a pair-step's handful of instructions no longer covers an LDS round trip and the
             // sweep's own chain of them would become the slot: two (round 5).
             // (two and four pair-steps ahead in the eight-wavefront narrow shapes too: no change, 1.28-1.30 ms at 4096 x 512 on 1024 samples
             //  either way -- profiles/r05/cluster_form.txt)
-            constexpr int PF = NSW == 7 ? 2 : 1, NPS = PW * B;
-            float2 fwq[B][NL], xbuf[PF], qbuf[PF];
-            double2 dcur;
-            auto row_off = [&](int i, bool q) { return tbase + (i % B) * RB + (q ? o_q : o_x) + 8 * (i / B) * KQ; };   // pair-step i = pair * B + step
+            // (NU units of PU pairs per wavefront; a pair-step is one unit in one step.  Where PU = 1 a unit is a pair and all of this is
+            //  what it was.)
+            // The second lane map (G = 8, NL = 2, lane = ng + 8 kq): in the matrix instruction's maps -- A: i + 4 b + 16 k,
+            // B: j + 4 b + 16 k, D: j + 4 b + 16 i, see the kMfmaD branch of phase D below -- lane bits 0-1 are ng & 3 = i, bit 2 is ng >> 2
+            // and bit 3 is kq & 1 (together the block b), bits 4-5 are kq >> 1 = k.  A = u[n][e] as it stands, B = the float64 row of
+            // step lane & 3 at the lane's own sample, D = step j of neuron group i + 4 (b & 1), partial over kq & 1 = b >> 1: ONE row
+            // rotation by eight per accumulator is left of the k-lane fold, where the first map -- its block index is kq & 3 -- leaves two.
+            constexpr int NU = PW / PU;
+            constexpr int PF = NSW == 7 ? 2 : 1, NPS = NU * B;
+            using XRow = std::conditional_t<PU == 2, float4, float2>;     // a unit's samples of an operand row
+            struct DRow2 { double2 v[2]; };
+            using DRow = std::conditional_t<PU == 2, DRow2, double2>;     // ... and of a float64 row
+            auto dhalf = [](const DRow &r, int h) -> const double2 & { if constexpr (PU == 2) return r.v[h]; else return r; };
+            float2 fwq[B][NL];
+            XRow xbuf[PF], qbuf[PF];
+            DRow dcur;
+            auto row_off = [&](int i, bool q) { return tbase + (i % B) * RB + (q ? o_q : o_x) + 8 * PU * (i / B) * KQ; };   // pair-step i = unit * B + step
+            auto ld_drow = [&](int off) -> DRow {
+                if constexpr (PU == 2) return DRow{{lds_ld<double2>(lds, off), lds_ld<double2>(lds, off + 16)}};
+                else return lds_ld<double2>(lds, off);
+            };
             auto first_requests = [&]() {
 #pragma unroll
                 for (int s = 0; s < B; ++s)
@@ -932,10 +1001,28 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                     for (int n = 0; n < NL; ++n) fwq[s][n] = lds_ld<float2>(lds, o_wq + pbq + (n * B + s) * 8);
 #pragma unroll
                 for (int i = 0; i < PF; ++i)
-                    if (i < NPS) { xbuf[i] = lds_ld<float2>(lds, row_off(i, false)); qbuf[i] = lds_ld<float2>(lds, row_off(i, true)); }
-                dcur = lds_ld<double2>(lds, rbm);
+                    if (i < NPS) { xbuf[i] = lds_ld<XRow>(lds, row_off(i, false)); qbuf[i] = lds_ld<XRow>(lds, row_off(i, true)); }
+                dcur = ld_drow(rbm);
             };
-            if constexpr (kTopSym) {
+            if constexpr (kTopSym && G == 8) {
+                // (eight neuron groups) the same region in its two-neuron form, slot_top_sym2: twelve requests, pair-steps 0 and 1 of the
+                // lane's first unit -- four samples of two neurons each -- under counted waits; see below for what it is there for
+                static_assert(!(kTopSym && G == 8) || (B == 4 && NL == 2 && PU == 2 && PF == 1), "slot_top_sym2: two neurons per lane, pair-steps 0..2 are unit 0's steps 0..2");
+                nf4 w01[2], w23[2], x2n, q2n;
+                nd2 d01[2];
+                __builtin_amdgcn_s_setprio(2);
+                slot_top_sym2<RB>(w01, w23, x2n, q2n, d01, u[0][0], u[0][1], u[0][2], u[0][3], u[1][0], u[1][1], u[1][2], u[1][3],
+                                  lds + row_off(0, false), lds + row_off(0, true), lds + o_wq + pbq, lds + rbm);
+                __builtin_amdgcn_s_waitcnt(0xC07F);            // (lgkmcnt(0) alone, for hipcc's waitcnt pass: see below)
+                __builtin_memcpy(&xbuf[0], &x2n, sizeof(XRow)); __builtin_memcpy(&qbuf[0], &q2n, sizeof(XRow));   // the rows of pair-step 2
+#pragma unroll
+                for (int h = 0; h < PU; ++h) dcur.v[h] = make_double2(d01[h].x, d01[h].y);
+#pragma unroll
+                for (int n = 0; n < NL; ++n) {
+                    fwq[0][n] = make_float2(w01[n].x, w01[n].y); fwq[1][n] = make_float2(w01[n].z, w01[n].w);
+                    fwq[2][n] = make_float2(w23[n].x, w23[n].y); fwq[3][n] = make_float2(w23[n].z, w23[n].w);
+                }
+            } else if constexpr (kTopSym) {
                 // Symmetric alphabets: the slot's fifteen first requests AND the arithmetic of pair-steps 0 and 1 as one asm region
                 // (slot_top_sym) -- pair-step 0 starts when its own six answers are in, pair-step 1 when its rows are, while the later
                 // requests are still out; the region ends with a full wait, so every register the compiler sees has landed.  With the
@@ -981,38 +1068,42 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
             } else {
                 first_requests();
             }
-            double2 dprev = make_double2(0.0, 0.0);
+            DRow dprev;
+            if constexpr (PU == 2) dprev = DRow{{make_double2(0.0, 0.0), make_double2(0.0, 0.0)}};
+            else dprev = make_double2(0.0, 0.0);
             double acc[NL];
 #pragma unroll
             for (int n = 0; n < NL; ++n) acc[n] = 0.0;
-            auto mfma_pair = [&](int pp, int i, const double2 &dd) {      // matrix instruction i = 0 .. 2 NL - 1 of pair pp
+            constexpr int NM = 2 * PU * NL;                               // matrix instructions of a unit: one per (sample, neuron) of the lane
+            auto mfma_pair = [&](int pp, int i, const DRow &dd) {         // matrix instruction i = 0 .. NM - 1 of unit pp
                 const int n = i % NL, e = i / NL;
-                acc[n] = __builtin_amdgcn_mfma_f64_4x4x4f64(u[n][2 * pp + e], e ? dd.y : dd.x, acc[n], 0, 0, 0);
+                const double2 &dh = dhalf(dd, e / 2);
+                acc[n] = __builtin_amdgcn_mfma_f64_4x4x4f64(u[n][2 * PU * pp + e], (e & 1) ? dh.y : dh.x, acc[n], 0, 0, 0);
             };
 #pragma unroll
-            for (int p = 0; p < PW; ++p) {
+            for (int p = 0; p < NU; ++p) {
                 // issue priority falls with progress through the slot (the laggard of a SIMD is served first, see below)
                 {
                     // (priorities by wavefront AGE instead of progress measured slower: DESIGN_HISTORY.md, "gpfq_blk.hip notes" 6)
-                    const int pr = 2 - (3 * p) / PW;
-                    if (p == 0 || pr != 2 - (3 * (p - 1)) / PW) {
+                    const int pr = 2 - (3 * p) / NU;
+                    if (p == 0 || pr != 2 - (3 * (p - 1)) / NU) {
                         const int v = pr;
                         if (v >= 2) __builtin_amdgcn_s_setprio(2);
                         else if (v == 1) __builtin_amdgcn_s_setprio(1);
                         else __builtin_amdgcn_s_setprio(0);
                     }
                 }
-                if (p > 0) dcur = lds_ld<double2>(lds, rbm + DB * p * KQ);       // (consumed under the NEXT pair's updates, or at the end)
+                if (p > 0) dcur = ld_drow(rbm + DB * PU * p * KQ);               // (consumed under the NEXT pair's updates, or at the end)
 #pragma unroll
                 for (int st = 0; st < B; ++st) {
                     const int ips = p * B + st;                                  // this pair-step; its operands sit in buffer ips % PF
                     if (kTopSym && ips < 2) continue;                            // (done inside slot_top_sym)
-                    const float2 x2 = xbuf[ips % PF], q2 = qbuf[ips % PF];
+                    const XRow x2 = xbuf[ips % PF], q2 = qbuf[ips % PF];
                     const int pn = (ips + 1) / B, sn = (ips + 1) % B;            // (the GPFQ_BLK_X_LDS2 experiment re-reads the next one)
                     (void)pn; (void)sn;
                     if (ips + PF < NPS) {
-                        xbuf[ips % PF] = lds_ld<float2>(lds, row_off(ips + PF, false));
-                        qbuf[ips % PF] = lds_ld<float2>(lds, row_off(ips + PF, true));
+                        xbuf[ips % PF] = lds_ld<XRow>(lds, row_off(ips + PF, false));
+                        qbuf[ips % PF] = lds_ld<XRow>(lds, row_off(ips + PF, true));
                     }
                     // (kTopSym: the pieces of pair-steps 0 and 1 -- M0 and scalar address stepping cannot sit inside the region -- go out at
                     //  pair-steps 2 and 3, in front of those pair-steps' own: two back to back at the most, never a burst)
@@ -1061,11 +1152,12 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                     float wv[NL], qv[NL];
 #pragma unroll
                     for (int n = 0; n < NL; ++n) { wv[n] = fwq[st][n].x; qv[n] = fwq[st][n].y; }
-                    update_pair(p, x2, q2, wv, qv);
+                    if constexpr (PU == 2) update_unit2(p, x2, q2, wv, qv);
+                    else update_pair(p, x2, q2, wv, qv);
                     if (p > 0) {                                   // the previous pair's 2 NL matrix instructions, spread over this pair's B steps
 #pragma unroll
-                        for (int i = 0; i < 2 * NL; ++i)
-                            if (i * B / (2 * NL) == st) mfma_pair(p - 1, i, dprev);
+                        for (int i = 0; i < NM; ++i)
+                            if (i * B / NM == st) mfma_pair(p - 1, i, dprev);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -1074,11 +1166,18 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
             for (int k = PTS * B * PPP < PER_MIN ? PTS * B * PPP : PER_MIN; wave + NSW * k < NPIECES; ++k) issue_piece(bn, k);   // the rest
             STAMP(st2);
 #pragma unroll
-            for (int i = 0; i < 2 * NL; ++i) mfma_pair(PW - 1, i, dprev);
+            for (int i = 0; i < NM; ++i) mfma_pair(NU - 1, i, dprev);
+            // what is left of the sum over the k-lanes: the blocks' k-lane bits -- lane bits 2 and 3 where G = 4, lane bit 3 where G = 8
+            // (bit 2 is the upper bit of the neuron group there)
 #pragma unroll
-            for (int n = 0; n < NL; ++n) { acc[n] = ror_add<8>(acc[n]); acc[n] = ror_add<4>(acc[n]); }   // blocks: lane bits 2, 3
-            if (b + 1 < nslots && (lane & 12) == 0) {             // one lane per (step, neuron group)
-                const int od = L.off_d + ((((((b + 1) & 1) * NW + wave) * B) + (lane & 3)) * NB + NL * (lane >> 4)) * 8;
+            for (int n = 0; n < NL; ++n) {
+                acc[n] = ror_add<8>(acc[n]);
+                if constexpr (G == 4) acc[n] = ror_add<4>(acc[n]);
+            }
+            const bool dwriter = G == 8 ? (lane & 8) == 0 : (lane & 12) == 0;   // one lane per (step, neuron group)
+            const int dgroup = G == 8 ? (lane >> 4) + (lane & 4) : lane >> 4;   // D's row i (+ 4 x block bit 0)
+            if (b + 1 < nslots && dwriter) {
+                const int od = L.off_d + ((((((b + 1) & 1) * NW + wave) * B) + (lane & 3)) * NB + NL * dgroup) * 8;
                 if constexpr (NL == 4) {
                     lds_st<double2>(lds, od, make_double2(acc[0], acc[1]));
                     lds_st<double2>(lds, od + 16, make_double2(acc[2], acc[3]));
@@ -1294,6 +1393,28 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
 
     )
     // ---- epilogue: residual norms through the same partial-sum path, residual vectors straight to memory ----
+    if constexpr (G == 8) {
+        // The four-group map's sums, bit for bit: a wavefront holds the same samples under both maps, and this lane the pairs of that
+        // map's k-lanes 2 kq and 2 kq + 1 -- so a chain per (neuron, pair of the unit) over the units in order, the fold over lane bits
+        // 5, 4, 3 (that map's k-lane bits 3, 2, 1), and the two pairs of the unit (its k-lane bit 0) added last, across rows.
+        if (K.resid) {
+            double ss[4];
+#pragma unroll
+            for (int n = 0; n < NL; ++n)
+#pragma unroll
+                for (int h = 0; h < PU; ++h) {
+                    double q = 0.0;
+#pragma unroll
+                    for (int P = 0; P < PW / PU; ++P)
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) q = fma(u[n][2 * (PU * P + h) + e], u[n][2 * (PU * P + h) + e], q);
+                    ss[PU * n + h] = q;
+                }
+            double v = fold_klanes<G>(ss);                        // row 2 n + h: (neuron n, pair h)
+            v = fold16(v, v);                                     // rows 2 n, 2 n + 1: neuron n
+            if (writer) lds_st<double>(lds, o_dw, v);
+        }
+    } else
     if (K.resid) {
         double ss[NL];
 #pragma unroll
@@ -1316,7 +1437,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                 for (int p = 0; p < PW; ++p)
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
-                        const int i = 2 * (pbase + p * KQ + kq) + e;
+                        const int i = 2 * (pbase + pair_off(p) + PU * kq) + e;
                         if constexpr (CL) {
                             if (i < cs.m_sl) K.u_out[jn * K.u_ld + (int64_t)cs.slice * MP + i] = u[n][2 * p + e];
                         } else {
@@ -2288,6 +2409,18 @@ static BlkShape blk_shape(int64_t m, int64_t C, const Options &opt)
     return {0, 0, 0, 0, 0, 0};
 }
 
+// Neuron groups per sweep wavefront of the sixteen-neuron shape on 1024-sample rows or slices over eleven sweep wavefronts (the headline
+// layer, the cluster form's 1024-sample slices) under a symmetric alphabet: 4 (four neurons per lane) or 8 (two: half the fold of the
+// matrix instruction's partial sums, twice the operand reads -- blk_sweep_role, the kMfmaD note).  Option blk_groups forces one; left to
+// the shape it is kGroupsByShape: profiles/groups8/README.md has the measurement that decides it.
+constexpr int kGroupsByShape = 8;
+static int blk_groups(const BlkShape &sh, bool sym, const Options &opt)
+{
+    const bool applies = sym && sh.G == 4 && sh.S == 32 && sh.B == 4 && sh.NW == 11 && sh.NL == 4;
+    if (!applies) return 4;
+    return opt.blk_groups ? opt.blk_groups : kGroupsByShape;
+}
+
 // (blk_uniform, blk_sym_of, form_device_alphabet: gpfq_device.hpp -- shared with the median's last workgroup, which forms the alphabet itself)
 
 // A host alphabet's DevAlphabet, computed on the host (launch_blk), stored into the call's workspace.
@@ -2365,7 +2498,7 @@ static float blk_sym_a(const PipeArgs &a)
     return blk_sym_of(a.A.a, a.A.M);
 }
 
-constexpr bool blk_kout_shape(int G, int B, int NL, int CLM) { return G == 4 && B == 4 && NL == 4 && CLM == 0; }
+constexpr bool blk_kout_shape(int G, int B, int NL, int CLM) { return ((G == 4 && NL == 4) || (G == 8 && NL == 2)) && B == 4 && CLM == 0; }
 
 template <int G, int S, int B, int NSW, bool SYM, int NL, int CLM = 0, bool KOUT = false>
 static hipError_t launch_blk_sym(const PipeArgs &a, const BlkShape &sh, const DevAlphabet *alpha, hipStream_t stream)
@@ -2553,6 +2686,10 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
             const int nw = forced == 8 || forced == 11 ? forced : (sym ? 11 : 8);
             return nw == 8 ? GPFQ_BLK_CL(24, 8, 4, 1) : GPFQ_BLK_CL(24, 11, 4, 1);
         }
+        if (sh.NL == 4 && blk_groups(sh, sym != 0, a.opt) == 8) {
+            note_dense_kernel("gpfq_blk_kernel, cluster form (rows cut into 1024-sample slices: one workgroup of 11 sweep wavefronts + 1 decision wavefront per slice, partial dot products exchanged once per slot; eight neuron groups)");
+            return launch_blk_sym<8, 64, 4, 11, true, 2, 1>(a, sh, alpha, stream);
+        }
         if (sh.NL == 4) return GPFQ_BLK_CL(32, 11, 4, 1);
         return sh.NL == 1 ? GPFQ_BLK_CL(32, 8, 1, 1) : GPFQ_BLK_CL(32, 8, 2, 1);
 #undef GPFQ_BLK_CL
@@ -2622,6 +2759,10 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
     if (sh.G == 4 && sh.NW == 11) {
         if (sh.S == 16) return launch_blk_inst<4, 16, 4, 11>(a, sh, alpha, stream);
         if (sh.S == 24) return launch_blk_inst<4, 24, 4, 11>(a, sh, alpha, stream);
+        if (blk_groups(sh, sym_shape != 0, a.opt) == 8) {
+            note_dense_kernel("gpfq_blk_kernel (4 to 11 sweep wavefronts + 1 decision wavefront per workgroup, blocks of steps per slot; eight neuron groups)");
+            return launch_blk_sym<8, 64, 4, 11, true, 2>(a, sh, alpha, stream);
+        }
         return launch_blk_inst<4, 32, 4, 11>(a, sh, alpha, stream);
     }
     if (sh.G == 4) {

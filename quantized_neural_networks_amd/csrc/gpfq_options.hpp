@@ -1,6 +1,7 @@
 // The library's tuning / test options (gpfq_set_option, gpfq_get_option): ONE table.  Results never depend on them.
 // Everything else about an option is derived from its row: the member of gpfq::Options, the process-wide store, the snapshot, the
 // setter's rule.  include/gpfq.h documents the keys for callers, one line each, in the same order.
+// (blk_groups is documented here and in DESIGN.md 4.1 only: an A/B and test switch of one shape.)
 #pragma once
 
 namespace gpfq {
@@ -28,6 +29,7 @@ namespace gpfq {
     X(blk_quad_groups, 2, true, v < 0 ? 0 : (v > 2 ? 2 : v), "")   /* four neuron groups x 1 / 2 neurons per lane for layers of at most 2048 neurons on rows of 257..1024 samples; 2: every such layer, 1: 129..2048 neurons only, 0: off */ \
     X(blk_quad_waves, 0, v == 0 || v == 7 || v == 8, v, "0 (by shape), 7 or 8")      /* sweep wavefronts of the four-group narrow shapes on rows of at most 768 samples: 0 = by shape (seven for layers of at most 1024 neurons, else eight) */ \
     X(blk_sweep_waves, 0, v == 0 || v == 8 || v == 11, v, "0 (by shape), 8 or 11")   /* sweep wavefronts of the 16-neuron four-step shapes: 0 = by shape (eleven for rows of 769..1024 samples, eight below) */ \
+    X(blk_groups, 0, v == 0 || v == 4 || v == 8, v, "0 (by shape), 4 or 8")            /* neuron groups per sweep wavefront of the 16-neuron shape on 1024-sample rows and slices, eleven sweep wavefronts, symmetric alphabets: 0 = by shape, 4 = four neurons per lane, 8 = two */ \
     X(blk_prep_run, 1, true, v >= 4 && v <= 16 ? v : (v ? 1 : 0), "")   /* 1: the record pre-pass takes runs of 4 .. 16 records per workgroup for walks of 2048+ steps; 0: one record per workgroup; 4 .. 16: runs of that many at any length (A/B, tests) */ \
     X(blk_prep_norms, 1, true, v ? 1 : 0, "")                   /* 1: gpfq_quantize_dense_layer's row norms inside the record pre-pass where that is bit-identical; 0: always the row-norm kernel (A/B, tests) */ \
     /* ... its cluster form: rows cut into 1024-sample slices over several workgroups, up to 28672 samples */                                \

@@ -322,6 +322,62 @@ __device__ __forceinline__ void slot_top_sym(nf4 (&w01)[4], nf4 (&w23)[4], nf2 &
                    "v163", "v164", "v165", "v166", "v167");
 #undef GPFQ_TOP_PAIR_STEP
 }
+// slot_top_sym2: the same region for the eight-group lane map (two neurons per lane, a unit of two adjacent sample pairs -- four
+// consecutive samples -- per pair-step).  Twelve requests in the order of their use: pair-step 0's rows (16 bytes each), the two
+// neurons' (w, q) of steps 0 and 1 (aw + 32 n), pair-step 1's rows, the (w, q) of steps 2 and 3 (aw + 32 n + 16), the unit's 32 bytes of
+// the first float64 row, pair-step 2's rows.  The arithmetic of a pair-step is update_pair's, instruction for instruction, over (pair,
+// neuron) where slot_top_sym has it over four neurons: four products, four fused multiply-adds, eight conversions, eight additions,
+// stage by stage, no instruction behind the one whose result it takes.  Named registers: the (w, q) of steps 0 and 1 in v[22:29]
+// (outputs), rows, products and conversions in v[144:167] (clobbered).
+template <int RB>
+__device__ __forceinline__ void slot_top_sym2(nf4 (&w01)[2], nf4 (&w23)[2], nf4 &x2, nf4 &q2, nd2 (&d)[2],
+                                              double &u00, double &u01, double &u02, double &u03, double &u10, double &u11, double &u12, double &u13,
+                                              lchar *px, lchar *pq, lchar *pwq, lchar *pd)
+{
+    static_assert(2 * RB + 16 <= 65536, "the rows of pair-steps 1 and 2 are reached through the 16-bit offset field");
+    // (W0, W1: the two neurons' (w, q) of the step; XA, XB / QA, QB: the halves of the step's rows -- pairs a and b; v[160:167]: products of
+    //  neuron 0 and the conversions' second set of results)
+#define GPFQ_TOP2_PAIR_STEP(W0, W1, XA, XAL, XAH, XB, XBL, XBH, QA, QB)                                            \
+    "v_pk_fma_f32 v[160:161], " W0 ", " QA ", v[160:161] op_sel:[1,0,0]\n\t"                                       \
+    "v_pk_fma_f32 v[162:163], " W0 ", " QB ", v[162:163] op_sel:[1,0,0]\n\t"                                       \
+    "v_pk_fma_f32 " XA ", " W1 ", " QA ", " XA " op_sel:[1,0,0]\n\t"                                               \
+    "v_pk_fma_f32 " XB ", " W1 ", " QB ", " XB " op_sel:[1,0,0]\n\t"                                               \
+    "v_cvt_f64_f32 " QA ", v160\n\tv_cvt_f64_f32 v[160:161], v161\n\t"                                             \
+    "v_cvt_f64_f32 v[164:165], " XAL "\n\tv_cvt_f64_f32 " XA ", " XAH "\n\t"                                       \
+    "v_cvt_f64_f32 " QB ", v162\n\tv_cvt_f64_f32 v[162:163], v163\n\t"                                             \
+    "v_cvt_f64_f32 v[166:167], " XBL "\n\tv_cvt_f64_f32 " XB ", " XBH "\n\t"                                       \
+    "v_add_f64 %[u01], %[u01], v[160:161]\n\tv_add_f64 %[u10], %[u10], v[164:165]\n\t"                             \
+    "v_add_f64 %[u11], %[u11], " XA "\n\tv_add_f64 %[u02], %[u02], " QB "\n\t"                                     \
+    "v_add_f64 %[u03], %[u03], v[162:163]\n\tv_add_f64 %[u12], %[u12], v[166:167]\n\t"                             \
+    "v_add_f64 %[u00], %[u00], " QA "\n\tv_add_f64 %[u13], %[u13], " XB "\n\t"
+    asm volatile("ds_read_b128 v[144:147], %[ax]\n\tds_read_b128 v[148:151], %[aq]\n\t"
+                 "ds_read_b128 v[26:29], %[aw]\n\tds_read_b128 v[22:25], %[aw] offset:32\n\t"
+                 "ds_read_b128 v[152:155], %[ax] offset:%[r1]\n\tds_read_b128 v[156:159], %[aq] offset:%[r1]\n\t"
+                 "ds_read_b128 %[w2], %[aw] offset:16\n\tds_read_b128 %[w3], %[aw] offset:48\n\t"
+                 "ds_read_b128 %[d0], %[ad]\n\tds_read_b128 %[d1], %[ad] offset:16\n\t"
+                 "ds_read_b128 %[x2], %[ax] offset:%[r2]\n\tds_read_b128 %[q2], %[aq] offset:%[r2]\n\t"
+                 // pair-step 0: twelve requests out; its rows and neuron 0's (w, q) are the first three of them, neuron 1's the fourth
+                 "s_waitcnt lgkmcnt(9)\n\tv_pk_mul_f32 v[160:161], v[144:145], v[26:27] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[162:163], v[146:147], v[26:27] op_sel_hi:[1,0]\n\t"
+                 "s_waitcnt lgkmcnt(8)\n\tv_pk_mul_f32 v[144:145], v[144:145], v[22:23] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[146:147], v[146:147], v[22:23] op_sel_hi:[1,0]\n\t"
+                 GPFQ_TOP2_PAIR_STEP("v[26:27]", "v[22:23]", "v[144:145]", "v144", "v145", "v[146:147]", "v146", "v147", "v[148:149]", "v[150:151]")
+                 // pair-step 1: its rows are requests 5 and 6; the six behind them may still be out
+                 "s_waitcnt lgkmcnt(6)\n\tv_pk_mul_f32 v[160:161], v[152:153], v[28:29] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[162:163], v[154:155], v[28:29] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[152:153], v[152:153], v[24:25] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[154:155], v[154:155], v[24:25] op_sel_hi:[1,0]\n\t"
+                 GPFQ_TOP2_PAIR_STEP("v[28:29]", "v[24:25]", "v[152:153]", "v152", "v153", "v[154:155]", "v154", "v155", "v[156:157]", "v[158:159]")
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&{v[26:29]}"(w01[0]), "=&{v[22:25]}"(w01[1]), [w2] "=&v"(w23[0]), [w3] "=&v"(w23[1]), [d0] "=&v"(d[0]), [d1] "=&v"(d[1]),
+                   [x2] "=&v"(x2), [q2] "=&v"(q2),
+                   [u00] "+v"(u00), [u01] "+v"(u01), [u02] "+v"(u02), [u03] "+v"(u03), [u10] "+v"(u10), [u11] "+v"(u11), [u12] "+v"(u12), [u13] "+v"(u13)
+                 : [ax] "v"((unsigned)(uintptr_t)px), [aq] "v"((unsigned)(uintptr_t)pq), [aw] "v"((unsigned)(uintptr_t)pwq), [ad] "v"((unsigned)(uintptr_t)pd),
+                   [r1] "i"(RB), [r2] "i"(2 * RB)
+                 : "memory", "v144", "v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152", "v153", "v154", "v155", "v156", "v157", "v158",
+                   "v159", "v160", "v161", "v162", "v163", "v164", "v165", "v166", "v167");
+#undef GPFQ_TOP2_PAIR_STEP
+}
 __device__ __forceinline__ int lds_read_now(lchar *p)
 {
     int v;

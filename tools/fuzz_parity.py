@@ -69,7 +69,7 @@ while time.time() < t_end:
                         blk_pair_groups=int(rng.choice([1, 1, 0])), blk_single_groups=int(rng.choice([1, 1, 0])), blk_quad_groups=int(rng.choice([2, 2, 0, 1])), blk_quad_waves=int(rng.choice([0, 0, 7, 8])),
                         variant=int(rng.choice([0, 0, 32])),
                         blk_cluster=int(rng.choice([1, 1, 0, 1024, 2048])), blk_cluster_map=int(rng.choice([-1, 0, 1])), blk_cluster_nl=int(rng.choice([0, 0, 1, 2, 4])),
-                        blk_cluster768=int(rng.choice([-1, -1, 0, 8, 11])))   # cluster form (round 5): by shape, off, from 1025 / 2049 samples up; both workgroup maps
+                        blk_cluster768=int(rng.choice([-1, -1, 0, 8, 11])), blk_groups=int(rng.choice([0, 0, 4, 8])))   # cluster form (round 5): by shape, off, from 1025 / 2049 samples up; both workgroup maps
         elif path == 1:
             opts = dict(lanes_per_neuron=int(rng.choice([0, 1, 16, 32, 64])), waves_per_neuron=int(rng.choice([0, 0, 2, 4, 8, 16])),
                         onchip_mode=int(rng.integers(0, 2)))
@@ -84,7 +84,7 @@ while time.time() < t_end:
         # device, the Keras kernel read in place, the record pre-pass in runs of records / on a second stream), every shape -- the ones
         # without a block-pipelined kernel fall back to the host alphabet inside
         if M <= 64 and rng.random() < 0.6:
-            popts = dict(blk_prep_run=int(rng.choice([1, 1, 0, 4, 8])), blk_cluster=int(rng.choice([1, 1, 0, 1024])))
+            popts = dict(blk_prep_run=int(rng.choice([1, 1, 0, 4, 8])), blk_cluster=int(rng.choice([1, 1, 0, 1024])), blk_groups=int(rng.choice([0, 0, 4, 8])))
             with hip.options(**popts):
                 out = layer.quantize_dense_layer(torch.from_numpy(W).to(dev), torch.from_numpy(X).to(dev), torch.from_numpy(Xq).to(dev),
                                                  np.linspace(-1, 1, M), scalar, overlap=bool(rng.random() < 0.5), kernel_ready=[None, True][int(rng.random() < 0.5)])

@@ -65,6 +65,7 @@ def main():
     hip.set_option("blk_cluster_map", int(os.environ.get("BLK_CLUSTER_MAP", "-1")))
     hip.set_option("blk_cluster_nl", int(os.environ.get("BLK_CLUSTER_NL", "0")))    # cluster form: neurons per lane (0: by width)
     hip.set_option("blk_cluster", int(os.environ.get("BLK_CLUSTER", "1")))     # cluster form: 1 = rows beyond 5120 samples, 0 = off, >= 1024: rows beyond that
+    hip.set_option("blk_groups", int(os.environ.get("BLK_GROUPS", "0")))      # 16 neurons, eleven sweep wavefronts, 1024-sample rows, symmetric alphabet: 4 or 8 neuron groups (0: by shape)
     hip.set_option("blk_wide_groups", int(os.environ.get("BLK_WIDE", "1")))   # rows > 1024 samples, > 2048 neurons: 16 neurons per workgroup
     base = run(pipe=0)
     print(f"shape N={N} C={C} m={m} M={M}; row-group kernel fallbacks={hip.exact_fallbacks(base)}")

@@ -1,5 +1,5 @@
 """Run the cfg2 dense kernel a few times (for rocprofv3 --pmc passes).
-usage: pmc_probe.py M mode lanes_per_neuron variant tile_steps blk_sweep_waves      (env PMC_C / PMC_M: another width / row length)"""
+usage: pmc_probe.py M mode lanes_per_neuron variant tile_steps blk_sweep_waves      (env PMC_C / PMC_M: another width / row length; PMC_GROUPS: option blk_groups)"""
 import os
 import sys
 import numpy as np, torch
@@ -16,6 +16,7 @@ alphabet = rad * np.linspace(-1, 1, M)
 Xd, Xqd, Wt = torch.from_numpy(X).cuda(), torch.from_numpy(Xq).cuda(), torch.from_numpy(W.T.copy()).cuda()
 hip.set_option("onchip_mode", arg(2, 1)); hip.set_option("lanes_per_neuron", arg(3, 0))
 hip.set_option("variant", arg(4, 0)); hip.set_option("tile_steps", arg(5, 0)); hip.set_option("blk_sweep_waves", arg(6, 0))
+hip.set_option("blk_groups", int(os.environ.get("PMC_GROUPS", "0")))    # the headline shape's lane map: 0 by shape, 4 or 8 neuron groups
 nrm = hip.row_norms(Xqd)
 if os.environ.get("PMC_LAYER", "0") != "0":
     # round 6: the kernel as bench.py's step runs it -- device-resident alphabet, the Keras kernel read in place, Q and the indices
