@@ -77,6 +77,8 @@ def main():
     ap.add_argument("--csv", default=None, help="append the metrics rows here (reference schema and append semantics)")
     ap.add_argument("--save-dir", default=None, help="save every quantized model there (quantize_pretrained_cnn.py:97-100)")
     ap.add_argument("--test-samples", type=int, default=2000)
+    ap.add_argument("--refine-passes", type=int, default=0, metavar="K",
+                    help="up to K refinement sweeps over every Dense layer and every --conv-walk filter Conv2D layer after its walk (DESIGN.md section 12); 0: none")
     ap.add_argument("--export-packed", default=None, metavar="PATH",
                     help="also write the quantized network in the packed low-bit form (deploy.export_packed; with several settings the "
                          "file holds the last one's)")
@@ -96,7 +98,7 @@ def main():
         get_data = CIFAR10Sequence(X_train[0:params.q_train_size], y_train[0:params.q_train_size], batch_size=16)
         my_quant_net = QuantizedCNN(network=model, batch_size=params.q_train_size, get_data=get_data, logger=quiet,
                                     bits=params.bits, alphabet_scalar=params.alphabet_scalar, radius=args.radius,
-                                    conv_walk=args.conv_walk, conv_columns=args.conv_columns)
+                                    conv_walk=args.conv_walk, conv_columns=args.conv_columns, refine_passes=args.refine_passes)
         tic = time()
         my_quant_net.quantize_network()
         quantization_time = time() - tic

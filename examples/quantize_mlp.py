@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--csv", default=None, help="append one metrics row per setting there, the reference's schema and "
                                                 "append semantics (quantize_pretrained_mlp.py:119-153)")
     ap.add_argument("--widths", type=int, nargs="+", default=[500, 300], help="hidden layer widths")
+    ap.add_argument("--refine-passes", type=int, default=0, metavar="K",
+                    help="up to K refinement sweeps over every Dense layer after its walk (DESIGN.md section 12); 0: none")
     ap.add_argument("--export-packed", default=None, metavar="PATH",
                     help="also write the quantized network in the packed low-bit form (deploy.export_packed; with several settings the "
                          "file holds the last one's)")
@@ -75,7 +77,8 @@ def main():
         get_data = MNISTSequence(X_train, y_train, batch_size=args.samples)
         my_quant_net = QuantizedNeuralNetwork(network=model, batch_size=args.samples, get_data=get_data,
                                               logger=type("Quiet", (), {"info": staticmethod(lambda m: None)})(),
-                                              bits=params.bits, alphabet_scalar=params.alphabet_scalar, radius=args.radius)
+                                              bits=params.bits, alphabet_scalar=params.alphabet_scalar, radius=args.radius,
+                                              refine_passes=args.refine_passes)
         tic = time()
         my_quant_net.quantize_network()
         quantization_time = time() - tic

@@ -498,6 +498,44 @@ int gpfq_select_candidates(const void *qidx, int bits, int64_t N, int64_t C, int
                            double *radii_sel, double *resid_sel, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Refinement sweeps after the walk (refine_passes): coordinate descent on the walk's own objective, the
+ * layer's output error ||X w - Xq q|| on the calibration data, started from the walk's result and staying on its alphabet.  For
+ * output channel j the value of index k is a_k = radii[j] * unit_alphabet[k] (a float64 product, as gpfq_assemble_kernel_colrad
+ * forms it; a layer radius: the same number C times), the literal zero (index -1) has the value 0, and all arithmetic is float64:
+ *   start     u_i = sum_t (W[t][j] * X_t[i] - a_{k_t} * Xq_t[i]), t ascending, every product and sum rounded on its own: the true
+ *             residual of the installed q (not the walk's, whose increments are rounded to float32); n2_t = sum_i Xq_t[i]^2.
+ *   a sweep   for t = 0 .. N-1: nothing happens when nrm32[t] < 1e-16 (the walk's dead-row test) or k_t = -1; otherwise
+ *             p = <Xq_t, u>, v = a_{k_t} + p / n2_t, k' = the first index of min_k |a_k - v|, and only if |a_k' - v| < |a_{k_t} - v|
+ *             strictly: u -= (a_k' - a_{k_t}) * Xq_t, k_t = k'.
+ *   passes    up to `sweeps` sweeps; a neuron whose sweep changed nothing is converged and takes no further one.
+ * Outputs: qidx updated in place; Q[t][j] = (float)a_{k_t} (0.0f for -1) for every t; resid_before[j] / resid_after[j] = ||u|| at the
+ * start / the end; changed[j] = weights changed over all sweeps; sweeps_run[j] = sweeps run, the last, changeless one included
+ * (less than `sweeps`: converged).  p is a sum of lane partials, a wavefront reduction and the wavefronts in ascending order: results
+ * are bitwise repeatable from call to call and differ from a sequential float64 sum at the 1e-16 level.
+ * One workgroup owns gpfq_refine_neurons_per_workgroup(m) neurons (8; 2 beyond 4096 samples) and keeps their residuals in registers
+ * for the whole call; neurons exchange nothing.  Two launches (n2, then start + sweeps), no host synchronisation.
+ *   X, Xq [device] f32 [N][ld], ld >= m; nrm32 [device] f32 [N] (gpfq_row_norms); W [device] f32 [N][ldw], ldw >= C;
+ *   radii [device] f64 [C]; unit_alphabet [host] f64 [M], 1 <= M <= GPFQ_MAX_ALPHABET, in any order, finite;
+ *   qidx [device] [N][ldi], ldi >= C: i8 for M <= 64, i16 beyond; an index outside [0, M) is treated as -1;
+ *   Q [device] f32 [N][ldq], ldq >= C, or NULL; resid_before, resid_after [device] f64 [C], changed, sweeps_run [device] i32 [C]:
+ *   each may be NULL; workspace [device], 8-byte aligned, >= gpfq_refine_workspace_bytes(N).
+ * Pointers need their natural alignment only, every access is 4 bytes wide or less, and nothing beyond column m of X / Xq or
+ * column C of W / qidx / Q is read or written.  sweeps >= 1; m > GPFQ_REFINE_MAX_M: GPFQ_ERR_UNSUPPORTED.
+ */
+#define GPFQ_REFINE_MAX_M 8192     /* 1024 threads x 8 float64 residual elements per thread and neuron */
+size_t gpfq_refine_workspace_bytes(int64_t N);
+int gpfq_refine_neurons_per_workgroup(int64_t m);
+int gpfq_refine_neurons(const float *X, const float *Xq, int64_t ld, const float *nrm32,
+                        const float *W, int64_t ldw,              /* Keras layout [N][ldw], ldw >= C */
+                        const double *radii,                      /* [device] f64 [C] */
+                        const double *unit_alphabet, int M,       /* [host] */
+                        int64_t N, int64_t m, int64_t C, int sweeps,
+                        void *qidx, int64_t ldi,                  /* [device] Keras layout [N][ldi], updated IN PLACE */
+                        float *Q, int64_t ldq,                    /* [device] [N][ldq], may be NULL */
+                        double *resid_before, double *resid_after, int32_t *changed, int32_t *sweeps_run,  /* each may be NULL */
+                        void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * median(|W|) of n float32 weights with NumPy's semantics (float32 result; even n -> float32 mean of
  * the two middle values).  Replaces `median(abs(W.flatten()))` of the alphabet radius
  * (scripts/quantized_network.py:544, :831).  Exact radix select, no sort.

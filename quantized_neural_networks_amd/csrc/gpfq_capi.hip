@@ -918,6 +918,53 @@ int gpfq_select_candidates(const void *qidx, int bits, int64_t N, int64_t C, int
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_select_candidates");
 }
 
+// ---- refinement sweeps after the walk (gpfq_refine.hip) ----
+
+size_t gpfq_refine_workspace_bytes(int64_t N) { return gpfq::refine_workspace_bytes(N); }
+
+int gpfq_refine_neurons_per_workgroup(int64_t m) { return gpfq::refine_neurons_per_workgroup(m); }
+
+int gpfq_refine_neurons(const float *X, const float *Xq, int64_t ld, const float *nrm32, const float *W, int64_t ldw,
+                        const double *radii, const double *unit_alphabet, int M, int64_t N, int64_t m, int64_t C, int sweeps,
+                        void *qidx, int64_t ldi, float *Q, int64_t ldq, double *resid_before, double *resid_after, int32_t *changed,
+                        int32_t *sweeps_run, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const gpfq::Options o = gpfq::options_snapshot();     // (no option reaches the refinement kernel yet)
+    (void)o;
+    if (N < 0 || m < 0 || C < 0)
+        return fail(GPFQ_ERR_INVALID_ARG, "negative size N=%lld m=%lld C=%lld", (long long)N, (long long)m, (long long)C);
+    if (sweeps < 1) return fail(GPFQ_ERR_INVALID_ARG, "sweeps=%d must be >= 1", sweeps);
+    HostAlphabet H;
+    int rc = make_alphabet(unit_alphabet, M, -1, &H);
+    if (rc != GPFQ_OK) return rc;
+    if (m > GPFQ_REFINE_MAX_M)
+        return fail(GPFQ_ERR_UNSUPPORTED, "refinement needs m <= GPFQ_REFINE_MAX_M=%d (got %lld)", GPFQ_REFINE_MAX_M, (long long)m);
+    if (N > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "walks of more than 2^31 - 1 steps");
+    if (C == 0) return GPFQ_OK;
+    if (!radii) return fail(GPFQ_ERR_INVALID_ARG, "radii is NULL");
+    if (N > 0) {
+        if (!W || !nrm32 || !qidx) return fail(GPFQ_ERR_INVALID_ARG, "W/nrm32/qidx is NULL");
+        if (m > 0 && (!X || !Xq)) return fail(GPFQ_ERR_INVALID_ARG, "X/Xq is NULL");
+        if (ld < m) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ld=%lld < m=%lld", (long long)ld, (long long)m);
+        if (ldw < C) return fail(GPFQ_ERR_INVALID_ARG, "weight pitch ldw=%lld < C=%lld", (long long)ldw, (long long)C);
+        if (ldi < C) return fail(GPFQ_ERR_INVALID_ARG, "index pitch ldi=%lld < C=%lld", (long long)ldi, (long long)C);
+        if (Q && ldq < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldq=%lld < C=%lld", (long long)ldq, (long long)C);
+        if (H.is_big && (uintptr_t)qidx % 2 != 0) return fail(GPFQ_ERR_INVALID_ARG, "int16 indices must be 2-byte aligned");
+        const size_t need = gpfq::refine_workspace_bytes(N);
+        if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 8 != 0)
+            return fail(GPFQ_ERR_WORKSPACE, "refinement needs %zu aligned workspace bytes, got %zu", need, workspace ? workspace_bytes : (size_t)0);
+    }
+    gpfq::RefineArgs a{};
+    a.X = X; a.Xq = Xq; a.ld = ld; a.nrm32 = nrm32; a.W = W; a.ldw = ldw; a.radii = radii;
+    a.U.M = M;
+    for (int k = 0; k < M; ++k) a.U.a[k] = unit_alphabet[k];
+    a.N = N; a.m = m; a.C = C; a.sweeps = sweeps; a.qidx = qidx; a.ldi = ldi; a.Q = Q; a.ldq = ldq;
+    a.resid_before = resid_before; a.resid_after = resid_after; a.changed = changed; a.sweeps_run = sweeps_run;
+    a.workspace = workspace;
+    hipError_t e = gpfq::launch_refine(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_refine_neurons");
+}
+
 size_t gpfq_median_abs_workspace_bytes(void) { return gpfq::median_workspace_bytes() + 64; }
 size_t gpfq_median_abs_workspace_bytes_for(int64_t n) { return n > 0 ? gpfq::median_workspace_bytes_fast(n) : gpfq::median_workspace_bytes() + 64; }
 

@@ -297,6 +297,29 @@ hipError_t launch_select_candidates(const void *qidx, int bits, int64_t N, int64
                                     const double *radii, const AlphabetArg &A, const AlphabetBig *big, int per_layer, int32_t *best,
                                     double *scores, float *Q, void *qsel, double *radii_sel, double *resid_sel, double *totals,
                                     hipStream_t stream);
+// gpfq_refine.hip (refine_passes): coordinate-descent sweeps over the walk's result, in place
+constexpr int kRefineMaxM = 8192;                // 1024 threads x 8 residual elements (float64) per thread and neuron
+struct RefineArgs {
+    const float *X, *Xq;
+    int64_t ld;
+    const float *nrm32;
+    const float *W;                              // Keras layout [N][ldw]
+    int64_t ldw;
+    const double *radii;                         // [device] f64 [C]
+    AlphabetBig U;                               // the unit alphabet (any M <= 256; int16 indices beyond 64 members)
+    int64_t N, m, C;
+    int sweeps;
+    void *qidx;                                  // Keras layout [N][ldi], updated in place
+    int64_t ldi;
+    float *Q;                                    // [N][ldq] or NULL
+    int64_t ldq;
+    double *resid_before, *resid_after;          // [C] or NULL
+    int32_t *changed, *sweeps_run;               // [C] or NULL
+    void *workspace;                             // refine_workspace_bytes(N), 8-byte aligned
+};
+size_t refine_workspace_bytes(int64_t N);
+int refine_neurons_per_workgroup(int64_t m);
+hipError_t launch_refine(const RefineArgs &a, hipStream_t stream);
 size_t median_workspace_bytes();
 size_t median_workspace_bytes_fast(int64_t n);   // ... with room for the one-GPU form's candidate list (gpfq_median_abs_workspace_bytes_for)
 size_t channel_sumsq_workspace_bytes(int64_t Cin);

@@ -22,6 +22,8 @@ GPFQ_DEVICE_ALPHABET_BYTES = 1024
 GPFQ_LAYOUT_NEURON_MAJOR, GPFQ_LAYOUT_KERAS = 0, 1
 GPFQ_ERR_CLUSTER_TIMEOUT, GPFQ_ERR_ALPHABET = -6, -7
 GPFQ_SEARCH_MAX_CANDIDATES = 16    # candidate scalars of one search (include/gpfq.h)
+GPFQ_REFINE_MAX_M = 8192           # longest row the refinement sweeps take (include/gpfq.h)
+GPFQ_ERR_INVALID_ARG, GPFQ_ERR_UNSUPPORTED, GPFQ_ERR_WORKSPACE = -1, -2, -3
 
 # every symbol include/gpfq.h declares: (restype, argtypes)
 _i64, _int, _vp, _sz = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
@@ -65,6 +67,10 @@ SYMBOLS = {
     "gpfq_select_candidates_workspace_bytes": (_sz, [_int, _i64]),
     "gpfq_select_candidates": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _dp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                       _vp]),
+    "gpfq_refine_workspace_bytes": (_sz, [_i64]),
+    "gpfq_refine_neurons_per_workgroup": (_int, [_i64]),
+    "gpfq_refine_neurons": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _dp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64,
+                                   _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpfq_gram_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "gpfq_quantize_neurons_gram": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _i64, _dp, _int, _int, _i64, _i64, _i64,
                                           _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -898,6 +904,63 @@ def select_candidates(qidx, resid, radii, unit_alphabet, K, per_layer=False, wan
                                           out["resid"].data_ptr(), ws.data_ptr() if ws is not None else None, nbytes, _stream()),
                "gpfq_select_candidates")
     return out
+
+
+def refine_neurons_per_workgroup(m):
+    """Output channels one workgroup of the refinement kernel owns at rows of m samples (gpfq_refine_neurons_per_workgroup)."""
+    return int(load().gpfq_refine_neurons_per_workgroup(int(m)))
+
+
+def refine_neurons(X, Xq, W, idx, radii, unit_alphabet, sweeps, nrm32=None, want_values=True, inplace=False, out=None):
+    """Refinement sweeps over a walk's result (gpfq_refine_neurons).  X, Xq f32 [N][m] (rows of any pitch),
+    W f32 [N][C] the ORIGINAL kernel (Keras layout, rows of any pitch), idx [N][C] the walk's Keras-layout indices (int8; int16 beyond
+    64 members), radii f64 [C], unit_alphabet a host sequence: index k of channel j has the value radii[j] * unit_alphabet[k].
+    Returns dict(Q f32 [N][C] or None, idx, resid_before f64 [C], resid_after f64 [C], changed i32 [C], sweeps i32 [C]).  idx is a
+    refined copy, or, with inplace=True, the given tensor itself (rows of any pitch); out: a f32 [N][C] view (rows of any pitch) to
+    take Q.  Two launches, no sync."""
+    arr, M, _ = _alphabet(unit_alphabet)
+    _dev(X, torch.float32, "X"); _dev(Xq, torch.float32, "Xq"); _dev(W, torch.float32, "W")
+    _dev(idx, index_dtype(M), "idx"); _dev(radii, torch.float64, "radii")
+    px, N, m, ld = _rows(X, "X")
+    pq, Nq, mq, ldq_ = _rows(Xq, "Xq")
+    if (Nq, mq) != (N, m):
+        raise GpfqError(f"X {tuple(X.shape)} and Xq {tuple(Xq.shape)} differ in shape")
+    if ldq_ != ld:
+        raise GpfqError("X and Xq must share their row pitch")
+    pw, Nw, C, ldw = _rows(W, "W")
+    if Nw != N or tuple(idx.shape) != (N, C):
+        raise GpfqError(f"W {tuple(W.shape)} / idx {tuple(idx.shape)} do not match the {N} rows of X")
+    if radii.numel() != C or not radii.is_contiguous():
+        raise GpfqError(f"radii must be a contiguous [{C}] tensor")
+    sweeps = int(sweeps)
+    dev = X.device
+    if not inplace:
+        idx = idx.clone(memory_format=torch.contiguous_format)
+    pi, _, _, ldi = _rows(idx, "idx")
+    if nrm32 is None:
+        nrm32 = row_norms(Xq)
+    _dev(nrm32, torch.float32, "nrm32")
+    if nrm32.numel() != N or not nrm32.is_contiguous():
+        raise GpfqError(f"nrm32 must be a contiguous [{N}] tensor")
+    Q = out if out is not None else (torch.empty((N, C), dtype=torch.float32, device=dev) if want_values else None)
+    pQ, ldQ = (None, 0)
+    if Q is not None:
+        _dev(Q, torch.float32, "out")
+        pQ, Nq_, Cq_, ldQ = _rows(Q, "out")
+        if (Nq_, Cq_) != (N, C):
+            raise GpfqError(f"out must be [{N}][{C}]")
+    res = dict(Q=Q, idx=idx, resid_before=torch.empty(C, dtype=torch.float64, device=dev),
+               resid_after=torch.empty(C, dtype=torch.float64, device=dev), changed=torch.empty(C, dtype=torch.int32, device=dev),
+               sweeps=torch.empty(C, dtype=torch.int32, device=dev))
+    lib = load()
+    nbytes = lib.gpfq_refine_workspace_bytes(N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        _check(lib.gpfq_refine_neurons(px, pq, ld, nrm32.data_ptr(), pw, ldw, radii.data_ptr(), arr, M, N, m, C, sweeps, pi, ldi, pQ, ldQ,
+                                       res["resid_before"].data_ptr(), res["resid_after"].data_ptr(), res["changed"].data_ptr(),
+                                       res["sweeps"].data_ptr(), ws.data_ptr() if ws is not None else None, nbytes, _stream()),
+               "gpfq_refine_neurons")
+    return res
 
 
 def last_dense_kernel():

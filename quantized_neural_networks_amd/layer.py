@@ -240,8 +240,58 @@ def _beside_prepare(W, from_kernel, kernel_ready, X, Xq, unit_alphabet, rows):
     return made, ws
 
 
+def check_refine(refine, name="refine"):
+    """The number of refinement sweeps as an int >= 0 (ValueError otherwise; a bool is not a count)."""
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0:
+        raise ValueError(f"{name} must be an integer >= 0, got {refine!r}")
+    return int(refine)
+
+
+def refine_dense(W, X, Xq, idx, radii, unit_alphabet, sweeps):
+    """Refinement sweeps after the walk: coordinate descent on the walk's own objective ||X w - Xq q|| over
+    the members a_k = radii[j] * unit_alphabet[k] of every neuron's alphabet, started from the walk's indices.
+
+    W        f32 [N][C]  the ORIGINAL Keras kernel (not a rescaled W')
+    X, Xq    f32 [N][m]  the rows the walk ran on, m <= hip.GPFQ_REFINE_MAX_M
+    idx      [N][C]      the walk's Keras-layout indices (int8; int16 beyond 64 members); left as it is
+    radii    f64 [C]     on the device; a layer radius: the same number C times
+    sweeps   >= 1        at most this many sweeps; a neuron whose sweep changed nothing stops
+
+    Returns dict(Q f32 [N][C], idx, resid_before f64 [C], resid_after f64 [C], changed i32 [C], sweeps i32 [C]): the norms are those of
+    the true float64 residual of the installed kernel before / after.  Two launches, no sync."""
+    r = hip.refine_neurons(X, Xq, W.detach(), idx, radii, unit_alphabet, sweeps)
+    return dict(Q=r["Q"], idx=r["idx"], resid_before=r["resid_before"], resid_after=r["resid_after"], changed=r["changed"],
+                sweeps=r["sweeps"])
+
+
+def _refined(out, W, X, Xq, radii, unit, refine, group):
+    """A dense driver's result with `refine` sweeps applied against the original kernel W: Q and idx replaced, + "refine" =
+    dict(resid_before, resid_after, changed, sweeps).  "resid" stays the walk's."""
+    if not refine:
+        return out
+    if _group_info(group)[0] > 1:
+        raise NotImplementedError("refinement sweeps are not sharded over a process group yet")
+    if W.numel() == 0:
+        return out
+    if X.shape[1] > hip.GPFQ_REFINE_MAX_M:
+        raise NotImplementedError(f"refinement sweeps take rows of at most GPFQ_REFINE_MAX_M = {hip.GPFQ_REFINE_MAX_M} samples, got "
+                                  f"{X.shape[1]}")
+    r = refine_dense(W, X, Xq, out["idx"], radii, unit, refine)
+    out["Q"], out["idx"] = r.pop("Q"), r.pop("idx")
+    out["refine"] = r
+    return out
+
+
+def _alphabet_radii(alphabet, C, device):
+    """(radii f64 [C] on the device, unit alphabet) with radii[j] * unit[k] = member k of a layer alphabet: a DeviceAlphabet's radius is
+    broadcast on the device (no read-back); a host alphabet is its own unit alphabet under the radius 1."""
+    if isinstance(alphabet, hip.DeviceAlphabet):
+        return alphabet.buf[:8].view(torch.float64).expand(C).contiguous(), alphabet.unit
+    return torch.ones(C, dtype=torch.float64, device=device), np.asarray(alphabet, dtype=np.float64)
+
+
 def quantize_dense_layer(W, X, Xq, unit_alphabet, alphabet_scalar, group=None, want_resid=True, log=None, check=True, overlap=False,
-                         kernel_ready=None):
+                         kernel_ready=None, refine=0):
     """The body of _quantize_layer_parallel (scripts/quantized_network.py:523-574) from "the activations are there" to the tensors
     set_weights takes, with nothing crossing to the host: median of |W| -> rad * alphabet on the device (:544-545), row norms, record
     pre-pass, the recurrence reading the Keras kernel in place.
@@ -251,7 +301,9 @@ def quantize_dense_layer(W, X, Xq, unit_alphabet, alphabet_scalar, group=None, w
     k + 1 also fills the tail of layer k.  Measured at the north-star layer: 3.05 -> 3.00 ms per layer (profiles/r06/overlap_ab.txt).
     (Round 6's first scheme -- the pre-pass on the side stream behind a fork wait -- measured a wash and is gone.)
 
-    Same tensors as quantize_dense(W, X, Xq, rad * unit_alphabet), bit for bit.  Returns its dict + "alphabet" (the hip.DeviceAlphabet)."""
+    Same tensors as quantize_dense(W, X, Xq, rad * unit_alphabet), bit for bit.  Returns its dict + "alphabet" (the hip.DeviceAlphabet).
+    refine: as quantize_dense."""
+    refine = check_refine(refine)
     N, C = W.shape
     world, rank = _group_info(group)
     lo, hi = shard_bounds(C, world, rank)
@@ -262,12 +314,12 @@ def quantize_dense_layer(W, X, Xq, unit_alphabet, alphabet_scalar, group=None, w
                                         X, Xq, unit_alphabet, hi - lo)
     else:
         dalpha, ws = layer_alphabet_device(W, unit_alphabet, alphabet_scalar, group), None
-    out = quantize_dense(W, X, Xq, dalpha, group=group, want_resid=want_resid, log=log, check=check, prepared=ws)
+    out = quantize_dense(W, X, Xq, dalpha, group=group, want_resid=want_resid, log=log, check=check, prepared=ws, refine=refine)
     out["alphabet"] = dalpha
     return out
 
 
-def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, check=True, prepared=None):
+def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, check=True, prepared=None, refine=0):
     """Quantize every neuron (column) of a Dense kernel.
 
     W        f32 [N][C]  Keras kernel layout (row = input feature), on the GPU
@@ -282,7 +334,10 @@ def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, ch
     Deferred failures are logged and repaired before anything is returned or sent to another rank (_launch_repaired).
     check=False (device alphabets; benchmarks): the deferred status of the launch is NOT read here -- no host wait at all; the result
     carries "workspace" and the caller owes hip.call_status(result) before it trusts Q.
+    refine > 0: that many refinement sweeps (refine_dense) follow the walk, against W on the members of `alphabet`; Q and idx are the
+    refined ones, "refine" holds dict(resid_before, resid_after, changed, sweeps), "resid" stays the walk's.  0: today's path, untouched.
     """
+    refine = check_refine(refine)
     N, C = W.shape
     m = X.shape[1]
     world, rank = _group_info(group)
@@ -331,8 +386,12 @@ def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, ch
                     f"rerunning the layer with the host alphabet without the cluster form")
         return f"Dense layer {N} x {C}: the cluster form's exchange timed out; rerunning the layer through the classic kernels"
 
-    return _launch_repaired(launch, finish, alphabet, log, line, check=check, status_first=world > 1,
-                            block_kernel=lambda a: m > 0 and hip.dense_layer_supported(N, m, max(hi - lo, 1), a.unit))
+    out = _launch_repaired(launch, finish, alphabet, log, line, check=check, status_first=world > 1,
+                           block_kernel=lambda a: m > 0 and hip.dense_layer_supported(N, m, max(hi - lo, 1), a.unit))
+    if refine:
+        radii, unit = _alphabet_radii(alphabet, C, W.device)
+        out = _refined(out, Wc, X, Xq, radii, unit, refine, group)
+    return out
 
 
 # ------------------------------------------------------------------------------------------
@@ -562,7 +621,7 @@ def _channel_radii(W2d, alphabet_scalar, scale):
 
 
 def quantize_dense_channels(W, X, Xq, unit_alphabet, alphabet_scalar, group=None, overlap=False, kernel_ready=None, want_resid=True,
-                            log=None, check=True):
+                            log=None, check=True, refine=0):
     """quantize_dense with one radius per neuron (radius="channel"): r_j = alphabet_scalar * median(|W[:, j]|) (the layer radius
     where that is not a finite positive number, then 0), the walk run by quantize_dense -- every kernel, fallback and repair as there --
     on W' = float32(W / r_j) with the unit alphabet (a device alphabet of radius 1 up to 64 members), and
@@ -572,7 +631,9 @@ def quantize_dense_channels(W, X, Xq, unit_alphabet, alphabet_scalar, group=None
     all-gather still carries packed indices only.  overlap=True: the median and the radii / W' launch go to a side stream beside the row
     norms and the record pre-pass (_beside_prepare, which explains kernel_ready).
 
-    Returns quantize_dense's dict with Q, resid as above + "radii" (f64 [C]) and "layer_median" (f32 device scalar)."""
+    Returns quantize_dense's dict with Q, resid as above + "radii" (f64 [C]) and "layer_median" (f32 device scalar).
+    refine > 0: refinement sweeps (refine_dense) against the original W -- not W' -- on the members r_j * unit[k]; as quantize_dense."""
+    refine = check_refine(refine)
     N, C = W.shape
     world, rank = _group_info(group)
     lo, hi = shard_bounds(C, world, rank)
@@ -590,7 +651,7 @@ def quantize_dense_channels(W, X, Xq, unit_alphabet, alphabet_scalar, group=None
     if "resid" in out:
         out["resid"] = out["resid"] * r
     out["radii"], out["layer_median"] = r, med
-    return out
+    return _refined(out, Wc, X, Xq, r, unit, refine, group)
 
 
 def quantize_conv2d_channels(W, act_w, act_q, unit_alphabet, alphabet_scalar, strides, padding, rate, group=None, want_resid=True,
@@ -669,7 +730,7 @@ def _search_base(W2d, per_layer):
 
 
 def quantize_dense_search(W, X, Xq, unit_alphabet, alphabet_scalars, per="channel", group=None, overlap=False, kernel_ready=None,
-                          log=None, check=True):
+                          log=None, check=True, refine=0):
     """quantize_dense with the alphabet scalar SEARCHED over the candidates alphabet_scalars = (s_0 .. s_{K-1}), 1 <= K <= 16: base
     radius b_j = median(|W[:, j]|) (per="channel"; the layer median where that is not finite and positive, then 0) or median(|W|) for
     every j (per="layer"), r_{k,j} = s_k * b_j, and ONE quantize_dense call -- every kernel, fallback and repair as there -- walks the
@@ -687,9 +748,11 @@ def quantize_dense_search(W, X, Xq, unit_alphabet, alphabet_scalars, per="channe
     record pre-pass for the K * C columns (_beside_prepare, which explains kernel_ready).  check=False holds for a single group only.
 
     Returns dict(Q f32 [N][C], idx [N][C], resid f64 [C] = r * norm, radii f64 [C] -- all of the selected candidates --, best i32 [C],
-    scores f64 [K][C], layer_median f32 device scalar)."""
+    scores f64 [K][C], layer_median f32 device scalar).  refine > 0: refinement sweeps (refine_dense) run ONCE, after the selection,
+    against the original W on the selected radii; "resid" and "scores" stay the walk's."""
     scalars = check_scalars(alphabet_scalars)
     per_layer = _check_per(per)
+    refine = check_refine(refine)
     K = len(scalars)
     N, C = W.shape
     world, rank = _group_info(group)
@@ -728,7 +791,7 @@ def quantize_dense_search(W, X, Xq, unit_alphabet, alphabet_scalars, per="channe
                layer_median=base["med"])
     if len(parts) == 1 and "workspace" in parts[0][0]:
         res["workspace"] = parts[0][0]["workspace"]
-    return res
+    return _refined(res, Wc, X, Xq, res["radii"], unit, refine, group)
 
 
 def quantize_conv2d_search(W, act_w, act_q, unit_alphabet, alphabet_scalars, strides, padding, rate, per="channel", group=None):
@@ -790,7 +853,8 @@ def _as_filters(out, W, m, total):
     return out
 
 
-def quantize_conv2d_filters(W, act_w, act_q, alphabet, strides, padding, rate, columns=8192, seed=0, group=None, want_resid=True, log=None):
+def quantize_conv2d_filters(W, act_w, act_q, alphabet, strides, padding, rate, columns=8192, seed=0, group=None, want_resid=True, log=None,
+                            refine=0):
     """Quantize a Conv2D kernel filter by filter: filter f is neuron f of the Dense problem (W2, X, Xq) of _filter_rows -- a walk of
     kh*kw*Cin steps over the im2col rows of ALL input channels, where quantize_conv2d walks every (channel, filter) pair on its own.
 
@@ -801,23 +865,25 @@ def quantize_conv2d_filters(W, act_w, act_q, alphabet, strides, padding, rate, c
 
     The walk is quantize_dense's: its kernels, repairs and fallbacks, its sharding (filters over the ranks, one all-gather of packed
     indices).  Returns dict(Q f32 [kh][kw][Cin][F], idx same shape, resid f64 [F], columns=m, total=total) (+ quantize_dense's
-    "workspace" for a device alphabet)."""
+    "workspace" for a device alphabet).  refine > 0: quantize_dense's refinement sweeps on the gathered columns the walk used
+    (columns <= hip.GPFQ_REFINE_MAX_M)."""
     W2, X, Xq, m, total = _filter_rows(W, act_w, act_q, strides, padding, rate, columns, seed)
-    return _as_filters(quantize_dense(W2, X, Xq, alphabet, group=group, want_resid=want_resid, log=log), W, m, total)
+    return _as_filters(quantize_dense(W2, X, Xq, alphabet, group=group, want_resid=want_resid, log=log, refine=refine), W, m, total)
 
 
 def quantize_conv2d_filters_channels(W, act_w, act_q, unit_alphabet, alphabet_scalar, strides, padding, rate, columns=8192, seed=0,
-                                     group=None, want_resid=True, log=None):
+                                     group=None, want_resid=True, log=None, refine=0):
     """quantize_conv2d_filters with one radius per filter (radius="channel"): quantize_dense_channels on the rows of _filter_rows (the
     columns of W2 are the filters).  Returns its dict with Q, idx in the kernel's shape + columns, total."""
     W2, X, Xq, m, total = _filter_rows(W, act_w, act_q, strides, padding, rate, columns, seed)
-    return _as_filters(quantize_dense_channels(W2, X, Xq, unit_alphabet, alphabet_scalar, group=group, want_resid=want_resid, log=log),
-                       W, m, total)
+    return _as_filters(quantize_dense_channels(W2, X, Xq, unit_alphabet, alphabet_scalar, group=group, want_resid=want_resid, log=log,
+                                               refine=refine), W, m, total)
 
 
 def quantize_conv2d_filters_search(W, act_w, act_q, unit_alphabet, alphabet_scalars, strides, padding, rate, per="channel", columns=8192,
-                                   seed=0, group=None, log=None):
+                                   seed=0, group=None, log=None, refine=0):
     """quantize_conv2d_filters with the alphabet scalar searched per filter (per="channel") or for the layer (per="layer"):
     quantize_dense_search on the rows of _filter_rows.  Returns its dict with Q, idx in the kernel's shape + columns, total."""
     W2, X, Xq, m, total = _filter_rows(W, act_w, act_q, strides, padding, rate, columns, seed)
-    return _as_filters(quantize_dense_search(W2, X, Xq, unit_alphabet, alphabet_scalars, per=per, group=group, log=log), W, m, total)
+    return _as_filters(quantize_dense_search(W2, X, Xq, unit_alphabet, alphabet_scalars, per=per, group=group, log=log, refine=refine),
+                       W, m, total)

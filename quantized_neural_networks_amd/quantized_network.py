@@ -149,6 +149,19 @@ def _check_conv_walk(conv_walk, conv_columns, conv_columns_seed):
     return conv_walk, conv_columns, int(conv_columns_seed)
 
 
+def _check_refine_passes(refine_passes, process_group):
+    """refine_passes validated: an integer >= 0 (ValueError); with a process group of more than one rank only 0 (NotImplementedError)."""
+    n = _layer.check_refine(refine_passes, "refine_passes")
+    if n and process_group is not None and _layer._group_info(process_group)[0] > 1:
+        raise NotImplementedError("refine_passes > 0 with a process group of more than one rank: the refinement sweeps are not sharded yet")
+    return n
+
+
+def _refine_stats(out):
+    """{"refine": lazy dict(resid_before, resid_after, changed, sweeps)} of a refined layer, {} otherwise."""
+    return {"refine": _LazyStats(**out["refine"])} if "refine" in out else {}
+
+
 def _scalar_candidates(alphabet_scalar):
     """None for a plain number (the reference's alphabet_scalar, used as it is), else the validated candidates of a search
     (layer.check_scalars: 1..16 finite positive numbers, ValueError otherwise)."""
@@ -221,10 +234,12 @@ class QuantizedNeuralNetwork:
     """Wrapper around a Keras-style model that quantizes its Dense layers (reference :331-590)."""
 
     def __init__(self, network, batch_size, get_data, mini_batch_size=32, logger=None, ignore_layers=[],
-                 bits=np.log2(3), alphabet_scalar=1, *, device=None, process_group=None, fix_partial_batch=False, radius="layer"):
+                 bits=np.log2(3), alphabet_scalar=1, *, device=None, process_group=None, fix_partial_batch=False, radius="layer",
+                 refine_passes=0):
         # batch_size and mini_batch_size are accepted and ignored, as in the reference (:371-400):
         # the sample count comes from get_data alone.
         self.radius = _check_radius(radius)
+        self.refine_passes = _check_refine_passes(refine_passes, process_group)
         self.alphabet_scalars = _scalar_candidates(alphabet_scalar)      # a sequence: search the scalar (DESIGN.md section 9)
         self.get_data = get_data
         self.trained_net = network
@@ -252,6 +267,18 @@ class QuantizedNeuralNetwork:
         self.process_group = process_group
         self.fix_partial_batch = fix_partial_batch
         self.last_layer_stats = {}          # layer_idx -> dict(rad, alphabet, resid) for inspection/tests
+
+    refine_passes = 0
+
+    def _refine_kw(self, layer_idx, m=None):
+        """The drivers' refine argument: nothing at all for refine_passes = 0 (today's calls, unchanged)."""
+        if not self.refine_passes:
+            return {}
+        if m is not None and m > hip.GPFQ_REFINE_MAX_M:
+            layer = self.trained_net.layers[layer_idx]
+            raise NotImplementedError(f"layer {layer_idx} ({getattr(layer, 'name', layer.__class__.__name__)}): refine_passes takes rows "
+                                      f"of at most GPFQ_REFINE_MAX_M = {hip.GPFQ_REFINE_MAX_M} samples, this layer has {m}")
+        return {"refine": self.refine_passes}
 
     def _log(self, msg):
         if self.logger:
@@ -694,6 +721,7 @@ class QuantizedNeuralNetwork:
         wX, qX = self._get_layer_data_generator(layer_idx, transpose=True)
         self._log(f"\tdone. {time()-tic:2f} seconds.")
 
+        refine_kw = self._refine_kw(layer_idx, wX.shape[1])
         if self.alphabet_scalars is not None or self.radius == "channel":
             self._quantize_layer_channels(layer_idx, Wd, wX, qX)
             return
@@ -707,7 +735,7 @@ class QuantizedNeuralNetwork:
             # (a deferred failure of the kernel -- the cluster form's exchange timing out -- is noticed, logged and repaired INSIDE this
             #  call, before Q exists: nothing unchecked reaches set_weights, as nothing does in the reference, :563-565)
             out = _layer.quantize_dense(Wd, wX, qX, layer_alphabet if dalpha is None else dalpha, group=self.process_group, want_resid=None,
-                                        log=lambda msg: self._log(f"\t\tLayer {layer_idx}: {msg}"))
+                                        log=lambda msg: self._log(f"\t\tLayer {layer_idx}: {msg}"), **refine_kw)
             Q = out["Q"]
         except Exception as exc:
             self._log(f"\t\tLayer {layer_idx} generated an exception: {exc}")
@@ -715,7 +743,8 @@ class QuantizedNeuralNetwork:
         self._log_units("\t\tNeuron {} of " + f"{N_ell_plus_1} quantized successfully.", N_ell_plus_1)
         self._update_weights(layer_idx, Q)
         self._log(f"\tdone. {time()-tic:.2f} seconds.")
-        self.last_layer_stats[layer_idx] = _LazyStats(rad=rad, alphabet=layer_alphabet, resid=out["resid"], idx=out["idx"])
+        self.last_layer_stats[layer_idx] = _LazyStats(rad=rad, alphabet=layer_alphabet, resid=out["resid"], idx=out["idx"],
+                                                      **_refine_stats(out))
 
     def _quantize_layer_channels(self, layer_idx, Wd, wX, qX):
         """radius="channel": the radii, the scaled kernel and the walk all queued on the device (layer.quantize_dense_channels); no
@@ -727,20 +756,21 @@ class QuantizedNeuralNetwork:
         tic = time()
         try:
             log = lambda msg: self._log(f"\t\tLayer {layer_idx}: {msg}")
+            refine_kw = self._refine_kw(layer_idx, wX.shape[1])
             if search:
                 out = _layer.quantize_dense_search(Wd, wX, qX, self.alphabet, self.alphabet_scalars, per=self.radius,
-                                                   group=self.process_group, log=log)
+                                                   group=self.process_group, log=log, **refine_kw)
             else:
                 out = _layer.quantize_dense_channels(Wd, wX, qX, self.alphabet, self.alphabet_scalar, group=self.process_group,
-                                                     want_resid=None, log=log)
+                                                     want_resid=None, log=log, **refine_kw)
         except Exception as exc:
             self._log(f"\t\tLayer {layer_idx} generated an exception: {exc}")
             raise exc
         self._log_units("\t\tNeuron {} of " + f"{N_ell_plus_1} quantized successfully.", N_ell_plus_1)
         self._update_weights(layer_idx, out["Q"])
         self._log(f"\tdone. {time()-tic:.2f} seconds.")
-        self.last_layer_stats[layer_idx] = (_search_stats(out, self.alphabet) if search
-                                            else _channel_stats(out, self.alphabet, self.alphabet_scalar))
+        self.last_layer_stats[layer_idx] = (_search_stats(out, self.alphabet, **_refine_stats(out)) if search
+                                            else _channel_stats(out, self.alphabet, self.alphabet_scalar, **_refine_stats(out)))
 
     # The reference logs one record per neuron / filter as its futures complete (:567, :716).  Here all of a layer's units complete
     # together; the records still go out ONE PER UNIT (handlers and formatters that count or prefix records see what they saw), unless
@@ -779,8 +809,9 @@ class QuantizedCNN(QuantizedNeuralNetwork):
     def __init__(self, network, batch_size, get_data, mini_batch_size=32, logger=None, bits=np.log2(3),
                  alphabet_scalar=1, patch_mini_batch_size=5000, is_quantize_conv2d=True, *,
                  device=None, process_group=None, fix_partial_batch=False, radius="layer", conv_walk="channel", conv_columns=8192,
-                 conv_columns_seed=0):
+                 conv_columns_seed=0, refine_passes=0):
         self.radius = _check_radius(radius)
+        self.refine_passes = _check_refine_passes(refine_passes, process_group)
         self.alphabet_scalars = _scalar_candidates(alphabet_scalar)
         self.conv_walk, self.conv_columns, self.conv_columns_seed = _check_conv_walk(conv_walk, conv_columns, conv_columns_seed)
         self.get_data = get_data
@@ -825,6 +856,9 @@ class QuantizedCNN(QuantizedNeuralNetwork):
             # (a DepthwiseConv2D output channel depends on one input channel: its whole-filter walk IS the per-channel one below)
             self._quantize_conv2D_layer_filters(layer_idx, layer, Wd, wX, qX, rate)
             return
+        if self.refine_passes:
+            self._log(f"\t\tLayer {layer_idx} ({layer.__class__.__name__}): refine_passes does not take the walks per (input channel, "
+                      f"filter) pair; the layer stays as the walk made it")
         channels = self.radius == "channel" and not search
         if not channels and not search:
             alphabet, rad = self._layer_alphabet(Wd, layer_idx)                    # (:831-832)
@@ -866,7 +900,7 @@ class QuantizedCNN(QuantizedNeuralNetwork):
         channels = self.radius == "channel" and not search
         conv = dict(strides=tuple(layer.strides), padding=layer.padding.upper(), rate=tuple(rate) if rate else None,
                     columns=self.conv_columns, seed=self.conv_columns_seed, group=self.process_group,
-                    log=lambda msg: self._log(f"\t\tLayer {layer_idx}: {msg}"))
+                    log=lambda msg: self._log(f"\t\tLayer {layer_idx}: {msg}"), **self._refine_kw(layer_idx))
         if not channels and not search:
             alphabet, rad = self._layer_alphabet(Wd, layer_idx)                    # (:831-832)
             dalpha = self._layer_alphabet_device(layer_idx, rad)
@@ -879,13 +913,16 @@ class QuantizedCNN(QuantizedNeuralNetwork):
                 out = _layer.quantize_conv2d_filters_channels(Wd, wX, qX, self.alphabet, self.alphabet_scalar, want_resid=None, **conv)
             else:
                 out = _layer.quantize_conv2d_filters(Wd, wX, qX, alphabet if dalpha is None else dalpha, want_resid=None, **conv)
+        except NotImplementedError as exc:                  # (rows beyond the refinement kernel's: name the layer)
+            self._log(f"\t\t\tLayer {layer_idx} generated an exception: {exc}")
+            raise NotImplementedError(f"layer {layer_idx} ({getattr(layer, 'name', layer.__class__.__name__)}): {exc}")
         except Exception as exc:
             self._log(f"\t\t\tLayer {layer_idx} generated an exception: {exc}")
             raise exc
         self._log(f"\t\tGathered {out['columns']} of {out['total']} patch columns; quantized {F} filters of {kh * kw * Cin} weights each. "
                   f"{time()-tic:.2f} seconds.")
         self._update_weights(layer_idx, out["Q"])
-        extra = dict(conv_walk="filter", columns=out["columns"], total=out["total"])
+        extra = dict(conv_walk="filter", columns=out["columns"], total=out["total"], **_refine_stats(out))
         if search:
             self.last_layer_stats[layer_idx] = _search_stats(out, self.alphabet, **extra)
         elif channels:
