@@ -107,6 +107,12 @@ size_t gpfq_workspace_bytes(int64_t N, int64_t m, int64_t C, int path);
  * the first call); diagnostics for benchmarks and tests. */
 const char *gpfq_last_dense_kernel(void);
 
+/* Which instantiation of the block-pipelined kernel a gpfq_quantize_dense_layer call of this shape and unit alphabet would launch under
+ * the current options: 1 and out = {G, S, B, NSW, SYM, NL, CLM, KOUT-capable} (neuron groups per sweep wavefront, sample pairs per k-lane,
+ * steps per slot, sweep wavefronts, symmetric form, neurons per lane, cluster form, writes the Keras layout itself), or 0 where
+ * gpfq_dense_layer_supported says 0.  Host only: needs no device.  Diagnostics for tests. */
+int gpfq_blk_instance(int64_t N, int64_t m, int64_t C, const double *alphabet, int M, int32_t out[8]);
+
 /* Measurement hook: two hipEvent_t of the caller (NULL, NULL to clear; per calling thread; created with timing enabled) that take the
  * start and the end of a dense layer's MAIN kernel -- the recurrence, without the pre-passes that share the call -- so that a
  * benchmark times exactly the kernel its roofline statement names (bench.py): hipEventElapsedTime(start, stop) afterwards.  The

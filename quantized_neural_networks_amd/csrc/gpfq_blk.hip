@@ -30,14 +30,8 @@
 // piece at a time from inside the sweep's update phase (scalar addressing): issued back to back at the top of the slot the
 // pieces filled the vector-memory queue and stalled every sweep ~1000 cycles per slot.
 //
-// Shapes (blk_shape): G neuron groups per sweep wavefront (4G neurons per workgroup), S sample pairs per k-lane over the
-// sweep wavefronts, B steps per slot, NSW sweep wavefronts -- <4,16|24|32,4> x 8 for rows of up to 512 / 768 / 1024 samples,
-// <2,24|32,2> x 8 up to 1536 / 2048 (8 neurons per workgroup), <4,48|64,2> x 11 for the same rows in layers of more than
-// 2048 neurons (16 neurons per workgroup: one round of workgroups instead of two, half the folds and decisions per weight:
-// 8.2 -> 6.5 ms at 4096 x 4096 x 2048), and <2,16,4> x 8 (8 neurons per workgroup: half the sweep per slot) for rows of
-// 769..1024 samples when the layer has at most 2048 neurons, <1,8,4> / <1,12|16,2> x 8 (4 neurons per workgroup) for rows of 769..2048
-// samples when it has at most 1024, and one step per slot -- <2,48|64,1> x 11, <1,24|32,1> x 8 -- for rows of 2049..4096 samples.
-// What bounds a slot: the sweeps (nine sample pairs on three of
+// Shapes: the instantiations the library ships are the rows of ONE table, kBlkInst below; blk_shape chooses among them by the rows'
+// length and the layer's width, blk_instance resolves a call to its row.  What bounds a slot: the sweeps (nine sample pairs on three of
 // the SIMDs) for <4,32,4> and the B = 2 shapes, the decision wavefront's chain everywhere else; it runs at raised priority
 // (s_setprio) because it shares its SIMD with two sweep wavefronts, and the sweeps lower theirs as they progress through the
 // slot.  Symmetric alphabets take the SYM instantiation (BlkK::sym_a).  profiles/r02/blk_phase_stamps.txt has the per-phase
@@ -49,6 +43,8 @@
 
 #include <cstdlib>
 #include <mutex>
+#include <optional>
+#include <utility>
 #include "gpfq_device.hpp"
 #include <hip/hip_ext.h>
 #include "gpfq_launch.hpp"
@@ -582,50 +578,92 @@ __device__ __forceinline__ void cl_exchange(const BlkK &K, ClState &cs, int lane
     cl_gather<KV, CLB>(K, cs, lane, v);
 }
 
-// Sample-pair split over the sweep wavefronts: PairSplit for eight of them (the decision wavefront, wavefront 8, shares
-// SIMD 0 with wavefronts 0 and 4); with eleven the twelve wavefronts of a workgroup are three per SIMD.
-template <int S, int NSW> struct BlkSplit { static constexpr const int *pw = PairSplit<S>::pw; };
-template <> struct BlkSplit<4, 4>   { static constexpr int pw_[4] = {1, 1, 1, 1}; static constexpr const int *pw = pw_; };   // rows of up to 512 samples, four sweep wavefronts
-// (eleven sweep wavefronts: wavefronts w, w + 4, w + 8 share SIMD w, the decision wavefront is the third of SIMD 3, whose sweep
-//  wavefronts 3 and 7 therefore hold five pairs where the other SIMDs hold nine)
-template <> struct BlkSplit<32, 11> { static constexpr int pw_[11] = {3, 3, 3, 3, 3, 3, 3, 2, 3, 3, 3}; static constexpr const int *pw = pw_; };
-template <> struct BlkSplit<24, 11> { static constexpr int pw_[11] = {2, 2, 2, 2, 2, 2, 2, 1, 3, 3, 3}; static constexpr const int *pw = pw_; };
-
-// (the eleven-wavefront 48- and 64-pair tables come from measured sweeps, tools/split_sweep.sh: DESIGN_HISTORY.md, "gpfq_blk.hip notes" 2)
-template <> struct BlkSplit<64, 11> { static constexpr int pw_[11] = {4, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6}; static constexpr const int *pw = pw_; };
-template <> struct BlkSplit<48, 11> { static constexpr int pw_[11] = {4, 5, 4, 4, 5, 4, 4, 5, 4, 4, 5}; static constexpr const int *pw = pw_; };
-template <> struct BlkSplit<16, 11> { static constexpr int pw_[11] = {2, 2, 1, 1, 2, 2, 1, 1, 1, 1, 2}; static constexpr const int *pw = pw_; };
-
-// The four-group narrow shapes on rows of 769..1024 samples (G = 4, one or two neurons per lane, eight sweep wavefronts): their slot is the
-// chain of decisions, and every pair on the two sweep wavefronts that share the decision wavefront's SIMD lengthens it: 2,5,5,4,2,5,5,4 is
-// the measured optimum (1.42 against 1.56-1.72 ms for the other splits at 4096 x 512; four sweep wavefronts, or the decision wavefront
-// alone on its SIMD, are slower: DESIGN_HISTORY.md, "gpfq_blk.hip notes" 3).
-struct BlkSplitQuad32 { static constexpr int pw[8] = {2, 5, 5, 4, 2, 5, 5, 4}; };
-// (four neurons per workgroup on rows of 1537..2048 samples, two steps per slot -- cfg3's predictions layer, 4096 x 1000 on 2048 samples:
-//  1,2,2,3,2,2,2,2 2.70-2.75 ms against PairSplit<16>'s 2.81-2.87; the other splits tried there were slower than either)
-struct BlkSplitFour16 { static constexpr int pw[8] = {1, 2, 2, 3, 2, 2, 2, 2}; };
+// ---- the shipped instantiations ----------------------------------------------------------------------------
+// ONE table: a row is a gpfq_blk_kernel<G, S, B, NSW, SYM, NL, CLM> the library ships -- G neuron groups per sweep wavefront, NL neurons
+// per lane (NL G per workgroup), S sample pairs per k-lane (rows or slices of up to 128 S / G samples), B steps per slot, NSW sweep
+// wavefronts, CLM = 1 the cluster form -- with its split of the S pairs over the sweep wavefronts.  Every row exists for SYM true and
+// false, except G = 8 (symmetric alphabets only); the Keras-layout variant is derived from the row (blk_kout_shape).  The kernel reads
+// its split here (blk_split), the host resolves a call to a row (blk_instance) and launches by row index (launch_blk): there is no other list.
+// The splits follow from which wavefronts share a SIMD (a workgroup's go to the SIMDs in cyclic order).  Eight sweep wavefronts: the
+// decision wavefront, wavefront 8, shares SIMD 0 with wavefronts 0 and 4, which hold fewer pairs (kP8 .. kP40: gpfq_roles.hpp's PairSplit).
+struct BlkPairs { int pw[11]; };
+constexpr BlkPairs kP8{{1, 1, 1, 1, 1, 1, 1, 1}}, kP12{{1, 2, 2, 1, 1, 2, 2, 1}}, kP16{{1, 2, 2, 2, 1, 3, 3, 2}},
+                   kP24{{1, 3, 3, 3, 2, 4, 4, 4}}, kP32{{2, 4, 4, 4, 3, 5, 5, 5}}, kP40{{5, 5, 5, 5, 5, 5, 5, 5}};
 // Round 5: the four-group narrow shapes on rows of at most 768 samples take SEVEN sweep wavefronts -- eight wavefronts per workgroup, two per
 // SIMD, 256 registers per wavefront; the decision wavefront, wavefront 7, shares SIMD 3 with sweep wavefront 3, which holds the fewest pairs.
 // 4096 x 1024 on 768 samples 1.39 -> 1.20-1.22 ms, on 512 samples 1.26 -> 1.19, cfg1's Dense(784 -> 128) 0.267 -> 0.239; rows of 769..1024
 // samples keep eight (their five-pair wavefronts at two per SIMD become the slot: 1.39 / 1.40-1.44 ms at 4096 x 512, 1.93 / 2.08 at 4096 x
 // 2048): profiles/r05/quad_seven_wavefronts_ab.txt.
-template <int S> struct BlkSplit7;
-template <> struct BlkSplit7<32> { static constexpr int pw[7] = {5, 5, 5, 2, 5, 5, 5}; };
-template <> struct BlkSplit7<24> { static constexpr int pw[7] = {4, 4, 4, 1, 4, 4, 3}; };
-template <> struct BlkSplit7<16> { static constexpr int pw[7] = {3, 3, 2, 1, 3, 2, 2}; };
-// Eight neuron groups (G = 8, two neurons per lane: the lane map of blk_sweep_role's kMfmaD note), rows of 769..1024 samples: a pair is 16
-// samples, 64 of them to a row, and a lane updates two adjacent ones per pair-step -- BlkSplit<32, 11>'s proportions, the four-pair
-// wavefront being wavefront 7, on the decision wavefront's SIMD.
-struct BlkSplitOct64 { static constexpr int pw[11] = {6, 6, 6, 6, 6, 6, 6, 4, 6, 6, 6}; };
+constexpr BlkPairs kP16x7{{3, 3, 2, 1, 3, 2, 2}}, kP24x7{{4, 4, 4, 1, 4, 4, 3}}, kP32x7{{5, 5, 5, 2, 5, 5, 5}};
+// The four-group narrow shapes on rows or slices of 769..1024 samples (eight sweep wavefronts): their slot is the chain of decisions, and
+// every pair on the two sweep wavefronts that share the decision wavefront's SIMD lengthens it: the measured optimum (1.42 against 1.56-1.72
+// ms for the other splits at 4096 x 512; four sweep wavefronts, or the decision wavefront alone on its SIMD, are slower: DESIGN_HISTORY.md,
+// "gpfq_blk.hip notes" 3).
+constexpr BlkPairs kP32quad{{2, 5, 5, 4, 2, 5, 5, 4}};
+// Eleven sweep wavefronts: wavefronts w, w + 4, w + 8 share SIMD w, the decision wavefront is the third of SIMD 3, whose sweep wavefronts 3
+// and 7 therefore hold five pairs where the other SIMDs hold nine.  (The 48- and 64-pair splits come from measured sweeps,
+// tools/split_sweep.sh: DESIGN_HISTORY.md, "gpfq_blk.hip notes" 2.)
+constexpr BlkPairs kP16x11{{2, 2, 1, 1, 2, 2, 1, 1, 1, 1, 2}}, kP24x11{{2, 2, 2, 2, 2, 2, 2, 1, 3, 3, 3}}, kP32x11{{3, 3, 3, 3, 3, 3, 3, 2, 3, 3, 3}},
+                   kP48x11{{4, 5, 4, 4, 5, 4, 4, 5, 4, 4, 5}}, kP64x11{{4, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6}};
+// Eight neuron groups (two neurons per lane: the lane map of blk_sweep_role's kMfmaD note), rows or slices of 769..1024 samples: a pair is
+// 16 samples, 64 of them to a row, and a lane updates two adjacent ones per pair-step -- kP32x11's proportions, the four-pair wavefront
+// being wavefront 7, on the decision wavefront's SIMD.
+constexpr BlkPairs kP64oct{{6, 6, 6, 6, 6, 6, 6, 4, 6, 6, 6}};
+struct BlkInst { int G, S, B, NSW, NL, CLM; BlkPairs split; };
+constexpr BlkInst kBlkInst[] = {
+    //  G   S  B NSW NL CLM
+    // four neuron groups, one or two neurons per lane: layers of at most 2048 neurons on rows of 257..1024 samples
+    {4, 16, 4,  7, 1, 0, kP16x7},   {4, 16, 4,  7, 2, 0, kP16x7},   {4, 24, 4,  7, 1, 0, kP24x7},   {4, 24, 4,  7, 2, 0, kP24x7},   {4, 32, 4,  7, 1, 0, kP32x7},   {4, 32, 4,  7, 2, 0, kP32x7},
+    // (eleven sweep wavefronts buy these shapes nothing: 4096 x 512 on 1024 samples 1.77 against 1.62 ms, 4096 x 2048 1.94 / 1.95 in round 4;
+    //  measured again on round 5's kernels, one neuron per lane: 1.326 against 1.285 -- profiles/r05/cluster_form.txt)
+    {4, 16, 4,  8, 1, 0, kP16},     {4, 16, 4,  8, 2, 0, kP16},     {4, 24, 4,  8, 1, 0, kP24},     {4, 24, 4,  8, 2, 0, kP24},     {4, 32, 4,  8, 1, 0, kP32quad}, {4, 32, 4,  8, 2, 0, kP32quad},
+    // one group, one or two neurons per workgroup: layers of at most 128 / 512 neurons, rows of up to 5120 samples (four sweep wavefronts up to 512)
+    {1,  4, 4,  4, 1, 0, {{1, 1, 1, 1}}}, {1,  4, 4,  4, 2, 0, {{1, 1, 1, 1}}},
+    {1,  8, 4,  8, 1, 0, kP8},      {1,  8, 4,  8, 2, 0, kP8},      {1, 12, 2,  8, 1, 0, kP12},     {1, 12, 2,  8, 2, 0, kP12},
+    {1, 16, 2,  8, 1, 0, kP16},     {1, 16, 2,  8, 2, 0, kP16},     {1, 24, 1,  8, 1, 0, kP24},     {1, 24, 1,  8, 2, 0, kP24},
+    {1, 32, 1,  8, 1, 0, kP32},     {1, 32, 1,  8, 2, 0, kP32},     {1, 40, 1,  8, 1, 0, kP40},     {1, 40, 1,  8, 2, 0, kP40},
+    // one step per slot: rows of 2049..5120 samples
+    {1, 40, 1,  8, 4, 0, kP40},     {2, 48, 1, 11, 4, 0, kP48x11},  {2, 64, 1, 11, 4, 0, kP64x11},  {1, 24, 1,  8, 4, 0, kP24},     {1, 32, 1,  8, 4, 0, kP32},
+    // sixteen neurons per workgroup, two steps per slot: rows of 1025..2048 samples in layers of more than 2048 neurons
+    {4, 48, 2, 11, 4, 0, kP48x11},  {4, 64, 2, 11, 4, 0, kP64x11},
+    // sixteen neurons per workgroup, four steps per slot: eleven sweep wavefronts (<4,32,4,11,4> is the headline layer's, <8,64,4,11,2> its
+    // eight-group form: blk_groups), then eight
+    {4, 16, 4, 11, 4, 0, kP16x11},  {4, 24, 4, 11, 4, 0, kP24x11},  {4, 32, 4, 11, 4, 0, kP32x11},  {8, 64, 4, 11, 2, 0, kP64oct},
+    {4, 16, 4,  8, 4, 0, kP16},     {4, 24, 4,  8, 4, 0, kP24},     {4, 32, 4,  8, 4, 0, kP32},
+    // four neurons per workgroup: layers of at most 1024 neurons on rows of 769..2048 samples.  (Two steps per slot on rows of 1537..2048
+    // samples -- cfg3's predictions layer, 4096 x 1000 on 2048 samples: 1,2,2,3,2,2,2,2 2.70-2.75 ms against kP16's 2.81-2.87; the other
+    // splits tried there were slower than either)
+    {1,  8, 4,  8, 4, 0, kP8},      {1, 12, 2,  8, 4, 0, kP12},     {1, 16, 2,  8, 4, 0, {{1, 2, 2, 3, 2, 2, 2, 2}}},
+    // eight neurons per workgroup: rows of 769..2048 samples
+    {2, 16, 4,  8, 4, 0, kP16},     {2, 24, 2,  8, 4, 0, kP24},     {2, 32, 2,  8, 4, 0, kP32},
+    // cluster form: four 768-sample slices over eight or eleven sweep wavefronts; 1024-sample slices of 16, 4 or 8 neurons per workgroup
+    {4, 24, 4,  8, 4, 1, kP24},     {4, 24, 4, 11, 4, 1, kP24x11},  {4, 32, 4, 11, 4, 1, kP32x11},  {8, 64, 4, 11, 2, 1, kP64oct},  {4, 32, 4,  8, 1, 1, kP32quad}, {4, 32, 4,  8, 2, 1, kP32quad},
+};
+constexpr int kBlkInsts = (int)(sizeof(kBlkInst) / sizeof(kBlkInst[0]));
+constexpr bool blk_sym_only(const BlkInst &r) { return r.G == 8; }
+
+// The row with this key, or -1.  B < 0: the first row of this (G, S, NSW, NL) -- what the kernel's split depends on -- or -1 where two
+// such rows disagree about it.
+constexpr int blk_inst_find(int G, int S, int B, int NSW, int NL, int CLM)
+{
+    int row = -1;
+    for (int i = 0; i < kBlkInsts && (B < 0 || row < 0); ++i) {
+        const BlkInst &r = kBlkInst[i];
+        if (r.G != G || r.S != S || r.NSW != NSW || r.NL != NL || (B >= 0 && (r.B != B || r.CLM != CLM))) continue;
+        if (row < 0) row = i;
+        for (int w = 0; w < 11; ++w)
+            if (r.split.pw[w] != kBlkInst[row].split.pw[w]) return -1;
+    }
+    return row;
+}
+constexpr int blk_pairs(const BlkInst &r) { int n = 0; for (int w = 0; w < r.NSW; ++w) n += r.split.pw[w]; return n; }
+
 template <int G, int S, int NSW, int NL> constexpr const int *blk_split()
 {
-    if constexpr (G == 8) { static_assert(S == 64 && NSW == 11 && NL == 2, "the eight-group map: 1024-sample rows over eleven sweep wavefronts"); return BlkSplitOct64::pw; }
-    else
-    if constexpr (NSW == 7) return BlkSplit7<S>::pw;
-    else
-    if constexpr (G == 4 && NL < 4 && S == 32 && NSW == 8) return BlkSplitQuad32::pw;
-    else if constexpr (G == 1 && NL == 4 && S == 16 && NSW == 8) return BlkSplitFour16::pw;
-    else return BlkSplit<S, NSW>::pw;
+    constexpr int row = blk_inst_find(G, S, -1, NSW, NL, 0);
+    static_assert(row >= 0, "kBlkInst has no row for this instantiation, or two with different splits");
+    static_assert(blk_pairs(kBlkInst[row]) == S, "the row's pairs do not sum to S");
+    return kBlkInst[row].split.pw;
 }
 
 template <int G, int S, int NSW, int NL> constexpr bool blk_split_has(int k)
@@ -2284,7 +2322,7 @@ static bool blk_chip_ok(const Options &opt)
 // slices of a cluster side by side in ONE XCD's queue (the exchange stays inside that XCD's L2 domain); but an XCD's 32 CUs then hold
 // 32 / nsl whole clusters and 32 % nsl slices of the next one, which wait a whole round for their mates -- and so does every round after
 // (three slices: four rounds' time for three rounds of work).  Map 1, consecutive ids, strands at most one cluster of the whole chip.
-static int blk_cluster_map(int nsl, int64_t clusters, const Options &opt)
+static int blk_cluster_map(int nsl, const Options &opt)
 {
     if (opt.blk_cluster_map >= 0) return opt.blk_cluster_map;      // (0 / 1 force a map; -1: by the number of slices)
     // The two maps take the same time at every slice count measured (profiles/r05/cluster_form.txt) -- the exchange hides behind the chain of
@@ -2298,7 +2336,6 @@ static int blk_cluster_map(int nsl, int64_t clusters, const Options &opt)
     // every slice count; map 0 -- and its per-XCD deadlock-freedom argument -- runs only when the option forces it (tests, A/B).
     // (Measured, profiles/r05/cluster_form.txt: the two tie at 3, 5, 6, 7 slices of 256 clusters; 20 slices: 32 rounds against 22,
     //  122.0 against 83.9 ms at 4096 x 4096 on 20000 samples; 28 slices of 64 clusters: 40.3 against 37.3 ms.)
-    (void)clusters;
     return 1;
 }
 
@@ -2307,26 +2344,25 @@ static int blk_cluster_map(int nsl, int64_t clusters, const Options &opt)
 // each -- the sweeps are halved by giving a workgroup 8 neurons instead of 16 (4096 x 2048, m = 1024: 4.0 -> 2.9 ms).
 static BlkShape blk_shape(int64_t m, int64_t C, const Options &opt)
 {
-    if (m <= 0 || C <= 0) return {0, 0, 0, 0, 0, 0};               // (an empty calibration set has no shape: the slice count below would divide by zero)
+    if (m <= 0 || C <= 0) return {0, 0, 0, 0, 0, 0, 0};            // (an empty calibration set has no shape: the slice count below would divide by zero)
     {
         // By default (1): every row beyond 3072 samples -- a slot of the cluster form is the headline shape's (its exchange hides behind the
         // chain of decisions), the classic shapes lose a third of that rate from 2049 samples up --, and rows of 1537..3072 samples
         // wherever the layer is ONE round of the chip (an XCD holds 32 / slices clusters at a time: up to 2048 neurons at two slices,
         // 1280 at three): profiles/r05/cluster_form.txt.
         const int clm = opt.blk_cluster;
-        const int ns_ = (int)((m + 1023) / 1024);
-        const bool one_round = ns_ <= 32 && ((C + 15) / 16 + 7) / 8 <= 32 / ns_;      // with 16 neurons per workgroup
+        const int ns = (int)((m + 1023) / 1024);
+        const bool one_round = ns <= 32 && ((C + 15) / 16 + 7) / 8 <= 32 / ns;        // with 16 neurons per workgroup
         const bool take = blk_chip_ok(opt) && (clm == 1 ? (m > 3072 || (m > 1536 && one_round && (m > 2048 || C > 128))) : (clm > 1 && m > clm));   // (at most 128 neurons on rows of at most 2048 samples: the one-neuron workgroups stay ahead, 1.98 / 2.07 ms)
         // Round 6: rows of 2049..3072 samples in layers wider than 2048 neurons -- three 1024-sample slices would be 85 clusters per round
         // (four rounds for 3.01 rounds of work: 12.6 ms at 4096 x 4096 on 3000 samples, behind the classic one-step shape's 11.5) -- as FOUR
         // slices of 768 samples: 64 clusters per round, four whole rounds of a shorter slot.  (Other ragged lengths gain nothing from
         // shorter slices: a 768-sample slot takes 0.875 of a 1024-sample one)
         if (clm == 1 && blk_chip_ok(opt) && m > 2048 && m <= 3072 && C > 2048 && opt.blk_cluster768 != 0)
-            return {4, 24, 4, 768, 11, 4, 4};                      // (eight or eleven sweep wavefronts: launch_blk, by the alphabet's form)
+            return {4, 24, 4, 768, 11, 4, 4};                      // (eight or eleven sweep wavefronts: blk_instance, by the alphabet's form)
         if (take && m <= kClusterMaxM) {
             // neurons per workgroup: the fewest (4, 8, 16) with which the layer is still ONE round of the chip -- a slot of the 4- and
             // 8-neuron shapes is the decision wavefront's (with the exchange's flight exposed), a slot of the 16-neuron shape the sweeps'
-            const int ns = (int)((m + 1023) / 1024);
             const int cn = opt.blk_cluster_nl;
             // (measured, profiles/r05/cluster_form.txt: 8 neurons per workgroup wherever the layer is then still one round -- an XCD holds
             //  32 / ns clusters at a time --, 16 otherwise; 4 per workgroup never beat 8)
@@ -2352,34 +2388,26 @@ static BlkShape blk_shape(int64_t m, int64_t C, const Options &opt)
     // rotations per slot, and the short rows no longer put 16 neurons on a workgroup (a layer of 1024 neurons filled 64 CUs):
     // 4096 x 512 on 1024 samples 1.74 -> 1.56 ms, x 1024 2.10 -> 1.65, x 2048 2.44 -> 1.97; 4096 x 1024 on 768 samples 2.69 -> 1.48,
     // on 512 samples 1.96 -> 1.38 (profiles/r04/latency_shapes.txt).  At most 128 neurons: 1.57 both ways at first; with the pair split of
-    // BlkSplitQuad32 the four-group form is ahead there too (4096 x 128 on 1024 samples 1.58 -> 1.40 ms, on 768 1.62 -> 1.39, on 512 1.37 ->
+    // 2,5,5,4,2,5,5,4 the four-group form is ahead there too (4096 x 128 on 1024 samples 1.58 -> 1.40 ms, on 768 1.62 -> 1.39, on 512 1.37 ->
     // 1.33; 4096 x 10 1.62 -> 1.50; cfg1's Dense(784 -> 128) 0.279 -> 0.271) and is the default for every layer of at most 2048 neurons.
     const int quad = opt.blk_quad_groups; // 2 (default): every layer of at most 2048 neurons; 1: 129..2048 only; 0: off
     if (quad && C <= 2048 && (quad >= 2 || C > 128) && m > 256 && m <= 1024) {
         const int nl = C > 1024 ? 2 : 1;
         const int qw = opt.blk_quad_waves;
-        const int qnw = qw ? qw : (nl == 1 ? 7 : 8);                  // (seven sweep wavefronts: see BlkSplit7; rows beyond 768 samples keep eight)
+        const int qnw = qw ? qw : (nl == 1 ? 7 : 8);                  // (seven sweep wavefronts: see kBlkInst; rows beyond 768 samples keep eight)
         if (m <= 512) return {4, 16, 4, 512, qnw, nl};
         if (m <= 768) return {4, 24, 4, 768, qnw, nl};
         return {4, 32, 4, 1024, qw == 7 ? 7 : 8, nl};                 // (rows of 769..1024 samples: seven only when the option forces it)
     }
-    if (C <= 128 && opt.blk_pair_groups && opt.blk_single_groups) {
-        if (m > 256 && m <= 512) return {1, 4, 4, 512, 4, 1};
-        if (m > 512 && m <= 1024) return {1, 8, 4, 1024, 8, 1};
-        if (m > 1024 && m <= 1536) return {1, 12, 2, 1536, 8, 1};
-        if (m > 1536 && m <= 2048) return {1, 16, 2, 2048, 8, 1};
-        if (m > 2048 && m <= 3072) return {1, 24, 1, 3072, 8, 1};
-        if (m > 3072 && m <= 4096) return {1, 32, 1, 4096, 8, 1};
-        if (m > 4096 && m <= 5120) return {1, 40, 1, 5120, 8, 1};    // (eleven sweep wavefronts of 2-4 pairs: 2.17 against 2.06 ms at 2048 x 128 on 5008 samples)
-    }
     if (C <= 512 && opt.blk_pair_groups) {
-        if (m > 256 && m <= 512) return {1, 4, 4, 512, 4, 2};
-        if (m > 512 && m <= 1024) return {1, 8, 4, 1024, 8, 2};
-        if (m > 1024 && m <= 1536) return {1, 12, 2, 1536, 8, 2};
-        if (m > 1536 && m <= 2048) return {1, 16, 2, 2048, 8, 2};
-        if (m > 2048 && m <= 3072) return {1, 24, 1, 3072, 8, 2};
-        if (m > 3072 && m <= 4096) return {1, 32, 1, 4096, 8, 2};
-        if (m > 4096 && m <= 5120) return {1, 40, 1, 5120, 8, 2};
+        const int nl = C <= 128 && opt.blk_single_groups ? 1 : 2;
+        if (m > 256 && m <= 512) return {1, 4, 4, 512, 4, nl};
+        if (m > 512 && m <= 1024) return {1, 8, 4, 1024, 8, nl};
+        if (m > 1024 && m <= 1536) return {1, 12, 2, 1536, 8, nl};
+        if (m > 1536 && m <= 2048) return {1, 16, 2, 2048, 8, nl};
+        if (m > 2048 && m <= 3072) return {1, 24, 1, 3072, 8, nl};
+        if (m > 3072 && m <= 4096) return {1, 32, 1, 4096, 8, nl};
+        if (m > 4096 && m <= 5120) return {1, 40, 1, 5120, 8, nl};   // (eleven sweep wavefronts of 2-4 pairs: 2.17 against 2.06 ms at 2048 x 128 on 5008 samples, one neuron)
     }
     if (m > 256 && m <= 512) return {4, 16, 4, 512, nw4, 4};
     if (m > 512 && m <= 768) return {4, 24, 4, 768, nw4, 4};
@@ -2406,7 +2434,7 @@ static BlkShape blk_shape(int64_t m, int64_t C, const Options &opt)
     // record, 4 neurons per workgroup at any width -- a layer of 4096 neurons takes four rounds of workgroups, still several times
     // the several-wavefronts-per-neuron kernel these rows had
     if (m > 4096 && m <= 5120) return {1, 40, 1, 5120, 8, 4};
-    return {0, 0, 0, 0, 0, 0};
+    return {0, 0, 0, 0, 0, 0, 0};
 }
 
 // Neuron groups per sweep wavefront of the sixteen-neuron shape on 1024-sample rows or slices over eleven sweep wavefronts (the headline
@@ -2452,17 +2480,57 @@ static size_t blk_hdrs_bytes(int64_t nblk, int B, bool CL = false) { return (siz
 static size_t blk_hdrs_off(int64_t nblk, const BlkShape &sh) { return blk_recs_bytes(nblk, sh) * (size_t)(sh.NS ? sh.NS : 1); }     // compact headers: behind the last record stream
 static size_t blk_mbox_off(int64_t nblk, const BlkShape &sh) { return blk_hdrs_off(nblk, sh) + ((blk_hdrs_bytes(nblk, sh.B, sh.NS != 0) + 255) & ~(size_t)255); }
 
-// Whether the kernel itself writes Keras-layout outputs for this shape (the 16-neuron four-step shapes: blk_kout_shape)
-bool blk_keras_out_supported(int64_t m, int64_t C, const Options &opt)
+// a32 of a symmetric alphabet {-a, 0, a} or {-a, a} (DevAlphabet::sym_a), else 0.  Option "variant" bit 5 keeps the general form (A/B timing).
+// (device alphabets: a.A is the UNIT alphabet linspace(-1, 1, M) -- symmetric exactly when rad * unit is, for a finite rad > 0)
+static float blk_sym_a(const PipeArgs &a) { return (a.opt.variant >> 4) & 2 ? 0.f : blk_sym_of(a.A.a, a.A.M); }
+
+constexpr bool blk_kout_shape(int G, int B, int NL, int CLM) { return ((G == 4 && NL == 4) || (G == 8 && NL == 2)) && B == 4 && CLM == 0; }
+
+// The call's row of kBlkInst, or nullptr: the shape blk_shape gives its rows and width (*sh: what sizes the records and the workspace), with
+// the two choices the alphabet's form makes.  Everything that asks whether or what the kernel runs asks here.
+static const BlkInst *blk_instance(const PipeArgs &a, BlkShape *sh)
 {
-    const BlkShape sh = blk_shape(m, C, opt);
-    return sh.G == 4 && sh.B == 4 && sh.NL == 4 && sh.NS == 0;
+    *sh = blk_shape(a.m, a.C, a.opt);
+    if (!sh->G) return nullptr;
+    const bool sym = blk_sym_a(a) != 0.f;
+    int G = sh->G, S = sh->S, NSW = sh->NW, NL = sh->NL;
+    if (sh->NS && S == 24) {
+        // four 768-sample slices (blk_shape).  Sweep wavefronts, measured at 4096 x 4096 on 3000 samples (tools/c768_probe.py): the symmetric
+        // form 10.29 ms with eleven against 10.68 with eight, the general form 11.02 with eight against 11.25 with eleven
+        NSW = a.opt.blk_cluster768 > 0 ? a.opt.blk_cluster768 : (sym ? 11 : 8);       // (the option: -1, or 8 / 11 forced)
+    } else if (blk_groups(*sh, sym, a.opt) == 8) {
+        G = 8; S = 64; NL = 2;                                     // (the same 16 neurons and 1024 samples: records and workspace are the shape's)
+    }
+    const int row = blk_inst_find(G, S, sh->B, NSW, NL, sh->NS ? 1 : 0);
+    return row < 0 || (blk_sym_only(kBlkInst[row]) && !sym) ? nullptr : &kBlkInst[row];
 }
+
+// What gpfq_last_dense_kernel says of a row's launch
+static const char *blk_family(const BlkInst &r)
+{
+    if (r.CLM)
+        return r.G == 8 ? "gpfq_blk_kernel, cluster form (rows cut into 1024-sample slices: one workgroup of 11 sweep wavefronts + 1 decision wavefront per slice, partial dot products exchanged once per slot; eight neuron groups)"
+                        : "gpfq_blk_kernel, cluster form (rows cut into 1024-sample slices: one workgroup of 8 or 11 sweep wavefronts + 1 decision wavefront per slice, partial dot products exchanged once per slot)";
+    return r.G == 8 ? "gpfq_blk_kernel (4 to 11 sweep wavefronts + 1 decision wavefront per workgroup, blocks of steps per slot; eight neuron groups)"
+                    : "gpfq_blk_kernel (4 to 11 sweep wavefronts + 1 decision wavefront per workgroup, blocks of steps per slot)";
+}
+
+bool blk_instance_query(const PipeArgs &a, int32_t out[8])
+{
+    BlkShape sh;
+    const BlkInst *r = blk_instance(a, &sh);
+    if (!r) return false;
+    const int32_t v[8] = {r->G, r->S, r->B, r->NSW, blk_sym_a(a) != 0.f, r->NL, r->CLM, blk_kout_shape(r->G, r->B, r->NL, r->CLM)};
+    std::memcpy(out, v, sizeof v);
+    return true;
+}
+// Whether the kernel itself writes Keras-layout outputs for this call (the 16-neuron four-step shapes: blk_kout_shape)
+bool blk_keras_out_supported(const PipeArgs &a) { int32_t v[8]; return blk_instance_query(a, v) && v[7]; }
 
 bool blk_supported(const PipeArgs &a)
 {
-    const BlkShape sh = blk_shape(a.m, a.C, a.opt);
-    if (sh.G == 0 || a.N < 1 || a.m < 1) return false;
+    BlkShape sh;
+    if (a.N < 1 || a.m < 1 || !blk_instance(a, &sh)) return false;
     if (a.A.M > 64 || !a.A.ascending) return false;
     DevAlphabet D{};
     D.M = a.A.M;
@@ -2484,21 +2552,11 @@ size_t blk_workspace_bytes(int64_t N, int64_t m, int64_t Cn, const Options &opt)
         if (!sh.G) continue;
         const int64_t nblk = (N + sh.B - 1) / sh.B;
         // (cluster form: a record stream per slice, the compact headers once, the exchange buffers + the error word)
-        const size_t b = blk_recs_bytes(nblk, sh) * (size_t)(sh.NS ? sh.NS : 1) + ((blk_hdrs_bytes(nblk, sh.B, sh.NS != 0) + 255) & ~(size_t)255) + blk_mbox_bytes(Cn, sh);
+        const size_t b = blk_mbox_off(nblk, sh) + blk_mbox_bytes(Cn, sh);
         if (b > need) need = b;
     }
     return need ? need + kAlphaBlock : 0;
 }
-
-// a32 of a symmetric alphabet {-a, 0, a} or {-a, a} (DevAlphabet::sym_a), else 0.  Option "variant" bit 5 keeps the general form (A/B timing).
-// (device alphabets: a.A is the UNIT alphabet linspace(-1, 1, M) -- symmetric exactly when rad * unit is, for a finite rad > 0)
-static float blk_sym_a(const PipeArgs &a)
-{
-    if ((a.opt.variant >> 4) & 2) return 0.f;
-    return blk_sym_of(a.A.a, a.A.M);
-}
-
-constexpr bool blk_kout_shape(int G, int B, int NL, int CLM) { return ((G == 4 && NL == 4) || (G == 8 && NL == 2)) && B == 4 && CLM == 0; }
 
 template <int G, int S, int B, int NSW, bool SYM, int NL, int CLM = 0, bool KOUT = false>
 static hipError_t launch_blk_sym(const PipeArgs &a, const BlkShape &sh, const DevAlphabet *alpha, hipStream_t stream)
@@ -2521,7 +2579,7 @@ static hipError_t launch_blk_sym(const PipeArgs &a, const BlkShape &sh, const De
     K.hdrs = K.recs + blk_hdrs_off(nblk_, sh);
     K.alpha = alpha;
     K.alpha_err = a.fallback_count ? reinterpret_cast<int *>(a.fallback_count + 1) + 1 : nullptr;   // (fourth 32-bit word of the call's counter block, zeroed with it)
-    K.nsl = CL ? sh.NS : 0; K.cl_map = blk_cluster_map(sh.NS, (a.C + NB - 1) / NB, a.opt); K.slice_bytes = (int64_t)blk_recs_bytes(nblk_, sh); K.mbox = nullptr; K.cl_err = nullptr;
+    K.nsl = CL ? sh.NS : 0; K.cl_map = blk_cluster_map(sh.NS, a.opt); K.slice_bytes = (int64_t)blk_recs_bytes(nblk_, sh); K.mbox = nullptr; K.cl_err = nullptr;
     K.u_ld = a.m; K.slack = 0x1p-43 * (double)(sh.NS > 1 ? sh.NS : 1);
     K.cl_timeout = 100000ull * (unsigned long long)a.opt.blk_cluster_timeout_ms; K.cl_fault = a.opt.blk_cluster_fault;
     if constexpr (CLM == 1) {
@@ -2549,12 +2607,21 @@ static hipError_t launch_blk_sym(const PipeArgs &a, const BlkShape &sh, const De
     return hipGetLastError();
 }
 
-template <int G, int S, int B, int NSW = 8, int NL = 4>
-static hipError_t launch_blk_inst(const PipeArgs &a, const BlkShape &sh, const DevAlphabet *alpha, hipStream_t stream)
+// (Row index, form) -> template arguments, I = 2 row + SYM: every row of kBlkInst in its symmetric form (sweep-bound shapes gain 3-4 %,
+// the others nothing) and, unless the row has none (blk_sym_only), its general form.
+template <int I>
+static hipError_t launch_blk_row(const PipeArgs &a, const BlkShape &sh, const DevAlphabet *alpha, hipStream_t stream)
 {
-    // (sweep-bound shapes gain 3-4 %, the others nothing)
-    if (blk_sym_a(a) != 0.f) return launch_blk_sym<G, S, B, NSW, true, NL>(a, sh, alpha, stream);
-    return launch_blk_sym<G, S, B, NSW, false, NL>(a, sh, alpha, stream);
+    constexpr BlkInst R = kBlkInst[I / 2];
+    if constexpr (I % 2 || !blk_sym_only(R)) return launch_blk_sym<R.G, R.S, R.B, R.NSW, I % 2 != 0, R.NL, R.CLM>(a, sh, alpha, stream);
+    else return hipErrorInvalidValue;
+}
+template <int... I>
+static hipError_t launch_blk_rows(std::integer_sequence<int, I...>, int i, const PipeArgs &a, const BlkShape &sh, const DevAlphabet *alpha, hipStream_t stream)
+{
+    hipError_t e = hipErrorInvalidValue;
+    (void)((i == I && ((e = launch_blk_row<I>(a, sh, alpha, stream)), true)) || ...);
+    return e;
 }
 
 // One cluster-form launch in flight per device: the co-residency of a cluster's slices is argued for ONE such launch on the
@@ -2626,14 +2693,17 @@ hipError_t launch_alphabet_device(const float *median32, double alphabet_scalar,
 
 hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
 {
-    const BlkShape sh = blk_shape(a.m, a.C, a.opt);
-    if (!sh.G) return hipErrorInvalidValue;
+    BlkShape sh;
+    const BlkInst *const inst = blk_instance(a, &sh);
+    if (!inst) return hipErrorInvalidValue;
     const int64_t nblk = (a.N + sh.B - 1) / sh.B;
     const int64_t nrec = (nblk + 1) * sh.B + 1;
     const bool r64 = blk_row64(sh.G, sh.B);
     // a.phase: 0 = the whole call; 1 = the alphabet-independent half (the record pre-pass, rows unscaled); 2 = the rest (symmetric form: the
     // records' Xq rows scaled in place, then the kernel) -- gpfq_dense_layer_prepare / _run, which a caller runs on two streams
     const bool do_prep = a.phase != 2, do_run = a.phase != 1;
+    // (the cluster form is noted by a two-phase call's first half already, as it always was)
+    if (do_run || inst->CLM) note_dense_kernel(blk_family(*inst));
     const DevAlphabet *alpha = nullptr;
     hipError_t e = do_run ? blk_alphabet(a, &alpha, stream) : hipSuccess;
     if (e != hipSuccess) return e;
@@ -2665,39 +2735,14 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
             nrm32 = a.nrm32_out; zero16 = nullptr;
         }
     }
-    if (sh.NS) {                                                   // cluster form: NS slices of the headline shape
-        note_dense_kernel("gpfq_blk_kernel, cluster form (rows cut into 1024-sample slices: one workgroup of 8 or 11 sweep wavefronts + 1 decision wavefront per slice, partial dot products exchanged once per slot)");
-        const int sym = sym_shape;
-        if (do_prep) {
-            hipLaunchKernelGGL((gpfq_blk_prep_kernel<4, true, true>), dim3((unsigned)nrec), dim3(256), 0, stream, a.X, a.Xq, a.ld, a.N, (int)a.m, sh.mp * sh.NS,
-                               nrm32, wbase, wbase + blk_hdrs_off(nblk, sh), alpha, sym_prep,
-                               sh.NS, (int64_t)blk_recs_bytes(nblk, sh));
-            e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-        if (!do_run) return hipSuccess;
-        ClusterLaunchGuard one_at_a_time(stream);
-        if (one_at_a_time.err != hipSuccess) return one_at_a_time.err;
-#define GPFQ_BLK_CL(S_, NSW_, NL_, M_) (sym ? launch_blk_sym<4, S_, 4, NSW_, true, NL_, M_>(a, sh, alpha, stream) : launch_blk_sym<4, S_, 4, NSW_, false, NL_, M_>(a, sh, alpha, stream))
-        if (sh.S == 24) {
-            // four 768-sample slices (blk_shape).  Sweep wavefronts, measured at 4096 x 4096 on 3000 samples (tools/c768_probe.py): the symmetric
-            // form 10.29 ms with eleven against 10.68 with eight, the general form 11.02 with eight against 11.25 with eleven
-            const int forced = a.opt.blk_cluster768;
-            const int nw = forced == 8 || forced == 11 ? forced : (sym ? 11 : 8);
-            return nw == 8 ? GPFQ_BLK_CL(24, 8, 4, 1) : GPFQ_BLK_CL(24, 11, 4, 1);
-        }
-        if (sh.NL == 4 && blk_groups(sh, sym != 0, a.opt) == 8) {
-            note_dense_kernel("gpfq_blk_kernel, cluster form (rows cut into 1024-sample slices: one workgroup of 11 sweep wavefronts + 1 decision wavefront per slice, partial dot products exchanged once per slot; eight neuron groups)");
-            return launch_blk_sym<8, 64, 4, 11, true, 2, 1>(a, sh, alpha, stream);
-        }
-        if (sh.NL == 4) return GPFQ_BLK_CL(32, 11, 4, 1);
-        return sh.NL == 1 ? GPFQ_BLK_CL(32, 8, 1, 1) : GPFQ_BLK_CL(32, 8, 2, 1);
-#undef GPFQ_BLK_CL
-    }
     auto *prep = sh.B == 4 ? (r64 ? gpfq_blk_prep_kernel<4, true> : gpfq_blk_prep_kernel<4, false>)
                            : (sh.B == 2 ? (r64 ? gpfq_blk_prep_kernel<2, true> : gpfq_blk_prep_kernel<2, false>) : gpfq_blk_prep_kernel<1, false>);
-    const int sym = sym_prep;   // (exactly the launches launch_blk_inst gives the symmetric form)
+    const int sym = sym_prep;   // (exactly the launches that take the symmetric form)
     if (!do_prep) {
+    } else if (sh.NS) {                                            // cluster form: NS slices, one record stream each
+        hipLaunchKernelGGL((gpfq_blk_prep_kernel<4, true, true>), dim3((unsigned)nrec), dim3(256), 0, stream, a.X, a.Xq, a.ld, a.N, (int)a.m, sh.mp * sh.NS,
+                           nrm32, wbase, wbase + blk_hdrs_off(nblk, sh), alpha, sym,
+                           sh.NS, (int64_t)blk_recs_bytes(nblk, sh));
     } else if (run_form) {
         // (walks of fewer than 2048 steps: runs of records would be fewer workgroups than the chip has compute units, each a chain of eight
         //  records -- a Dense(128 -> 10) layer's pre-pass 0.08 ms longer; those keep one record per workgroup)
@@ -2724,60 +2769,9 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
     }
     e = hipGetLastError();
     if (e != hipSuccess || !do_run) return e;
-    // (four neuron groups with one or two neurons per lane: the narrow forms of the fused matrix shape)
-    if (sh.G == 4 && sh.NL < 4 && sh.NW == 7) {                    // (rows of at most 768 samples: blk_shape)
-        if (sh.S == 16) return sh.NL == 1 ? launch_blk_inst<4, 16, 4, 7, 1>(a, sh, alpha, stream) : launch_blk_inst<4, 16, 4, 7, 2>(a, sh, alpha, stream);
-        if (sh.S == 24) return sh.NL == 1 ? launch_blk_inst<4, 24, 4, 7, 1>(a, sh, alpha, stream) : launch_blk_inst<4, 24, 4, 7, 2>(a, sh, alpha, stream);
-        return sh.NL == 1 ? launch_blk_inst<4, 32, 4, 7, 1>(a, sh, alpha, stream) : launch_blk_inst<4, 32, 4, 7, 2>(a, sh, alpha, stream);
-    }
-    if (sh.G == 4 && sh.NL < 4) {
-        if (sh.S == 16) return sh.NL == 1 ? launch_blk_inst<4, 16, 4, 8, 1>(a, sh, alpha, stream) : launch_blk_inst<4, 16, 4, 8, 2>(a, sh, alpha, stream);
-        if (sh.S == 24) return sh.NL == 1 ? launch_blk_inst<4, 24, 4, 8, 1>(a, sh, alpha, stream) : launch_blk_inst<4, 24, 4, 8, 2>(a, sh, alpha, stream);
-        // (eleven sweep wavefronts buy these shapes nothing: 4096 x 512 on 1024 samples 1.77 against 1.62 ms, 4096 x 2048 1.94 / 1.95 in round 4;
-        //  measured again on round 5's kernels, one neuron per lane: 1.326 against 1.285 -- profiles/r05/cluster_form.txt)
-        return sh.NL == 1 ? launch_blk_inst<4, 32, 4, 8, 1>(a, sh, alpha, stream) : launch_blk_inst<4, 32, 4, 8, 2>(a, sh, alpha, stream);
-    }
-    if (sh.NL == 1) {                                              // one-neuron workgroups (layers of at most 128 neurons)
-        if (sh.B == 4) return sh.S == 4 ? launch_blk_inst<1, 4, 4, 4, 1>(a, sh, alpha, stream) : launch_blk_inst<1, 8, 4, 8, 1>(a, sh, alpha, stream);
-        if (sh.B == 2) return sh.S == 12 ? launch_blk_inst<1, 12, 2, 8, 1>(a, sh, alpha, stream) : launch_blk_inst<1, 16, 2, 8, 1>(a, sh, alpha, stream);
-        if (sh.S == 24) return launch_blk_inst<1, 24, 1, 8, 1>(a, sh, alpha, stream);
-        return sh.S == 32 ? launch_blk_inst<1, 32, 1, 8, 1>(a, sh, alpha, stream) : launch_blk_inst<1, 40, 1, 8, 1>(a, sh, alpha, stream);
-    }
-    if (sh.NL == 2) {                                              // two-neuron workgroups (layers of at most 512 neurons)
-        if (sh.B == 4) return sh.S == 4 ? launch_blk_inst<1, 4, 4, 4, 2>(a, sh, alpha, stream) : launch_blk_inst<1, 8, 4, 8, 2>(a, sh, alpha, stream);
-        if (sh.B == 2) return sh.S == 12 ? launch_blk_inst<1, 12, 2, 8, 2>(a, sh, alpha, stream) : launch_blk_inst<1, 16, 2, 8, 2>(a, sh, alpha, stream);
-        if (sh.S == 24) return launch_blk_inst<1, 24, 1, 8, 2>(a, sh, alpha, stream);
-        return sh.S == 32 ? launch_blk_inst<1, 32, 1, 8, 2>(a, sh, alpha, stream) : launch_blk_inst<1, 40, 1, 8, 2>(a, sh, alpha, stream);
-    }
-    if (sh.B == 1 && sh.S == 40) return launch_blk_inst<1, 40, 1>(a, sh, alpha, stream);
-    if (sh.B == 1) {
-        if (sh.G == 2) return sh.S == 64 ? launch_blk_inst<2, 64, 1, 11>(a, sh, alpha, stream) : launch_blk_inst<2, 48, 1, 11>(a, sh, alpha, stream);
-        return sh.S == 32 ? launch_blk_inst<1, 32, 1>(a, sh, alpha, stream) : launch_blk_inst<1, 24, 1>(a, sh, alpha, stream);
-    }
-    if (sh.G == 4 && sh.S == 64) return launch_blk_inst<4, 64, 2, 11>(a, sh, alpha, stream);
-    if (sh.G == 4 && sh.S == 48) return launch_blk_inst<4, 48, 2, 11>(a, sh, alpha, stream);
-    if (sh.G == 4 && sh.NW == 11) {
-        if (sh.S == 16) return launch_blk_inst<4, 16, 4, 11>(a, sh, alpha, stream);
-        if (sh.S == 24) return launch_blk_inst<4, 24, 4, 11>(a, sh, alpha, stream);
-        if (blk_groups(sh, sym_shape != 0, a.opt) == 8) {
-            note_dense_kernel("gpfq_blk_kernel (4 to 11 sweep wavefronts + 1 decision wavefront per workgroup, blocks of steps per slot; eight neuron groups)");
-            return launch_blk_sym<8, 64, 4, 11, true, 2>(a, sh, alpha, stream);
-        }
-        return launch_blk_inst<4, 32, 4, 11>(a, sh, alpha, stream);
-    }
-    if (sh.G == 4) {
-        if (sh.S == 16) return launch_blk_inst<4, 16, 4>(a, sh, alpha, stream);
-        if (sh.S == 24) return launch_blk_inst<4, 24, 4>(a, sh, alpha, stream);
-        return launch_blk_inst<4, 32, 4>(a, sh, alpha, stream);
-    }
-    if (sh.G == 1) {
-        if (sh.S == 8) return launch_blk_inst<1, 8, 4>(a, sh, alpha, stream);
-        if (sh.S == 12) return launch_blk_inst<1, 12, 2>(a, sh, alpha, stream);
-        return launch_blk_inst<1, 16, 2>(a, sh, alpha, stream);
-    }
-    if (sh.B == 4) return launch_blk_inst<2, 16, 4>(a, sh, alpha, stream);
-    if (sh.S == 24) return launch_blk_inst<2, 24, 2>(a, sh, alpha, stream);
-    return launch_blk_inst<2, 32, 2>(a, sh, alpha, stream);
+    std::optional<ClusterLaunchGuard> one_at_a_time;
+    if (inst->CLM && one_at_a_time.emplace(stream).err != hipSuccess) return one_at_a_time->err;
+    return launch_blk_rows(std::make_integer_sequence<int, 2 * kBlkInsts>{}, 2 * (int)(inst - kBlkInst) + sym_shape, a, sh, alpha, stream);
 }
 
 }  // namespace gpfq

@@ -355,8 +355,7 @@ int gpfq_quantize_neurons(const float *X, const float *Xq, int64_t ld, const flo
                 pa.workspace = static_cast<char *>(workspace) + onchip_stats_bytes(N);
                 pa.fallback_count = static_cast<unsigned long long *>(workspace);
                 pa.zero_counters = 1;                              // (the kernel that stores the alphabet zeroes the counter block as well: one launch, no memset)
-                gpfq::note_dense_kernel("gpfq_blk_kernel (4 to 11 sweep wavefronts + 1 decision wavefront per workgroup, blocks of steps per slot)");
-                hipError_t e = gpfq::launch_blk(pa, s);
+                hipError_t e = gpfq::launch_blk(pa, s);             // (notes its kernel family itself, by the instantiation it resolves)
                 if (e != hipSuccess) return hip_fail(e, "gpfq_quantize_neurons(block-pipelined)");
                 return o.sync_errors ? gpfq_call_status(workspace, stream) : GPFQ_OK;
             }
@@ -454,8 +453,9 @@ int gpfq_layer_alphabet_from_kernel(const float *W, int64_t n, double alphabet_s
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_layer_alphabet_from_kernel");
 }
 
-// The answers of gpfq_dense_layer_supported / _workspace_bytes under the caller's snapshot (dense_layer_impl: one call, one reading)
-static bool dense_layer_supported(int64_t N, int64_t m, int64_t C, const double *unit_alphabet, int M, const gpfq::Options &o)
+// The answers of gpfq_dense_layer_supported / _workspace_bytes under the caller's snapshot (dense_layer_impl: one call, one reading).
+// *pa: what the block kernel's host-side queries are asked with.
+static bool dense_layer_supported(int64_t N, int64_t m, int64_t C, const double *unit_alphabet, int M, const gpfq::Options &o, gpfq::PipeArgs *pa)
 {
     if (N < 1 || m < 1 || C < 1 || !unit_alphabet || M < 1 || M > 64) return false;
     HostAlphabet H;
@@ -463,9 +463,9 @@ static bool dense_layer_supported(int64_t N, int64_t m, int64_t C, const double 
     // exactly the rows and alphabets gpfq_quantize_neurons gives the block-pipelined kernel by default
     const bool forced_old = o.lanes_per_neuron != 0 || o.waves_per_neuron != 0 || o.onchip_mode != 1 || o.pipe == 0 || o.pipe == 1;
     if (forced_old || !(m > 256 && m <= GPFQ_ONCHIP_MAX_M)) return false;
-    gpfq::PipeArgs pa{};
-    pa.A = H.A; pa.N = N; pa.m = m; pa.C = C; pa.opt = o;
-    return gpfq::blk_supported(pa);
+    *pa = gpfq::PipeArgs{};
+    pa->A = H.A; pa->N = N; pa->m = m; pa->C = C; pa->opt = o;
+    return gpfq::blk_supported(*pa);
 }
 
 static size_t dense_layer_workspace_bytes(int64_t N, int64_t m, int64_t C, const gpfq::Options &o)
@@ -476,13 +476,21 @@ static size_t dense_layer_workspace_bytes(int64_t N, int64_t m, int64_t C, const
 
 int gpfq_dense_layer_supported(int64_t N, int64_t m, int64_t C, const double *unit_alphabet, int M)
 {
-    return dense_layer_supported(N, m, C, unit_alphabet, M, gpfq::options_snapshot()) ? 1 : 0;
+    gpfq::PipeArgs pa;
+    return dense_layer_supported(N, m, C, unit_alphabet, M, gpfq::options_snapshot(), &pa) ? 1 : 0;
 }
 
 int gpfq_dense_layer_keras_out_supported(int64_t N, int64_t m, int64_t C, const double *unit_alphabet, int M)
 {
-    const gpfq::Options o = gpfq::options_snapshot();
-    return dense_layer_supported(N, m, C, unit_alphabet, M, o) && gpfq::blk_keras_out_supported(m, C, o) ? 1 : 0;
+    gpfq::PipeArgs pa;
+    return dense_layer_supported(N, m, C, unit_alphabet, M, gpfq::options_snapshot(), &pa) && gpfq::blk_keras_out_supported(pa) ? 1 : 0;
+}
+
+int gpfq_blk_instance(int64_t N, int64_t m, int64_t C, const double *alphabet, int M, int32_t out[8])
+{
+    gpfq::PipeArgs pa;
+    if (!out || !dense_layer_supported(N, m, C, alphabet, M, gpfq::options_snapshot(), &pa)) return 0;
+    return gpfq::blk_instance_query(pa, out) ? 1 : 0;
 }
 
 size_t gpfq_dense_layer_workspace_bytes(int64_t N, int64_t m, int64_t C)
@@ -508,15 +516,19 @@ static int dense_layer_impl(int phase, const float *X, const float *Xq, int64_t 
     if (phase != 1 && (!W || !dev_alphabet)) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (ld < m) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ld=%lld < m=%lld", (long long)ld, (long long)m);
     const gpfq::Options o = gpfq::options_snapshot();
+    gpfq::PipeArgs pa{};
+    pa.A = H.A; pa.N = N; pa.m = m; pa.C = C;
+    pa.opt = o;
     if (phase != 1) {
         if (ldc < c_lo + C) return fail(GPFQ_ERR_INVALID_ARG, "kernel pitch ldc=%lld < c_lo + C=%lld", (long long)ldc, (long long)(c_lo + C));
         if (out_layout != GPFQ_LAYOUT_NEURON_MAJOR && out_layout != GPFQ_LAYOUT_KERAS) return fail(GPFQ_ERR_INVALID_ARG, "unknown output layout %d", out_layout);
         if (out_layout == GPFQ_LAYOUT_KERAS && ldo < c_lo + C) return fail(GPFQ_ERR_INVALID_ARG, "output pitch ldo=%lld < c_lo + C=%lld", (long long)ldo, (long long)(c_lo + C));
-        if (out_layout == GPFQ_LAYOUT_KERAS && ldo != 1 && !gpfq::blk_keras_out_supported(m, C, o))
+        if (out_layout == GPFQ_LAYOUT_KERAS && ldo != 1 && !gpfq::blk_keras_out_supported(pa))
             return fail(GPFQ_ERR_UNSUPPORTED, "the kernel of this shape (m=%lld, C=%lld) writes neuron-major outputs only (gpfq_dense_layer_keras_out_supported): "
                                               "ask for GPFQ_LAYOUT_NEURON_MAJOR and lay them out with gpfq_assemble_kernel_device", (long long)m, (long long)C);
     }
-    if (!dense_layer_supported(N, m, C, unit_alphabet, M, o))
+    gpfq::PipeArgs query;
+    if (!dense_layer_supported(N, m, C, unit_alphabet, M, o, &query))
         return fail(GPFQ_ERR_UNSUPPORTED, "no block-pipelined kernel for N=%lld m=%lld C=%lld M=%d (gpfq_dense_layer_supported): use gpfq_quantize_neurons with a host alphabet",
                     (long long)N, (long long)m, (long long)C, M);
     if (!workspace || (uintptr_t)workspace % 16 != 0 || workspace_bytes < dense_layer_workspace_bytes(N, m, C, o))
@@ -534,12 +546,9 @@ static int dense_layer_impl(int phase, const float *X, const float *Xq, int64_t 
             if (e != hipSuccess) return hip_fail(e, what);
         }
     }
-    gpfq::PipeArgs pa{};
     pa.X = X; pa.Xq = Xq; pa.ld = ld; pa.nrm32 = nrm32; pa.nrm32_out = n32_out;
     pa.Wt = W ? W + c_lo : nullptr; pa.ldw = 1; pa.ldt = ldc;     // the Keras kernel itself: neuron j's weight of step t is W[t][c_lo + j]
-    pa.A = H.A; pa.N = N; pa.m = m; pa.C = C;
     pa.resid = resid; pa.u_out = nullptr;
-    pa.opt = o;
     if (out_layout == GPFQ_LAYOUT_KERAS) {
         pa.qidx = qidx ? qidx + c_lo : nullptr; pa.Qt = Q ? Q + c_lo : nullptr;
         pa.o_sj = 1; pa.o_st = ldo;
@@ -551,7 +560,6 @@ static int dense_layer_impl(int phase, const float *X, const float *Xq, int64_t 
     pa.phase = phase;
     pa.workspace = static_cast<char *>(workspace) + onchip_stats_bytes(N);
     pa.fallback_count = static_cast<unsigned long long *>(workspace);
-    if (phase != 1) gpfq::note_dense_kernel("gpfq_blk_kernel (4 to 11 sweep wavefronts + 1 decision wavefront per workgroup, blocks of steps per slot)");
     e = gpfq::launch_blk(pa, s);
     if (e != hipSuccess) return hip_fail(e, what);
     return (o.sync_errors && phase != 1) ? gpfq_call_status(workspace, stream) : GPFQ_OK;

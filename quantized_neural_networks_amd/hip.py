@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the HIP stream; every comput
 through the C ABI with raw device pointers.  There is NO CPU fallback: if the library cannot be
 loaded, or a tensor is not on a GPU, the call raises.
 """
+import collections
 import ctypes
 import os
 
@@ -35,6 +36,7 @@ SYMBOLS = {
     "gpfq_row_norms": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "gpfq_workspace_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "gpfq_last_dense_kernel": (ctypes.c_char_p, []),
+    "gpfq_blk_instance": (_int, [_i64, _i64, _i64, _dp, _int, ctypes.POINTER(ctypes.c_int32)]),
     "gpfq_set_main_kernel_events": (_int, [_vp, _vp]),
     "gpfq_set_option": (_int, [ctypes.c_char_p, _int]),
     "gpfq_get_option": (_int, [ctypes.c_char_p, ctypes.POINTER(_int)]),
@@ -653,6 +655,20 @@ def dense_layer_supported(N, m, C, unit_alphabet):
     """Whether quantize_dense_layer (device-resident alphabet, the block-pipelined kernel) takes this shape and unit alphabet."""
     arr = (ctypes.c_double * len(unit_alphabet))(*[float(v) for v in unit_alphabet])
     return bool(load().gpfq_dense_layer_supported(int(N), int(m), int(C), arr, len(unit_alphabet)))
+
+
+BlkInstance = collections.namedtuple("BlkInstance", "G S B NSW SYM NL CLM KOUT")
+
+
+def blk_instance(N, m, C, unit_alphabet):
+    """The instantiation of the block-pipelined kernel that quantize_dense_layer would launch for this shape and unit alphabet under the
+    current options (gpfq_blk_instance: a row of gpfq_blk.hip's table, the alphabet's form, whether it writes the Keras layout itself),
+    or None where dense_layer_supported() says no.  Host only: needs no device."""
+    arr = (ctypes.c_double * len(unit_alphabet))(*[float(v) for v in unit_alphabet])
+    out = (ctypes.c_int32 * 8)()
+    if not load().gpfq_blk_instance(int(N), int(m), int(C), arr, len(unit_alphabet), out):
+        return None
+    return BlkInstance(*out)
 
 
 def device_alphabet_ok(median32, unit_alphabet, alphabet_scalar):

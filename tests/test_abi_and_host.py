@@ -441,3 +441,41 @@ def test_dispatch_answers_match_golden(lib):
     differ = np.argwhere(got != want["answers"])
     assert differ.size == 0, differ[:10]
     _assert_options_at_defaults(lib)
+
+
+@pytest.fixture(scope="module")
+def blk_instances(lib):
+    """(generator module, gpfq_blk_instance over its grid): computed once for the tests below, which leave it unchanged."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_blk_instances_golden", os.path.join(ROOT, "tools", "gen_blk_instances_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    got = gen.answers(lib)
+    _assert_options_at_defaults(lib)
+    return gen, got
+
+
+def test_blk_instances_match_golden(lib, blk_instances):
+    """The instantiation of the block kernel that gpfq_blk_instance resolves over the grid of tools/gen_blk_instances_golden.py equals,
+    element for element, the template arguments the commit named in that script launched (tests/golden/blk_instances.npz, recorded
+    there by a dry-run hook -- never regenerated from the code under test)."""
+    gen, got = blk_instances
+    want = np.load(os.path.join(ROOT, "tests", "golden", "blk_instances.npz"))
+    assert list(want["settings"]) == list(gen.setting_names()) and tuple(want["fields"]) == gen.FIELDS
+    assert (tuple(want["alphabets"]), tuple(want["m"]), tuple(want["C"])) == (gen.ALPHABET_SIZES, gen.M_AXIS, gen.C_AXIS)
+    assert got.shape == want["answers"].shape == (28, 3, 25, 13, 9) and got.dtype == want["answers"].dtype
+    differ = np.argwhere(got != want["answers"])
+    assert differ.size == 0, differ[:10]
+
+
+def test_blk_instance_is_total(lib, blk_instances):
+    """Wherever gpfq_dense_layer_supported says yes there is a row of the kernel's table to launch (supported means exactly that), and
+    the row's Keras-layout flag is gpfq_dense_layer_keras_out_supported's answer."""
+    gen, got = blk_instances
+    sup = gen.support_answers(lib)
+    _assert_options_at_defaults(lib)
+    assert sup[..., 0].any() and not sup[..., 0].all() and set(np.unique(got[..., 0])) == {0, 1}
+    missing = np.argwhere((sup[..., 0] == 1) & (got[..., 0] != 1))
+    assert missing.size == 0, missing[:10]
+    kout = np.argwhere(got[..., 8] != sup[..., 1])
+    assert kout.size == 0, kout[:10]
