@@ -79,6 +79,9 @@ def main():
     ap.add_argument("--test-samples", type=int, default=2000)
     ap.add_argument("--refine-passes", type=int, default=0, metavar="K",
                     help="up to K refinement sweeps over every Dense layer and every --conv-walk filter Conv2D layer after its walk (DESIGN.md section 12); 0: none")
+    ap.add_argument("--refine-form", choices=("residual", "gram"), default="residual",
+                    help="the refinement sweeps on the residual held on chip (rows of up to 8192 samples), or on the Gram matrix of the "
+                         "layer's inputs (rows of any length; DESIGN.md section 12, addendum)")
     ap.add_argument("--export-packed", default=None, metavar="PATH",
                     help="also write the quantized network in the packed low-bit form (deploy.export_packed; with several settings the "
                          "file holds the last one's)")
@@ -98,7 +101,8 @@ def main():
         get_data = CIFAR10Sequence(X_train[0:params.q_train_size], y_train[0:params.q_train_size], batch_size=16)
         my_quant_net = QuantizedCNN(network=model, batch_size=params.q_train_size, get_data=get_data, logger=quiet,
                                     bits=params.bits, alphabet_scalar=params.alphabet_scalar, radius=args.radius,
-                                    conv_walk=args.conv_walk, conv_columns=args.conv_columns, refine_passes=args.refine_passes)
+                                    conv_walk=args.conv_walk, conv_columns=args.conv_columns, refine_passes=args.refine_passes,
+                                    refine_form=args.refine_form)
         tic = time()
         my_quant_net.quantize_network()
         quantization_time = time() - tic

@@ -60,6 +60,9 @@ def main():
     ap.add_argument("--widths", type=int, nargs="+", default=[500, 300], help="hidden layer widths")
     ap.add_argument("--refine-passes", type=int, default=0, metavar="K",
                     help="up to K refinement sweeps over every Dense layer after its walk (DESIGN.md section 12); 0: none")
+    ap.add_argument("--refine-form", choices=("residual", "gram"), default="residual",
+                    help="the refinement sweeps on the residual held on chip (rows of up to 8192 samples), or on the Gram matrix of the "
+                         "layer's inputs (rows of any length; DESIGN.md section 12, addendum)")
     ap.add_argument("--export-packed", default=None, metavar="PATH",
                     help="also write the quantized network in the packed low-bit form (deploy.export_packed; with several settings the "
                          "file holds the last one's)")
@@ -78,7 +81,7 @@ def main():
         my_quant_net = QuantizedNeuralNetwork(network=model, batch_size=args.samples, get_data=get_data,
                                               logger=type("Quiet", (), {"info": staticmethod(lambda m: None)})(),
                                               bits=params.bits, alphabet_scalar=params.alphabet_scalar, radius=args.radius,
-                                              refine_passes=args.refine_passes)
+                                              refine_passes=args.refine_passes, refine_form=args.refine_form)
         tic = time()
         my_quant_net.quantize_network()
         quantization_time = time() - tic

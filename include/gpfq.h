@@ -542,6 +542,43 @@ int gpfq_refine_neurons(const float *X, const float *Xq, int64_t ld, const float
                         void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Refinement sweeps on Gram matrices (refine_form="gram"; DESIGN.md section 12, addendum): the sweeps of gpfq_refine_neurons written
+ * on h = Xq u (length N) instead of the residual u (length m), so that no row length limits them.  With G = Xq Xq^T (N x N), of one
+ * output channel j, everything float64 and every product, quotient and sum rounded on its own (no fused multiply-add):
+ *   a sweep   for t = 0 .. N-1: nothing happens when nrm32[t] < 1e-16 or k_t = -1; otherwise v = a_{k_t} + h_t / G[t][t],
+ *             k' = the first index of min_k |a_k - v|, and only if |a_k' - v| < |a_{k_t} - v| strictly: delta = a_k' - a_{k_t},
+ *             h_s = h_s - (delta * G[s][t]) for every s, k_t = k'.  Every h_s receives the accepted steps in their order.
+ *   passes    as gpfq_refine_neurons.
+ * In exact arithmetic, with h0 = Xq (X^T w - Xq^T q), these are the decisions of gpfq_refine_neurons.  Given G and h0 every
+ * element's arithmetic is a fixed sequence: the results are bitwise those of a sequential evaluation, on any data.
+ * Outputs: qidx updated in place; Q[t][j] = (float)a_{k_t} (0.0f for -1) for every t; H[j] = the final h; changed[j], sweeps_run[j] as
+ * gpfq_refine_neurons; gain[j] = the sum over the accepted steps, in their order, of G[t][t] * ((a_{k_t} - v)^2 - (a_k' - v)^2): the
+ * decrease of ||u||^2 in exact arithmetic.
+ * One workgroup owns one neuron and keeps its h in registers for the whole call; a wavefront walks 64 steps at a time (a ballot
+ * finds the first lane that accepts; the block is updated from 64 elements of that row of G and the later lanes decide again), the
+ * accepted steps reach the rest of h through LDS.  Only rows of G of accepted steps are read.  One launch, no host synchronisation,
+ * no atomics, nothing exchanged between workgroups.
+ *   G [device] f64 [N][ldg], ldg >= N, SYMMETRIC bit for bit (row t is read where the semantics name column t); H [device] f64
+ *   neuron-major [C][ldh], ldh >= N: h0 in, the final h out; nrm32 [device] f32 [N]; radii [device] f64 [C]; unit_alphabet [host] f64
+ *   [M], 1 <= M <= GPFQ_MAX_ALPHABET, in any order, finite; qidx [device] [N][ldi], ldi >= C: i8 for M <= 64, i16 beyond; an index
+ *   outside [0, M) is treated as -1; Q [device] f32 [N][ldq], ldq >= C, or NULL; changed, sweeps_run [device] i32 [C], gain [device]
+ *   f64 [C]: each may be NULL.
+ * Nothing beyond column N of G / H or column C of qidx / Q is read or written.  sweeps >= 1; N > GPFQ_REFINE_GRAM_MAX_N:
+ * GPFQ_ERR_UNSUPPORTED.  A refused call launches nothing.
+ */
+#define GPFQ_REFINE_GRAM_MAX_N 25600     /* 1024 threads x 25 float64 elements of h per thread (VGG16's fc1: 25088) */
+int gpfq_refine_gram_neurons(const double *G, int64_t ldg,        /* [device] f64 [N][ldg], symmetric */
+                             double *H, int64_t ldh,               /* [device] f64 [C][ldh]: h0 in, final h out */
+                             const float *nrm32,
+                             const double *radii,                  /* [device] f64 [C] */
+                             const double *unit_alphabet, int M,   /* [host] */
+                             int64_t N, int64_t C, int sweeps,
+                             void *qidx, int64_t ldi,              /* [device] Keras layout [N][ldi], updated IN PLACE */
+                             float *Q, int64_t ldq,                /* [device] [N][ldq], may be NULL */
+                             int32_t *changed, int32_t *sweeps_run, double *gain,   /* each may be NULL */
+                             void *stream);
+
+/*
  * median(|W|) of n float32 weights with NumPy's semantics (float32 result; even n -> float32 mean of
  * the two middle values).  Replaces `median(abs(W.flatten()))` of the alphabet radius
  * (scripts/quantized_network.py:544, :831).  Exact radix select, no sort.

@@ -973,6 +973,42 @@ int gpfq_refine_neurons(const float *X, const float *Xq, int64_t ld, const float
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_refine_neurons");
 }
 
+// ---- refinement sweeps on Gram matrices (gpfq_refine_gram.hip, DESIGN.md section 12 addendum) ----
+
+int gpfq_refine_gram_neurons(const double *G, int64_t ldg, double *H, int64_t ldh, const float *nrm32, const double *radii,
+                             const double *unit_alphabet, int M, int64_t N, int64_t C, int sweeps, void *qidx, int64_t ldi, float *Q,
+                             int64_t ldq, int32_t *changed, int32_t *sweeps_run, double *gain, void *stream)
+{
+    if (N < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size N=%lld C=%lld", (long long)N, (long long)C);
+    if (sweeps < 1) return fail(GPFQ_ERR_INVALID_ARG, "sweeps=%d must be >= 1", sweeps);
+    HostAlphabet H_;
+    int rc = make_alphabet(unit_alphabet, M, -1, &H_);
+    if (rc != GPFQ_OK) return rc;
+    if (N > GPFQ_REFINE_GRAM_MAX_N)
+        return fail(GPFQ_ERR_UNSUPPORTED, "refinement on the Gram matrix needs N <= GPFQ_REFINE_GRAM_MAX_N=%d (got %lld)",
+                    GPFQ_REFINE_GRAM_MAX_N, (long long)N);
+    if (C > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "more than 2^31 - 1 neurons in one call");
+    if (C == 0) return GPFQ_OK;
+    if (!radii) return fail(GPFQ_ERR_INVALID_ARG, "radii is NULL");
+    if (N > 0) {
+        if (!G || !H || !nrm32 || !qidx) return fail(GPFQ_ERR_INVALID_ARG, "G/H/nrm32/qidx is NULL");
+        if (ldg < N) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldg=%lld < N=%lld", (long long)ldg, (long long)N);
+        if (ldh < N) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldh=%lld < N=%lld", (long long)ldh, (long long)N);
+        if (ldi < C) return fail(GPFQ_ERR_INVALID_ARG, "index pitch ldi=%lld < C=%lld", (long long)ldi, (long long)C);
+        if (Q && ldq < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldq=%lld < C=%lld", (long long)ldq, (long long)C);
+        if ((uintptr_t)G % 8 != 0 || (uintptr_t)H % 8 != 0) return fail(GPFQ_ERR_INVALID_ARG, "G and H must be 8-byte aligned");
+        if (H_.is_big && (uintptr_t)qidx % 2 != 0) return fail(GPFQ_ERR_INVALID_ARG, "int16 indices must be 2-byte aligned");
+    }
+    gpfq::RefineGramArgs a{};
+    a.G = G; a.ldg = ldg; a.H = H; a.ldh = ldh; a.nrm32 = nrm32; a.radii = radii;
+    a.U.M = M;
+    for (int k = 0; k < M; ++k) a.U.a[k] = unit_alphabet[k];
+    a.N = N; a.C = C; a.sweeps = sweeps; a.qidx = qidx; a.ldi = ldi; a.Q = Q; a.ldq = ldq;
+    a.changed = changed; a.sweeps_run = sweeps_run; a.gain = gain;
+    hipError_t e = gpfq::launch_refine_gram(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_refine_gram_neurons");
+}
+
 size_t gpfq_median_abs_workspace_bytes(void) { return gpfq::median_workspace_bytes() + 64; }
 size_t gpfq_median_abs_workspace_bytes_for(int64_t n) { return n > 0 ? gpfq::median_workspace_bytes_fast(n) : gpfq::median_workspace_bytes() + 64; }
 

@@ -321,6 +321,26 @@ struct RefineArgs {
 size_t refine_workspace_bytes(int64_t N);
 int refine_neurons_per_workgroup(int64_t m);
 hipError_t launch_refine(const RefineArgs &a, hipStream_t stream);
+// gpfq_refine_gram.hip (refine_form="gram", DESIGN.md section 12 addendum): the same sweeps on h = Xq u and the Gram matrix G = Xq Xq^T
+constexpr int kRefineGramMaxN = 25600;           // 1024 threads x 25 elements of h (float64) per thread
+struct RefineGramArgs {
+    const double *G;                             // [N][ldg], symmetric bit for bit
+    int64_t ldg;
+    double *H;                                   // neuron-major [C][ldh]: h0 in, the final h out
+    int64_t ldh;
+    const float *nrm32;
+    const double *radii;                         // [device] f64 [C]
+    AlphabetBig U;                               // the unit alphabet (any M <= 256; int16 indices beyond 64 members)
+    int64_t N, C;
+    int sweeps;
+    void *qidx;                                  // Keras layout [N][ldi], updated in place
+    int64_t ldi;
+    float *Q;                                    // [N][ldq] or NULL
+    int64_t ldq;
+    int32_t *changed, *sweeps_run;               // [C] or NULL
+    double *gain;                                // [C] or NULL
+};
+hipError_t launch_refine_gram(const RefineGramArgs &a, hipStream_t stream);
 size_t median_workspace_bytes();
 size_t median_workspace_bytes_fast(int64_t n);   // ... with room for the one-GPU form's candidate list (gpfq_median_abs_workspace_bytes_for)
 size_t channel_sumsq_workspace_bytes(int64_t Cin);

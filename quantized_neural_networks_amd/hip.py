@@ -24,6 +24,7 @@ GPFQ_LAYOUT_NEURON_MAJOR, GPFQ_LAYOUT_KERAS = 0, 1
 GPFQ_ERR_CLUSTER_TIMEOUT, GPFQ_ERR_ALPHABET = -6, -7
 GPFQ_SEARCH_MAX_CANDIDATES = 16    # candidate scalars of one search (include/gpfq.h)
 GPFQ_REFINE_MAX_M = 8192           # longest row the refinement sweeps take (include/gpfq.h)
+GPFQ_REFINE_GRAM_MAX_N = 25600     # longest walk the refinement sweeps on the Gram matrix take (include/gpfq.h)
 GPFQ_ERR_INVALID_ARG, GPFQ_ERR_UNSUPPORTED, GPFQ_ERR_WORKSPACE = -1, -2, -3
 
 # every symbol include/gpfq.h declares: (restype, argtypes)
@@ -73,6 +74,8 @@ SYMBOLS = {
     "gpfq_refine_neurons_per_workgroup": (_int, [_i64]),
     "gpfq_refine_neurons": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _dp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64,
                                    _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpfq_refine_gram_neurons": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _dp, _int, _i64, _i64, _int, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                        _vp]),
     "gpfq_gram_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "gpfq_quantize_neurons_gram": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _i64, _dp, _int, _int, _i64, _i64, _i64,
                                           _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -976,6 +979,46 @@ def refine_neurons(X, Xq, W, idx, radii, unit_alphabet, sweeps, nrm32=None, want
                                        res["resid_before"].data_ptr(), res["resid_after"].data_ptr(), res["changed"].data_ptr(),
                                        res["sweeps"].data_ptr(), ws.data_ptr() if ws is not None else None, nbytes, _stream()),
                "gpfq_refine_neurons")
+    return res
+
+
+def refine_gram_neurons(G, H, nrm32, idx, radii, unit_alphabet, sweeps, want_values=True, inplace=False, out=None):
+    """Refinement sweeps on the Gram matrix (gpfq_refine_gram_neurons, DESIGN.md section 12 addendum).  G f64 [N][N] (rows of any
+    pitch) = Xq Xq^T, symmetric bit for bit; H f64 [C][N] (rows of any pitch) the start vectors h0 = Xq (X^T w - Xq^T q) of the C
+    neurons, REPLACED by the final h; nrm32 f32 [N]; idx [N][C] the walk's Keras-layout indices (int8; int16 beyond 64 members); radii
+    f64 [C]; unit_alphabet a host sequence.  Returns dict(Q f32 [N][C] or None, idx, H, changed i32 [C], sweeps i32 [C], gain f64 [C]);
+    idx, inplace and out as refine_neurons.  One launch, no sync."""
+    arr, M, _ = _alphabet(unit_alphabet)
+    _dev(G, torch.float64, "G"); _dev(H, torch.float64, "H"); _dev(nrm32, torch.float32, "nrm32")
+    _dev(idx, index_dtype(M), "idx"); _dev(radii, torch.float64, "radii")
+    pg, N, Ng, ldg = _rows(G, "G")
+    if Ng != N:
+        raise GpfqError(f"G {tuple(G.shape)} is not square")
+    ph, C, Nh, ldh = _rows(H, "H")
+    if Nh != N or tuple(idx.shape) != (N, C):
+        raise GpfqError(f"H {tuple(H.shape)} / idx {tuple(idx.shape)} do not match the {N} rows of G")
+    if radii.numel() != C or not radii.is_contiguous():
+        raise GpfqError(f"radii must be a contiguous [{C}] tensor")
+    if nrm32.numel() != N or not nrm32.is_contiguous():
+        raise GpfqError(f"nrm32 must be a contiguous [{N}] tensor")
+    sweeps = int(sweeps)
+    dev = G.device
+    if not inplace:
+        idx = idx.clone(memory_format=torch.contiguous_format)
+    pi, _, _, ldi = _rows(idx, "idx")
+    Q = out if out is not None else (torch.empty((N, C), dtype=torch.float32, device=dev) if want_values else None)
+    pQ, ldQ = (None, 0)
+    if Q is not None:
+        _dev(Q, torch.float32, "out")
+        pQ, Nq_, Cq_, ldQ = _rows(Q, "out")
+        if (Nq_, Cq_) != (N, C):
+            raise GpfqError(f"out must be [{N}][{C}]")
+    res = dict(Q=Q, idx=idx, H=H, changed=torch.empty(C, dtype=torch.int32, device=dev), sweeps=torch.empty(C, dtype=torch.int32, device=dev),
+               gain=torch.empty(C, dtype=torch.float64, device=dev))
+    with torch.cuda.device(dev):
+        _check(load().gpfq_refine_gram_neurons(pg, ldg, ph, ldh, nrm32.data_ptr(), radii.data_ptr(), arr, M, N, C, sweeps, pi, ldi, pQ, ldQ,
+                                               res["changed"].data_ptr(), res["sweeps"].data_ptr(), res["gain"].data_ptr(), _stream()),
+               "gpfq_refine_gram_neurons")
     return res
 
 

@@ -247,36 +247,119 @@ def check_refine(refine, name="refine"):
     return int(refine)
 
 
-def refine_dense(W, X, Xq, idx, radii, unit_alphabet, sweeps):
+REFINE_FORMS = ("residual", "gram")
+_GRAM_CHUNK_ELEMS = 1 << 24        # float64 elements of one operand chunk of the Gram form's products (128 MiB)
+
+
+def check_refine_form(form, name="refine_form"):
+    """The form of the refinement sweeps: "residual" (gpfq_refine_neurons) or "gram" (gpfq_refine_gram_neurons); ValueError otherwise."""
+    if form not in REFINE_FORMS:
+        raise ValueError(f"{name} must be one of {REFINE_FORMS}, got {form!r}")
+    return form
+
+
+def refine_dense(W, X, Xq, idx, radii, unit_alphabet, sweeps, form="residual"):
     """Refinement sweeps after the walk: coordinate descent on the walk's own objective ||X w - Xq q|| over
     the members a_k = radii[j] * unit_alphabet[k] of every neuron's alphabet, started from the walk's indices.
 
     W        f32 [N][C]  the ORIGINAL Keras kernel (not a rescaled W')
-    X, Xq    f32 [N][m]  the rows the walk ran on, m <= hip.GPFQ_REFINE_MAX_M
+    X, Xq    f32 [N][m]  the rows the walk ran on; form="residual": m <= hip.GPFQ_REFINE_MAX_M
     idx      [N][C]      the walk's Keras-layout indices (int8; int16 beyond 64 members); left as it is
     radii    f64 [C]     on the device; a layer radius: the same number C times
     sweeps   >= 1        at most this many sweeps; a neuron whose sweep changed nothing stops
+    form     "residual": the sweeps on the residual held on chip (two launches, no sync).  "gram": the sweeps on h = Xq u and the Gram
+             matrix Xq Xq^T (_refine_dense_gram): rows of any length, N <= hip.GPFQ_REFINE_GRAM_MAX_N
 
-    Returns dict(Q f32 [N][C], idx, resid_before f64 [C], resid_after f64 [C], changed i32 [C], sweeps i32 [C]): the norms are those of
-    the true float64 residual of the installed kernel before / after.  Two launches, no sync."""
+    Returns dict(Q f32 [N][C], idx, resid_before f64 [C], resid_after f64 [C], changed i32 [C], sweeps i32 [C]) -- "gram": + gain f64
+    [C]: the norms are those of the true float64 residual of the installed kernel before / after."""
+    if check_refine_form(form, "form") == "gram":
+        return _refine_dense_gram(W.detach(), X, Xq, idx, radii, unit_alphabet, sweeps)
     r = hip.refine_neurons(X, Xq, W.detach(), idx, radii, unit_alphabet, sweeps)
     return dict(Q=r["Q"], idx=r["idx"], resid_before=r["resid_before"], resid_after=r["resid_after"], changed=r["changed"],
                 sweeps=r["sweeps"])
 
 
-def _refined(out, W, X, Xq, radii, unit, refine, group):
+def _index_values(idx, radii, unit):
+    """f64 [N][C]: a_{k_t} = radii[j] * unit[k] of every index (a float64 product, as the kernels form it); 0 outside the alphabet."""
+    M = unit.numel()
+    k = idx.long()
+    on = (k >= 0) & (k < M)
+    return torch.where(on, radii[None, :] * unit[k.clamp(0, M - 1)], torch.zeros((), dtype=torch.float64, device=idx.device))
+
+
+def _gram_chunks(N, m):
+    """Column ranges of the Gram form's chunked products: at most _GRAM_CHUNK_ELEMS float64 elements per [N][chunk] operand (at
+    least 256 columns)."""
+    step = max(256, _GRAM_CHUNK_ELEMS // max(N, 1))
+    return [(c, min(c + step, m)) for c in range(0, m, step)]
+
+
+def _residual_sumsq(W64, A, X, Xq, G=None, H=None):
+    """Column sums of squares (f64 [C]) of the true residual U = X^T W - Xq^T A, by chunks of columns; on the way, where given,
+    G += Xq Xq^T and H += (Xq U)^T."""
+    N, m = X.shape
+    same = X is Xq
+    D = W64 - A if same else None
+    ss = torch.zeros(W64.shape[1], dtype=torch.float64, device=W64.device)
+    for c0, c1 in _gram_chunks(N, m):
+        q = Xq[:, c0:c1].double()
+        U = q.T @ D if same else X[:, c0:c1].double().T @ W64 - q.T @ A
+        ss += (U * U).sum(0)
+        if G is not None:
+            G.addmm_(q, q.T)
+        if H is not None:
+            H.addmm_(U.T, q.T)
+    return ss
+
+
+def _mirror_upper(G, rows=1024):
+    """G made symmetric bit for bit, in place: the upper triangle copied onto the lower one, `rows` rows at a time."""
+    N = G.shape[0]
+    for r0 in range(0, N, rows):
+        r1 = min(r0 + rows, N)
+        if r0:
+            G[r0:r1, :r0] = G[:r0, r0:r1].T
+        blk = G[r0:r1, r0:r1]
+        blk.copy_(torch.triu(blk) + torch.triu(blk, 1).T)
+    return G
+
+
+def _refine_dense_gram(W, X, Xq, idx, radii, unit_alphabet, sweeps):
+    """refine_dense's form="gram".  The m-long work is float64 matrix products shared by the C neurons: G = Xq Xq^T [N][N], the start
+    vectors H = (Xq (X^T W - Xq^T A))^T [C][N] (A = the values of the walk's indices) and the residual norms before / after, all by
+    chunks of columns (_gram_chunks); X is Xq (the same tensor: a first layer): one product per chunk less.  Memory: G (N^2 f64), H
+    and three more [N][C] f64 matrices (W, A and the products' results), and per chunk two [N][chunk] and one [chunk][C] f64
+    operands, chunk * N <= 2^24 elements (128 MiB each; chunk >= 256).  The norms come from the data, not from the kernel's gain."""
+    N, C = W.shape
+    if N > hip.GPFQ_REFINE_GRAM_MAX_N:
+        raise NotImplementedError(f"refinement sweeps on the Gram matrix take walks of at most GPFQ_REFINE_GRAM_MAX_N = "
+                                  f"{hip.GPFQ_REFINE_GRAM_MAX_N} steps, got {N}")
+    dev = W.device
+    unit = torch.as_tensor(np.asarray(unit_alphabet, dtype=np.float64), device=dev)
+    W64 = W.double()
+    G = torch.zeros((N, N), dtype=torch.float64, device=dev)
+    H = torch.zeros((C, N), dtype=torch.float64, device=dev)
+    before = _residual_sumsq(W64, _index_values(idx, radii, unit), X, Xq, G, H).sqrt_()
+    r = hip.refine_gram_neurons(_mirror_upper(G), H, hip.row_norms(Xq), idx, radii, unit_alphabet, sweeps)
+    del G, H
+    after = _residual_sumsq(W64, _index_values(r["idx"], radii, unit), X, Xq).sqrt_()
+    return dict(Q=r["Q"], idx=r["idx"], resid_before=before, resid_after=after, changed=r["changed"], sweeps=r["sweeps"], gain=r["gain"])
+
+
+def _refined(out, W, X, Xq, radii, unit, refine, group, refine_form="residual"):
     """A dense driver's result with `refine` sweeps applied against the original kernel W: Q and idx replaced, + "refine" =
-    dict(resid_before, resid_after, changed, sweeps).  "resid" stays the walk's."""
+    dict(resid_before, resid_after, changed, sweeps) (refine_form="gram": + gain).  "resid" stays the walk's."""
+    check_refine_form(refine_form)
     if not refine:
         return out
     if _group_info(group)[0] > 1:
         raise NotImplementedError("refinement sweeps are not sharded over a process group yet")
     if W.numel() == 0:
         return out
-    if X.shape[1] > hip.GPFQ_REFINE_MAX_M:
+    if refine_form == "residual" and X.shape[1] > hip.GPFQ_REFINE_MAX_M:
         raise NotImplementedError(f"refinement sweeps take rows of at most GPFQ_REFINE_MAX_M = {hip.GPFQ_REFINE_MAX_M} samples, got "
-                                  f"{X.shape[1]}")
-    r = refine_dense(W, X, Xq, out["idx"], radii, unit, refine)
+                                  f"{X.shape[1]} (refine_form=\"gram\" takes longer rows)")
+    r = refine_dense(W, X, Xq, out["idx"], radii, unit, refine, form=refine_form)
     out["Q"], out["idx"] = r.pop("Q"), r.pop("idx")
     out["refine"] = r
     return out
@@ -291,7 +374,7 @@ def _alphabet_radii(alphabet, C, device):
 
 
 def quantize_dense_layer(W, X, Xq, unit_alphabet, alphabet_scalar, group=None, want_resid=True, log=None, check=True, overlap=False,
-                         kernel_ready=None, refine=0):
+                         kernel_ready=None, refine=0, refine_form="residual"):
     """The body of _quantize_layer_parallel (scripts/quantized_network.py:523-574) from "the activations are there" to the tensors
     set_weights takes, with nothing crossing to the host: median of |W| -> rad * alphabet on the device (:544-545), row norms, record
     pre-pass, the recurrence reading the Keras kernel in place.
@@ -302,8 +385,9 @@ def quantize_dense_layer(W, X, Xq, unit_alphabet, alphabet_scalar, group=None, w
     (Round 6's first scheme -- the pre-pass on the side stream behind a fork wait -- measured a wash and is gone.)
 
     Same tensors as quantize_dense(W, X, Xq, rad * unit_alphabet), bit for bit.  Returns its dict + "alphabet" (the hip.DeviceAlphabet).
-    refine: as quantize_dense."""
+    refine, refine_form: as quantize_dense."""
     refine = check_refine(refine)
+    check_refine_form(refine_form)
     N, C = W.shape
     world, rank = _group_info(group)
     lo, hi = shard_bounds(C, world, rank)
@@ -314,12 +398,14 @@ def quantize_dense_layer(W, X, Xq, unit_alphabet, alphabet_scalar, group=None, w
                                         X, Xq, unit_alphabet, hi - lo)
     else:
         dalpha, ws = layer_alphabet_device(W, unit_alphabet, alphabet_scalar, group), None
-    out = quantize_dense(W, X, Xq, dalpha, group=group, want_resid=want_resid, log=log, check=check, prepared=ws, refine=refine)
+    out = quantize_dense(W, X, Xq, dalpha, group=group, want_resid=want_resid, log=log, check=check, prepared=ws, refine=refine,
+                         refine_form=refine_form)
     out["alphabet"] = dalpha
     return out
 
 
-def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, check=True, prepared=None, refine=0):
+def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, check=True, prepared=None, refine=0,
+                   refine_form="residual"):
     """Quantize every neuron (column) of a Dense kernel.
 
     W        f32 [N][C]  Keras kernel layout (row = input feature), on the GPU
@@ -336,8 +422,10 @@ def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, ch
     carries "workspace" and the caller owes hip.call_status(result) before it trusts Q.
     refine > 0: that many refinement sweeps (refine_dense) follow the walk, against W on the members of `alphabet`; Q and idx are the
     refined ones, "refine" holds dict(resid_before, resid_after, changed, sweeps), "resid" stays the walk's.  0: today's path, untouched.
+    refine_form: refine_dense's form, "residual" or "gram" (the latter: rows of any length, + "gain" in "refine").
     """
     refine = check_refine(refine)
+    check_refine_form(refine_form)
     N, C = W.shape
     m = X.shape[1]
     world, rank = _group_info(group)
@@ -390,7 +478,7 @@ def quantize_dense(W, X, Xq, alphabet, group=None, want_resid=True, log=None, ch
                            block_kernel=lambda a: m > 0 and hip.dense_layer_supported(N, m, max(hi - lo, 1), a.unit))
     if refine:
         radii, unit = _alphabet_radii(alphabet, C, W.device)
-        out = _refined(out, Wc, X, Xq, radii, unit, refine, group)
+        out = _refined(out, Wc, X, Xq, radii, unit, refine, group, refine_form)
     return out
 
 
@@ -621,7 +709,7 @@ def _channel_radii(W2d, alphabet_scalar, scale):
 
 
 def quantize_dense_channels(W, X, Xq, unit_alphabet, alphabet_scalar, group=None, overlap=False, kernel_ready=None, want_resid=True,
-                            log=None, check=True, refine=0):
+                            log=None, check=True, refine=0, refine_form="residual"):
     """quantize_dense with one radius per neuron (radius="channel"): r_j = alphabet_scalar * median(|W[:, j]|) (the layer radius
     where that is not a finite positive number, then 0), the walk run by quantize_dense -- every kernel, fallback and repair as there --
     on W' = float32(W / r_j) with the unit alphabet (a device alphabet of radius 1 up to 64 members), and
@@ -634,6 +722,7 @@ def quantize_dense_channels(W, X, Xq, unit_alphabet, alphabet_scalar, group=None
     Returns quantize_dense's dict with Q, resid as above + "radii" (f64 [C]) and "layer_median" (f32 device scalar).
     refine > 0: refinement sweeps (refine_dense) against the original W -- not W' -- on the members r_j * unit[k]; as quantize_dense."""
     refine = check_refine(refine)
+    check_refine_form(refine_form)
     N, C = W.shape
     world, rank = _group_info(group)
     lo, hi = shard_bounds(C, world, rank)
@@ -651,7 +740,7 @@ def quantize_dense_channels(W, X, Xq, unit_alphabet, alphabet_scalar, group=None
     if "resid" in out:
         out["resid"] = out["resid"] * r
     out["radii"], out["layer_median"] = r, med
-    return _refined(out, Wc, X, Xq, r, unit, refine, group)
+    return _refined(out, Wc, X, Xq, r, unit, refine, group, refine_form)
 
 
 def quantize_conv2d_channels(W, act_w, act_q, unit_alphabet, alphabet_scalar, strides, padding, rate, group=None, want_resid=True,
@@ -730,7 +819,7 @@ def _search_base(W2d, per_layer):
 
 
 def quantize_dense_search(W, X, Xq, unit_alphabet, alphabet_scalars, per="channel", group=None, overlap=False, kernel_ready=None,
-                          log=None, check=True, refine=0):
+                          log=None, check=True, refine=0, refine_form="residual"):
     """quantize_dense with the alphabet scalar SEARCHED over the candidates alphabet_scalars = (s_0 .. s_{K-1}), 1 <= K <= 16: base
     radius b_j = median(|W[:, j]|) (per="channel"; the layer median where that is not finite and positive, then 0) or median(|W|) for
     every j (per="layer"), r_{k,j} = s_k * b_j, and ONE quantize_dense call -- every kernel, fallback and repair as there -- walks the
@@ -753,6 +842,7 @@ def quantize_dense_search(W, X, Xq, unit_alphabet, alphabet_scalars, per="channe
     scalars = check_scalars(alphabet_scalars)
     per_layer = _check_per(per)
     refine = check_refine(refine)
+    check_refine_form(refine_form)
     K = len(scalars)
     N, C = W.shape
     world, rank = _group_info(group)
@@ -791,7 +881,7 @@ def quantize_dense_search(W, X, Xq, unit_alphabet, alphabet_scalars, per="channe
                layer_median=base["med"])
     if len(parts) == 1 and "workspace" in parts[0][0]:
         res["workspace"] = parts[0][0]["workspace"]
-    return _refined(res, Wc, X, Xq, res["radii"], unit, refine, group)
+    return _refined(res, Wc, X, Xq, res["radii"], unit, refine, group, refine_form)
 
 
 def quantize_conv2d_search(W, act_w, act_q, unit_alphabet, alphabet_scalars, strides, padding, rate, per="channel", group=None):
@@ -854,7 +944,7 @@ def _as_filters(out, W, m, total):
 
 
 def quantize_conv2d_filters(W, act_w, act_q, alphabet, strides, padding, rate, columns=8192, seed=0, group=None, want_resid=True, log=None,
-                            refine=0):
+                            refine=0, refine_form="residual"):
     """Quantize a Conv2D kernel filter by filter: filter f is neuron f of the Dense problem (W2, X, Xq) of _filter_rows -- a walk of
     kh*kw*Cin steps over the im2col rows of ALL input channels, where quantize_conv2d walks every (channel, filter) pair on its own.
 
@@ -868,22 +958,24 @@ def quantize_conv2d_filters(W, act_w, act_q, alphabet, strides, padding, rate, c
     "workspace" for a device alphabet).  refine > 0: quantize_dense's refinement sweeps on the gathered columns the walk used
     (columns <= hip.GPFQ_REFINE_MAX_M)."""
     W2, X, Xq, m, total = _filter_rows(W, act_w, act_q, strides, padding, rate, columns, seed)
-    return _as_filters(quantize_dense(W2, X, Xq, alphabet, group=group, want_resid=want_resid, log=log, refine=refine), W, m, total)
+    return _as_filters(quantize_dense(W2, X, Xq, alphabet, group=group, want_resid=want_resid, log=log, refine=refine,
+                                      refine_form=refine_form), W, m, total)
 
 
 def quantize_conv2d_filters_channels(W, act_w, act_q, unit_alphabet, alphabet_scalar, strides, padding, rate, columns=8192, seed=0,
-                                     group=None, want_resid=True, log=None, refine=0):
+                                     group=None, want_resid=True, log=None, refine=0, refine_form="residual"):
     """quantize_conv2d_filters with one radius per filter (radius="channel"): quantize_dense_channels on the rows of _filter_rows (the
     columns of W2 are the filters).  Returns its dict with Q, idx in the kernel's shape + columns, total."""
     W2, X, Xq, m, total = _filter_rows(W, act_w, act_q, strides, padding, rate, columns, seed)
     return _as_filters(quantize_dense_channels(W2, X, Xq, unit_alphabet, alphabet_scalar, group=group, want_resid=want_resid, log=log,
-                                               refine=refine), W, m, total)
+                                               refine=refine, refine_form=refine_form), W, m, total)
 
 
 def quantize_conv2d_filters_search(W, act_w, act_q, unit_alphabet, alphabet_scalars, strides, padding, rate, per="channel", columns=8192,
-                                   seed=0, group=None, log=None, refine=0):
+                                   seed=0, group=None, log=None, refine=0, refine_form="residual"):
     """quantize_conv2d_filters with the alphabet scalar searched per filter (per="channel") or for the layer (per="layer"):
     quantize_dense_search on the rows of _filter_rows.  Returns its dict with Q, idx in the kernel's shape + columns, total."""
     W2, X, Xq, m, total = _filter_rows(W, act_w, act_q, strides, padding, rate, columns, seed)
-    return _as_filters(quantize_dense_search(W2, X, Xq, unit_alphabet, alphabet_scalars, per=per, group=group, log=log, refine=refine),
+    return _as_filters(quantize_dense_search(W2, X, Xq, unit_alphabet, alphabet_scalars, per=per, group=group, log=log, refine=refine,
+                                             refine_form=refine_form),
                        W, m, total)

@@ -158,7 +158,7 @@ def _check_refine_passes(refine_passes, process_group):
 
 
 def _refine_stats(out):
-    """{"refine": lazy dict(resid_before, resid_after, changed, sweeps)} of a refined layer, {} otherwise."""
+    """{"refine": lazy dict(resid_before, resid_after, changed, sweeps; refine_form="gram": + gain)} of a refined layer, {} otherwise."""
     return {"refine": _LazyStats(**out["refine"])} if "refine" in out else {}
 
 
@@ -235,11 +235,12 @@ class QuantizedNeuralNetwork:
 
     def __init__(self, network, batch_size, get_data, mini_batch_size=32, logger=None, ignore_layers=[],
                  bits=np.log2(3), alphabet_scalar=1, *, device=None, process_group=None, fix_partial_batch=False, radius="layer",
-                 refine_passes=0):
+                 refine_passes=0, refine_form="residual"):
         # batch_size and mini_batch_size are accepted and ignored, as in the reference (:371-400):
         # the sample count comes from get_data alone.
         self.radius = _check_radius(radius)
         self.refine_passes = _check_refine_passes(refine_passes, process_group)
+        self.refine_form = _layer.check_refine_form(refine_form)
         self.alphabet_scalars = _scalar_candidates(alphabet_scalar)      # a sequence: search the scalar
         self.get_data = get_data
         self.trained_net = network
@@ -269,15 +270,20 @@ class QuantizedNeuralNetwork:
         self.last_layer_stats = {}          # layer_idx -> dict(rad, alphabet, resid) for inspection/tests
 
     refine_passes = 0
+    refine_form = "residual"
 
     def _refine_kw(self, layer_idx, m=None):
-        """The drivers' refine argument: nothing at all for refine_passes = 0 (today's calls, unchanged)."""
+        """The drivers' refine arguments: nothing at all for refine_passes = 0 (today's calls, unchanged), no refine_form under the
+        default form."""
         if not self.refine_passes:
             return {}
+        if self.refine_form == "gram":                      # (rows of any length)
+            return {"refine": self.refine_passes, "refine_form": "gram"}
         if m is not None and m > hip.GPFQ_REFINE_MAX_M:
             layer = self.trained_net.layers[layer_idx]
             raise NotImplementedError(f"layer {layer_idx} ({getattr(layer, 'name', layer.__class__.__name__)}): refine_passes takes rows "
-                                      f"of at most GPFQ_REFINE_MAX_M = {hip.GPFQ_REFINE_MAX_M} samples, this layer has {m}")
+                                      f"of at most GPFQ_REFINE_MAX_M = {hip.GPFQ_REFINE_MAX_M} samples, this layer has {m} "
+                                      f"(refine_form=\"gram\" takes longer rows)")
         return {"refine": self.refine_passes}
 
     def _log(self, msg):
@@ -809,9 +815,10 @@ class QuantizedCNN(QuantizedNeuralNetwork):
     def __init__(self, network, batch_size, get_data, mini_batch_size=32, logger=None, bits=np.log2(3),
                  alphabet_scalar=1, patch_mini_batch_size=5000, is_quantize_conv2d=True, *,
                  device=None, process_group=None, fix_partial_batch=False, radius="layer", conv_walk="channel", conv_columns=8192,
-                 conv_columns_seed=0, refine_passes=0):
+                 conv_columns_seed=0, refine_passes=0, refine_form="residual"):
         self.radius = _check_radius(radius)
         self.refine_passes = _check_refine_passes(refine_passes, process_group)
+        self.refine_form = _layer.check_refine_form(refine_form)
         self.alphabet_scalars = _scalar_candidates(alphabet_scalar)
         self.conv_walk, self.conv_columns, self.conv_columns_seed = _check_conv_walk(conv_walk, conv_columns, conv_columns_seed)
         self.get_data = get_data
