@@ -421,76 +421,73 @@ def neuron_major(W, lo=0, hi=None):
     return out
 
 
-def quantize_conv_channels(act_w_cm, act_q_cm, Wt_all, alphabet, kernel_size, strides, rate, padding,
-                           idx, Q, resid, unc):
+def conv_geometry(kernel_size, strides, rate, padding):
+    """(kh, kw, sh, sw, rh, rw, same) of a conv layer's Keras arguments, in the order every conv entry point of the library takes them:
+    rate None is (1, 1), and any padding but "same" (in either case) is VALID."""
+    (kh, kw), (sh, sw), (rh, rw) = kernel_size, strides, rate if rate else (1, 1)
+    return int(kh), int(kw), int(sh), int(sw), int(rh), int(rw), str(padding).upper() == "SAME"
+
+
+def _contiguous(what, pairs, name="tensor", plural="tensors"):
+    """Every (tensor, dtype) of `pairs` is a contiguous GPU tensor of that dtype; a None tensor (an optional output) is passed over."""
+    for t, dt in pairs:
+        if t is not None:
+            _dev(t, dt, name)
+            if not t.is_contiguous():
+                raise GpfqError(f"{what} needs contiguous {plural}")
+
+
+def _launch(device, entry, nbytes, *args):
+    """entry(*args, a workspace of nbytes (16 at the least), nbytes, the current stream) of the library on `device`; GpfqError unless
+    the call returns 0."""
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        rc = getattr(load(), entry)(*args, ws.data_ptr(), nbytes, _stream())
+    _check(rc, entry)
+
+
+def quantize_conv_channels(act_w_cm, act_q_cm, Wt_all, alphabet, kernel_size, strides, rate, padding, idx, Q, resid, unc):
     """All channels of a conv layer shard in one library call (gpfq_quantize_conv_channels).
     act_*_cm: channel-major f32 [nch][n][H][W]; Wt_all f32 [nch][F][K]; outputs are caller tensors
-    idx i8 / Q f32 [nch][F][K], resid f64 [nch][F], unc i32 [nch][F].  No sync; returns nothing."""
-    for t, dt in ((act_w_cm, torch.float32), (act_q_cm, torch.float32), (Wt_all, torch.float32),
-                  (idx, index_dtype(len(alphabet))), (Q, torch.float32), (resid, torch.float64), (unc, torch.int32)):
-        if t is None:
-            continue                                  # resid is optional (skips the exact replay)
-        _dev(t, dt, "tensor")
-        if not t.is_contiguous():
-            raise GpfqError("quantize_conv_channels needs contiguous tensors")
+    idx i8 / Q f32 [nch][F][K], resid f64 [nch][F] (None skips the exact replay), unc i32 [nch][F].  No sync; returns nothing."""
+    _contiguous("quantize_conv_channels", ((act_w_cm, torch.float32), (act_q_cm, torch.float32), (Wt_all, torch.float32),
+                                           (idx, index_dtype(len(alphabet))), (Q, torch.float32), (resid, torch.float64), (unc, torch.int32)))
     nch, n, H, W = act_w_cm.shape
-    kh, kw = kernel_size
-    sh, sw = strides
-    rh, rw = rate if rate else (1, 1)
-    same = 1 if str(padding).upper() == "SAME" else 0
+    geo = conv_geometry(kernel_size, strides, rate, padding)
     F, K = Wt_all.shape[1], Wt_all.shape[2]
-    if (tuple(act_q_cm.shape) != (nch, n, H, W) or Wt_all.shape[0] != nch or K != kh * kw or tuple(idx.shape) != (nch, F, K)
+    if (tuple(act_q_cm.shape) != (nch, n, H, W) or Wt_all.shape[0] != nch or K != geo[0] * geo[1] or tuple(idx.shape) != (nch, F, K)
             or tuple(Q.shape) != (nch, F, K) or (resid is not None and tuple(resid.shape) != (nch, F))
             or tuple(unc.shape) != (nch, F)):
         raise GpfqError("quantize_conv_channels: shape mismatch")
     arr, M, zero_idx = _alphabet(alphabet)
-    lib = load()
-    nbytes = lib.gpfq_conv_channels_workspace_bytes(n, H, W, nch, kh, kw, sh, sw, rh, rw, same, F, 0 if resid is None else 1)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=act_w_cm.device)
-    with torch.cuda.device(act_w_cm.device):
-        rc = lib.gpfq_quantize_conv_channels(act_w_cm.data_ptr(), act_q_cm.data_ptr(), n, H, W, nch, kh, kw, sh, sw, rh, rw,
-                                             same, Wt_all.data_ptr(), arr, M, zero_idx, F, idx.data_ptr(), Q.data_ptr(),
-                                             resid.data_ptr() if resid is not None else None, unc.data_ptr(),
-                                             ws.data_ptr(), nbytes, _stream())
-    _check(rc, "gpfq_quantize_conv_channels")
+    nbytes = load().gpfq_conv_channels_workspace_bytes(n, H, W, nch, *geo, F, 0 if resid is None else 1)
+    _launch(act_w_cm.device, "gpfq_quantize_conv_channels", nbytes, act_w_cm.data_ptr(), act_q_cm.data_ptr(), n, H, W, nch, *geo,
+            Wt_all.data_ptr(), arr, M, zero_idx, F, idx.data_ptr(), Q.data_ptr(), resid.data_ptr() if resid is not None else None,
+            unc.data_ptr())
 
 
 def conv_channels_nhwc_supported(n, H, W, nch, kernel_size, strides, rate, padding):
     """Whether quantize_conv_channels_nhwc has a kernel for this layer shape (today: 7 x 7 / stride 2 / VALID, the shift-sum form)."""
-    rh, rw = rate if rate else (1, 1)
-    return bool(load().gpfq_conv_channels_nhwc_supported(int(n), int(H), int(W), int(nch), int(kernel_size[0]), int(kernel_size[1]),
-                                                        int(strides[0]), int(strides[1]), int(rh), int(rw),
-                                                        1 if str(padding).upper() == "SAME" else 0))
+    return bool(load().gpfq_conv_channels_nhwc_supported(int(n), int(H), int(W), int(nch), *conv_geometry(kernel_size, strides, rate, padding)))
 
 
 def quantize_conv_channels_nhwc(act_w, act_q, c_lo, c_hi, Wt_all, alphabet, kernel_size, strides, rate, padding, idx, Q, unc):
     """Channels [c_lo, c_hi) of a conv layer whose kernel reads the NHWC activations itself (gpfq_quantize_conv_channels_nhwc): no
     channel-major copy.  act_* f32 [n][H][W][Cin]; Wt_all f32 [nch][F][K]; outputs are caller tensors idx / Q [nch][F][K],
     unc i32 [nch][F].  No sync; returns nothing."""
-    for t, dt in ((act_w, torch.float32), (act_q, torch.float32), (Wt_all, torch.float32), (idx, index_dtype(len(alphabet))),
-                  (Q, torch.float32), (unc, torch.int32)):
-        _dev(t, dt, "tensor")
-        if not t.is_contiguous():
-            raise GpfqError("quantize_conv_channels_nhwc needs contiguous tensors")
+    _contiguous("quantize_conv_channels_nhwc", ((act_w, torch.float32), (act_q, torch.float32), (Wt_all, torch.float32),
+                                                (idx, index_dtype(len(alphabet))), (Q, torch.float32), (unc, torch.int32)))
     n, H, W, Cin = act_w.shape
     nch = c_hi - c_lo
-    kh, kw = kernel_size
-    sh, sw = strides
-    rh, rw = rate if rate else (1, 1)
-    same = 1 if str(padding).upper() == "SAME" else 0
+    geo = conv_geometry(kernel_size, strides, rate, padding)
     F, K = Wt_all.shape[1], Wt_all.shape[2]
-    if (tuple(act_q.shape) != (n, H, W, Cin) or not 0 <= c_lo <= c_hi <= Cin or Wt_all.shape[0] != nch or K != kh * kw
+    if (tuple(act_q.shape) != (n, H, W, Cin) or not 0 <= c_lo <= c_hi <= Cin or Wt_all.shape[0] != nch or K != geo[0] * geo[1]
             or tuple(idx.shape) != (nch, F, K) or tuple(Q.shape) != (nch, F, K) or tuple(unc.shape) != (nch, F)):
         raise GpfqError("quantize_conv_channels_nhwc: shape mismatch")
     arr, M, zero_idx = _alphabet(alphabet)
-    lib = load()
-    nbytes = lib.gpfq_conv_channels_workspace_bytes(n, H, W, nch, kh, kw, sh, sw, rh, rw, same, F, 0)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=act_w.device)
-    with torch.cuda.device(act_w.device):
-        rc = lib.gpfq_quantize_conv_channels_nhwc(act_w.data_ptr(), act_q.data_ptr(), n, H, W, Cin, c_lo, nch, kh, kw, sh, sw, rh, rw,
-                                                  same, Wt_all.data_ptr(), arr, M, zero_idx, F, idx.data_ptr(), Q.data_ptr(),
-                                                  unc.data_ptr(), ws.data_ptr(), nbytes, _stream())
-    _check(rc, "gpfq_quantize_conv_channels_nhwc")
+    nbytes = load().gpfq_conv_channels_workspace_bytes(n, H, W, nch, *geo, F, 0)
+    _launch(act_w.device, "gpfq_quantize_conv_channels_nhwc", nbytes, act_w.data_ptr(), act_q.data_ptr(), n, H, W, Cin, c_lo, nch, *geo,
+            Wt_all.data_ptr(), arr, M, zero_idx, F, idx.data_ptr(), Q.data_ptr(), unc.data_ptr())
 
 
 def conv3x3_nhwc_supported(n, H, W, nch):
@@ -502,11 +499,8 @@ def quantize_conv3x3_nhwc(act_w, act_q, c_lo, c_hi, Wt_all, alphabet, idx, Q, un
     """Channels [c_lo, c_hi) of a 3 x 3 / stride 1 / SAME conv layer straight from the NHWC activations
     (gpfq_quantize_conv3x3_nhwc): no channel-major copy.  act_* f32 [n][H][W][Cin]; Wt_all f32 [nch][F][9]; outputs are caller
     tensors idx / Q [nch][F][9], unc i32 [nch][F].  No sync; returns nothing."""
-    for t, dt in ((act_w, torch.float32), (act_q, torch.float32), (Wt_all, torch.float32), (idx, index_dtype(len(alphabet))),
-                  (Q, torch.float32), (unc, torch.int32)):
-        _dev(t, dt, "tensor")
-        if not t.is_contiguous():
-            raise GpfqError("quantize_conv3x3_nhwc needs contiguous tensors")
+    _contiguous("quantize_conv3x3_nhwc", ((act_w, torch.float32), (act_q, torch.float32), (Wt_all, torch.float32),
+                                          (idx, index_dtype(len(alphabet))), (Q, torch.float32), (unc, torch.int32)))
     n, H, W, Cin = act_w.shape
     nch = c_hi - c_lo
     F = Wt_all.shape[1]
@@ -514,80 +508,49 @@ def quantize_conv3x3_nhwc(act_w, act_q, c_lo, c_hi, Wt_all, alphabet, idx, Q, un
             or tuple(Q.shape) != (nch, F, 9) or tuple(unc.shape) != (nch, F)):
         raise GpfqError("quantize_conv3x3_nhwc: shape mismatch")
     arr, M, zero_idx = _alphabet(alphabet)
-    lib = load()
-    nbytes = lib.gpfq_conv3x3_nhwc_workspace_bytes(n, H, W, nch, F)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=act_w.device)
-    with torch.cuda.device(act_w.device):
-        rc = lib.gpfq_quantize_conv3x3_nhwc(act_w.data_ptr(), act_q.data_ptr(), n, H, W, Cin, c_lo, nch, Wt_all.data_ptr(), arr, M, zero_idx,
-                                            F, idx.data_ptr(), Q.data_ptr(), unc.data_ptr(), ws.data_ptr(), nbytes, _stream())
-    _check(rc, "gpfq_quantize_conv3x3_nhwc")
+    nbytes = load().gpfq_conv3x3_nhwc_workspace_bytes(n, H, W, nch, F)
+    _launch(act_w.device, "gpfq_quantize_conv3x3_nhwc", nbytes, act_w.data_ptr(), act_q.data_ptr(), n, H, W, Cin, c_lo, nch, Wt_all.data_ptr(),
+            arr, M, zero_idx, F, idx.data_ptr(), Q.data_ptr(), unc.data_ptr())
 
 
 def conv_records_supported(n, H, W, nch, kernel_size, strides, rate, padding):
     """Whether conv_channel_records / conv_channels_from_records have a plane kernel for n images of H x W."""
-    kh, kw = kernel_size
-    sh, sw = strides
-    rh, rw = rate if rate else (1, 1)
-    same = 1 if str(padding).upper() == "SAME" else 0
-    return bool(load().gpfq_conv_records_supported(int(n), int(H), int(W), int(nch), kh, kw, sh, sw, rh, rw, same))
+    return bool(load().gpfq_conv_records_supported(int(n), int(H), int(W), int(nch), *conv_geometry(kernel_size, strides, rate, padding)))
 
 
 def conv_channel_records(act_w_cm, act_q_cm, kernel_size, strides, rate, padding):
     """First half of quantize_conv_channels for column-sharded multi-GPU runs: the Gram records of all channels over
     THESE images (planes f32 [nch][n][H][W]).  Returns (records f64 [nch][K*K*2 + K], negflags i32 [nch]); both are
     summed / maximised over the ranks before conv_channels_from_records.  No sync."""
-    for t in (act_w_cm, act_q_cm):
-        _dev(t, torch.float32, "planes")
-        if not t.is_contiguous():
-            raise GpfqError("conv_channel_records needs contiguous planes")
+    _contiguous("conv_channel_records", ((act_w_cm, torch.float32), (act_q_cm, torch.float32)), "planes", "planes")
     nch, n, H, W = act_w_cm.shape
-    kh, kw = kernel_size
-    sh, sw = strides
-    rh, rw = rate if rate else (1, 1)
-    same = 1 if str(padding).upper() == "SAME" else 0
-    K = kh * kw
-    dev = act_w_cm.device
+    geo = conv_geometry(kernel_size, strides, rate, padding)
+    K, dev = geo[0] * geo[1], act_w_cm.device
     records = torch.zeros((nch, K * K * 2 + K), dtype=torch.float64, device=dev)
     negflags = torch.zeros((nch,), dtype=torch.int32, device=dev)
     if n == 0:
         return records, negflags
-    lib = load()
-    nbytes = lib.gpfq_conv_channels_workspace_bytes(n, H, W, nch, kh, kw, sh, sw, rh, rw, same, 0, 0)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gpfq_conv_channel_records(act_w_cm.data_ptr(), act_q_cm.data_ptr(), n, H, W, nch, kh, kw, sh, sw, rh, rw, same,
-                                           records.data_ptr(), negflags.data_ptr(), ws.data_ptr(), nbytes, _stream())
-    _check(rc, "gpfq_conv_channel_records")
+    nbytes = load().gpfq_conv_channels_workspace_bytes(n, H, W, nch, *geo, 0, 0)
+    _launch(dev, "gpfq_conv_channel_records", nbytes, act_w_cm.data_ptr(), act_q_cm.data_ptr(), n, H, W, nch, *geo, records.data_ptr(),
+            negflags.data_ptr())
     return records, negflags
 
 
-def conv_channels_from_records(records, negflags, act_w_cm, act_q_cm, Wt_all, alphabet, kernel_size, strides, rate, padding,
-                               idx, Q, unc):
+def conv_channels_from_records(records, negflags, act_w_cm, act_q_cm, Wt_all, alphabet, kernel_size, strides, rate, padding, idx, Q, unc):
     """Second half: decide (and repair) all channels from summed records; planes of ALL images.  No sync."""
     nch, n, H, W = act_w_cm.shape
-    kh, kw = kernel_size
-    sh, sw = strides
-    rh, rw = rate if rate else (1, 1)
-    same = 1 if str(padding).upper() == "SAME" else 0
+    geo = conv_geometry(kernel_size, strides, rate, padding)
     F, K = Wt_all.shape[1], Wt_all.shape[2]
-    if (tuple(records.shape) != (nch, K * K * 2 + K) or tuple(negflags.shape) != (nch,) or K != kh * kw
+    if (tuple(records.shape) != (nch, K * K * 2 + K) or tuple(negflags.shape) != (nch,) or K != geo[0] * geo[1]
             or tuple(idx.shape) != (nch, F, K) or tuple(Q.shape) != (nch, F, K) or tuple(unc.shape) != (nch, F)):
         raise GpfqError("conv_channels_from_records: shape mismatch")
-    for t, dt in ((records, torch.float64), (negflags, torch.int32), (act_w_cm, torch.float32), (act_q_cm, torch.float32),
-                  (Wt_all, torch.float32), (idx, index_dtype(len(alphabet))), (Q, torch.float32), (unc, torch.int32)):
-        _dev(t, dt, "tensor")
-        if not t.is_contiguous():
-            raise GpfqError("conv_channels_from_records needs contiguous tensors")
+    _contiguous("conv_channels_from_records", ((records, torch.float64), (negflags, torch.int32), (act_w_cm, torch.float32),
+                                               (act_q_cm, torch.float32), (Wt_all, torch.float32), (idx, index_dtype(len(alphabet))),
+                                               (Q, torch.float32), (unc, torch.int32)))
     arr, M, zero_idx = _alphabet(alphabet)
-    lib = load()
-    nbytes = lib.gpfq_conv_channels_workspace_bytes(n, H, W, nch, kh, kw, sh, sw, rh, rw, same, F, 0)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=act_w_cm.device)
-    with torch.cuda.device(act_w_cm.device):
-        rc = lib.gpfq_quantize_conv_channels_from_records(records.data_ptr(), negflags.data_ptr(), act_w_cm.data_ptr(),
-                                                          act_q_cm.data_ptr(), n, H, W, nch, kh, kw, sh, sw, rh, rw, same,
-                                                          Wt_all.data_ptr(), arr, M, zero_idx, F, idx.data_ptr(), Q.data_ptr(),
-                                                          unc.data_ptr(), ws.data_ptr(), nbytes, _stream())
-    _check(rc, "gpfq_quantize_conv_channels_from_records")
+    nbytes = load().gpfq_conv_channels_workspace_bytes(n, H, W, nch, *geo, F, 0)
+    _launch(act_w_cm.device, "gpfq_quantize_conv_channels_from_records", nbytes, records.data_ptr(), negflags.data_ptr(), act_w_cm.data_ptr(),
+            act_q_cm.data_ptr(), n, H, W, nch, *geo, Wt_all.data_ptr(), arr, M, zero_idx, F, idx.data_ptr(), Q.data_ptr(), unc.data_ptr())
 
 
 class DeviceAlphabet:
@@ -1240,10 +1203,7 @@ def extract_patches(act, channel, kernel_size, strides, rate, padding, out=None)
     if act.dim() != 4 or not act.is_contiguous():
         raise GpfqError("act must be a contiguous NHWC tensor")
     n, H, W, Cin = act.shape
-    kh, kw = kernel_size
-    sh, sw = strides
-    rh, rw = rate if rate else (1, 1)
-    same = str(padding).upper() == "SAME"
+    kh, kw, sh, sw, rh, rw, same = conv_geometry(kernel_size, strides, rate, padding)
     if not same and str(padding).upper() != "VALID":
         raise GpfqError(f"unknown padding {padding!r}")
     oh, ow = patch_out_dim(H, kh, sh, rh, same), patch_out_dim(W, kw, sw, rw, same)

@@ -8,6 +8,8 @@ process group (one process per GPU, backend "nccl" = RCCL over xGMI).  Every ran
 activation matrices and the full analog kernel, quantizes its shard, and ONE all-gather per layer
 reassembles the quantized kernel; there is no other communication.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -502,6 +504,185 @@ def _quantize_conv1x1(W, act_q, alphabet, strides):
     return dict(Q=Q.reshape(1, 1, Cin, F), idx=idx.reshape(1, 1, Cin, F), resid=resid)
 
 
+# What quantize_conv2d decides before it queues anything.  Geometry: kh, kw, K = kh * kw (the length of a pair's walk), sh, sw, rh, rw,
+# same_pad, cols (n * oh * ow, the columns of a channel's patch matrix), conv = (kernel_size, strides, rate, padding) as the binding takes
+# them.  Shard: world, rank, by_channel (the ranks split the channels; else every rank walks all channels for its filters), [c_lo, c_hi),
+# [f_lo, f_hi).  same: act_q is act_w.  form: see _conv_plan; second: what "records" falls to where a rank lacks its kernels.
+_ConvPlan = namedtuple("_ConvPlan", "kh kw K sh sw rh rw same_pad cols conv world rank by_channel c_lo c_hi f_lo f_hi same form second")
+
+
+def _conv_plan(W, act_w, same, alphabet, strides, padding, rate, group, want_resid):
+    """The forms in the order they are tried.  "conv1x1": one MSQ call, not sharded.  "empty": no filter is this rank's.  "loop":
+    patch matrices and one quantize_neurons_checked per channel -- walks beyond GPFQ_GRAM_AUTO_MAX_N steps, and residual norms on patch
+    matrices too short for the whole-shard call's replay to pay.  Everything else is ONE whole-shard Gram call: "planes_filters" (fewer
+    channels than ranks) or, by channel, "nhwc3x3" (3 x 3 / stride 1 / SAME shards of 32+ channels, narrower ones where image groups
+    fill the lanes) and "nhwc" (7 x 7 / stride 2 / VALID, the shift-sum form: ResNet50's conv1), which read the NHWC tensors directly
+    and form no residual norms, else "planes".  (No layer the two NHWC queries take is a "loop" layer.)  Ahead of them all, with fewer
+    channels than ranks, short walks and an image for every rank: "records" -- it needs the ranks' agreement at run time (_agreed_form)."""
+    kh, kw, Cin, F = W.shape
+    conv = ((kh, kw), strides, rate, padding)
+    _, _, sh, sw, rh, rw, same_pad = hip.conv_geometry(*conv)
+    K, (n, H, Wd) = kh * kw, act_w.shape[:3]
+    cols = n * hip.patch_out_dim(H, kh, sh, rh, same_pad) * hip.patch_out_dim(Wd, kw, sw, rw, same_pad)
+    one_by_one = K == 1 and not want_resid
+    world, rank = (1, 0) if one_by_one else _group_info(group)
+    by_channel = Cin >= world
+    (c_lo, c_hi), (f_lo, f_hi) = (shard_bounds(Cin, world, rank), (0, F)) if by_channel else ((0, Cin), shard_bounds(F, world, rank))
+    gram = K <= hip.GPFQ_GRAM_AUTO_MAX_N
+    if one_by_one:
+        form = "conv1x1"
+    elif f_hi <= f_lo:
+        form = "empty"
+    elif not gram or cols <= (hip.GPFQ_GRAM_MIN_M if want_resid else 0):
+        form = "loop"
+    elif not by_channel:
+        form = "planes_filters"
+    elif want_resid or len(alphabet) > hip.GPFQ_MAX_ALPHABET:
+        form = "planes"
+    elif (kh, kw, sh, sw, rh, rw, same_pad) == (3, 3, 1, 1, 1, 1, True) and hip.conv3x3_nhwc_supported(n, H, Wd, c_hi - c_lo):
+        form = "nhwc3x3"
+    elif hip.conv_channels_nhwc_supported(n, H, Wd, c_hi - c_lo, *conv):
+        form = "nhwc"
+    else:
+        form = "planes"
+    records = not by_channel and not want_resid and gram and n >= world
+    return _ConvPlan(kh, kw, K, sh, sw, rh, rw, same_pad, cols, conv, world, rank, by_channel, c_lo, c_hi, f_lo, f_hi, same,
+                     "records" if records else form, form)
+
+
+class _ConvPatches:
+    """The one source of a quantize_conv2d call's channel planes and patch matrices.  The channel-major copies [nch][n][H][W] of this
+    rank's channels are formed lazily and at most once (one transposing pass per activation tensor: a channel's gather then reads
+    contiguous planes instead of one float out of every Cin); the NHWC forms have none: their (rare) reruns slice that channel alone
+    out of the NHWC tensors.  The patch matrices [K][cols] are allocated for the first channel asked for and reused for the others."""
+
+    def __init__(self, plan, act_w, act_q):
+        self.plan, self.act = plan, (act_w, act_q)
+        self.cm = self.Pw = self.Pq = None
+
+    def planes(self):
+        if self.cm is None:
+            w = hip.channel_planes(self.act[0], self.plan.c_lo, self.plan.c_hi)
+            self.cm = (w, w if self.plan.same else hip.channel_planes(self.act[1], self.plan.c_lo, self.plan.c_hi))
+        return self.cm
+
+    def _channel(self, which, c):
+        if self.plan.form in ("nhwc3x3", "nhwc"):
+            return self.act[which][..., c:c + 1].contiguous()
+        return self.planes()[which][c - self.plan.c_lo].unsqueeze(-1)
+
+    def of(self, c):
+        """(Pw, Pq) of channel c, valid until the next call."""
+        self.Pw = hip.extract_patches(self._channel(0, c), 0, *self.plan.conv, out=self.Pw)
+        self.Pq = self.Pw if self.plan.same else hip.extract_patches(self._channel(1, c), 0, *self.plan.conv, out=self.Pq)
+        return self.Pw, self.Pq
+
+
+def _agreed_form(plan, patches, group):
+    """(the form the layer takes, the summed records or None).  Only "records" is open at run time.  Fewer input channels than ranks
+    (an image input has 3): the Gram records are sums over the patch columns, so every rank forms them over its share of the IMAGES,
+    one all-reduce of Cin * (2 K^2 + K) doubles sums them, and every rank finishes (decide + repair, milliseconds) from the same
+    records -- no gather afterwards; certified decisions do not depend on the summation order.  Both phases must have a kernel for
+    their shape (the first sees this rank's images, the second all of them): all ranks agree on that first, and take plan.second if not."""
+    if plan.form != "records":
+        return plan.form, None
+    import torch.distributed as dist
+    act_w, act_q = patches.act
+    n, H, Wd, Cin = act_w.shape
+    n_lo, n_hi = shard_bounds(n, plan.world, plan.rank)
+    try:
+        pw = hip.channel_planes(act_w[n_lo:n_hi].contiguous(), 0, Cin)
+        pq = pw if plan.same else hip.channel_planes(act_q[n_lo:n_hi].contiguous(), 0, Cin)
+        rec, neg = hip.conv_channel_records(pw, pq, *plan.conv)
+        supported = 1 if hip.conv_records_supported(n, H, Wd, Cin, *plan.conv) else 0
+    except hip.GpfqError:                                           # (a rank that failed here still enters the all-reduce, and loses)
+        supported = 0
+    ok = torch.tensor([supported], dtype=torch.int32, device=act_w.device)
+    dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=group)          # all ranks take the same branch
+    if not int(ok.item()):
+        return plan.second, None
+    dist.all_reduce(rec, op=dist.ReduceOp.SUM, group=group)
+    dist.all_reduce(neg, op=dist.ReduceOp.MAX, group=group)
+    return "records", (rec, neg)
+
+
+def _walk_conv_shard(form, records, plan, patches, Wt_all, alphabet, want_resid, Qc, Ic, Rc):
+    """This rank's (channel, filter) pairs through `form`, written into Qc / Ic [Cin][F][K] and Rc [Cin][F].  Returns the flags
+    int32 [Cin][F] of the pairs a whole-shard call could not certify (_rerun_flagged), None from the forms that have none.  A
+    whole-shard call is the channel loop (:844-860) in one library call: no per-channel allocation, Python or sync."""
+    p, f = plan, slice(plan.f_lo, plan.f_hi)
+    if form == "empty":
+        return None
+    if form == "loop":
+        for c in range(p.c_lo, p.c_hi):
+            r = quantize_neurons_checked(*patches.of(c), Wt_all[c, f], alphabet)
+            Qc[c, f], Ic[c, f], Rc[c, f] = r["Q"], r["idx"], r["resid"]
+        return None
+    (Cin, F), dev, c = Wt_all.shape[:2], Wt_all.device, slice(p.c_lo, p.c_hi)
+    Unc = torch.zeros((Cin, F), dtype=torch.int32, device=dev)
+    if form == "records":
+        hip.conv_channels_from_records(*records, *patches.planes(), Wt_all, alphabet, *p.conv, Ic, Qc, Unc)
+    elif form == "nhwc3x3":
+        hip.quantize_conv3x3_nhwc(*patches.act, p.c_lo, p.c_hi, Wt_all[c], alphabet, Ic[c], Qc[c], Unc[c])
+    elif form == "nhwc":
+        hip.quantize_conv_channels_nhwc(*patches.act, p.c_lo, p.c_hi, Wt_all[c], alphabet, *p.conv, Ic[c], Qc[c], Unc[c])
+    elif form == "planes":
+        hip.quantize_conv_channels(*patches.planes(), Wt_all[c], alphabet, *p.conv, Ic[c], Qc[c], Rc[c] if want_resid else None, Unc[c])
+    else:                                      # "planes_filters": every rank walks all channels for its filters
+        Wt_f = Wt_all[:, f].contiguous()
+        i_f = torch.empty((Cin, p.f_hi - p.f_lo, p.K), dtype=Ic.dtype, device=dev)
+        q_f = torch.empty((Cin, p.f_hi - p.f_lo, p.K), dtype=torch.float32, device=dev)
+        r_f = torch.full((Cin, p.f_hi - p.f_lo), float("nan"), dtype=torch.float64, device=dev)
+        u_f = torch.empty((Cin, p.f_hi - p.f_lo), dtype=torch.int32, device=dev)
+        hip.quantize_conv_channels(*patches.planes(), Wt_f, alphabet, *p.conv, i_f, q_f, r_f if want_resid else None, u_f)
+        Ic[:, f], Qc[:, f], Rc[:, f], Unc[:, f] = i_f, q_f, r_f, u_f
+    return Unc
+
+
+def _rerun_flagged(Unc, patches, Wt_all, alphabet, Qc, Ic, Rc):
+    """The (channel, filter) pairs the Gram path left flagged, through the verbatim flow on the channel's patch matrices: ONE
+    exact call per CHANNEL for all its flagged filters (round 5).  Normally about one pair in 10^4; but where the quantized
+    network's activations have drifted orders of magnitude away from the analog ones (the last blocks of a 50-layer network
+    whose 1 x 1 layers are plain MSQ: ResNet50's conv5_block3_2_conv flagged 179 000 of its 262 144 pairs) the prediction's
+    bound is wider than the alphabet's spacing for most walks -- one call per PAIR was 33 s of launches for that layer.  Returns
+    the number of pairs; Rc None: their residual norms are not kept."""
+    flagged = torch.nonzero(Unc)                                   # one sync per layer
+    if flagged.numel() == 0:
+        return 0
+    by_c = {}
+    for c, f in flagged.tolist():
+        by_c.setdefault(c, []).append(f)
+    for c, fs in by_c.items():
+        Pw, Pq = patches.of(c)
+        fsel = torch.tensor(fs, dtype=torch.long, device=Unc.device)
+        path = hip.GPFQ_PATH_ONCHIP if Pw.shape[1] <= hip.GPFQ_ONCHIP_MAX_M else hip.GPFQ_PATH_STREAM
+        r = quantize_neurons_checked(Pw, Pq, Wt_all[c].index_select(0, fsel).contiguous(), alphabet, path=path)     # (rows of up to 28672 samples: possibly the cluster form)
+        Qc[c, fsel], Ic[c, fsel] = r["Q"], r["idx"]
+        if Rc is not None:
+            Rc[c, fsel] = r["resid"]
+    return int(flagged.shape[0])
+
+
+def _gather_conv_kernel(Ic, Rc, want_resid, plan, alphabet, group):
+    """(Q, idx [kh][kw][Cin][F], resid [Cin][F]) on every rank from the ranks' shards of Ic [Cin][F][K] and Rc [Cin][F]; a shard's unit
+    is the channel, or the filter where the filters are split.  ONE all-gather of the packed alphabet indices ((unit, other) pairs are
+    rows of K weights; a shard may be empty); the float32 values never travel: every rank looks them up while laying the kernel out
+    ([K][pairs] is [kh][kw][unit][other]).  Residual norms: a second all-gather where they are wanted, this rank's own where not."""
+    p, (Cin, F, K) = plan, Ic.shape
+    if p.by_channel:                           # shard(t): this rank's units of t in front; back(t): [..][unit][other] as [..][Cin][F]
+        units, other, shard, back = Cin, F, (lambda t: t[p.c_lo:p.c_hi]), (lambda t: t)
+    else:
+        units, other, shard, back = F, Cin, (lambda t: t[:, p.f_lo:p.f_hi].transpose(0, 1)), (lambda t: t.transpose(-2, -1))
+    local = shard(Ic)
+    packed, bits = hip.pack_indices(local.reshape(-1, K).contiguous(), len(alphabet))
+    g = all_gather_units(packed.reshape(local.shape[0], other * packed.shape[1]), units, group)
+    Qk, Ik = hip.assemble_kernel(g.reshape(units * other, packed.shape[1]).contiguous(), alphabet, bits=bits, N=K)
+    Q, idx = (back(t.reshape(p.kh, p.kw, units, other)).contiguous() for t in (Qk, Ik))
+    if not want_resid:
+        return Q, idx, Rc
+    return Q, idx, back(all_gather_units(shard(Rc).contiguous(), units, group))
+
+
 def quantize_conv2d(W, act_w, act_q, alphabet, strides, padding, rate, group=None, want_resid=True):
     """Quantize a Conv2D / DepthwiseConv2D kernel channel by channel.
 
@@ -512,172 +693,29 @@ def quantize_conv2d(W, act_w, act_q, alphabet, strides, padding, rate, group=Non
     Gram records are formed over image shards and all-reduced (or, where that does not apply, the filters of each
     channel are partitioned instead).  Sharded runs exchange ONE all-gather per layer: the alphabet indices of the
     rank's (channel, filter) pairs, packed to 2 / 4 bits per weight as the dense path's are; values are looked up
-    locally (+ one all-gather of the residual norms when they are requested).
+    locally (+ one all-gather of the residual norms when they are requested).  _conv_plan names the forms a layer can take.
 
-    Returns dict(Q f32 [kh][kw][Cin][F], idx i8 same shape, resid f64 [Cin][F]).
+    Returns dict(Q f32 [kh][kw][Cin][F], idx i8 same shape, resid f64 [Cin][F], reruns: this rank's pairs rerun through the exact path).
     """
-    kh, kw, Cin, F = W.shape
-    K = kh * kw
-    dev = W.device
-    if K == 1 and not want_resid:
+    (kh, kw, Cin, F), dev = W.shape, W.device
+    plan = _conv_plan(W, act_w, act_q is act_w, alphabet, strides, padding, rate, group, want_resid)
+    if plan.form == "conv1x1":
         return _quantize_conv1x1(W, act_q, alphabet, strides)
-    world, rank = _group_info(group)
-    by_channel = Cin >= world
-    Qc = torch.zeros((Cin, F, K), dtype=torch.float32, device=dev)
-    Ic = torch.zeros((Cin, F, K), dtype=hip.index_dtype(len(alphabet)), device=dev)
+    Qc = torch.zeros((Cin, F, plan.K), dtype=torch.float32, device=dev)
+    Ic = torch.zeros((Cin, F, plan.K), dtype=hip.index_dtype(len(alphabet)), device=dev)
     Rc = torch.full((Cin, F), 0.0 if want_resid else float("nan"), dtype=torch.float64, device=dev)
-    c_lo, c_hi = shard_bounds(Cin, world, rank) if by_channel else (0, Cin)
-    f_lo, f_hi = (0, F) if by_channel else shard_bounds(F, world, rank)
-    Pw = Pq = None
-    reruns = 0                                 # filters of this rank rerun through the exact path (diagnostics)
-    # channel-major copies [Cin][n][H][W] of this rank's channels: the per-channel gather then reads
-    # contiguous planes instead of one float out of every Cin (one transposing pass per layer)
-    same = act_q is act_w
     act_w = act_w.contiguous()
-    act_q = act_w if same else act_q.contiguous()
-    # 3 x 3 / stride 1 / SAME shards of 32+ channels (narrower ones where image groups fill the lanes) read the NHWC tensors directly; everything else goes through the planes
-    nhwc = (not want_resid and by_channel and (kh, kw) == (3, 3) and tuple(strides) == (1, 1) and tuple(rate or (1, 1)) == (1, 1)
-            and str(padding).upper() == "SAME" and len(alphabet) <= hip.GPFQ_MAX_ALPHABET
-            and hip.conv3x3_nhwc_supported(act_w.shape[0], act_w.shape[1], act_w.shape[2], c_hi - c_lo))
-    # ... and so do the layers of the 7 x 7 / stride 2 / VALID shift-sum form (ResNet50's conv1): its requests gather the bands out of the
-    # interleaved rows
-    nhwc_any = (not nhwc and not want_resid and by_channel and len(alphabet) <= hip.GPFQ_MAX_ALPHABET
-                and hip.conv_channels_nhwc_supported(act_w.shape[0], act_w.shape[1], act_w.shape[2], c_hi - c_lo, (kh, kw), strides,
-                                                     rate, padding))
-    cm = {}
-
-    def planes():
-        if not cm:
-            cm["w"] = hip.channel_planes(act_w, c_lo, c_hi)
-            cm["q"] = cm["w"] if same else hip.channel_planes(act_q, c_lo, c_hi)
-        return cm["w"], cm["q"]
-
-    def patches(c):
-        nonlocal Pw, Pq
-        if nhwc or nhwc_any:                                           # (rare reruns: that channel's slice alone)
-            Pw = hip.extract_patches(act_w[..., c:c + 1].contiguous(), 0, (kh, kw), strides, rate, padding, out=Pw)
-            Pq = Pw if same else hip.extract_patches(act_q[..., c:c + 1].contiguous(), 0, (kh, kw), strides, rate, padding, out=Pq)
-            return
-        cm_w, cm_q = planes()
-        Pw = hip.extract_patches(cm_w[c - c_lo].unsqueeze(-1), 0, (kh, kw), strides, rate, padding, out=Pw)
-        Pq = Pw if same else hip.extract_patches(cm_q[c - c_lo].unsqueeze(-1), 0, (kh, kw), strides, rate, padding, out=Pq)
-
-    def rerun_flagged(Unc, with_resid):
-        """The (channel, filter) pairs the Gram path left flagged, through the verbatim flow on the channel's patch matrices: ONE
-        exact call per CHANNEL for all its flagged filters (round 5).  Normally about one pair in 10^4; but where the quantized
-        network's activations have drifted orders of magnitude away from the analog ones (the last blocks of a 50-layer network
-        whose 1 x 1 layers are plain MSQ: ResNet50's conv5_block3_2_conv flagged 179 000 of its 262 144 pairs) the prediction's
-        bound is wider than the alphabet's spacing for most walks -- one call per PAIR was 33 s of launches for that layer."""
-        flagged = torch.nonzero(Unc)                                   # one sync per layer
-        if flagged.numel() == 0:
-            return 0
-        by_c = {}
-        for c, f in flagged.tolist():
-            by_c.setdefault(c, []).append(f)
-        for c, fs in by_c.items():
-            patches(c)
-            fsel = torch.tensor(fs, dtype=torch.long, device=dev)
-            path = hip.GPFQ_PATH_ONCHIP if Pw.shape[1] <= hip.GPFQ_ONCHIP_MAX_M else hip.GPFQ_PATH_STREAM
-            r = quantize_neurons_checked(Pw, Pq, Wt_all[c].index_select(0, fsel).contiguous(), alphabet, path=path)     # (rows of up to 28672 samples: possibly the cluster form)
-            Qc[c, fsel], Ic[c, fsel] = r["Q"], r["idx"]
-            if with_resid:
-                Rc[c, fsel] = r["resid"]
-        return int(flagged.shape[0])
-
+    patches = _ConvPatches(plan, act_w, act_w if plan.same else act_q.contiguous())
     # neuron-major filters [Cin][F][K]: row-major flattening of each kh x kw filter (:215), t = ky*kw + kx
-    Wt_all = W.permute(2, 3, 0, 1).reshape(Cin, F, K).contiguous()
-    rh, rw = rate if rate else (1, 1)
-    same_pad = str(padding).upper() == "SAME"
-    cols = (act_w.shape[0] * hip.patch_out_dim(act_w.shape[1], kh, strides[0], rh, same_pad)
-            * hip.patch_out_dim(act_w.shape[2], kw, strides[1], rw, same_pad))
-    replicated = False                         # every rank already holds the whole result (column-sharded records)
-    if not by_channel and not want_resid and K <= hip.GPFQ_GRAM_AUTO_MAX_N and act_w.shape[0] >= world:
-        # Fewer input channels than ranks (an image input has 3): the Gram records are sums over the patch columns, so
-        # every rank forms them over its share of the IMAGES, one all-reduce of Cin * (2 K^2 + K) doubles sums them,
-        # and every rank finishes (decide + repair, milliseconds) from the same records -- no gather afterwards.
-        # Certified decisions do not depend on the summation order of the records.  Both phases must have a kernel
-        # for their shape (the first sees this rank's images, the second all of them): all ranks agree on that first.
-        import torch.distributed as dist
-        n_lo, n_hi = shard_bounds(act_w.shape[0], world, rank)
-        rec = neg = None
-        try:
-            pw = hip.channel_planes(act_w[n_lo:n_hi].contiguous(), 0, Cin)
-            pq = pw if same else hip.channel_planes(act_q[n_lo:n_hi].contiguous(), 0, Cin)
-            rec, neg = hip.conv_channel_records(pw, pq, (kh, kw), strides, rate, padding)
-            supported = 1 if hip.conv_records_supported(act_w.shape[0], act_w.shape[1], act_w.shape[2], Cin, (kh, kw), strides,
-                                                        rate, padding) else 0
-        except hip.GpfqError:
-            supported = 0
-        if rec is None:
-            rec = torch.zeros((Cin, K * K * 2 + K), dtype=torch.float64, device=dev)
-            neg = torch.zeros((Cin,), dtype=torch.int32, device=dev)
-        ok = torch.tensor([supported], dtype=torch.int32, device=dev)
-        dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=group)          # all ranks take the same branch
-        if int(ok.item()):
-            dist.all_reduce(rec, op=dist.ReduceOp.SUM, group=group)
-            dist.all_reduce(neg, op=dist.ReduceOp.MAX, group=group)
-            Unc = torch.zeros((Cin, F), dtype=torch.int32, device=dev)
-            hip.conv_channels_from_records(rec, neg, *planes(), Wt_all, alphabet, (kh, kw), strides, rate, padding, Ic, Qc, Unc)
-            reruns += rerun_flagged(Unc, False)                            # the same (rare) pairs on every rank
-            replicated = True
-    # the whole-shard Gram call for every conv layer (one launch chain instead of a Python loop over the
-    # channels); with residual norms requested it builds patch matrices, which only pays for long ones
-    whole_shard = K <= hip.GPFQ_GRAM_AUTO_MAX_N and cols > (hip.GPFQ_GRAM_MIN_M if want_resid else 0)
-    if replicated or f_hi <= f_lo:
-        pass
-    elif whole_shard:
-        # Gram path, the whole channel loop (:844-860) in one library call: no per-channel allocation,
-        # Python or sync; the filters whose decision chain could not be certified are collected once
-        Unc = torch.zeros((Cin, F), dtype=torch.int32, device=dev)
-        if (f_lo, f_hi) == (0, F) and nhwc:
-            hip.quantize_conv3x3_nhwc(act_w, act_q, c_lo, c_hi, Wt_all[c_lo:c_hi], alphabet, Ic[c_lo:c_hi], Qc[c_lo:c_hi], Unc[c_lo:c_hi])
-        elif (f_lo, f_hi) == (0, F) and nhwc_any:
-            hip.quantize_conv_channels_nhwc(act_w, act_q, c_lo, c_hi, Wt_all[c_lo:c_hi], alphabet, (kh, kw), strides, rate, padding,
-                                            Ic[c_lo:c_hi], Qc[c_lo:c_hi], Unc[c_lo:c_hi])
-        elif (f_lo, f_hi) == (0, F):
-            hip.quantize_conv_channels(*planes(), Wt_all[c_lo:c_hi], alphabet, (kh, kw), strides, rate, padding,
-                                       Ic[c_lo:c_hi], Qc[c_lo:c_hi], Rc[c_lo:c_hi] if want_resid else None, Unc[c_lo:c_hi])
-        else:                                  # filters split over ranks (Cin < world): every rank walks all channels
-            Wt_f = Wt_all[:, f_lo:f_hi].contiguous()
-            i_f = torch.empty((Cin, f_hi - f_lo, K), dtype=hip.index_dtype(len(alphabet)), device=dev)
-            q_f = torch.empty((Cin, f_hi - f_lo, K), dtype=torch.float32, device=dev)
-            r_f = torch.full((Cin, f_hi - f_lo), float("nan"), dtype=torch.float64, device=dev)
-            u_f = torch.empty((Cin, f_hi - f_lo), dtype=torch.int32, device=dev)
-            hip.quantize_conv_channels(*planes(), Wt_f, alphabet, (kh, kw), strides, rate, padding, i_f, q_f,
-                                       r_f if want_resid else None, u_f)
-            Ic[:, f_lo:f_hi], Qc[:, f_lo:f_hi], Rc[:, f_lo:f_hi], Unc[:, f_lo:f_hi] = i_f, q_f, r_f, u_f
-        reruns = rerun_flagged(Unc, True)                             # one sync per layer; ~1 filter in 10^4
+    Wt_all = W.permute(2, 3, 0, 1).reshape(Cin, F, plan.K).contiguous()
+    form, records = _agreed_form(plan, patches, group)
+    Unc = _walk_conv_shard(form, records, plan, patches, Wt_all, alphabet, want_resid, Qc, Ic, Rc)
+    replicated = form == "records"             # every rank already holds the whole result; its residual norms are left unformed
+    reruns = 0 if Unc is None else _rerun_flagged(Unc, patches, Wt_all, alphabet, Qc, Ic, None if replicated else Rc)
+    if plan.world > 1 and not replicated:
+        Q, idx, Rc = _gather_conv_kernel(Ic, Rc, want_resid, plan, alphabet, group)
     else:
-        for c in range(c_lo, c_hi):
-            patches(c)
-            r = quantize_neurons_checked(Pw, Pq, Wt_all[c, f_lo:f_hi], alphabet)
-            Qc[c, f_lo:f_hi] = r["Q"]
-            Ic[c, f_lo:f_hi] = r["idx"]
-            Rc[c, f_lo:f_hi] = r["resid"]
-    if world > 1 and not replicated:
-        # ONE all-gather of the packed alphabet indices ((channel, filter) pairs are rows of K weights); the float32
-        # values never travel: every rank looks them up while laying the kernel out ([K][pairs] is Keras' [kh][kw][Cin][F])
-        if by_channel:
-            rows = Ic[c_lo:c_hi].reshape(-1, K).contiguous()                       # (c, f) rows of this rank's channels
-            packed, bits = hip.pack_indices(rows, len(alphabet))
-            g = all_gather_units(packed.reshape(c_hi - c_lo, F * packed.shape[1]), Cin, group)   # units = channels (a shard may be empty)
-            Qk, Ik = hip.assemble_kernel(g.reshape(Cin * F, packed.shape[1]).contiguous(), alphabet, bits=bits, N=K)
-            Q = Qk.reshape(kh, kw, Cin, F)
-            idx = Ik.reshape(kh, kw, Cin, F)
-            if want_resid:
-                Rc = all_gather_units(Rc[c_lo:c_hi].contiguous(), Cin, group)
-        else:
-            rows = Ic[:, f_lo:f_hi].transpose(0, 1).reshape(-1, K).contiguous()    # (f, c) rows of this rank's filters
-            packed, bits = hip.pack_indices(rows, len(alphabet))
-            g = all_gather_units(packed.reshape(f_hi - f_lo, Cin * packed.shape[1]), F, group)   # units = filters
-            Qk, Ik = hip.assemble_kernel(g.reshape(F * Cin, packed.shape[1]).contiguous(), alphabet, bits=bits, N=K)
-            Q = Qk.reshape(kh, kw, F, Cin).permute(0, 1, 3, 2).contiguous()
-            idx = Ik.reshape(kh, kw, F, Cin).permute(0, 1, 3, 2).contiguous()
-            if want_resid:
-                Rc = all_gather_units(Rc[:, f_lo:f_hi].transpose(0, 1).contiguous(), F, group).transpose(0, 1)
-        return dict(Q=Q, idx=idx, resid=Rc.contiguous(), reruns=torch.tensor(reruns))
-    Q = Qc.reshape(Cin, F, kh, kw).permute(2, 3, 0, 1).contiguous()
-    idx = Ic.reshape(Cin, F, kh, kw).permute(2, 3, 0, 1).contiguous()
+        Q, idx = (t.reshape(Cin, F, kh, kw).permute(2, 3, 0, 1).contiguous() for t in (Qc, Ic))
     return dict(Q=Q, idx=idx, resid=Rc.contiguous(), reruns=torch.tensor(reruns))
 
 
