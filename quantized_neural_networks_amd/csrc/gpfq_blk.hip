@@ -476,11 +476,17 @@ struct BlkK {
 // kTop3Ship: which of the slot-top pieces of the symmetric eleven-wavefront shapes are issued from inside the pair loop (blk_sweep_role,
 // kLateHdr / kLateW): bit 0 the header piece, bit 1 the weight piece.  A diagnostic build can choose another set (-DGPFQ_BLK_TOP3=n).
 constexpr int kTop3Ship = 3;
+// kPkAheadShip: the pair loop of the eight-group shapes under a symmetric alphabet (blk_sweep_role, kRows2 / kPkA): bit 0 the operand
+// rows requested two pair-steps ahead, bit 1 the float32 products of the next pair-step formed among the conversions and additions of
+// the current one (needs bit 0).  Both ship; bit 0 alone measured SLOWER than neither (profiles/pk_ahead/README.md).
+// -DGPFQ_BLK_PK_AHEAD=n builds another set.
+constexpr int kPkAheadShip = 3;
 #ifdef GPFQ_BLK_DIAG
 #include "gpfq_blk_diag.hpp"
 #else
 constexpr bool kNoMfmaD = false, kNoFused = false;
 constexpr int kTop3 = kTop3Ship;
+constexpr int kPkAhead = kPkAheadShip;
 #define STAMP(var) do { } while (0)
 #define STAMP_DO(...)
 #endif
@@ -990,6 +996,45 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                 for (int n = 0; n < NL; ++n) { u[n][4 * P + 2 * h] += c0[h][n]; u[n][4 * P + 2 * h + 1] += c1[h][n]; }
         };
         (void)update_unit2;
+        // (kPkA) update_unit2 in two parts, so that the packed float32 third of a pair-step's flow is issued among the FP64-rate two thirds
+        // of the pair-step before instead of as a run of its own (measured in the kernel: profiles/pk_ahead/README.md; the
+        // micro-benchmark tools/ubench/pair_step_order.hip does not show it).  unit2_products: the four v_pk_mul_f32 and four v_pk_fma_f32 of a pair-step, into dd.
+        // unit2_accumulate_ahead: the conversions and additions of the pair-step whose products dd holds, and -- nxt -- the products
+        // of the NEXT pair-step behind them, one packed instruction per two FP64-rate ones: (cvt cvt mul) x 4, (add add fma) x 4, each
+        // product formed in the registers its conversions have just read.  Every dependence is at least eleven instructions long.  The
+        // instructions, their operands and their roundings are update_unit2's; sched_barrier holds the order of the groups.
+        auto unit2_products = [&](pk2 (&dd)[2][NL], const float4 &x4, const float4 &q4, const float2 (&wq)[NL]) {
+            const pk2 xv[2] = {{x4.x, x4.y}, {x4.z, x4.w}}, qx[2] = {{q4.x, q4.y}, {q4.z, q4.w}};
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int n = 0; n < NL; ++n) dd[h][n] = pk2{wq[n].x, wq[n].x} * xv[h];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int n = 0; n < NL; ++n) dd[h][n] = __builtin_elementwise_fma(pk2{wq[n].y, wq[n].y}, qx[h], dd[h][n]);
+        };
+        auto unit2_accumulate_ahead = [&](int P, pk2 (&dd)[2][NL], bool nxt, const float4 &x4, const float4 &q4, const float2 (&wq)[NL]) {
+            const pk2 xv[2] = {{x4.x, x4.y}, {x4.z, x4.w}}, qx[2] = {{q4.x, q4.y}, {q4.z, q4.w}};
+            double c0[2][NL], c1[2][NL];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int n = 0; n < NL; ++n) {
+                    c0[h][n] = (double)dd[h][n].x; c1[h][n] = (double)dd[h][n].y;
+                    if (nxt) dd[h][n] = pk2{wq[n].x, wq[n].x} * xv[h];
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int n = 0; n < NL; ++n) {
+                    u[n][4 * P + 2 * h] += c0[h][n]; u[n][4 * P + 2 * h + 1] += c1[h][n];
+                    if (nxt) dd[h][n] = __builtin_elementwise_fma(pk2{wq[n].y, wq[n].y}, qx[h], dd[h][n]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+        };
+        (void)unit2_products; (void)unit2_accumulate_ahead;
         // ---- phase U: the B updates of block b-1, in order: u += f32(w x) - f32(q xq)  (:119) ----
         // Software-pipelined by hand: the operands of the NEXT pair (and the next step's four (w, q)) are requested before
         // the arithmetic of the current one (sched_barrier keeps hipcc from sinking the requests to their first use,
@@ -1019,7 +1064,12 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
             // step lane & 3 at the lane's own sample, D = step j of neuron group i + 4 (b & 1), partial over kq & 1 = b >> 1: ONE row
             // rotation by eight per accumulator is left of the k-lane fold, where the first map -- its block index is kq & 3 -- leaves two.
             constexpr int NU = PW / PU;
-            constexpr int PF = NSW == 7 ? 2 : 1, NPS = NU * B;
+            // (eight neuron groups, kRows2: two as well -- the products of pair-step i + 1 are formed while pair-step i runs, kPkA below, so
+            //  its rows have to be in by then: requested during pair-step i - 1, they have the one pair-step of lead they had before.  The
+            //  rows of pair-step 3 are requested right behind slot_top_sym2, which brings those of pair-step 2.)
+            constexpr bool kRows2 = kTopSym && G == 8 && (kPkAhead & 1) != 0;
+            constexpr bool kPkA = kRows2 && (kPkAhead & 2) != 0;
+            constexpr int PF = (NSW == 7 || kRows2) ? 2 : 1, NPS = NU * B;
             using XRow = std::conditional_t<PU == 2, float4, float2>;     // a unit's samples of an operand row
             struct DRow2 { double2 v[2]; };
             using DRow = std::conditional_t<PU == 2, DRow2, double2>;     // ... and of a float64 row
@@ -1045,7 +1095,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
             if constexpr (kTopSym && G == 8) {
                 // (eight neuron groups) the same region in its two-neuron form, slot_top_sym2: twelve requests, pair-steps 0 and 1 of the
                 // lane's first unit -- four samples of two neurons each -- under counted waits; see below for what it is there for
-                static_assert(!(kTopSym && G == 8) || (B == 4 && NL == 2 && PU == 2 && PF == 1), "slot_top_sym2: two neurons per lane, pair-steps 0..2 are unit 0's steps 0..2");
+                static_assert(!(kTopSym && G == 8) || (B == 4 && NL == 2 && PU == 2 && PF == (kRows2 ? 2 : 1) && NPS >= 4), "slot_top_sym2: two neurons per lane, pair-steps 0..2 are unit 0's steps 0..2");
                 nf4 w01[2], w23[2], x2n, q2n;
                 nd2 d01[2];
                 __builtin_amdgcn_s_setprio(2);
@@ -1053,6 +1103,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                                   lds + row_off(0, false), lds + row_off(0, true), lds + o_wq + pbq, lds + rbm);
                 __builtin_amdgcn_s_waitcnt(0xC07F);            // (lgkmcnt(0) alone, for hipcc's waitcnt pass: see below)
                 __builtin_memcpy(&xbuf[0], &x2n, sizeof(XRow)); __builtin_memcpy(&qbuf[0], &q2n, sizeof(XRow));   // the rows of pair-step 2
+                if constexpr (kRows2) { xbuf[PF - 1] = lds_ld<XRow>(lds, row_off(3, false)); qbuf[PF - 1] = lds_ld<XRow>(lds, row_off(3, true)); }
 #pragma unroll
                 for (int h = 0; h < PU; ++h) dcur.v[h] = make_double2(d01[h].x, d01[h].y);
 #pragma unroll
@@ -1106,6 +1157,12 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
             } else {
                 first_requests();
             }
+            // (kPkA) The products of pair-step 2, the first one behind the region: the loop's pair-steps find theirs formed.  Products are
+            // formed one pair-step ahead INSIDE a slot only -- the slot's last pair-step forms none, so nothing of slot b + 1 is computed
+            // before slot b's barrier, its control word and its slow path.
+            pk2 ddn[2][NL];
+            if constexpr (kPkA) unit2_products(ddn, xbuf[2 % PF], qbuf[2 % PF], fwq[2]);
+            (void)ddn;
             DRow dprev;
             if constexpr (PU == 2) dprev = DRow{{make_double2(0.0, 0.0), make_double2(0.0, 0.0)}};
             else dprev = make_double2(0.0, 0.0);
@@ -1190,7 +1247,10 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                     float wv[NL], qv[NL];
 #pragma unroll
                     for (int n = 0; n < NL; ++n) { wv[n] = fwq[st][n].x; qv[n] = fwq[st][n].y; }
-                    if constexpr (PU == 2) update_unit2(p, x2, q2, wv, qv);
+                    // (kPkA: this pair-step's conversions and additions with the next one's products among them -- the next pair-step is
+                    //  the unit's next step, or step 0 of the next unit on that unit's rows)
+                    if constexpr (kPkA) unit2_accumulate_ahead(p, ddn, ips + 1 < NPS, xbuf[(ips + 1) % PF], qbuf[(ips + 1) % PF], fwq[(st + 1) % B]);
+                    else if constexpr (PU == 2) update_unit2(p, x2, q2, wv, qv);
                     else update_pair(p, x2, q2, wv, qv);
                     if (p > 0) {                                   // the previous pair's 2 NL matrix instructions, spread over this pair's B steps
 #pragma unroll

@@ -5,6 +5,8 @@
 //   -DGPFQ_BLK_NO_FUSED  matrix-unit phase D as a phase of its own behind the updates: round 4's first form
 //   -DGPFQ_BLK_TOP3=n    which slot-top pieces of the symmetric eleven-wavefront shapes go out from inside the pair loop (kTop3Ship in
 //                        gpfq_blk.hip is the shipped set): bit 0 the header piece, bit 1 the weight piece; 0 = both at the top of the slot
+//   -DGPFQ_BLK_PK_AHEAD=n  the pair loop of the eight-group shapes (kPkAheadShip in gpfq_blk.hip is the shipped set): bit 0 operand rows two
+//                        pair-steps ahead, bit 1 the next pair-step's float32 products among this one's conversions and additions; 0 = neither
 // The marginal-cost experiments of rounds 4-5 (every matrix / vector / LDS / DMA instruction issued twice, the barrier removed, pair splits
 // from the environment, the flush forced to one side) were removed in round 6; their numbers are in profiles/r04 and profiles/r05, their
 // code in the history (commit 1050215 and before).
@@ -24,6 +26,11 @@ constexpr bool kNoFused = false;
 constexpr int kTop3 = GPFQ_BLK_TOP3;
 #else
 constexpr int kTop3 = kTop3Ship;
+#endif
+#ifdef GPFQ_BLK_PK_AHEAD
+constexpr int kPkAhead = GPFQ_BLK_PK_AHEAD;
+#else
+constexpr int kPkAhead = kPkAheadShip;
 #endif
 
 #ifdef GPFQ_BLK_STAMPS

@@ -9,6 +9,8 @@
 # Round 6 added the groups VERDICT r05 asked for (instruction fetch / instruction cache, issue cycles of the memory instruction classes and
 # their in-flight levels, LDS address conflicts / unaligned stalls / FIFO-full cycles and the load / store split, the scalar data cache).
 #   PMC_LAYER=1 bash tools/pmc.sh gpfq_blk_kernel tools/pmc_probe.py 3 1 0 0 0        (the headline kernel as bench.py's step launches it)
+# PMC_SETS="1 2 4" takes only those groups (numbered in the order below); every pass runs under its own time limit, and the script ends
+# at the first pass that does not come back clean (nothing more is started on a GPU that may have faulted).
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 export PYTHONPATH=$ROOT
 KS=$1; shift
@@ -28,9 +30,12 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS
            "SQC_DCACHE_REQ SQC_DCACHE_HITS SQC_DCACHE_MISSES SQC_TC_STALL SQ_VMEM_TA_ADDR_FIFO_FULL SQ_VMEM_TA_CMD_FIFO_FULL SQ_INSTS_SMEM_NORM" \
            "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE"; do
   i=$((i+1))
+  if [ -n "$PMC_SETS" ] && ! [[ " $PMC_SETS " == *" $i "* ]]; then continue; fi
   d=$OUT/p$i
-  rocprofv3 --pmc $set --output-format csv -d $d -- python3 $ROOT/$1 "${@:2}" > $d.log 2>&1
+  timeout -k 10 ${PMC_TIMEOUT:-300} rocprofv3 --pmc $set --output-format csv -d $d -- python3 $ROOT/$1 "${@:2}" > $d.log 2>&1
+  rc=$?
   echo "== $set"
+  if [ $rc -ne 0 ]; then echo "  pass $i ended with status $rc: stopping"; tail -5 $d.log; exit $rc; fi
   python3 - "$d" "$KS" <<'PY'
 import csv, glob, sys
 d, ks = sys.argv[1:3]
