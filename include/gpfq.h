@@ -711,6 +711,20 @@ int gpfq_quantize_conv_channels(const float *act_w, const float *act_q, int64_t 
                                 void *qidx, float *Qt, double *resid, int32_t *uncertified,
                                 void *workspace, size_t workspace_bytes, void *stream);
 
+/* Which Gram kernel a conv channel-loop call of this shape would run under the current options (the one resolver every entry above and
+ * below asks): want_resid as gpfq_conv_channels_workspace_bytes, nhwc = 1 for gpfq_quantize_conv_channels_nhwc
+ * (activations [n][H][W][Cin], Cin > 1), same_act = 1 when act_w == act_q.  Returns 1 and out = {class, a, b, c, SAME_ACT, kh * kw, 0, 0}:
+ *   class 1 "loop"   per-channel patch matrices + the dense Gram path (residual norms, "conv_fused" = 0, shapes no plane kernel takes)
+ *         2 "image"  3 x 3 / stride 1 per output position, a = strip length S;  3 "shift": its shift form, a = S
+ *         4 "tile"   register tiles on the vector units, a x b = TB x SB
+ *         5 "mfma"   matrix cores, a = NB blocks of 16 rows, b = REM1 (one more row on the vector units), c = PADDED (taps outside the image)
+ *         6 "s2"     7 x 7 / stride 2 / VALID shift sums, a x b = 7 x 7
+ *   (SAME_ACT: 1 where act_w == act_q selects another instantiation -- shift, s2), or 0 and out = {0 ...} where the call would run
+ * nothing: an invalid or empty shape, kh * kw > GPFQ_GRAM_MAX_N, n * oh * ow >= 2^30, NHWC activations for any class but "s2".
+ * The two halves (gpfq_conv_channel_records ...) take every class but "loop".  Host only: needs no device.  Diagnostics for tests. */
+int gpfq_conv_form(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
+                   int want_resid, int nhwc, int same_act, int32_t out[8]);
+
 /*
  * The channel loop of a 3 x 3 / stride 1 / SAME conv layer straight from the NHWC activations Keras hands over
  * (`layer_data[..., channel_idx]`, scripts/quantized_network.py:769-770, without the channel-major copy): the shift-form Gram

@@ -1198,28 +1198,21 @@ int gpfq_quantize_conv1x1(const float *act_q, int64_t n, int64_t H, int64_t W, i
 
 static size_t al256c(size_t x) { return (x + 255) & ~(size_t)255; }
 
-static size_t conv_channels_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw,
-                                           int rh, int rw, int same_padding, int64_t F, int want_resid, const gpfq::Options &o)
-{
-    const int64_t oh = gpfq_patch_out_dim(H, kh, sh, rh, same_padding), ow = gpfq_patch_out_dim(W, kw, sw, rw, same_padding);
-    const int64_t cols = n * oh * ow;
-    const int64_t K = (int64_t)kh * kw;
-    if (cols <= 0 || K <= 0 || F < 0 || nch < 0) return 0;
-    if (!want_resid && o.conv_fused && gpfq::gram_image_supported(n, H, W, kh, kw, sh, sw, rh, rw, same_padding))
-        return gpfq::gram_image_workspace_bytes(nch, F);
-    if (!want_resid && o.conv_fused && gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow)) {
-        size_t b = al256c(gpfq::gram_conv_workspace_bytes(K, nch, F, cols));
-        if (!same_padding && gpfq::gram_s2_supported(n, H, W, kh, kw, sh, sw, rh, rw, 0, 0, nch)) b += gpfq::gram_s2_workspace_bytes(n, H, W, nch);
-        return b;
-    }
-    const int64_t ldp = (cols + 3) & ~(int64_t)3;
-    return 2 * al256c((size_t)K * ldp * sizeof(float)) + al256c((size_t)K * sizeof(float)) + gpfq::gram_workspace_bytes(K, cols, F);
-}
-
+// Every conv channel-loop entry below asks gpfq::resolve_conv_form (gpfq_gram_conv.hip) which kernel runs and what it needs; none of
+// them holds a rule about the forms.
 size_t gpfq_conv_channels_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw,
                                           int rh, int rw, int same_padding, int64_t F, int want_resid)
 {
-    return conv_channels_workspace_bytes(n, H, W, nch, kh, kw, sh, sw, rh, rw, same_padding, F, want_resid, gpfq::options_snapshot());
+    return gpfq::resolve_conv_form(n, H, W, nch, kh, kw, sh, sw, rh, rw, same_padding, F, want_resid != 0, false, false, gpfq::options_snapshot()).workspace_bytes;
+}
+
+int gpfq_conv_form(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
+                   int want_resid, int nhwc, int same_act, int32_t out[8])
+{
+    if (!out) return 0;
+    gpfq::conv_form_query(gpfq::resolve_conv_form(n, H, W, nch, kh, kw, sh, sw, rh, rw, same_padding, 0, want_resid != 0, nhwc != 0, same_act != 0,
+                                                  gpfq::options_snapshot()), out);
+    return out[0] != gpfq::ConvForm::none ? 1 : 0;
 }
 
 // phase 0: the whole channel loop; 1: Gram records only (-> records, negflags); 2: decide from given records
@@ -1239,22 +1232,24 @@ static int conv_channels_impl(int phase, double *records, int32_t *negflags,
     }
     const gpfq::AlphabetArg &A = HA.A;
     int8_t *qidx = static_cast<int8_t *>(qidx_v);          // int16 elements when HA.is_big
-    const int64_t oh = gpfq_patch_out_dim(H, kh, sh, rh, same_padding), ow = gpfq_patch_out_dim(W, kw, sw, rw, same_padding);
-    const int64_t cols = n * oh * ow, K = (int64_t)kh * kw;
+    const bool same_act = act_w == act_q;          // first layer: both networks see the raw data (:478-481)
+    const gpfq::Options o = gpfq::options_snapshot();
+    const gpfq::ConvForm f = gpfq::resolve_conv_form(n, H, W, nch, kh, kw, sh, sw, rh, rw, same_padding, F, resid != nullptr, pix > 1, same_act, o);
+    const int64_t cols = f.cols, K = f.K;
     if (phase && (!records || !negflags)) return fail(GPFQ_ERR_INVALID_ARG, "NULL records / negflags");
     if (nch == 0 || (F == 0 && phase != 1) || cols == 0) return GPFQ_OK;
-    if (K > GPFQ_GRAM_MAX_N || cols >= (1LL << 30)) return fail(GPFQ_ERR_UNSUPPORTED, "needs kh*kw <= %d and n*oh*ow < 2^30", GPFQ_GRAM_MAX_N);
+    if (f.too_large) return fail(GPFQ_ERR_UNSUPPORTED, "needs kh*kw <= %d and n*oh*ow < 2^30", GPFQ_GRAM_MAX_N);
     if (!act_w || !act_q) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (phase != 1 && (!Wt || !qidx || !Qt || !uncertified)) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (phase && resid) return fail(GPFQ_ERR_UNSUPPORTED, "residual norms need the whole call");
-    const gpfq::Options o = gpfq::options_snapshot();
-    const size_t need = conv_channels_workspace_bytes(n, H, W, nch, kh, kw, sh, sw, rh, rw, same_padding, F, resid != nullptr, o);
-    if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16 != 0)
-        return fail(GPFQ_ERR_WORKSPACE, "conv channel loop needs %zu aligned workspace bytes", need);
-    if (pix > 1 && !(same_padding == 0 && !resid && !phase && o.conv_fused && gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow) &&
-                     gpfq::gram_s2_supported(n, H, W, kh, kw, sh, sw, rh, rw, 0, 0, nch)))
+    if (!workspace || workspace_bytes < f.workspace_bytes || (uintptr_t)workspace % 16 != 0)
+        return fail(GPFQ_ERR_WORKSPACE, "conv channel loop needs %zu aligned workspace bytes", f.workspace_bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (f.cls) {
+    case gpfq::ConvForm::none:
         return fail(GPFQ_ERR_UNSUPPORTED, "NHWC activations: only the 7x7 / stride 2 / VALID shift-sum form reads them (gpfq_conv_channels_nhwc_supported)");
-    if (pix == 1 && !resid && o.conv_fused && gpfq::gram_image_supported(n, H, W, kh, kw, sh, sw, rh, rw, same_padding)) {
+    case gpfq::ConvForm::image:
+    case gpfq::ConvForm::shift: {
         // 3x3 / stride 1: Gram matrices of every channel straight from the planes, one batched decide launch
         gpfq::ImageGramArgs g;
         g.act_w = act_w; g.act_q = act_q; g.n = n; g.H = H; g.W = W; g.nch = nch; g.pad = same_padding ? 1 : 0;
@@ -1263,31 +1258,25 @@ static int conv_channels_impl(int phase, double *records, int32_t *negflags,
         g.slack = std::ldexp(1.0, o.gram_slack_log2);
         g.opt = o;
         g.phase = phase; g.records = records; g.negflags = negflags;
-        hipError_t e = gpfq::launch_gram_image(g, static_cast<hipStream_t>(stream));
+        hipError_t e = gpfq::launch_gram_image(g, f, s);
         return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_quantize_conv_channels(fused)");
     }
-    int pad_top = 0, pad_left = 0;
-    if (same_padding) {
-        const int64_t keh = kh + (int64_t)(kh - 1) * (rh - 1), kew = kw + (int64_t)(kw - 1) * (rw - 1);
-        int64_t th = (oh - 1) * sh + keh - H; if (th < 0) th = 0;
-        int64_t tw = (ow - 1) * sw + kew - W; if (tw < 0) tw = 0;
-        pad_top = (int)(th / 2);
-        pad_left = (int)(tw / 2);
-    }
-    if (!resid && o.conv_fused && gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow)) {
+    case gpfq::ConvForm::tile:
+    case gpfq::ConvForm::mfma:
+    case gpfq::ConvForm::s2: {
         // any other shape: the tile kernel gathers its patch rows from the planes (implicit im2col)
         gpfq::ConvGramArgs g;
         g.act_w = act_w; g.act_q = act_q; g.n = n; g.H = H; g.W = W; g.nch = nch;
-        g.kh = kh; g.kw = kw; g.sh = sh; g.sw = sw; g.rh = rh; g.rw = rw; g.pt = pad_top; g.pl = pad_left; g.oh = oh; g.ow = ow;
+        g.kh = kh; g.kw = kw; g.sh = sh; g.sw = sw; g.rh = rh; g.rw = rw;
         g.Wt = Wt; g.A = A; g.big = HA.big(); g.F = F; g.qidx = qidx; g.Qt = Qt; g.uncertified = uncertified;
         g.workspace = workspace;
         g.slack = std::ldexp(1.0, o.gram_slack_log2);
-        g.opt = o;
         g.phase = phase; g.records = records; g.negflags = negflags; g.pix = pix;
-        if (pad_top == 0 && pad_left == 0 && gpfq::gram_s2_supported(n, H, W, kh, kw, sh, sw, rh, rw, pad_top, pad_left, nch))
-            g.s2_part = reinterpret_cast<double *>(static_cast<char *>(workspace) + al256c(gpfq::gram_conv_workspace_bytes(K, nch, F, cols)));
-        hipError_t e = gpfq::launch_gram_conv(g, static_cast<hipStream_t>(stream));
+        hipError_t e = gpfq::launch_gram_conv(g, f, s);
         return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_quantize_conv_channels(implicit)");
+    }
+    case gpfq::ConvForm::loop:
+        break;
     }
     if (phase) return fail(GPFQ_ERR_UNSUPPORTED, "records in / out need a kernel shape the plane kernels take");
     const int64_t ldp = (cols + 3) & ~(int64_t)3;
@@ -1295,15 +1284,13 @@ static int conv_channels_impl(int phase, double *records, int32_t *negflags,
     float *Pw = reinterpret_cast<float *>(ws);   ws += al256c((size_t)K * ldp * sizeof(float));
     float *Pq = reinterpret_cast<float *>(ws);   ws += al256c((size_t)K * ldp * sizeof(float));
     float *nrm = reinterpret_cast<float *>(ws);  ws += al256c((size_t)K * sizeof(float));
-    const bool same_act = act_w == act_q;          // first layer: both networks see the raw data (:478-481)
     const int64_t plane = n * H * W;
-    hipStream_t s = static_cast<hipStream_t>(stream);
     for (int64_t c = 0; c < nch; ++c) {
-        hipError_t e = gpfq::launch_extract_patches(act_w + c * plane, n, H, W, 1, 0, kh, kw, sh, sw, rh, rw, pad_top, pad_left,
-                                                    oh, ow, Pw, ldp, s);
+        hipError_t e = gpfq::launch_extract_patches(act_w + c * plane, n, H, W, 1, 0, kh, kw, sh, sw, rh, rw, f.pad_top, f.pad_left,
+                                                    f.oh, f.ow, Pw, ldp, s);
         if (e == hipSuccess && !same_act)
-            e = gpfq::launch_extract_patches(act_q + c * plane, n, H, W, 1, 0, kh, kw, sh, sw, rh, rw, pad_top, pad_left,
-                                             oh, ow, Pq, ldp, s);
+            e = gpfq::launch_extract_patches(act_q + c * plane, n, H, W, 1, 0, kh, kw, sh, sw, rh, rw, f.pad_top, f.pad_left,
+                                             f.oh, f.ow, Pq, ldp, s);
         if (e != hipSuccess) return hip_fail(e, "gpfq_quantize_conv_channels(patches)");
         gpfq::GramArgs a;
         a.X = Pw; a.Xq = same_act ? Pw : Pq; a.ld = ldp; a.nrm32 = nrm; a.nrm32_out = nrm;
@@ -1361,12 +1348,8 @@ int gpfq_quantize_conv3x3_nhwc(const float *act_w, const float *act_q, int64_t n
 int gpfq_conv_records_supported(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw, int rh, int rw,
                                 int same_padding)
 {
-    if (n <= 0 || H <= 0 || W <= 0 || nch <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || rh <= 0 || rw <= 0) return 0;
-    const int64_t oh = gpfq_patch_out_dim(H, kh, sh, rh, same_padding), ow = gpfq_patch_out_dim(W, kw, sw, rw, same_padding);
-    const int64_t cols = n * oh * ow, K = (int64_t)kh * kw;
-    if (cols <= 0 || K > GPFQ_GRAM_MAX_N || cols >= (1LL << 30) || !gpfq::options_snapshot().conv_fused) return 0;
-    return (gpfq::gram_image_supported(n, H, W, kh, kw, sh, sw, rh, rw, same_padding) ||
-            gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow)) ? 1 : 0;
+    const gpfq::ConvForm f = gpfq::resolve_conv_form(n, H, W, nch, kh, kw, sh, sw, rh, rw, same_padding, 0, false, false, false, gpfq::options_snapshot());
+    return f.cls != gpfq::ConvForm::none && f.cls != gpfq::ConvForm::loop ? 1 : 0;       // (the halves need a plane kernel)
 }
 
 int gpfq_quantize_conv_channels(const float *act_w, const float *act_q, int64_t n, int64_t H, int64_t W, int64_t nch,
@@ -1382,10 +1365,8 @@ int gpfq_quantize_conv_channels(const float *act_w, const float *act_q, int64_t 
 int gpfq_conv_channels_nhwc_supported(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding)
 {
     const gpfq::Options o = gpfq::options_snapshot();
-    if (n <= 0 || H <= 0 || W <= 0 || nch <= 0 || same_padding || !o.conv_fused || !o.conv_planes_free) return 0;
-    const int64_t oh = gpfq_patch_out_dim(H, kh, sh, rh, 0), ow = gpfq_patch_out_dim(W, kw, sw, rw, 0);
-    if ((int64_t)kh * kw > GPFQ_GRAM_MAX_N || n * oh * ow >= (1LL << 30)) return 0;
-    return gpfq::gram_conv_supported(n, H, W, nch, kh, kw, oh, ow) && gpfq::gram_s2_supported(n, H, W, kh, kw, sh, sw, rh, rw, 0, 0, nch) ? 1 : 0;
+    // (conv_planes_free = 0: the layer driver is to form channel planes first, whatever the kernels could read)
+    return o.conv_planes_free && gpfq::resolve_conv_form(n, H, W, nch, kh, kw, sh, sw, rh, rw, same_padding, 0, false, true, false, o).cls == gpfq::ConvForm::s2 ? 1 : 0;
 }
 
 int gpfq_quantize_conv_channels_nhwc(const float *act_w, const float *act_q, int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t c_lo,

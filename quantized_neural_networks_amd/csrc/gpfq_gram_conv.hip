@@ -7,6 +7,7 @@
 // walkers x lower-triangle tiles x channels), so a 7x7/2 layer no longer writes and re-reads 20 GB of patch
 // data per channel.  The 3x3 / stride-1 case has its own kernel (gpfq_gram_image.hip).
 
+#include "../../include/gpfq.h"
 #include "gpfq_device.hpp"
 #include "gpfq_gram_tile.hpp"
 #include "gpfq_launch.hpp"
@@ -385,19 +386,129 @@ bool gram_conv_supported(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, i
     return n * H * W < (1LL << 31) - (1LL << 20) && n * oh * ow < (1LL << 30);
 }
 
-size_t gram_conv_workspace_bytes(int64_t K, int64_t nch, int64_t F, int64_t m)
+GramAreas gram_areas(int64_t K, int64_t nch, int64_t F, int64_t part_records, bool zero_word)
 {
+    GramAreas w{};
     size_t b = 0;
-    int64_t parts = conv_walkers(K, nch, m);                                                // partial records (either kernel)
-    if (conv_mfma_shape(K) && conv_mfma_walkers(nch, m) * kCmSplit > parts) parts = conv_mfma_walkers(nch, m) * kCmSplit;
-    b += al256v((size_t)nch * parts * gram_record(K) * sizeof(double));
-    b += al256v((size_t)nch * gram_record(K) * sizeof(double));                             // Gram records
-    b += al256v((size_t)nch * K * sizeof(float));                                           // row norms
-    b += al256v((size_t)nch * F * K * sizeof(float));                                       // chosen values per filter and step
-    b += gram_fix_bytes();
-    b += al256v((size_t)nch * sizeof(int));                                                 // negative-activation flags
-    b += 256;                                                                               // a zero word for out-of-image taps
-    return b;
+    w.part = b;    b += al256v((size_t)part_records * gram_record(K) * sizeof(double));     // partial records (any kernel of the class)
+    w.gram = b;    b += al256v((size_t)nch * gram_record(K) * sizeof(double));              // Gram records
+    w.nrm = b;     b += al256v((size_t)nch * K * sizeof(float));                            // row norms
+    w.q32h = b;    b += al256v((size_t)nch * F * K * sizeof(float));                        // chosen values per filter and step
+    w.fix = b;     b += gram_fix_bytes();                                                   // device-side repair of uncertified chains
+    w.negflag = b; b += al256v((size_t)nch * sizeof(int));                                  // "channel has negative activations" flags
+    w.zero = b;    b += zero_word ? 256 : 0;                                                // a zero word for out-of-image taps
+    w.bytes = b;
+    return w;
+}
+
+// The one statement of which kernel a conv channel-loop call runs.  Host arithmetic only: no device is asked anything.
+ConvForm resolve_conv_form(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
+                           int64_t F, bool want_resid, bool nhwc, bool same_act, const Options &opt)
+{
+    ConvForm f;
+    f.oh = gpfq_patch_out_dim(H, kh, sh, rh, same_padding);
+    f.ow = gpfq_patch_out_dim(W, kw, sw, rw, same_padding);
+    f.cols = n * f.oh * f.ow;
+    f.K = (int64_t)kh * kw;
+    if (same_padding) {
+        const int64_t keh = kh + (int64_t)(kh - 1) * (rh - 1), kew = kw + (int64_t)(kw - 1) * (rw - 1);
+        int64_t th = (f.oh - 1) * sh + keh - H; if (th < 0) th = 0;
+        int64_t tw = (f.ow - 1) * sw + kew - W; if (tw < 0) tw = 0;
+        f.pad_top = (int)(th / 2);
+        f.pad_left = (int)(tw / 2);
+    }
+    if (f.cols <= 0 || f.K <= 0 || F < 0 || nch < 0) return f;             // nothing to size, nothing to run
+    // Which kernels take the shape (the workspace follows from this alone: it is the same for planes and for NHWC activations).
+    // Residual norms need the patch rows themselves; option conv_fused = 0 asks for them.
+    const bool fused = !want_resid && opt.conv_fused;
+    const bool image_shape = fused && gram_image_supported(n, H, W, kh, kw, sh, sw, rh, rw, same_padding);
+    const bool conv_shape = fused && !image_shape && gram_conv_supported(n, H, W, nch, kh, kw, f.oh, f.ow);
+    // (3 x 3 / stride 1 planes that image_plan refuses -- rows wider than it stages -- are conv_shape: the K = 9 matrix-core kernel)
+    const bool s2_shape = conv_shape && f.pad_top == 0 && f.pad_left == 0 &&
+                          gram_s2_supported(n, H, W, kh, kw, sh, sw, rh, rw, f.pad_top, f.pad_left, nch);
+    if (image_shape) {
+        f.workspace_bytes = gram_areas(9, nch, F, gram_image_part_records(nch), false).bytes;
+    } else if (conv_shape) {
+        f.parts = conv_walkers(f.K, nch, f.cols);                          // either tile kernel's partial records fit
+        if (conv_mfma_shape(f.K) && conv_mfma_walkers(nch, f.cols) * kCmSplit > f.parts) f.parts = conv_mfma_walkers(nch, f.cols) * kCmSplit;
+        f.workspace_bytes = al256v(gram_areas(f.K, nch, F, nch * f.parts, true).bytes);
+        if (s2_shape) {                                                    // (part of the workspace whatever option conv_s2 says)
+            f.s2_offset = f.workspace_bytes;
+            f.workspace_bytes += gram_s2_workspace_bytes(n, H, W, nch);
+        }
+    } else {                                                               // two patch matrices, their row norms, launch_gram's own
+        const int64_t ldp = (f.cols + 3) & ~(int64_t)3;
+        f.workspace_bytes = 2 * al256v((size_t)f.K * ldp * sizeof(float)) + al256v((size_t)f.K * sizeof(float)) + gram_workspace_bytes(f.K, f.cols, F);
+    }
+    if (n <= 0 || H <= 0 || W <= 0 || nch <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || rh <= 0 || rw <= 0) return f;
+    f.too_large = f.K > GPFQ_GRAM_MAX_N || f.cols >= (1LL << 30);
+    if (f.too_large) return f;
+    if (nhwc) {
+        // NHWC activations: only the shift sums read them -- and there they are taken even with conv_s2 = 0 (no other kernel could)
+        if (s2_shape) f.cls = ConvForm::s2;
+    } else if (image_shape) {
+        // SAME padding: the shift form (27 instead of 99 FMAs per position) wherever its band layout fits.  Measured on ResNet50's
+        // 3x3 layers at 4096 images (tools/conv3x3_probe.py, kernel alone): 56 x 56: 6.8 -> 3.1 ms, 28 x 28: 2.8 -> 1.6, 14 x 14: 1.63 ->
+        // 1.57, 7 x 7: 1.5 -> 1.7 (a third of the positions are on the border and the bands are short); the CIFAR10 CNN's layers at 5008
+        // images (tools/conv3x3_probe.py, whole layer): 32 x 32, 32 channels: 1.93 -> 1.49 ms; 24 x 24: 1.70 -> 1.50; 20 x 20: 2.24 ->
+        // 2.02; 16 x 16 loses; 3 channels at 32 x 32 (hundreds of short workgroups per channel, each with its class sums to reduce):
+        // 0.34 -> 0.50.  So: from 20 x 20 up, with 8 channels or more in the shard.
+        // option conv_shift = 2 forces it for every size it can take (tests).
+        const int pad = same_padding ? 1 : 0;
+        if (opt.conv_shift && (opt.conv_shift == 2 || (H >= 20 && W >= 20 && nch >= 8)))
+            f.S = gram_image_strip(n, H, W, pad, opt.conv_strip, true);    // (0: the band layout declines -- the per-position form answers)
+        f.cls = f.S ? ConvForm::shift : ConvForm::image;
+        if (!f.S) f.S = gram_image_strip(n, H, W, pad, opt.conv_strip, false);
+    } else if (conv_shape) {
+        // 7x7 / stride 2 / VALID: shift sums of the parity classes of the planes instead of every (t, s) product (gpfq_gram_s2.hip),
+        // for shards of up to 8 channels (gram_s2_supported); else the matrix cores where they are ahead (conv_mfma_shape; variant bit 2:
+        // vector-unit tiles all the same); else the register-tile kernel
+        f.cls = opt.conv_s2 && s2_shape ? ConvForm::s2 : conv_mfma_shape(f.K) && !(opt.variant & 4) ? ConvForm::mfma : ConvForm::tile;
+    } else {
+        f.cls = ConvForm::loop;
+    }
+    // taps reach from -pt to (oh-1)*sh + (kh-1)*rh - pt (rows), likewise for columns
+    f.PADDED = f.pad_top > 0 || f.pad_left > 0 || (f.oh - 1) * sh + (int64_t)(kh - 1) * rh - f.pad_top >= H
+               || (f.ow - 1) * sw + (int64_t)(kw - 1) * rw - f.pad_left >= W;
+    f.SAME_ACT = (f.cls == ConvForm::shift || f.cls == ConvForm::s2) && same_act;
+    if (f.cls == ConvForm::mfma) {
+        f.REM1 = f.K == 17 || f.K == 33 || f.K == 49;                      // one row past a block edge: that row on the vector units
+        f.NB = (int)((f.K - (f.REM1 ? 1 : 0) + 15) / 16);
+    } else if (f.cls == ConvForm::tile) {
+        f.TB = kConvTB; f.SB = kConvSB;
+    }
+    return f;
+}
+
+void conv_form_query(const ConvForm &f, int32_t out[8])
+{
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (f.cls == ConvForm::none) return;
+    out[0] = (int32_t)f.cls;
+    switch (f.cls) {
+    case ConvForm::image: case ConvForm::shift: out[1] = f.S; break;
+    case ConvForm::tile: out[1] = f.TB; out[2] = f.SB; break;
+    case ConvForm::mfma: out[1] = f.NB; out[2] = f.REM1; out[3] = f.PADDED; break;
+    case ConvForm::s2: out[1] = out[2] = 7; break;
+    default: break;
+    }
+    out[4] = f.SAME_ACT;
+    out[5] = (int32_t)f.K;
+}
+
+// The matrix-core kernel of a resolved form (REM1 has no NB = 4 instantiation: K <= 64)
+using ConvKernel = void (*)(ConvParams);
+template <int NB>
+static ConvKernel conv_mfma_kernel_of(bool rem1, bool padded)
+{
+    if constexpr (NB < 4)
+        if (rem1) return padded ? gpfq_gram_conv_mfma_kernel<NB, true, true> : gpfq_gram_conv_mfma_kernel<NB, true, false>;
+    return padded ? gpfq_gram_conv_mfma_kernel<NB, false, true> : gpfq_gram_conv_mfma_kernel<NB, false, false>;
+}
+static ConvKernel conv_mfma_kernel(const ConvForm &f)
+{
+    return f.NB == 1 ? conv_mfma_kernel_of<1>(f.REM1, f.PADDED) : f.NB == 2 ? conv_mfma_kernel_of<2>(f.REM1, f.PADDED)
+         : f.NB == 3 ? conv_mfma_kernel_of<3>(f.REM1, f.PADDED) : conv_mfma_kernel_of<4>(false, f.PADDED);
 }
 
 static void decompose(int64_t v, int64_t oh, int64_t ow, int (&d)[3])
@@ -408,101 +519,56 @@ static void decompose(int64_t v, int64_t oh, int64_t ow, int (&d)[3])
     d[2] = (int)(v - (int64_t)d[1] * ow);
 }
 
-hipError_t launch_gram_conv(const ConvGramArgs &a, hipStream_t stream)
+hipError_t launch_gram_conv(const ConvGramArgs &a, const ConvForm &f, hipStream_t stream)
 {
     if (a.nch == 0 || (a.F == 0 && a.phase != 1)) return hipSuccess;
-    const int64_t K = (int64_t)a.kh * a.kw, m = a.n * a.oh * a.ow;
-    if (!gram_conv_supported(a.n, a.H, a.W, a.nch, a.kh, a.kw, a.oh, a.ow)) return hipErrorInvalidValue;
-    const bool mfma = conv_mfma_shape(K) && !(a.opt.variant & 4);
+    const bool mfma = f.cls == ConvForm::mfma, s2 = f.cls == ConvForm::s2;
+    if ((!mfma && !s2 && f.cls != ConvForm::tile) || (a.pix > 1 && !s2)) return hipErrorInvalidValue;   // (the tile kernels read channel planes)
+    const int64_t K = f.K, m = f.cols;
     const bool same_act = a.act_w == a.act_q;
     const int64_t walkers = mfma ? conv_mfma_walkers(a.nch, m) : conv_walkers(K, a.nch, m);
     const int64_t nparts = mfma ? walkers * (same_act ? 4 : 2) : walkers;
-    int64_t maxparts = conv_walkers(K, a.nch, m);
-    if (conv_mfma_shape(K) && conv_mfma_walkers(a.nch, m) * kCmSplit > maxparts) maxparts = conv_mfma_walkers(a.nch, m) * kCmSplit;
     const int64_t chunk = mfma ? kCmCH : kGramCH;
     ConvParams p{};
     p.act_w = a.act_w; p.act_q = a.act_q; p.plane = a.n * a.H * a.W;
     p.H = (int)a.H; p.W = (int)a.W; p.kw = a.kw; p.sh = a.sh; p.sw = a.sw; p.rh = a.rh; p.rw = a.rw;
-    p.pt = a.pt; p.pl = a.pl; p.oh = (int)a.oh; p.ow = (int)a.ow;
+    p.pt = f.pad_top; p.pl = f.pad_left; p.oh = (int)f.oh; p.ow = (int)f.ow;
     p.K = (int)K; p.m = (int)m;
     p.nchunks = (int)((m + chunk - 1) / chunk);
     p.same_act = same_act;
-    // taps reach from -pt to (oh-1)*sh + (kh-1)*rh - pt (rows), likewise for columns
-    p.padded = a.pt > 0 || a.pl > 0 || (a.oh - 1) * a.sh + (int64_t)(a.kh - 1) * a.rh - a.pt >= a.H
-               || (a.ow - 1) * a.sw + (int64_t)(a.kw - 1) * a.rw - a.pl >= a.W;
-    decompose(64, a.oh, a.ow, p.d64);
-    decompose(chunk * walkers, a.oh, a.ow, p.dch);
+    p.padded = f.PADDED;
+    decompose(64, f.oh, f.ow, p.d64);
+    decompose(chunk * walkers, f.oh, f.ow, p.dch);
     p.nparts = (int)nparts;
-    char *ws = static_cast<char *>(a.workspace);
-    double *part = reinterpret_cast<double *>(ws);  ws += al256v((size_t)a.nch * maxparts * gram_record(K) * sizeof(double));
-    double *gram = reinterpret_cast<double *>(ws);  ws += al256v((size_t)a.nch * gram_record(K) * sizeof(double));
-    float *nrm = reinterpret_cast<float *>(ws);     ws += al256v((size_t)a.nch * K * sizeof(float));
-    float *q32h = reinterpret_cast<float *>(ws);    ws += al256v((size_t)a.nch * a.F * K * sizeof(float));
-    void *fixws = ws;                               ws += gram_fix_bytes();
-    int *negflag = reinterpret_cast<int *>(ws);     ws += al256v((size_t)a.nch * sizeof(int));
-    p.zero = reinterpret_cast<const float *>(ws);
-    hipError_t e0 = hipMemsetAsync(negflag, 0, al256v((size_t)a.nch * sizeof(int)) + 256, stream);
-    if (e0 != hipSuccess) return e0;
-    p.part = part;
-    p.negflag = negflag;
-    hipError_t e;
-    if (a.phase == 2) {                                    // records formed elsewhere (and summed over the column shards)
-        e = hipMemcpyAsync(negflag, a.negflags, (size_t)a.nch * sizeof(int), hipMemcpyDeviceToDevice, stream);
+    const GramAreas w = gram_areas(K, a.nch, a.F, a.nch * f.parts, true);
+    double *gram = gram_area<double>(a.workspace, w.gram);
+    float *nrm = gram_area<float>(a.workspace, w.nrm);
+    p.part = gram_area<double>(a.workspace, w.part);
+    p.negflag = gram_area<int>(a.workspace, w.negflag);
+    p.zero = gram_area<const float>(a.workspace, w.zero);
+    hipError_t e = hipMemsetAsync(p.negflag, 0, w.bytes - w.negflag, stream);          // the flags and the zero word behind them
+    if (e != hipSuccess) return e;
+    if (a.phase == 2) {
+        // records formed elsewhere: finish_gram_records takes them in
+    } else if (s2) {
+        e = launch_gram_s2(a.act_w, a.act_q, a.n, a.H, a.W, a.nch, gram_area<double>(a.workspace, f.s2_offset), gram, nrm, p.negflag, stream, a.pix);
         if (e != hipSuccess) return e;
-        e = launch_gram_reduce(a.records, 1, (int)K, gram, nrm, a.nch, stream);
-        if (e != hipSuccess) return e;
-    } else if ((a.opt.conv_s2 || a.pix > 1) && a.s2_part &&
-               gram_s2_supported(a.n, a.H, a.W, a.kh, a.kw, a.sh, a.sw, a.rh, a.rw, a.pt, a.pl, a.nch)) {
-        // 7x7 / stride 2 / VALID: shift sums of the parity classes of the planes instead of every (t, s) product (gpfq_gram_s2.hip)
-        e = launch_gram_s2(a.act_w, a.act_q, a.n, a.H, a.W, a.nch, a.s2_part, gram, nrm, negflag, stream, a.pix);
-        if (e != hipSuccess) return e;
-        if (a.phase == 1) {
-            e = hipMemcpyAsync(a.records, gram, (size_t)a.nch * gram_record(K) * sizeof(double), hipMemcpyDeviceToDevice, stream);
-            if (e != hipSuccess) return e;
-            return hipMemcpyAsync(a.negflags, negflag, (size_t)a.nch * sizeof(int), hipMemcpyDeviceToDevice, stream);
-        }
     } else {
-        if (a.pix > 1) return hipErrorInvalidValue;        // the tile kernels read channel planes
-        if (mfma) {
-            const dim3 grid((unsigned)walkers, 1, (unsigned)a.nch);
-#define GPFQ_CM(NB_, REM_)                                                                                                          \
-            do {                                                                                                                    \
-                if (p.padded) hipLaunchKernelGGL((gpfq_gram_conv_mfma_kernel<NB_, REM_, true>), grid, dim3(kGramThreads), 0, stream, p);  \
-                else hipLaunchKernelGGL((gpfq_gram_conv_mfma_kernel<NB_, REM_, false>), grid, dim3(kGramThreads), 0, stream, p);          \
-            } while (0)
-            if (K <= 16) GPFQ_CM(1, false);
-            else if (K == 17) GPFQ_CM(1, true);
-            else if (K <= 32) GPFQ_CM(2, false);
-            else if (K == 33) GPFQ_CM(2, true);
-            else if (K <= 48) GPFQ_CM(3, false);
-            else if (K == 49) GPFQ_CM(3, true);
-            else GPFQ_CM(4, false);
-#undef GPFQ_CM
-        } else {
+        if (mfma)
+            hipLaunchKernelGGL(conv_mfma_kernel(f), dim3((unsigned)walkers, 1, (unsigned)a.nch), dim3(kGramThreads), 0, stream, p);
+        else
             hipLaunchKernelGGL((gpfq_gram_conv_kernel<kConvTB, kConvSB>),
                                dim3((unsigned)tile_count<kConvTB, kConvSB>((int)K), (unsigned)nparts, (unsigned)a.nch), dim3(kGramThreads), 0, stream, p);
-        }
         e = hipGetLastError();
         if (e != hipSuccess) return e;
-        e = launch_gram_reduce(part, nparts, (int)K, gram, nrm, a.nch, stream);
+        e = launch_gram_reduce(p.part, nparts, (int)K, gram, nrm, a.nch, stream);
         if (e != hipSuccess) return e;
-        if (a.phase == 1) {
-            e = hipMemcpyAsync(a.records, gram, (size_t)a.nch * gram_record(K) * sizeof(double), hipMemcpyDeviceToDevice, stream);
-            if (e != hipSuccess) return e;
-            return hipMemcpyAsync(a.negflags, negflag, (size_t)a.nch * sizeof(int), hipMemcpyDeviceToDevice, stream);
-        }
     }
-    DecideBatch bs;
-    bs.nch = a.nch; bs.gram_cs = gram_record(K); bs.nrm_cs = K; bs.w_cs = a.F * K; bs.out_cs = a.F * K; bs.unc_cs = a.F;
-    bs.hist_cs = a.F * K;
     FixSrc src{};
     src.X = a.act_w; src.Xq = a.act_q; src.ld = 0; src.m = m; src.planes = 1; src.plane = a.pix > 1 ? 1 : p.plane; src.pix = a.pix > 1 ? a.pix : 1;
     src.n = (int)a.n; src.H = p.H; src.W = p.W; src.oh = p.oh; src.ow = p.ow;
-    src.kw = a.kw; src.sh = a.sh; src.sw = a.sw; src.rh = a.rh; src.rw = a.rw; src.pt = a.pt; src.pl = a.pl;
-    e = launch_canonical_norms(src, (int)K, a.nch, nrm, K, fixws, stream);      // few channels: norms in an order fixed by the dimensions
-    if (e != hipSuccess) return e;
-    return launch_gram_decide(gram, nrm, a.Wt, K, a.A, (int)K, a.F, a.slack, a.qidx, a.Qt, a.uncertified, q32h, bs, &src, fixws, negflag,
-                              stream, a.big);
+    src.kw = a.kw; src.sh = a.sh; src.sw = a.sw; src.rh = a.rh; src.rw = a.rw; src.pt = p.pt; src.pl = p.pl;
+    return finish_gram_records(a, f, src, w, stream);
 }
 
 }  // namespace gpfq

@@ -737,41 +737,43 @@ bool gram_image_supported(int64_t n, int64_t H, int64_t W, int kh, int kw, int s
     return image_plan(n, H, W, same_padding ? 1 : 0, 0, nullptr, nullptr, nullptr);
 }
 
-size_t gram_image_workspace_bytes(int64_t nch, int64_t F)
+int gram_image_strip(int64_t n, int64_t H, int64_t W, int pad, int conv_strip, bool shift)
 {
-    size_t b = 0;
-    b += al256i((size_t)(nch + kImgBlocks) * 2 * kRec9 * sizeof(double));   // partials: nch * ceil(kImgBlocks / nch) * 2 at most
-    b += al256i((size_t)nch * kRec9 * sizeof(double));                      // Gram records
-    b += al256i((size_t)nch * 9 * sizeof(float));                           // row norms
-    b += al256i((size_t)nch * F * 9 * sizeof(float));                       // chosen values per filter and step
-    b += gram_fix_bytes();                                                  // device-side repair of uncertified chains
-    b += al256i((size_t)nch * sizeof(int));                                 // "channel has negative activations" flags
-    return b;
+    int S = 0;
+    return image_plan(n, H, W, pad, conv_strip, nullptr, &S, nullptr, shift) ? S : 0;
 }
 
-hipError_t launch_gram_image(const ImageGramArgs &a, hipStream_t stream)
+int64_t gram_image_part_records(int64_t nch) { return (nch + kImgBlocks) * 2; }   // partials: nch * ceil(kImgBlocks / nch) * 2 at most
+
+// The record kernel of a resolved form: the pointer the occupancy query is asked about and the pointer launched are this one object.
+using ImgKernel = void (*)(ImgParams);
+template <int S>
+static ImgKernel image_kernel_of(ConvForm::Class cls, bool same_act)
+{
+    if (cls != ConvForm::shift) return gpfq_gram_image_kernel<S>;
+    return same_act ? gpfq_gram_shift_kernel<S, true> : gpfq_gram_shift_kernel<S, false>;
+}
+static ImgKernel image_kernel(ConvForm::Class cls, int S, bool same_act)
+{
+    return S == 4 ? image_kernel_of<4>(cls, same_act) : S == 2 ? image_kernel_of<2>(cls, same_act) : image_kernel_of<1>(cls, same_act);
+}
+
+hipError_t launch_gram_image(const ImageGramArgs &a, const ConvForm &f, hipStream_t stream)
 {
     if (a.nch == 0 || (a.F == 0 && a.phase != 1)) return hipSuccess;
+    const bool shift = f.cls == ConvForm::shift;
     ImgParams p;
     int S;
     size_t lds;
-    // SAME padding: the shift form (27 instead of 99 FMAs per position) wherever its band layout fits.  Measured on ResNet50's
-    // 3x3 layers at 4096 images (tools/conv3x3_probe.py, kernel alone): 56 x 56: 6.8 -> 3.1 ms, 28 x 28: 2.8 -> 1.6, 14 x 14: 1.63 ->
-    // 1.57, 7 x 7: 1.5 -> 1.7 (a third of the positions are on the border and the bands are short); the CIFAR10 CNN's layers at 5008
-    // images (tools/conv3x3_probe.py, whole layer): 32 x 32, 32 channels: 1.93 -> 1.49 ms; 24 x 24: 1.70 -> 1.50; 20 x 20: 2.24 ->
-    // 2.02; 16 x 16 loses; 3 channels at 32 x 32 (hundreds of short workgroups per channel, each with its class sums to reduce):
-    // 0.34 -> 0.50.  So: from 20 x 20 up, with 8 channels or more in the shard.
-    // option conv_shift = 2 forces it for every size it can take (tests).
-    const bool shift = a.opt.conv_shift && (a.opt.conv_shift == 2 || (a.H >= 20 && a.W >= 20 && a.nch >= 8)) && image_plan(a.n, a.H, a.W, a.pad, a.opt.conv_strip, &p, &S, &lds, true);
-    if (!shift && !image_plan(a.n, a.H, a.W, a.pad, a.opt.conv_strip, &p, &S, &lds)) return hipErrorInvalidValue;
+    if ((!shift && f.cls != ConvForm::image) || !image_plan(a.n, a.H, a.W, a.pad, a.opt.conv_strip, &p, &S, &lds, shift) || S != f.S)
+        return hipErrorInvalidValue;
     p.act_w = a.act_w; p.act_q = a.act_q; p.same_act = a.act_w == a.act_q;
+    const ImgKernel kernel = image_kernel(f.cls, S, f.SAME_ACT);
     // one round of the chip: as many workgroups as are co-resident
-    const void *fn = shift ? (S == 4 ? (const void *)gpfq_gram_shift_kernel<4, false> : S == 2 ? (const void *)gpfq_gram_shift_kernel<2, false>
-                                                                                        : (const void *)gpfq_gram_shift_kernel<1, false>)
-                           : (S == 4 ? (const void *)gpfq_gram_image_kernel<4> : S == 2 ? (const void *)gpfq_gram_image_kernel<2>
-                                                                                 : (const void *)gpfq_gram_image_kernel<1>);
+    // (the shift form has always been asked about as its SAME_ACT = false instantiation, whichever runs: asking about the one launched
+    //  could change nbx, and with it the order of the partial sums)
     int per_cu = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kImgThreads, lds) != hipSuccess || per_cu < 1) per_cu = 2;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)image_kernel(f.cls, S, false), kImgThreads, lds) != hipSuccess || per_cu < 1) per_cu = 2;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
         cus = 256;
     int64_t resident = (int64_t)per_cu * cus;
@@ -779,69 +781,30 @@ hipError_t launch_gram_image(const ImageGramArgs &a, hipStream_t stream)
     int64_t nbx = (resident + a.nch - 1) / a.nch;
     if (nbx > p.nbands) nbx = p.nbands;
     p.nbx = (int)nbx;
-    char *ws = static_cast<char *>(a.workspace);
-    double *part = reinterpret_cast<double *>(ws);  ws += al256i((size_t)(a.nch + kImgBlocks) * 2 * kRec9 * sizeof(double));
-    double *gram = reinterpret_cast<double *>(ws);  ws += al256i((size_t)a.nch * kRec9 * sizeof(double));
-    float *nrm = reinterpret_cast<float *>(ws);     ws += al256i((size_t)a.nch * 9 * sizeof(float));
-    float *q32h = reinterpret_cast<float *>(ws);    ws += al256i((size_t)a.nch * a.F * 9 * sizeof(float));
-    void *fixws = ws;                               ws += gram_fix_bytes();
-    int *negflag = reinterpret_cast<int *>(ws);
-    hipError_t e;
-    if (a.phase == 2) {                                    // records formed elsewhere (and summed over the column shards)
-        e = hipMemcpyAsync(negflag, a.negflags, (size_t)a.nch * sizeof(int), hipMemcpyDeviceToDevice, stream);
+    const GramAreas w = gram_areas(9, a.nch, a.F, gram_image_part_records(a.nch), false);
+    if (a.phase != 2) {
+        p.part = gram_area<double>(a.workspace, w.part);
+        p.negflag = gram_area<int>(a.workspace, w.negflag);
+        double *gram = gram_area<double>(a.workspace, w.gram);
+        float *nrm = gram_area<float>(a.workspace, w.nrm);
+        hipError_t e = hipMemsetAsync(p.negflag, 0, (size_t)a.nch * sizeof(int), stream);
         if (e != hipSuccess) return e;
-        e = launch_gram_reduce(a.records, 1, 9, gram, nrm, a.nch, stream);
-        if (e != hipSuccess) return e;
-    } else {
-        hipError_t e0 = hipMemsetAsync(negflag, 0, (size_t)a.nch * sizeof(int), stream);
-        if (e0 != hipSuccess) return e0;
-        p.part = part;
-        p.negflag = negflag;
-        const dim3 grid((unsigned)nbx, (unsigned)a.nch), block(kImgThreads);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nbx, (unsigned)a.nch), dim3(kImgThreads), lds, stream, p);
         if (shift) {
             // partials: [nch][nbx][9 classes][27], inside the area sized for the per-output-position form's records
-#define GPFQ_SHIFT(S_)                                                                                                   \
-            do {                                                                                                             \
-                if (p.same_act) hipLaunchKernelGGL((gpfq_gram_shift_kernel<S_, true>), grid, block, lds, stream, p);         \
-                else hipLaunchKernelGGL((gpfq_gram_shift_kernel<S_, false>), grid, block, lds, stream, p);                   \
-            } while (0)
-            switch (S) {
-            case 4:  GPFQ_SHIFT(4); break;
-            case 2:  GPFQ_SHIFT(2); break;
-            default: GPFQ_SHIFT(1); break;
-            }
-#undef GPFQ_SHIFT
-            hipLaunchKernelGGL(gpfq_gram_shift_combine_kernel, dim3((unsigned)a.nch), dim3(256), 0, stream, part, (int)nbx, gram, nrm);
+            hipLaunchKernelGGL(gpfq_gram_shift_combine_kernel, dim3((unsigned)a.nch), dim3(256), 0, stream, p.part, (int)nbx, gram, nrm);
             e = hipGetLastError();
-            if (e != hipSuccess) return e;
         } else {
-        switch (S) {
-        case 4:  hipLaunchKernelGGL(gpfq_gram_image_kernel<4>, grid, block, lds, stream, p); break;
-        case 2:  hipLaunchKernelGGL(gpfq_gram_image_kernel<2>, grid, block, lds, stream, p); break;
-        default: hipLaunchKernelGGL(gpfq_gram_image_kernel<1>, grid, block, lds, stream, p); break;
+            e = hipGetLastError();
+            if (e == hipSuccess) e = launch_gram_reduce(p.part, nbx * 2, 9, gram, nrm, a.nch, stream);
         }
-        e = hipGetLastError();
         if (e != hipSuccess) return e;
-        e = launch_gram_reduce(part, nbx * 2, 9, gram, nrm, a.nch, stream);
-        if (e != hipSuccess) return e;
-        }
-        if (a.phase == 1) {
-            e = hipMemcpyAsync(a.records, gram, (size_t)a.nch * kRec9 * sizeof(double), hipMemcpyDeviceToDevice, stream);
-            if (e != hipSuccess) return e;
-            return hipMemcpyAsync(a.negflags, negflag, (size_t)a.nch * sizeof(int), hipMemcpyDeviceToDevice, stream);
-        }
     }
-    DecideBatch bs;
-    bs.nch = a.nch; bs.gram_cs = kRec9; bs.nrm_cs = 9; bs.w_cs = a.F * 9; bs.out_cs = a.F * 9; bs.unc_cs = a.F; bs.hist_cs = a.F * 9;
     FixSrc src{};
-    src.X = a.act_w; src.Xq = a.act_q; src.ld = 0; src.planes = 1; src.plane = p.plane; src.pix = 1;
-    src.n = p.n; src.H = p.H; src.W = p.W; src.oh = p.oh; src.ow = p.SPR * S;
+    src.X = a.act_w; src.Xq = a.act_q; src.ld = 0; src.m = f.cols; src.planes = 1; src.plane = p.plane; src.pix = 1;
+    src.n = p.n; src.H = p.H; src.W = p.W; src.oh = (int)f.oh; src.ow = (int)f.ow;
     src.kw = 3; src.sh = src.sw = src.rh = src.rw = 1; src.pt = src.pl = p.pad;
-    src.m = (int64_t)p.grows * src.ow;
-    e = launch_canonical_norms(src, 9, a.nch, nrm, 9, fixws, stream);           // few channels: norms in an order fixed by the dimensions
-    if (e != hipSuccess) return e;
-    return launch_gram_decide(gram, nrm, a.Wt, 9, a.A, 9, a.F, a.slack, a.qidx, a.Qt, a.uncertified, q32h, bs, &src, fixws, negflag,
-                              stream, a.big);
+    return finish_gram_records(a, f, src, w, stream);
 }
 
 // ---- NHWC entry: 3 x 3, stride 1, SAME, all channels of the shard in one launch chain ----

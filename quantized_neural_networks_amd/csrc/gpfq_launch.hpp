@@ -199,7 +199,7 @@ struct ImageGramArgs {
     int32_t *uncertified;         // [nch][F]
     void *workspace;
     double slack = 1.0;
-    Options opt;                  // the call's snapshot (conv_strip, conv_shift; conv_nhwc_halves, conv_nhwc_slots)
+    Options opt;                  // the call's snapshot (conv_strip; conv_nhwc_halves, conv_nhwc_slots)
     int64_t nhwc_cin = 0;         // launch_gram_image_nhwc: act_w / act_q are NHWC tensors (offset to the shard's first channel) of this many channels
     // phase 1: stop after the Gram records (written to `records` [nch][171] f64 and `negflags` [nch] i32);
     // phase 2: take the records from there instead of forming them (column-sharded multi-GPU runs sum them in between)
@@ -212,8 +212,7 @@ struct ImageGramArgs {
 struct ConvGramArgs {
     const float *act_w, *act_q;   // channel-major planes [nch][n][H][W]
     int64_t n, H, W, nch;
-    int kh, kw, sh, sw, rh, rw, pt, pl;
-    int64_t oh, ow;
+    int kh, kw, sh, sw, rh, rw;   // (output size and padding: the call's ConvForm)
     const float *Wt;              // [nch][F][kh*kw]
     AlphabetArg A;
     const AlphabetBig *big = nullptr;   // as GramArgs
@@ -223,25 +222,87 @@ struct ConvGramArgs {
     int32_t *uncertified;         // [nch][F]
     void *workspace;
     double slack = 1.0;
-    Options opt;            // the call's snapshot (variant bit 2: vector-unit tiles instead of the matrix cores for 16 < kh*kw <= 64; conv_s2)
     int phase = 0;          // as ImageGramArgs: 1 = records only, 2 = from records ([nch][K*K*2 + K] f64, [nch] i32)
     double *records = nullptr;
     int32_t *negflags = nullptr;
-    double *s2_part = nullptr;   // gram_s2_workspace_bytes of scratch behind the workspace proper (7x7 / 2 layers; NULL: the matrix-core kernel)
     int64_t pix = 1;             // > 1: act_w / act_q are NHWC tensors of this many channels, offset to the shard's first channel (7x7 / 2 shift-sum form only)
 };
-bool gram_conv_supported(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int64_t oh, int64_t ow);
-size_t gram_conv_workspace_bytes(int64_t K, int64_t nch, int64_t F, int64_t m);
-hipError_t launch_gram_conv(const ConvGramArgs &a, hipStream_t stream);
+
+// Which Gram kernel a conv channel-loop call runs, decided ONCE (resolve_conv_form, gpfq_gram_conv.hip; DESIGN.md section 4.3 states the
+// rules): the C API's size functions, its queries, the call itself and both launchers read this and hold no form rule of their own.
+struct ConvForm {
+    enum Class { none, loop, image, shift, tile, mfma, s2 };
+    // none:  invalid or empty shape, or no kernel (too_large; NHWC activations anywhere but the shift sums)
+    // loop:  per-channel patch matrices + launch_gram (residual norms wanted, option conv_fused = 0, shapes no plane kernel takes)
+    // image, shift: 3 x 3 / stride 1 from the planes, per output position / the shift form (launch_gram_image)
+    // tile, mfma, s2: any other shape on the vector units / the matrix cores, 7 x 7 / 2 / VALID shift sums (launch_gram_conv)
+    Class cls = none;
+    bool too_large = false;                     // kh * kw > GPFQ_GRAM_MAX_N or n * oh * ow >= 2^30: beyond the records' error bounds
+    int64_t oh = 0, ow = 0, cols = 0, K = 0;    // output size, columns n * oh * ow and rows kh * kw of a channel's patch matrix
+    int pad_top = 0, pad_left = 0;              // SAME padding above / left of the image (0 for VALID)
+    // the instantiation within the class (zero where the class has no such template argument)
+    int S = 0;                                  // image, shift: strip length
+    int NB = 0;                                 // mfma: 16-row blocks on the matrix cores, REM1: one more row on the vector units,
+    bool REM1 = false, PADDED = false;          //       PADDED: taps outside the image
+    int TB = 0, SB = 0;                         // tile
+    bool SAME_ACT = false;                      // shift, s2: act_w == act_q
+    int64_t parts = 0;                          // tile, mfma, s2: partial records per channel the workspace holds (either tile kernel fits)
+    size_t workspace_bytes = 0;                 // gpfq_conv_channels_workspace_bytes (the same whether the activations are planes or NHWC)
+    size_t s2_offset = 0;                       // where the shift sums' scratch starts, wherever the shape takes them (else 0)
+};
+ConvForm resolve_conv_form(int64_t n, int64_t H, int64_t W, int64_t nch, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
+                           int64_t F, bool want_resid, bool nhwc, bool same_act, const Options &opt);
+void conv_form_query(const ConvForm &f, int32_t out[8]);   // {class, three instantiation numbers, SAME_ACT, K, 0, 0} (gpfq_conv_form)
+
+// The areas the plane kernels' launchers carve from their workspace, as byte offsets: partial records, [nch] Gram records, row norms,
+// chosen values per filter and step, the repair pass's scratch, sign flags (, a zero word for out-of-image taps).
+struct GramAreas {
+    size_t part, gram, nrm, q32h, fix, negflag, zero, bytes;
+};
+GramAreas gram_areas(int64_t K, int64_t nch, int64_t F, int64_t part_records, bool zero_word);
+template <class T> T *gram_area(void *workspace, size_t offset) { return reinterpret_cast<T *>(static_cast<char *>(workspace) + offset); }
+// What follows the record kernels, whichever ran (a: ImageGramArgs or ConvGramArgs; src: the planes the repair pass reads): phase 2 takes
+// records and flags from the caller instead, phase 1 hands them out and stops, else canonical norms and the batched decide + repair.
+template <class Args>
+hipError_t finish_gram_records(const Args &a, const ConvForm &f, const FixSrc &src, const GramAreas &w, hipStream_t stream)
+{
+    const int K = (int)f.K;
+    const int64_t rec = f.K * f.K * 2 + f.K;               // gram_record(K)
+    double *gram = gram_area<double>(a.workspace, w.gram);
+    float *nrm = gram_area<float>(a.workspace, w.nrm);
+    int *negflag = gram_area<int>(a.workspace, w.negflag);
+    void *fixws = gram_area<char>(a.workspace, w.fix);
+    hipError_t e;
+    if (a.phase == 2) {                                    // records formed elsewhere (and summed over the column shards)
+        e = hipMemcpyAsync(negflag, a.negflags, (size_t)a.nch * sizeof(int), hipMemcpyDeviceToDevice, stream);
+        if (e != hipSuccess) return e;
+        e = launch_gram_reduce(a.records, 1, K, gram, nrm, a.nch, stream);
+        if (e != hipSuccess) return e;
+    } else if (a.phase == 1) {
+        e = hipMemcpyAsync(a.records, gram, (size_t)a.nch * rec * sizeof(double), hipMemcpyDeviceToDevice, stream);
+        if (e != hipSuccess) return e;
+        return hipMemcpyAsync(a.negflags, negflag, (size_t)a.nch * sizeof(int), hipMemcpyDeviceToDevice, stream);
+    }
+    DecideBatch bs;
+    bs.nch = a.nch; bs.gram_cs = rec; bs.nrm_cs = K; bs.w_cs = a.F * K; bs.out_cs = a.F * K; bs.unc_cs = a.F; bs.hist_cs = a.F * K;
+    e = launch_canonical_norms(src, K, a.nch, nrm, K, fixws, stream);           // few channels: norms in an order fixed by the dimensions
+    if (e != hipSuccess) return e;
+    return launch_gram_decide(gram, nrm, a.Wt, K, a.A, K, a.F, a.slack, a.qidx, a.Qt, a.uncertified, gram_area<float>(a.workspace, w.q32h), bs,
+                              &src, fixws, negflag, stream, a.big);
+}
+hipError_t launch_gram_conv(const ConvGramArgs &a, const ConvForm &f, hipStream_t stream);
 // 7x7 / stride 2 / VALID (ResNet50's conv1): the Gram records from shift sums of the parity classes of the planes (gpfq_gram_s2.hip)
 bool gram_s2_supported(int64_t n, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int rh, int rw, int pt, int pl, int64_t nch);
 size_t gram_s2_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch);
 hipError_t launch_gram_s2(const float *act_w, const float *act_q, int64_t n, int64_t H, int64_t W, int64_t nch, double *part,
                           double *gram, float *nrm32, int *negflag, hipStream_t stream, int64_t pix = 1);
 
+// 3 x 3 / stride 1 / rate 1 (gpfq_gram_image.hip), the resolver's building blocks: whether the per-position form stages these planes,
+// and the strip length the per-position (shift = false) or the shift form takes under option conv_strip (0: the form declines)
 bool gram_image_supported(int64_t n, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding);
-size_t gram_image_workspace_bytes(int64_t nch, int64_t F);
-hipError_t launch_gram_image(const ImageGramArgs &a, hipStream_t stream);
+int gram_image_strip(int64_t n, int64_t H, int64_t W, int pad, int conv_strip, bool shift);
+int64_t gram_image_part_records(int64_t nch);
+hipError_t launch_gram_image(const ImageGramArgs &a, const ConvForm &f, hipStream_t stream);
 // The same from NHWC activations (ImageGramArgs::nhwc_cin; 3 x 3 / stride 1 / SAME, phase 0 only): no channel-major copy
 bool gram_image_nhwc_supported(int64_t n, int64_t H, int64_t W, int64_t nch, const Options &opt);
 size_t gram_image_nhwc_workspace_bytes(int64_t n, int64_t H, int64_t W, int64_t nch, int64_t F, const Options &opt);

@@ -96,6 +96,7 @@ SYMBOLS = {
     "gpfq_quantize_conv_channels": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
                                            _vp, _dp, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpfq_conv_records_supported": (_int, [_i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int]),
+    "gpfq_conv_form": (_int, [_i64, _i64, _i64, _i64] + [_int] * 10 + [ctypes.POINTER(ctypes.c_int32)]),
     "gpfq_conv_channel_records": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
                                          _vp, _vp, _vp, _sz, _vp]),
     "gpfq_quantize_conv_channels_from_records": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int,
@@ -635,6 +636,20 @@ def blk_instance(N, m, C, unit_alphabet):
     if not load().gpfq_blk_instance(int(N), int(m), int(C), arr, len(unit_alphabet), out):
         return None
     return BlkInstance(*out)
+
+
+def conv_form(n, H, W, nch, kernel_size, strides, rate, padding, want_resid=False, nhwc=False, same_act=False):
+    """The Gram kernel a conv channel-loop call of this shape would run under the current options (gpfq_conv_form: the library's one
+    resolver), as 'class/instantiation': 'image/S2', 'shift/S4', 'tile/2x8', 'mfma/NB2+1/padded', 's2/7x7'; 'loop' for the per-channel
+    patch matrices; None where the call would run nothing.  Host only: needs no device."""
+    out = (ctypes.c_int32 * 8)()
+    geo = conv_geometry(kernel_size, strides, rate, padding)
+    if not load().gpfq_conv_form(int(n), int(H), int(W), int(nch), *geo, int(bool(want_resid)), int(bool(nhwc)), int(bool(same_act)), out):
+        return None
+    cls, a, b, c = ("none", "loop", "image", "shift", "tile", "mfma", "s2")[out[0]], out[1], out[2], out[3]
+    if cls == "mfma":
+        return f"mfma/NB{a}{'+1' if b else ''}/{'padded' if c else 'unpadded'}"
+    return {"loop": "loop", "image": f"image/S{a}", "shift": f"shift/S{a}"}.get(cls, f"{cls}/{a}x{b}")
 
 
 def device_alphabet_ok(median32, unit_alphabet, alphabet_scalar):

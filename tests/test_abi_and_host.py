@@ -479,3 +479,60 @@ def test_blk_instance_is_total(lib, blk_instances):
     assert missing.size == 0, missing[:10]
     kout = np.argwhere(got[..., 8] != sup[..., 1])
     assert kout.size == 0, kout[:10]
+
+
+@pytest.fixture(scope="module")
+def conv_forms(lib):
+    """(generator module, its answers from the library under test, the golden): computed once for the tests below, which leave it unchanged."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_conv_forms_golden", os.path.join(ROOT, "tools", "gen_conv_forms_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    got = gen.answers(lib)
+    _assert_options_at_defaults(lib)
+    want = np.load(os.path.join(ROOT, "tests", "golden", "conv_forms.npz"))
+    assert (tuple(want["options"]), tuple(want["geometry"]), tuple(want["classes"])) == (tuple(k for k, _ in gen.OPTIONS), gen.GEOMETRY, gen.CLASSES)
+    assert [tuple(c) for c in want["calls"]] == list(gen.CALLS) and int(want["F"]) == gen.F
+    assert np.array_equal(want["cells"], gen.cells()) and want["cells"].shape == (17, 14702)
+    return gen, got, want
+
+
+def test_conv_forms_match_golden(lib, conv_forms):
+    """(a) gpfq_conv_form, gpfq_conv_channels_workspace_bytes and the two `supported` queries over the list of tools/gen_conv_forms_golden.py
+    equal, cell for cell, what the commit named in that script launched, sized and answered (tests/golden/conv_forms.npz, the forms
+    recorded there by a dry-run hook -- never regenerated from the code under test)."""
+    gen, (ws, sup, forms), want = conv_forms
+    for name, got in (("workspace", ws), ("supported", sup), ("forms", forms)):
+        assert got.shape == want[name].shape and got.dtype == want[name].dtype, name
+        differ = np.argwhere(got != want[name])
+        assert differ.size == 0, (name, [(d.tolist(), want["cells"][:, d[-1]].tolist()) for d in differ[:5]])
+
+
+def test_conv_forms_reach_every_instantiation(lib, conv_forms):
+    """(b) every class, and every instantiation that has a kernel, is the answer somewhere in the list."""
+    gen, (ws, sup, forms), want = conv_forms
+    found = forms[:, 0] == 1
+    seen = {tuple(r) for r in forms.transpose(0, 2, 1)[found][:, 1:6].tolist()}                 # (class, a, b, c, SAME_ACT)
+    cls = {name: i for i, name in enumerate(gen.CLASSES)}
+    assert set(np.unique(forms[:, 1])) == set(range(len(gen.CLASSES))) and not found[forms[:, 1] == 0].any() and found[forms[:, 1] != 0].all()
+    assert {(cls["image"], S, 0, 0, 0) for S in (1, 2, 4)} <= seen
+    assert {(cls["shift"], S, 0, 0, same) for S in (1, 2, 4) for same in (0, 1)} <= seen
+    assert {(cls["mfma"], nb, rem, padded, 0) for nb in (1, 2, 3, 4) for rem in (0, 1) for padded in (0, 1) if (nb, rem) != (4, 1)} <= seen
+    assert {(cls["tile"], 2, 8, 0, 0), (cls["loop"], 0, 0, 0, 0), (cls["s2"], 7, 7, 0, 0), (cls["s2"], 7, 7, 0, 1)} <= seen
+    assert len(seen) == 3 + 6 + 14 + 4, sorted(seen)                                            # ... and nothing else
+    # REM1 is the row past a block edge: K = 17, 33, 49 and no other
+    mfma = forms.transpose(0, 2, 1)[forms[:, 1] == cls["mfma"]]
+    assert set(np.unique(mfma[mfma[:, 3] == 1][:, 6])) == {17, 33, 49} and not set(np.unique(mfma[mfma[:, 3] == 0][:, 6])) & {17, 33, 49}
+
+
+def test_conv_forms_are_consistent(lib, conv_forms):
+    """(c) what the golden shows of the parent, held on the library under test: a workspace size is 0 in the same cells, and
+    gpfq_conv_records_supported is 1 exactly where the form of a call without residual norms on channel planes is neither none nor loop."""
+    gen, (ws, sup, forms), want = conv_forms
+    assert np.array_equal(ws == 0, want["workspace"] == 0) and (ws == 0).any() and not (ws == 0).all()
+    cls = {name: i for i, name in enumerate(gen.CLASSES)}
+    for f, s in ((want["forms"], want["supported"]), (forms, sup)):
+        for same_act in (0, 1):
+            planes = f[gen.CALLS.index((0, 0, same_act)), 1]
+            assert np.array_equal(s[0] == 1, (planes != cls["none"]) & (planes != cls["loop"]))
+    assert set(np.unique(sup)) == {0, 1}

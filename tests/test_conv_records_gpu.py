@@ -5,7 +5,8 @@ unequal strides and rates, every instantiation of the matrix-core kernel.  Then 
 same shapes against the CPU oracle through the three routes a layer can take.
 
 Records are compared with the NumPy reference only, never with another GPU form.  Which kernel a case runs is stated by hand
-(`want`) and held against the launchers' rules restated below and, where the library has one, its query."""
+(`want`) and held against the launchers' rules restated below (the independent statement) and against the library's own answer,
+hip.conv_form."""
 import functools
 import os
 import sys
@@ -217,6 +218,7 @@ def test_records(hip, want, n, H, W, nch, geom, kind, opt):
     with hip.options(**opt):
         form = expected_form(hip, n, H, W, nch, geom, opt)
         assert form == want, form
+        assert hip.conv_form(n, H, W, nch, *conv, same_act=act_q is act_w) == want                # the library's own statement
         assert hip.conv_records_supported(n, H, W, nch, *conv)
         if want == "s2/7x7":
             assert hip.conv_channels_nhwc_supported(n, H, W, nch, *conv)
@@ -292,6 +294,7 @@ def test_sign_flags(hip, want, n, H, W, geom, opt, where, tensor):
     t[spot + (1,)] = -t[spot + (1,)]
     with hip.options(**opt):
         assert expected_form(hip, n, H, W, 2, geom, opt).split("/")[0] == want
+        assert hip.conv_form(n, H, W, 2, *conv) == expected_form(hip, n, H, W, 2, geom, opt)
         rec, neg = hip.conv_channel_records(*_planes(hip, act_w, act_q, 2), *conv)
         torch.cuda.synchronize()
     neg = neg.cpu().numpy()
@@ -383,6 +386,7 @@ def test_decisions(hip, oracle_mod, want, n, H, W, k, s, r, pad, nch, opt, M, ki
     with hip.options(**opt):
         if want != "nhwc3x3":
             assert expected_form(hip, n, H, W, nch, geom, opt).split("/")[0] == want
+            assert hip.conv_form(n, H, W, nch, *conv, same_act=aq is aw) == expected_form(hip, n, H, W, nch, geom, opt)
         pw = hip.channel_planes(aw, 0, nch)
         pq = pw if aq is aw else hip.channel_planes(aq, 0, nch)
         idx, Q, unc = outputs()
