@@ -82,6 +82,9 @@ def main():
     ap.add_argument("--refine-form", choices=("residual", "gram"), default="residual",
                     help="the refinement sweeps on the residual held on chip (rows of up to 8192 samples), or on the Gram matrix of the "
                          "layer's inputs (rows of any length; DESIGN.md section 12, addendum)")
+    ap.add_argument("--refine-channel-walks", action="store_true",
+                    help="with --refine-passes: also refine the walks per (input channel, filter) pair -- Conv2D layers under --conv-walk "
+                         "channel and every DepthwiseConv2D layer (DESIGN.md section 12b)")
     ap.add_argument("--export-packed", default=None, metavar="PATH",
                     help="also write the quantized network in the packed low-bit form (deploy.export_packed; with several settings the "
                          "file holds the last one's)")
@@ -102,7 +105,7 @@ def main():
         my_quant_net = QuantizedCNN(network=model, batch_size=params.q_train_size, get_data=get_data, logger=quiet,
                                     bits=params.bits, alphabet_scalar=params.alphabet_scalar, radius=args.radius,
                                     conv_walk=args.conv_walk, conv_columns=args.conv_columns, refine_passes=args.refine_passes,
-                                    refine_form=args.refine_form)
+                                    refine_form=args.refine_form, refine_channel_walks=args.refine_channel_walks)
         tic = time()
         my_quant_net.quantize_network()
         quantization_time = time() - tic

@@ -100,7 +100,8 @@ def preprocess(x):
     return (np.asarray(x, dtype=np.float32) - np.array([103.939, 116.779, 123.68], dtype=np.float32)) / 64.0
 
 
-def quantize_network(parameters, dir_data, dir_processed_images, logger, save_dir, classes, conv_walk="channel", conv_columns=8192):
+def quantize_network(parameters, dir_data, dir_processed_images, logger, save_dir, classes, conv_walk="channel", conv_columns=8192,
+                     refine_passes=0, refine_channel_walks=False):
     import pandas as pd
     model, model_name_analog = parameters.pretrained_model
     np.random.seed(np_seed)                                               # the seeds for splitting training and testing (:104-106)
@@ -123,7 +124,8 @@ def quantize_network(parameters, dir_data, dir_processed_images, logger, save_di
     my_quant_net = QuantizedCNN(network=model, batch_size=parameters.q_train_size, get_data=quantization_train_generator,
                                 logger=logger, bits=parameters.bits, alphabet_scalar=parameters.alphabet_scalar,
                                 patch_mini_batch_size=1000, is_quantize_conv2d=parameters.is_quantize_conv2d,
-                                conv_walk=conv_walk, conv_columns=conv_columns)
+                                conv_walk=conv_walk, conv_columns=conv_columns, refine_passes=refine_passes, refine_form="gram",
+                                refine_channel_walks=refine_channel_walks)
     tic = time()
     my_quant_net.quantize_network()
     quantization_time = time() - tic
@@ -173,6 +175,11 @@ def main():
     ap.add_argument("--conv-walk", choices=["channel", "filter"], default="channel",
                     help="Conv2D layers: one walk per (input channel, filter) pair (the reference's rule) or one per whole filter")
     ap.add_argument("--conv-columns", type=int, default=8192, help="patch columns sampled per Conv2D layer with --conv-walk filter")
+    ap.add_argument("--refine-passes", type=int, default=0, metavar="K",
+                    help="up to K refinement sweeps after a layer's walk, on Gram matrices (DESIGN.md section 12, addendum); 0: none")
+    ap.add_argument("--refine-channel-walks", action="store_true",
+                    help="with --refine-passes: also refine the walks per (input channel, filter) pair -- Conv2D layers under --conv-walk "
+                         "channel and every DepthwiseConv2D layer (DESIGN.md section 12b)")
     ap.add_argument("--bits", type=float, nargs="+", default=[np.log2(3)])
     ap.add_argument("--scalars", type=float, nargs="+", default=[2.0])
     ap.add_argument("--csv", default=None, help="append the metrics rows here (reference schema and append semantics)")
@@ -196,7 +203,8 @@ def main():
     n_rows = 0
     for idx, params in enumerate(ParamConfig(*c) for c in grid):
         trial_metrics = quantize_network(params, dir_data, dir_processed, quiet, args.save_dir, args.classes,
-                                         conv_walk=args.conv_walk, conv_columns=args.conv_columns)
+                                         conv_walk=args.conv_walk, conv_columns=args.conv_columns, refine_passes=args.refine_passes,
+                                         refine_channel_walks=args.refine_channel_walks)
         if args.csv:                                    # header with the first row only, rows appended (:283-291)
             trial_metrics.to_csv(args.csv, mode="a", header=(idx == 0))
         n_rows += 1

@@ -579,6 +579,50 @@ int gpfq_refine_gram_neurons(const double *G, int64_t ldg,        /* [device] f6
                              void *stream);
 
 /*
+ * Refinement sweeps for the walks per (input channel, filter) pair of a conv layer: Conv2D layers under
+ * conv_walk="channel" and DepthwiseConv2D layers.  A pair (c, f) is a neuron of K = kh*kw weights over the rows of channel c's patch
+ * matrices X_c, Xq_c [K][cols]; the Gram form of the sweeps needs G = Xq_c Xq_c^T and C = Xq_c X_c^T only, and both come from the
+ * records of gpfq_conv_channel_records ([K*K*2 + K] per channel: G1[t][s] = <Xq_t, X_s> at (t*K + s)*2, G2[t][s] = <Xq_t, Xq_s> at
+ * (t*K + s)*2 + 1, s <= t):
+ *   G         G[t][s] = G[s][t] = records' G2[max(t, s)][min(t, s)].
+ *   C         C[t][s] = records' G1[t][s] for s <= t; for s > t records_swapped's G1[s][t] (the records of the same call with the
+ *             two activation tensors swapped: <X_s, Xq_t>); records_swapped NULL (act_w == act_q, a first layer: C is symmetric)
+ *             reads records' G1[s][t] there.
+ *   values    a_k = radii[c][f] * unit_alphabet[k]; index -1, or any index outside [0, M), has the value 0 and is never revisited.
+ *   start     h_t = 0, then for s = 0 .. K-1 in order: h_t = h_t + C[t][s] * (double)w_s, then h_t = h_t - G[t][s] * a_{k_s}.
+ *   a sweep   as gpfq_refine_gram_neurons with nrm32[t] = (float)sqrt(G[t][t]): for t = 0 .. K-1 nothing happens when
+ *             nrm32[t] < 1e-16 or k_t is outside [0, M); otherwise v = a_{k_t} + h_t / G[t][t], k' = the first index of
+ *             min_k |a_k - v|, and only if |a_k' - v| < |a_{k_t} - v| strictly: delta = a_k' - a_{k_t},
+ *             h_s = h_s - (delta * G[s][t]) for every s, k_t = k'.
+ *   passes    up to `sweeps` sweeps; a pair whose sweep changed nothing takes no further one.
+ * Everything is float64 and every product, quotient and sum is rounded on its own (no fused multiply-add): given the records the
+ * results are bitwise those of a sequential evaluation, on any data.
+ * Outputs: qidx updated in place; Qt[c][f][t] = (float)a_{k_t} (0.0f for the literal zero) for every t; changed[c][f] = the steps
+ * accepted, sweeps_run[c][f] = the sweeps taken (the one that changed nothing included), gain[c][f] = the sum over the accepted steps,
+ * in their order, of G[t][t] * ((a_{k_t} - v)^2 - (a_k' - v)^2): the decrease of ||X_c^T w - Xq_c^T q||^2 in exact arithmetic.
+ * One thread per pair; a workgroup (one wavefront) takes 64 filters of one channel and holds that channel's G and C in LDS, read at
+ * one address by all lanes.  K = 1, 4, 9, 25 keep a pair's h and indices in registers; every other K keeps them in lane-contiguous
+ * LDS columns.  One launch, no workspace, no host synchronisation, no atomics, nothing exchanged between workgroups.
+ *   records, records_swapped [device] f64 [nch][K*K*2 + K], 8-byte aligned; Wt [device] f32 [nch][F][K] (gpfq_quantize_conv_channels'
+ *   layout); radii [device] f64 [nch][F]; unit_alphabet [host] f64 [M], 1 <= M <= GPFQ_MAX_ALPHABET, in any order, finite; qidx
+ *   [device] [nch][F][K]: i8 for M <= 64, i16 beyond; Qt [device] f32 [nch][F][K] or NULL; changed, sweeps_run [device] i32 [nch][F],
+ *   gain [device] f64 [nch][F]: each may be NULL.
+ * K > GPFQ_REFINE_PAIRS_MAX_K: GPFQ_ERR_UNSUPPORTED; K < 1, sweeps < 1: GPFQ_ERR_INVALID_ARG; M as every alphabet.  nch == 0 or
+ * F == 0: success.  A refused call launches nothing.
+ */
+#define GPFQ_REFINE_PAIRS_MAX_K 64      /* = the whole-shard Gram call's bound, GPFQ_GRAM_AUTO_MAX_N */
+int gpfq_refine_conv_pairs(const double *records,          /* [device] f64 [nch][2K^2+K]: gpfq_conv_channel_records(act_w, act_q) */
+                           const double *records_swapped,  /* ... (act_q, act_w); NULL: act_w == act_q (a first layer) */
+                           int K, const float *Wt,         /* [device] f32 [nch][F][K], as gpfq_quantize_conv_channels takes it */
+                           const double *radii,            /* [device] f64 [nch][F]: one radius per pair */
+                           const double *unit_alphabet, int M,   /* [host] */
+                           int64_t nch, int64_t F, int sweeps,
+                           void *qidx,                     /* [device] [nch][F][K], i8 (M <= 64) / i16, updated IN PLACE */
+                           float *Qt,                      /* [device] f32 [nch][F][K] or NULL */
+                           int32_t *changed, int32_t *sweeps_run, double *gain,   /* [nch][F], each may be NULL */
+                           void *stream);
+
+/*
  * median(|W|) of n float32 weights with NumPy's semantics (float32 result; even n -> float32 mean of
  * the two middle values).  Replaces `median(abs(W.flatten()))` of the alphabet radius
  * (scripts/quantized_network.py:544, :831).  Exact radix select, no sort.

@@ -1009,6 +1009,37 @@ int gpfq_refine_gram_neurons(const double *G, int64_t ldg, double *H, int64_t ld
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_refine_gram_neurons");
 }
 
+// ---- refinement sweeps per (input channel, filter) pair of a conv layer (gpfq_refine_pairs.hip) ----
+
+int gpfq_refine_conv_pairs(const double *records, const double *records_swapped, int K, const float *Wt, const double *radii,
+                           const double *unit_alphabet, int M, int64_t nch, int64_t F, int sweeps, void *qidx, float *Qt,
+                           int32_t *changed, int32_t *sweeps_run, double *gain, void *stream)
+{
+    if (nch < 0 || F < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size nch=%lld F=%lld", (long long)nch, (long long)F);
+    if (K < 1) return fail(GPFQ_ERR_INVALID_ARG, "K=%d must be >= 1", K);
+    if (sweeps < 1) return fail(GPFQ_ERR_INVALID_ARG, "sweeps=%d must be >= 1", sweeps);
+    HostAlphabet H_;
+    int rc = make_alphabet(unit_alphabet, M, -1, &H_);
+    if (rc != GPFQ_OK) return rc;
+    if (K > GPFQ_REFINE_PAIRS_MAX_K)
+        return fail(GPFQ_ERR_UNSUPPORTED, "refinement per (channel, filter) pair needs kh*kw <= GPFQ_REFINE_PAIRS_MAX_K=%d (got %d)",
+                    GPFQ_REFINE_PAIRS_MAX_K, K);
+    if (nch == 0 || F == 0) return GPFQ_OK;
+    if (nch > 2147483647LL / ((F + 63) / 64)) return fail(GPFQ_ERR_UNSUPPORTED, "more than 2^31 - 1 tiles of 64 pairs in one call");
+    if (!records || !Wt || !radii || !qidx) return fail(GPFQ_ERR_INVALID_ARG, "records/Wt/radii/qidx is NULL");
+    if ((uintptr_t)records % 8 != 0 || (uintptr_t)records_swapped % 8 != 0 || (uintptr_t)radii % 8 != 0)
+        return fail(GPFQ_ERR_INVALID_ARG, "records and radii must be 8-byte aligned");
+    if (H_.is_big && (uintptr_t)qidx % 2 != 0) return fail(GPFQ_ERR_INVALID_ARG, "int16 indices must be 2-byte aligned");
+    gpfq::RefinePairsArgs a{};
+    a.records = records; a.records_swapped = records_swapped; a.K = K; a.Wt = Wt; a.radii = radii;
+    a.U.M = M;
+    for (int k = 0; k < M; ++k) a.U.a[k] = unit_alphabet[k];
+    a.nch = nch; a.F = F; a.sweeps = sweeps; a.qidx = qidx; a.Qt = Qt;
+    a.changed = changed; a.sweeps_run = sweeps_run; a.gain = gain;
+    hipError_t e = gpfq::launch_refine_pairs(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_refine_conv_pairs");
+}
+
 size_t gpfq_median_abs_workspace_bytes(void) { return gpfq::median_workspace_bytes() + 64; }
 size_t gpfq_median_abs_workspace_bytes_for(int64_t n) { return n > 0 ? gpfq::median_workspace_bytes_fast(n) : gpfq::median_workspace_bytes() + 64; }
 

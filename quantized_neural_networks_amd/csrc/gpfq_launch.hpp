@@ -402,6 +402,23 @@ struct RefineGramArgs {
     double *gain;                                // [C] or NULL
 };
 hipError_t launch_refine_gram(const RefineGramArgs &a, hipStream_t stream);
+// gpfq_refine_pairs.hip (refine_channel_walks): the sweeps of every (input channel, filter) pair of a conv layer
+// on the channel's Gram records, one thread per pair
+constexpr int kRefinePairsMaxK = 64;
+struct RefinePairsArgs {
+    const double *records, *records_swapped;     // [nch][K*K*2 + K]; records_swapped may be NULL (act_w == act_q)
+    int K;
+    const float *Wt;                             // [nch][F][K]
+    const double *radii;                         // [device] f64 [nch][F]
+    AlphabetBig U;                               // the unit alphabet (any M <= 256; int16 indices beyond 64 members)
+    int64_t nch, F;
+    int sweeps;
+    void *qidx;                                  // [nch][F][K], updated in place
+    float *Qt;                                   // [nch][F][K] or NULL
+    int32_t *changed, *sweeps_run;               // [nch][F] or NULL
+    double *gain;                                // [nch][F] or NULL
+};
+hipError_t launch_refine_pairs(const RefinePairsArgs &a, hipStream_t stream);
 size_t median_workspace_bytes();
 size_t median_workspace_bytes_fast(int64_t n);   // ... with room for the one-GPU form's candidate list (gpfq_median_abs_workspace_bytes_for)
 size_t channel_sumsq_workspace_bytes(int64_t Cin);

@@ -25,6 +25,7 @@ GPFQ_ERR_CLUSTER_TIMEOUT, GPFQ_ERR_ALPHABET = -6, -7
 GPFQ_SEARCH_MAX_CANDIDATES = 16    # candidate scalars of one search (include/gpfq.h)
 GPFQ_REFINE_MAX_M = 8192           # longest row the refinement sweeps take (include/gpfq.h)
 GPFQ_REFINE_GRAM_MAX_N = 25600     # longest walk the refinement sweeps on the Gram matrix take (include/gpfq.h)
+GPFQ_REFINE_PAIRS_MAX_K = 64       # longest walk of an (input channel, filter) pair refine_conv_pairs takes (include/gpfq.h)
 GPFQ_ERR_INVALID_ARG, GPFQ_ERR_UNSUPPORTED, GPFQ_ERR_WORKSPACE = -1, -2, -3
 
 # every symbol include/gpfq.h declares: (restype, argtypes)
@@ -76,6 +77,7 @@ SYMBOLS = {
                                    _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpfq_refine_gram_neurons": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _dp, _int, _i64, _i64, _int, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
                                         _vp]),
+    "gpfq_refine_conv_pairs": (_int, [_vp, _vp, _int, _vp, _vp, _dp, _int, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gpfq_gram_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "gpfq_quantize_neurons_gram": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _i64, _dp, _int, _int, _i64, _i64, _i64,
                                           _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -997,6 +999,36 @@ def refine_gram_neurons(G, H, nrm32, idx, radii, unit_alphabet, sweeps, want_val
         _check(load().gpfq_refine_gram_neurons(pg, ldg, ph, ldh, nrm32.data_ptr(), radii.data_ptr(), arr, M, N, C, sweeps, pi, ldi, pQ, ldQ,
                                                res["changed"].data_ptr(), res["sweeps"].data_ptr(), res["gain"].data_ptr(), _stream()),
                "gpfq_refine_gram_neurons")
+    return res
+
+
+def refine_conv_pairs(records, records_swapped, K, Wt, radii, unit_alphabet, sweeps, idx, want_values=True):
+    """Refinement sweeps of every (input channel, filter) pair of a conv layer on its channel's Gram records
+    (gpfq_refine_conv_pairs, DESIGN.md section 12b).  records f64 [nch][K*K*2 + K] = conv_channel_records(planes of act_w, of act_q);
+    records_swapped the same call with the two arguments swapped, or None where act_q is act_w; Wt f32 [nch][F][K]; radii f64 [nch][F];
+    unit_alphabet a host sequence; idx [nch][F][K] (int8; int16 beyond 64 members), UPDATED IN PLACE.  Returns dict(Q f32 [nch][F][K]
+    or None, idx, changed i32 [nch][F], sweeps i32 [nch][F], gain f64 [nch][F]).  One launch, no workspace, no sync."""
+    arr, M, _ = _alphabet(unit_alphabet)
+    K, sweeps = int(K), int(sweeps)
+    _contiguous("refine_conv_pairs", ((records, torch.float64), (records_swapped, torch.float64), (Wt, torch.float32),
+                                      (radii, torch.float64), (idx, index_dtype(M))))
+    if Wt.dim() != 3 or Wt.shape[2] != K:
+        raise GpfqError(f"refine_conv_pairs: Wt {tuple(Wt.shape)} is not [nch][F][{K}]")
+    nch, F = Wt.shape[0], Wt.shape[1]
+    rlen = K * K * 2 + K
+    if (tuple(records.shape) != (nch, rlen) or (records_swapped is not None and tuple(records_swapped.shape) != (nch, rlen))
+            or tuple(radii.shape) != (nch, F) or tuple(idx.shape) != (nch, F, K)):
+        raise GpfqError("refine_conv_pairs: shape mismatch")
+    dev = Wt.device
+    Q = torch.empty((nch, F, K), dtype=torch.float32, device=dev) if want_values else None
+    res = dict(Q=Q, idx=idx, changed=torch.empty((nch, F), dtype=torch.int32, device=dev),
+               sweeps=torch.empty((nch, F), dtype=torch.int32, device=dev), gain=torch.empty((nch, F), dtype=torch.float64, device=dev))
+    with torch.cuda.device(dev):
+        _check(load().gpfq_refine_conv_pairs(records.data_ptr(), records_swapped.data_ptr() if records_swapped is not None else None, K,
+                                             Wt.data_ptr(), radii.data_ptr(), arr, M, nch, F, sweeps, idx.data_ptr(),
+                                             Q.data_ptr() if Q is not None else None, res["changed"].data_ptr(), res["sweeps"].data_ptr(),
+                                             res["gain"].data_ptr(), _stream()),
+               "gpfq_refine_conv_pairs")
     return res
 
 

@@ -719,6 +719,67 @@ def quantize_conv2d(W, act_w, act_q, alphabet, strides, padding, rate, group=Non
     return dict(Q=Q, idx=idx, resid=Rc.contiguous(), reruns=torch.tensor(reruns))
 
 
+def _pair_radii(radii, Cin, F, depthwise, device):
+    """f64 [Cin][F] on the device, one radius per (input channel, filter) pair, with no read-back: a DeviceAlphabet's radius or a host
+    number broadcast; f64 [F] (one per Conv2D filter) repeated over the channels; f64 [Cin * F] of a depthwise kernel (output channel
+    c * mult + d) viewed as it is."""
+    if isinstance(radii, hip.DeviceAlphabet):
+        return radii.buf[:8].view(torch.float64).expand(Cin, F).contiguous()
+    if not isinstance(radii, torch.Tensor):
+        return torch.full((Cin, F), float(radii), dtype=torch.float64, device=device)
+    if radii.dtype != torch.float64 or radii.numel() != (Cin * F if depthwise else F):
+        raise ValueError(f"radii must be f64 [{Cin * F if depthwise else F}], got {radii.dtype} {tuple(radii.shape)}")
+    return radii.reshape(Cin, F).contiguous() if depthwise else radii.reshape(1, F).expand(Cin, F).contiguous()
+
+
+def refine_conv2d(W, act_w, act_q, idx, radii, unit_alphabet, sweeps, strides, padding, rate, depthwise=False, group=None):
+    """Refinement sweeps for the walks per (input channel, filter) pair of a Conv2D / DepthwiseConv2D kernel: the
+    coordinate descent of refine_dense's Gram form for every pair -- a neuron of kh*kw weights over the rows of its channel's patch
+    matrices -- on the pair's own objective ||X_c^T w - Xq_c^T q||, started from the walk's indices.  It runs after quantize_conv2d (or
+    its radius="channel" / search forms), on their result.  No patch matrix is formed: the channels' Gram matrices come from
+    hip.conv_channel_records, called once, or twice with swapped arguments when act_q is not act_w (the second call's lower triangle is
+    the upper one of Xq_c X_c^T); one kernel call walks all pairs (hip.refine_conv_pairs).
+
+    W        f32 [kh][kw][Cin][F]  the ORIGINAL Keras kernel (not a rescaled W'); a depthwise kernel: F = the depth multiplier
+    act_w/q  f32 NHWC              the layer inputs the walk ran on
+    idx      [kh][kw][Cin][F]      the walk's indices (int8; int16 beyond 64 members); left as it is
+    radii    a hip.DeviceAlphabet or a host number (the layer radius), f64 [F] on the device (one per filter: radius="channel" and the
+             search on Conv2D), or -- depthwise=True -- f64 [Cin * F] (radius="channel" on a depthwise kernel)
+    sweeps   >= 1
+
+    NotImplementedError: kh * kw beyond hip.GPFQ_REFINE_PAIRS_MAX_K, a shape the record kernels do not take, a group of several ranks.
+    Returns dict(Q f32 [kh][kw][Cin][F], idx, changed i32 [Cin][F], sweeps i32 [Cin][F], gain f64 [Cin][F])."""
+    sweeps = check_refine(sweeps, "sweeps")
+    if sweeps < 1:
+        raise ValueError("sweeps must be >= 1")
+    kh, kw, Cin, F = W.shape
+    K, dev = kh * kw, W.device
+    if _group_info(group)[0] > 1:
+        raise NotImplementedError("refinement sweeps are not sharded over a process group yet")
+    if K > hip.GPFQ_REFINE_PAIRS_MAX_K:
+        raise NotImplementedError(f"refinement sweeps per (input channel, filter) pair take kernels of at most GPFQ_REFINE_PAIRS_MAX_K = "
+                                  f"{hip.GPFQ_REFINE_PAIRS_MAX_K} weights, got {kh} x {kw} = {K}")
+    conv = ((kh, kw), strides, rate, padding)
+    n, H, Wd = act_w.shape[:3]
+    if not hip.conv_records_supported(n, H, Wd, Cin, *conv):
+        raise NotImplementedError(f"refinement sweeps per (input channel, filter) pair need the Gram records of the layer's channels, and "
+                                  f"no record kernel takes {n} images of {H} x {Wd} under a {kh} x {kw} kernel, strides {tuple(strides)}, "
+                                  f"rate {tuple(rate) if rate else (1, 1)}, padding {padding}")
+    R = _pair_radii(radii, Cin, F, depthwise, dev)
+    same = act_q is act_w
+    pw = hip.channel_planes(act_w.contiguous(), 0, Cin)
+    pq = pw if same else hip.channel_planes(act_q.contiguous(), 0, Cin)
+    rec, _ = hip.conv_channel_records(pw, pq, *conv)
+    swapped = None if same else hip.conv_channel_records(pq, pw, *conv)[0]
+    Wt = W.detach().permute(2, 3, 0, 1).reshape(Cin, F, K).contiguous()
+    It = idx.permute(2, 3, 0, 1).reshape(Cin, F, K).contiguous()
+    if It.data_ptr() == idx.data_ptr():             # (a 1 x 1 kernel of one channel: the permutation is the tensor itself)
+        It = It.clone()
+    r = hip.refine_conv_pairs(rec, swapped, K, Wt, R, unit_alphabet, sweeps, It)
+    Q, out_idx = (t.reshape(Cin, F, kh, kw).permute(2, 3, 0, 1).contiguous() for t in (r["Q"], It))
+    return dict(Q=Q, idx=out_idx, changed=r["changed"], sweeps=r["sweeps"], gain=r["gain"])
+
+
 # ------------------------------------------------------------------------------------------
 # radius = "channel": one alphabet radius per output channel (DESIGN.md section 8)
 # ------------------------------------------------------------------------------------------

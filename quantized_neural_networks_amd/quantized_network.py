@@ -22,7 +22,8 @@ every candidate is walked in the same launch and each output channel (``radius="
 the candidate with the smallest output error on the calibration data; a plain number is today's behaviour.
 ``QuantizedCNN(..., conv_walk="filter")`` walks every Conv2D filter as one neuron of kh*kw*Cin weights over a sample of
 ``conv_columns`` patch columns; the default ``conv_walk="channel"`` is the reference's walk per (input channel,
-filter) pair.
+filter) pair.  ``QuantizedCNN(..., refine_passes=K, refine_channel_walks=True)`` extends the refinement sweeps to those walks per
+pair -- Conv2D layers under ``conv_walk="channel"`` and DepthwiseConv2D layers; off by default.
 """
 import logging
 from collections import namedtuple
@@ -157,6 +158,13 @@ def _check_refine_passes(refine_passes, process_group):
     return n
 
 
+def _check_refine_channel_walks(flag):
+    """refine_channel_walks validated: a bool (ValueError otherwise)."""
+    if not isinstance(flag, (bool, np.bool_)):
+        raise ValueError(f"refine_channel_walks must be True or False, got {flag!r}")
+    return bool(flag)
+
+
 def _refine_stats(out):
     """{"refine": lazy dict(resid_before, resid_after, changed, sweeps; refine_form="gram": + gain)} of a refined layer, {} otherwise."""
     return {"refine": _LazyStats(**out["refine"])} if "refine" in out else {}
@@ -271,6 +279,7 @@ class QuantizedNeuralNetwork:
 
     refine_passes = 0
     refine_form = "residual"
+    refine_channel_walks = False        # (QuantizedCNN's: the walks per (input channel, filter) pair)
 
     def _refine_kw(self, layer_idx, m=None):
         """The drivers' refine arguments: nothing at all for refine_passes = 0 (today's calls, unchanged), no refine_form under the
@@ -815,10 +824,11 @@ class QuantizedCNN(QuantizedNeuralNetwork):
     def __init__(self, network, batch_size, get_data, mini_batch_size=32, logger=None, bits=np.log2(3),
                  alphabet_scalar=1, patch_mini_batch_size=5000, is_quantize_conv2d=True, *,
                  device=None, process_group=None, fix_partial_batch=False, radius="layer", conv_walk="channel", conv_columns=8192,
-                 conv_columns_seed=0, refine_passes=0, refine_form="residual"):
+                 conv_columns_seed=0, refine_passes=0, refine_form="residual", refine_channel_walks=False):
         self.radius = _check_radius(radius)
         self.refine_passes = _check_refine_passes(refine_passes, process_group)
         self.refine_form = _layer.check_refine_form(refine_form)
+        self.refine_channel_walks = _check_refine_channel_walks(refine_channel_walks)
         self.alphabet_scalars = _scalar_candidates(alphabet_scalar)
         self.conv_walk, self.conv_columns, self.conv_columns_seed = _check_conv_walk(conv_walk, conv_columns, conv_columns_seed)
         self.get_data = get_data
@@ -863,7 +873,8 @@ class QuantizedCNN(QuantizedNeuralNetwork):
             # (a DepthwiseConv2D output channel depends on one input channel: its whole-filter walk IS the per-channel one below)
             self._quantize_conv2D_layer_filters(layer_idx, layer, Wd, wX, qX, rate)
             return
-        if self.refine_passes:
+        refine = bool(self.refine_passes) and self.refine_channel_walks
+        if self.refine_passes and not refine:
             self._log(f"\t\tLayer {layer_idx} ({layer.__class__.__name__}): refine_passes does not take the walks per (input channel, "
                       f"filter) pair; the layer stays as the walk made it")
         channels = self.radius == "channel" and not search
@@ -888,15 +899,34 @@ class QuantizedCNN(QuantizedNeuralNetwork):
             self._log(f"\t\t\tLayer {layer_idx} generated an exception: {exc}")
             raise Exception
         self._log(f"\t\tdone. {time()-tic:.2f} seconds.")
+        if refine:
+            Q = self._refine_channel_walks(layer_idx, layer, Wd, wX, qX, out, rad if not channels and not search else out["radii"], conv)
         self._update_weights(layer_idx, Q)
+        extra = dict(reruns=int(out.get("reruns", 0)), **_refine_stats(out))
         if search:
-            self.last_layer_stats[layer_idx] = _search_stats(out, self.alphabet, reruns=int(out.get("reruns", 0)))
+            self.last_layer_stats[layer_idx] = _search_stats(out, self.alphabet, **extra)
             return
         if channels:
-            self.last_layer_stats[layer_idx] = _channel_stats(out, self.alphabet, self.alphabet_scalar, reruns=int(out.get("reruns", 0)))
+            self.last_layer_stats[layer_idx] = _channel_stats(out, self.alphabet, self.alphabet_scalar, **extra)
             return
-        self.last_layer_stats[layer_idx] = _LazyStats(rad=rad, alphabet=alphabet, resid=out["resid"], idx=out["idx"],
-                                                      reruns=int(out.get("reruns", 0)))
+        self.last_layer_stats[layer_idx] = _LazyStats(rad=rad, alphabet=alphabet, resid=out["resid"], idx=out["idx"], **extra)
+
+    def _refine_channel_walks(self, layer_idx, layer, Wd, wX, qX, out, radii, conv):
+        """refine_channel_walks: refine_passes sweeps over every (input channel, filter) pair of the layer the walk just made
+        (layer.refine_conv2d), against the original kernel and on the members radius * unit alphabet -- the
+        layer radius, or the radii of radius="channel" / the search.  Replaces out["Q"] and out["idx"], adds out["refine"] =
+        dict(changed, sweeps, gain) and returns the new Q.  A refusal names the layer."""
+        tic = time()
+        try:
+            r = _layer.refine_conv2d(Wd, wX, qX, out["idx"], radii, self.alphabet, self.refine_passes, conv["strides"], conv["padding"],
+                                     conv["rate"], depthwise=layer.__class__.__name__ == "DepthwiseConv2D", group=self.process_group)
+        except NotImplementedError as exc:
+            self._log(f"\t\t\tLayer {layer_idx} generated an exception: {exc}")
+            raise NotImplementedError(f"layer {layer_idx} ({getattr(layer, 'name', layer.__class__.__name__)}): {exc}")
+        out["Q"], out["idx"] = r.pop("Q"), r.pop("idx")
+        out["refine"] = r
+        self._log(f"\t\tRefined the walks per (input channel, filter) pair: up to {self.refine_passes} sweeps. {time()-tic:.2f} seconds.")
+        return out["Q"]
 
     def _quantize_conv2D_layer_filters(self, layer_idx, layer, Wd, wX, qX, rate):
         """conv_walk="filter": every filter of the Conv2D kernel is ONE neuron of kh*kw*Cin weights, walked over the im2col rows of a
