@@ -66,6 +66,9 @@ def main():
     ap.add_argument("--export-packed", default=None, metavar="PATH",
                     help="also write the quantized network in the packed low-bit form (deploy.export_packed; with several settings the "
                          "file holds the last one's)")
+    ap.add_argument("--packed-activations", choices=("float32", "int8"), default=None,
+                    help="with --export-packed: load the file back (deploy.load_packed) with its Dense layers running on float32 or on "
+                         "int8 activations, and print that network's agreement with the analog one")
     args = ap.parse_args()
 
     rng = np.random.default_rng(0)
@@ -93,7 +96,13 @@ def main():
 
         if args.export_packed:
             from quantized_neural_networks_amd import deploy
-            print(f"packed network written to {deploy.export_packed(my_quant_net, args.export_packed)}")
+            packed_path = deploy.export_packed(my_quant_net, args.export_packed)
+            print(f"packed network written to {packed_path}")
+            if args.packed_activations:
+                packed_net = deploy.load_packed(packed_path, activations=args.packed_activations)
+                p_acc = agreement(packed_net, y_test, X_test)
+                print(f"packed network on {args.packed_activations} activations: argmax agreement {p_acc[0]:.4f}, relative L2 error "
+                      f"{p_acc[1]:.4g} (float kernels: {q_acc[0]:.4f}, {q_acc[1]:.4g})")
 
         # MSQ baseline: same radius as the corresponding GPFQ layer (quantize_pretrained_mlp.py:97-112)
         MSQ_model = keras.clone_model(model)

@@ -463,6 +463,38 @@ int gpfq_packed_dense_forward_tiled(const float *x, int64_t B, int64_t ldx, cons
                                     float *y, int64_t ldy, void *stream);
 
 /*
+ * The same forward pass on int8 activations and exact int32 sums (the i8 matrix instruction; DESIGN.md section 11, addendum), for the
+ * equispaced unit alphabet linspace(-1, 1, M) only, 2 <= M <= 64: unit_alphabet is not passed.  Opt-in; bit for bit:
+ *
+ * gpfq_quantize_rows_i8, independently for every batch row b of x: with amax = max |x[b][t]| over t < N,
+ *   a NaN or an Inf anywhere in the row:  scales[b] = NaN, xq[b][:] = 0;
+ *   else amax < 2^-100 (zero included):   scales[b] = 0.0f, xq[b][:] = 0;
+ *   else inv = 127.0f / amax, scales[b] = amax / 127.0f (float32 divisions, correctly rounded) and
+ *        xq[b][t] = (int8) clamp(rintf(x[b][t] * inv), -127, 127): one float32 product, rounded half to even.
+ * Bytes t = N .. roundup16(N) - 1 of every row of xq are written as 0, none beyond; x is not read beyond column N or row B.
+ *   x [device] f32 [B][ldx], ldx >= N; xq [device] i8 [B][ldq], 16-byte aligned, ldq a multiple of 16 and >= N; scales [device] f32 [B].
+ *
+ * gpfq_packed_dense_forward_i8: with the code c of weight t of channel j (the packed rows above) and k = c - zero_code,
+ *   w[t][j]   = 2 k - (M - 1) for 0 <= k < M, else 0 (the literal zero, and any code no member has);
+ *   acc[b][j] = sum over t < N of xq[b][t] * w[t][j], in int32: exact, since |xq| <= 127, |w| <= 63 and
+ *               N <= GPFQ_PACKED_I8_MAX_N keep |acc| < 2^31 (an xq of -128 is taken as it is; the bound is the caller's then);
+ *   p         = ((double)acc * (double)scales[b]) * (radii[j] / (double)(M - 1)): two float64 products in that order;
+ *   y[b][j]   = (float)p + bias[j], a float32 add; (float)p without a bias.
+ * So a row of x that is not finite gives a row of NaN and leaves every other row alone; row b of y depends on row b of xq and scales
+ * alone, not on B; and every call gives the same bits.  Bytes t >= N of xq are not used.  Any B >= 1, C, 0 <= N (N = 0: acc = 0).
+ * The arguments it shares with gpfq_packed_dense_forward are checked as there (xq and ldq in the place of x and ldx), with the same
+ * status codes; GPFQ_ERR_INVALID_ARG also for N > GPFQ_PACKED_I8_MAX_N, M < 2 or M > 64, ldq not a multiple of 16, xq not 16-byte
+ * aligned, scales NULL.
+ *   xq, scales as above; packed, radii, bias, y as for gpfq_packed_dense_forward.
+ * Both are one launch each, asynchronous on `stream`, without atomics, workspace or host synchronisation.
+ */
+#define GPFQ_PACKED_I8_MAX_N 262144
+int gpfq_quantize_rows_i8(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales, void *stream);
+int gpfq_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
+                                 int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
+                                 int64_t ldy, void *stream);
+
+/*
  * Search over the alphabet scalar (a sequence as alphabet_scalar).  K candidate scalars s_0 .. s_{K-1}
  * (1 <= K <= GPFQ_SEARCH_MAX_CANDIDATES, each a finite positive number) are K * C independent columns of one walk with the unit
  * alphabet: candidate k of output channel j is column k * C + j (k-major: candidate k is a contiguous block of C columns).

@@ -817,7 +817,30 @@ int gpfq_unpack_kernel(const uint8_t *packed, int bits, int zero_code, const dou
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_unpack_kernel");
 }
 
-// Both forward entries: one set of argument checks, and the launcher of the kernel family named.
+// The forward entries: one set of checks for the arguments all three share (in: x, or xq for the int8 entry, with its row pitch), and
+// the launcher of the kernel family named.  *nothing: an empty batch or layer, the call is done.
+static int packed_forward_args(const void *in, const char *ld_name, int64_t ld, int64_t B, const uint8_t *packed,
+                               int bits, int zero_code, const double *radii, int M, int64_t N, int64_t C, const float *y, int64_t ldy,
+                               bool *nothing)
+{
+    *nothing = false;
+    int rc = packed_width_ok(bits, zero_code, M);
+    if (rc != GPFQ_OK) return rc;
+    if (B == 0 || C == 0) {
+        *nothing = true;
+        return GPFQ_OK;
+    }
+    if (!y || !radii) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (ldy < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldy=%lld < C=%lld", (long long)ldy, (long long)C);
+    if (N > 0) {
+        if (!in || !packed) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+        if (ld < N) return fail(GPFQ_ERR_INVALID_ARG, "row pitch %s=%lld < N=%lld", ld_name, (long long)ld, (long long)N);
+        if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "packed must be 16-byte aligned");
+    }
+    if (C > 2147483647LL * 8) return fail(GPFQ_ERR_UNSUPPORTED, "layer too wide for one launch");
+    return GPFQ_OK;
+}
+
 typedef hipError_t (*PackedForwardLaunch)(const float *, int64_t, int64_t, const uint8_t *, int, int, const double *, const gpfq::AlphabetArg &,
                                           const float *, int64_t, int64_t, float *, int64_t, hipStream_t);
 
@@ -829,17 +852,9 @@ static int packed_forward_entry(const char *name, PackedForwardLaunch launch, co
     HostAlphabet H;
     int rc = packed_alphabet(unit_alphabet, M, &H);
     if (rc != GPFQ_OK) return rc;
-    rc = packed_width_ok(bits, zero_code, M);
-    if (rc != GPFQ_OK) return rc;
-    if (B == 0 || C == 0) return GPFQ_OK;
-    if (!y || !radii) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
-    if (ldy < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldy=%lld < C=%lld", (long long)ldy, (long long)C);
-    if (N > 0) {
-        if (!x || !packed) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
-        if (ldx < N) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldx=%lld < N=%lld", (long long)ldx, (long long)N);
-        if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "packed must be 16-byte aligned");
-    }
-    if (C > 2147483647LL * 8) return fail(GPFQ_ERR_UNSUPPORTED, "layer too wide for one launch");
+    bool nothing;
+    rc = packed_forward_args(x, "ldx", ldx, B, packed, bits, zero_code, radii, M, N, C, y, ldy, &nothing);
+    if (rc != GPFQ_OK || nothing) return rc;
     hipError_t e = launch(x, B, ldx, packed, bits, zero_code, radii, H.A, bias, N, C, y, ldy, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
 }
@@ -858,6 +873,41 @@ int gpfq_packed_dense_forward_tiled(const float *x, int64_t B, int64_t ldx, cons
 {
     return packed_forward_entry("gpfq_packed_dense_forward_tiled", gpfq::launch_packed_dense_forward_tiled, x, B, ldx, packed, bits,
                                 zero_code, radii, unit_alphabet, M, bias, N, C, y, ldy, stream);
+}
+
+int gpfq_quantize_rows_i8(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales, void *stream)
+{
+    if (B < 0 || N < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size B=%lld N=%lld", (long long)B, (long long)N);
+    if (ldq % 16 != 0 || ldq < N) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldq=%lld must be a multiple of 16 and at least N=%lld", (long long)ldq, (long long)N);
+    if (B == 0) return GPFQ_OK;
+    if (!scales) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (N > 0) {
+        if (!x || !xq) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+        if (ldx < N) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldx=%lld < N=%lld", (long long)ldx, (long long)N);
+        if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
+    }
+    if (B > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "batch too long for one launch");
+    hipError_t e = gpfq::launch_quantize_rows_i8(x, B, ldx, N, xq, ldq, scales, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_quantize_rows_i8");
+}
+
+int gpfq_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
+                                 int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
+                                 int64_t ldy, void *stream)
+{
+    if (B < 0 || N < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size B=%lld N=%lld C=%lld", (long long)B, (long long)N, (long long)C);
+    if (M < 2 || M > 64) return fail(GPFQ_ERR_INVALID_ARG, "the int8 forward pass takes linspace(-1, 1, M) of 2..64 members, got M=%d", M);
+    if (N > GPFQ_PACKED_I8_MAX_N)
+        return fail(GPFQ_ERR_INVALID_ARG, "N=%lld > GPFQ_PACKED_I8_MAX_N=%d: the int32 sums could overflow", (long long)N, GPFQ_PACKED_I8_MAX_N);
+    bool nothing;
+    int rc = packed_forward_args(xq, "ldq", ldq, B, packed, bits, zero_code, radii, M, N, C, y, ldy, &nothing);
+    if (rc != GPFQ_OK || nothing) return rc;
+    if (!scales) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (ldq % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldq=%lld must be a multiple of 16", (long long)ldq);
+    if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
+    hipError_t e = gpfq::launch_packed_dense_forward_i8(xq, B, ldq, scales, packed, bits, zero_code, radii, M, bias, N, C, y, ldy,
+                                                        static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_packed_dense_forward_i8");
 }
 
 int gpfq_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii, const float *layer_median,

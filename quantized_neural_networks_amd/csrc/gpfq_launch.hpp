@@ -343,6 +343,13 @@ hipError_t launch_packed_dense_forward(const float *x, int64_t B, int64_t ldx, c
 hipError_t launch_packed_dense_forward_tiled(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int bits, int zero_code,
                                              const double *radii, const AlphabetArg &U, const float *bias, int64_t N, int64_t C, float *y,
                                              int64_t ldy, hipStream_t stream);
+// gpfq_packed_i8.hip: x -> int8 rows + one float32 scale per row, and the product of such rows with the packed rows as exact int32 sums
+// on the i8 matrix instruction (the equispaced unit alphabet linspace(-1, 1, M) only: M is all of it the kernel needs)
+hipError_t launch_quantize_rows_i8(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales,
+                                   hipStream_t stream);
+hipError_t launch_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
+                                          int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
+                                          int64_t ldy, hipStream_t stream);
 // gpfq_search.hip (a sequence as alphabet_scalar): the K candidate scalars travel by value
 constexpr int kSearchMaxK = 16;
 struct SearchScalars {

@@ -1,0 +1,286 @@
+// The Dense forward pass from packed rows on int8 activations and the i8 matrix instruction (addendum): every
+// alphabet the library makes is radius * linspace(-1, 1, M), so the weight of code c of channel j is radii[j] / (M - 1) times the
+// integer 2 (c - zero_code) - (M - 1), of magnitude at most 63.  With the activations rounded to int8 per batch row the product is an
+// exact int32 sum, whatever the order; the two scales meet it in float64 at the end.  include/gpfq.h states the contract bit for bit.
+//
+//   gpfq_quantize_rows_i8_kernel
+//       One workgroup per batch row: the largest |x| of the row (and whether anything in it is not finite) as the maximum of the
+//       bit patterns of |x|, then xq = rint(x * (127 / amax)), four bytes per thread and store.  x is read twice, 4 bytes at a time
+//       (any row pitch); the second read meets the caches.
+//
+//   gpfq_packed_dense_i8_kernel<BITS, MT>
+//       One workgroup owns a column tile of 16 output channels and a share of the batch's passes of 16 MT rows (MT = 1, 2, 4; grid.y
+//       strides over the passes); its four wavefronts split the row (K) and their partial int32 tiles are summed through LDS.
+//       Products on v_mfma_i32_16x16x64_i8: lane l holds 16 weights of channel l & 15 as the B operand and 16 activations of batch
+//       row l & 15 of each of the MT row tiles as the A operands, both from the same 16 t; the result has the channel on l & 15 and
+//       batch rows 4 (l >> 4) + reg.  The instruction sums over all 64 lanes' 16 elements: which k of the instruction an element is
+//       does not matter as long as both operands of a lane and element come from the same t.
+//
+//   K.  A lane quarter owns a whole 16-byte group of its channel's row (W = 128 / BITS weights: 4 / 2 / 1 B operands), a wavefront
+//   four groups and a round of the workgroup sixteen, as in gpfq_packed_tiled.hip.  The A operand of B operand i of group g is the
+//   aligned 16-byte piece xq[row][g W + 16 i ..+15], read from global memory as it is: no wavefront shares it with another, so
+//   nothing is staged in LDS and the K loop has no barrier.
+//
+//   Decoding.  Four codes in the bytes of a register become four int8 weights by byte-wise arithmetic on the whole register
+//   (decode4); at 2 bits the four possible weights are one register and a byte permute with the codes as its selector looks them up.
+//   Weights at or beyond N (the pad codes) are masked to zero, so what xq holds there does not matter; pieces at or beyond N are not
+//   read.  Rows at or beyond B read row B - 1, channels at or beyond C row C - 1; nothing of theirs is stored.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "gpfq_device.hpp"
+#include "gpfq_launch.hpp"
+
+namespace gpfq {
+
+namespace {
+
+constexpr int kQuantThreads = 256;                  // one workgroup per batch row
+
+constexpr int kI8Waves = 4;                         // wavefronts per workgroup: they split K
+constexpr int kI8Threads = kI8Waves * 64;
+constexpr int kI8Channels = 16;                     // output channels per workgroup: one MFMA column tile
+constexpr int kI8WaveGroups = 4;                    // 16-byte groups per wavefront and round: one per lane quarter
+constexpr int kI8RoundGroups = kI8Waves * kI8WaveGroups;
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+__device__ inline int8_t quantize_one(float v, float inv)
+{
+    float q = rintf(v * inv);                       // one float32 product, then round half to even
+    q = q < -127.f ? -127.f : (q > 127.f ? 127.f : q);
+    return (int8_t)(int)q;
+}
+
+__global__ void __launch_bounds__(kQuantThreads)
+gpfq_quantize_rows_i8_kernel(const float *__restrict__ x, int64_t ldx, int64_t N, int8_t *__restrict__ xq, int64_t ldq,
+                             float *__restrict__ scales)
+{
+    __shared__ unsigned wmax[kQuantThreads / 64];
+    const int tid = threadIdx.x;
+    const float *row = x + (int64_t)blockIdx.x * ldx;
+    int8_t *out = xq + (int64_t)blockIdx.x * ldq;
+    const int64_t n16 = (N + 15) & ~(int64_t)15;
+
+    // the bit pattern of |v| orders the finite floats as their magnitudes and puts every Inf and NaN at or above 0x7f800000
+    unsigned top = 0u;
+    for (int64_t t = 4 * (int64_t)tid; t < N; t += 4 * kQuantThreads) {
+        const int64_t end = t + 4 < N ? t + 4 : N;
+        for (int64_t e = t; e < end; ++e) {
+            const unsigned a = __float_as_uint(row[e]) & 0x7fffffffu;
+            top = a > top ? a : top;
+        }
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        const unsigned o = (unsigned)__shfl_xor((int)top, s, 64);
+        top = o > top ? o : top;
+    }
+    if ((tid & 63) == 0) wmax[tid >> 6] = top;
+    __syncthreads();
+    for (int w = 0; w < kQuantThreads / 64; ++w) top = wmax[w] > top ? wmax[w] : top;
+
+    const float amax = __uint_as_float(top);
+    float inv = 0.f, scale = 0.f;                   // inv == 0: a row of zeros
+    if (top >= 0x7f800000u) scale = __uint_as_float(0x7fc00000u);
+    else if (amax >= 0x1p-100f) { inv = 127.0f / amax; scale = amax / 127.0f; }
+    if (tid == 0) scales[blockIdx.x] = scale;
+
+    for (int64_t t = 4 * (int64_t)tid; t < n16; t += 4 * kQuantThreads) {
+        unsigned word = 0u;
+        if (inv != 0.f) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (t + e < N) word |= (unsigned)(uint8_t)quantize_one(row[t + e], inv) << (8 * e);
+        }
+        *reinterpret_cast<unsigned *>(out + t) = word;               // (xq is 16-byte aligned and ldq a multiple of 16)
+    }
+}
+
+// What turns codes into weights, one copy in every byte: the first code of a member, the first code past the members, and
+// 128 - (2 zero_code + M - 1), which puts 2 c - (2 zero_code + M - 1) into excess-128 form without a carry between bytes.
+struct DecodeBytes {
+    unsigned lo, hi, bias;
+};
+
+__device__ inline DecodeBytes decode_bytes(int zero_code, int M)
+{
+    const unsigned ones = 0x01010101u;
+    return DecodeBytes{(unsigned)zero_code * ones, (unsigned)(zero_code + M) * ones, (unsigned)(128 - (2 * zero_code + M - 1)) * ones};
+}
+
+// Four codes, one per byte (any value 0..255) -> four int8 weights: 2 (c - zero_code) - (M - 1) where zero_code <= c < zero_code + M,
+// else 0.  No byte borrows from or carries into its neighbour: (c & 127 | 128) - v >= 128 - 65 for v <= 65; a member's 2 c is at
+// most 128 and 2 c + bias lies in [128 - 63, 128 + 63]; a masked byte's 0 + bias in [63, 128].
+__device__ inline unsigned decode4(unsigned codes, const DecodeBytes &D)
+{
+    const unsigned H = 0x80808080u;
+    const unsigned c7 = (codes & 0x7f7f7f7fu) | H;
+    const unsigned member = (c7 - D.lo) & ~(c7 - D.hi) & ~codes & H;             // bit 7 of the bytes that hold a member's code
+    const unsigned mask = (member >> 7) * 0xffu;
+    return ((((codes & mask) << 1) + D.bias) ^ H) & mask;
+}
+
+// B operand i of a 16-byte group: its weights 16 i .. 16 i + 15 in the order of their t, one per byte.
+template <int BITS>
+__device__ inline i32x4 decode_operand(const unsigned (&words)[4], int i, const DecodeBytes &D, unsigned tab)
+{
+    i32x4 b;
+    if constexpr (BITS == 2) {                      // word i; byte d of it holds the four codes of register d
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const unsigned byte = (words[i] >> (8 * d)) & 0xffu;
+            const unsigned codes = (byte | (byte << 6) | (byte << 12) | (byte << 18)) & 0x03030303u;
+            b[d] = (int)__builtin_amdgcn_perm(tab, tab, codes);      // byte e of the result: byte codes[e] of tab
+        }
+    } else if constexpr (BITS == 4) {               // words 2 i, 2 i + 1; half a word holds the four codes of a register
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            unsigned v = (words[2 * i + (d >> 1)] >> (16 * (d & 1))) & 0xffffu;
+            v = (v | (v << 8)) & 0x00ff00ffu;
+            v = (v | (v << 4)) & 0x0f0f0f0fu;
+            b[d] = (int)decode4(v, D);
+        }
+    } else {
+#pragma unroll
+        for (int d = 0; d < 4; ++d) b[d] = (int)decode4(words[d], D);
+    }
+    return b;
+}
+
+template <int BITS, int MT>
+__global__ void __launch_bounds__(kI8Threads)
+gpfq_packed_dense_i8_kernel(const int8_t *__restrict__ xq, int64_t B, int64_t ldq, const float *__restrict__ scales,
+                            const uint8_t *__restrict__ packed, int64_t pitch, int zero_code, const double *__restrict__ radii, int M,
+                            const float *__restrict__ bias, int N, int64_t C, float *__restrict__ y, int64_t ldy)
+{
+    constexpr int W = 128 / BITS, NB = W / 16;      // weights and B operands per group
+    constexpr int R = 16 * MT;                      // batch rows per pass
+    __shared__ int red[kI8Waves * MT * 4 * 64];     // the partial tiles [wave][tile][reg][lane]
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int r = lane & 15, h = lane >> 4;
+    const int64_t j0 = (int64_t)blockIdx.x * kI8Channels;
+
+    const DecodeBytes D = decode_bytes(zero_code, M);
+    const unsigned tab = decode4(0x03020100u, D);   // the weights of the codes 0..3 (2 bits)
+
+    const int64_t groups = pitch / 16;
+    const int64_t rounds = (groups + kI8RoundGroups - 1) / kI8RoundGroups;
+    const int64_t j = j0 + r;
+    const uint4 *rowp = reinterpret_cast<const uint4 *>(packed + (j < C ? j : C - 1) * pitch);
+    const double unit = j < C ? radii[j] / (double)(M - 1) : 0.0;
+    auto codes = [&](int64_t round) {
+        const int64_t g = round * kI8RoundGroups + wave * kI8WaveGroups + h;
+        return g < groups ? rowp[g] : make_uint4(0u, 0u, 0u, 0u);
+    };
+
+    for (int64_t b0 = (int64_t)blockIdx.y * R; b0 < B; b0 += (int64_t)gridDim.y * R) {
+        i32x4 acc[MT];
+        const int8_t *xrow[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            acc[m] = i32x4{0, 0, 0, 0};
+            const int64_t b = b0 + m * 16 + r;
+            xrow[m] = xq + (b < B ? b : B - 1) * ldq;
+        }
+
+        uint4 cwn = rounds > 0 ? codes(0) : make_uint4(0u, 0u, 0u, 0u);
+        for (int64_t round = 0; round < rounds; ++round) {
+            const uint4 cw = cwn;
+            if (round + 1 < rounds) cwn = codes(round + 1);
+            if (round * kI8RoundGroups + wave * kI8WaveGroups >= groups) continue;               // (wave-uniform)
+            const unsigned words[4] = {cw.x, cw.y, cw.z, cw.w};
+            const int64_t t0 = (round * kI8RoundGroups + wave * kI8WaveGroups + h) * W;        // this quarter's first weight
+
+            i32x4 a[NB][MT];
+#pragma unroll
+            for (int i = 0; i < NB; ++i)
+#pragma unroll
+                for (int m = 0; m < MT; ++m) {
+                    a[i][m] = i32x4{0, 0, 0, 0};
+                    if (t0 + 16 * i < N) a[i][m] = *reinterpret_cast<const i32x4 *>(xrow[m] + t0 + 16 * i);
+                }
+            i32x4 b[NB];
+#pragma unroll
+            for (int i = 0; i < NB; ++i) b[i] = decode_operand<BITS>(words, i, D, tab);
+            if (t0 + W > N) {                       // the group that straddles N, and those beyond it: weights t >= N are zeros
+#pragma unroll
+                for (int i = 0; i < NB; ++i)
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) {
+                        const int64_t left = N - (t0 + 16 * i + 4 * d);
+                        b[i][d] &= left >= 4 ? -1 : (left <= 0 ? 0 : (int)((1u << (8 * (int)left)) - 1u));
+                    }
+            }
+#pragma unroll
+            for (int i = 0; i < NB; ++i)
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i][m], b[i], acc[m], 0, 0, 0);
+        }
+
+        // the partial tiles of the four wavefronts: integer sums, any order
+        __syncthreads();                            // (the pass before this one has been summed)
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) red[((wave * MT + m) * 4 + g) * 64 + lane] = acc[m][g];
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            int s = 0;
+#pragma unroll
+            for (int w = 0; w < kI8Waves; ++w) s += red[((w * MT + m) * 4 + wave) * 64 + lane];
+            const int64_t b = b0 + m * 16 + 4 * h + wave;             // (this thread sums register `wave` of every partial tile)
+            if (j < C && b < B) {
+                const double p = ((double)s * (double)scales[b]) * unit;
+                const float v = (float)p;
+                y[b * ldy + j] = bias ? v + bias[j] : v;
+            }
+        }
+    }
+}
+
+template <int BITS, int MT>
+hipError_t launch_i8_mt(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int64_t pitch,
+                        int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y, int64_t ldy,
+                        hipStream_t stream)
+{
+    const int64_t blocks = (C + kI8Channels - 1) / kI8Channels;
+    int64_t passes = (B + 16 * MT - 1) / (16 * MT);
+    if (passes > 65535) passes = 65535;
+    hipLaunchKernelGGL((gpfq_packed_dense_i8_kernel<BITS, MT>), dim3((unsigned)blocks, (unsigned)passes), dim3(kI8Threads), 0, stream, xq,
+                       B, ldq, scales, packed, pitch, zero_code, radii, M, bias, (int)N, C, y, ldy);
+    return hipGetLastError();
+}
+
+template <int BITS>
+hipError_t launch_i8_bits(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int64_t pitch,
+                          int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y, int64_t ldy,
+                          hipStream_t stream)
+{
+    if (B <= 16) return launch_i8_mt<BITS, 1>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
+    if (B <= 32) return launch_i8_mt<BITS, 2>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
+    return launch_i8_mt<BITS, 4>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
+}
+
+}  // namespace
+
+hipError_t launch_quantize_rows_i8(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales,
+                                   hipStream_t stream)
+{
+    hipLaunchKernelGGL(gpfq_quantize_rows_i8_kernel, dim3((unsigned)B), dim3(kQuantThreads), 0, stream, x, ldx, N, xq, ldq, scales);
+    return hipGetLastError();
+}
+
+hipError_t launch_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
+                                          int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
+                                          int64_t ldy, hipStream_t stream)
+{
+    const int64_t pitch = (int64_t)packed_row_bytes(N, bits);
+    if (bits == 2) return launch_i8_bits<2>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
+    if (bits == 4) return launch_i8_bits<4>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
+    return launch_i8_bits<8>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
+}
+
+}  // namespace gpfq

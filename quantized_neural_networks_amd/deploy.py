@@ -125,11 +125,30 @@ def _read_packed(z, k, device):
                 depthwise=bool(int(z[f"p{k}_depthwise"])))
 
 
-def load_packed(path, device=None):
+def _check_int8_layer(layer, packed):
+    """What the int8 forward pass assumes of a layer, checked on the host: the stored alphabet is linspace(-1, 1, M) exactly (the
+    kernel takes the weight of index k as radius / (M - 1) times the integer 2 k - (M - 1)) and the row is short enough for int32."""
+    unit = np.asarray(packed["alphabet"], dtype=np.float64)
+    M = len(unit)
+    if M < 2 or not np.array_equal(unit, np.linspace(-1, 1, M)):
+        raise ValueError(f"layer {layer.name}: activations=\"int8\" needs the alphabet np.linspace(-1, 1, M) with M >= 2, the file holds "
+                         f"{M} other members")
+    if layer.fan_in > hip.GPFQ_PACKED_I8_MAX_N:
+        raise ValueError(f"layer {layer.name}: activations=\"int8\" takes at most {hip.GPFQ_PACKED_I8_MAX_N} input features "
+                         f"(GPFQ_PACKED_I8_MAX_N), the layer has {layer.fan_in}")
+
+
+def load_packed(path, device=None, activations="float32"):
     """Inverse of export_packed: a keras_shim network on ``device`` (default: the current GPU).  Dense layers that were exported
     packed come back as keras_shim.PackedDense (codes, radii and bias in device memory; the float kernel is never formed unless
-    get_weights() or a batch beyond keras_shim.PACKED_FORWARD_MAX_BATCH asks for it); packed Conv2D / DepthwiseConv2D kernels are
-    decoded on the device."""
+    get_weights() or a batch beyond keras_shim.PACKED_TILED_MAX_BATCH asks for it); packed Conv2D / DepthwiseConv2D kernels are
+    decoded on the device.
+
+    activations="int8": every PackedDense layer rounds its input to int8 per batch row and runs the exact-int32 forward pass at every
+    batch size (keras_shim.PackedDense.activations; the float kernel is then formed by get_weights() alone).  Raises ValueError naming
+    the layer whose alphabet is not np.linspace(-1, 1, M) or whose rows are longer than GPFQ_PACKED_I8_MAX_N."""
+    if activations not in keras_shim.PackedDense.ACTIVATIONS:
+        raise ValueError(f"activations must be one of {keras_shim.PackedDense.ACTIVATIONS}, got {activations!r}")
     path = str(path)
     with np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False) as z:
         if "__packed__" not in z.files:
@@ -146,7 +165,10 @@ def load_packed(path, device=None):
                 packed = _read_packed(z, k, net.device)
                 rest = [z[f"w{k}_{j}"] for j in range(1, 1 + (1 if layer.use_bias else 0))]
                 if k in classes:
+                    if activations == "int8":
+                        _check_int8_layer(layer, packed)
                     layer.set_packed(packed, rest[0] if rest else None)
+                    layer.activations = activations
                 else:
                     layer.set_weights([unpack_kernel(packed)] + rest)
             elif layer._weights:

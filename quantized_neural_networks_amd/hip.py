@@ -27,6 +27,7 @@ GPFQ_REFINE_MAX_M = 8192           # longest row the refinement sweeps take (inc
 GPFQ_REFINE_GRAM_MAX_N = 25600     # longest walk the refinement sweeps on the Gram matrix take (include/gpfq.h)
 GPFQ_REFINE_PAIRS_MAX_K = 64       # longest walk of an (input channel, filter) pair refine_conv_pairs takes (include/gpfq.h)
 GPFQ_ERR_INVALID_ARG, GPFQ_ERR_UNSUPPORTED, GPFQ_ERR_WORKSPACE = -1, -2, -3
+GPFQ_PACKED_I8_MAX_N = 262144      # longest row of the int8 packed forward pass: its int32 sums cannot overflow (include/gpfq.h)
 
 # every symbol include/gpfq.h declares: (restype, argtypes)
 _i64, _int, _vp, _sz = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
@@ -67,6 +68,8 @@ SYMBOLS = {
     "gpfq_unpack_kernel": (_int, [_vp, _int, _int, _vp, _dp, _int, _i64, _i64, _vp, _i64, _vp, _vp]),
     "gpfq_packed_dense_forward": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _dp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
     "gpfq_packed_dense_forward_tiled": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _dp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "gpfq_quantize_rows_i8": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "gpfq_packed_dense_forward_i8": (_int, [_vp, _i64, _i64, _vp, _vp, _int, _int, _vp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
     "gpfq_candidate_kernels": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dp, _int, _vp, _vp, _i64, _i64, _i64, _vp]),
     "gpfq_select_candidates_workspace_bytes": (_sz, [_int, _i64]),
     "gpfq_select_candidates": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _dp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
@@ -1417,3 +1420,66 @@ def packed_dense_forward_tiled(x, packed, bits, zero_code, radii, unit_alphabet,
     """The same product, arguments and checks on the tiled kernel (gpfq_packed_dense_forward_tiled): 16 output channels against up to
     64 batch rows per pass of the codes, for batches beyond the few rows packed_dense_forward is for.  No sync."""
     return _packed_forward("gpfq_packed_dense_forward_tiled", x, packed, bits, zero_code, radii, unit_alphabet, N, bias, out)
+
+
+def quantize_rows_i8(x, N=None, out=None):
+    """x f32 [B][N] (rows contiguous, any row pitch) -> (xq i8 [B][roundup16(N)], scales f32 [B]) (gpfq_quantize_rows_i8): per batch
+    row, xq = rint(x * (127 / amax)) and scales = amax / 127; a row that is not finite gets the scale NaN and zeros, a row below 2^-100
+    the scale 0 and zeros; the pad bytes are zeros.  N: the leading columns of x to take (default: all).  out: an optional
+    (xq, scales) pair; xq may be a view of [B] rows whose pitch is a multiple of 16, on a 16-byte aligned address.  No sync."""
+    _dev(x, torch.float32, "x")
+    xp, B, Nx, ldx = _rows(x, "x")
+    N = Nx if N is None else int(N)
+    if not 0 <= N <= Nx:
+        raise GpfqError(f"x {tuple(x.shape)} does not have {N} columns")
+    n16 = (N + 15) // 16 * 16
+    if out is None:
+        out = (torch.empty((B, n16), dtype=torch.int8, device=x.device), torch.empty(B, dtype=torch.float32, device=x.device))
+    xq, scales = out
+    _dev(xq, torch.int8, "xq"); _dev(scales, torch.float32, "scales")
+    qp, Bq, Nq, ldq = _rows(xq, "xq")
+    if Bq != B or Nq < n16 or scales.numel() != B or not scales.is_contiguous():
+        raise GpfqError(f"out must be (int8 [{B}][>= {n16}], float32 [{B}]), got {tuple(xq.shape)}, {tuple(scales.shape)}")
+    if B <= 1:
+        ldq = max(n16, 16)
+    with torch.cuda.device(x.device):
+        _check(load().gpfq_quantize_rows_i8(xp, B, ldx, N, qp, ldq, scales.data_ptr(), _stream()), "gpfq_quantize_rows_i8")
+    return xq, scales
+
+
+def packed_dense_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, N, bias=None, out=None, scales=None):
+    """y f32 [B][C] of a Dense layer held as packed rows, on int8 activations and exact int32 sums (gpfq_packed_dense_forward_i8; the
+    contract is include/gpfq.h's, bit for bit).  x_or_xq: float32 x [B][N], quantized here (quantize_rows_i8), or -- with `scales`
+    f32 [B] -- a ready int8 xq [B][>= N] whose row pitch is a multiple of 16.  M: the size of the layer's unit alphabet, which must be
+    linspace(-1, 1, M).  No sync."""
+    if scales is None:
+        _dev(x_or_xq, torch.float32, "x")
+        if x_or_xq.dim() != 2 or x_or_xq.shape[1] != int(N):
+            raise GpfqError(f"x {tuple(x_or_xq.shape)} does not have the layer's {N} input features")
+        xq, scales = quantize_rows_i8(x_or_xq)
+    else:
+        xq = _dev(x_or_xq, torch.int8, "xq")
+    _dev(scales, torch.float32, "scales")
+    qp, B, Nq, ldq = _rows(xq, "xq")
+    if Nq < int(N):
+        raise GpfqError(f"xq {tuple(xq.shape)} does not have the layer's {N} input features")
+    if B <= 1:
+        ldq = (max(Nq, 1) + 15) // 16 * 16          # (one row: the pitch is never used, any multiple of 16 that holds N will do)
+    if scales.numel() != B or not scales.is_contiguous():
+        raise GpfqError(f"scales must be a contiguous [{B}] tensor")
+    C = _packed_args(packed, bits, zero_code, radii, N)
+    if bias is not None:
+        _dev(bias, torch.float32, "bias")
+        if bias.numel() != C or not bias.is_contiguous():
+            raise GpfqError(f"bias must be a contiguous [{C}] tensor")
+    if out is None:
+        out = torch.empty((B, C), dtype=torch.float32, device=xq.device)
+    _dev(out, torch.float32, "out")
+    yp, By, Cy, ldy = _rows(out, "out")
+    if (By, Cy) != (B, C):
+        raise GpfqError(f"out {tuple(out.shape)} must be [{B}][{C}]")
+    with torch.cuda.device(xq.device):
+        _check(load().gpfq_packed_dense_forward_i8(qp, B, ldq, scales.data_ptr(), packed.data_ptr(), int(bits), int(zero_code),
+                                                   radii.data_ptr(), int(M), bias.data_ptr() if bias is not None else None, int(N), C,
+                                                   yp, ldy, _stream()), "gpfq_packed_dense_forward_i8")
+    return out

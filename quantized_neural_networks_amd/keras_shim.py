@@ -227,11 +227,20 @@ PACKED_TILED_MAX_BATCH = 128
 
 class PackedDense(Dense):
     """A Dense layer that holds its quantized kernel as packed low-bit codes (deploy.load_packed): only the
-    codes, the radii and the bias live in device memory.  ``get_weights()`` decodes on demand; the weights cannot be set."""
+    codes, the radii and the bias live in device memory.  ``get_weights()`` decodes on demand; the weights cannot be set.
+
+    ``activations``: "float32" (the default) runs float32 x through the packed kernels up to PACKED_TILED_MAX_BATCH rows and through
+    decode + matmul beyond; "int8" rounds every batch row of x to int8 with its own scale and runs gpfq_packed_dense_forward_i8 at
+    every batch -- exact int32 sums, the float kernel is never formed (include/gpfq.h has the arithmetic; the layer's alphabet must be
+    linspace(-1, 1, M), which deploy.load_packed checks).  A property of the loaded layer, not of its configuration: config(),
+    clone() and save_model() record what they always did."""
+
+    ACTIVATIONS = ("float32", "int8")
 
     def __init__(self, units, activation=None, use_bias=True, input_shape=None, name=None):
         super().__init__(units, activation, use_bias, input_shape, name)
         self.packed = None
+        self.activations = "float32"
 
     def build(self, input_shape, device, rng):
         Layer.build(self, input_shape, device, rng)
@@ -270,8 +279,13 @@ class PackedDense(Dense):
             raise RuntimeError(f"PackedDense layer {self.name} holds no packed kernel (deploy.load_packed installs one)")
         x2 = x.reshape(-1, self.fan_in)
         bias = self._weights[0] if self.use_bias else None
-        if 0 < x2.shape[0] <= max(PACKED_FORWARD_MAX_BATCH, PACKED_TILED_MAX_BATCH):
-            p = self.packed
+        p = self.packed
+        if self.activations not in self.ACTIVATIONS:
+            raise ValueError(f"PackedDense layer {self.name}: activations must be one of {self.ACTIVATIONS}, got {self.activations!r}")
+        if self.activations == "int8" and x2.shape[0] > 0:
+            y = hip.packed_dense_forward_i8(x2.contiguous(), p["codes"], p["bits"], p["zero_code"], p["radii"], len(p["alphabet"]),
+                                            self.fan_in, bias=bias)
+        elif 0 < x2.shape[0] <= max(PACKED_FORWARD_MAX_BATCH, PACKED_TILED_MAX_BATCH):
             forward = hip.packed_dense_forward if x2.shape[0] <= PACKED_FORWARD_MAX_BATCH else hip.packed_dense_forward_tiled
             y = forward(x2.contiguous(), p["codes"], p["bits"], p["zero_code"], p["radii"], p["alphabet"], self.fan_in, bias=bias)
         else:

@@ -5,6 +5,8 @@
     float     x @ Q on the float32 kernel (torch.matmul)
     decode    gpfq_unpack_kernel + torch.matmul
     tiled     gpfq_packed_dense_forward_tiled on the packed rows
+    i8        (--i8 only) gpfq_quantize_rows_i8 + gpfq_packed_dense_forward_i8 on the packed rows, timed together
+              -> profiles/packed_forward_i8.txt, batches up to 1024; no routing constant follows from it
 
 Shapes 4096 x 4096 (ternary, 16 levels) and 25088 x 4096 (ternary), and 4096 x 1000 (ternary) for what a layer of few column tiles
 costs the tiled kernel (63 workgroups on 256 compute units); batches 1 .. 256.  Every figure is device time per call: the call is
@@ -23,6 +25,7 @@ has -- on both 4096 x 4096 shapes (4 if there is none: nothing is routed).
 Also the file sizes of a VGG16-shaped Dense stack written by save_model and by export_packed.
 
     python tools/packed_forward_probe.py [--out profiles/packed_forward_tiled.txt] [--quick]
+    python tools/packed_forward_probe.py --i8 --out profiles/packed_forward_i8.txt
 """
 import argparse
 import os
@@ -37,6 +40,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from quantized_neural_networks_amd import deploy, hip, keras_shim as ks  # noqa: E402
 
 BATCHES = (1, 2, 4, 5, 8, 16, 32, 64, 128, 256)
+I8_BATCHES = BATCHES + (512, 1024)                  # --i8: the batch sizes a network is evaluated at
 TILED_MARGIN = 0.95                                 # tiled / (decode + matmul) at or below this: the tiled kernel is routed
 
 
@@ -89,10 +93,11 @@ def measure(label, N, C, M, args, dev, out):
     wins, tiled = {}, {}
     for state, ncopies in (("same", 1), ("rotated", copies_rot)):
         out(f"  weights {state}; us per call, median (min):   B    packed          float           decode+matmul   tiled           "
-            f"packed/float  packed/decode  tiled/decode  tiled/packed")
-        for B in BATCHES:
+            f"packed/float  packed/decode  tiled/decode  tiled/packed" + ("   quantize+i8     i8/decode  i8/tiled" if args.i8 else ""))
+        for B in (I8_BATCHES if args.i8 else BATCHES):
             x = torch.randn((B, N), device=dev)
-            y = [torch.empty((B, C), device=dev) for _ in range(4)]
+            y = [torch.empty((B, C), device=dev) for _ in range(5 if args.i8 else 4)]
+            xq = (torch.empty((B, (N + 15) // 16 * 16), dtype=torch.int8, device=dev), torch.empty(B, device=dev))
 
             def f_packed(i):
                 p = layers[i % ncopies][0]
@@ -110,15 +115,22 @@ def measure(label, N, C, M, args, dev, out):
                 p = layers[i % ncopies][0]
                 hip.packed_dense_forward_tiled(x, p["codes"], p["bits"], p["zero_code"], p["radii"], p["alphabet"], N, out=y[3])
 
-            graphs = [capture(f, args.chain) for f in (f_packed, f_float, f_decode, f_tiled)]
+            def f_i8(i):
+                p = layers[i % ncopies][0]
+                hip.quantize_rows_i8(x, out=xq)
+                hip.packed_dense_forward_i8(xq[0], p["codes"], p["bits"], p["zero_code"], p["radii"], M, N, out=y[4], scales=xq[1])
+
+            graphs = [capture(f, args.chain) for f in (f_packed, f_float, f_decode, f_tiled) + ((f_i8,) if args.i8 else ())]
             res = timed(graphs, args.replays)
             us = [(1e3 * m / args.chain, 1e3 * lo / args.chain) for m, lo in res]
             ref64 = x.double() @ layers[(args.chain - 1) % ncopies][1].double()
             err = [float((t.double() - ref64).abs().max() / ref64.abs().max()) for t in y]
-            assert max(err) < 1e-4, err
+            assert max(err[:4]) < 1e-4, err
+            assert not args.i8 or err[4] < 0.05, err            # (int8 activations: the rounding of x, half a step of 1/127 of a row's amax)
             out(f"                                              {B:4d}  {us[0][0]:7.2f} ({us[0][1]:6.2f})  {us[1][0]:7.2f} ({us[1][1]:6.2f})  "
                 f"{us[2][0]:7.2f} ({us[2][1]:6.2f})  {us[3][0]:7.2f} ({us[3][1]:6.2f})     {us[0][0] / us[1][0]:5.2f}        "
-                f"{us[0][0] / us[2][0]:5.2f}         {us[3][0] / us[2][0]:5.2f}         {us[3][0] / us[0][0]:5.2f}")
+                f"{us[0][0] / us[2][0]:5.2f}         {us[3][0] / us[2][0]:5.2f}         {us[3][0] / us[0][0]:5.2f}"
+                + (f"      {us[4][0]:7.2f} ({us[4][1]:6.2f})    {us[4][0] / us[2][0]:5.2f}     {us[4][0] / us[3][0]:5.2f}" if args.i8 else ""))
             wins[(state, B)] = us[0][0] < us[1][0] and us[0][0] < us[2][0]
             tiled[(state, B)] = us[3][0] <= TILED_MARGIN * us[2][0]
             del graphs
@@ -154,6 +166,7 @@ def main():
     ap.add_argument("--chain", type=int, default=32, help="calls captured into one graph")
     ap.add_argument("--replays", type=int, default=15)
     ap.add_argument("--quick", action="store_true", help="4096 x 4096 ternary only, no file sizes")
+    ap.add_argument("--i8", action="store_true", help="a fifth way: row quantization + the int8 kernel, timed together; batches up to 1024")
     args = ap.parse_args()
     dev = torch.device("cuda", torch.cuda.current_device())
     lines = []
@@ -163,7 +176,7 @@ def main():
         lines.append(s)
 
     out(f"# {torch.cuda.get_device_name(dev)}; device time per call: {args.chain} calls captured into one graph, {args.replays} timed replays "
-        f"per form, the four forms alternating; median (min); us")
+        f"per form, the {'five' if args.i8 else 'four'} forms alternating; median (min); us")
     shapes = [("fc 4096 x 4096 ternary", 4096, 4096, 3)]
     if not args.quick:
         shapes += [("fc 4096 x 4096 16 levels", 4096, 4096, 16), ("VGG16 fc1 25088 x 4096 ternary", 25088, 4096, 3),
