@@ -14,6 +14,7 @@
 
 #include "../../include/gpfq.h"
 #include "gpfq_launch.hpp"
+#include "gpfq_packed.hpp"
 
 namespace {
 

@@ -326,11 +326,9 @@ hipError_t launch_column_radii(const float *W, int64_t R, int64_t C, int64_t ld,
                                double *radii, float *Wp, int64_t ldo, int64_t c_lo, int64_t c_hi, hipStream_t stream);
 hipError_t launch_assemble_colrad(const void *qidx, int bits, int keras_layout, const AlphabetArg &A, const AlphabetBig *big,
                                   const double *radii, int64_t N, int64_t C, float *Q, void *idxT, hipStream_t stream);
-// gpfq_packed.hip: the packed low-bit form of a kernel [R][C] -- the width and pitch rules (host only), Q ->
-// indices + the two counters (zeroed on the stream in front of the launch), indices -> packed rows [C][pitch] and back, and the Dense
-// forward pass y = x . q (+ bias) from the packed rows.  U: the unit alphabet (at most 64 members).
-int packed_bits(int M, int zero_code);
-size_t packed_row_bytes(int64_t R, int bits);
+// gpfq_packed.hip: the packed low-bit form of a kernel [R][C] (gpfq_packed.hpp: the format, its width and pitch
+// rules) -- Q -> indices + the two counters (zeroed on the stream in front of the launch), indices -> packed rows [C][pitch] and back,
+// and the Dense forward pass y = x . q (+ bias) from the packed rows.  U: the unit alphabet (at most 64 members).
 hipError_t launch_encode_kernel(const float *Q, int64_t R, int64_t C, int64_t ld, const double *radii, const AlphabetArg &U, int8_t *idx,
                                 unsigned long long *counters, hipStream_t stream);
 hipError_t launch_pack_codes(const int8_t *idx, int64_t R, int64_t C, int bits, int zero_code, uint8_t *packed, hipStream_t stream);

@@ -1,10 +1,5 @@
-// Packed low-bit form of a quantized kernel and the Dense forward pass that runs from it.
-//
-// A kernel is the row-major f32 matrix [R][C] of include/gpfq.h's output channels (a Dense kernel [N][C]; a Conv2D kernel viewed as
-// [kh*kw*Cin][F]; a DepthwiseConv2D kernel viewed as [kh*kw][Cin*mult]).  Its packed form holds, per output channel j, one row of
-// `pitch` bytes: code t at bit t * bits of the row, little-endian (bits = 2, 4 or 8; pitch = ceil(R * bits / 8) rounded up to 16; pad
-// bits zero), code = index + zero_code, code 0 = the literal zero when zero_code is 1.  The value of code c of channel j is
-// (float)(radii[j] * unit[c - zero_code]): what gpfq_assemble_kernel_colrad installs.
+// Packed low-bit form of a quantized kernel and the Dense forward pass that runs from it.  gpfq_packed.hpp states
+// the format.
 //
 //   gpfq_encode_kernel          Q -> indices (the first member that reproduces the float; -1 for a zero no member gives) + two counters
 //   gpfq_pack_codes_kernel      indices [R][C] -> packed rows [C][pitch]
@@ -20,6 +15,7 @@
 
 #include "gpfq_device.hpp"
 #include "gpfq_launch.hpp"
+#include "gpfq_packed.hpp"
 
 namespace gpfq {
 
@@ -40,7 +36,7 @@ gpfq_encode_kernel(const float *__restrict__ Q, int64_t R, int64_t C, int64_t ld
     const int64_t j = (int64_t)blockIdx.x * kEncCols + lane;
     const bool live = j < C;
     if (threadIdx.x < 2) cnt[threadIdx.x] = 0u;
-    for (int k = r0; k < U.M; k += kEncRowsPerSweep) val[k][lane] = live ? (float)(radii[j] * U.a[k]) : 0.f;
+    for (int k = r0; k < U.M; k += kEncRowsPerSweep) val[k][lane] = live ? index_value(k, radii[j], U) : 0.f;
     __syncthreads();
     unsigned zeros = 0u, misses = 0u;
     if (live) {
@@ -98,7 +94,7 @@ gpfq_unpack_kernel(const uint8_t *__restrict__ packed, int bits, int zero_code, 
             const int64_t t = w * per + i;
             if (t >= R) break;
             const int k = (int)((word >> (i * bits)) & mask) - zero_code;
-            if (Q) Q[t * ldq + j] = (k >= 0 && k < U.M) ? (float)(rad * U.a[k]) : 0.f;
+            if (Q) Q[t * ldq + j] = index_value(k, rad, U);
             if (idx) idx[t * C + j] = (int8_t)(k < U.M ? k : -1);
         }
     }
@@ -140,9 +136,7 @@ gpfq_packed_dense_kernel(const float *__restrict__ x, int64_t B, int64_t ldx, co
                          int zero_code, const double *__restrict__ radii, AlphabetArg U, const float *__restrict__ bias, int64_t N,
                          int64_t C, float *__restrict__ y, int64_t ldy)
 {
-    constexpr int W = 128 / BITS, NQ = W / 4;
-    constexpr int P = BITS == 2 ? 2 : 1;           // weights per table entry
-    constexpr int IB = P * BITS, TE = 1 << IB;     // index bits, entries per table
+    constexpr int W = packed_group_weights(BITS), NQ = W / 4, P = packed_entry_weights(BITS), TE = packed_table_entries(BITS);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *xs = reinterpret_cast<float *>(smem);
     float *tab = xs + BT * W * 64;
@@ -150,8 +144,7 @@ gpfq_packed_dense_kernel(const float *__restrict__ x, int64_t B, int64_t ldx, co
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int64_t j0 = (int64_t)blockIdx.x * kFwdNeurons;
 
-    // the tables: entry c of neuron n holds the weights of the P codes in c (code 0 = the literal zero when zero_code is 1; codes no
-    // member has: 0)
+    // the tables: entry c of neuron n holds the weights of the P codes in c (index_value's rule, and 0 for neurons past the layer)
     for (int e = tid; e < kFwdNeurons * TE * P; e += kFwdThreads) {
         const int n = e / (TE * P), c = (e / P) % TE, p = e % P;
         const int k = ((c >> (p * BITS)) & ((1 << BITS) - 1)) - zero_code;
@@ -207,19 +200,9 @@ gpfq_packed_dense_kernel(const float *__restrict__ x, int64_t B, int64_t ldx, co
                         xv[bb] = *reinterpret_cast<const float4 *>(xs + ((bb * NQ + q) * 64 + ((lane + q) & 63)) * 4);
 #pragma unroll
                     for (int r = 0; r < kFwdNR; ++r) {
-                        const unsigned words[4] = {cw[r].x, cw[r].y, cw[r].z, cw[r].w};
                         float w4[4];
 #pragma unroll
-                        for (int i = 0; i < 4; i += P) {
-                            const int bit = (4 * q + i) * BITS;
-                            const unsigned c = (words[bit >> 5] >> (bit & 31)) & (unsigned)(TE - 1);
-                            if constexpr (P == 2) {
-                                const float2 pr = *reinterpret_cast<const float2 *>(tabr[r] + 2 * c);
-                                w4[i] = pr.x; w4[i + 1] = pr.y;
-                            } else {
-                                w4[i] = tabr[r][c];
-                            }
-                        }
+                        for (int i = 0; i < 4; i += P) lookup_weights<BITS, 1>(cw[r], 4 * q + i, tabr[r], w4 + i);
 #pragma unroll
                         for (int bb = 0; bb < BT; ++bb) {
                             float a = acc[r][bb];
@@ -246,29 +229,18 @@ gpfq_packed_dense_kernel(const float *__restrict__ x, int64_t B, int64_t ldx, co
 }
 
 template <int BITS, int BT>
-hipError_t launch_forward_bt(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int64_t pitch, int zero_code,
-                             const double *radii, const AlphabetArg &U, const float *bias, int64_t N, int64_t C, float *y, int64_t ldy,
+hipError_t launch_forward_bt(const float *x, int64_t B, int64_t ldx, const PackedLayer &L, const AlphabetArg &U, const PackedOut &out,
                              hipStream_t stream)
 {
-    constexpr int W = 128 / BITS, P = BITS == 2 ? 2 : 1, TE = 1 << (P * BITS);
+    constexpr int W = packed_group_weights(BITS), P = packed_entry_weights(BITS), TE = packed_table_entries(BITS);
     const size_t lds = ((size_t)BT * W * 64 + (size_t)kFwdNeurons * TE * P) * sizeof(float);
     auto kernel = gpfq_packed_dense_kernel<BITS, BT>;
     hipError_t e = ensure_dynamic_lds((const void *)kernel, lds);
     if (e != hipSuccess) return e;
-    const int64_t blocks = (C + kFwdNeurons - 1) / kFwdNeurons;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kFwdThreads), lds, stream, x, B, ldx, packed, pitch, zero_code, radii, U, bias,
-                       N, C, y, ldy);
+    const int64_t blocks = (L.C + kFwdNeurons - 1) / kFwdNeurons;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kFwdThreads), lds, stream, x, B, ldx, L.packed, L.pitch, L.zero_code, L.radii,
+                       U, L.bias, L.N, L.C, out.y, out.ldy);
     return hipGetLastError();
-}
-
-template <int BITS>
-hipError_t launch_forward_bits(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int64_t pitch, int zero_code,
-                               const double *radii, const AlphabetArg &U, const float *bias, int64_t N, int64_t C, float *y, int64_t ldy,
-                               hipStream_t stream)
-{
-    if (B == 1) return launch_forward_bt<BITS, 1>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
-    if (B == 2) return launch_forward_bt<BITS, 2>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
-    return launch_forward_bt<BITS, 4>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
 }
 
 unsigned grid_for(int64_t total)
@@ -329,10 +301,11 @@ hipError_t launch_packed_dense_forward(const float *x, int64_t B, int64_t ldx, c
                                        const double *radii, const AlphabetArg &U, const float *bias, int64_t N, int64_t C, float *y,
                                        int64_t ldy, hipStream_t stream)
 {
-    const int64_t pitch = (int64_t)packed_row_bytes(N, bits);
-    if (bits == 2) return launch_forward_bits<2>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
-    if (bits == 4) return launch_forward_bits<4>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
-    return launch_forward_bits<8>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
+    const PackedLayer L(packed, bits, zero_code, radii, bias, N, C);
+    const PackedOut out{y, ldy};
+    return packed_dispatch(bits, row_tier(B), [&](auto width, auto tier) {
+        return launch_forward_bt<decltype(width)::value, decltype(tier)::value>(x, B, ldx, L, U, out, stream);
+    });
 }
 
 }  // namespace gpfq

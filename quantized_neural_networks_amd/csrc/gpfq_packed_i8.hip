@@ -31,18 +31,13 @@
 
 #include "gpfq_device.hpp"
 #include "gpfq_launch.hpp"
+#include "gpfq_packed.hpp"
 
 namespace gpfq {
 
 namespace {
 
 constexpr int kQuantThreads = 256;                  // one workgroup per batch row
-
-constexpr int kI8Waves = 4;                         // wavefronts per workgroup: they split K
-constexpr int kI8Threads = kI8Waves * 64;
-constexpr int kI8Channels = 16;                     // output channels per workgroup: one MFMA column tile
-constexpr int kI8WaveGroups = 4;                    // 16-byte groups per wavefront and round: one per lane quarter
-constexpr int kI8RoundGroups = kI8Waves * kI8WaveGroups;
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
@@ -149,29 +144,29 @@ __device__ inline i32x4 decode_operand(const unsigned (&words)[4], int i, const 
 }
 
 template <int BITS, int MT>
-__global__ void __launch_bounds__(kI8Threads)
+__global__ void __launch_bounds__(kMfmaThreads)
 gpfq_packed_dense_i8_kernel(const int8_t *__restrict__ xq, int64_t B, int64_t ldq, const float *__restrict__ scales,
                             const uint8_t *__restrict__ packed, int64_t pitch, int zero_code, const double *__restrict__ radii, int M,
                             const float *__restrict__ bias, int N, int64_t C, float *__restrict__ y, int64_t ldy)
 {
-    constexpr int W = 128 / BITS, NB = W / 16;      // weights and B operands per group
-    constexpr int R = 16 * MT;                      // batch rows per pass
-    __shared__ int red[kI8Waves * MT * 4 * 64];     // the partial tiles [wave][tile][reg][lane]
+    constexpr int W = packed_group_weights(BITS), NB = W / 16;       // weights and B operands per group
+    constexpr int R = mfma_pass_rows(MT);
+    __shared__ int red[kMfmaWaves * MT * 4 * 64];     // the partial tiles [wave][tile][reg][lane]
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int r = lane & 15, h = lane >> 4;
-    const int64_t j0 = (int64_t)blockIdx.x * kI8Channels;
+    const int64_t j0 = (int64_t)blockIdx.x * kMfmaChannels;
 
     const DecodeBytes D = decode_bytes(zero_code, M);
     const unsigned tab = decode4(0x03020100u, D);   // the weights of the codes 0..3 (2 bits)
 
     const int64_t groups = pitch / 16;
-    const int64_t rounds = (groups + kI8RoundGroups - 1) / kI8RoundGroups;
+    const int64_t rounds = (groups + kMfmaRoundGroups - 1) / kMfmaRoundGroups;
     const int64_t j = j0 + r;
     const uint4 *rowp = reinterpret_cast<const uint4 *>(packed + (j < C ? j : C - 1) * pitch);
     const double unit = j < C ? radii[j] / (double)(M - 1) : 0.0;
     auto codes = [&](int64_t round) {
-        const int64_t g = round * kI8RoundGroups + wave * kI8WaveGroups + h;
+        const int64_t g = round * kMfmaRoundGroups + wave * kMfmaWaveGroups + h;
         return g < groups ? rowp[g] : make_uint4(0u, 0u, 0u, 0u);
     };
 
@@ -189,9 +184,9 @@ gpfq_packed_dense_i8_kernel(const int8_t *__restrict__ xq, int64_t B, int64_t ld
         for (int64_t round = 0; round < rounds; ++round) {
             const uint4 cw = cwn;
             if (round + 1 < rounds) cwn = codes(round + 1);
-            if (round * kI8RoundGroups + wave * kI8WaveGroups >= groups) continue;               // (wave-uniform)
+            if (round * kMfmaRoundGroups + wave * kMfmaWaveGroups >= groups) continue;               // (wave-uniform)
             const unsigned words[4] = {cw.x, cw.y, cw.z, cw.w};
-            const int64_t t0 = (round * kI8RoundGroups + wave * kI8WaveGroups + h) * W;        // this quarter's first weight
+            const int64_t t0 = (round * kMfmaRoundGroups + wave * kMfmaWaveGroups + h) * W;        // this quarter's first weight
 
             i32x4 a[NB][MT];
 #pragma unroll
@@ -230,7 +225,7 @@ gpfq_packed_dense_i8_kernel(const int8_t *__restrict__ xq, int64_t B, int64_t ld
         for (int m = 0; m < MT; ++m) {
             int s = 0;
 #pragma unroll
-            for (int w = 0; w < kI8Waves; ++w) s += red[((w * MT + m) * 4 + wave) * 64 + lane];
+            for (int w = 0; w < kMfmaWaves; ++w) s += red[((w * MT + m) * 4 + wave) * 64 + lane];
             const int64_t b = b0 + m * 16 + 4 * h + wave;             // (this thread sums register `wave` of every partial tile)
             if (j < C && b < B) {
                 const double p = ((double)s * (double)scales[b]) * unit;
@@ -242,26 +237,15 @@ gpfq_packed_dense_i8_kernel(const int8_t *__restrict__ xq, int64_t B, int64_t ld
 }
 
 template <int BITS, int MT>
-hipError_t launch_i8_mt(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int64_t pitch,
-                        int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y, int64_t ldy,
+hipError_t launch_i8_mt(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const PackedLayer &L, int M, const PackedOut &out,
                         hipStream_t stream)
 {
-    const int64_t blocks = (C + kI8Channels - 1) / kI8Channels;
-    int64_t passes = (B + 16 * MT - 1) / (16 * MT);
+    const int64_t blocks = (L.C + kMfmaChannels - 1) / kMfmaChannels;
+    int64_t passes = (B + mfma_pass_rows(MT) - 1) / mfma_pass_rows(MT);
     if (passes > 65535) passes = 65535;
-    hipLaunchKernelGGL((gpfq_packed_dense_i8_kernel<BITS, MT>), dim3((unsigned)blocks, (unsigned)passes), dim3(kI8Threads), 0, stream, xq,
-                       B, ldq, scales, packed, pitch, zero_code, radii, M, bias, (int)N, C, y, ldy);
+    hipLaunchKernelGGL((gpfq_packed_dense_i8_kernel<BITS, MT>), dim3((unsigned)blocks, (unsigned)passes), dim3(kMfmaThreads), 0, stream,
+                       xq, B, ldq, scales, L.packed, L.pitch, L.zero_code, L.radii, M, L.bias, (int)L.N, L.C, out.y, out.ldy);
     return hipGetLastError();
-}
-
-template <int BITS>
-hipError_t launch_i8_bits(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int64_t pitch,
-                          int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y, int64_t ldy,
-                          hipStream_t stream)
-{
-    if (B <= 16) return launch_i8_mt<BITS, 1>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
-    if (B <= 32) return launch_i8_mt<BITS, 2>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
-    return launch_i8_mt<BITS, 4>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
 }
 
 }  // namespace
@@ -277,10 +261,11 @@ hipError_t launch_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t l
                                           int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
                                           int64_t ldy, hipStream_t stream)
 {
-    const int64_t pitch = (int64_t)packed_row_bytes(N, bits);
-    if (bits == 2) return launch_i8_bits<2>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
-    if (bits == 4) return launch_i8_bits<4>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
-    return launch_i8_bits<8>(xq, B, ldq, scales, packed, pitch, zero_code, radii, M, bias, N, C, y, ldy, stream);
+    const PackedLayer L(packed, bits, zero_code, radii, bias, N, C);
+    const PackedOut out{y, ldy};
+    return packed_dispatch(bits, mfma_tier(B), [&](auto width, auto tier) {
+        return launch_i8_mt<decltype(width)::value, decltype(tier)::value>(xq, B, ldq, scales, L, M, out, stream);
+    });
 }
 
 }  // namespace gpfq

@@ -1,5 +1,5 @@
 // The Dense forward pass from packed rows on exact-f32 matrix tiles: y = x . q (+ bias) for batches beyond the
-// few rows gpfq_packed_dense_kernel (gpfq_packed.hip) is for.  The format of the packed rows is that unit's.
+// few rows gpfq_packed_dense_kernel (gpfq_packed.hip) is for.  gpfq_packed.hpp states the format of the packed rows and the tile.
 //
 //   gpfq_packed_dense_tiled_kernel<BITS, MT>
 //       One workgroup owns a column tile of 16 neurons and walks the batch in passes of 16 MT rows (MT = 1, 2, 4); its four wavefronts
@@ -27,38 +27,31 @@
 
 #include "gpfq_device.hpp"
 #include "gpfq_launch.hpp"
+#include "gpfq_packed.hpp"
 
 namespace gpfq {
 
 namespace {
-
-constexpr int kTiledWaves = 4;                      // wavefronts per workgroup: they split K
-constexpr int kTiledThreads = kTiledWaves * 64;
-constexpr int kTiledNeurons = 16;                   // neurons per workgroup: one MFMA column tile
-constexpr int kTiledWaveGroups = 4;                 // 16-byte groups per wavefront and round: one per lane quarter
-constexpr int kTiledRoundGroups = kTiledWaves * kTiledWaveGroups;
 
 // Weights per group and step: a whole group where it fits, and at least 32 of them where a group has as many -- 128 contiguous bytes
 // of a row of x, one cache line when the row is aligned; a step of 16 left half of every line it fetched to be fetched again --
 // within 128 KiB of LDS for x, [16 groups][E][16 MT rows] floats, and 32 slots of 16 bytes per thread.
 constexpr int tiled_step(int bits, int mt)
 {
-    const int w = 128 / bits, most = mt == 1 ? 64 : 32;
+    const int w = packed_group_weights(bits), most = mt == 1 ? 64 : 32;
     return w < most ? w : most;
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int BITS, int MT>
-__global__ void __launch_bounds__(kTiledThreads)
+__global__ void __launch_bounds__(kMfmaThreads)
 gpfq_packed_dense_tiled_kernel(const float *__restrict__ x, int64_t B, int64_t ldx, const uint8_t *__restrict__ packed, int64_t pitch,
                                int zero_code, const double *__restrict__ radii, AlphabetArg U, const float *__restrict__ bias, int64_t N,
                                int64_t C, float *__restrict__ y, int64_t ldy)
 {
-    constexpr int W = 128 / BITS, E = tiled_step(BITS, MT), STEPS = W / E, NQ = E / 4;     // NQ: 16-byte quads of x per group and step
-    constexpr int P = BITS == 2 ? 2 : 1;            // weights per table entry
-    constexpr int IB = P * BITS, TE = 1 << IB;      // index bits, entries per table
-    constexpr int R = 16 * MT;                      // batch rows per pass
+    constexpr int W = packed_group_weights(BITS), P = packed_entry_weights(BITS), TE = packed_table_entries(BITS), R = mfma_pass_rows(MT);
+    constexpr int E = tiled_step(BITS, MT), STEPS = W / E, NQ = E / 4;               // NQ: 16-byte quads of x per group and step
     constexpr int SL = R * NQ / 16;                 // 16-byte slots of x a thread stages per step: 16 NQ R slots, 256 threads
     // the 8 lanes a 16-byte LDS store serves together are NQ quads x RL rows (NQ = 4) or 8 quads of one row: a row rotated by FROT
     // times its quad puts them on 8 different slots
@@ -69,11 +62,11 @@ gpfq_packed_dense_tiled_kernel(const float *__restrict__ x, int64_t B, int64_t l
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int r = lane & 15, h = lane >> 4;
-    const int64_t j0 = (int64_t)blockIdx.x * kTiledNeurons;
+    const int64_t j0 = (int64_t)blockIdx.x * kMfmaChannels;
 
-    // the tables: column i of entry c holds the weights of the P codes in c for neuron i & 15 (code 0 = the literal zero when
-    // zero_code is 1; codes no member has, and neurons past the layer: 0)
-    for (int e = tid; e < TE * 32 * P; e += kTiledThreads) {
+    // the tables: column i of entry c holds the weights of the P codes in c for neuron i & 15 (index_value's rule, and 0 for neurons
+    // past the layer)
+    for (int e = tid; e < TE * 32 * P; e += kMfmaThreads) {
         const int c = e / (32 * P), i = (e / P) % 32, p = e % P;
         const int k = ((c >> (p * BITS)) & ((1 << BITS) - 1)) - zero_code;
         const int64_t j = j0 + (i & 15);
@@ -82,7 +75,7 @@ gpfq_packed_dense_tiled_kernel(const float *__restrict__ x, int64_t B, int64_t l
     const char *tabl = reinterpret_cast<const char *>(tab) + (lane & 31) * (4 * P);
 
     const int64_t groups = pitch / 16;
-    const int64_t rounds = (groups + kTiledRoundGroups - 1) / kTiledRoundGroups;
+    const int64_t rounds = (groups + kMfmaRoundGroups - 1) / kMfmaRoundGroups;
     const uint4 *rowp;
     {
         int64_t j = j0 + r;
@@ -108,7 +101,7 @@ gpfq_packed_dense_tiled_kernel(const float *__restrict__ x, int64_t B, int64_t l
     // waits for a load here).  x is not read at or beyond row B -- a lane of such a row reads row 0, which exists -- or column N:
     // only the one slot that straddles N goes element by element, and slots beyond N read nothing.
     auto fetch = [&](int64_t round, int step) {
-        const int64_t t = (round * kTiledRoundGroups + sg) * W + step * E + 4 * sq;
+        const int64_t t = (round * kMfmaRoundGroups + sg) * W + step * E + 4 * sq;
         if (t + 3 < N) {
             if (whole) {                            // (workgroup-uniform: the rows are RI ldx apart)
                 const float *px = xfirst + t;
@@ -133,8 +126,8 @@ gpfq_packed_dense_tiled_kernel(const float *__restrict__ x, int64_t B, int64_t l
     };
     // ... and from the registers to LDS: weights at or beyond N -- pad codes, groups past the row -- and rows at or beyond B meet zeros
     auto stage = [&](int64_t b0, int64_t round, int step) {
-        const int64_t t = (round * kTiledRoundGroups + sg) * W + step * E + 4 * sq;
-        const int64_t tend = (round * kTiledRoundGroups + kTiledRoundGroups - 1) * W + step * E + E;
+        const int64_t t = (round * kMfmaRoundGroups + sg) * W + step * E + 4 * sq;
+        const int64_t tend = (round * kMfmaRoundGroups + kMfmaRoundGroups - 1) * W + step * E + E;
         if (b0 + R <= B && tend <= N) {             // (workgroup-uniform: nothing of this step to mask)
 #pragma unroll
             for (int s = 0; s < SL; ++s) xs[slot_of(srow + RI * s)] = xr[s];
@@ -155,7 +148,7 @@ gpfq_packed_dense_tiled_kernel(const float *__restrict__ x, int64_t B, int64_t l
         }
     };
     auto codes = [&](int64_t round) {
-        const int64_t g = round * kTiledRoundGroups + wave * kTiledWaveGroups + h;
+        const int64_t g = round * kMfmaRoundGroups + wave * kMfmaWaveGroups + h;
         return g < groups ? rowp[g] : make_uint4(0u, 0u, 0u, 0u);
     };
 
@@ -170,8 +163,7 @@ gpfq_packed_dense_tiled_kernel(const float *__restrict__ x, int64_t B, int64_t l
             const uint4 cw = cwn;
             const bool last = round + 1 == rounds;
             if (!last) cwn = codes(round + 1);
-            const unsigned words[4] = {cw.x, cw.y, cw.z, cw.w};
-            const bool work = round * kTiledRoundGroups + wave * kTiledWaveGroups < groups;      // (wave-uniform)
+            const bool work = round * kMfmaRoundGroups + wave * kMfmaWaveGroups < groups;      // (wave-uniform)
 #pragma unroll
             for (int step = 0; step < STEPS; ++step) {
                 __syncthreads();                    // the step before this one has been read (first: the tables are written)
@@ -188,20 +180,11 @@ gpfq_packed_dense_tiled_kernel(const float *__restrict__ x, int64_t B, int64_t l
                     for (int q = 0; q < NQ; ++q) {
                         float wt[4];                // four weights, decoded once
 #pragma unroll
-                        for (int i = 0; i < 4; i += P) {
-                            const int bit = (step * E + 4 * q + i) * BITS;
-                            const unsigned c = (words[bit >> 5] >> (bit & 31)) & (unsigned)(TE - 1);
-                            if constexpr (P == 2) {
-                                const float2 pr = *reinterpret_cast<const float2 *>(tabl + c * (32 * 8));
-                                wt[i] = pr.x; wt[i + 1] = pr.y;
-                            } else {
-                                wt[i] = *reinterpret_cast<const float *>(tabl + c * (32 * 4));
-                            }
-                        }
+                        for (int i = 0; i < 4; i += P) lookup_weights<BITS, 32 * sizeof(float)>(cw, step * E + 4 * q + i, tabl, wt + i);
                         float4 xv[MT];
 #pragma unroll
                         for (int m = 0; m < MT; ++m)
-                            xv[m] = xs[((wave * kTiledWaveGroups + h) * NQ + q) * R + m * 16 + ((r + FROT * q) & 15)];
+                            xv[m] = xs[((wave * kMfmaWaveGroups + h) * NQ + q) * R + m * 16 + ((r + FROT * q) & 15)];
 #pragma unroll
                         for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[m].x, wt[0], acc[m], 0, 0, 0);
 #pragma unroll
@@ -228,7 +211,7 @@ gpfq_packed_dense_tiled_kernel(const float *__restrict__ x, int64_t B, int64_t l
         for (int m = 0; m < MT; ++m) {
             float s = red[((0 * MT + m) * 4 + wave) * 64 + lane];
 #pragma unroll
-            for (int w = 1; w < kTiledWaves; ++w) s += red[((w * MT + m) * 4 + wave) * 64 + lane];
+            for (int w = 1; w < kMfmaWaves; ++w) s += red[((w * MT + m) * 4 + wave) * 64 + lane];
             const int64_t b = b0 + m * 16 + 4 * h + wave;             // (this thread sums register `wave` of every partial tile)
             if (j < C && b < B) y[b * ldy + j] = bias ? s + bias[j] : s;
         }
@@ -236,29 +219,18 @@ gpfq_packed_dense_tiled_kernel(const float *__restrict__ x, int64_t B, int64_t l
 }
 
 template <int BITS, int MT>
-hipError_t launch_tiled_mt(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int64_t pitch, int zero_code,
-                           const double *radii, const AlphabetArg &U, const float *bias, int64_t N, int64_t C, float *y, int64_t ldy,
+hipError_t launch_tiled_mt(const float *x, int64_t B, int64_t ldx, const PackedLayer &L, const AlphabetArg &U, const PackedOut &out,
                            hipStream_t stream)
 {
-    constexpr int P = BITS == 2 ? 2 : 1, TE = 1 << (P * BITS);
-    const size_t lds = ((size_t)kTiledRoundGroups * tiled_step(BITS, MT) * 16 * MT + (size_t)TE * 32 * P) * sizeof(float);
+    constexpr int P = packed_entry_weights(BITS), TE = packed_table_entries(BITS);
+    const size_t lds = ((size_t)kMfmaRoundGroups * tiled_step(BITS, MT) * mfma_pass_rows(MT) + (size_t)TE * 32 * P) * sizeof(float);
     auto kernel = gpfq_packed_dense_tiled_kernel<BITS, MT>;
     hipError_t e = ensure_dynamic_lds((const void *)kernel, lds);
     if (e != hipSuccess) return e;
-    const int64_t blocks = (C + kTiledNeurons - 1) / kTiledNeurons;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kTiledThreads), lds, stream, x, B, ldx, packed, pitch, zero_code, radii, U,
-                       bias, N, C, y, ldy);
+    const int64_t blocks = (L.C + kMfmaChannels - 1) / kMfmaChannels;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kMfmaThreads), lds, stream, x, B, ldx, L.packed, L.pitch, L.zero_code, L.radii,
+                       U, L.bias, L.N, L.C, out.y, out.ldy);
     return hipGetLastError();
-}
-
-template <int BITS>
-hipError_t launch_tiled_bits(const float *x, int64_t B, int64_t ldx, const uint8_t *packed, int64_t pitch, int zero_code,
-                             const double *radii, const AlphabetArg &U, const float *bias, int64_t N, int64_t C, float *y, int64_t ldy,
-                             hipStream_t stream)
-{
-    if (B <= 16) return launch_tiled_mt<BITS, 1>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
-    if (B <= 32) return launch_tiled_mt<BITS, 2>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
-    return launch_tiled_mt<BITS, 4>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
 }
 
 }  // namespace
@@ -267,10 +239,11 @@ hipError_t launch_packed_dense_forward_tiled(const float *x, int64_t B, int64_t 
                                              const double *radii, const AlphabetArg &U, const float *bias, int64_t N, int64_t C, float *y,
                                              int64_t ldy, hipStream_t stream)
 {
-    const int64_t pitch = (int64_t)packed_row_bytes(N, bits);
-    if (bits == 2) return launch_tiled_bits<2>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
-    if (bits == 4) return launch_tiled_bits<4>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
-    return launch_tiled_bits<8>(x, B, ldx, packed, pitch, zero_code, radii, U, bias, N, C, y, ldy, stream);
+    const PackedLayer L(packed, bits, zero_code, radii, bias, N, C);
+    const PackedOut out{y, ldy};
+    return packed_dispatch(bits, mfma_tier(B), [&](auto width, auto tier) {
+        return launch_tiled_mt<decltype(width)::value, decltype(tier)::value>(x, B, ldx, L, U, out, stream);
+    });
 }
 
 }  // namespace gpfq

@@ -1386,6 +1386,22 @@ def unpack_kernel(packed, bits, zero_code, radii, unit_alphabet, R, want_values=
     return Q, idx
 
 
+def _packed_bias_out(bias, out, B, C, device):
+    """What the three forward entries share: the checks of `bias` (f32 [C] or None) and `out` (f32 [B][C], rows contiguous; made here if
+    None) -> (bias pointer or None, out pointer, out's row pitch, out)."""
+    if bias is not None:
+        _dev(bias, torch.float32, "bias")
+        if bias.numel() != C or not bias.is_contiguous():
+            raise GpfqError(f"bias must be a contiguous [{C}] tensor")
+    if out is None:
+        out = torch.empty((B, C), dtype=torch.float32, device=device)
+    _dev(out, torch.float32, "out")
+    yp, By, Cy, ldy = _rows(out, "out")
+    if (By, Cy) != (B, C):
+        raise GpfqError(f"out {tuple(out.shape)} must be [{B}][{C}]")
+    return (bias.data_ptr() if bias is not None else None), yp, ldy, out
+
+
 def _packed_forward(entry, x, packed, bits, zero_code, radii, unit_alphabet, N, bias, out):
     """The checks and the call of both forward entries (the same parameter list)."""
     _dev(x, torch.float32, "x")
@@ -1393,20 +1409,11 @@ def _packed_forward(entry, x, packed, bits, zero_code, radii, unit_alphabet, N, 
     if Nx != int(N):
         raise GpfqError(f"x {tuple(x.shape)} does not have the layer's {N} input features")
     C = _packed_args(packed, bits, zero_code, radii, N)
-    if bias is not None:
-        _dev(bias, torch.float32, "bias")
-        if bias.numel() != C or not bias.is_contiguous():
-            raise GpfqError(f"bias must be a contiguous [{C}] tensor")
     arr, M = _unit64(unit_alphabet)
-    if out is None:
-        out = torch.empty((B, C), dtype=torch.float32, device=x.device)
-    _dev(out, torch.float32, "out")
-    yp, By, Cy, ldy = _rows(out, "out")
-    if (By, Cy) != (B, C):
-        raise GpfqError(f"out {tuple(out.shape)} must be [{B}][{C}]")
+    bp, yp, ldy, out = _packed_bias_out(bias, out, B, C, x.device)
     with torch.cuda.device(x.device):
-        _check(getattr(load(), entry)(xp, B, ldx, packed.data_ptr(), int(bits), int(zero_code), radii.data_ptr(), arr, M,
-                                      bias.data_ptr() if bias is not None else None, int(N), C, yp, ldy, _stream()), entry)
+        _check(getattr(load(), entry)(xp, B, ldx, packed.data_ptr(), int(bits), int(zero_code), radii.data_ptr(), arr, M, bp, int(N), C,
+                                      yp, ldy, _stream()), entry)
     return out
 
 
@@ -1468,18 +1475,9 @@ def packed_dense_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, N, bias=
     if scales.numel() != B or not scales.is_contiguous():
         raise GpfqError(f"scales must be a contiguous [{B}] tensor")
     C = _packed_args(packed, bits, zero_code, radii, N)
-    if bias is not None:
-        _dev(bias, torch.float32, "bias")
-        if bias.numel() != C or not bias.is_contiguous():
-            raise GpfqError(f"bias must be a contiguous [{C}] tensor")
-    if out is None:
-        out = torch.empty((B, C), dtype=torch.float32, device=xq.device)
-    _dev(out, torch.float32, "out")
-    yp, By, Cy, ldy = _rows(out, "out")
-    if (By, Cy) != (B, C):
-        raise GpfqError(f"out {tuple(out.shape)} must be [{B}][{C}]")
+    bp, yp, ldy, out = _packed_bias_out(bias, out, B, C, xq.device)
     with torch.cuda.device(xq.device):
         _check(load().gpfq_packed_dense_forward_i8(qp, B, ldq, scales.data_ptr(), packed.data_ptr(), int(bits), int(zero_code),
-                                                   radii.data_ptr(), int(M), bias.data_ptr() if bias is not None else None, int(N), C,
-                                                   yp, ldy, _stream()), "gpfq_packed_dense_forward_i8")
+                                                   radii.data_ptr(), int(M), bp, int(N), C, yp, ldy, _stream()),
+               "gpfq_packed_dense_forward_i8")
     return out

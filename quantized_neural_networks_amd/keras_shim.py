@@ -273,6 +273,19 @@ class PackedDense(Dense):
         c.name = self.name
         return c
 
+    def route(self, batch):
+        """Which way a batch of `batch` rows runs: "i8", "row" (gpfq_packed_dense_forward), "tiled" (gpfq_packed_dense_forward_tiled) or
+        "matmul" (decode + torch.matmul: an empty batch, and float32 batches beyond the packed kernels' limits)."""
+        if self.activations not in self.ACTIVATIONS:
+            raise ValueError(f"PackedDense layer {self.name}: activations must be one of {self.ACTIVATIONS}, got {self.activations!r}")
+        if batch <= 0:
+            return "matmul"
+        if self.activations == "int8":
+            return "i8"
+        if batch <= PACKED_FORWARD_MAX_BATCH:
+            return "row"
+        return "tiled" if batch <= PACKED_TILED_MAX_BATCH else "matmul"
+
     def call(self, x):
         from . import hip
         if self.packed is None:
@@ -280,13 +293,12 @@ class PackedDense(Dense):
         x2 = x.reshape(-1, self.fan_in)
         bias = self._weights[0] if self.use_bias else None
         p = self.packed
-        if self.activations not in self.ACTIVATIONS:
-            raise ValueError(f"PackedDense layer {self.name}: activations must be one of {self.ACTIVATIONS}, got {self.activations!r}")
-        if self.activations == "int8" and x2.shape[0] > 0:
+        route = self.route(x2.shape[0])
+        if route == "i8":
             y = hip.packed_dense_forward_i8(x2.contiguous(), p["codes"], p["bits"], p["zero_code"], p["radii"], len(p["alphabet"]),
                                             self.fan_in, bias=bias)
-        elif 0 < x2.shape[0] <= max(PACKED_FORWARD_MAX_BATCH, PACKED_TILED_MAX_BATCH):
-            forward = hip.packed_dense_forward if x2.shape[0] <= PACKED_FORWARD_MAX_BATCH else hip.packed_dense_forward_tiled
+        elif route != "matmul":
+            forward = hip.packed_dense_forward if route == "row" else hip.packed_dense_forward_tiled
             y = forward(x2.contiguous(), p["codes"], p["bits"], p["zero_code"], p["radii"], p["alphabet"], self.fan_in, bias=bias)
         else:
             y = x2 @ self._kernel()

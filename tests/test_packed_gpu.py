@@ -17,39 +17,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _packed_ref as ref  # noqa: E402
+from _packed_gpu import FORWARD_CASES, U24, deploy, hip, layer as _layer, padded_x as _padded_x  # noqa: E402, F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-U24 = 2.0 ** -24
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from quantized_neural_networks_amd import build, hip
-    build.build()
-    hip.load()
-    return hip
-
-
-@pytest.fixture(scope="module")
-def deploy(hip):
-    from quantized_neural_networks_amd import deploy
-    return deploy
-
-
-def _layer(rng, R, C, M, zeros):
-    """A random on-alphabet kernel [R][C]: per-channel radii with one channel of radius 0 (C > 1), literal zeros on request."""
-    unit = np.linspace(-1, 1, M)
-    radii = rng.uniform(0.05, 2.0, C)
-    if C > 1:
-        radii[C // 2] = 0.0
-    idx = rng.integers(0, M, size=(R, C))
-    if zeros:
-        idx[rng.random((R, C)) < 0.2] = -1
-        idx[0, 0] = -1
-    vals = ref.member_values(radii, unit)
-    Q = np.where(idx >= 0, vals[np.arange(C)[None, :], np.clip(idx, 0, M - 1)], np.float32(0)).astype(np.float32)
-    return unit, radii, Q
 
 
 # (M, literal zeros): all of 2 / 4 / 8 bits and both flag values occur (odd alphabets hold 0.0: their zeros are members)
@@ -121,10 +92,6 @@ def test_one_ulp_off_the_alphabet_is_one_miss(hip, deploy, M):
         deploy.pack_kernel(Q, radii, unit)
 
 
-# (M, literal zeros) -> (bits, zero_code): 2/0, 2/1, 4/0, 4/1, 8/0, 8/1
-FORWARD_CASES = [(3, False), (2, True), (16, False), (4, True), (64, False), (16, True)]
-
-
 @pytest.mark.parametrize("M,zeros", FORWARD_CASES)
 def test_forward_against_float64(hip, deploy, M, zeros):
     rng = np.random.default_rng(31 * M + zeros)
@@ -142,8 +109,7 @@ def test_forward_against_float64(hip, deploy, M, zeros):
             for B in (1, 3, 8, 9, 40):
                 x = rng.standard_normal((B, N)).astype(np.float32)
                 x[:, tail:] *= 64.0                                     # the largest entries sit where an unmasked tail would show
-                xbuf = torch.full((B, N + 5), float("nan"), dtype=torch.float32, device="cuda")     # ldx > N, never to be read
-                xbuf[:, :N] = torch.from_numpy(x).cuda()
+                xbuf = _padded_x(x)                                     # ldx > N, never to be read
                 exact = x.astype(np.float64) @ Q.astype(np.float64)
                 S = np.abs(x).astype(np.float64) @ np.abs(Q).astype(np.float64)
                 for b_d, b_h in ((None, np.zeros(C)), (bias_d, bias.astype(np.float64))):
@@ -189,8 +155,7 @@ def test_forward_second_and_later_chunks(hip, deploy, M, zeros, N):
     for B in (1, 2, 5):
         x = rng.standard_normal((B, N)).astype(np.float32)
         x[:, tail:] *= 64.0                                             # the largest entries sit where an unmasked tail would show
-        xbuf = torch.full((B, N + 5), float("nan"), dtype=torch.float32, device="cuda")
-        xbuf[:, :N] = torch.from_numpy(x).cuda()
+        xbuf = _padded_x(x)
         exact = x.astype(np.float64) @ Q.astype(np.float64)
         S = np.abs(x).astype(np.float64) @ np.abs(Q).astype(np.float64)
         for b_d, b_h in ((None, np.zeros(C)), (bias_d, bias.astype(np.float64))):

@@ -12,24 +12,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _packed_ref as ref  # noqa: E402
 import _packed_i8_ref as i8  # noqa: E402
+from _packed_gpu import FORWARD_CASES, ROUND_GROUPS, WAVE_GROUPS, hip, padded_x as _padded_x, run_sentinel  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
-
-# The kernel's own constants (csrc/gpfq_packed_i8.hip): a lane quarter owns one 16-byte group of W = 128 / bits weights, a wavefront
-# kI8WaveGroups = 4 of them, and a round of the workgroup's kI8Waves = 4 wavefronts 16; a pass is 16, 32 or 64 batch rows.
-WAVE_GROUPS, ROUND_GROUPS = 4, 16
-
-# (M, literal zeros) -> (bits, zero_code): 2/0, 2/1, 4/0, 4/1, 8/0, 8/1
-FORWARD_CASES = [(3, False), (2, True), (16, False), (4, True), (64, False), (16, True)]
 BATCHES = (1, 5, 16, 17, 33, 64, 65, 130)          # every MT (<= 16, <= 32, more), ragged last tiles, passes on a second workgroup
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from quantized_neural_networks_amd import build, hip
-    build.build()
-    hip.load()
-    return hip
 
 
 def _cuda(a):
@@ -54,14 +40,10 @@ def _xq_view(rng, B, N):
 
 
 def _run_sentinel(hip, xq, scales, pk, bits, zero_code, radii, M, N, C, bias):
-    """One call into a [:B, :C] view of a (B + 2) x (C + 2) buffer of -7; asserts the sentinels and returns y."""
-    B = xq.shape[0]
-    ybuf = torch.full((B + 2, C + 2), -7.0, dtype=torch.float32, device="cuda")
-    out = hip.packed_dense_forward_i8(xq, pk, bits, zero_code, radii, M, N, bias=bias, out=ybuf[:B, :C], scales=scales)
-    assert out.data_ptr() == ybuf.data_ptr()
-    y = ybuf.cpu().numpy()
-    assert np.all(y[B:, :] == -7.0) and np.all(y[:, C:] == -7.0)        # every sentinel row and column untouched
-    return y[:B, :C]
+    """One sentinel-framed call of the int8 entry."""
+    def forward(out):
+        return hip.packed_dense_forward_i8(xq, pk, bits, zero_code, radii, M, N, bias=bias, out=out, scales=scales)
+    return run_sentinel(forward, xq.shape[0], C)
 
 
 # ---- the row quantizer ----------------------------------------------------------------------------------------------------------
@@ -96,8 +78,7 @@ def test_row_quantizer_equals_the_restatement(hip, N):
     n16 = i8.roundup16(N)
     for B in (1, 5, 130):
         x = _special_rows(rng, B, N)
-        xbuf = torch.full((B, N + 5), float("nan"), dtype=torch.float32, device="cuda")      # ldx = N + 5, NaN in the pad columns
-        xbuf[:, :N] = _cuda(x)
+        xbuf = _padded_x(x)                                             # ldx = N + 5, NaN in the pad columns
         qbuf = torch.full((B, n16 + 16), 0x55, dtype=torch.int8, device="cuda")
         sc = torch.full((B + 1,), -7.0, dtype=torch.float32, device="cuda")
         xq, scales = hip.quantize_rows_i8(xbuf[:, :N], out=(qbuf[:, :n16], sc[:B]))

@@ -14,67 +14,19 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _packed_ref as ref  # noqa: E402
+from _packed_gpu import FORWARD_CASES, ROUND_GROUPS, U24, WAVE_GROUPS, deploy, hip, layer as _layer, padded_x as _padded_x  # noqa: E402, F401
+from _packed_gpu import run_sentinel  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-U24 = 2.0 ** -24
-
-# The kernel's own constants (csrc/gpfq_packed_tiled.hip): a lane quarter owns one 16-byte group of W = 128 / bits weights, a
-# wavefront kTiledWaveGroups = 4 of them, and a round of the workgroup's kTiledWaves = 4 wavefronts 16.
-WAVE_GROUPS, ROUND_GROUPS = 4, 16
-
-
-@pytest.fixture(scope="module")
-def hip():
-    from quantized_neural_networks_amd import build, hip
-    build.build()
-    hip.load()
-    return hip
-
-
-@pytest.fixture(scope="module")
-def deploy(hip):
-    from quantized_neural_networks_amd import deploy
-    return deploy
-
-
-def _layer(rng, R, C, M, zeros, unit=None, radii=None):
-    """A random on-alphabet kernel [R][C] as test_packed_gpu.py builds it: per-channel radii with one channel of radius 0 (C > 1),
-    literal zeros on request."""
-    unit = np.linspace(-1, 1, M) if unit is None else unit
-    if radii is None:
-        radii = rng.uniform(0.05, 2.0, C)
-        if C > 1:
-            radii[C // 2] = 0.0
-    idx = rng.integers(0, M, size=(R, C))
-    if zeros:
-        idx[rng.random((R, C)) < 0.2] = -1
-        idx[0, 0] = -1
-    vals = ref.member_values(radii, unit)
-    Q = np.where(idx >= 0, vals[np.arange(C)[None, :], np.clip(idx, 0, M - 1)], np.float32(0)).astype(np.float32)
-    return unit, radii, Q
-
-
-def _padded_x(x):
-    """x as a view with ldx = N + 5 whose pad columns hold NaN."""
-    B, N = x.shape
-    xbuf = torch.full((B, N + 5), float("nan"), dtype=torch.float32, device="cuda")
-    xbuf[:, :N] = torch.from_numpy(x).cuda()
-    return xbuf
 
 
 def _run_sentinel(hip, xview, p, unit, N, C, bias_d):
-    """One call into a [:B, :C] view of a (B + 2) x (C + 2) buffer of -7; asserts the sentinels and returns y as float64."""
-    B = xview.shape[0]
-    ybuf = torch.full((B + 2, C + 2), -7.0, dtype=torch.float32, device="cuda")
-    out = hip.packed_dense_forward_tiled(xview, p["codes"], p["bits"], p["zero_code"], p["radii"], unit, N, bias=bias_d, out=ybuf[:B, :C])
-    assert out.data_ptr() == ybuf.data_ptr()
-    y = ybuf.cpu().numpy()
-    assert np.all(y[B:, :] == -7.0) and np.all(y[:, C:] == -7.0)        # every sentinel row and column untouched
-    return y[:B, :C].astype(np.float64)
+    """One sentinel-framed call of the tiled entry; returns y as float64."""
+    def forward(out):
+        return hip.packed_dense_forward_tiled(xview, p["codes"], p["bits"], p["zero_code"], p["radii"], unit, N, bias=bias_d, out=out)
+    return run_sentinel(forward, xview.shape[0], C).astype(np.float64)
 
 
-# (M, literal zeros) -> (bits, zero_code): 2/0, 2/1, 4/0, 4/1, 8/0, 8/1
-FORWARD_CASES = [(3, False), (2, True), (16, False), (4, True), (64, False), (16, True)]
 BATCHES = (1, 5, 15, 16, 17, 33, 64, 65, 130)      # every MT (<= 16, <= 32, more), ragged last tiles, a second pass of 64 rows
 
 
