@@ -481,12 +481,24 @@ constexpr int kTop3Ship = 3;
 // the current one (needs bit 0).  Both ship; bit 0 alone measured SLOWER than neither (profiles/pk_ahead/README.md).
 // -DGPFQ_BLK_PK_AHEAD=n builds another set.
 constexpr int kPkAheadShip = 3;
+// kPrioShip: the issue priorities of the sweep wavefronts in the eight-group shapes under a symmetric alphabet (blk_sweep_role; records:
+// profiles/prio/README.md).  Two bits per form, bits 0-1 the classic form, bits 2-3 the cluster form's slices.  The low bit: the level of
+// the slot top (2) is raised in front of the slot's barrier instead of behind the control word's round trip.  The high bit: the row of
+// kPrioSched -- per age class of a six-pair wavefront on its SIMD (wave >> 2: wavefronts w, w + 4, w + 8 share SIMD w and reach it in
+// this order) the pair-steps at which its level drops 2 -> 1 and 1 -> 0.  Row 0 is the schedule by progress alone, row 1 staggers it by
+// two pair-steps per class: the oldest wavefront, which the SIMD serves first at equal levels, yields two pair-steps earlier, the
+// youngest two later.  The classic form ships both (kernel 0.034 ms, step 0.036 ms lower); the cluster slices the raised level alone --
+// the stagger makes them SLOWER (8192-sample rows 21.6 -> 22.0 ms).  -DGPFQ_BLK_PRIO=n builds another setting.
+struct BlkPrioSched { int d21[3], d10[3]; };
+constexpr BlkPrioSched kPrioSched[2] = {{{4, 4, 4}, {8, 8, 8}}, {{2, 4, 6}, {6, 8, 10}}};
+constexpr int kPrioShip = 3 + 4 * 1;
 #ifdef GPFQ_BLK_DIAG
 #include "gpfq_blk_diag.hpp"
 #else
 constexpr bool kNoMfmaD = false, kNoFused = false;
 constexpr int kTop3 = kTop3Ship;
 constexpr int kPkAhead = kPkAheadShip;
+constexpr int kPrio = kPrioShip;
 #define STAMP(var) do { } while (0)
 #define STAMP_DO(...)
 #endif
@@ -787,6 +799,9 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
     constexpr bool kBatchTop = kFused && (NL == 4 || G == 8) && NSW == 11;
     // ... and with a symmetric alphabet the first two pair-steps of a slot inside the same asm region (slot_top_sym)
     constexpr bool kTopSym = kBatchTop && SYM;
+    // (eight neuron groups, kPrio's low bit of the form) the slot top's issue priority raised in front of the slot's barrier: see the barrier
+    constexpr int kPrioForm = CL ? (kPrio >> 2) & 3 : kPrio & 3;   // (the cluster form's slices have a setting of their own)
+    constexpr bool kPrioUp = kTopSym && G == 8 && (kPrioForm & 1) != 0;
     // ... and the two LDS-DMA pieces a slot owes besides its record pieces -- the header piece of tile b + 2, the weight piece of block
     // b + 1 -- issued from inside the pair loop instead of between the slot's barrier and its first LDS request, where every wavefront
     // of the CU waits for the same thing and nothing hides their address arithmetic (kLateHdr, kLateW: see the pair loop).  With two
@@ -1175,11 +1190,38 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                 const double2 &dh = dhalf(dd, e / 2);
                 acc[n] = __builtin_amdgcn_mfma_f64_4x4x4f64(u[n][2 * PU * pp + e], (e & 1) ? dh.y : dh.x, acc[n], 0, 0, 0);
             };
+            // (kSched) The level drops of a six-pair wavefront per PAIR-STEP and by the wavefront's age class on its SIMD (kPrioSched): a drop
+            // that every class takes at the same pair-step is a plain s_setprio, one that depends on the class a compare and a branch
+            // inside one asm statement (setprio_if_age).  The four-pair wavefront keeps the schedule by units.
+            constexpr int kSched = (kTopSym && G == 8 && NU == 3) ? (kPrioForm >> 1) & 1 : 0;
+            auto prio_at = [&](int ips) {
+                constexpr BlkPrioSched sc = kPrioSched[kSched];
+                if (sc.d21[0] == sc.d21[1] && sc.d21[1] == sc.d21[2]) {
+                    if (ips == sc.d21[0]) __builtin_amdgcn_s_setprio(1);
+                } else {
+                    if (ips == sc.d21[0]) setprio_if_age<0, 1>(wave);
+                    if (ips == sc.d21[1]) setprio_if_age<1, 1>(wave);
+                    if (ips == sc.d21[2]) setprio_if_age<2, 1>(wave);
+                }
+                if (sc.d10[0] == sc.d10[1] && sc.d10[1] == sc.d10[2]) {
+                    if (ips == sc.d10[0]) __builtin_amdgcn_s_setprio(0);
+                } else {
+                    if (ips == sc.d10[0]) setprio_if_age<0, 0>(wave);
+                    if (ips == sc.d10[1]) setprio_if_age<1, 0>(wave);
+                    if (ips == sc.d10[2]) setprio_if_age<2, 0>(wave);
+                }
+            };
+            (void)prio_at;
 #pragma unroll
             for (int p = 0; p < NU; ++p) {
                 // issue priority falls with progress through the slot (the laggard of a SIMD is served first, see below)
-                {
-                    // (priorities by wavefront AGE instead of progress measured slower: DESIGN_HISTORY.md, "gpfq_blk.hip notes" 6)
+                if constexpr (kSched != 0) {
+                    if (p == 0) __builtin_amdgcn_s_setprio(2);                   // (the drops: prio_at, per pair-step)
+                } else {
+                    // (levels by wavefront AGE ALONE measured slower in round 4, and a C++ branch on the wavefront's number here makes
+                    //  hipcc spill: DESIGN_HISTORY.md, "gpfq_blk.hip notes" 6.  Progress AND age -- the drops per pair-step, staggered by
+                    //  age class through setprio_if_age, which the compiler sees no branch in -- is kSched above: a gain in the classic
+                    //  form, a loss in the cluster slices, which keep this schedule.  profiles/prio/README.md)
                     const int pr = 2 - (3 * p) / NU;
                     if (p == 0 || pr != 2 - (3 * (p - 1)) / NU) {
                         const int v = pr;
@@ -1244,6 +1286,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                         wsrc += (int64_t)B * K.ldt;
                     }
                     __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (kSched != 0) prio_at(ips);
                     float wv[NL], qv[NL];
 #pragma unroll
                     for (int n = 0; n < NL; ++n) { wv[n] = fwq[st][n].x; qv[n] = fwq[st][n].y; }
@@ -1461,6 +1504,9 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
         STAMP(st3);
         dma_wait();                                               // this wavefront's share of the next tile has landed
         STAMP(st4);
+        // (kPrioUp) The level of the next slot's top, set here: the control word's round trip, its test, the branch and the loop's scalar
+        // control then run at one level in all the sweep wavefronts of a SIMD, whichever left the barrier first (the slow path too).
+        if constexpr (kPrioUp) __builtin_amdgcn_s_setprio(2);
         slot_barrier();
         STAMP(st5);
         STAMP_DO(acc_dma += st1 - st0; acc_u += st2 - st1; acc_d += st3 - st2; acc_w += st4 - st3; acc_b += st5 - st4;)
@@ -1487,9 +1533,14 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
         unsigned long long *o = K.stamps + (wave == 0 ? 0 : 8);
         o[0] = acc_dma; o[1] = acc_u; o[2] = acc_d; o[3] = acc_w; o[4] = acc_b; o[5] = (unsigned long long)nslots; o[6] = acc_t;
     }
-    if (K.stamps && blockIdx.x == 0 && lane == 0) K.stamps[32 + wave] = acc_dma + acc_u + acc_d + acc_w;   // slot top -> arrival at the barrier, every sweep wavefront
-
+    if (K.stamps && blockIdx.x == 0 && lane == 0) {
+        K.stamps[32 + wave] = acc_dma + acc_u + acc_d + acc_w;     // slot top -> arrival at the barrier, every sweep wavefront
+        // ... its barrier -> slot top in the words the decision wavefront's five leave free in front of those, and its wait at the barrier
+        // behind them (walks whose row-statistics area holds the 64 words: the probe's)
+        if (K.N * (int64_t)sizeof(RowStats) >= 64 * 8) { K.stamps[21 + wave] = acc_t; K.stamps[48 + wave] = acc_b; }
+    }
     )
+    if constexpr (kPrioUp) __builtin_amdgcn_s_setprio(0);         // (the epilogue at the level the last slot ended on before)
     // ---- epilogue: residual norms through the same partial-sum path, residual vectors straight to memory ----
     if constexpr (G == 8) {
         // The four-group map's sums, bit for bit: a wavefront holds the same samples under both maps, and this lane the pairs of that

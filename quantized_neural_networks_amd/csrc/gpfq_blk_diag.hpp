@@ -1,5 +1,5 @@
 // Diagnostic switches of gpfq_blk.hip -- included ONLY by diagnostic builds (-DGPFQ_BLK_DIAG; never the shipped library):
-//   -DGPFQ_BLK_STAMPS    in-kernel phase stamps (s_memtime) of two sweep wavefronts and the decision wavefront of workgroup 0, accumulated
+//   -DGPFQ_BLK_STAMPS    in-kernel phase stamps (s_memtime) of the sweep wavefronts and the decision wavefront of workgroup 0, accumulated
 //                        per slot and left in the unused row-statistics area behind the call's counter block (tools/pipe_probe.py prints them)
 //   -DGPFQ_BLK_NO_MFMA   phase D (the block dot products) on the vector unit in every shape: the A/B of round 4's matrix form
 //   -DGPFQ_BLK_NO_FUSED  matrix-unit phase D as a phase of its own behind the updates: round 4's first form
@@ -7,6 +7,9 @@
 //                        gpfq_blk.hip is the shipped set): bit 0 the header piece, bit 1 the weight piece; 0 = both at the top of the slot
 //   -DGPFQ_BLK_PK_AHEAD=n  the pair loop of the eight-group shapes (kPkAheadShip in gpfq_blk.hip is the shipped set): bit 0 operand rows two
 //                        pair-steps ahead, bit 1 the next pair-step's float32 products among this one's conversions and additions; 0 = neither
+//   -DGPFQ_BLK_PRIO=n    the issue priorities of the sweep wavefronts in the eight-group shapes (kPrioShip in gpfq_blk.hip is the shipped
+//                        setting): bits 0-1 the classic form, bits 2-3 the cluster slices; of a form's two bits the low one raises the slot
+//                        top's level in front of the slot's barrier, the high one staggers the level drops by the wavefront's age (kPrioSched)
 // The marginal-cost experiments of rounds 4-5 (every matrix / vector / LDS / DMA instruction issued twice, the barrier removed, pair splits
 // from the environment, the flush forced to one side) were removed in round 6; their numbers are in profiles/r04 and profiles/r05, their
 // code in the history (commit 1050215 and before).
@@ -31,6 +34,12 @@ constexpr int kTop3 = kTop3Ship;
 constexpr int kPkAhead = GPFQ_BLK_PK_AHEAD;
 #else
 constexpr int kPkAhead = kPkAheadShip;
+#endif
+
+#ifdef GPFQ_BLK_PRIO
+constexpr int kPrio = GPFQ_BLK_PRIO;
+#else
+constexpr int kPrio = kPrioShip;
 #endif
 
 #ifdef GPFQ_BLK_STAMPS

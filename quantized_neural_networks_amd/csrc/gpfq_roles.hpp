@@ -207,6 +207,22 @@ template <int R> __device__ __forceinline__ int sub_sumi(int x)
 // would also wait for the output stores (vmcnt) every step.  The "memory" clobber keeps LDS accesses on their side.
 __device__ __forceinline__ void slot_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// s_setprio LEVEL in the wavefronts of age class CLS only.  The class of sweep wavefront w of eleven is w >> 2 (wavefronts w, w + 4, w + 8
+// share SIMD w and reach it in this order), read off the wavefront's NUMBER as it sits in a scalar register anyway: class 0 is w <= 3,
+// class 1 bit 2 of w, class 2 bit 3 -- a register for the class itself cost the cluster slices six more scalar spills.  One statement -- a
+// scalar compare, a forward branch over the s_setprio to a label of this expansion's own -- so the compiler sees no control flow: a C++
+// `if` on the wavefront's number inside an unrolled loop splits the loop for hipcc's register allocation, which then spills
+// (DESIGN_HISTORY.md, "gpfq_blk.hip notes" 6).  SCC is overwritten and named in the clobber list.
+template <int CLS, int LEVEL>
+__device__ __forceinline__ void setprio_if_age(int wave_uniform)
+{
+    static_assert(CLS >= 0 && CLS <= 2, "three wavefronts per SIMD");
+    if constexpr (CLS == 0)
+        asm volatile("s_cmp_gt_u32 %0, 3\n\ts_cbranch_scc1 .Lgpfq_prio_%=\n\ts_setprio %1\n.Lgpfq_prio_%=:" :: "s"(wave_uniform), "n"(LEVEL) : "scc");
+    else
+        asm volatile("s_bitcmp0_b32 %0, %2\n\ts_cbranch_scc1 .Lgpfq_prio_%=\n\ts_setprio %1\n.Lgpfq_prio_%=:" :: "s"(wave_uniform), "n"(LEVEL), "n"(CLS + 1) : "scc");
+}
+
 typedef float pk2 __attribute__((ext_vector_type(2)));
 
 // Sample-pair split over the eight sweep wavefronts (pairs per k-lane).  Wavefronts 0 and 4 share their SIMD with the

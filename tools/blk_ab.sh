@@ -10,7 +10,7 @@
 #                                            (the in-kernel stamps): csrc/gpfq_blk_diag.hpp.  (The marginal-cost switches of rounds 4-5 -- a part of
 #                                            the slot issued twice, the barrier removed -- were removed in round 6: profiles/r04, profiles/r05 hold their numbers.)
 mode=$1; shift
-G='old kernel|pipe mode|oracle|cycles per slot|decision wave|slot top|rror'
+G='old kernel|pipe mode|oracle|cycles per slot|decision wave|slot top|barrier wait|barrier is closed|rror'
 probe() { timeout 900 python tools/pipe_probe.py $1 2>&1 | grep -E "$G" | cut -c1-250; }
 case $mode in
   shapes)

@@ -95,12 +95,17 @@ def main():
         if hip.cluster_timeouts(r):
             print("  !! cluster form: an exchange timed out")
         if os.environ.get("GPFQ_DIAG") and mode == 2:
-            st = r["workspace"][64:64 + 48 * 8].view(torch.int64).cpu().numpy()
+            st = r["workspace"][64:64 + 64 * 8].view(torch.int64).cpu().numpy()
             ns = max(int(st[5]), 1)
             for name, o in (("sweep wave 0 (few pairs)", 0), ("sweep wave 7 (most pairs)", 8)):
                 print(f"    {name}: cycles per slot: dma issue {st[o]/ns:.0f}, phase U {st[o+1]/ns:.0f}, phase D+fold {st[o+2]/ns:.0f}, "
                       f"dma wait {st[o+3]/ns:.0f}, barrier {st[o+4]/ns:.0f}, barrier -> next slot {st[o+6]/ns:.0f}  ({ns} slots)")
             print("    slot top -> barrier arrival, sweep wavefronts 0..: " + " ".join(f"{st[32 + w]/ns:.0f}" for w in range(sw)))
+            print("    barrier -> slot top, sweep wavefronts 0..:           " + " ".join(f"{st[21 + w]/ns:.0f}" for w in range(sw)))
+            print("    barrier wait, sweep wavefronts 0..:                  " + " ".join(f"{st[48 + w]/ns:.0f}" for w in range(sw)))
+            waits = [int(st[48 + w]) for w in range(sw)]
+            print(f"    the barrier is closed by sweep wavefront {int(np.argmin(waits))} (the smallest wait, {min(waits)/ns:.0f}; "
+                  f"the decision wavefront's is {st[17]/ns:.0f})")
             print(f"    decision wave: work {st[16]/ns:.0f} (prologue {st[18]/ns:.0f}, chain + certification {st[19]/ns:.0f}), barrier {st[17]/ns:.0f}, barrier -> next slot {st[20]/ns:.0f} cycles per slot")
         tmin, tavg = timed(lambda: hip.quantize_neurons(Xd, Xqd, Wt, alphabet, nrm32=nrm, want_values=False,
                                                         path=hip.GPFQ_PATH_ONCHIP))
