@@ -495,6 +495,39 @@ int gpfq_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const
                                  int64_t ldy, void *stream);
 
 /*
+ * The Conv2D forward pass on the same footing: int8 NHWC images, the kernel [kh][kw][Cin][F] held as the
+ * packed rows of its matrix view [kh*kw*Cin][F] (what deploy.export_packed writes), exact int32 sums on the i8 matrix instruction.
+ * No patch matrix is built.  Opt-in; bit for bit:
+ *
+ * gpfq_packed_conv2d_forward_i8:
+ *   xq [device] i8: image i at xq + i * ldq, NHWC [H][W][Cin]; ldq >= H*W*Cin and a multiple of 16, xq 16-byte aligned;
+ *   scales [device] f32 [n]: one per image -- what gpfq_quantize_rows_i8 makes of the float32 images with B = n and
+ *   N = ldx = H*W*Cin, its row contract carried over to images: a NaN or an Inf anywhere in an image gives it the scale NaN,
+ *   amax < 2^-100 the scale 0, rounding is half to even.
+ *   Geometry: TensorFlow's.  OH = gpfq_patch_out_dim(H, kh, sh, rh, same_padding), OW likewise; under SAME the total pad
+ *   max((OH - 1) sh + (kh - 1) rh + 1 - H, 0) splits floor(total / 2) before (pad_top) and the rest after, likewise pad_left; VALID has
+ *   no pad.  A tap outside the image contributes 0.
+ *   With t = (ky * kw + kx) * Cin + c, the code of weight t of filter f, k = code - zero_code, and w[t][f] as above
+ *   (2 k - (M - 1) for 0 <= k < M, else 0):
+ *   acc[i][oh][ow][f] = sum over t of xq[i][oh * sh + ky * rh - pad_top][ow * sw + kx * rw - pad_left][c] * w[t][f], in int32: exact,
+ *                       since kh*kw*Cin <= GPFQ_PACKED_I8_MAX_N (longer kernels are refused);
+ *   p                 = ((double)acc * (double)scales[i]) * (radii[f] / (double)(M - 1));
+ *   y[i][oh][ow][f]   = (float)p + bias[f]; (float)p without a bias.   y [device] f32 [n][OH][OW][F], contiguous.
+ * So an image that is not finite gives an image of NaN and leaves every other image alone; output image i depends on input image i
+ * and scales[i] alone, not on n; and every call gives the same bits.  Whether Cin is a multiple of 16 decides how the kernel gathers
+ * its operands (16-byte reads, or byte by byte), never what it computes.
+ * n = 0, F = 0 or an empty output (OH or OW = 0) returns GPFQ_OK without a launch.  GPFQ_ERR_INVALID_ARG, before any launch: M < 2 or
+ * M > 64; bits other than gpfq_packed_bits(M, zero_code); H, W, Cin, kh, kw, sh, sw, rh or rw not positive; n or F negative;
+ * kh*kw*Cin > GPFQ_PACKED_I8_MAX_N; ldq not a multiple of 16 or below H*W*Cin; xq or packed not 16-byte aligned; a NULL xq, scales,
+ * packed, radii or y.  GPFQ_ERR_UNSUPPORTED: H*W*Cin or n*OH*OW at or beyond 2^31, a side beyond 2^24.
+ * One launch, asynchronous on `stream`, without atomics, workspace, scratch or host synchronisation.
+ */
+int gpfq_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                  int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
+                                  const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                  const float *bias, int64_t F, float *y, void *stream);
+
+/*
  * Search over the alphabet scalar (a sequence as alphabet_scalar).  K candidate scalars s_0 .. s_{K-1}
  * (1 <= K <= GPFQ_SEARCH_MAX_CANDIDATES, each a finite positive number) are K * C independent columns of one walk with the unit
  * alphabet: candidate k of output channel j is column k * C + j (k-major: candidate k is a contiguous block of C columns).

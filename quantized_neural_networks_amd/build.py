@@ -22,9 +22,9 @@ STAMP = LIB + ".sha"
 OBJDIR = os.path.join(CSRC, "build")
 SOURCES = ["gpfq_capi.hip", "gpfq_onchip.hip", "gpfq_rows.hip", "gpfq_pipe.hip", "gpfq_blk.hip", "gpfq_wide.hip", "gpfq_stream.hip",
            "gpfq_gram.hip", "gpfq_gram_image.hip", "gpfq_gram_conv.hip", "gpfq_gram_s2.hip", "gpfq_gram_mfma.hip", "gpfq_misc.hip",
-           "gpfq_colrad.hip", "gpfq_search.hip", "gpfq_gather.hip", "gpfq_packed.hip", "gpfq_packed_tiled.hip", "gpfq_packed_i8.hip", "gpfq_refine.hip",
+           "gpfq_colrad.hip", "gpfq_search.hip", "gpfq_gather.hip", "gpfq_packed.hip", "gpfq_packed_tiled.hip", "gpfq_packed_i8.hip", "gpfq_packed_conv_i8.hip", "gpfq_refine.hip",
            "gpfq_refine_gram.hip", "gpfq_refine_pairs.hip"]
-HEADERS = ["gpfq_device.hpp", "gpfq_launch.hpp", "gpfq_options.hpp", "gpfq_gram_tile.hpp", "gpfq_roles.hpp", "gpfq_blk_diag.hpp", "gpfq_packed.hpp", os.path.join("..", "..", "include", "gpfq.h")]
+HEADERS = ["gpfq_device.hpp", "gpfq_launch.hpp", "gpfq_options.hpp", "gpfq_gram_tile.hpp", "gpfq_roles.hpp", "gpfq_blk_diag.hpp", "gpfq_packed.hpp", "gpfq_packed_i8.hpp", os.path.join("..", "..", "include", "gpfq.h")]
 
 # -ffp-contract=off: the float32 products/subtraction of the residual update must round
 # separately (reference numerics); float64 accumulations use explicit fma().
@@ -34,11 +34,12 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++
 EXTRA_FLAGS = {"gpfq_pipe.hip": ["-fno-slp-vectorize"], "gpfq_blk.hip": ["-fno-slp-vectorize"]}
 # diagnostic builds (never the shipped library): GPFQ_DIAG="-DGPFQ_BLK_STAMPS" adds in-kernel phase stamps to gpfq_blk.hip,
 # "-DGPFQ_WIDE_STAMPS" to the several-wavefronts-per-neuron kernel of gpfq_wide.hip (printed from the kernel),
-# "-DGPFQ_S2_SKIP=n" leaves a phase of gpfq_gram_s2_kernel out (wrong sums: timing experiments only)
+# "-DGPFQ_S2_SKIP=n" leaves a phase of gpfq_gram_s2_kernel out (wrong sums: timing experiments only),
+# "-DGPFQ_CONV_I8_SKIP=n" one of gpfq_packed_conv_i8_kernel (the gather, the decode or the matrix instruction; the same)
 # A diagnostic build lives beside the shipped library, in csrc/diag_<hash of the flags>/ (round 5): several variants can be built in the
 # CPU container, travel to the GPU box together and be timed there without a compiler run (the box's minutes are the scarce resource);
 # objects of sources that take no diagnostic flag are shared with the shipped build.
-DIAG_SOURCES = ("gpfq_blk.hip", "gpfq_wide.hip", "gpfq_gram_s2.hip", "gpfq_gram_image.hip", "gpfq_misc.hip")
+DIAG_SOURCES = ("gpfq_blk.hip", "gpfq_wide.hip", "gpfq_gram_s2.hip", "gpfq_gram_image.hip", "gpfq_misc.hip", "gpfq_packed_conv_i8.hip")
 if os.environ.get("GPFQ_DIAG"):
     for _src in DIAG_SOURCES:
         EXTRA_FLAGS[_src] = EXTRA_FLAGS.get(_src, []) + os.environ["GPFQ_DIAG"].split()

@@ -911,6 +911,55 @@ int gpfq_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_packed_dense_forward_i8");
 }
 
+int gpfq_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                  int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
+                                  const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                  const float *bias, int64_t F, float *y, void *stream)
+{
+    if (n < 0 || F < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size n=%lld F=%lld", (long long)n, (long long)F);
+    if (H <= 0 || W <= 0 || Cin <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad image shape H=%lld W=%lld Cin=%lld", (long long)H, (long long)W, (long long)Cin);
+    if (kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || rh <= 0 || rw <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad kernel/stride/rate");
+    if (M < 2 || M > 64) return fail(GPFQ_ERR_INVALID_ARG, "the int8 forward pass takes linspace(-1, 1, M) of 2..64 members, got M=%d", M);
+    const int64_t K = (int64_t)kh * kw * Cin;       // (each factor checked below its own bound first: no overflow)
+    if (kh > GPFQ_PACKED_I8_MAX_N || kw > GPFQ_PACKED_I8_MAX_N || Cin > GPFQ_PACKED_I8_MAX_N || (int64_t)kh * kw > GPFQ_PACKED_I8_MAX_N ||
+        K > GPFQ_PACKED_I8_MAX_N)
+        return fail(GPFQ_ERR_INVALID_ARG, "kh*kw*Cin=%d*%d*%lld > GPFQ_PACKED_I8_MAX_N=%d: the int32 sums could overflow", kh, kw,
+                    (long long)Cin, GPFQ_PACKED_I8_MAX_N);
+    int rc = packed_width_ok(bits, zero_code, M);
+    if (rc != GPFQ_OK) return rc;
+    if (bits != gpfq::packed_bits(M, zero_code))
+        return fail(GPFQ_ERR_INVALID_ARG, "bits=%d, but %d members%s pack to %d bits (gpfq_packed_bits)", bits, M,
+                    zero_code ? " and the literal zero" : "", gpfq::packed_bits(M, zero_code));
+    if (ldq % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld must be a multiple of 16", (long long)ldq);
+    const int64_t oh = gpfq_patch_out_dim(H, kh, sh, rh, same_padding), ow = gpfq_patch_out_dim(W, kw, sw, rw, same_padding);
+    if (n == 0 || F == 0 || oh == 0 || ow == 0) return GPFQ_OK;
+    // what the kernel indexes with 32 bits: a place inside an image, a position, a tap's row and column
+    const int64_t limit = 1LL << 24, keh = kh + (int64_t)(kh - 1) * (rh - 1), kew = kw + (int64_t)(kw - 1) * (rw - 1);
+    if (H > limit || W > limit || sh > limit || sw > limit || keh > limit || kew > limit || H * W > 2147483647LL / Cin)
+        return fail(GPFQ_ERR_UNSUPPORTED, "image, stride or dilated kernel too large for one launch");
+    if (oh * ow > 0x7fff0000LL / n) return fail(GPFQ_ERR_UNSUPPORTED, "n*OH*OW output positions: too many for one launch");
+    const int64_t ftiles = (F + 15) / 16, pblocks = (n * oh * ow + 63) / 64;
+    if (ftiles > 2147483647LL / pblocks) return fail(GPFQ_ERR_UNSUPPORTED, "layer too wide for one launch");
+    if (ldq < H * W * Cin) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld < H*W*Cin=%lld", (long long)ldq, (long long)(H * W * Cin));
+    if (!xq || !scales || !packed || !radii || !y) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "packed must be 16-byte aligned");
+    gpfq::ConvI8Shape S;
+    S.H = (int)H; S.W = (int)W; S.Cin = (int)Cin; S.kh = kh; S.kw = kw; S.sh = sh; S.sw = sw; S.rh = rh; S.rw = rw;
+    S.OH = (int)oh; S.OW = (int)ow;
+    S.pad_top = S.pad_left = 0;
+    if (same_padding) {
+        // TF SAME: total = max((out-1)*stride + k_eff - in, 0), before = total / 2 (floor)
+        int64_t th = (oh - 1) * sh + keh - H; if (th < 0) th = 0;
+        int64_t tw = (ow - 1) * sw + kew - W; if (tw < 0) tw = 0;
+        S.pad_top = (int)(th / 2);
+        S.pad_left = (int)(tw / 2);
+    }
+    hipError_t e = gpfq::launch_packed_conv2d_forward_i8(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y,
+                                                         static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_packed_conv2d_forward_i8");
+}
+
 int gpfq_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii, const float *layer_median,
                            const double *scalars, int K, double *radii, float *W_cand, int64_t ldo, int64_t c_lo, int64_t c_hi,
                            void *stream)

@@ -348,6 +348,15 @@ hipError_t launch_quantize_rows_i8(const float *x, int64_t B, int64_t ldx, int64
 hipError_t launch_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
                                           int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
                                           int64_t ldy, hipStream_t stream);
+// gpfq_packed_conv_i8.hip: the Conv2D forward pass of int8 NHWC images with the kernel [kh*kw*Cin][F] held as
+// packed rows, an implicit GEMM on the same instruction (rows: the n*OH*OW output positions; no patch matrix).  The geometry as the
+// entry resolved it: output size and the pads before (TensorFlow's SAME split), every field checked to fit what the kernel indexes with.
+struct ConvI8Shape {
+    int H, W, Cin, kh, kw, sh, sw, rh, rw, pad_top, pad_left, OH, OW;
+};
+hipError_t launch_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
+                                           const uint8_t *packed, int bits, int zero_code, const double *radii, int M, const float *bias,
+                                           int64_t F, float *y, hipStream_t stream);
 // gpfq_search.hip (a sequence as alphabet_scalar): the K candidate scalars travel by value
 constexpr int kSearchMaxK = 16;
 struct SearchScalars {

@@ -32,14 +32,13 @@
 #include "gpfq_device.hpp"
 #include "gpfq_launch.hpp"
 #include "gpfq_packed.hpp"
+#include "gpfq_packed_i8.hpp"
 
 namespace gpfq {
 
 namespace {
 
 constexpr int kQuantThreads = 256;                  // one workgroup per batch row
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 __device__ inline int8_t quantize_one(float v, float inv)
 {
@@ -90,57 +89,6 @@ gpfq_quantize_rows_i8_kernel(const float *__restrict__ x, int64_t ldx, int64_t N
         }
         *reinterpret_cast<unsigned *>(out + t) = word;               // (xq is 16-byte aligned and ldq a multiple of 16)
     }
-}
-
-// What turns codes into weights, one copy in every byte: the first code of a member, the first code past the members, and
-// 128 - (2 zero_code + M - 1), which puts 2 c - (2 zero_code + M - 1) into excess-128 form without a carry between bytes.
-struct DecodeBytes {
-    unsigned lo, hi, bias;
-};
-
-__device__ inline DecodeBytes decode_bytes(int zero_code, int M)
-{
-    const unsigned ones = 0x01010101u;
-    return DecodeBytes{(unsigned)zero_code * ones, (unsigned)(zero_code + M) * ones, (unsigned)(128 - (2 * zero_code + M - 1)) * ones};
-}
-
-// Four codes, one per byte (any value 0..255) -> four int8 weights: 2 (c - zero_code) - (M - 1) where zero_code <= c < zero_code + M,
-// else 0.  No byte borrows from or carries into its neighbour: (c & 127 | 128) - v >= 128 - 65 for v <= 65; a member's 2 c is at
-// most 128 and 2 c + bias lies in [128 - 63, 128 + 63]; a masked byte's 0 + bias in [63, 128].
-__device__ inline unsigned decode4(unsigned codes, const DecodeBytes &D)
-{
-    const unsigned H = 0x80808080u;
-    const unsigned c7 = (codes & 0x7f7f7f7fu) | H;
-    const unsigned member = (c7 - D.lo) & ~(c7 - D.hi) & ~codes & H;             // bit 7 of the bytes that hold a member's code
-    const unsigned mask = (member >> 7) * 0xffu;
-    return ((((codes & mask) << 1) + D.bias) ^ H) & mask;
-}
-
-// B operand i of a 16-byte group: its weights 16 i .. 16 i + 15 in the order of their t, one per byte.
-template <int BITS>
-__device__ inline i32x4 decode_operand(const unsigned (&words)[4], int i, const DecodeBytes &D, unsigned tab)
-{
-    i32x4 b;
-    if constexpr (BITS == 2) {                      // word i; byte d of it holds the four codes of register d
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            const unsigned byte = (words[i] >> (8 * d)) & 0xffu;
-            const unsigned codes = (byte | (byte << 6) | (byte << 12) | (byte << 18)) & 0x03030303u;
-            b[d] = (int)__builtin_amdgcn_perm(tab, tab, codes);      // byte e of the result: byte codes[e] of tab
-        }
-    } else if constexpr (BITS == 4) {               // words 2 i, 2 i + 1; half a word holds the four codes of a register
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            unsigned v = (words[2 * i + (d >> 1)] >> (16 * (d & 1))) & 0xffffu;
-            v = (v | (v << 8)) & 0x00ff00ffu;
-            v = (v | (v << 4)) & 0x0f0f0f0fu;
-            b[d] = (int)decode4(v, D);
-        }
-    } else {
-#pragma unroll
-        for (int d = 0; d < 4; ++d) b[d] = (int)decode4(words[d], D);
-    }
-    return b;
 }
 
 template <int BITS, int MT>

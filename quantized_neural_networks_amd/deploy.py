@@ -3,7 +3,9 @@
 ``quantize_network()`` leaves float32 kernels whose entries take 3, 4, 16 ... values.  This module turns them into codes of 2, 4 or 8
 bits per weight plus one radius per output channel, writes a whole network that way (``export_packed``) and reads it back
 (``load_packed``): Conv2D / DepthwiseConv2D kernels are decoded on the device at load, Dense layers stay packed
-(``keras_shim.PackedDense``) and run from the codes (``gpfq_packed_dense_forward``).
+(``keras_shim.PackedDense``) and run from the codes (``gpfq_packed_dense_forward``).  With ``load_packed(..., packed_conv=True)``
+Conv2D layers stay packed as well (``keras_shim.PackedConv2D``; on int8 activations they run from the codes through
+``gpfq_packed_conv2d_forward_i8``).
 
     pack_kernel(Q, radii, unit_alphabet)   any on-alphabet kernel -> dict(codes, radii, alphabet, bits, zero_code, shape, depthwise)
     unpack_kernel(packed)                  the inverse: the kernel as float32, bit for bit (-0.0 reads back as 0.0)
@@ -138,7 +140,7 @@ def _check_int8_layer(layer, packed):
                          f"(GPFQ_PACKED_I8_MAX_N), the layer has {layer.fan_in}")
 
 
-def load_packed(path, device=None, activations="float32"):
+def load_packed(path, device=None, activations="float32", packed_conv=False):
     """Inverse of export_packed: a keras_shim network on ``device`` (default: the current GPU).  Dense layers that were exported
     packed come back as keras_shim.PackedDense (codes, radii and bias in device memory; the float kernel is never formed unless
     get_weights() or a batch beyond keras_shim.PACKED_TILED_MAX_BATCH asks for it); packed Conv2D / DepthwiseConv2D kernels are
@@ -146,7 +148,12 @@ def load_packed(path, device=None, activations="float32"):
 
     activations="int8": every PackedDense layer rounds its input to int8 per batch row and runs the exact-int32 forward pass at every
     batch size (keras_shim.PackedDense.activations; the float kernel is then formed by get_weights() alone).  Raises ValueError naming
-    the layer whose alphabet is not np.linspace(-1, 1, M) or whose rows are longer than GPFQ_PACKED_I8_MAX_N."""
+    the layer whose alphabet is not np.linspace(-1, 1, M) or whose rows are longer than GPFQ_PACKED_I8_MAX_N.
+
+    packed_conv=True: every Conv2D layer that was exported packed stays packed too (keras_shim.PackedConv2D),
+    with ``activations`` set on it: "int8" rounds every image to int8 with its own scale and runs gpfq_packed_conv2d_forward_i8, and
+    the same two checks apply with kh * kw * Cin as the row length; "float32" decodes at every call.  DepthwiseConv2D kernels are
+    decoded at load either way: their rows are kh * kw long, too short for the matrix instruction to matter."""
     if activations not in keras_shim.PackedDense.ACTIVATIONS:
         raise ValueError(f"activations must be one of {keras_shim.PackedDense.ACTIVATIONS}, got {activations!r}")
     path = str(path)
@@ -159,6 +166,8 @@ def load_packed(path, device=None, activations="float32"):
         arch = json.loads(bytes(z["__arch__"]).decode("utf-8"))
         packed_at = [k for k in range(len(arch["layers"])) if f"p{k}_codes" in z.files]
         classes = {k: keras_shim.PackedDense for k in packed_at if arch["layers"][k]["cls"] == "Dense"}
+        if packed_conv:
+            classes.update({k: keras_shim.PackedConv2D for k in packed_at if arch["layers"][k]["cls"] == "Conv2D"})
         net = keras_shim._network_from_arch(arch, device, classes)
         for k, layer in enumerate(net.layers):
             if k in packed_at:

@@ -70,6 +70,8 @@ SYMBOLS = {
     "gpfq_packed_dense_forward_tiled": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _dp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
     "gpfq_quantize_rows_i8": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "gpfq_packed_dense_forward_i8": (_int, [_vp, _i64, _i64, _vp, _vp, _int, _int, _vp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "gpfq_packed_conv2d_forward_i8": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
+                                             _vp, _int, _int, _vp, _int, _vp, _i64, _vp, _vp]),
     "gpfq_candidate_kernels": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dp, _int, _vp, _vp, _i64, _i64, _i64, _vp]),
     "gpfq_select_candidates_workspace_bytes": (_sz, [_int, _i64]),
     "gpfq_select_candidates": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _dp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
@@ -1480,4 +1482,53 @@ def packed_dense_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, N, bias=
         _check(load().gpfq_packed_dense_forward_i8(qp, B, ldq, scales.data_ptr(), packed.data_ptr(), int(bits), int(zero_code),
                                                    radii.data_ptr(), int(M), bp, int(N), C, yp, ldy, _stream()),
                "gpfq_packed_dense_forward_i8")
+    return out
+
+
+def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias=None, scales=None,
+                             out=None):
+    """y f32 [n][OH][OW][F] of a Conv2D layer whose kernel [kh][kw][Cin][F] = kernel_shape is held as the packed rows of its matrix
+    view [kh*kw*Cin][F], on int8 images and exact int32 sums (gpfq_packed_conv2d_forward_i8; the contract is include/gpfq.h's, bit for
+    bit; TensorFlow's geometry).  x_or_xq: float32 NHWC x [n][H][W][Cin], each image quantized here with its own scale
+    (quantize_rows_i8 on the flattened images), or -- with `scales` f32 [n] -- ready int8 images [n][H][W][Cin], each contiguous, an
+    image pitch (stride(0)) that is a multiple of 16.  M: the size of the layer's unit alphabet, which must be linspace(-1, 1, M).
+    out: an optional contiguous [n][OH][OW][F] tensor.  No sync."""
+    kh, kw, Cin, F = (int(v) for v in kernel_shape)
+    kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
+    if not isinstance(x_or_xq, torch.Tensor) or x_or_xq.dim() != 4 or x_or_xq.shape[3] != Cin:
+        raise GpfqError(f"x must be an NHWC tensor [n][H][W][{Cin}] for a kernel of shape {(kh, kw, Cin, F)}")
+    n, H, W = (int(v) for v in x_or_xq.shape[:3])
+    if min(H, W, Cin, kh, kw, sh, sw, rh, rw) <= 0:
+        raise GpfqError("image sides, kernel sides, strides and dilation must be positive")
+    hwc = H * W * Cin
+    if scales is None:
+        _dev(x_or_xq, torch.float32, "x")
+        xq, scales = quantize_rows_i8(x_or_xq.contiguous().reshape(n, hwc))
+        ldq = xq.shape[1]
+    else:
+        xq = _dev(x_or_xq, torch.int8, "xq")
+        if n > 0 and not xq[0].is_contiguous():
+            raise GpfqError("xq: every image must be contiguous [H][W][Cin]")
+        ldq = xq.stride(0) if n > 1 else (hwc + 15) // 16 * 16     # (one image: the pitch is never used)
+    _dev(scales, torch.float32, "scales")
+    if scales.numel() != n or not scales.is_contiguous():
+        raise GpfqError(f"scales must be a contiguous [{n}] tensor")
+    C = _packed_args(packed, bits, zero_code, radii, kh * kw * Cin)
+    if C != F:
+        raise GpfqError(f"radii has {C} entries, the kernel {F} filters")
+    if bias is not None:
+        _dev(bias, torch.float32, "bias")
+        if bias.numel() != F or not bias.is_contiguous():
+            raise GpfqError(f"bias must be a contiguous [{F}] tensor")
+    OH, OW = patch_out_dim(H, kh, sh, rh, same), patch_out_dim(W, kw, sw, rw, same)
+    if out is None:
+        out = torch.empty((n, OH, OW, F), dtype=torch.float32, device=xq.device)
+    _dev(out, torch.float32, "out")
+    if tuple(out.shape) != (n, OH, OW, F) or not out.is_contiguous():
+        raise GpfqError(f"out {tuple(out.shape)} must be a contiguous [{n}][{OH}][{OW}][{F}] tensor")
+    with torch.cuda.device(xq.device):
+        _check(load().gpfq_packed_conv2d_forward_i8(xq.data_ptr(), n, ldq, scales.data_ptr(), H, W, Cin, kh, kw, sh, sw, rh, rw,
+                                                    1 if same else 0, packed.data_ptr(), int(bits), int(zero_code), radii.data_ptr(),
+                                                    int(M), bias.data_ptr() if bias is not None else None, F, out.data_ptr(), _stream()),
+               "gpfq_packed_conv2d_forward_i8")
     return out

@@ -351,6 +351,9 @@ class Conv2D(Layer):
     def _torch_weight(self):
         return self._weights[0].permute(3, 2, 0, 1), 1                      # OIHW, groups
 
+    def _bias(self):
+        return self._weights[1] if self.use_bias else None
+
     def call(self, x):
         x = x.permute(0, 3, 1, 2)                                           # NHWC -> NCHW (a channels-last view)
         pad = (0, 0)
@@ -362,9 +365,84 @@ class Conv2D(Layer):
             else:
                 x = F.pad(x, (pl, pr, pt, pb))
         w, groups = self._torch_weight()
-        y = F.conv2d(x, w.contiguous(), self._weights[1] if self.use_bias else None, stride=self.strides,
+        y = F.conv2d(x, w.contiguous(), self._bias(), stride=self.strides,
                      padding=pad, dilation=self.dilation_rate, groups=groups)
         return _activation(self.activation)(y.permute(0, 2, 3, 1).contiguous())
+
+
+class PackedConv2D(Conv2D):
+    """A Conv2D layer that holds its quantized kernel as packed low-bit codes (deploy.load_packed(..., packed_conv=True); DESIGN.md
+    section 11b): only the codes, the radii and the bias live in device memory.  ``get_weights()`` decodes on demand; the weights
+    cannot be set.
+
+    ``activations``: "float32" (the default) decodes the kernel at every call and runs the float32 convolution exactly as Conv2D.call
+    does; "int8" rounds every image of x to int8 with its own scale and runs gpfq_packed_conv2d_forward_i8 -- exact int32 sums, the
+    float kernel is never formed (include/gpfq.h has the arithmetic; the layer's alphabet must be linspace(-1, 1, M), which
+    deploy.load_packed checks).  A property of the loaded layer, not of its configuration: config(), clone() and save_model() record
+    the Conv2D it decodes to."""
+
+    ACTIVATIONS = ("float32", "int8")
+
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", dilation_rate=(1, 1),
+                 activation=None, use_bias=True, input_shape=None, name=None):
+        super().__init__(filters, kernel_size, strides, padding, dilation_rate, activation, use_bias, input_shape, name)
+        self.packed = None
+        self.activations = "float32"
+
+    def build(self, input_shape, device, rng):
+        Layer.build(self, input_shape, device, rng)
+        self.kernel_shape = self._kernel_shape(int(input_shape[-1]))
+        self.fan_in = self.kernel_shape[0] * self.kernel_shape[1] * self.kernel_shape[2]
+        self._weights = [torch.zeros(self.filters, device=device)] if self.use_bias else []     # (the bias alone)
+
+    def set_packed(self, packed, bias=None):
+        """packed: a deploy.pack_kernel result for a [kh][kw][Cin][filters] kernel, on this layer's device."""
+        if tuple(packed["shape"]) != tuple(self.kernel_shape) or packed["depthwise"]:
+            raise ValueError(f"packed kernel of shape {tuple(packed['shape'])}, layer {self.name} expects {tuple(self.kernel_shape)}")
+        self.packed = packed
+        if self.use_bias and bias is not None:
+            Layer.set_weights(self, [bias])
+
+    def _kernel(self):
+        from . import deploy
+        if self.packed is None:
+            raise RuntimeError(f"PackedConv2D layer {self.name} holds no packed kernel (deploy.load_packed installs one)")
+        return deploy.unpack_kernel(self.packed)
+
+    def get_weights(self):
+        return [self._kernel().cpu().numpy()] + Layer.get_weights(self)
+
+    def set_weights(self, weights):
+        raise NotImplementedError("a PackedConv2D layer holds codes, not floats: its weights cannot be set")
+
+    def clone(self):
+        """A Conv2D layer of the same configuration (clone_model: fresh float weights, as for every other layer)."""
+        c = Conv2D(**self.config())
+        c.name = self.name
+        return c
+
+    def route(self):
+        """Which way a call runs: "i8" (gpfq_packed_conv2d_forward_i8) or "decode" (decode + the float32 convolution)."""
+        if self.activations not in self.ACTIVATIONS:
+            raise ValueError(f"PackedConv2D layer {self.name}: activations must be one of {self.ACTIVATIONS}, got {self.activations!r}")
+        return "i8" if self.activations == "int8" else "decode"
+
+    def _torch_weight(self):
+        return self._kernel().permute(3, 2, 0, 1), 1                        # OIHW, groups
+
+    def _bias(self):
+        return self._weights[0] if self.use_bias else None
+
+    def call(self, x):
+        if self.route() == "decode":
+            return Conv2D.call(self, x)                                     # (the kernel through _torch_weight, the bias through _bias)
+        from . import hip
+        if self.packed is None:
+            raise RuntimeError(f"PackedConv2D layer {self.name} holds no packed kernel (deploy.load_packed installs one)")
+        p = self.packed
+        y = hip.packed_conv2d_forward_i8(x, p["codes"], p["bits"], p["zero_code"], p["radii"], len(p["alphabet"]), self.kernel_shape,
+                                         self.strides, self.dilation_rate, self.padding, bias=self._bias())
+        return _activation(self.activation)(y)
 
 
 class DepthwiseConv2D(Conv2D):
@@ -835,8 +913,10 @@ def _arch_arrays(model):
     functional = isinstance(model, Model)
     specs = []
     for l in model.layers:
-        # (a PackedDense layer is recorded as the Dense layer it decodes to: save_model writes its float kernel, load_model reads it)
-        spec = dict(cls="Dense" if isinstance(l, PackedDense) else l.__class__.__name__, name=l.name, config=l.config())
+        # (a PackedDense / PackedConv2D layer is recorded as the Dense / Conv2D layer it decodes to: save_model writes its float
+        #  kernel, load_model reads it)
+        cls = "Dense" if isinstance(l, PackedDense) else ("Conv2D" if isinstance(l, PackedConv2D) else l.__class__.__name__)
+        spec = dict(cls=cls, name=l.name, config=l.config())
         if functional:
             inbound = l.inbound_nodes[0].inbound_layers
             spec["inbound"] = [p.name for p in inbound] if isinstance(inbound, (list, tuple)) else [inbound.name]
