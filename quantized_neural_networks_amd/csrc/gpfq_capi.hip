@@ -1032,18 +1032,44 @@ size_t gpfq_refine_workspace_bytes(int64_t N) { return gpfq::refine_workspace_by
 
 int gpfq_refine_neurons_per_workgroup(int64_t m) { return gpfq::refine_neurons_per_workgroup(m); }
 
+// What the three refinement entries refuse alike, each called at the place where the entry makes the check (the order of an entry's
+// refusals is part of its contract: tests/golden/refine_refusals.json).
+// The number of sweeps, then the unit alphabet, which goes into U, the kernels' argument (M and the members; the rest stays zero).
+static int refine_sweeps_and_alphabet(int sweeps, const double *unit_alphabet, int M, gpfq::AlphabetBig *U)
+{
+    if (sweeps < 1) return fail(GPFQ_ERR_INVALID_ARG, "sweeps=%d must be >= 1", sweeps);
+    HostAlphabet H;
+    int rc = make_alphabet(unit_alphabet, M, -1, &H);
+    if (rc != GPFQ_OK) return rc;
+    U->M = M;
+    for (int k = 0; k < M; ++k) U->a[k] = unit_alphabet[k];
+    return GPFQ_OK;
+}
+
+// The pitches of the Keras-layout index and value arrays [N][C].
+static int refine_keras_pitches(int64_t ldi, const float *Q, int64_t ldq, int64_t C)
+{
+    if (ldi < C) return fail(GPFQ_ERR_INVALID_ARG, "index pitch ldi=%lld < C=%lld", (long long)ldi, (long long)C);
+    if (Q && ldq < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldq=%lld < C=%lld", (long long)ldq, (long long)C);
+    return GPFQ_OK;
+}
+
+// Indices are int16 beyond 64 members.
+static int refine_index_alignment(const gpfq::AlphabetBig &U, const void *qidx)
+{
+    if (U.M > 64 && (uintptr_t)qidx % 2 != 0) return fail(GPFQ_ERR_INVALID_ARG, "int16 indices must be 2-byte aligned");
+    return GPFQ_OK;
+}
+
 int gpfq_refine_neurons(const float *X, const float *Xq, int64_t ld, const float *nrm32, const float *W, int64_t ldw,
                         const double *radii, const double *unit_alphabet, int M, int64_t N, int64_t m, int64_t C, int sweeps,
                         void *qidx, int64_t ldi, float *Q, int64_t ldq, double *resid_before, double *resid_after, int32_t *changed,
                         int32_t *sweeps_run, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const gpfq::Options o = gpfq::options_snapshot();     // (no option reaches the refinement kernel yet)
-    (void)o;
     if (N < 0 || m < 0 || C < 0)
         return fail(GPFQ_ERR_INVALID_ARG, "negative size N=%lld m=%lld C=%lld", (long long)N, (long long)m, (long long)C);
-    if (sweeps < 1) return fail(GPFQ_ERR_INVALID_ARG, "sweeps=%d must be >= 1", sweeps);
-    HostAlphabet H;
-    int rc = make_alphabet(unit_alphabet, M, -1, &H);
+    gpfq::RefineArgs a{};
+    int rc = refine_sweeps_and_alphabet(sweeps, unit_alphabet, M, &a.U);
     if (rc != GPFQ_OK) return rc;
     if (m > GPFQ_REFINE_MAX_M)
         return fail(GPFQ_ERR_UNSUPPORTED, "refinement needs m <= GPFQ_REFINE_MAX_M=%d (got %lld)", GPFQ_REFINE_MAX_M, (long long)m);
@@ -1055,17 +1081,12 @@ int gpfq_refine_neurons(const float *X, const float *Xq, int64_t ld, const float
         if (m > 0 && (!X || !Xq)) return fail(GPFQ_ERR_INVALID_ARG, "X/Xq is NULL");
         if (ld < m) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ld=%lld < m=%lld", (long long)ld, (long long)m);
         if (ldw < C) return fail(GPFQ_ERR_INVALID_ARG, "weight pitch ldw=%lld < C=%lld", (long long)ldw, (long long)C);
-        if (ldi < C) return fail(GPFQ_ERR_INVALID_ARG, "index pitch ldi=%lld < C=%lld", (long long)ldi, (long long)C);
-        if (Q && ldq < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldq=%lld < C=%lld", (long long)ldq, (long long)C);
-        if (H.is_big && (uintptr_t)qidx % 2 != 0) return fail(GPFQ_ERR_INVALID_ARG, "int16 indices must be 2-byte aligned");
+        if ((rc = refine_keras_pitches(ldi, Q, ldq, C)) != GPFQ_OK || (rc = refine_index_alignment(a.U, qidx)) != GPFQ_OK) return rc;
         const size_t need = gpfq::refine_workspace_bytes(N);
         if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 8 != 0)
             return fail(GPFQ_ERR_WORKSPACE, "refinement needs %zu aligned workspace bytes, got %zu", need, workspace ? workspace_bytes : (size_t)0);
     }
-    gpfq::RefineArgs a{};
     a.X = X; a.Xq = Xq; a.ld = ld; a.nrm32 = nrm32; a.W = W; a.ldw = ldw; a.radii = radii;
-    a.U.M = M;
-    for (int k = 0; k < M; ++k) a.U.a[k] = unit_alphabet[k];
     a.N = N; a.m = m; a.C = C; a.sweeps = sweeps; a.qidx = qidx; a.ldi = ldi; a.Q = Q; a.ldq = ldq;
     a.resid_before = resid_before; a.resid_after = resid_after; a.changed = changed; a.sweeps_run = sweeps_run;
     a.workspace = workspace;
@@ -1080,9 +1101,8 @@ int gpfq_refine_gram_neurons(const double *G, int64_t ldg, double *H, int64_t ld
                              int64_t ldq, int32_t *changed, int32_t *sweeps_run, double *gain, void *stream)
 {
     if (N < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size N=%lld C=%lld", (long long)N, (long long)C);
-    if (sweeps < 1) return fail(GPFQ_ERR_INVALID_ARG, "sweeps=%d must be >= 1", sweeps);
-    HostAlphabet H_;
-    int rc = make_alphabet(unit_alphabet, M, -1, &H_);
+    gpfq::RefineGramArgs a{};
+    int rc = refine_sweeps_and_alphabet(sweeps, unit_alphabet, M, &a.U);
     if (rc != GPFQ_OK) return rc;
     if (N > GPFQ_REFINE_GRAM_MAX_N)
         return fail(GPFQ_ERR_UNSUPPORTED, "refinement on the Gram matrix needs N <= GPFQ_REFINE_GRAM_MAX_N=%d (got %lld)",
@@ -1094,15 +1114,11 @@ int gpfq_refine_gram_neurons(const double *G, int64_t ldg, double *H, int64_t ld
         if (!G || !H || !nrm32 || !qidx) return fail(GPFQ_ERR_INVALID_ARG, "G/H/nrm32/qidx is NULL");
         if (ldg < N) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldg=%lld < N=%lld", (long long)ldg, (long long)N);
         if (ldh < N) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldh=%lld < N=%lld", (long long)ldh, (long long)N);
-        if (ldi < C) return fail(GPFQ_ERR_INVALID_ARG, "index pitch ldi=%lld < C=%lld", (long long)ldi, (long long)C);
-        if (Q && ldq < C) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldq=%lld < C=%lld", (long long)ldq, (long long)C);
+        if ((rc = refine_keras_pitches(ldi, Q, ldq, C)) != GPFQ_OK) return rc;
         if ((uintptr_t)G % 8 != 0 || (uintptr_t)H % 8 != 0) return fail(GPFQ_ERR_INVALID_ARG, "G and H must be 8-byte aligned");
-        if (H_.is_big && (uintptr_t)qidx % 2 != 0) return fail(GPFQ_ERR_INVALID_ARG, "int16 indices must be 2-byte aligned");
+        if ((rc = refine_index_alignment(a.U, qidx)) != GPFQ_OK) return rc;
     }
-    gpfq::RefineGramArgs a{};
     a.G = G; a.ldg = ldg; a.H = H; a.ldh = ldh; a.nrm32 = nrm32; a.radii = radii;
-    a.U.M = M;
-    for (int k = 0; k < M; ++k) a.U.a[k] = unit_alphabet[k];
     a.N = N; a.C = C; a.sweeps = sweeps; a.qidx = qidx; a.ldi = ldi; a.Q = Q; a.ldq = ldq;
     a.changed = changed; a.sweeps_run = sweeps_run; a.gain = gain;
     hipError_t e = gpfq::launch_refine_gram(a, static_cast<hipStream_t>(stream));
@@ -1117,9 +1133,8 @@ int gpfq_refine_conv_pairs(const double *records, const double *records_swapped,
 {
     if (nch < 0 || F < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size nch=%lld F=%lld", (long long)nch, (long long)F);
     if (K < 1) return fail(GPFQ_ERR_INVALID_ARG, "K=%d must be >= 1", K);
-    if (sweeps < 1) return fail(GPFQ_ERR_INVALID_ARG, "sweeps=%d must be >= 1", sweeps);
-    HostAlphabet H_;
-    int rc = make_alphabet(unit_alphabet, M, -1, &H_);
+    gpfq::RefinePairsArgs a{};
+    int rc = refine_sweeps_and_alphabet(sweeps, unit_alphabet, M, &a.U);
     if (rc != GPFQ_OK) return rc;
     if (K > GPFQ_REFINE_PAIRS_MAX_K)
         return fail(GPFQ_ERR_UNSUPPORTED, "refinement per (channel, filter) pair needs kh*kw <= GPFQ_REFINE_PAIRS_MAX_K=%d (got %d)",
@@ -1129,11 +1144,8 @@ int gpfq_refine_conv_pairs(const double *records, const double *records_swapped,
     if (!records || !Wt || !radii || !qidx) return fail(GPFQ_ERR_INVALID_ARG, "records/Wt/radii/qidx is NULL");
     if ((uintptr_t)records % 8 != 0 || (uintptr_t)records_swapped % 8 != 0 || (uintptr_t)radii % 8 != 0)
         return fail(GPFQ_ERR_INVALID_ARG, "records and radii must be 8-byte aligned");
-    if (H_.is_big && (uintptr_t)qidx % 2 != 0) return fail(GPFQ_ERR_INVALID_ARG, "int16 indices must be 2-byte aligned");
-    gpfq::RefinePairsArgs a{};
+    if ((rc = refine_index_alignment(a.U, qidx)) != GPFQ_OK) return rc;
     a.records = records; a.records_swapped = records_swapped; a.K = K; a.Wt = Wt; a.radii = radii;
-    a.U.M = M;
-    for (int k = 0; k < M; ++k) a.U.a[k] = unit_alphabet[k];
     a.nch = nch; a.F = F; a.sweeps = sweeps; a.qidx = qidx; a.Qt = Qt;
     a.changed = changed; a.sweeps_run = sweeps_run; a.gain = gain;
     hipError_t e = gpfq::launch_refine_pairs(a, static_cast<hipStream_t>(stream));

@@ -24,23 +24,13 @@
 
 #include "gpfq_device.hpp"
 #include "gpfq_launch.hpp"
+#include "gpfq_refine.hpp"
 
 namespace gpfq {
 
 namespace {
 
-constexpr int kCap = 256;               // alphabet members (GPFQ_MAX_ALPHABET)
-
-__device__ __forceinline__ int load_index(const void *qidx, int64_t off, int idx16)
-{
-    return idx16 ? (int)static_cast<const int16_t *>(qidx)[off] : (int)static_cast<const int8_t *>(qidx)[off];
-}
-
-__device__ __forceinline__ void store_index(void *qidx, int64_t off, int idx16, int k)
-{
-    if (idx16) static_cast<int16_t *>(qidx)[off] = (int16_t)k;
-    else static_cast<int8_t *>(qidx)[off] = (int8_t)k;
-}
+using namespace refine;
 
 // n2[t] = sum_i Xq_t[i]^2 in float64: one workgroup per row, thread x the elements x, x + 256, ... ascending, wave_sum, the four
 // wavefronts ascending.
@@ -84,6 +74,11 @@ gpfq_refine_kernel(const float *__restrict__ X, const float *__restrict__ Xq, in
     const int M = U.M;
     const int nn = (int)(C - j0 < NPW ? C - j0 : NPW);          // neurons of this workgroup (>= 1)
 
+    // Three places of this kernel stay written out where gpfq_refine.hpp has a function: the fill below is
+    // refine::fill_alphabet_tables<NPW, T>, the start phase's value lookup refine::index_value, the decider's step
+    // refine::decide_step with gap[tid] -- and they must say what those say.  Inlined, each of them moves this kernel's blocks and
+    // waits: the lookup cost the start phase 8 - 27 % and the step 3 % per sweep on cfg2 (profiles/refine_family_refactor_ab.txt);
+    // as written the unit compiles to the assembly it had before the header existed.
     for (int e = tid; e < NPW * M; e += T) {
         const int n = e / M, k = e - n * M;
         alpha[n][k] = n < nn ? radii[j0 + n] * U.a[k] : 0.0;
@@ -132,7 +127,7 @@ gpfq_refine_kernel(const float *__restrict__ X, const float *__restrict__ Xq, in
         for (int e = 0; e < EPT; ++e) { cw[e] = xw[e]; cq[e] = xq[e]; }
         if (Q && tid < nn) {
             const int k = load_index(qidx, t * ldi + j0 + tid, idx16);
-            Q[t * ldq + j0 + tid] = (k >= 0 && k < M) ? (float)alpha[tid][k] : 0.f;
+            Q[t * ldq + j0 + tid] = (float)index_value(k, M, [&](int i) { return alpha[tid][i]; });
         }
         fetch_row(X, t + 1, xw);
         fetch_row(Xq, t + 1, xq);
@@ -144,7 +139,8 @@ gpfq_refine_kernel(const float *__restrict__ X, const float *__restrict__ Xq, in
             const double wv = (double)w_next[n];
             fetch_coeffs(t + 1, n);
             if (n < nn) {
-                const double av = (k >= 0 && k < M) ? alpha[n][k] : 0.0;
+                // (not index_value: through it the waits for the rows fetched ahead come earlier, 13 more s_waitcnt per instantiation)
+                const double av = on_alphabet(k, M) ? alpha[n][k] : 0.0;
 #pragma unroll
                 for (int e = 0; e < EPT; ++e) u[n][e] += wv * (double)cw[e] - av * (double)cq[e];
             }
@@ -209,7 +205,8 @@ gpfq_refine_kernel(const float *__restrict__ X, const float *__restrict__ Xq, in
             __syncthreads();
             if (decider) {
                 double delta = 0.0;
-                if (live && kc >= 0 && kc < M && !((double)nr < 1e-16)) {
+                // (refine::decide_step with the gap table, written out: see the top of the kernel)
+                if (live && kc >= 0 && kc < M && !((double)nr < kDeadRowNorm)) {
                     double p = 0.0;
                     for (int w = 0; w < NW; ++w) p += part[tid][w];
                     const double a_cur = alpha[tid][kc];

@@ -6,7 +6,7 @@
 // Work decomposition: one workgroup of NW wavefronts owns ONE neuron for the whole call.  Thread x holds the elements
 // {x + T e, e < EPT} (T = 64 NW) of the neuron's h in registers from the first load to the last store.  The walk goes in blocks of
 // 64 steps; block b (t = 64 b + lane) is held -- register b / NW -- by wavefront b % NW, which walks it alone:
-//   every lane forms its own decision from its current h_t (v = a_cur + h_t / G[t][t]; the quick test and the scan of gpfq_refine.hip);
+//   every lane forms its own decision from its current h_t (v = a_cur + h_t / G[t][t]; refine::decide_step, quick test included);
 //   a ballot finds the first lane that accepts.  The lanes before it are final: nothing ahead of them in the block changed.  The
 //   wavefront reads the 64 elements G[t][64 b ...] of that row, updates the whole block (lane t included) and the later lanes decide
 //   again: the serial chain of a block is its number of accepted steps plus one, not 64.
@@ -24,23 +24,13 @@
 
 #include "gpfq_device.hpp"
 #include "gpfq_launch.hpp"
+#include "gpfq_refine.hpp"
 
 namespace gpfq {
 
 namespace {
 
-constexpr int kCap = 256;               // alphabet members (GPFQ_MAX_ALPHABET)
-
-__device__ __forceinline__ int load_index(const void *qidx, int64_t off, int idx16)
-{
-    return idx16 ? (int)static_cast<const int16_t *>(qidx)[off] : (int)static_cast<const int8_t *>(qidx)[off];
-}
-
-__device__ __forceinline__ void store_index(void *qidx, int64_t off, int idx16, int k)
-{
-    if (idx16) static_cast<int16_t *>(qidx)[off] = (int16_t)k;
-    else static_cast<int8_t *>(qidx)[off] = (int8_t)k;
-}
+using namespace refine;
 
 template <int NW, int EPT>
 __global__ void __launch_bounds__(NW * 64)
@@ -62,21 +52,8 @@ gpfq_refine_gram_kernel(const double *__restrict__ G, int64_t ldg, double *H, in
     const int M = U.M;
     const int nblocks = (N + 63) >> 6;
 
-    {
-        const double r = radii[j];
-        for (int k = tid; k < M; k += T) alpha[k] = r * U.a[k];
-    }
-    __syncthreads();
-    for (int k = tid; k < M; k += T) {
-        const double a = alpha[k];
-        double g = __longlong_as_double(0x7ff0000000000000LL);
-        for (int k2 = 0; k2 < M; ++k2) {
-            const double d = fabs(alpha[k2] - a);
-            if (d > 0.0 && d < g) g = d;
-        }
-        gap[k] = g;
-    }
-    __syncthreads();
+    fill_alphabet_tables<1, T>(&alpha, &gap, radii, j, 1, U, tid);
+    const auto member = [&](int k) { return alpha[k]; };
 
     // ---- start: h of the neuron into registers; Q of the walk's indices ----
     double h[EPT];
@@ -88,7 +65,7 @@ gpfq_refine_gram_kernel(const double *__restrict__ G, int64_t ldg, double *H, in
             h[e] = H[j * ldh + s];
             if (Q) {
                 const int k = load_index(qidx, (int64_t)s * ldi + j, idx16);
-                Q[(int64_t)s * ldq + j] = (k >= 0 && k < M) ? (float)alpha[k] : 0.f;
+                Q[(int64_t)s * ldq + j] = (float)index_value(k, M, member);
             }
         }
     }
@@ -105,7 +82,7 @@ gpfq_refine_gram_kernel(const double *__restrict__ G, int64_t ldg, double *H, in
             const int k = load_index(qidx, (int64_t)t * ldi + j, idx16);
             const float nr = nrm32[t];
             diag_next = G[(int64_t)t * ldg + t];
-            k_next = (k >= 0 && k < M && !((double)nr < 1e-16)) ? k : -1;
+            k_next = (on_alphabet(k, M) && !dead_row(nr)) ? k : -1;
         }
     };
     fetch_block(wave);
@@ -132,41 +109,21 @@ gpfq_refine_gram_kernel(const double *__restrict__ G, int64_t ldg, double *H, in
                     if (e == e_own) hl = h[e];
                 int first = 0, count = 0;               // lanes before `first` are final
                 for (;;) {
-                    int kb = kc;
-                    double delta = 0.0, gt = 0.0;
-                    if (kc >= 0 && lane >= first) {
-                        const double a_cur = alpha[kc];
-                        const double v = a_cur + hl / diag;
-                        const double d_cur = fabs(a_cur - v);
-                        if (!(d_cur < 0.49 * gap[kc])) {
-                            int kmin = 0;
-                            double db = fabs(alpha[0] - v);
-                            for (int k = 1; k < M; ++k) {
-                                const double d = fabs(alpha[k] - v);
-                                if (d < db) { db = d; kmin = k; }
-                            }
-                            if (db < d_cur) {
-                                const double a_new = alpha[kmin];
-                                const double x = a_cur - v, y = a_new - v;
-                                kb = kmin;
-                                delta = a_new - a_cur;
-                                gt = diag * (x * x - y * y);
-                            }
-                        }
-                    }
-                    const unsigned long long accept = __ballot(kb != kc);
+                    Step st{false, kc, 0.0, 0.0};
+                    if (kc >= 0 && lane >= first) st = decide_step<true>(kc, hl, diag, M, member, gap);
+                    const unsigned long long accept = __ballot(st.accepted);
                     if (accept == 0ull) break;
                     const int f = __builtin_ctzll(accept);
                     const int tf = t0 + f;
                     if (lane == f) {
-                        kc = kb;
-                        store_index(qidx, (int64_t)tf * ldi + j, idx16, kb);
-                        if (Q) Q[(int64_t)tf * ldq + j] = (float)alpha[kb];
-                        delta_s[turn][count] = delta;
-                        gterm_s[turn][count] = gt;
+                        kc = st.k;
+                        store_index(qidx, (int64_t)tf * ldi + j, idx16, st.k);
+                        if (Q) Q[(int64_t)tf * ldq + j] = (float)alpha[st.k];
+                        delta_s[turn][count] = st.delta;
+                        gterm_s[turn][count] = st.gain;
                         t_s[turn][count] = tf;
                     }
-                    const double d = __shfl(delta, f);
+                    const double d = __shfl(st.delta, f);
                     if (in_rows) hl -= d * G[(int64_t)tf * ldg + t];
                     first = f + 1;
                     ++count;

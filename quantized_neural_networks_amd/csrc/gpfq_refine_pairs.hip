@@ -17,6 +17,7 @@
 
 #include "gpfq_device.hpp"
 #include "gpfq_launch.hpp"
+#include "gpfq_refine.hpp"
 
 // (`#pragma unroll` on a loop over K unrolls the register forms in full; the LDS-column form's K is a run-time value, where the same
 //  pragma can only report that it did nothing)
@@ -26,8 +27,9 @@ namespace gpfq {
 
 namespace {
 
-constexpr int kCap = 256;              // alphabet members (GPFQ_MAX_ALPHABET)
-constexpr int kLanes = 64;              // pairs per workgroup: one wavefront
+using namespace refine;
+
+constexpr int kLanes = 64;             // pairs per workgroup: one wavefront
 
 // LDS of one workgroup: G [K][K], C [K][K], unit [kCap] (f64), dead [kRefinePairsMaxK] (i32), then -- KT == 0 only -- the columns
 // h [K][kLanes] (f64) and k [K][kLanes] (i16)
@@ -73,7 +75,7 @@ gpfq_refine_pairs_kernel(const double *__restrict__ records, const double *__res
         for (int k = lane; k < M; k += kLanes) us[k] = U.a[k];
         for (int t = lane; t < K; t += kLanes) {
             const float nr = (float)sqrt(rec[((int64_t)t * K + t) * 2 + 1]);
-            dead[t] = (double)nr < 1e-16 ? 1 : 0;
+            dead[t] = dead_row(nr) ? 1 : 0;
         }
     }
     __syncthreads();
@@ -92,13 +94,11 @@ gpfq_refine_pairs_kernel(const double *__restrict__ records, const double *__res
 
     // ---- start: h_t = sum over s, in order, of + C[t][s] w_s, - G[t][s] a_{k_s} (s outside, t inside: the order of every h_t's
     // operations is that of the semantics, and w_s, a_{k_s} are formed once) ----
-    auto load_index = [&](int s) -> int {
-        return idx16 ? (int)static_cast<const int16_t *>(qidx)[base + s] : (int)static_cast<const int8_t *>(qidx)[base + s];
-    };
+    const auto member = [&](int k) { return r * us[k]; };          // a_k, formed where it is used
 #pragma unroll
     for (int t = 0; t < K; ++t) {
         h_set(t, 0.0);
-        k_set(t, valid ? load_index(t) : -1);
+        k_set(t, valid ? load_index(qidx, base + t, idx16) : -1);
     }
     if (valid) {
         // (s is a rolled loop: unrolled, the K * K pairs of LDS reads are hoisted into more registers than there are; the index of
@@ -106,8 +106,7 @@ gpfq_refine_pairs_kernel(const double *__restrict__ records, const double *__res
 #pragma unroll 1
         for (int s = 0; s < K; ++s) {
             const double ws = (double)Wt[base + s];
-            const int ks = load_index(s);
-            const double as = (ks >= 0 && ks < M) ? r * us[ks] : 0.0;
+            const double as = index_value(load_index(qidx, base + s, idx16), M, member);
 #pragma unroll
             for (int t = 0; t < K; ++t) {
                 double h = h_get(t);
@@ -129,25 +128,13 @@ gpfq_refine_pairs_kernel(const double *__restrict__ records, const double *__res
 #pragma unroll
         for (int t = 0; t < K; ++t) {
             const int kc = k_get(t);
-            if (live && !dead[t] && kc >= 0 && kc < M) {
-                const double gtt = Gs[t * K + t];
-                const double a_cur = r * us[kc];
-                const double v = a_cur + h_get(t) / gtt;
-                const double d_cur = fabs(a_cur - v);
-                int kmin = 0;
-                double db = fabs(r * us[0] - v);
-                for (int k = 1; k < M; ++k) {
-                    const double d = fabs(r * us[k] - v);
-                    if (d < db) { db = d; kmin = k; }
-                }
-                if (db < d_cur) {
-                    const double a_new = r * us[kmin];
-                    const double x = a_cur - v, y = a_new - v;
-                    gain_acc = gain_acc + gtt * (x * x - y * y);
-                    const double delta = a_new - a_cur;
+            if (live && !dead[t] && on_alphabet(kc, M)) {
+                const Step st = decide_step<true>(kc, h_get(t), Gs[t * K + t], M, member, nullptr);     // (no quick test here)
+                if (st.accepted) {
+                    gain_acc = gain_acc + st.gain;
 #pragma unroll
-                    for (int s = 0; s < K; ++s) h_set(s, h_get(s) - delta * Gs[s * K + t]);
-                    k_set(t, kmin);
+                    for (int s = 0; s < K; ++s) h_set(s, h_get(s) - st.delta * Gs[s * K + t]);
+                    k_set(t, st.k);
                     ++moved;
                 }
             }
@@ -163,9 +150,8 @@ gpfq_refine_pairs_kernel(const double *__restrict__ records, const double *__res
 #pragma unroll
     for (int t = 0; t < K; ++t) {
         const int k = k_get(t);
-        if (idx16) static_cast<int16_t *>(qidx)[base + t] = (int16_t)k;
-        else static_cast<int8_t *>(qidx)[base + t] = (int8_t)k;
-        if (Qt) Qt[base + t] = (k >= 0 && k < M) ? (float)(r * us[k]) : 0.f;
+        store_index(qidx, base + t, idx16, k);
+        if (Qt) Qt[base + t] = (float)index_value(k, M, member);
     }
     if (changed) changed[pair] = n_changed;
     if (sweeps_run) sweeps_run[pair] = n_sweeps;

@@ -915,6 +915,36 @@ def refine_neurons_per_workgroup(m):
     return int(load().gpfq_refine_neurons_per_workgroup(int(m)))
 
 
+def _refine_counts(shape, dev, gain=False):
+    """The per-neuron (per-pair) result tensors of a refinement call: changed, sweeps i32 and, with gain, gain f64."""
+    res = dict(changed=torch.empty(shape, dtype=torch.int32, device=dev), sweeps=torch.empty(shape, dtype=torch.int32, device=dev))
+    if gain:
+        res["gain"] = torch.empty(shape, dtype=torch.float64, device=dev)
+    return res
+
+
+def _refine_io(dev, idx, radii, nrm32, N, C, want_values, inplace, out, gain=False):
+    """What refine_neurons and refine_gram_neurons share: radii [C] and nrm32 [N] checked, the indices to refine (a contiguous copy
+    unless inplace), Q (out, a new [N][C] tensor, or None) and the counts.  Returns (dict(Q, idx, changed, sweeps[, gain]), pointer
+    and pitch of idx, pointer and pitch of Q)."""
+    if radii.numel() != C or not radii.is_contiguous():
+        raise GpfqError(f"radii must be a contiguous [{C}] tensor")
+    _dev(nrm32, torch.float32, "nrm32")
+    if nrm32.numel() != N or not nrm32.is_contiguous():
+        raise GpfqError(f"nrm32 must be a contiguous [{N}] tensor")
+    if not inplace:
+        idx = idx.clone(memory_format=torch.contiguous_format)
+    pi, _, _, ldi = _rows(idx, "idx")
+    Q = out if out is not None else (torch.empty((N, C), dtype=torch.float32, device=dev) if want_values else None)
+    pQ, ldQ = (None, 0)
+    if Q is not None:
+        _dev(Q, torch.float32, "out")
+        pQ, Nq_, Cq_, ldQ = _rows(Q, "out")
+        if (Nq_, Cq_) != (N, C):
+            raise GpfqError(f"out must be [{N}][{C}]")
+    return dict(Q=Q, idx=idx, **_refine_counts(C, dev, gain)), pi, ldi, pQ, ldQ
+
+
 def refine_neurons(X, Xq, W, idx, radii, unit_alphabet, sweeps, nrm32=None, want_values=True, inplace=False, out=None):
     """Refinement sweeps over a walk's result (gpfq_refine_neurons).  X, Xq f32 [N][m] (rows of any pitch),
     W f32 [N][C] the ORIGINAL kernel (Keras layout, rows of any pitch), idx [N][C] the walk's Keras-layout indices (int8; int16 beyond
@@ -934,28 +964,12 @@ def refine_neurons(X, Xq, W, idx, radii, unit_alphabet, sweeps, nrm32=None, want
     pw, Nw, C, ldw = _rows(W, "W")
     if Nw != N or tuple(idx.shape) != (N, C):
         raise GpfqError(f"W {tuple(W.shape)} / idx {tuple(idx.shape)} do not match the {N} rows of X")
-    if radii.numel() != C or not radii.is_contiguous():
-        raise GpfqError(f"radii must be a contiguous [{C}] tensor")
     sweeps = int(sweeps)
     dev = X.device
-    if not inplace:
-        idx = idx.clone(memory_format=torch.contiguous_format)
-    pi, _, _, ldi = _rows(idx, "idx")
     if nrm32 is None:
         nrm32 = row_norms(Xq)
-    _dev(nrm32, torch.float32, "nrm32")
-    if nrm32.numel() != N or not nrm32.is_contiguous():
-        raise GpfqError(f"nrm32 must be a contiguous [{N}] tensor")
-    Q = out if out is not None else (torch.empty((N, C), dtype=torch.float32, device=dev) if want_values else None)
-    pQ, ldQ = (None, 0)
-    if Q is not None:
-        _dev(Q, torch.float32, "out")
-        pQ, Nq_, Cq_, ldQ = _rows(Q, "out")
-        if (Nq_, Cq_) != (N, C):
-            raise GpfqError(f"out must be [{N}][{C}]")
-    res = dict(Q=Q, idx=idx, resid_before=torch.empty(C, dtype=torch.float64, device=dev),
-               resid_after=torch.empty(C, dtype=torch.float64, device=dev), changed=torch.empty(C, dtype=torch.int32, device=dev),
-               sweeps=torch.empty(C, dtype=torch.int32, device=dev))
+    res, pi, ldi, pQ, ldQ = _refine_io(dev, idx, radii, nrm32, N, C, want_values, inplace, out)
+    res.update(resid_before=torch.empty(C, dtype=torch.float64, device=dev), resid_after=torch.empty(C, dtype=torch.float64, device=dev))
     lib = load()
     nbytes = lib.gpfq_refine_workspace_bytes(N)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
@@ -982,25 +996,10 @@ def refine_gram_neurons(G, H, nrm32, idx, radii, unit_alphabet, sweeps, want_val
     ph, C, Nh, ldh = _rows(H, "H")
     if Nh != N or tuple(idx.shape) != (N, C):
         raise GpfqError(f"H {tuple(H.shape)} / idx {tuple(idx.shape)} do not match the {N} rows of G")
-    if radii.numel() != C or not radii.is_contiguous():
-        raise GpfqError(f"radii must be a contiguous [{C}] tensor")
-    if nrm32.numel() != N or not nrm32.is_contiguous():
-        raise GpfqError(f"nrm32 must be a contiguous [{N}] tensor")
     sweeps = int(sweeps)
-    dev = G.device
-    if not inplace:
-        idx = idx.clone(memory_format=torch.contiguous_format)
-    pi, _, _, ldi = _rows(idx, "idx")
-    Q = out if out is not None else (torch.empty((N, C), dtype=torch.float32, device=dev) if want_values else None)
-    pQ, ldQ = (None, 0)
-    if Q is not None:
-        _dev(Q, torch.float32, "out")
-        pQ, Nq_, Cq_, ldQ = _rows(Q, "out")
-        if (Nq_, Cq_) != (N, C):
-            raise GpfqError(f"out must be [{N}][{C}]")
-    res = dict(Q=Q, idx=idx, H=H, changed=torch.empty(C, dtype=torch.int32, device=dev), sweeps=torch.empty(C, dtype=torch.int32, device=dev),
-               gain=torch.empty(C, dtype=torch.float64, device=dev))
-    with torch.cuda.device(dev):
+    res, pi, ldi, pQ, ldQ = _refine_io(G.device, idx, radii, nrm32, N, C, want_values, inplace, out, gain=True)
+    res["H"] = H
+    with torch.cuda.device(G.device):
         _check(load().gpfq_refine_gram_neurons(pg, ldg, ph, ldh, nrm32.data_ptr(), radii.data_ptr(), arr, M, N, C, sweeps, pi, ldi, pQ, ldQ,
                                                res["changed"].data_ptr(), res["sweeps"].data_ptr(), res["gain"].data_ptr(), _stream()),
                "gpfq_refine_gram_neurons")
@@ -1026,8 +1025,7 @@ def refine_conv_pairs(records, records_swapped, K, Wt, radii, unit_alphabet, swe
         raise GpfqError("refine_conv_pairs: shape mismatch")
     dev = Wt.device
     Q = torch.empty((nch, F, K), dtype=torch.float32, device=dev) if want_values else None
-    res = dict(Q=Q, idx=idx, changed=torch.empty((nch, F), dtype=torch.int32, device=dev),
-               sweeps=torch.empty((nch, F), dtype=torch.int32, device=dev), gain=torch.empty((nch, F), dtype=torch.float64, device=dev))
+    res = dict(Q=Q, idx=idx, **_refine_counts((nch, F), dev, gain=True))
     with torch.cuda.device(dev):
         _check(load().gpfq_refine_conv_pairs(records.data_ptr(), records_swapped.data_ptr() if records_swapped is not None else None, K,
                                              Wt.data_ptr(), radii.data_ptr(), arr, M, nch, F, sweeps, idx.data_ptr(),

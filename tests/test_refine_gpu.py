@@ -18,16 +18,12 @@ import torch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-DEV = torch.device("cuda", 0)
 
+import _refine_gpu as rg    # noqa: E402
 import _refine_ref as ref    # noqa: E402
 from _layouts import intact, place    # noqa: E402
-
-EPS = 2.0 ** -53
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+from _refine_gpu import DEV, EPS, dev as _dev, exact_mlp as _exact_mlp    # noqa: E402
+from _refine_gpu import packed_round_trip as _packed_round_trip, ulp_equal as _ulp_equal    # noqa: E402
 
 
 def _walk(W, X, Xq, radii, unit):
@@ -53,10 +49,6 @@ def _run(W, X, Xq, idx, radii, unit, sweeps, **kw):
     return {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
 
 
-def _ulp_equal(a, b, ulps=1):
-    return bool((np.abs(a - b) <= ulps * np.spacing(np.maximum(np.abs(a), np.abs(b)))).all())
-
-
 def _residual_bound(W, X, Xq, radii, unit, n_updates):
     """E [C][m]: a bound on the distance, element by element, between two float64 evaluations of a neuron's residual that round
     every product and sum of the start and of n_updates accepted steps once each but may fuse or order them differently: each of
@@ -76,19 +68,9 @@ def _v_bound(step, m, Xq_abs_row, E_j):
 
 
 # ---- 1. exact data ---------------------------------------------------------------------------------------------------------------
-def _unit(kind):
-    """Unit alphabets of the exact cases.  linspace(-1, 1, M) has dyadic members for M = 2, 3 and 65 (step 1 / 32); the 4- and 16-level
-    linspace members (thirds, fifteenths) are not dyadic, so with them the sums over a_k * Xq are NOT exact: those two are compared
-    neuron by neuron where the decisions are safe from the rounding of v, the norms within the float64 rounding of the sums, and
-    their dyadic neighbours -- 4 members that are not uniform, 16 that are not ascending -- carry the exact check at those sizes."""
-    if kind == "d4":
-        return np.array([-1.0, -0.25, 0.25, 1.0]), True
-    if kind == "d16":
-        return np.random.default_rng(16).permutation(np.arange(-15, 16, 2) / 16.0), True
-    M = int(kind)
-    return np.linspace(-1, 1, M), M in (2, 3, 65)
-
-
+# (the unit alphabets: tests/_refine_gpu.py `unit`.  The 4- and 16-level linspace alphabets are not dyadic: those two are compared neuron
+#  by neuron where the decisions are safe from the rounding of v, the norms within the float64 rounding of the sums, and their dyadic
+#  neighbours -- 4 members that are not uniform, 16 that are not ascending -- carry the exact check at those sizes)
 def _npw(m):
     from quantized_neural_networks_amd import hip
     return hip.refine_neurons_per_workgroup(m)
@@ -109,7 +91,7 @@ NOT_VACUOUS = [c for c in EXACT if c[0] == 97 and c[1] >= 40]
 
 
 def _exact_inputs(N, m, C, kind, radii, seed):
-    unit, dyadic = _unit(kind)
+    unit, dyadic = rg.unit(kind), rg.dyadic(kind)
     if isinstance(C, str):
         C = _npw(m) + (1 if C.endswith("+1") else -1)
     if isinstance(radii, str):
@@ -299,6 +281,7 @@ def test_status_codes():
     from quantized_neural_networks_amd import hip
     lib = hip.load()
     N, m, C = 4, 8, 3
+    max_m = hip.GPFQ_REFINE_MAX_M
     X = torch.ones((N, m), dtype=torch.float32, device=DEV)
     W = torch.ones((N, C), dtype=torch.float32, device=DEV)
     idx = torch.zeros((N, C), dtype=torch.int8, device=DEV)
@@ -307,75 +290,34 @@ def test_status_codes():
     ws = torch.empty(lib.gpfq_refine_workspace_bytes(N), dtype=torch.uint8, device=DEV)
     unit = (ctypes.c_double * 3)(-1.0, 0.0, 1.0)
 
-    def call(**kw):
-        a = dict(X=X.data_ptr(), Xq=X.data_ptr(), ld=m, nrm=nrm.data_ptr(), W=W.data_ptr(), ldw=C, radii=radii.data_ptr(), unit=unit, M=3,
-                 N=N, m=m, C=C, sweeps=1, idx=idx.data_ptr(), ldi=C, ws=ws.data_ptr(), ws_bytes=ws.numel())
-        a.update(kw)
-        return lib.gpfq_refine_neurons(a["X"], a["Xq"], a["ld"], a["nrm"], a["W"], a["ldw"], a["radii"], a["unit"], a["M"], a["N"], a["m"],
-                                       a["C"], a["sweeps"], a["idx"], a["ldi"], None, 0, None, None, None, None, a["ws"], a["ws_bytes"],
-                                       None)
-
+    call = rg.entry_call(lib.gpfq_refine_neurons, dict(
+        X=X.data_ptr(), Xq=X.data_ptr(), ld=m, nrm=nrm.data_ptr(), W=W.data_ptr(), ldw=C, radii=radii.data_ptr(), unit=unit, M=3, N=N, m=m,
+        C=C, sweeps=1, idx=idx.data_ptr(), ldi=C, Q=None, ldq=0, resid_before=None, resid_after=None, changed=None, sweeps_run=None,
+        ws=ws.data_ptr(), ws_bytes=ws.numel(), stream=None))
     assert call() == 0
     torch.cuda.synchronize()
     first = idx.clone()
     assert (first == 2).all()                      # (w = 1 on X = Xq: every weight moves from -1 to +1)
-    bad = hip.GPFQ_ERR_INVALID_ARG
-    assert call(sweeps=0) == bad and b"sweeps" in lib.gpfq_last_error()
-    assert call(X=None) == bad and call(W=None) == bad and call(idx=None) == bad and call(radii=None) == bad and call(unit=None) == bad
-    assert call(ld=m - 1) == bad and call(ldw=C - 1) == bad and call(ldi=C - 1) == bad and call(N=-1) == bad and call(M=0) == bad
-    assert call(m=hip.GPFQ_REFINE_MAX_M + 1, ld=hip.GPFQ_REFINE_MAX_M + 1) == hip.GPFQ_ERR_UNSUPPORTED
-    assert b"GPFQ_REFINE_MAX_M" in lib.gpfq_last_error()
-    assert call(M=257) == hip.GPFQ_ERR_UNSUPPORTED
-    assert call(ws=None) == hip.GPFQ_ERR_WORKSPACE and call(ws_bytes=8 * N - 1) == hip.GPFQ_ERR_WORKSPACE
+    rg.assert_status(lib, call, hip.GPFQ_ERR_INVALID_ARG, [dict(sweeps=0)], b"sweeps")
+    rg.assert_status(lib, call, hip.GPFQ_ERR_INVALID_ARG, [dict(X=None), dict(W=None), dict(idx=None), dict(radii=None), dict(unit=None),
+                                                          dict(ld=m - 1), dict(ldw=C - 1), dict(ldi=C - 1), dict(N=-1), dict(M=0)])
+    rg.assert_status(lib, call, hip.GPFQ_ERR_UNSUPPORTED, [dict(m=max_m + 1, ld=max_m + 1)], b"GPFQ_REFINE_MAX_M")
+    rg.assert_status(lib, call, hip.GPFQ_ERR_UNSUPPORTED, [dict(M=257)])
+    rg.assert_status(lib, call, hip.GPFQ_ERR_WORKSPACE, [dict(ws=None), dict(ws_bytes=8 * N - 1)])
     torch.cuda.synchronize()
     assert torch.equal(idx, first)                 # a refused call launches nothing
 
 
 # ---- 4. the drivers and the classes ----------------------------------------------------------------------------------------------
-class _Quiet:
-    def __init__(self):
-        self.lines = []
-
-    def info(self, msg):
-        self.lines.append(str(msg))
-
-
-def _exact_mlp():
-    """Two Dense layers whose kernels are multiples of 1/8 (the bias of 1/4): on integer inputs every activation of the analog and of
-    the quantized network, every radius (scalar 2 times a dyadic median) and every sum of the refinement is exact."""
-    from quantized_neural_networks_amd import keras_shim as ks
-    net = ks.Sequential([ks.Dense(11, activation="relu", input_shape=(24,)), ks.Dense(5)], seed=1)
-    r = np.random.default_rng(8)
-    for layer, shape in zip(net.layers, ((24, 11), (11, 5))):
-        layer.set_weights([(r.integers(-8, 9, shape) / 8.0).astype(np.float32), (r.integers(-2, 3, shape[1]) / 4.0).astype(np.float32)])
-    return net
-
-
 def _quantize_exact_mlp(refine_passes, radius, alphabet_scalar=2, capture=None):
     from quantized_neural_networks_amd import quantized_network as qn
     x = np.random.default_rng(3).integers(0, 4, (40, 24)).astype(np.float32)
-    q = qn.QuantizedNeuralNetwork(network=_exact_mlp(), batch_size=8, get_data=qn.MNISTSequence(x, np.zeros((40, 1)), 8), logger=_Quiet(),
+    q = qn.QuantizedNeuralNetwork(network=_exact_mlp(), batch_size=8, get_data=qn.MNISTSequence(x, np.zeros((40, 1)), 8), logger=rg.Quiet(),
                                   bits=np.log2(3), alphabet_scalar=alphabet_scalar, radius=radius, refine_passes=refine_passes)
     if capture is not None:
-        orig = q._get_layer_data_generator
-
-        def wrapped(layer_idx, transpose=False):
-            wX, qX = orig(layer_idx, transpose)
-            capture[layer_idx] = (wX.clone(), qX.clone())
-            return wX, qX
-
-        q._get_layer_data_generator = wrapped
+        rg.capture_layer_data(q, capture, clone=True)
     q.quantize_network()
     return q
-
-
-def _packed_round_trip(q, tmp_path):
-    from quantized_neural_networks_amd import deploy
-    path = deploy.export_packed(q, tmp_path / "net")            # a kernel off its alphabet does not encode
-    back = deploy.load_packed(path)
-    for k, layer in enumerate(q.quantized_net.layers):
-        if q._will_quantize(k):
-            assert np.array_equal(np.asarray(back.layers[k].get_weights()[0]), np.asarray(layer.get_weights()[0])), k
 
 
 @pytest.mark.parametrize("radius,scalar", [("layer", 2), ("channel", 2), ("channel", (1, 2, 4)), ("layer", (1, 2, 4))])
@@ -438,16 +380,7 @@ def test_driver_refines_with_a_device_alphabet_and_a_host_alphabet():
 
 
 def _cnn(refine_passes, conv_walk, radius="layer", conv_columns=300):
-    from quantized_neural_networks_amd import keras_shim as ks, quantized_network as qn
-    net = ks.Sequential([ks.Conv2D(6, 3, padding="same", activation="relu", input_shape=(8, 8, 3)),
-                         ks.DepthwiseConv2D(3, padding="valid", depth_multiplier=2, use_bias=False), ks.Flatten(), ks.Dense(3)], seed=3)
-    x = np.random.default_rng(5).random((32, 8, 8, 3)).astype(np.float32)
-    log = _Quiet()
-    q = qn.QuantizedCNN(network=net, batch_size=16, get_data=qn.CIFAR10Sequence(x, np.zeros((32, 3), np.float32), 16), logger=log,
-                        bits=2, alphabet_scalar=3, radius=radius, conv_walk=conv_walk, conv_columns=conv_columns,
-                        refine_passes=refine_passes)
-    q.quantize_network()
-    return q, log
+    return rg.cnn(refine_passes, radius=radius, conv_walk=conv_walk, conv_columns=conv_columns)
 
 
 @pytest.mark.parametrize("radius", ["layer", "channel"])

@@ -18,44 +18,18 @@ import torch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-DEV = torch.device("cuda", 0)
 
+import _refine_gpu as rg    # noqa: E402
 import _refine_gram_ref as gref    # noqa: E402
 import _refine_ref as ref    # noqa: E402
 from _layouts import intact, place    # noqa: E402
-
-EPS = 2.0 ** -53
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _host(out):
-    return {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
-
-
-def _index_type(unit):
-    return np.int16 if len(unit) > 64 else np.int8
+from _refine_gpu import DEV, EPS, dev as _dev, exact_mlp as _exact_mlp, host as _host, index_type as _index_type    # noqa: E402
+from _refine_gpu import packed_round_trip as _packed_round_trip, ulp_equal as _ulp_equal, unit as _unit    # noqa: E402
 
 
 def _run(G, H0, nrm, idx, radii, unit, sweeps, **kw):
     from quantized_neural_networks_amd import hip
     return _host(hip.refine_gram_neurons(_dev(G), _dev(H0), _dev(nrm), _dev(idx.astype(_index_type(unit))), _dev(radii), unit, sweeps, **kw))
-
-
-def _ulp_equal(a, b, ulps=1):
-    return bool((np.abs(a - b) <= ulps * np.spacing(np.maximum(np.abs(a), np.abs(b)))).all())
-
-
-def _unit(kind):
-    """Unit alphabets: 1 member, linspace, the dyadic 4 (not uniform) and 16 (not ascending) of tests/test_refine_gpu.py."""
-    if kind == "d4":
-        return np.array([-1.0, -0.25, 0.25, 1.0])
-    if kind == "d16":
-        return np.random.default_rng(16).permutation(np.arange(-15, 16, 2) / 16.0)
-    M = int(kind)
-    return np.linspace(-1, 1, M) if M > 1 else np.array([1.0])
 
 
 def _nearest(W, radii, unit):
@@ -199,28 +173,21 @@ def test_status_codes():
     nrm = torch.ones(N, dtype=torch.float32, device=DEV)
     unit = (ctypes.c_double * 3)(-1.0, 0.0, 1.0)
 
-    def call(**kw):
-        a = dict(G=G.data_ptr(), ldg=N, H=H.data_ptr(), ldh=N, nrm=nrm.data_ptr(), radii=radii.data_ptr(), unit=unit, M=3, N=N, C=C, sweeps=1,
-                 idx=idx.data_ptr(), ldi=C, Q=None, ldq=0)
-        a.update(kw)
-        return lib.gpfq_refine_gram_neurons(a["G"], a["ldg"], a["H"], a["ldh"], a["nrm"], a["radii"], a["unit"], a["M"], a["N"], a["C"],
-                                            a["sweeps"], a["idx"], a["ldi"], a["Q"], a["ldq"], None, None, None, None)
-
+    call = rg.entry_call(lib.gpfq_refine_gram_neurons, dict(
+        G=G.data_ptr(), ldg=N, H=H.data_ptr(), ldh=N, nrm=nrm.data_ptr(), radii=radii.data_ptr(), unit=unit, M=3, N=N, C=C, sweeps=1,
+        idx=idx.data_ptr(), ldi=C, Q=None, ldq=0, changed=None, sweeps_run=None, gain=None, stream=None))
     assert call() == 0
     torch.cuda.synchronize()
     first, h_first = idx.clone(), H.clone()
     assert (first == 2).all() and (h_first == 0).all()      # (v = -1 + 2 / 1: every weight moves from -1 to +1, h = 2 - 2 * 1)
-    bad = hip.GPFQ_ERR_INVALID_ARG
-    assert call(sweeps=0) == bad and b"sweeps" in lib.gpfq_last_error()
-    assert call(G=None) == bad and call(H=None) == bad and call(nrm=None) == bad and call(idx=None) == bad and call(radii=None) == bad
-    assert call(unit=None) == bad and call(M=0) == bad and call(N=-1) == bad and call(C=-1) == bad
-    assert call(ldg=N - 1) == bad and call(ldh=N - 1) == bad and call(ldi=C - 1) == bad
     Q = torch.zeros((N, C), dtype=torch.float32, device=DEV)
-    assert call(Q=Q.data_ptr(), ldq=C - 1) == bad
-    assert call(G=G.data_ptr() + 4) == bad and call(H=H.data_ptr() + 4) == bad
     big = hip.GPFQ_REFINE_GRAM_MAX_N + 1
-    assert call(N=big, ldg=big, ldh=big) == hip.GPFQ_ERR_UNSUPPORTED and b"GPFQ_REFINE_GRAM_MAX_N" in lib.gpfq_last_error()
-    assert call(M=257) == hip.GPFQ_ERR_UNSUPPORTED
+    rg.assert_status(lib, call, hip.GPFQ_ERR_INVALID_ARG, [dict(sweeps=0)], b"sweeps")
+    rg.assert_status(lib, call, hip.GPFQ_ERR_INVALID_ARG, [
+        dict(G=None), dict(H=None), dict(nrm=None), dict(idx=None), dict(radii=None), dict(unit=None), dict(M=0), dict(N=-1), dict(C=-1),
+        dict(ldg=N - 1), dict(ldh=N - 1), dict(ldi=C - 1), dict(Q=Q.data_ptr(), ldq=C - 1), dict(G=G.data_ptr() + 4), dict(H=H.data_ptr() + 4)])
+    rg.assert_status(lib, call, hip.GPFQ_ERR_UNSUPPORTED, [dict(N=big, ldg=big, ldh=big)], b"GPFQ_REFINE_GRAM_MAX_N")
+    rg.assert_status(lib, call, hip.GPFQ_ERR_UNSUPPORTED, [dict(M=257)])
     assert hip.GPFQ_REFINE_GRAM_MAX_N >= 25088
     torch.cuda.synchronize()
     assert torch.equal(idx, first) and torch.equal(H, h_first) and (Q == 0).all()       # a refused call launches nothing
@@ -378,41 +345,14 @@ def test_drivers_pass_the_form_on_and_refuse_what_the_kernel_does_not_take(monke
 
 
 # ---- 4. the classes ------------------------------------------------------------------------------------------------------------------
-class _Quiet:
-    def __init__(self):
-        self.lines = []
-
-    def info(self, msg):
-        self.lines.append(str(msg))
-
-
 SAMPLES = 8193          # one more than the residual form's rows
-
-
-def _exact_mlp():
-    """Two Dense layers whose kernels are multiples of 1/8 (the bias of 1/4) on integer inputs: every sum of the refinement is exact."""
-    from quantized_neural_networks_amd import keras_shim as ks
-    net = ks.Sequential([ks.Dense(11, activation="relu", input_shape=(24,)), ks.Dense(5)], seed=1)
-    r = np.random.default_rng(8)
-    for layer_, shape in zip(net.layers, ((24, 11), (11, 5))):
-        layer_.set_weights([(r.integers(-8, 9, shape) / 8.0).astype(np.float32), (r.integers(-2, 3, shape[1]) / 4.0).astype(np.float32)])
-    return net
 
 
 def _mlp_quantizer(**kw):
     from quantized_neural_networks_amd import quantized_network as qn
     x = np.random.default_rng(3).integers(0, 4, (SAMPLES, 24)).astype(np.float32)
     return qn.QuantizedNeuralNetwork(network=_exact_mlp(), batch_size=8, get_data=qn.MNISTSequence(x, np.zeros((SAMPLES, 1)), SAMPLES),
-                                     logger=_Quiet(), bits=np.log2(3), alphabet_scalar=2, **kw)
-
-
-def _packed_round_trip(q, tmp_path):
-    from quantized_neural_networks_amd import deploy
-    path = deploy.export_packed(q, tmp_path / "net")            # a kernel off its alphabet does not encode
-    back = deploy.load_packed(path)
-    for k, layer_ in enumerate(q.quantized_net.layers):
-        if q._will_quantize(k):
-            assert np.array_equal(np.asarray(back.layers[k].get_weights()[0]), np.asarray(layer_.get_weights()[0])), k
+                                     logger=rg.Quiet(), bits=np.log2(3), alphabet_scalar=2, **kw)
 
 
 @pytest.mark.parametrize("radius", ["layer", "channel"])
@@ -443,17 +383,9 @@ def test_an_mlp_on_more_samples_than_the_residual_form_takes_is_refined(radius, 
 
 
 def _cnn(refine_passes, conv_columns, **kw):
-    from quantized_neural_networks_amd import keras_shim as ks, quantized_network as qn
-    net = ks.Sequential([ks.Conv2D(6, 3, padding="same", activation="relu", input_shape=(16, 16, 8)),
-                         ks.DepthwiseConv2D(3, padding="valid", depth_multiplier=2, use_bias=False), ks.Flatten(), ks.Dense(3)], seed=3)
     # (signed inputs and 72 weights per filter: on all-positive images with nearly every patch column gathered, the walk of a 27-weight
     #  filter leaves no single weight to improve -- checked with the oracle's walk and tests/_refine_ref.py on the host)
-    x = np.random.default_rng(5).standard_normal((36, 16, 16, 8)).astype(np.float32)
-    log = _Quiet()
-    q = qn.QuantizedCNN(network=net, batch_size=36, get_data=qn.CIFAR10Sequence(x, np.zeros((36, 3), np.float32), 36), logger=log,
-                        bits=2, alphabet_scalar=3, conv_walk="filter", conv_columns=conv_columns, refine_passes=refine_passes, **kw)
-    q.quantize_network()
-    return q, log
+    return rg.cnn(refine_passes, input_shape=(16, 16, 8), images=36, batch=36, signed=True, conv_walk="filter", conv_columns=conv_columns, **kw)
 
 
 def test_a_filter_walk_on_more_columns_than_the_residual_form_takes_is_refined(tmp_path):

@@ -15,31 +15,30 @@ import torch
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-DEV = torch.device("cuda", 0)
 
+import _refine_gpu as rg    # noqa: E402
 import _refine_pairs_ref as pref    # noqa: E402
 import _refine_ref as ref    # noqa: E402
 from _im2col_ref import patches    # noqa: E402
+from _refine_gpu import DEV, dev as _dev, host as _np    # noqa: E402
 
 # name -> (n, H, W, kernel_size, strides, rate, padding); then per geometry (F, nch, M) of the kernel test: between them F = 1, 5, 65,
-# 257 (one lane, a partial wavefront, a second workgroup with one lane, a fifth), nch = 1, 3, M = 1, 3, 4, 16, 200 (int16 indices)
+# 70, 257 (one lane, a partial wavefront, a second workgroup with one lane or six, a fifth), nch = 1, 3, M = 1, 3, 4, 16, 65, 200 (the
+# last two: int16 indices).  K = 1, 4, 9, 25 are the register forms of the kernel, every other K the LDS-column form.
 GEOMS = {
     "3x3-same": (4, 8, 8, (3, 3), (1, 1), (1, 1), "SAME"),
     "3x3-s2-valid": (3, 9, 9, (3, 3), (2, 2), (1, 1), "VALID"),
     "5x5-same": (2, 8, 8, (5, 5), (1, 1), (1, 1), "SAME"),
     "7x7-s2-valid": (2, 16, 16, (7, 7), (2, 2), (1, 1), "VALID"),
     "1x1": (3, 6, 6, (1, 1), (1, 1), (1, 1), "VALID"),
+    "2x2": (3, 7, 7, (2, 2), (1, 1), (1, 1), "VALID"),
     "2x3": (3, 7, 7, (2, 3), (1, 1), (1, 1), "VALID"),
     "8x8": (4, 12, 12, (8, 8), (1, 1), (1, 1), "VALID"),
     "3x3-dilated": (3, 9, 9, (3, 3), (1, 1), (2, 2), "SAME"),
 }
 KERNEL_CASE = {"3x3-same": (257, 3, 3), "3x3-s2-valid": (65, 3, 16), "5x5-same": (65, 1, 4), "7x7-s2-valid": (5, 3, 200),
-               "1x1": (257, 3, 16), "2x3": (65, 3, 1), "8x8": (5, 1, 3), "3x3-dilated": (1, 3, 4)}
+               "1x1": (257, 3, 16), "2x2": (70, 3, 65), "2x3": (65, 3, 1), "8x8": (5, 1, 3), "3x3-dilated": (1, 3, 4)}
 SAME = [False, True]
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _geom(name):
@@ -75,10 +74,6 @@ def _records(name, act_w, act_q, same):
     pq = pw if same else hip.channel_planes(_dev(act_q), 0, Cin)
     rec, _ = hip.conv_channel_records(pw, pq, *conv)
     return rec, (None if same else hip.conv_channel_records(pq, pw, *conv)[0])
-
-
-def _np(out):
-    return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
 
 
 # ---- 1. the kernel against the restatement -------------------------------------------------------------------------------------------
@@ -264,40 +259,15 @@ def test_driver_with_channel_radii_on_conv2d_and_depthwise_and_with_the_searchs_
 
 
 # ---- 5. the class ------------------------------------------------------------------------------------------------------------------
-class _Quiet:
-    def __init__(self):
-        self.lines = []
-
-    def info(self, msg):
-        self.lines.append(str(msg))
-
-
 def _cnn(refine_passes, radius="layer", one_by_one=False, capture=None, **kw):
-    """The small CNN of tests/test_refine_gpu.py::_cnn under conv_walk="channel"; one_by_one: a 1 x 1 Conv2D in the depthwise layer's
-    place (32 -> 64 channels: 2048 one-step walks on quantized inputs that differ from the analog ones).  capture: a dict that takes
-    the (wX, qX) every layer was given."""
-    from quantized_neural_networks_amd import keras_shim as ks, quantized_network as qn
+    """The small CNN of tests/_refine_gpu.py under conv_walk="channel"; one_by_one: a 1 x 1 Conv2D in the depthwise layer's place
+    (32 -> 64 channels: 2048 one-step walks on quantized inputs that differ from the analog ones).  capture: a dict that takes the
+    (wX, qX) every layer was given."""
+    from quantized_neural_networks_amd import keras_shim as ks
+    layers = None
     if one_by_one:
         layers = [ks.Conv2D(32, 3, padding="same", activation="relu", input_shape=(8, 8, 3)), ks.Conv2D(64, 1, use_bias=False)]
-    else:
-        layers = [ks.Conv2D(6, 3, padding="same", activation="relu", input_shape=(8, 8, 3)),
-                  ks.DepthwiseConv2D(3, padding="valid", depth_multiplier=2, use_bias=False)]
-    net = ks.Sequential(layers + [ks.Flatten(), ks.Dense(3)], seed=3)
-    x = np.random.default_rng(5).random((32, 8, 8, 3)).astype(np.float32)
-    log = _Quiet()
-    q = qn.QuantizedCNN(network=net, batch_size=16, get_data=qn.CIFAR10Sequence(x, np.zeros((32, 3), np.float32), 16), logger=log,
-                        bits=2, alphabet_scalar=3, radius=radius, conv_walk="channel", refine_passes=refine_passes, **kw)
-    if capture is not None:
-        orig = q._get_layer_data_generator
-
-        def wrapped(layer_idx, transpose=False):
-            wX, qX = orig(layer_idx, transpose)
-            capture[layer_idx] = (wX, qX)
-            return wX, qX
-
-        q._get_layer_data_generator = wrapped
-    q.quantize_network()
-    return q, log
+    return rg.cnn(refine_passes, layers=layers, capture=capture, radius=radius, conv_walk="channel", **kw)
 
 
 def _kernels(q, k):
@@ -385,7 +355,7 @@ def test_a_kernel_beyond_64_weights_and_several_ranks_are_refused(monkeypatch):
     assert hip.GPFQ_REFINE_PAIRS_MAX_K == 64 == hip.GPFQ_GRAM_AUTO_MAX_N
     net = ks.Sequential([ks.Conv2D(2, 9, padding="valid", input_shape=(12, 12, 1), name="wide_conv"), ks.Flatten(), ks.Dense(2)], seed=4)
     x = np.random.default_rng(6).random((8, 12, 12, 1)).astype(np.float32)
-    q = qn.QuantizedCNN(network=net, batch_size=8, get_data=qn.CIFAR10Sequence(x, np.zeros((8, 2), np.float32), 8), logger=_Quiet(), bits=2,
+    q = qn.QuantizedCNN(network=net, batch_size=8, get_data=qn.CIFAR10Sequence(x, np.zeros((8, 2), np.float32), 8), logger=rg.Quiet(), bits=2,
                         alphabet_scalar=3, refine_passes=1, refine_channel_walks=True)
     with pytest.raises(NotImplementedError, match="layer 0 .wide_conv.") as exc:
         q.quantize_network()
@@ -415,23 +385,18 @@ def test_status_codes():
     radii = torch.ones((nch, F), dtype=torch.float64, device=DEV)
     unit = (ctypes.c_double * 3)(-1.0, 0.0, 1.0)
 
-    def call(**kw):
-        a = dict(rec=rec.data_ptr(), swp=None, K=K, W=W.data_ptr(), radii=radii.data_ptr(), unit=unit, M=3, nch=nch, F=F, sweeps=1,
-                 idx=idx.data_ptr())
-        a.update(kw)
-        return lib.gpfq_refine_conv_pairs(a["rec"], a["swp"], a["K"], a["W"], a["radii"], a["unit"], a["M"], a["nch"], a["F"], a["sweeps"],
-                                          a["idx"], None, None, None, None, None)
-
+    call = rg.entry_call(lib.gpfq_refine_conv_pairs, dict(
+        rec=rec.data_ptr(), swp=None, K=K, W=W.data_ptr(), radii=radii.data_ptr(), unit=unit, M=3, nch=nch, F=F, sweeps=1, idx=idx.data_ptr(),
+        Qt=None, changed=None, sweeps_run=None, gain=None, stream=None))
     assert call() == 0
     torch.cuda.synchronize()
     first = idx.clone()
     assert (first.reshape(-1)[:nch * F * K] == 2).all() and (first.reshape(-1)[nch * F * K:] == 0).all()
-    bad = hip.GPFQ_ERR_INVALID_ARG
-    assert call(K=81, rec=big.data_ptr()) == hip.GPFQ_ERR_UNSUPPORTED and b"GPFQ_REFINE_PAIRS_MAX_K" in lib.gpfq_last_error()
-    assert call(K=65) == hip.GPFQ_ERR_UNSUPPORTED and call(M=257) == hip.GPFQ_ERR_UNSUPPORTED
-    assert call(K=0) == bad and call(sweeps=0) == bad and b"sweeps" in lib.gpfq_last_error()
-    assert call(M=0) == bad and call(unit=None) == bad and call(nch=-1) == bad and call(F=-1) == bad
-    assert call(rec=None) == bad and call(W=None) == bad and call(radii=None) == bad and call(idx=None) == bad
+    rg.assert_status(lib, call, hip.GPFQ_ERR_UNSUPPORTED, [dict(K=81, rec=big.data_ptr())], b"GPFQ_REFINE_PAIRS_MAX_K")
+    rg.assert_status(lib, call, hip.GPFQ_ERR_UNSUPPORTED, [dict(K=65), dict(M=257)])
+    rg.assert_status(lib, call, hip.GPFQ_ERR_INVALID_ARG, [dict(sweeps=0)], b"sweeps")
+    rg.assert_status(lib, call, hip.GPFQ_ERR_INVALID_ARG, [dict(K=0), dict(M=0), dict(unit=None), dict(nch=-1), dict(F=-1), dict(rec=None), dict(W=None),
+                                                          dict(radii=None), dict(idx=None)])
     assert call(nch=0) == 0 and call(F=0) == 0 and call(nch=0, rec=None, W=None, radii=None, idx=None) == 0
     torch.cuda.synchronize()
     assert torch.equal(idx, first)                         # a refused or empty call launches nothing
