@@ -487,9 +487,21 @@ int gpfq_packed_dense_forward_tiled(const float *x, int64_t B, int64_t ldx, cons
  * aligned, scales NULL.
  *   xq, scales as above; packed, radii, bias, y as for gpfq_packed_dense_forward.
  * Both are one launch each, asynchronous on `stream`, without atomics, workspace or host synchronisation.
+ *
+ * gpfq_quantize_rows_i8_split: gpfq_quantize_rows_i8's result bit for bit -- the same xq, pad bytes and scales for the same arguments,
+ * the same checks, status codes and early returns (B = 0: GPFQ_OK and nothing done; N = 0 with B > 0: scales of 0.0f, nothing of xq
+ * written) -- for rows long enough to occupy more than one workgroup (an image of a Conv2D layer).  It always splits: a row is cut into
+ * chunks of gpfq_quantize_split_chunk() floats (a multiple of 16) with one workgroup per (row, chunk), in up to four operations on
+ * `stream` ordered by the stream alone -- a clear of scales; the maximum of the bit patterns of |x| per chunk, met by one unsigned
+ * max atomic per workgroup on scales[b] read as an unsigned integer (the maximum does not depend on the order it is taken in); the
+ * chunks of xq; the scales -- with no workgroup waiting for another.  Between the call's first and last operation scales holds
+ * intermediate values (the maxima), not scales.  x, xq and scales must not overlap.  Asynchronous, capturable into a graph, without
+ * workspace or host synchronisation.  GPFQ_ERR_UNSUPPORTED also for N at or beyond 2^31 chunks.
  */
 #define GPFQ_PACKED_I8_MAX_N 262144
 int gpfq_quantize_rows_i8(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales, void *stream);
+int gpfq_quantize_rows_i8_split(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales, void *stream);
+int64_t gpfq_quantize_split_chunk(void);
 int gpfq_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
                                  int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
                                  int64_t ldy, void *stream);

@@ -22,7 +22,7 @@ STAMP = LIB + ".sha"
 OBJDIR = os.path.join(CSRC, "build")
 SOURCES = ["gpfq_capi.hip", "gpfq_onchip.hip", "gpfq_rows.hip", "gpfq_pipe.hip", "gpfq_blk.hip", "gpfq_wide.hip", "gpfq_stream.hip",
            "gpfq_gram.hip", "gpfq_gram_image.hip", "gpfq_gram_conv.hip", "gpfq_gram_s2.hip", "gpfq_gram_mfma.hip", "gpfq_misc.hip",
-           "gpfq_colrad.hip", "gpfq_search.hip", "gpfq_gather.hip", "gpfq_packed.hip", "gpfq_packed_tiled.hip", "gpfq_packed_i8.hip", "gpfq_packed_conv_i8.hip", "gpfq_refine.hip",
+           "gpfq_colrad.hip", "gpfq_search.hip", "gpfq_gather.hip", "gpfq_packed.hip", "gpfq_packed_tiled.hip", "gpfq_packed_i8.hip", "gpfq_packed_conv_i8.hip", "gpfq_quantize_split.hip", "gpfq_refine.hip",
            "gpfq_refine_gram.hip", "gpfq_refine_pairs.hip"]
 HEADERS = ["gpfq_device.hpp", "gpfq_launch.hpp", "gpfq_options.hpp", "gpfq_gram_tile.hpp", "gpfq_roles.hpp", "gpfq_blk_diag.hpp", "gpfq_packed.hpp", "gpfq_packed_i8.hpp", "gpfq_refine.hpp", os.path.join("..", "..", "include", "gpfq.h")]
 

@@ -876,7 +876,12 @@ int gpfq_packed_dense_forward_tiled(const float *x, int64_t B, int64_t ldx, cons
                                 zero_code, radii, unit_alphabet, M, bias, N, C, y, ldy, stream);
 }
 
-int gpfq_quantize_rows_i8(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales, void *stream)
+typedef hipError_t (*QuantizeRowsLaunch)(const float *, int64_t, int64_t, int64_t, int8_t *, int64_t, float *, hipStream_t);
+
+// the checks, early returns and status codes of both quantizers of the activations (the row kernel, chunk = 0, and the split form,
+// whose chunks of a row must fit a grid dimension)
+static int quantize_rows_entry(const char *name, QuantizeRowsLaunch launch, int64_t chunk, const float *x, int64_t B, int64_t ldx, int64_t N,
+                               int8_t *xq, int64_t ldq, float *scales, void *stream)
 {
     if (B < 0 || N < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size B=%lld N=%lld", (long long)B, (long long)N);
     if (ldq % 16 != 0 || ldq < N) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldq=%lld must be a multiple of 16 and at least N=%lld", (long long)ldq, (long long)N);
@@ -888,9 +893,23 @@ int gpfq_quantize_rows_i8(const float *x, int64_t B, int64_t ldx, int64_t N, int
         if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
     }
     if (B > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "batch too long for one launch");
-    hipError_t e = gpfq::launch_quantize_rows_i8(x, B, ldx, N, xq, ldq, scales, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_quantize_rows_i8");
+    if (chunk > 0 && N / chunk >= 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "row too long for one launch");
+    hipError_t e = launch(x, B, ldx, N, xq, ldq, scales, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
 }
+
+int gpfq_quantize_rows_i8(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales, void *stream)
+{
+    return quantize_rows_entry("gpfq_quantize_rows_i8", gpfq::launch_quantize_rows_i8, 0, x, B, ldx, N, xq, ldq, scales, stream);
+}
+
+int gpfq_quantize_rows_i8_split(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales, void *stream)
+{
+    return quantize_rows_entry("gpfq_quantize_rows_i8_split", gpfq::launch_quantize_rows_i8_split, gpfq::quantize_split_chunk(), x, B, ldx, N,
+                               xq, ldq, scales, stream);
+}
+
+int64_t gpfq_quantize_split_chunk(void) { return gpfq::quantize_split_chunk(); }
 
 int gpfq_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
                                  int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,

@@ -348,6 +348,11 @@ hipError_t launch_quantize_rows_i8(const float *x, int64_t B, int64_t ldx, int64
 hipError_t launch_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
                                           int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
                                           int64_t ldy, hipStream_t stream);
+// gpfq_quantize_split.hip (addendum): launch_quantize_rows_i8's result bit for bit with a row spread over
+// workgroups of quantize_split_chunk() floats each -- a clear of scales and three launches, scales holding the rows' maxima in between
+int64_t quantize_split_chunk();
+hipError_t launch_quantize_rows_i8_split(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales,
+                                         hipStream_t stream);
 // gpfq_packed_conv_i8.hip: the Conv2D forward pass of int8 NHWC images with the kernel [kh*kw*Cin][F] held as
 // packed rows, an implicit GEMM on the same instruction (rows: the n*OH*OW output positions; no patch matrix).  The geometry as the
 // entry resolved it: output size and the pads before (TensorFlow's SAME split), every field checked to fit what the kernel indexes with.

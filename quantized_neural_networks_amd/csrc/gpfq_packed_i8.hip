@@ -40,13 +40,6 @@ namespace {
 
 constexpr int kQuantThreads = 256;                  // one workgroup per batch row
 
-__device__ inline int8_t quantize_one(float v, float inv)
-{
-    float q = rintf(v * inv);                       // one float32 product, then round half to even
-    q = q < -127.f ? -127.f : (q > 127.f ? 127.f : q);
-    return (int8_t)(int)q;
-}
-
 __global__ void __launch_bounds__(kQuantThreads)
 gpfq_quantize_rows_i8_kernel(const float *__restrict__ x, int64_t ldx, int64_t N, int8_t *__restrict__ xq, int64_t ldq,
                              float *__restrict__ scales)

@@ -1,6 +1,7 @@
 // What the two units on the i8 matrix instruction share (gpfq_packed_i8.hip: Dense; gpfq_packed_conv_i8.hip: Conv2D): packed codes ->
 // int8 B operands of v_mfma_i32_16x16x64_i8 by register arithmetic.  The weight of code c is 2 (c - zero_code) - (M - 1) where
-// zero_code <= c < zero_code + M, else 0 (include/gpfq.h).
+// zero_code <= c < zero_code + M, else 0 (include/gpfq.h).  And what the two quantizers of the activations share (gpfq_packed_i8.hip:
+// a workgroup per row; gpfq_quantize_split.hip: a workgroup per chunk of a row): one element -> its int8.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +10,14 @@
 namespace gpfq {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// xq of one element, given the row's inv = 127.0f / amax (include/gpfq.h, gpfq_quantize_rows_i8)
+__device__ inline int8_t quantize_one(float v, float inv)
+{
+    float q = rintf(v * inv);                       // one float32 product, then round half to even
+    q = q < -127.f ? -127.f : (q > 127.f ? 127.f : q);
+    return (int8_t)(int)q;
+}
 
 // What turns codes into weights, one copy in every byte: the first code of a member, the first code past the members, and
 // 128 - (2 zero_code + M - 1), which puts 2 c - (2 zero_code + M - 1) into excess-128 form without a carry between bytes.

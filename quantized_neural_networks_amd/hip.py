@@ -69,6 +69,8 @@ SYMBOLS = {
     "gpfq_packed_dense_forward": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _dp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
     "gpfq_packed_dense_forward_tiled": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _dp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
     "gpfq_quantize_rows_i8": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "gpfq_quantize_rows_i8_split": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "gpfq_quantize_split_chunk": (_i64, []),
     "gpfq_packed_dense_forward_i8": (_int, [_vp, _i64, _i64, _vp, _vp, _int, _int, _vp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
     "gpfq_packed_conv2d_forward_i8": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
                                              _vp, _int, _int, _vp, _int, _vp, _i64, _vp, _vp]),
@@ -1429,11 +1431,35 @@ def packed_dense_forward_tiled(x, packed, bits, zero_code, radii, unit_alphabet,
     return _packed_forward("gpfq_packed_dense_forward_tiled", x, packed, bits, zero_code, radii, unit_alphabet, N, bias, out)
 
 
-def quantize_rows_i8(x, N=None, out=None):
+# Shortest row quantize_rows_i8 gives to the split form (gpfq_quantize_rows_i8_split: a workgroup per chunk of a row) by default;
+# shorter rows take the row kernel (a workgroup per row).  Both give the same bits, so this decides time alone.  The rule, fixed before
+# measuring: the smallest probed row length from which, for that length and every longer one, the split form's median is not above the
+# row form's at every probed batch (1, 8, 32, 256), "not above" allowing for the spread of the row form's own repeated runs; 2**62 --
+# never split -- if there is none (tools/packed_conv_probe.py --quantizer -> profiles/packed_conv_i8_split.txt).
+# Measured (us, split against row, at 1 / 8 / 32 / 256 rows): 1024 columns 8.4 : 3.7 .. 9.2 : 4.2; 4096 columns 9.6 : 6.0 .. 10.3 : 6.6;
+# 8192 columns 9.8 : 9.4 .. 10.9 : 10.2 (the split form's four launches still cost more than they save); 25088 columns 10.0 : 23.1,
+# 10.5 : 24.1, 11.2 : 24.4, 15.8 : 27.4; and from there on the split form ahead everywhere, 200704 columns 10.4 : 163, 14.5 : 170,
+# 25.3 : 182, 92 : 217.  Nothing was probed between 8192 and 25088 columns.
+QUANTIZE_SPLIT_MIN_N = 25088
+
+QUANTIZE_FORMS = (None, "row", "split")
+
+
+def quantize_split_chunk():
+    """The number of floats of a row one workgroup of the split quantizer handles (gpfq_quantize_split_chunk): a multiple of 16."""
+    return int(load().gpfq_quantize_split_chunk())
+
+
+def quantize_rows_i8(x, N=None, out=None, form=None):
     """x f32 [B][N] (rows contiguous, any row pitch) -> (xq i8 [B][roundup16(N)], scales f32 [B]) (gpfq_quantize_rows_i8): per batch
     row, xq = rint(x * (127 / amax)) and scales = amax / 127; a row that is not finite gets the scale NaN and zeros, a row below 2^-100
     the scale 0 and zeros; the pad bytes are zeros.  N: the leading columns of x to take (default: all).  out: an optional
-    (xq, scales) pair; xq may be a view of [B] rows whose pitch is a multiple of 16, on a 16-byte aligned address.  No sync."""
+    (xq, scales) pair; xq may be a view of [B] rows whose pitch is a multiple of 16, on a 16-byte aligned address.  form: "row" (one
+    workgroup per row, one launch), "split" (gpfq_quantize_rows_i8_split: a workgroup per chunk of a row, four stream operations,
+    scales holding the rows' maxima in between) or None: "split" from QUANTIZE_SPLIT_MIN_N columns on.  The same bits either way.
+    No sync."""
+    if form not in QUANTIZE_FORMS:
+        raise GpfqError(f"form must be one of {QUANTIZE_FORMS}, got {form!r}")
     _dev(x, torch.float32, "x")
     xp, B, Nx, ldx = _rows(x, "x")
     N = Nx if N is None else int(N)
@@ -1449,8 +1475,11 @@ def quantize_rows_i8(x, N=None, out=None):
         raise GpfqError(f"out must be (int8 [{B}][>= {n16}], float32 [{B}]), got {tuple(xq.shape)}, {tuple(scales.shape)}")
     if B <= 1:
         ldq = max(n16, 16)
+    if form is None:
+        form = "split" if N >= QUANTIZE_SPLIT_MIN_N else "row"
+    entry = "gpfq_quantize_rows_i8_split" if form == "split" else "gpfq_quantize_rows_i8"
     with torch.cuda.device(x.device):
-        _check(load().gpfq_quantize_rows_i8(xp, B, ldx, N, qp, ldq, scales.data_ptr(), _stream()), "gpfq_quantize_rows_i8")
+        _check(getattr(load(), entry)(xp, B, ldx, N, qp, ldq, scales.data_ptr(), _stream()), entry)
     return xq, scales
 
 

@@ -15,8 +15,21 @@ graph is replayed, the replays are timed with device events and the three ways a
 shipped library and once on each diagnostic build GPFQ_DIAG="-DGPFQ_CONV_I8_SKIP=1|2|3" (the gather, the decode, the matrix
 instruction left out; build.py): what a phase's absence saves is what it held.
 
+--quantizer: the image quantization alone, hip.quantize_rows_i8(form="row") against form="split" (gpfq_quantize_rows_i8_split; DESIGN.md
+section 11b, addendum) -> the first table of profiles/packed_conv_i8_split.txt.  Row lengths 1024 .. 802816, batches 1, 8, 32, 256; the
+row form is captured twice, so three graphs alternate (row, split, row again) and the file shows what the row form's own repeated runs
+differ by.  The rule for hip.QUANTIZE_SPLIT_MIN_N, fixed before measuring: the smallest probed row length from which, for that length
+and every longer one, the split form's median is not above the row form's at every probed batch -- "not above": at most the larger of
+the row form's two medians --; 2**62 (never split) if there is none.
+
+--ways i8,float: only these of the three ways (the layer table of profiles/packed_conv_i8_split.txt leaves decode out).
+--tree PATH: take the package (and its built library) from another checkout of this repository, e.g. the parent commit built in a
+scratch worktree: the same probe, alternating between two trees, is how a change to the layer call is measured.
+
     python tools/packed_conv_probe.py [--out profiles/packed_conv_i8.txt] [--quick]
     GPFQ_DIAG="-DGPFQ_CONV_I8_SKIP=1" python tools/packed_conv_probe.py --phases
+    python tools/packed_conv_probe.py --quantizer --out quantizer.txt
+    python tools/packed_conv_probe.py --ways i8,float [--tree ../parent] --out layers.txt
 """
 import argparse
 import os
@@ -25,7 +38,18 @@ import sys
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+def _tree():
+    """--tree PATH, read before the package is imported."""
+    for i, a in enumerate(sys.argv):
+        if a == "--tree" and i + 1 < len(sys.argv):
+            return os.path.abspath(sys.argv[i + 1])
+        if a.startswith("--tree="):
+            return os.path.abspath(a[len("--tree="):])
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+
+
+sys.path.insert(0, _tree())
 from quantized_neural_networks_amd import deploy, hip, keras_shim as ks  # noqa: E402
 
 # (label, H = W, Cin, F, k, stride)
@@ -46,6 +70,10 @@ SHAPES = [
 ]
 PHASE_SHAPES = [SHAPES[0], SHAPES[3], SHAPES[4], SHAPES[6]]
 IMAGES = (1, 8, 32)
+WAYS = ("i8", "float", "decode")
+QUANT_LENGTHS = (1024, 4096, 8192, 25088, 65536, 100352, 150528, 200704, 802816)
+QUANT_BATCHES = (1, 8, 32, 256)
+QUANT_BUDGET = 4 << 30                                  # bytes of x + xq a case may take; a case beyond it is skipped and named
 
 
 def on_alphabet(rng, shape, M, dev):
@@ -111,26 +139,68 @@ def measure(shape, M, args, dev, out):
     (l_i8, l_float, l_decode), packed, _ = layers_of(rng, H, Cin, F, k, stride, M, dev)
     out(f"{label}, M={M} ({packed['bits']}-bit codes): K={k * k * Cin}, {packed['codes'].numel() / 1e3:.1f} kB packed against "
         f"{k * k * Cin * F * 4 / 1e3:.1f} kB float32, {'fast' if Cin % 16 == 0 else 'general'} path")
-    out("    images   quantize+i8 us, median (min .. max)   float conv us                         decode+conv us                       "
-        "i8/float  i8/decode   max err / max |y|")
+    ways = [w for w in WAYS if w in args.ways]
+    head = {"i8": "quantize+i8 us, median (min .. max)   ", "float": "float conv us                         ",
+            "decode": "decode+conv us                       "}
+    out("    images   " + "".join(head[w] for w in ways) + ("i8/float  " if "float" in ways else "") +
+        ("i8/decode   " if "decode" in ways else "") + ("max err / max |y|" if "float" in ways else ""))
+    layer_of = {"i8": l_i8, "float": l_float, "decode": l_decode}
     for n in IMAGES:
         x = torch.relu(torch.randn((n, H, H, Cin), device=dev))
-        ys = [None, None, None]
+        ys = {}
 
-        def way(j, layer):
+        def way(w):
             def fn():
-                ys[j] = layer.call(x)
+                ys[w] = layer_of[w].call(x)
             return fn
 
         with torch.no_grad():
-            graphs = [capture(way(j, layer), args.chain) for j, layer in enumerate((l_i8, l_float, l_decode))]
-            res = timed(graphs, args.replays)
-        ref = ys[1].double()
-        err = [float((y.double() - ref).abs().max() / ref.abs().max()) for y in ys]
-        assert err[2] < 1e-4 and err[0] < 0.1, err      # (int8 activations: half a step of 1/127 of an image's amax per element)
-        out(f"    {n:6d}   {fmt(res[0], args.chain)}          {fmt(res[1], args.chain)}          {fmt(res[2], args.chain)}      "
-            f"{res[0][0] / res[1][0]:6.2f}    {res[0][0] / res[2][0]:6.2f}      {err[0]:.2e}")
+            graphs = [capture(way(w), args.chain) for w in ways]
+            res = dict(zip(ways, timed(graphs, args.replays)))
+        line = f"    {n:6d}   " + "".join(f"{fmt(res[w], args.chain)}          " for w in ways)
+        if "float" in ways:
+            ref = ys["float"].double()
+            err = {w: float((ys[w].double() - ref).abs().max() / ref.abs().max()) for w in ways}
+            assert err.get("decode", 0) < 1e-4 and err["i8"] < 0.1, err     # (int8 activations: half a step of 1/127 of an image's amax per element)
+            line += f"{res['i8'][0] / res['float'][0]:6.2f}    "
+        if "decode" in ways:
+            line += f"{res['i8'][0] / res['decode'][0]:6.2f}      "
+        if "float" in ways:
+            line += f"{err['i8']:.2e}"
+        out(line.rstrip())
         del graphs
+
+
+def quantizer(args, dev, out):
+    """form="row" against form="split" on rows of QUANT_LENGTHS floats; see the module's text for the rule."""
+    out(f"# {torch.cuda.get_device_name(dev)}; hip.quantize_rows_i8 alone, device time per call: {args.chain} calls captured into one graph, "
+        f"{args.replays} timed replays per graph, three graphs alternating (row, split, row again); median (min .. max); us; "
+        f"chunk = {hip.quantize_split_chunk()} floats")
+    out("#       N      B   row                               split                             row again                         "
+        "split/row   split <= larger row median")
+    ok = {}
+    for N in QUANT_LENGTHS:
+        for B in QUANT_BATCHES:
+            n16 = (N + 15) // 16 * 16
+            if B * (4 * N + n16) > QUANT_BUDGET:
+                out(f"{N:9d} {B:6d}   skipped: {B * (4 * N + n16) / 2 ** 30:.1f} GiB of x and xq, beyond the probe's {QUANT_BUDGET >> 30} GiB")
+                continue
+            x = torch.relu(torch.randn((B, N), device=dev))
+            outs = [(torch.empty((B, n16), dtype=torch.int8, device=dev), torch.empty(B, device=dev)) for _ in range(3)]
+
+            def call(k, form):
+                return lambda: hip.quantize_rows_i8(x, out=outs[k], form=form)
+
+            res = timed([capture(call(k, form), args.chain) for k, form in enumerate(("row", "split", "row"))], args.replays)
+            assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])          # the same bits
+            ok[(N, B)] = res[1][0] <= max(res[0][0], res[2][0])
+            out(f"{N:9d} {B:6d}   {fmt(res[0], args.chain)}   {fmt(res[1], args.chain)}   {fmt(res[2], args.chain)}   "
+                f"{res[1][0] / min(res[0][0], res[2][0]):8.2f}   {'yes' if ok[(N, B)] else 'no'}")
+            del x, outs
+    good = [all(v for (n, _), v in ok.items() if n >= N) for N in QUANT_LENGTHS]
+    first = next((N for N, g in zip(QUANT_LENGTHS, good) if g), None)
+    out(f"# rule: the smallest probed row length from which, for it and every longer one, split <= the larger row median at every probed "
+        f"batch -> QUANTIZE_SPLIT_MIN_N = {first if first is not None else '2**62 (none: the default never splits)'}")
 
 
 def phases(args, dev, out):
@@ -167,7 +237,13 @@ def main():
     ap.add_argument("--replays", type=int, default=15)
     ap.add_argument("--quick", action="store_true", help="two shapes only")
     ap.add_argument("--phases", action="store_true", help="the int8 kernel and the image quantization alone (see the module's text)")
+    ap.add_argument("--quantizer", action="store_true", help="the image quantization alone, form=\"row\" against form=\"split\"")
+    ap.add_argument("--ways", default=",".join(WAYS), help="which of i8,float,decode the layer table times (i8 always)")
+    ap.add_argument("--tree", default=None, help="another checkout of this repository to take the package and its library from")
     args = ap.parse_args()
+    args.ways = ["i8"] + [w for w in args.ways.split(",") if w != "i8"]
+    if not set(args.ways) <= set(WAYS):
+        ap.error(f"--ways takes {WAYS}")
     dev = torch.device("cuda", torch.cuda.current_device())
     lines = []
 
@@ -181,8 +257,12 @@ def main():
     if args.phases:
         phases(args, dev, out)
         return
+    if args.quantizer:
+        quantizer(args, dev, out)
+        return
     out(f"# {torch.cuda.get_device_name(dev)}; device time per layer call: {args.chain} calls captured into one graph, {args.replays} timed "
-        f"replays per way, the three ways alternating; median (min .. max); us")
+        f"replays per way, the ways ({', '.join(args.ways)}) alternating; median (min .. max); us; package from "
+        f"{'--tree' if args.tree else 'this tree'}")
     for shape in (SHAPES[:1] + SHAPES[7:8] if args.quick else SHAPES):
         for M in (3, 16):
             measure(shape, M, args, dev, out)

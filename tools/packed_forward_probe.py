@@ -26,6 +26,13 @@ Also the file sizes of a VGG16-shaped Dense stack written by save_model and by e
 
     python tools/packed_forward_probe.py [--out profiles/packed_forward_tiled.txt] [--quick]
     python tools/packed_forward_probe.py --i8 --out profiles/packed_forward_i8.txt
+
+--i8-only: the fifth way alone, with hip.quantize_rows_i8 choosing its form (the row kernel, or from hip.QUANTIZE_SPLIT_MIN_N columns on
+the split form), the same shapes, batches and cache states.  --tree PATH: take the package (and its built library) from another
+checkout of this repository, e.g. the parent commit built in a scratch worktree; the two together, alternating between two trees, are
+the Dense table of profiles/packed_conv_i8_split.txt.
+
+    python tools/packed_forward_probe.py --i8-only [--tree ../parent] --out dense.txt
 """
 import argparse
 import os
@@ -36,7 +43,18 @@ import types
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+def _tree():
+    """--tree PATH, read before the package is imported."""
+    for i, a in enumerate(sys.argv):
+        if a == "--tree" and i + 1 < len(sys.argv):
+            return os.path.abspath(sys.argv[i + 1])
+        if a.startswith("--tree="):
+            return os.path.abspath(a[len("--tree="):])
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+
+
+sys.path.insert(0, _tree())
 from quantized_neural_networks_amd import deploy, hip, keras_shim as ks  # noqa: E402
 
 BATCHES = (1, 2, 4, 5, 8, 16, 32, 64, 128, 256)
@@ -78,6 +96,41 @@ def capture(fn, chain):
     g.replay()
     torch.cuda.synchronize()
     return g
+
+
+def measure_i8_only(label, N, C, M, args, dev, out):
+    """quantize + i8 alone: median (min .. max) per batch and cache state."""
+    rng = np.random.default_rng(N + M)
+    copies_rot = max(2, -(-(512 << 20) // (N * C * 4)))
+    layers = []
+    for _ in range(copies_rot):
+        unit, radii, Q = on_alphabet(rng, N, C, M, dev)
+        layers.append(deploy.pack_kernel(Q, radii, unit))
+        del Q
+    out(f"{label}: N={N} C={C} M={M}; rotated = {copies_rot} copies; quantize+i8 us per call, median (min .. max)")
+    for B in I8_BATCHES:
+        x = torch.randn((B, N), device=dev)
+        y = torch.empty((B, C), device=dev)
+        xq = (torch.empty((B, (N + 15) // 16 * 16), dtype=torch.int8, device=dev), torch.empty(B, device=dev))
+        cells = []
+        for ncopies in (1, copies_rot):
+            def f_i8(i):
+                p = layers[i % ncopies]
+                hip.quantize_rows_i8(x, out=xq)
+                hip.packed_dense_forward_i8(xq[0], p["codes"], p["bits"], p["zero_code"], p["radii"], M, N, out=y, scales=xq[1])
+
+            g = capture(f_i8, args.chain)
+            t = []
+            for _ in range(args.replays):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                g.replay()
+                b.record()
+                b.synchronize()
+                t.append(1e3 * a.elapsed_time(b) / args.chain)
+            cells.append(f"{np.median(t):8.2f} ({np.min(t):7.2f} ..{np.max(t):8.2f})")
+            del g
+        out(f"    B {B:5d}   same {cells[0]}   rotated {cells[1]}")
 
 
 def measure(label, N, C, M, args, dev, out):
@@ -167,6 +220,8 @@ def main():
     ap.add_argument("--replays", type=int, default=15)
     ap.add_argument("--quick", action="store_true", help="4096 x 4096 ternary only, no file sizes")
     ap.add_argument("--i8", action="store_true", help="a fifth way: row quantization + the int8 kernel, timed together; batches up to 1024")
+    ap.add_argument("--i8-only", action="store_true", help="row quantization + the int8 kernel alone (see the module's text)")
+    ap.add_argument("--tree", default=None, help="another checkout of this repository to take the package and its library from")
     args = ap.parse_args()
     dev = torch.device("cuda", torch.cuda.current_device())
     lines = []
@@ -174,13 +229,24 @@ def main():
     def out(s):
         print(s, flush=True)
         lines.append(s)
+        if args.i8_only and args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
 
-    out(f"# {torch.cuda.get_device_name(dev)}; device time per call: {args.chain} calls captured into one graph, {args.replays} timed replays "
-        f"per form, the {'five' if args.i8 else 'four'} forms alternating; median (min); us")
+    if args.i8_only:
+        out(f"# {torch.cuda.get_device_name(dev)}; device time per call: {args.chain} calls captured into one graph, {args.replays} timed "
+            f"replays; package from {'--tree' if args.tree else 'this tree'}")
+    else:
+        out(f"# {torch.cuda.get_device_name(dev)}; device time per call: {args.chain} calls captured into one graph, {args.replays} timed "
+            f"replays per form, the {'five' if args.i8 else 'four'} forms alternating; median (min); us")
     shapes = [("fc 4096 x 4096 ternary", 4096, 4096, 3)]
     if not args.quick:
         shapes += [("fc 4096 x 4096 16 levels", 4096, 4096, 16), ("VGG16 fc1 25088 x 4096 ternary", 25088, 4096, 3),
                    ("fc 4096 x 1000 ternary (63 column tiles)", 4096, 1000, 3)]
+    if args.i8_only:
+        for s in shapes:
+            measure_i8_only(*s, args, dev, out)
+        return
     results = [measure(*s, args, dev, out) for s in shapes]
     square, square_tiled = [w for w, _ in results[:2]], [t for _, t in results[:2]]
     both = [B for B in BATCHES if all(w[("same", B)] for w in square)]
