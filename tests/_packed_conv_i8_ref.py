@@ -35,6 +35,50 @@ def geometry(H, W, kh, kw, sh, sw, rh, rw, same):
     return (out_size(H, kh, sh, rh, same), out_size(W, kw, sw, rw, same), pad_before(H, kh, sh, rh, same), pad_before(W, kw, sw, rw, same))
 
 
+# Geometries (H, W, kh, kw, sh, sw, rh, rw, same) whose two image axes differ, so that an exchange of the axes' parameters anywhere
+# between the layer and the kernel changes the result (tests/test_packed_conv_i8_cpu.py proves which exchange each one sees; the GPU
+# file holds the kernel to them).  OH, OW and the pads are geometry()'s.
+A_RECT = (6, 9, 3, 3, 1, 1, 1, 1, True)               # OH 6 != OW 9
+A_STRIDE = (8, 9, 3, 3, 2, 1, 1, 1, True)             # sh != sw; OH 4, OW 9; pad_top 0, pad_left 1
+A_DIL = (7, 6, 3, 3, 1, 1, 2, 1, True)                # rh != rw; pads 2 and 1
+A_KERN = (6, 7, 2, 5, 1, 1, 1, 1, True)               # kh != kw, even kh; pads 0 (1 after) and 2
+A_EVEN = (5, 5, 4, 4, 1, 1, 1, 1, True)               # even kernel at stride 1: 1 before, 2 after
+A_VALID = (9, 8, 3, 2, 2, 1, 1, 2, False)             # VALID with 4 x 6 positions; stride and rate unequal
+A_1X1S2 = (7, 9, 1, 1, 2, 2, 1, 1, True)              # ResNet50's shortcut layer; OH 4, OW 5
+A_SKIP = (9, 13, 2, 2, 3, 3, 1, 1, False)             # stride beyond the kernel: pixels nobody reads; 3 x 4
+A_ALL = (10, 7, 3, 2, 2, 3, 2, 1, True)               # everything unequal; OH 5, OW 3; pads 1 and 0
+A_TALL = (20, 3, 17, 1, 1, 1, 1, 1, True)             # kw = 1, K = 17 Cin: with Cin = 1 every t of a piece is a new tap row
+UNEQUAL_AXES = dict(A_RECT=A_RECT, A_STRIDE=A_STRIDE, A_DIL=A_DIL, A_KERN=A_KERN, A_EVEN=A_EVEN, A_VALID=A_VALID, A_1X1S2=A_1X1S2,
+                    A_SKIP=A_SKIP, A_ALL=A_ALL, A_TALL=A_TALL)
+
+# A two-layer network on rectangular images, as (filters, geometry of the layer on its own input, activation): 9x12x3 ->
+# Conv2D(16, (3, 2), strides (2, 1), SAME, relu) -> 5x12x16 -> Conv2D(8, (2, 3), dilation (1, 2), VALID) -> 4x8x8.
+RECT_INPUT = (9, 12, 3)
+RECT_LAYERS = [(16, (9, 12, 3, 2, 2, 1, 1, 1, True), "relu"), (8, (5, 12, 2, 3, 1, 1, 1, 2, False), None)]
+RECT_M = 16
+
+
+def rect_kernels(seed=41):
+    """The network's kernels, drawn here so that both test files hold the same ones: per layer (codes int64 [K][F] in [0, M),
+    radii f64 [F], bias f32 [F], kernel shape)."""
+    rng = np.random.default_rng(seed)
+    out, cin = [], RECT_INPUT[2]
+    for F, (_, _, kh, kw, *_), _ in RECT_LAYERS:
+        K = kh * kw * cin
+        out.append((rng.integers(0, RECT_M, size=(K, F)).astype(np.int64), rng.uniform(0.5, 1.5, F),
+                    rng.uniform(-1.0, 1.0, F).astype(np.float32), (kh, kw, cin, F)))
+        cin = F
+    return out
+
+
+def float_conv_tolerance(absx, absW, kernel_shape, strides, dilation, same, bias):
+    """How far a float32 convolution may lie from the float64 one, per element [n][OH][OW][F]:
+    64 (K + 2) 2^-24 (sum_t |x_t| |w_t| + |bias|).  (K + 2) 2^-24 bounds a float32 sum of K products in any order plus the bias
+    add; 64 is room for a transform-based algorithm in the library underneath."""
+    K = kernel_shape[0] * kernel_shape[1] * kernel_shape[2]
+    return 64 * (K + 2) * 2.0 ** -24 * exact_conv(absx, absW, kernel_shape, strides, dilation, same, np.abs(bias))
+
+
 def patches(img, kh, kw, sh, sw, rh, rw, same):
     """img [n][H][W][Cin] (any numeric type) -> the patch matrix [n * OH * OW][kh * kw * Cin] of the same type, row
     p = (i OH + oh) OW + ow, column t = (ky kw + kx) Cin + c, zeros where the tap lies outside the image."""

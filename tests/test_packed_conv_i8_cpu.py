@@ -1,7 +1,7 @@
 """No GPU: the int8 packed Conv2D forward pass -- the NumPy restatement's patch gathering against an
 independent four-loop convolution on integers, its geometry against keras_shim's, its y against the float64 convolution within the
-derived bound, the argument checks of the C entry (before any launch: safe without a device), and deploy.load_packed's ``packed_conv``
-argument on the host."""
+derived bound, the argument checks of the C entry (before any launch: safe without a device), deploy.load_packed's ``packed_conv``
+argument on the host, and the proof that the unequal-axes geometries of the GPU file see every transposition of the two image axes."""
 import ctypes
 import json
 import os
@@ -26,6 +26,16 @@ GEOMETRIES = [
     (9, 8, 2, 3, 3, 2, 1, 2, 2, 1, False),          # ... VALID, and unequal axes
     (4, 5, 3, 2, 4, 5, 1, 1, 1, 1, False),          # VALID, the kernel equals the image: one output position
 ]
+# ... and every geometry the kernel is held to on unequal axes (tests/test_packed_conv_i8_gpu.py), with a small Cin and F
+GEOMETRIES += [g[:2] + cf + g[2:] for g, cf in zip(c8.UNEQUAL_AXES.values(), [(3, 2), (2, 3), (3, 3), (1, 4), (2, 2), (3, 2), (3, 3),
+                                                                              (1, 2), (2, 3), (1, 3)])]
+
+# The geometries (H, W, kh, kw, sh, sw, rh, rw, same) the GPU file ran the kernel on before the unequal-axes grid, by value: all
+# but G_ONE are their own mirror images, and G_ONE has a single output position.
+OLD_GPU_GEOMETRIES = dict(
+    G_1X1=(5, 5, 1, 1, 1, 1, 1, 1, True), G_3X3=(5, 5, 3, 3, 1, 1, 1, 1, True), G_S2=(8, 8, 3, 3, 2, 2, 1, 1, True),
+    G_7X7=(10, 10, 7, 7, 2, 2, 1, 1, True), G_DIL=(5, 5, 3, 3, 1, 1, 2, 2, True), G_ONE=(4, 5, 4, 5, 1, 1, 1, 1, False),
+    G_BIG=(3, 3, 5, 5, 1, 1, 1, 1, True))
 
 
 @pytest.fixture(scope="module")
@@ -68,8 +78,16 @@ def test_patch_gathering_equals_a_direct_convolution_on_integers(geom):
     assert want.size > 0 and np.array_equal(got.reshape(want.shape), want)
     if (H, W, kh, kw, same) == (4, 5, 4, 5, False):
         assert want.shape[1:3] == (1, 1)
-    if (H, kh, sh, same) == (8, 3, 2, True):
+    if (H, W, kh, sh, same) == (8, 8, 3, 2, True):
         assert c8.geometry(H, W, kh, kw, sh, sw, rh, rw, same) == (4, 4, 0, 0)      # total pad 1: nothing before, 1 after
+
+
+def test_unequal_axes_geometries_are_what_their_names_say():
+    """(OH, OW, pad_top, pad_left) of the unequal-axes geometries: the sizes and pads the two test files count on."""
+    want = dict(A_RECT=(6, 9, 1, 1), A_STRIDE=(4, 9, 0, 1), A_DIL=(7, 6, 2, 1), A_KERN=(6, 7, 0, 2), A_EVEN=(5, 5, 1, 1),
+                A_VALID=(4, 6, 0, 0), A_1X1S2=(4, 5, 0, 0), A_SKIP=(3, 4, 0, 0), A_ALL=(5, 3, 1, 0), A_TALL=(20, 3, 8, 0))
+    assert {name: c8.geometry(*g) for name, g in c8.UNEQUAL_AXES.items()} == want
+    assert [c8.geometry(*g)[:2] for _, g, _ in c8.RECT_LAYERS] == [(5, 12), (4, 8)] and c8.geometry(*c8.RECT_LAYERS[0][1])[2:] == (1, 0)
 
 
 def test_geometry_equals_keras_shim():
@@ -87,6 +105,80 @@ def test_geometry_equals_keras_shim():
                             assert c8.pad_before(size, k, s, d, True) == before <= after <= before + 1
                         else:
                             assert c8.pad_before(size, k, s, d, False) == 0
+
+
+def _gather(img, kh, kw, sh, sw, rh, rw, OH, OW, pad_top, pad_left, div):
+    """A plain gatherer with every parameter of the kernel's position and tap arithmetic explicit, `div` the divisor that splits a
+    position into (oh, ow): img [n][H][W][Cin] -> [n * OH * OW][kh * kw * Cin], zeros outside the image."""
+    n, H, W, Cin = img.shape
+    P = np.zeros((n, OH * OW, kh * kw, Cin), dtype=img.dtype)
+    for rem in range(OH * OW):
+        oh = rem // div
+        ow = rem - oh * div
+        for ky in range(kh):
+            for kx in range(kw):
+                ih, iw = oh * sh + ky * rh - pad_top, ow * sw + kx * rw - pad_left
+                if 0 <= ih < H and 0 <= iw < W:
+                    P[:, rem, ky * kw + kx, :] = img[:, ih, iw, :]
+    return P.reshape(n * OH * OW, kh * kw * Cin)
+
+
+def _gather_args(geom):
+    H, W, kh, kw, sh, sw, rh, rw, same = geom
+    OH, OW, pt, pl = c8.geometry(*geom)
+    after = lambda size, k, s, d, out, before: (max((out - 1) * s + (k - 1) * d + 1 - size, 0) - before) if same else 0
+    return dict(kh=kh, kw=kw, sh=sh, sw=sw, rh=rh, rw=rw, OH=OH, OW=OW, pad_top=pt, pad_left=pl, div=OW), \
+        (after(H, kh, sh, rh, OH, pt), after(W, kw, sw, rw, OW, pl))
+
+
+def _edits(geom):
+    """The five transpositions, each as the gatherer's arguments after it."""
+    a, (pad_bottom, pad_right) = _gather_args(geom)
+    return {"a: sh <-> sw": dict(a, sh=a["sw"], sw=a["sh"]),
+            "b: rh <-> rw": dict(a, rh=a["rw"], rw=a["rh"]),
+            "c: pad_top <-> pad_left": dict(a, pad_top=a["pad_left"], pad_left=a["pad_top"]),
+            "d: OH for OW in the decode": dict(a, div=a["OH"]),
+            "e: pad_after for pad_before": dict(a, pad_top=pad_bottom, pad_left=pad_right)}
+
+
+def test_geometries_tell_transposed_axes_apart():
+    """Why the unequal-axes geometries exist.  A transposition of the two image axes anywhere between the layer and the kernel --
+    (a) sh <-> sw, (b) rh <-> rw, (c) pad_top <-> pad_left, (d) a position decoded with OH where OW belongs, (e) pad_after taken for
+    pad_before -- changes the patch matrix of at least one of them, and of none of the geometries the kernel ran on before them:
+    those are their own mirror images or have one output position.  (e) is not a transposition, and the two old geometries with an
+    odd total pad, G_S2 and G_7X7, already see it.  The same five edits move the float64 result of the two layers of the
+    rectangular network (c8.RECT_LAYERS) by more than twice the tolerance the float route is held to on the GPU, so that margin
+    cannot let one through."""
+    rng = np.random.default_rng(19)
+    letters = "abcde"
+    seen = {}
+    for name, geom in {**OLD_GPU_GEOMETRIES, **c8.UNEQUAL_AXES}.items():
+        img = rng.integers(-127, 128, size=(2, geom[0], geom[1], 2)).astype(np.int64)
+        want = c8.patches(img, *geom[2:])
+        assert want.size > 0 and np.array_equal(_gather(img, **_gather_args(geom)[0]), want), name
+        seen[name] = "".join(l for l, args in zip(letters, _edits(geom).values()) if not np.array_equal(_gather(img, **args), want))
+    for name in OLD_GPU_GEOMETRIES:                                     # the old grid: blind to (a)-(d)
+        assert seen[name] == ("e" if name in ("G_S2", "G_7X7") else ""), (name, seen[name])
+    for l in letters:
+        assert any(l in seen[name] for name in c8.UNEQUAL_AXES), l
+    assert {name: seen[name] for name in c8.UNEQUAL_AXES} == dict(
+        A_RECT="d", A_STRIDE="acde", A_DIL="bcd", A_KERN="cde", A_EVEN="e", A_VALID="abd", A_1X1S2="d", A_SKIP="d", A_ALL="abcde",
+        A_TALL="cd")
+
+    # the float route of the rectangular network: each edit moves some element of a layer's float64 result by more than 2 tol
+    x = rng.standard_normal((5,) + c8.RECT_INPUT)
+    moved = {l: [] for l in letters}
+    for (F, geom, act), (codes, radii, bias, shape) in zip(c8.RECT_LAYERS, c8.rect_kernels()):
+        assert x.shape[1:3] == geom[:2] and shape[:2] == geom[2:4] and shape[2] == x.shape[3]
+        Wm = radii[None, :] * (2 * codes - (c8.RECT_M - 1)) / (c8.RECT_M - 1)
+        geo = (shape, geom[4:6], geom[6:8], geom[8])
+        y = c8.exact_conv(x, Wm, *geo, bias)
+        tol = c8.float_conv_tolerance(np.abs(x), np.abs(Wm), *geo, bias).reshape(-1, F)
+        assert np.array_equal((_gather(x, **_gather_args(geom)[0]) @ Wm + bias).reshape(y.shape), y)
+        for l, args in zip(letters, _edits(geom).values()):
+            moved[l].append(bool(np.any(np.abs(_gather(x, **args) @ Wm + bias - y.reshape(-1, F)) > 2 * tol)))
+        x = np.maximum(y, 0) if act == "relu" else y
+    assert moved == dict(a=[True, False], b=[False, True], c=[True, False], d=[True, True], e=[True, False])
 
 
 def _packed_kernel(rng, K, F, M, zeros):

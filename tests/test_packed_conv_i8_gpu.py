@@ -2,6 +2,7 @@
 packed_conv=True)) against the NumPy restatement of its contract (tests/_packed_conv_i8_ref.py).  The contract
 is bitwise -- the sums are integers, the epilogue two float64 products and one float32 add --, so everything here is tested to
 equality; only the distance to the float64 convolution with the exact weights has a bound, _packed_conv_i8_ref.error_bound's."""
+import json
 import os
 import sys
 
@@ -117,6 +118,64 @@ def test_product_beyond_one_workgroup_and_on_every_tier(hip, M, zeros):
     _case(hip, rng, M, zeros, 16, 17, 1, (182, 182, 1, 1, 1, 1, 1, 1, True), check_acc=False)        # 33124: MT = 2
     _case(hip, rng, M, zeros, 16, 17, 1, (257, 257, 1, 1, 1, 1, 1, 1, True), check_acc=False)        # 66049: MT = 4
     _case(hip, rng, M, zeros, 3, 5, 2, (183, 181, 1, 1, 1, 1, 1, 1, True), check_acc=False)          # 66246, general path
+    # 130 x 100 positions an image, sh != sw, pad_top 0 != pad_left 1: images straddle tiles and workgroups of the upper tiers
+    _case(hip, rng, M, zeros, 16, 17, 3, (260, 100, 3, 3, 2, 1, 1, 1, True), check_acc=False)        # 39000: MT = 2
+    _case(hip, rng, M, zeros, 16, 17, 6, (260, 100, 3, 3, 2, 1, 1, 1, True), check_acc=False)        # 78000: MT = 4
+
+
+# (Cin, F, n, geometry): every geometry of _packed_conv_i8_ref.UNEQUAL_AXES with a Cin of both paths; Cin = 1 and 2 (a 16-weight
+# piece of the general path walks 16 or 8 taps); Cin / 16 = 5 on the fast path's multiply-shift division
+UNEQUAL_GRID = [
+    (3, 17, 3, c8.A_RECT), (16, 17, 3, c8.A_RECT),
+    (3, 40, 3, c8.A_STRIDE), (32, 16, 3, c8.A_STRIDE),
+    (20, 17, 3, c8.A_DIL), (16, 40, 1, c8.A_DIL),
+    (3, 16, 3, c8.A_KERN), (48, 17, 3, c8.A_KERN),
+    (2, 17, 3, c8.A_EVEN), (16, 1, 3, c8.A_EVEN),
+    (3, 17, 3, c8.A_VALID), (32, 40, 3, c8.A_VALID),
+    (20, 17, 3, c8.A_1X1S2), (80, 16, 3, c8.A_1X1S2),
+    (1, 17, 3, c8.A_SKIP), (16, 17, 1, c8.A_SKIP),
+    (3, 40, 3, c8.A_ALL), (80, 17, 3, c8.A_ALL), (1, 1, 1, c8.A_ALL),
+    (1, 5, 2, c8.A_TALL), (16, 17, 2, c8.A_TALL),
+    (1, 17, 3, G_7X7), (2, 16, 3, G_3X3),
+]
+
+
+@pytest.mark.parametrize("M,zeros", ALPHABETS)
+def test_product_on_unequal_axes(hip, M, zeros):
+    """The kernel on geometries whose two image axes differ in size, kernel, stride, rate or pad (the position decode, S.sh / S.sw,
+    S.rh / S.rw, the host's pads and output sizes and the order of the binding's arguments; test_packed_conv_i8_cpu.py proves that
+    these geometries see each transposition), bit for bit."""
+    rng = np.random.default_rng(57 * M + zeros)
+    assert {c for c, _, _, _ in UNEQUAL_GRID} == {1, 2, 3, 20, 16, 32, 48, 80}
+    assert {f for _, f, _, _ in UNEQUAL_GRID} >= {1, 16, 17, 40}
+    for geom in c8.UNEQUAL_AXES.values():                               # both paths meet every geometry
+        assert {c % 16 == 0 for c, _, _, g in UNEQUAL_GRID if g == geom} == {True, False}, geom
+    for Cin, F, n, geom in UNEQUAL_GRID:
+        _case(hip, rng, M, zeros, Cin, F, n, geom)
+
+
+@pytest.mark.parametrize("M,zeros", ALPHABETS)
+def test_tiles_that_span_many_images(hip, M, zeros):
+    """One and three positions an image: a 16-position tile covers 16 and 5 to 6 images, so scales[p / plane] changes inside a tile
+    at every row or every third.  _case draws one scale per image; then scales = 1 .. n with unit radii, where y[i] is
+    (i + 1) acc[i] exactly."""
+    rng = np.random.default_rng(91 * M + zeros)
+    bits, zero_code, F = ref.packed_bits(M, int(zeros)), int(zeros), 17
+    for n, geom in ((70, (3, 3, 3, 3, 1, 1, 1, 1, False)), (37, (1, 3, 1, 1, 1, 1, 1, 1, True))):
+        H, W, kh, kw, sh, sw, rh, rw, same = geom
+        assert c8.geometry(*geom)[:2] == ((1, 1) if n == 70 else (1, 3))
+        for Cin in (3, 16):
+            _case(hip, rng, M, zeros, Cin, F, n, geom)
+            shape = (kh, kw, Cin, F)
+            packed = _codes(rng, kh * kw * Cin, F, bits)
+            xq_d, xq_h = _xq_view(rng, n, H, W, Cin)
+            scales = np.arange(1, n + 1).astype(np.float32)
+            acc, _ = c8.forward(xq_h, scales, packed, bits, zero_code, np.full(F, M - 1.0), M, shape, (sh, sw), (rh, rw), same)
+            assert np.abs(acc).max() * n < 2 ** 24                      # so every (i + 1) acc[i] is a float32
+            unit_radii = torch.full((F,), float(M - 1), dtype=torch.float64, device="cuda")
+            got = _run(hip, xq_d, _cuda(scales), _cuda(packed), bits, zero_code, unit_radii, M, shape, geom, None)
+            want = acc.astype(np.int64) * np.arange(1, n + 1).reshape(n, 1, 1, 1)
+            assert np.array_equal(got.astype(np.int64), want) and np.array_equal(got, want.astype(np.float32)), (M, zeros, Cin, n)
 
 
 def test_accumulator_range_at_a_real_layers_k(hip):
@@ -317,6 +376,85 @@ def test_packed_conv_layers_on_int8_activations(hip, tmp_path, monkeypatch, case
     assert c8.same_bits(net8.predict(xt, batch_size=7), y8)
     with pytest.raises(AssertionError, match="float kernel"):
         netf.predict(xt, batch_size=7)
+
+
+def _write_rect_file(path):
+    """An export_packed file of the rectangular network (_packed_conv_i8_ref.RECT_LAYERS), made by hand: the codes from the NumPy
+    restatement of the format, a linspace alphabet, random radii, a bias that is not zero."""
+    from quantized_neural_networks_amd import deploy, keras_shim as ks
+    layers = []
+    for k, (F, (_, _, kh, kw, sh, sw, rh, rw, same), act) in enumerate(c8.RECT_LAYERS):
+        layers.append(ks.Conv2D(F, (kh, kw), strides=(sh, sw), dilation_rate=(rh, rw), padding="same" if same else "valid",
+                                activation=act, name=f"r{k + 1}", **(dict(input_shape=c8.RECT_INPUT) if k == 0 else {})))
+    arrays = ks._arch_arrays(ks.Sequential(layers, device="cpu"))
+    arrays["__packed__"] = np.frombuffer(json.dumps(dict(version=deploy.FORMAT_VERSION)).encode("utf-8"), dtype=np.uint8)
+    bits = ref.packed_bits(c8.RECT_M, 0)
+    for k, (codes, radii, bias, shape) in enumerate(c8.rect_kernels()):
+        arrays[f"p{k}_codes"] = ref.pack(codes, bits, 0)
+        arrays[f"p{k}_radii"] = radii
+        arrays[f"p{k}_alphabet"] = np.linspace(-1, 1, c8.RECT_M)
+        arrays[f"p{k}_bits"] = np.int32(bits)
+        arrays[f"p{k}_zero_code"] = np.int32(0)
+        arrays[f"p{k}_shape"] = np.asarray(shape, dtype=np.int64)
+        arrays[f"p{k}_depthwise"] = np.int32(0)
+        arrays[f"w{k}_1"] = bias
+    ks._write_npz(arrays, str(path))
+    return str(path)
+
+
+def test_packed_layers_on_rectangular_images(hip, tmp_path):
+    """The layer, the load path and the shim on unequal axes: 9x12x3 images through Conv2D(16, (3, 2), strides (2, 1), SAME, relu)
+    and Conv2D(8, (2, 3), dilation (1, 2), VALID).  int8 route: every layer equals the restatement bit for bit.  packed_conv=True on
+    float32 activations: the default load bit for bit.  Default load (Conv2D.call, whose F.pad takes (left, right, top, bottom)):
+    every element within tol = 64 (K + 2) 2^-24 (sum_t |x_t| |w_t| + |bias|) of the float64 convolution of the same input --
+    (K + 2) 2^-24 bounds a float32 sum of K products and the bias in any order, 64 is room for a transform-based algorithm in the
+    library underneath; test_packed_conv_i8_cpu.py asserts that each transposition of the axes moves some element by more than
+    2 tol.  Measured on an MI355X: the worst error / tol is 9.2e-4 on r1 and 1.1e-4 on r2 (printed
+    here at every run)."""
+    from quantized_neural_networks_amd import deploy, keras_shim as ks
+    path = _write_rect_file(tmp_path / "rect.npz")
+    xt = np.random.default_rng(8).standard_normal((5,) + c8.RECT_INPUT).astype(np.float32)
+    plain = deploy.load_packed(path, device="cuda")
+    netf = deploy.load_packed(path, device="cuda", packed_conv=True)
+    net8 = deploy.load_packed(path, device="cuda", activations="int8", packed_conv=True)
+    assert [type(l) for l in plain.layers] == [ks.Conv2D] * 2
+    assert [type(l) for l in netf.layers] == [ks.PackedConv2D] * 2 and [l.route() for l in netf.layers] == ["decode"] * 2
+    assert [type(l) for l in net8.layers] == [ks.PackedConv2D] * 2 and [l.route() for l in net8.layers] == ["i8"] * 2
+    M = c8.RECT_M
+
+    # int8 activations: layer by layer against the restatement, each layer fed the previous layer's device output
+    inp = _cuda(xt)
+    for layer, (F, geom, act), (codes, radii, bias, shape) in zip(net8.layers, c8.RECT_LAYERS, c8.rect_kernels()):
+        p = layer.packed
+        assert tuple(layer.kernel_shape) == shape and tuple(inp.shape[1:3]) == geom[:2]
+        assert np.array_equal(p["codes"].cpu().numpy(), ref.pack(codes, p["bits"], 0)) and np.array_equal(p["radii"].cpu().numpy(), radii)
+        xq, scales = c8.quantize_images(inp.cpu().numpy())
+        _, want = c8.forward(xq, scales, ref.pack(codes, p["bits"], 0), p["bits"], 0, radii, M, shape, geom[4:6], geom[6:8], geom[8], bias)
+        out = layer.call(inp)
+        assert c8.same_bits(out.cpu().numpy(), ks._activation(act)(torch.from_numpy(want)).numpy()), layer.name
+        inp = out
+    assert tuple(inp.shape) == (5, 4, 8, 8) and c8.same_bits(net8.predict(xt, batch_size=5), inp.cpu().numpy())
+
+    # float32 activations on the packed layers: the default load, bit for bit
+    y_plain = plain.predict(xt, batch_size=5)
+    assert y_plain.shape == (5, 4, 8, 8) and c8.same_bits(netf.predict(xt, batch_size=5), y_plain)
+
+    # the default load against the float64 convolution of the same input, every element
+    inp = _cuda(xt)
+    for layer, (F, geom, act), (_, _, bias, shape) in zip(plain.layers, c8.RECT_LAYERS, c8.rect_kernels()):
+        kernel, b = layer.get_weights()
+        assert np.array_equal(b, bias) and kernel.shape == shape
+        x64, W64 = inp.cpu().numpy().astype(np.float64), kernel.astype(np.float64).reshape(-1, F)
+        geo = (shape, geom[4:6], geom[6:8], geom[8])
+        exact = c8.exact_conv(x64, W64, *geo, bias)
+        tol = c8.float_conv_tolerance(np.abs(x64), np.abs(W64), *geo, bias)
+        out = layer.call(inp)
+        want = ks._activation(act)(torch.from_numpy(exact)).numpy()
+        ratio = np.abs(out.cpu().numpy().astype(np.float64) - want) / tol
+        at = np.unravel_index(np.argmax(ratio), ratio.shape)
+        print(f"{layer.name}: worst error / tol = {ratio.max():.3g} at (image, oh, ow, filter) = {tuple(int(v) for v in at)}")
+        assert out.shape == exact.shape and np.all(ratio <= 1.0), (layer.name, at, float(ratio.max()))
+        inp = out
 
 
 def test_depthwise_layers_come_back_decoded_and_bad_alphabets_name_the_layer(hip, tmp_path):
