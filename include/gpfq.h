@@ -540,6 +540,55 @@ int gpfq_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, cons
                                   const float *bias, int64_t F, float *y, void *stream);
 
 /*
+ * The two int8 forward passes with a fused epilogue, and the quantizer that takes what it leaves.  Opt-in; bit
+ * for bit.  The entries above keep their contracts and their device code.
+ *
+ * gpfq_packed_dense_forward_i8_fused / gpfq_packed_conv2d_forward_i8_fused: the arguments of gpfq_packed_dense_forward_i8 up to ldy /
+ * of gpfq_packed_conv2d_forward_i8 up to y, with their meaning, checks, status codes and early returns, then relu and amax_bits.
+ *   acc, p and v = (float)p + bias[j] ((float)p without a bias) are exactly as defined above.  Then
+ *   y = (relu && v < 0) ? +0.0f : v: a NaN stays a NaN and -0.0f stays -0.0f.  relu other than 0 or 1: GPFQ_ERR_INVALID_ARG.
+ *   amax_bits may be NULL: no atomics then, and nothing else changes.  Otherwise amax_bits is [device] u32 [B] (Dense: one cell per
+ *   batch row) or [n] (Conv2D: one cell per image).  The call clears it asynchronously on `stream` and on completion
+ *       amax_bits[i] = max over the stored y of row / image i of (bits(y) & 0x7fffffff),
+ *   the bit pattern of |y| read as an unsigned integer: it orders every finite magnitude as the magnitudes themselves, and any Inf or NaN
+ *   among the row's / image's y puts the cell at or above 0x7f800000 -- the pattern gpfq_quantize_rows_i8 reduces.  Only elements that
+ *   are stored take part: nothing of rows at or beyond B, channels at or beyond C or F, or positions past the last output.
+ *   The maximum is taken inside a wavefront first; a wavefront then issues at most one agent-scope unsigned-max atomic without a return
+ *   value per row or image its tile touches (a Conv2D tile of 16 positions can straddle several images), and none where its maximum
+ *   is 0, which the cleared cell already holds.  An unsigned maximum does not depend on the order it is taken in: every call gives the
+ *   same bits in y and in amax_bits.  No workgroup waits for another; no workspace, no scratch, no host synchronisation; the call can be
+ *   captured into a graph.  amax_bits must not overlap y or any input.
+ *   The empty cases (B = 0 or C = 0; n = 0, F = 0 or an empty output) return GPFQ_OK as the unfused calls do; amax_bits, when given, is
+ *   still cleared when B / n is positive.  GPFQ_ERR_UNSUPPORTED also for B / n at or beyond 2^31 with amax_bits given.
+ *   Up to two operations on `stream`: the clear (when amax_bits is given) and one launch.
+ *
+ * gpfq_quantize_rows_i8_from_amax: gpfq_quantize_rows_i8 with the maximum supplied instead of searched.  Per row b, a = amax_bits[b]:
+ *   a >= 0x7f800000:                          scales[b] = NaN,  xq[b][:] = 0;
+ *   else amax = float-of-bits(a) < 2^-100:    scales[b] = 0.0f, xq[b][:] = 0;
+ *   else inv = 127.0f / amax, scales[b] = amax / 127.0f (float32 divisions, correctly rounded) and
+ *        xq[b][t] = (int8) clamp(rintf(x[b][t] * inv), -127, 127): one float32 product, rounded half to even, as above.
+ *   So when amax_bits[b] is the row's own pattern -- the maximum of bits(x[b][t]) & 0x7fffffff over t < N, what the fused forward passes
+ *   leave for the rows / images of their y -- xq, its pad bytes and scales equal gpfq_quantize_rows_i8's bit for bit.  The result is a
+ *   function of (x, amax_bits) whatever the caller passes: under a maximum below the row's the clamp acts (an infinite element gives
+ *   +-127), and a NaN element under a finite maximum gives 0.
+ *   Pad bytes, alignment rules, status codes and early returns are gpfq_quantize_rows_i8's (B = 0: GPFQ_OK and nothing done; N = 0 with
+ *   B > 0: the scales by the rule above, nothing of xq written); GPFQ_ERR_INVALID_ARG also for a NULL amax_bits with B > 0, and
+ *   GPFQ_ERR_UNSUPPORTED for N at or beyond 2^31 chunks.  x is read once: one workgroup per (row, chunk of gpfq_quantize_split_chunk()
+ *   floats) for every N, a short row being one chunk; ONE operation on `stream`, no workgroup waiting for another, without atomics,
+ *   workspace or host synchronisation.  amax_bits is only read; x, amax_bits, xq and scales must not overlap.
+ *     x, xq, scales as for gpfq_quantize_rows_i8; amax_bits [device] u32 [B].
+ */
+int gpfq_packed_dense_forward_i8_fused(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
+                                       int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
+                                       int64_t ldy, int relu, uint32_t *amax_bits, void *stream);
+int gpfq_packed_conv2d_forward_i8_fused(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                        int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw,
+                                        int same_padding, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                        const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits, void *stream);
+int gpfq_quantize_rows_i8_from_amax(const float *x, int64_t B, int64_t ldx, int64_t N, const uint32_t *amax_bits, int8_t *xq, int64_t ldq,
+                                    float *scales, void *stream);
+
+/*
  * Search over the alphabet scalar (a sequence as alphabet_scalar).  K candidate scalars s_0 .. s_{K-1}
  * (1 <= K <= GPFQ_SEARCH_MAX_CANDIDATES, each a finite positive number) are K * C independent columns of one walk with the unit
  * alphabet: candidate k of output channel j is column k * C + j (k-major: candidate k is a contiguous block of C columns).

@@ -878,14 +878,18 @@ int gpfq_packed_dense_forward_tiled(const float *x, int64_t B, int64_t ldx, cons
 
 typedef hipError_t (*QuantizeRowsLaunch)(const float *, int64_t, int64_t, int64_t, int8_t *, int64_t, float *, hipStream_t);
 
-// the checks, early returns and status codes of both quantizers of the activations (the row kernel, chunk = 0, and the split form,
-// whose chunks of a row must fit a grid dimension)
-static int quantize_rows_entry(const char *name, QuantizeRowsLaunch launch, int64_t chunk, const float *x, int64_t B, int64_t ldx, int64_t N,
-                               int8_t *xq, int64_t ldq, float *scales, void *stream)
+// the checks, early returns and status codes of the quantizers of the activations (the row kernel, chunk = 0, and the split forms,
+// whose chunks of a row must fit a grid dimension).  *nothing: an empty batch, the call is done.
+static int quantize_rows_args(int64_t chunk, const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales,
+                              bool *nothing)
 {
+    *nothing = false;
     if (B < 0 || N < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size B=%lld N=%lld", (long long)B, (long long)N);
     if (ldq % 16 != 0 || ldq < N) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldq=%lld must be a multiple of 16 and at least N=%lld", (long long)ldq, (long long)N);
-    if (B == 0) return GPFQ_OK;
+    if (B == 0) {
+        *nothing = true;
+        return GPFQ_OK;
+    }
     if (!scales) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (N > 0) {
         if (!x || !xq) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
@@ -894,6 +898,15 @@ static int quantize_rows_entry(const char *name, QuantizeRowsLaunch launch, int6
     }
     if (B > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "batch too long for one launch");
     if (chunk > 0 && N / chunk >= 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "row too long for one launch");
+    return GPFQ_OK;
+}
+
+static int quantize_rows_entry(const char *name, QuantizeRowsLaunch launch, int64_t chunk, const float *x, int64_t B, int64_t ldx, int64_t N,
+                               int8_t *xq, int64_t ldq, float *scales, void *stream)
+{
+    bool nothing;
+    int rc = quantize_rows_args(chunk, x, B, ldx, N, xq, ldq, scales, &nothing);
+    if (rc != GPFQ_OK || nothing) return rc;
     hipError_t e = launch(x, B, ldx, N, xq, ldq, scales, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
 }
@@ -911,30 +924,71 @@ int gpfq_quantize_rows_i8_split(const float *x, int64_t B, int64_t ldx, int64_t 
 
 int64_t gpfq_quantize_split_chunk(void) { return gpfq::quantize_split_chunk(); }
 
-int gpfq_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
-                                 int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
-                                 int64_t ldy, void *stream)
+int gpfq_quantize_rows_i8_from_amax(const float *x, int64_t B, int64_t ldx, int64_t N, const uint32_t *amax_bits, int8_t *xq, int64_t ldq,
+                                    float *scales, void *stream)
 {
+    bool nothing;
+    int rc = quantize_rows_args(gpfq::quantize_split_chunk(), x, B, ldx, N, xq, ldq, scales, &nothing);
+    if (rc != GPFQ_OK || nothing) return rc;
+    if (!amax_bits) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    hipError_t e = gpfq::launch_quantize_rows_i8_from_amax(x, B, ldx, N, amax_bits, xq, ldq, scales, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_quantize_rows_i8_from_amax");
+}
+
+// both int8 Dense entries: the checks, early returns and status codes are the unfused entry's; fused adds relu and amax_bits
+static int packed_dense_i8_entry(const char *name, bool fused, const int8_t *xq, int64_t B, int64_t ldq, const float *scales,
+                                 const uint8_t *packed, int bits, int zero_code, const double *radii, int M, const float *bias, int64_t N,
+                                 int64_t C, float *y, int64_t ldy, int relu, uint32_t *amax_bits, void *stream)
+{
+    if (relu != 0 && relu != 1) return fail(GPFQ_ERR_INVALID_ARG, "relu=%d: must be 0 or 1", relu);
     if (B < 0 || N < 0 || C < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size B=%lld N=%lld C=%lld", (long long)B, (long long)N, (long long)C);
     if (M < 2 || M > 64) return fail(GPFQ_ERR_INVALID_ARG, "the int8 forward pass takes linspace(-1, 1, M) of 2..64 members, got M=%d", M);
     if (N > GPFQ_PACKED_I8_MAX_N)
         return fail(GPFQ_ERR_INVALID_ARG, "N=%lld > GPFQ_PACKED_I8_MAX_N=%d: the int32 sums could overflow", (long long)N, GPFQ_PACKED_I8_MAX_N);
     bool nothing;
     int rc = packed_forward_args(xq, "ldq", ldq, B, packed, bits, zero_code, radii, M, N, C, y, ldy, &nothing);
-    if (rc != GPFQ_OK || nothing) return rc;
+    if (rc != GPFQ_OK) return rc;
+    if (B > 2147483647LL && amax_bits) return fail(GPFQ_ERR_UNSUPPORTED, "batch too long for one clear of amax_bits");
+    if (nothing) {                                  // an empty layer still leaves its rows' cells cleared
+        if (amax_bits && B > 0) {
+            hipError_t e = gpfq::launch_amax_clear(amax_bits, B, static_cast<hipStream_t>(stream));
+            if (e != hipSuccess) return hip_fail(e, name);
+        }
+        return GPFQ_OK;
+    }
     if (!scales) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (ldq % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "row pitch ldq=%lld must be a multiple of 16", (long long)ldq);
     if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
-    hipError_t e = gpfq::launch_packed_dense_forward_i8(xq, B, ldq, scales, packed, bits, zero_code, radii, M, bias, N, C, y, ldy,
-                                                        static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_packed_dense_forward_i8");
+    hipError_t e = fused ? gpfq::launch_packed_dense_forward_i8_fused(xq, B, ldq, scales, packed, bits, zero_code, radii, M, bias, N, C, y,
+                                                                      ldy, relu, amax_bits, static_cast<hipStream_t>(stream))
+                         : gpfq::launch_packed_dense_forward_i8(xq, B, ldq, scales, packed, bits, zero_code, radii, M, bias, N, C, y, ldy,
+                                                                static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
 }
 
-int gpfq_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
-                                  int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
-                                  const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
-                                  const float *bias, int64_t F, float *y, void *stream)
+int gpfq_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
+                                 int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
+                                 int64_t ldy, void *stream)
 {
+    return packed_dense_i8_entry("gpfq_packed_dense_forward_i8", false, xq, B, ldq, scales, packed, bits, zero_code, radii, M, bias, N, C, y,
+                                 ldy, 0, nullptr, stream);
+}
+
+int gpfq_packed_dense_forward_i8_fused(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
+                                       int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
+                                       int64_t ldy, int relu, uint32_t *amax_bits, void *stream)
+{
+    return packed_dense_i8_entry("gpfq_packed_dense_forward_i8_fused", true, xq, B, ldq, scales, packed, bits, zero_code, radii, M, bias, N,
+                                 C, y, ldy, relu, amax_bits, stream);
+}
+
+// both int8 Conv2D entries, as packed_dense_i8_entry
+static int packed_conv_i8_entry(const char *name, bool fused, const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
+                                const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits, void *stream)
+{
+    if (relu != 0 && relu != 1) return fail(GPFQ_ERR_INVALID_ARG, "relu=%d: must be 0 or 1", relu);
     if (n < 0 || F < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size n=%lld F=%lld", (long long)n, (long long)F);
     if (H <= 0 || W <= 0 || Cin <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad image shape H=%lld W=%lld Cin=%lld", (long long)H, (long long)W, (long long)Cin);
     if (kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || rh <= 0 || rw <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad kernel/stride/rate");
@@ -951,7 +1005,14 @@ int gpfq_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, cons
                     zero_code ? " and the literal zero" : "", gpfq::packed_bits(M, zero_code));
     if (ldq % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld must be a multiple of 16", (long long)ldq);
     const int64_t oh = gpfq_patch_out_dim(H, kh, sh, rh, same_padding), ow = gpfq_patch_out_dim(W, kw, sw, rw, same_padding);
-    if (n == 0 || F == 0 || oh == 0 || ow == 0) return GPFQ_OK;
+    if (n > 2147483647LL && amax_bits) return fail(GPFQ_ERR_UNSUPPORTED, "too many images for one clear of amax_bits");
+    if (n == 0 || F == 0 || oh == 0 || ow == 0) {   // an empty layer still leaves its images' cells cleared
+        if (amax_bits && n > 0) {
+            hipError_t e = gpfq::launch_amax_clear(amax_bits, n, static_cast<hipStream_t>(stream));
+            if (e != hipSuccess) return hip_fail(e, name);
+        }
+        return GPFQ_OK;
+    }
     // what the kernel indexes with 32 bits: a place inside an image, a position, a tap's row and column
     const int64_t limit = 1LL << 24, keh = kh + (int64_t)(kh - 1) * (rh - 1), kew = kw + (int64_t)(kw - 1) * (rw - 1);
     if (H > limit || W > limit || sh > limit || sw > limit || keh > limit || kew > limit || H * W > 2147483647LL / Cin)
@@ -974,9 +1035,29 @@ int gpfq_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, cons
         S.pad_top = (int)(th / 2);
         S.pad_left = (int)(tw / 2);
     }
-    hipError_t e = gpfq::launch_packed_conv2d_forward_i8(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y,
-                                                         static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_packed_conv2d_forward_i8");
+    hipError_t e = fused ? gpfq::launch_packed_conv2d_forward_i8_fused(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y,
+                                                                       relu, amax_bits, static_cast<hipStream_t>(stream))
+                         : gpfq::launch_packed_conv2d_forward_i8(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y,
+                                                                 static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
+}
+
+int gpfq_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                  int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
+                                  const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                  const float *bias, int64_t F, float *y, void *stream)
+{
+    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8", false, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw, rh, rw, same_padding,
+                                packed, bits, zero_code, radii, M, bias, F, y, 0, nullptr, stream);
+}
+
+int gpfq_packed_conv2d_forward_i8_fused(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                        int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw,
+                                        int same_padding, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                        const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits, void *stream)
+{
+    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_fused", true, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw, rh, rw,
+                                same_padding, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
 }
 
 int gpfq_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii, const float *layer_median,

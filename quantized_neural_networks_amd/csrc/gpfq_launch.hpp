@@ -348,11 +348,20 @@ hipError_t launch_quantize_rows_i8(const float *x, int64_t B, int64_t ldx, int64
 hipError_t launch_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed, int bits,
                                           int zero_code, const double *radii, int M, const float *bias, int64_t N, int64_t C, float *y,
                                           int64_t ldy, hipStream_t stream);
+// the same with the fused epilogue: an optional ReLU and, where amax_bits is given, a clear of its B cells
+// followed by the rows' maxima of bits(y) & 0x7fffffff; launch_amax_clear is that clear (the Conv2D launcher and the entries use it)
+hipError_t launch_amax_clear(uint32_t *amax_bits, int64_t cells, hipStream_t stream);
+hipError_t launch_packed_dense_forward_i8_fused(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed,
+                                                int bits, int zero_code, const double *radii, int M, const float *bias, int64_t N,
+                                                int64_t C, float *y, int64_t ldy, int relu, uint32_t *amax_bits, hipStream_t stream);
 // gpfq_quantize_split.hip (addendum): launch_quantize_rows_i8's result bit for bit with a row spread over
 // workgroups of quantize_split_chunk() floats each -- a clear of scales and three launches, scales holding the rows' maxima in between
 int64_t quantize_split_chunk();
 hipError_t launch_quantize_rows_i8_split(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales,
                                          hipStream_t stream);
+// the split form's quantizing step alone, the rows' maxima supplied (gpfq_quantize_rows_i8_from_amax): one launch
+hipError_t launch_quantize_rows_i8_from_amax(const float *x, int64_t B, int64_t ldx, int64_t N, const uint32_t *amax_bits, int8_t *xq,
+                                             int64_t ldq, float *scales, hipStream_t stream);
 // gpfq_packed_conv_i8.hip: the Conv2D forward pass of int8 NHWC images with the kernel [kh*kw*Cin][F] held as
 // packed rows, an implicit GEMM on the same instruction (rows: the n*OH*OW output positions; no patch matrix).  The geometry as the
 // entry resolved it: output size and the pads before (TensorFlow's SAME split), every field checked to fit what the kernel indexes with.
@@ -362,6 +371,10 @@ struct ConvI8Shape {
 hipError_t launch_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
                                            const uint8_t *packed, int bits, int zero_code, const double *radii, int M, const float *bias,
                                            int64_t F, float *y, hipStream_t stream);
+hipError_t launch_packed_conv2d_forward_i8_fused(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
+                                                 const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                                 const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits,
+                                                 hipStream_t stream);
 // gpfq_search.hip (a sequence as alphabet_scalar): the K candidate scalars travel by value
 constexpr int kSearchMaxK = 16;
 struct SearchScalars {

@@ -26,11 +26,17 @@
 //       general (any Cin)      pieces straddle taps: 16 byte reads, each at its own (ky, kx, c), stepped from the piece's first.
 //   Both form the same integers.  Bytes of A at t >= K are zeros, so what the pad codes decode to does not matter.
 //
+//   gpfq_packed_conv_i8_kernel<BITS, MT, FAST, FusedStore>   (gpfq_packed_conv2d_forward_i8_fused)
+//       The same kernel with the fused epilogue compiled in: an optional ReLU on the value about to be stored and, per image, the
+//       maximum of the stored values' bit patterns of |y| for the next layer's quantizer.  With PlainStore (the unfused entry) none
+//       of the epilogue's code or arguments exists in the kernel.
+//
 //   Tiers.  MT = 1, 2, 4 position tiles per wavefront on the fast path, from the position count alone (conv_tier below); the general
 //   path has MT = 1 only.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/gpfq.h"
 #include "gpfq_device.hpp"
@@ -75,11 +81,11 @@ struct ConvI8Args {
     unsigned cin16_magic, kw_magic;                 // div_magic(Cin / 16), div_magic(kw): the fast path's
 };
 
-template <int BITS, int MT, bool FAST>
+template <int BITS, int MT, bool FAST, class EPI = PlainStore>
 __global__ void __launch_bounds__(kMfmaThreads)
 gpfq_packed_conv_i8_kernel(const int8_t *__restrict__ xq, int64_t ldq, const float *__restrict__ scales, const ConvI8Args A,
                            const uint8_t *__restrict__ packed, int64_t pitch, int zero_code, const double *__restrict__ radii, int M,
-                           const float *__restrict__ bias, int64_t F, float *__restrict__ y)
+                           const float *__restrict__ bias, int64_t F, float *__restrict__ y, EPI epi)
 {
     constexpr int W = packed_group_weights(BITS), NB = W / 16;       // weights and B operands per group
     const ConvI8Shape &S = A.S;
@@ -187,37 +193,86 @@ gpfq_packed_conv_i8_kernel(const int8_t *__restrict__ xq, int64_t ldq, const flo
     }
 
     // the Dense epilogue, the scale taken per row: a tile's 16 positions can lie in two images
-    if (j >= F) return;
-    const double unit = radii[j] / (double)(M - 1);
-    const float bj = bias ? bias[j] : 0.f;
+    if constexpr (!EPI::fused) {
+        if (j >= F) return;
+        const double unit = radii[j] / (double)(M - 1);
+        const float bj = bias ? bias[j] : 0.f;
 #pragma unroll
-    for (int m = 0; m < MT; ++m)
+        for (int m = 0; m < MT; ++m)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int p = p0 + 16 * m + 4 * h + g;
-            if (p < A.P) {
-                const double pr = ((double)acc[m][g] * (double)scales[p / plane]) * unit;
-                const float v = (float)pr;
-                y[(int64_t)p * F + j] = bias ? v + bj : v;
+            for (int g = 0; g < 4; ++g) {
+                const int p = p0 + 16 * m + 4 * h + g;
+                if (p < A.P) {
+                    const double pr = ((double)acc[m][g] * (double)scales[p / plane]) * unit;
+                    const float v = (float)pr;
+                    y[(int64_t)p * F + j] = bias ? v + bj : v;
+                }
             }
+    } else {
+        // The fused epilogue: no lane leaves before the shuffles.  top[m][g]: the bit pattern of |y| of what this lane stored, 0 (the
+        // identity of an unsigned maximum) for a masked filter lane or a position past the last.
+        const bool live = j < F;
+        const double unit = live ? radii[j] / (double)(M - 1) : 0.0;
+        const float bj = (live && bias) ? bias[j] : 0.f;
+        unsigned top[MT][4];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int p = p0 + 16 * m + 4 * h + g;
+                top[m][g] = 0u;
+                if (live && p < A.P) {
+                    const double pr = ((double)acc[m][g] * (double)scales[p / plane]) * unit;
+                    const float v = (float)pr;
+                    float out = bias ? v + bj : v;
+                    if (epi.relu && out < 0.f) out = 0.f;               // (a NaN and -0.0 are not below zero: they stay)
+                    y[(int64_t)p * F + j] = out;
+                    top[m][g] = __float_as_uint(out) & 0x7fffffffu;
+                }
+            }
+        if (!epi.amax) return;                      // (uniform over the grid)
+        // The wavefront's 16 MT positions are consecutive: they lie in the images first .. last, usually one, as many as 16 MT when
+        // an image is one position.  Per image: the lane's maximum over its positions inside it, six shuffle steps across the
+        // wavefront, at most one atomic without a return value from lane 0 (raise_cell) -- none where the maximum is 0, which the
+        // cleared cell already holds.
+        const int pend = p0 + 16 * MT < A.P ? p0 + 16 * MT : A.P;
+        const int first = p0 / plane, last = (pend - 1) / plane;
+        for (int i = first; i <= last; ++i) {       // (wave-uniform bounds)
+            const int lo = i * plane, hi = lo + plane;
+            unsigned t = 0u;
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int p = p0 + 16 * m + 4 * h + g;
+                    if (p >= lo && p < hi) t = umax(t, top[m][g]);
+                }
+            for (int sft = 32; sft >= 1; sft >>= 1) t = umax(t, (unsigned)__shfl_xor((int)t, sft, 64));
+            if (lane == 0 && t != 0u) raise_cell(epi.amax + i, t);
         }
+    }
 }
 
-template <int BITS, int MT, bool FAST>
+template <int BITS, int MT, bool FAST, bool FUSED>
 hipError_t launch_conv_i8(const int8_t *xq, int64_t ldq, const float *scales, const ConvI8Args &A, const PackedLayer &L, int M, float *y,
-                          hipStream_t stream)
+                          int relu, unsigned *amax, hipStream_t stream)
 {
     const int64_t pblocks = ((int64_t)A.P + conv_block_positions(MT) - 1) / conv_block_positions(MT);
-    hipLaunchKernelGGL((gpfq_packed_conv_i8_kernel<BITS, MT, FAST>), dim3((unsigned)(pblocks * A.ftiles)), dim3(kMfmaThreads), 0, stream,
-                       xq, ldq, scales, A, L.packed, L.pitch, L.zero_code, L.radii, M, L.bias, L.C, y);
+    using EPI = std::conditional_t<FUSED, FusedStore, PlainStore>;
+    EPI epi;
+    if constexpr (FUSED) {
+        epi.relu = relu;
+        epi.amax = amax;
+    }
+    hipLaunchKernelGGL((gpfq_packed_conv_i8_kernel<BITS, MT, FAST, EPI>), dim3((unsigned)(pblocks * A.ftiles)), dim3(kMfmaThreads), 0, stream,
+                       xq, ldq, scales, A, L.packed, L.pitch, L.zero_code, L.radii, M, L.bias, L.C, y, epi);
     return hipGetLastError();
 }
 
-}  // namespace
-
-hipError_t launch_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
-                                           const uint8_t *packed, int bits, int zero_code, const double *radii, int M, const float *bias,
-                                           int64_t F, float *y, hipStream_t stream)
+template <bool FUSED>
+hipError_t launch_conv_i8_any(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
+                              const uint8_t *packed, int bits, int zero_code, const double *radii, int M, const float *bias,
+                              int64_t F, float *y, int relu, unsigned *amax, hipStream_t stream)
 {
     ConvI8Args A;
     A.S = S;
@@ -233,10 +288,31 @@ hipError_t launch_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t 
     return packed_dispatch(bits, fast ? conv_tier(A.P) : 1, [&](auto width, auto tier) {
         constexpr int BITS = decltype(width)::value, MT = decltype(tier)::value;
         if constexpr (MT == 1) {
-            if (!fast) return launch_conv_i8<BITS, 1, false>(xq, ldq, scales, A, L, M, y, stream);
+            if (!fast) return launch_conv_i8<BITS, 1, false, FUSED>(xq, ldq, scales, A, L, M, y, relu, amax, stream);
         }
-        return launch_conv_i8<BITS, MT, true>(xq, ldq, scales, A, L, M, y, stream);
+        return launch_conv_i8<BITS, MT, true, FUSED>(xq, ldq, scales, A, L, M, y, relu, amax, stream);
     });
+}
+
+}  // namespace
+
+hipError_t launch_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
+                                           const uint8_t *packed, int bits, int zero_code, const double *radii, int M, const float *bias,
+                                           int64_t F, float *y, hipStream_t stream)
+{
+    return launch_conv_i8_any<false>(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y, 0, nullptr, stream);
+}
+
+hipError_t launch_packed_conv2d_forward_i8_fused(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
+                                                 const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                                 const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits,
+                                                 hipStream_t stream)
+{
+    if (amax_bits) {
+        hipError_t e = launch_amax_clear(amax_bits, n, stream);
+        if (e != hipSuccess) return e;
+    }
+    return launch_conv_i8_any<true>(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
 }
 
 }  // namespace gpfq

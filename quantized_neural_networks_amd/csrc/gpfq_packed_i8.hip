@@ -25,9 +25,20 @@
 //   (decode4); at 2 bits the four possible weights are one register and a byte permute with the codes as its selector looks them up.
 //   Weights at or beyond N (the pad codes) are masked to zero, so what xq holds there does not matter; pieces at or beyond N are not
 //   read.  Rows at or beyond B read row B - 1, channels at or beyond C row C - 1; nothing of theirs is stored.
+//
+//   gpfq_packed_dense_i8_kernel<BITS, MT, FusedStore>   (gpfq_packed_dense_forward_i8_fused)
+//       The same kernel with the fused epilogue compiled in: an optional ReLU on the value about to be stored, and the
+//       maximum of the stored values' bit patterns of |y| per batch row, for the quantizer of the next layer.  After the LDS sum a
+//       thread holds channel l & 15 of batch row 4 (l >> 4) + wave of a row tile: the 16 lanes of a quarter hold 16 channels of ONE
+//       row, so four shuffle steps inside the quarter leave the row's maximum over this column tile in every lane of it, and the
+//       quarter's first lane sends one atomic max without a return value -- at most one per wavefront and row (raise_cell: none
+//       where a load shows the cell to be as large already).  An element that is not stored enters as 0, the identity of an unsigned
+//       maximum; a quarter whose maximum is 0 sends nothing (the cell was cleared).
+//       With PlainStore (the unfused entry) none of the epilogue's code or arguments exists in the kernel.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "gpfq_device.hpp"
 #include "gpfq_launch.hpp"
@@ -84,11 +95,19 @@ gpfq_quantize_rows_i8_kernel(const float *__restrict__ x, int64_t ldx, int64_t N
     }
 }
 
-template <int BITS, int MT>
+// the cells of the fused epilogues' maxima, one thread per cell: 0, the identity of an unsigned maximum
+__global__ void __launch_bounds__(kQuantThreads)
+gpfq_amax_clear_kernel(unsigned *__restrict__ cells, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * kQuantThreads + threadIdx.x;
+    if (i < n) cells[i] = 0u;
+}
+
+template <int BITS, int MT, class EPI = PlainStore>
 __global__ void __launch_bounds__(kMfmaThreads)
 gpfq_packed_dense_i8_kernel(const int8_t *__restrict__ xq, int64_t B, int64_t ldq, const float *__restrict__ scales,
                             const uint8_t *__restrict__ packed, int64_t pitch, int zero_code, const double *__restrict__ radii, int M,
-                            const float *__restrict__ bias, int N, int64_t C, float *__restrict__ y, int64_t ldy)
+                            const float *__restrict__ bias, int N, int64_t C, float *__restrict__ y, int64_t ldy, EPI epi)
 {
     constexpr int W = packed_group_weights(BITS), NB = W / 16;       // weights and B operands per group
     constexpr int R = mfma_pass_rows(MT);
@@ -168,24 +187,46 @@ gpfq_packed_dense_i8_kernel(const int8_t *__restrict__ xq, int64_t B, int64_t ld
 #pragma unroll
             for (int w = 0; w < kMfmaWaves; ++w) s += red[((w * MT + m) * 4 + wave) * 64 + lane];
             const int64_t b = b0 + m * 16 + 4 * h + wave;             // (this thread sums register `wave` of every partial tile)
-            if (j < C && b < B) {
-                const double p = ((double)s * (double)scales[b]) * unit;
-                const float v = (float)p;
-                y[b * ldy + j] = bias ? v + bias[j] : v;
+            if constexpr (!EPI::fused) {
+                if (j < C && b < B) {
+                    const double p = ((double)s * (double)scales[b]) * unit;
+                    const float v = (float)p;
+                    y[b * ldy + j] = bias ? v + bias[j] : v;
+                }
+            } else {
+                unsigned top = 0u;                  // (what is not stored does not raise a maximum)
+                if (j < C && b < B) {
+                    const double p = ((double)s * (double)scales[b]) * unit;
+                    const float v = (float)p;
+                    float out = bias ? v + bias[j] : v;
+                    if (epi.relu && out < 0.f) out = 0.f;               // (a NaN and -0.0 are not below zero: they stay)
+                    y[b * ldy + j] = out;
+                    top = __float_as_uint(out) & 0x7fffffffu;
+                }
+                if (epi.amax) {                     // (uniform over the grid)
+                    for (int sft = 8; sft >= 1; sft >>= 1) top = umax(top, (unsigned)__shfl_xor((int)top, sft, 64));
+                    if (r == 0 && top != 0u) raise_cell(epi.amax + b, top);  // (top != 0 only where b < B)
+                }
             }
         }
     }
 }
 
-template <int BITS, int MT>
+template <int BITS, int MT, bool FUSED>
 hipError_t launch_i8_mt(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const PackedLayer &L, int M, const PackedOut &out,
-                        hipStream_t stream)
+                        int relu, unsigned *amax, hipStream_t stream)
 {
     const int64_t blocks = (L.C + kMfmaChannels - 1) / kMfmaChannels;
     int64_t passes = (B + mfma_pass_rows(MT) - 1) / mfma_pass_rows(MT);
     if (passes > 65535) passes = 65535;
-    hipLaunchKernelGGL((gpfq_packed_dense_i8_kernel<BITS, MT>), dim3((unsigned)blocks, (unsigned)passes), dim3(kMfmaThreads), 0, stream,
-                       xq, B, ldq, scales, L.packed, L.pitch, L.zero_code, L.radii, M, L.bias, (int)L.N, L.C, out.y, out.ldy);
+    using EPI = std::conditional_t<FUSED, FusedStore, PlainStore>;
+    EPI epi;
+    if constexpr (FUSED) {
+        epi.relu = relu;
+        epi.amax = amax;
+    }
+    hipLaunchKernelGGL((gpfq_packed_dense_i8_kernel<BITS, MT, EPI>), dim3((unsigned)blocks, (unsigned)passes), dim3(kMfmaThreads), 0, stream,
+                       xq, B, ldq, scales, L.packed, L.pitch, L.zero_code, L.radii, M, L.bias, (int)L.N, L.C, out.y, out.ldy, epi);
     return hipGetLastError();
 }
 
@@ -205,7 +246,31 @@ hipError_t launch_packed_dense_forward_i8(const int8_t *xq, int64_t B, int64_t l
     const PackedLayer L(packed, bits, zero_code, radii, bias, N, C);
     const PackedOut out{y, ldy};
     return packed_dispatch(bits, mfma_tier(B), [&](auto width, auto tier) {
-        return launch_i8_mt<decltype(width)::value, decltype(tier)::value>(xq, B, ldq, scales, L, M, out, stream);
+        return launch_i8_mt<decltype(width)::value, decltype(tier)::value, false>(xq, B, ldq, scales, L, M, out, 0, nullptr, stream);
+    });
+}
+
+// (a kernel, not hipMemsetAsync, as the split quantizer's clear and for its reason -- DESIGN.md section 11b, addendum: replayed from a
+//  captured graph the memset node left cells that were not zero)
+hipError_t launch_amax_clear(uint32_t *amax_bits, int64_t cells, hipStream_t stream)
+{
+    hipLaunchKernelGGL(gpfq_amax_clear_kernel, dim3((unsigned)((cells + kQuantThreads - 1) / kQuantThreads)), dim3(kQuantThreads), 0, stream,
+                       amax_bits, cells);
+    return hipGetLastError();
+}
+
+hipError_t launch_packed_dense_forward_i8_fused(const int8_t *xq, int64_t B, int64_t ldq, const float *scales, const uint8_t *packed,
+                                                int bits, int zero_code, const double *radii, int M, const float *bias, int64_t N,
+                                                int64_t C, float *y, int64_t ldy, int relu, uint32_t *amax_bits, hipStream_t stream)
+{
+    if (amax_bits) {
+        hipError_t e = launch_amax_clear(amax_bits, B, stream);
+        if (e != hipSuccess) return e;
+    }
+    const PackedLayer L(packed, bits, zero_code, radii, bias, N, C);
+    const PackedOut out{y, ldy};
+    return packed_dispatch(bits, mfma_tier(B), [&](auto width, auto tier) {
+        return launch_i8_mt<decltype(width)::value, decltype(tier)::value, true>(xq, B, ldq, scales, L, M, out, relu, amax_bits, stream);
     });
 }
 

@@ -1,7 +1,8 @@
 // What the two units on the i8 matrix instruction share (gpfq_packed_i8.hip: Dense; gpfq_packed_conv_i8.hip: Conv2D): packed codes ->
 // int8 B operands of v_mfma_i32_16x16x64_i8 by register arithmetic.  The weight of code c is 2 (c - zero_code) - (M - 1) where
 // zero_code <= c < zero_code + M, else 0 (include/gpfq.h).  And what the two quantizers of the activations share (gpfq_packed_i8.hip:
-// a workgroup per row; gpfq_quantize_split.hip: a workgroup per chunk of a row): one element -> its int8.
+// a workgroup per row; gpfq_quantize_split.hip: a workgroup per chunk of a row): one element -> its int8.  And the two epilogues of
+// the forward kernels: the plain store, and the fused one of DESIGN.md section 11c.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +18,28 @@ __device__ inline int8_t quantize_one(float v, float inv)
     float q = rintf(v * inv);                       // one float32 product, then round half to even
     q = q < -127.f ? -127.f : (q > 127.f ? 127.f : q);
     return (int8_t)(int)q;
+}
+
+// What a forward kernel does with a value about to be stored, as its last template argument and -- by value
+// -- its last argument.  PlainStore is empty: the kernel compiled with it holds none of the fused epilogue's code.
+struct PlainStore {
+    static constexpr bool fused = false;
+};
+struct FusedStore {
+    static constexpr bool fused = true;
+    int relu;                                       // 0 / 1: values below zero are stored as +0.0f
+    unsigned *amax;                                 // cells for the rows' / images' maxima of bits(y) & 0x7fffffff, cleared; or NULL
+};
+
+__device__ inline unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
+
+// One wavefront's maximum `top` into its row's / image's cell: an agent-scope unsigned-max atomic without a return value -- unless a
+// load shows the cell to be at least as large already.  The maximum only grows, so a stale value read here can only cause an atomic
+// that was not needed, never lose one; the load (agent scope: past the compute unit's own cache) is what keeps the thousands of
+// wavefronts of one image from queueing on one address: after the first few, most find a cell their maximum does not raise.
+__device__ inline void raise_cell(unsigned *cell, unsigned top)
+{
+    if (top > __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(cell, top);
 }
 
 // What turns codes into weights, one copy in every byte: the first code of a member, the first code past the members, and

@@ -14,6 +14,9 @@
 // A thread owns groups of four consecutive floats (one word of xq), a wavefront 64 consecutive groups.  Where the row starts on a
 // 16-byte boundary a group wholly below N is one 16-byte read, otherwise (and in the group that straddles N) element reads: the same
 // integers either way.  x is read twice; the second read meets the caches.  Rows go on grid.y with a stride loop.
+//
+//   gpfq_from_amax_kernel       (gpfq_quantize_rows_i8_from_amax) the quantizing step on maxima the caller supplies, the scales
+//                               written by the first chunk of a row: one launch, x read once.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -43,8 +46,6 @@ __device__ inline float4 load_group(const float *row, int64_t t, int64_t N, bool
     if (t + 3 < N) v.w = row[t + 3];
     return v;
 }
-
-__device__ inline unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
 
 __global__ void __launch_bounds__(kSplitThreads)
 gpfq_split_max_kernel(const float *__restrict__ x, int64_t B, int64_t ldx, int64_t N, unsigned *__restrict__ cells)
@@ -78,9 +79,9 @@ gpfq_split_max_kernel(const float *__restrict__ x, int64_t B, int64_t ldx, int64
     }
 }
 
-__global__ void __launch_bounds__(kSplitThreads)
-gpfq_split_quantize_kernel(const float *__restrict__ x, int64_t B, int64_t ldx, int64_t N, int8_t *__restrict__ xq, int64_t ldq,
-                           const unsigned *__restrict__ cells)
+// the chunks blockIdx.x of the rows blockIdx.y, + gridDim.y, ..: what gpfq_split_quantize_kernel and the from_amax kernel share
+__device__ __forceinline__ void split_quantize_chunks(const float *__restrict__ x, int64_t B, int64_t ldx, int64_t N,
+                                                      int8_t *__restrict__ xq, int64_t ldq, const unsigned *__restrict__ cells)
 {
     const int tid = threadIdx.x;
     const int64_t t0 = (int64_t)blockIdx.x * kSplitChunk + 4 * (int64_t)tid;
@@ -122,6 +123,33 @@ gpfq_split_quantize_kernel(const float *__restrict__ x, int64_t B, int64_t ldx, 
 }
 
 __global__ void __launch_bounds__(kSplitThreads)
+gpfq_split_quantize_kernel(const float *__restrict__ x, int64_t B, int64_t ldx, int64_t N, int8_t *__restrict__ xq, int64_t ldq,
+                           const unsigned *__restrict__ cells)
+{
+    split_quantize_chunks(x, B, ldx, N, xq, ldq, cells);
+}
+
+// the scale of a row whose maximum of bits(x) & 0x7fffffff is `top`: the row kernel's own branches
+__device__ inline float scale_of(unsigned top)
+{
+    const float amax = __uint_as_float(top);
+    if (top >= 0x7f800000u) return __uint_as_float(0x7fc00000u);
+    return amax >= 0x1p-100f ? amax / 127.0f : 0.f;
+}
+
+// gpfq_quantize_rows_i8_from_amax: the quantizing step with the cells supplied by the caller (the producing
+// layer's epilogue) and the finishing step folded in -- the first chunk's first thread writes the row's scale.  cells is only read and
+// scales only written, so no chunk depends on another.  N = 0 launches one chunk a row, which writes the scale alone.
+__global__ void __launch_bounds__(kSplitThreads)
+gpfq_from_amax_kernel(const float *__restrict__ x, int64_t B, int64_t ldx, int64_t N, const unsigned *__restrict__ cells,
+                      int8_t *__restrict__ xq, int64_t ldq, float *__restrict__ scales)
+{
+    split_quantize_chunks(x, B, ldx, N, xq, ldq, cells);
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int64_t b = blockIdx.y; b < B; b += gridDim.y) scales[b] = scale_of(cells[b]);
+}
+
+__global__ void __launch_bounds__(kSplitThreads)
 gpfq_split_clear_kernel(unsigned *__restrict__ cells, int64_t B)
 {
     const int64_t b = (int64_t)blockIdx.x * kSplitThreads + threadIdx.x;
@@ -160,6 +188,16 @@ hipError_t launch_quantize_rows_i8_split(const float *x, int64_t B, int64_t ldx,
     hipLaunchKernelGGL(gpfq_split_quantize_kernel, grid, dim3(kSplitThreads), 0, stream, x, B, ldx, N, xq, ldq, cells);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(gpfq_split_finish_kernel, rows, dim3(kSplitThreads), 0, stream, scales, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_quantize_rows_i8_from_amax(const float *x, int64_t B, int64_t ldx, int64_t N, const uint32_t *amax_bits, int8_t *xq,
+                                             int64_t ldq, float *scales, hipStream_t stream)
+{
+    int64_t chunks = (N + kSplitChunk - 1) / kSplitChunk;            // (the entry has checked that grid.x holds it)
+    if (chunks == 0) chunks = 1;                    // no column: the scales alone
+    const dim3 grid((unsigned)chunks, (unsigned)(B < 65535 ? B : 65535));
+    hipLaunchKernelGGL(gpfq_from_amax_kernel, grid, dim3(kSplitThreads), 0, stream, x, B, ldx, N, amax_bits, xq, ldq, scales);
     return hipGetLastError();
 }
 

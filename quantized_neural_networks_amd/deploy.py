@@ -140,7 +140,170 @@ def _check_int8_layer(layer, packed):
                          f"(GPFQ_PACKED_I8_MAX_N), the layer has {layer.fan_in}")
 
 
-def load_packed(path, device=None, activations="float32", packed_conv=False):
+def fold_batchnorm(radii, bias, gamma, beta, mean, var, epsilon):
+    """A BatchNormalization (inference form) behind a linear packed layer, folded into the layer's radii and bias: NumPy in and out,
+    float64 arithmetic on the stored values.  With inv = gamma / sqrt(var + epsilon) per channel,
+
+        radii' = radii * inv                                  (float64 [C])
+        bias'  = float32((bias - mean) * inv + beta)          (float32 [C]; bias None: a layer without one, taken as 0)
+
+    so that radii' * w * x + bias' = ((radii * w * x + bias) - mean) * inv + beta for every weight w of the channel.  A zero or negative
+    inv is legal: the alphabet of such a channel is scaled to nothing, or mirrored."""
+    radii = np.asarray(radii, dtype=np.float64).reshape(-1)
+    gamma, beta, mean, var = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (gamma, beta, mean, var))
+    b = np.zeros_like(radii) if bias is None else np.asarray(bias, dtype=np.float64).reshape(-1)
+    if not (len(radii) == len(gamma) == len(beta) == len(mean) == len(var) == len(b)):
+        raise ValueError("fold_batchnorm: radii, bias and the four BatchNormalization vectors must have one entry per channel")
+    inv = gamma / np.sqrt(var + np.float64(epsilon))
+    return radii * inv, ((b - mean) * inv + beta).astype(np.float32)
+
+
+def _kind(layer):
+    """The shim class a layer stands for: the first class of its ancestry that save_model knows by name (PackedDense -> Dense)."""
+    for c in type(layer).__mro__:
+        if c.__name__ in keras_shim._layer_classes():
+            return c.__name__
+    return type(layer).__name__
+
+
+def _rows_of(shape, kind):
+    """(rows per sample, floats per row) of a tensor of this static shape as the int8 quantizer of a `kind` layer cuts it: an image
+    is one row of a Conv2D layer, the last axis one row of a Dense layer."""
+    dims = [int(v) for v in shape[1:]]
+    if kind == "Conv2D":
+        return 1, int(np.prod(dims))
+    return int(np.prod(dims[:-1])), dims[-1]
+
+
+def _plan(nodes, outputs, packed_at, shapes=None):
+    """The fusion plan of a network given as tables (host only).  nodes: per position dict(kind, activation, inbound positions);
+    outputs: the positions of the network's outputs; packed_at: the positions of the packed layers on the int8 route; shapes: per
+    position (input shape, output shape), or None -- no links are made then.  Returns per packed position
+    dict(folded, relu, hands_to): positions or None; relu is the layer's own position where its own activation is the ReLU."""
+    consumers = [[] for _ in nodes]
+    for k, node in enumerate(nodes):
+        for p in node["inbound"]:
+            consumers[p].append(k)
+    outputs, packed_at = set(outputs), sorted(packed_at)
+
+    def sole(pos):
+        """The one consumer of position pos, or None (several, none, or a network output)."""
+        return consumers[pos][0] if pos not in outputs and len(consumers[pos]) == 1 else None
+
+    plan = {}
+    for k in packed_at:
+        act = nodes[k]["activation"]
+        linear, own_relu = act in (None, "linear"), act == "relu"
+        entry = dict(folded=None, relu=None, hands_to=None)
+        out = k
+        if linear:
+            c = sole(out)
+            if c is not None and nodes[c]["kind"] == "BatchNormalization":
+                entry["folded"] = out = c
+        if own_relu:
+            entry["relu"] = k
+        elif linear:
+            c = sole(out)
+            if c is not None and (nodes[c]["kind"] == "ReLU" or (nodes[c]["kind"] == "Activation" and nodes[c]["activation"] == "relu")):
+                entry["relu"] = out = c
+        if (linear or own_relu) and shapes is not None:               # (another activation stays a torch op: nothing to hand on)
+            pos = out
+            while True:
+                c = sole(pos)
+                if c is None:
+                    break
+                if nodes[c]["kind"] in ("Flatten", "Dropout"):
+                    pos = c
+                    continue
+                if c in packed_at and _rows_of(shapes[k][1], nodes[k]["kind"]) == _rows_of(shapes[c][0], nodes[c]["kind"]):
+                    entry["hands_to"] = c
+                break
+        plan[k] = entry
+    return plan
+
+
+def _net_tables(net):
+    layers = net.layers
+    if isinstance(net, keras_shim.Model):
+        inbound, _ = net.graph_tables()
+        pos = {id(l): k for k, l in enumerate(layers)}
+        outputs = [pos[id(t.layer)] for t in net.outputs]
+    else:
+        inbound, outputs = [[k - 1] if k else [] for k in range(len(layers))], [len(layers) - 1]
+    nodes = [dict(kind=_kind(l), activation=getattr(l, "activation", None), inbound=list(inbound[k])) for k, l in enumerate(layers)]
+    return nodes, outputs
+
+
+def plan_fusion(net, packed_at=None):
+    """The plan of load_packed(..., fuse=True) for a keras_shim network (Sequential, or a functional Model): a list with one dict per
+    packed layer on the int8 route, in layer order --
+
+        layer      the packed layer's name
+        folded     the BatchNormalization folded into its radii and bias, or None
+        relu       the ReLU / Activation("relu") layer applied in its epilogue -- its own name where its own activation is the ReLU --
+                   or None
+        hands_to   the packed layer whose quantizer takes this layer's maxima, or None
+
+    packed_at: the positions in net.layers to plan for (default: the PackedDense / PackedConv2D layers whose activations are "int8").
+    A function of the layer classes, activations, static shapes and the graph alone: nothing runs on a device.  The rules, in order,
+    per packed layer P: FOLD where P's activation is None / "linear" and its output has exactly one consumer,
+    a BatchNormalization, and is not a network output; RELU where P's own activation is "relu" (nothing is folded then), or where the
+    group's output so far has exactly one consumer, a ReLU or Activation("relu"), and is not a network output; LINK where the group's
+    output reaches, through single-consumer Flatten / Dropout layers at most, a packed layer whose rows are this layer's rows or
+    images one to one.  Any other activation stays a torch op and nothing is handed on."""
+    net = _shim_network(net)
+    if packed_at is None:
+        packed_at = [k for k, l in enumerate(net.layers)
+                     if isinstance(l, (keras_shim.PackedDense, keras_shim.PackedConv2D)) and l.activations == "int8"]
+    nodes, outputs = _net_tables(net)
+    bad = [k for k in packed_at if nodes[k]["kind"] not in ("Dense", "Conv2D")]
+    if bad:
+        raise ValueError(f"plan_fusion: positions {bad} are not Dense or Conv2D layers")
+    shapes = [(l.input_shape, l.output_shape) for l in net.layers]
+    plan = _plan(nodes, outputs, packed_at, shapes)
+    name = lambda k: None if k is None else net.layers[k].name
+    return [dict(layer=name(k), folded=name(e["folded"]), relu=name(e["relu"]), hands_to=name(e["hands_to"]))
+            for k, e in sorted(plan.items())]
+
+
+def _arch_tables(arch):
+    """_net_tables from an architecture record, before the network exists."""
+    specs = arch["layers"]
+    if arch.get("functional"):
+        pos = {s["name"]: k for k, s in enumerate(specs)}
+        inbound = [[pos[n] for n in s.get("inbound", [])] if s["cls"] != "InputLayer" else [] for s in specs]
+        outputs = [pos[n] for n in arch["outputs"]]
+    else:
+        inbound, outputs = [[k - 1] if k else [] for k in range(len(specs))], [len(specs) - 1]
+    nodes = [dict(kind=s["cls"], activation=s["config"].get("activation"), inbound=inbound[k]) for k, s in enumerate(specs)]
+    return nodes, outputs
+
+
+_FUSED_AWAY = {"BatchNormalization": "FoldedBatchNormalization", "Activation": "FusedActivation", "ReLU": "FusedReLU"}
+
+
+def _apply_fusion(net, packed_at):
+    """Sets the fused state of the packed layers of a loaded network from its plan and records the plan as net.fusion_plan."""
+    pos = {l.name: k for k, l in enumerate(net.layers)}
+    net.fusion_plan = plan_fusion(net, packed_at)
+    for e in net.fusion_plan:
+        layer = net.layers[pos[e["layer"]]]
+        p = layer.packed
+        radii = p["radii"].cpu().numpy()
+        bias = layer._weights[0].cpu().numpy() if layer.use_bias else None
+        if e["folded"] is not None:
+            bn = net.layers[pos[e["folded"]]]
+            gamma, beta, mean, var = (w.cpu().numpy() for w in bn._weights)
+            radii, bias = fold_batchnorm(radii, bias, gamma, beta, mean, var, bn.epsilon)
+        to = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device=net.device, dtype=dt).contiguous()
+        layer.fused = dict(radii=to(radii, torch.float64), bias=to(bias, torch.float32), relu=e["relu"] is not None)
+        layer.emit_amax = e["hands_to"] is not None
+        if e["hands_to"] is not None:
+            net.layers[pos[e["hands_to"]]].amax_from = layer
+    return net
+
+
+def load_packed(path, device=None, activations="float32", packed_conv=False, fuse=False):
     """Inverse of export_packed: a keras_shim network on ``device`` (default: the current GPU).  Dense layers that were exported
     packed come back as keras_shim.PackedDense (codes, radii and bias in device memory; the float kernel is never formed unless
     get_weights() or a batch beyond keras_shim.PACKED_TILED_MAX_BATCH asks for it); packed Conv2D / DepthwiseConv2D kernels are
@@ -153,9 +316,19 @@ def load_packed(path, device=None, activations="float32", packed_conv=False):
     packed_conv=True: every Conv2D layer that was exported packed stays packed too (keras_shim.PackedConv2D),
     with ``activations`` set on it: "int8" rounds every image to int8 with its own scale and runs gpfq_packed_conv2d_forward_i8, and
     the same two checks apply with kh * kw * Cin as the row length; "float32" decodes at every call.  DepthwiseConv2D kernels are
-    decoded at load either way: their rows are kh * kw long, too short for the matrix instruction to matter."""
+    decoded at load either way: their rows are kh * kw long, too short for the matrix instruction to matter.
+
+    fuse=True (needs activations="int8"): what stands around the packed layers moves into them, by the plan
+    of plan_fusion, recorded as ``net.fusion_plan``.  A BatchNormalization behind a linear packed layer is folded into the layer's
+    radii and bias (fold_batchnorm); a ReLU -- the layer's own, or the ReLU / Activation("relu") layer behind it -- is applied in the
+    kernel's epilogue; and a packed layer whose output feeds another one hands it the maxima its quantizer would search for.
+    The layers folded or fused away keep their positions, names and weights and pass their input on (keras_shim.FoldedBatchNormalization,
+    FusedActivation, FusedReLU): in a fused network the value at such a position, and at the packed layer's own, is the group's
+    output.  Everything but the fold is bit for bit what fuse=False computes; the fold differs by float32 roundings alone."""
     if activations not in keras_shim.PackedDense.ACTIVATIONS:
         raise ValueError(f"activations must be one of {keras_shim.PackedDense.ACTIVATIONS}, got {activations!r}")
+    if fuse and activations != "int8":
+        raise ValueError(f"fuse=True moves BatchNormalization and ReLU into the int8 kernels: it needs activations=\"int8\", got {activations!r}")
     path = str(path)
     with np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False) as z:
         if "__packed__" not in z.files:
@@ -168,12 +341,20 @@ def load_packed(path, device=None, activations="float32", packed_conv=False):
         classes = {k: keras_shim.PackedDense for k in packed_at if arch["layers"][k]["cls"] == "Dense"}
         if packed_conv:
             classes.update({k: keras_shim.PackedConv2D for k in packed_at if arch["layers"][k]["cls"] == "Conv2D"})
+        if fuse:
+            # the positions fused away, from the record alone (the fold and the ReLU need no shapes); the full plan follows the network
+            nodes, outputs = _arch_tables(arch)
+            fused_at = sorted(classes)
+            for e in _plan(nodes, outputs, fused_at).values():
+                for k in (e["folded"], e["relu"]):
+                    if k is not None and k not in fused_at:
+                        classes[k] = getattr(keras_shim, _FUSED_AWAY[arch["layers"][k]["cls"]])
         net = keras_shim._network_from_arch(arch, device, classes)
         for k, layer in enumerate(net.layers):
             if k in packed_at:
                 packed = _read_packed(z, k, net.device)
                 rest = [z[f"w{k}_{j}"] for j in range(1, 1 + (1 if layer.use_bias else 0))]
-                if k in classes:
+                if k in classes:                    # (a packed position: the layers fused away hold no codes)
                     if activations == "int8":
                         _check_int8_layer(layer, packed)
                     layer.set_packed(packed, rest[0] if rest else None)
@@ -182,4 +363,4 @@ def load_packed(path, device=None, activations="float32", packed_conv=False):
                     layer.set_weights([unpack_kernel(packed)] + rest)
             elif layer._weights:
                 layer.set_weights([z[f"w{k}_{j}"] for j in range(len(layer._weights))])
-    return net
+    return _apply_fusion(net, fused_at) if fuse else net

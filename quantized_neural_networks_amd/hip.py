@@ -74,6 +74,11 @@ SYMBOLS = {
     "gpfq_packed_dense_forward_i8": (_int, [_vp, _i64, _i64, _vp, _vp, _int, _int, _vp, _int, _vp, _i64, _i64, _vp, _i64, _vp]),
     "gpfq_packed_conv2d_forward_i8": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
                                              _vp, _int, _int, _vp, _int, _vp, _i64, _vp, _vp]),
+    "gpfq_packed_dense_forward_i8_fused": (_int, [_vp, _i64, _i64, _vp, _vp, _int, _int, _vp, _int, _vp, _i64, _i64, _vp, _i64, _int, _vp,
+                                                  _vp]),
+    "gpfq_packed_conv2d_forward_i8_fused": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
+                                                   _vp, _int, _int, _vp, _int, _vp, _i64, _vp, _int, _vp, _vp]),
+    "gpfq_quantize_rows_i8_from_amax": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "gpfq_candidate_kernels": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dp, _int, _vp, _vp, _i64, _i64, _i64, _vp]),
     "gpfq_select_candidates_workspace_bytes": (_sz, [_int, _i64]),
     "gpfq_select_candidates": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _dp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
@@ -1450,14 +1455,27 @@ def quantize_split_chunk():
     return int(load().gpfq_quantize_split_chunk())
 
 
-def quantize_rows_i8(x, N=None, out=None, form=None):
+def _amax_cells(t, B, name):
+    """A tensor of row maxima as the fused entries make them: uint32 or int32 [B], contiguous, on the device -> its pointer."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise GpfqError(f"{name} must be a GPU tensor (the HIP path has no CPU fallback)")
+    if t.dtype not in (torch.uint32, torch.int32):
+        raise GpfqError(f"{name} must be uint32 or int32, got {t.dtype}")
+    if t.dim() != 1 or t.numel() != B or not t.is_contiguous():
+        raise GpfqError(f"{name} must be a contiguous [{B}] tensor, got {tuple(t.shape)}")
+    return t.data_ptr()
+
+
+def quantize_rows_i8(x, N=None, out=None, form=None, amax=None):
     """x f32 [B][N] (rows contiguous, any row pitch) -> (xq i8 [B][roundup16(N)], scales f32 [B]) (gpfq_quantize_rows_i8): per batch
     row, xq = rint(x * (127 / amax)) and scales = amax / 127; a row that is not finite gets the scale NaN and zeros, a row below 2^-100
     the scale 0 and zeros; the pad bytes are zeros.  N: the leading columns of x to take (default: all).  out: an optional
     (xq, scales) pair; xq may be a view of [B] rows whose pitch is a multiple of 16, on a 16-byte aligned address.  form: "row" (one
     workgroup per row, one launch), "split" (gpfq_quantize_rows_i8_split: a workgroup per chunk of a row, four stream operations,
     scales holding the rows' maxima in between) or None: "split" from QUANTIZE_SPLIT_MIN_N columns on.  The same bits either way.
-    No sync."""
+    amax: a uint32 or int32 [B] tensor of the rows' maxima of bits(x) & 0x7fffffff, as the fused forward passes leave them
+    (amax_out): the maxima are not searched (gpfq_quantize_rows_i8_from_amax: one launch, x read once, whatever `form` says); the same
+    bits when they are the rows' own.  No sync."""
     if form not in QUANTIZE_FORMS:
         raise GpfqError(f"form must be one of {QUANTIZE_FORMS}, got {form!r}")
     _dev(x, torch.float32, "x")
@@ -1475,6 +1493,12 @@ def quantize_rows_i8(x, N=None, out=None, form=None):
         raise GpfqError(f"out must be (int8 [{B}][>= {n16}], float32 [{B}]), got {tuple(xq.shape)}, {tuple(scales.shape)}")
     if B <= 1:
         ldq = max(n16, 16)
+    if amax is not None:
+        ap = _amax_cells(amax, B, "amax")
+        with torch.cuda.device(x.device):
+            _check(load().gpfq_quantize_rows_i8_from_amax(xp, B, ldx, N, ap, qp, ldq, scales.data_ptr(), _stream()),
+                   "gpfq_quantize_rows_i8_from_amax")
+        return xq, scales
     if form is None:
         form = "split" if N >= QUANTIZE_SPLIT_MIN_N else "row"
     entry = "gpfq_quantize_rows_i8_split" if form == "split" else "gpfq_quantize_rows_i8"
@@ -1483,17 +1507,31 @@ def quantize_rows_i8(x, N=None, out=None, form=None):
     return xq, scales
 
 
-def packed_dense_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, N, bias=None, out=None, scales=None):
+def _fused_args(relu, amax_out, rows):
+    """relu and amax_out of the two fused forward passes -> (take the fused entry, relu as 0 / 1, the cells' pointer or None)."""
+    if relu not in (False, True, 0, 1):
+        raise GpfqError(f"relu must be a bool, got {relu!r}")
+    ap = _amax_cells(amax_out, rows, "amax_out") if amax_out is not None else None
+    return bool(relu) or ap is not None, int(bool(relu)), ap
+
+
+def packed_dense_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, N, bias=None, out=None, scales=None, relu=False, amax_out=None,
+                            amax=None):
     """y f32 [B][C] of a Dense layer held as packed rows, on int8 activations and exact int32 sums (gpfq_packed_dense_forward_i8; the
     contract is include/gpfq.h's, bit for bit).  x_or_xq: float32 x [B][N], quantized here (quantize_rows_i8), or -- with `scales`
     f32 [B] -- a ready int8 xq [B][>= N] whose row pitch is a multiple of 16.  M: the size of the layer's unit alphabet, which must be
-    linspace(-1, 1, M).  No sync."""
+    linspace(-1, 1, M).  relu / amax_out (a uint32 or int32 [B] tensor): the fused epilogue (gpfq_packed_dense_forward_i8_fused) -- y
+    clamped below at zero, and amax_out[b] = the maximum of bits(y[b][:]) & 0x7fffffff, what quantize_rows_i8(y, amax=amax_out) takes;
+    with neither, the call is gpfq_packed_dense_forward_i8's as before.  amax: with a float x, its rows' maxima, passed on to
+    quantize_rows_i8.  No sync."""
     if scales is None:
         _dev(x_or_xq, torch.float32, "x")
         if x_or_xq.dim() != 2 or x_or_xq.shape[1] != int(N):
             raise GpfqError(f"x {tuple(x_or_xq.shape)} does not have the layer's {N} input features")
-        xq, scales = quantize_rows_i8(x_or_xq)
+        xq, scales = quantize_rows_i8(x_or_xq, amax=amax)
     else:
+        if amax is not None:
+            raise GpfqError("amax goes with a float32 x: a ready xq has been quantized already")
         xq = _dev(x_or_xq, torch.int8, "xq")
     _dev(scales, torch.float32, "scales")
     qp, B, Nq, ldq = _rows(xq, "xq")
@@ -1505,21 +1543,28 @@ def packed_dense_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, N, bias=
         raise GpfqError(f"scales must be a contiguous [{B}] tensor")
     C = _packed_args(packed, bits, zero_code, radii, N)
     bp, yp, ldy, out = _packed_bias_out(bias, out, B, C, xq.device)
+    fused, relu, ap = _fused_args(relu, amax_out, B)
     with torch.cuda.device(xq.device):
-        _check(load().gpfq_packed_dense_forward_i8(qp, B, ldq, scales.data_ptr(), packed.data_ptr(), int(bits), int(zero_code),
-                                                   radii.data_ptr(), int(M), bp, int(N), C, yp, ldy, _stream()),
-               "gpfq_packed_dense_forward_i8")
+        if fused:
+            _check(load().gpfq_packed_dense_forward_i8_fused(qp, B, ldq, scales.data_ptr(), packed.data_ptr(), int(bits), int(zero_code),
+                                                             radii.data_ptr(), int(M), bp, int(N), C, yp, ldy, relu, ap, _stream()),
+                   "gpfq_packed_dense_forward_i8_fused")
+        else:
+            _check(load().gpfq_packed_dense_forward_i8(qp, B, ldq, scales.data_ptr(), packed.data_ptr(), int(bits), int(zero_code),
+                                                       radii.data_ptr(), int(M), bp, int(N), C, yp, ldy, _stream()),
+                   "gpfq_packed_dense_forward_i8")
     return out
 
 
 def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias=None, scales=None,
-                             out=None):
+                             out=None, relu=False, amax_out=None, amax=None):
     """y f32 [n][OH][OW][F] of a Conv2D layer whose kernel [kh][kw][Cin][F] = kernel_shape is held as the packed rows of its matrix
     view [kh*kw*Cin][F], on int8 images and exact int32 sums (gpfq_packed_conv2d_forward_i8; the contract is include/gpfq.h's, bit for
     bit; TensorFlow's geometry).  x_or_xq: float32 NHWC x [n][H][W][Cin], each image quantized here with its own scale
     (quantize_rows_i8 on the flattened images), or -- with `scales` f32 [n] -- ready int8 images [n][H][W][Cin], each contiguous, an
     image pitch (stride(0)) that is a multiple of 16.  M: the size of the layer's unit alphabet, which must be linspace(-1, 1, M).
-    out: an optional contiguous [n][OH][OW][F] tensor.  No sync."""
+    out: an optional contiguous [n][OH][OW][F] tensor.  relu / amax_out (a uint32 or int32 [n] tensor, one cell per image) / amax
+    (the maxima of a float x's images): as for packed_dense_forward_i8, through gpfq_packed_conv2d_forward_i8_fused.  No sync."""
     kh, kw, Cin, F = (int(v) for v in kernel_shape)
     kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
     if not isinstance(x_or_xq, torch.Tensor) or x_or_xq.dim() != 4 or x_or_xq.shape[3] != Cin:
@@ -1530,9 +1575,11 @@ def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_
     hwc = H * W * Cin
     if scales is None:
         _dev(x_or_xq, torch.float32, "x")
-        xq, scales = quantize_rows_i8(x_or_xq.contiguous().reshape(n, hwc))
+        xq, scales = quantize_rows_i8(x_or_xq.contiguous().reshape(n, hwc), amax=amax)
         ldq = xq.shape[1]
     else:
+        if amax is not None:
+            raise GpfqError("amax goes with a float32 x: a ready xq has been quantized already")
         xq = _dev(x_or_xq, torch.int8, "xq")
         if n > 0 and not xq[0].is_contiguous():
             raise GpfqError("xq: every image must be contiguous [H][W][Cin]")
@@ -1553,9 +1600,17 @@ def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_
     _dev(out, torch.float32, "out")
     if tuple(out.shape) != (n, OH, OW, F) or not out.is_contiguous():
         raise GpfqError(f"out {tuple(out.shape)} must be a contiguous [{n}][{OH}][{OW}][{F}] tensor")
+    fused, relu, ap = _fused_args(relu, amax_out, n)
+    bp = bias.data_ptr() if bias is not None else None
     with torch.cuda.device(xq.device):
-        _check(load().gpfq_packed_conv2d_forward_i8(xq.data_ptr(), n, ldq, scales.data_ptr(), H, W, Cin, kh, kw, sh, sw, rh, rw,
-                                                    1 if same else 0, packed.data_ptr(), int(bits), int(zero_code), radii.data_ptr(),
-                                                    int(M), bias.data_ptr() if bias is not None else None, F, out.data_ptr(), _stream()),
-               "gpfq_packed_conv2d_forward_i8")
+        if fused:
+            _check(load().gpfq_packed_conv2d_forward_i8_fused(xq.data_ptr(), n, ldq, scales.data_ptr(), H, W, Cin, kh, kw, sh, sw, rh, rw,
+                                                              1 if same else 0, packed.data_ptr(), int(bits), int(zero_code),
+                                                              radii.data_ptr(), int(M), bp, F, out.data_ptr(), relu, ap, _stream()),
+                   "gpfq_packed_conv2d_forward_i8_fused")
+        else:
+            _check(load().gpfq_packed_conv2d_forward_i8(xq.data_ptr(), n, ldq, scales.data_ptr(), H, W, Cin, kh, kw, sh, sw, rh, rw,
+                                                        1 if same else 0, packed.data_ptr(), int(bits), int(zero_code), radii.data_ptr(),
+                                                        int(M), bp, F, out.data_ptr(), _stream()),
+                   "gpfq_packed_conv2d_forward_i8")
     return out

@@ -16,6 +16,7 @@ Data format is channels-last (NHWC), weights use Keras layouts (Dense [in][out],
 [kh][kw][Cin][Cout], DepthwiseConv2D [kh][kw][Cin][mult]); this is plumbing, not the hot path.
 """
 import math
+import weakref
 
 import numpy as np
 import torch
@@ -225,7 +226,65 @@ PACKED_FORWARD_MAX_BATCH = 4
 PACKED_TILED_MAX_BATCH = 128
 
 
-class PackedDense(Dense):
+class _FusedI8:
+    """What deploy.load_packed(..., fuse=True) sets on a packed layer of the int8 route, and what the layer does
+    with it.  Three pieces of state, all None / False on a layer loaded without ``fuse``:
+
+    ``fused``      dict(radii f64 [C], bias f32 [C] or None, relu bool, on the device): used by the int8 route in place of
+                   packed["radii"], the layer's bias and the torch activation -- a folded BatchNormalization lives in radii and bias,
+                   a fused ReLU in the kernel's epilogue.  ``packed`` and get_weights() stay the original kernel.
+    ``emit_amax``  the layer's kernel also leaves, per batch row / image of its output, the maximum of the bit patterns of |y|.
+    ``amax_from``  the packed layer whose output -- through Flatten and Dropout layers at most -- is this layer's input: where that can
+                   be proved of the tensor handed to call(), the input's quantizer takes the producer's maxima instead of searching.
+
+    The proof (``_taken_maxima``): the producer remembers its last output by weak reference together with the tensor's version counter;
+    the consumer's input must be contiguous float32 over the same storage at the same offset with the same element count, the counter
+    unchanged (no in-place operation since the producer wrote it), and its rows must be the producer's rows or images one to one.
+    Anything else -- a tensor modified in place, a slice, a copy, another batch, a layer called by hand on other data -- runs the full
+    quantizer, silently: the result is the same either way."""
+
+    def _init_fused(self):
+        self.fused = None
+        self.emit_amax = False
+        self.amax_from = None
+        self._handoff = None                          # (weak reference to the output, its version, maxima i32 [rows], floats per row)
+
+    def _fused_parts(self, bias):
+        """(radii, bias, relu fused, what is left of the activation as a torch op) of a call on the int8 route."""
+        f = self.fused
+        if f is None:
+            return self.packed["radii"], bias, False, _activation(self.activation)
+        rest = (lambda y: y) if f["relu"] or self.activation in (None, "linear") else _activation(self.activation)
+        return f["radii"], f["bias"], f["relu"], rest
+
+    def _amax_out(self, rows, device):
+        return torch.empty(rows, dtype=torch.int32, device=device) if self.emit_amax and rows > 0 else None
+
+    def _remember(self, y, amax, per_row):
+        self._handoff = (weakref.ref(y), y._version, amax, int(per_row)) if amax is not None else None
+
+    def _taken_maxima(self, x, rows, row_len):
+        """The producer's maxima for the rows of x, or None (the full quantizer).  x: the contiguous tensor about to be quantized."""
+        producer = self.amax_from
+        hand = getattr(producer, "_handoff", None) if producer is not None else None
+        if hand is None:
+            return None
+        ref, version, amax, per_row = hand
+        y = ref()
+        if (y is None or x.dtype != torch.float32 or not x.is_contiguous() or x.device != y.device
+                or x.untyped_storage().data_ptr() != y.untyped_storage().data_ptr() or x.storage_offset() != y.storage_offset()
+                or x.numel() != y.numel() or x._version != version or y._version != version
+                or rows != amax.numel() or row_len != per_row):
+            return None
+        return amax
+
+    def _need_i8(self, route):
+        if self.fused is not None and route != "i8":
+            raise RuntimeError(f"layer {self.name} was loaded with fuse=True: its folded BatchNormalization and fused ReLU exist on the "
+                               f"int8 route alone (activations=\"int8\"), not on route {route!r}")
+
+
+class PackedDense(Dense, _FusedI8):
     """A Dense layer that holds its quantized kernel as packed low-bit codes (deploy.load_packed): only the
     codes, the radii and the bias live in device memory.  ``get_weights()`` decodes on demand; the weights cannot be set.
 
@@ -233,7 +292,7 @@ class PackedDense(Dense):
     decode + matmul beyond; "int8" rounds every batch row of x to int8 with its own scale and runs gpfq_packed_dense_forward_i8 at
     every batch -- exact int32 sums, the float kernel is never formed (include/gpfq.h has the arithmetic; the layer's alphabet must be
     linspace(-1, 1, M), which deploy.load_packed checks).  A property of the loaded layer, not of its configuration: config(),
-    clone() and save_model() record what they always did."""
+    clone() and save_model() record what they always did.  ``fused``, ``emit_amax``, ``amax_from``: _FusedI8."""
 
     ACTIVATIONS = ("float32", "int8")
 
@@ -241,6 +300,7 @@ class PackedDense(Dense):
         super().__init__(units, activation, use_bias, input_shape, name)
         self.packed = None
         self.activations = "float32"
+        self._init_fused()
 
     def build(self, input_shape, device, rng):
         Layer.build(self, input_shape, device, rng)
@@ -294,9 +354,16 @@ class PackedDense(Dense):
         bias = self._weights[0] if self.use_bias else None
         p = self.packed
         route = self.route(x2.shape[0])
+        if x2.shape[0] > 0:
+            self._need_i8(route)
         if route == "i8":
-            y = hip.packed_dense_forward_i8(x2.contiguous(), p["codes"], p["bits"], p["zero_code"], p["radii"], len(p["alphabet"]),
-                                            self.fan_in, bias=bias)
+            radii, fbias, relu, rest = self._fused_parts(bias)
+            x2 = x2.contiguous()
+            amax_out = self._amax_out(x2.shape[0], x2.device)
+            y = hip.packed_dense_forward_i8(x2, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]), self.fan_in, bias=fbias,
+                                            relu=relu, amax_out=amax_out, amax=self._taken_maxima(x2, x2.shape[0], self.fan_in))
+            self._remember(y, amax_out, self.units)
+            return rest(y.reshape(tuple(x.shape[:-1]) + (self.units,)))
         elif route != "matmul":
             forward = hip.packed_dense_forward if route == "row" else hip.packed_dense_forward_tiled
             y = forward(x2.contiguous(), p["codes"], p["bits"], p["zero_code"], p["radii"], p["alphabet"], self.fan_in, bias=bias)
@@ -370,7 +437,7 @@ class Conv2D(Layer):
         return _activation(self.activation)(y.permute(0, 2, 3, 1).contiguous())
 
 
-class PackedConv2D(Conv2D):
+class PackedConv2D(Conv2D, _FusedI8):
     """A Conv2D layer that holds its quantized kernel as packed low-bit codes (deploy.load_packed(..., packed_conv=True); DESIGN.md
     section 11b): only the codes, the radii and the bias live in device memory.  ``get_weights()`` decodes on demand; the weights
     cannot be set.
@@ -379,7 +446,7 @@ class PackedConv2D(Conv2D):
     does; "int8" rounds every image of x to int8 with its own scale and runs gpfq_packed_conv2d_forward_i8 -- exact int32 sums, the
     float kernel is never formed (include/gpfq.h has the arithmetic; the layer's alphabet must be linspace(-1, 1, M), which
     deploy.load_packed checks).  A property of the loaded layer, not of its configuration: config(), clone() and save_model() record
-    the Conv2D it decodes to."""
+    the Conv2D it decodes to.  ``fused``, ``emit_amax``, ``amax_from``: _FusedI8."""
 
     ACTIVATIONS = ("float32", "int8")
 
@@ -388,6 +455,7 @@ class PackedConv2D(Conv2D):
         super().__init__(filters, kernel_size, strides, padding, dilation_rate, activation, use_bias, input_shape, name)
         self.packed = None
         self.activations = "float32"
+        self._init_fused()
 
     def build(self, input_shape, device, rng):
         Layer.build(self, input_shape, device, rng)
@@ -435,14 +503,21 @@ class PackedConv2D(Conv2D):
 
     def call(self, x):
         if self.route() == "decode":
+            self._need_i8("decode")
             return Conv2D.call(self, x)                                     # (the kernel through _torch_weight, the bias through _bias)
         from . import hip
         if self.packed is None:
             raise RuntimeError(f"PackedConv2D layer {self.name} holds no packed kernel (deploy.load_packed installs one)")
         p = self.packed
-        y = hip.packed_conv2d_forward_i8(x, p["codes"], p["bits"], p["zero_code"], p["radii"], len(p["alphabet"]), self.kernel_shape,
-                                         self.strides, self.dilation_rate, self.padding, bias=self._bias())
-        return _activation(self.activation)(y)
+        radii, bias, relu, rest = self._fused_parts(self._bias())
+        x = x.contiguous()
+        n = int(x.shape[0])
+        amax_out = self._amax_out(n, x.device)
+        y = hip.packed_conv2d_forward_i8(x, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]), self.kernel_shape,
+                                         self.strides, self.dilation_rate, self.padding, bias=bias, relu=relu, amax_out=amax_out,
+                                         amax=self._taken_maxima(x, n, x[0].numel() if n else 0))
+        self._remember(y, amax_out, y[0].numel() if n else 0)
+        return rest(y)
 
 
 class DepthwiseConv2D(Conv2D):
@@ -590,6 +665,34 @@ class Dropout(Layer):
 
     def config(self):
         return dict(rate=self.rate)
+
+
+class _FusedAway:
+    """A layer position whose work a packed layer before it does (deploy.load_packed(..., fuse=True)): a
+    BatchNormalization folded into the radii and bias of the packed layer it follows, or a ReLU applied in that layer's epilogue.
+    call() is the identity, so IN A FUSED NETWORK THE VALUE AT THIS POSITION IS THE GROUP'S OUTPUT -- already normalised, already
+    clamped -- and so is the value at every position of the group before it, the packed layer's own included.  The weights are still
+    here and readable; config(), clone() and save_model() give the plain layer, and the layer keeps its position in ``layers``."""
+
+    def call(self, x):
+        return x
+
+    def clone(self):
+        c = self._plain(**self.config())
+        c.name = self.name
+        return c
+
+
+class FoldedBatchNormalization(_FusedAway, BatchNormalization):
+    _plain = BatchNormalization
+
+
+class FusedActivation(_FusedAway, Activation):
+    _plain = Activation
+
+
+class FusedReLU(_FusedAway, ReLU):
+    _plain = ReLU
 
 
 class Sequential:
@@ -915,7 +1018,10 @@ def _arch_arrays(model):
     for l in model.layers:
         # (a PackedDense / PackedConv2D layer is recorded as the Dense / Conv2D layer it decodes to: save_model writes its float
         #  kernel, load_model reads it)
+        #  (and a layer fused away as the plain layer it stands for)
         cls = "Dense" if isinstance(l, PackedDense) else ("Conv2D" if isinstance(l, PackedConv2D) else l.__class__.__name__)
+        if isinstance(l, _FusedAway):
+            cls = l._plain.__name__
         spec = dict(cls=cls, name=l.name, config=l.config())
         if functional:
             inbound = l.inbound_nodes[0].inbound_layers

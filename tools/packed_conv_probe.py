@@ -22,6 +22,11 @@ differ by.  The rule for hip.QUANTIZE_SPLIT_MIN_N, fixed before measuring: the s
 and every longer one, the split form's median is not above the row form's at every probed batch -- "not above": at most the larger of
 the row form's two medians --; 2**62 (never split) if there is none.
 
+--pairs: the chain mode of DESIGN.md section 11c (tools/packed_chain_pairs.py; `--chain` is taken: it counts the calls captured into
+one graph) -> the Conv2D part of profiles/packed_chain.txt.  Producer -> consumer links -- ResNet50's conv -> BN -> ReLU -> conv pairs
+at 56^2, 28^2, 14^2 and 7^2, a VGG-style conv(relu) -> conv pair, the CIFAR10 CNN's conv(relu) -> BN -> conv -- loaded with
+fuse=False and fuse=True and timed in alternation at 1, 8 and 32 images; the unfused network, captured twice, is the yardstick.
+
 --ways i8,float: only these of the three ways (the layer table of profiles/packed_conv_i8_split.txt leaves decode out).
 --tree PATH: take the package (and its built library) from another checkout of this repository, e.g. the parent commit built in a
 scratch worktree: the same probe, alternating between two trees, is how a change to the layer call is measured.
@@ -30,6 +35,7 @@ scratch worktree: the same probe, alternating between two trees, is how a change
     GPFQ_DIAG="-DGPFQ_CONV_I8_SKIP=1" python tools/packed_conv_probe.py --phases
     python tools/packed_conv_probe.py --quantizer --out quantizer.txt
     python tools/packed_conv_probe.py --ways i8,float [--tree ../parent] --out layers.txt
+    python tools/packed_conv_probe.py --pairs --out chain_conv.txt
 """
 import argparse
 import os
@@ -238,6 +244,7 @@ def main():
     ap.add_argument("--quick", action="store_true", help="two shapes only")
     ap.add_argument("--phases", action="store_true", help="the int8 kernel and the image quantization alone (see the module's text)")
     ap.add_argument("--quantizer", action="store_true", help="the image quantization alone, form=\"row\" against form=\"split\"")
+    ap.add_argument("--pairs", action="store_true", help="producer -> consumer links, fuse=False against fuse=True (see the module's text)")
     ap.add_argument("--ways", default=",".join(WAYS), help="which of i8,float,decode the layer table times (i8 always)")
     ap.add_argument("--tree", default=None, help="another checkout of this repository to take the package and its library from")
     args = ap.parse_args()
@@ -259,6 +266,13 @@ def main():
         return
     if args.quantizer:
         quantizer(args, dev, out)
+        return
+    if args.pairs:
+        import packed_chain_pairs as pairs
+        out(f"# {torch.cuda.get_device_name(dev)}; Conv2D links, device time per predict_on_batch: {args.chain} calls captured into one graph, "
+            f"{args.replays} timed replays per graph, three graphs alternating (unfused, fused, unfused again); median (min .. max); us")
+        with torch.no_grad():
+            pairs.run(pairs.conv_links()[:2] if args.quick else pairs.conv_links(), IMAGES, args, dev, out, deploy, hip, ks)
         return
     out(f"# {torch.cuda.get_device_name(dev)}; device time per layer call: {args.chain} calls captured into one graph, {args.replays} timed "
         f"replays per way, the ways ({', '.join(args.ways)}) alternating; median (min .. max); us; package from "

@@ -27,6 +27,12 @@ Also the file sizes of a VGG16-shaped Dense stack written by save_model and by e
     python tools/packed_forward_probe.py [--out profiles/packed_forward_tiled.txt] [--quick]
     python tools/packed_forward_probe.py --i8 --out profiles/packed_forward_i8.txt
 
+--pairs: the chain mode of DESIGN.md section 11c (tools/packed_chain_pairs.py; `--chain` is taken: it counts the calls captured into
+one graph) -> the Dense part of profiles/packed_chain.txt.  VGG16's fc1 -> fc2 -> predictions as one network, loaded with fuse=False
+and fuse=True and timed in alternation at 1, 8, 32 and 256 rows; the unfused network, captured twice, is the yardstick.
+
+    python tools/packed_forward_probe.py --pairs --out chain_dense.txt
+
 --i8-only: the fifth way alone, with hip.quantize_rows_i8 choosing its form (the row kernel, or from hip.QUANTIZE_SPLIT_MIN_N columns on
 the split form), the same shapes, batches and cache states.  --tree PATH: take the package (and its built library) from another
 checkout of this repository, e.g. the parent commit built in a scratch worktree; the two together, alternating between two trees, are
@@ -221,6 +227,7 @@ def main():
     ap.add_argument("--quick", action="store_true", help="4096 x 4096 ternary only, no file sizes")
     ap.add_argument("--i8", action="store_true", help="a fifth way: row quantization + the int8 kernel, timed together; batches up to 1024")
     ap.add_argument("--i8-only", action="store_true", help="row quantization + the int8 kernel alone (see the module's text)")
+    ap.add_argument("--pairs", action="store_true", help="producer -> consumer links, fuse=False against fuse=True (see the module's text)")
     ap.add_argument("--tree", default=None, help="another checkout of this repository to take the package and its library from")
     args = ap.parse_args()
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -229,10 +236,18 @@ def main():
     def out(s):
         print(s, flush=True)
         lines.append(s)
-        if args.i8_only and args.out:
+        if (args.i8_only or args.pairs) and args.out:
             with open(args.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
 
+    if args.pairs:
+        import packed_chain_pairs as pairs
+        out(f"# {torch.cuda.get_device_name(dev)}; Dense links, device time per predict_on_batch: {args.chain} calls captured into one graph, "
+            f"{args.replays} timed replays per graph, three graphs alternating (unfused, fused, unfused again); median (min .. max); us")
+        with torch.no_grad():
+            pairs.run(pairs.dense_links(), (1, 8, 32, 256), args, dev, out, deploy, hip, ks,
+                      members=(3,) if args.quick else (3, 16))
+        return
     if args.i8_only:
         out(f"# {torch.cuda.get_device_name(dev)}; device time per call: {args.chain} calls captured into one graph, {args.replays} timed "
             f"replays; package from {'--tree' if args.tree else 'this tree'}")
