@@ -322,7 +322,11 @@ int gpfq_quantize_dense_layer(const float *X, const float *Xq, int64_t ld, const
  * row norms and the record pre-pass on the activations alone.  gpfq_dense_layer_prepare (status block, row norms when nrm32 is NULL, record
  * pre-pass) may run on one stream while gpfq_median_abs + gpfq_layer_alphabet_device run on another; gpfq_dense_layer_run (for symmetric
  * alphabets one in-place pass over the records, then the kernel) follows once both are done, on the same workspace.  Same results as the
- * one-call form, bit for bit (quantized_neural_networks_amd/layer.py: quantize_dense_layer).
+ * one-call form, bit for bit (quantized_neural_networks_amd/layer.py: quantize_dense_layer).  The two calls read the options once each:
+ * gpfq_dense_layer_run on a workspace that gpfq_dense_layer_prepare laid out for another kernel shape (the options changed in between)
+ * returns GPFQ_ERR_INVALID_ARG and launches nothing.  The check is a host-side note of this process, keyed by the workspace pointer, of
+ * the last 64 workspaces prepared: a workspace it holds no note of (prepared by another process, copied to another address, or prepared
+ * more than 64 workspaces ago) is NOT checked and runs on the caller's word, as every workspace did before the check existed.
  */
 int gpfq_dense_layer_prepare(const float *X, const float *Xq, int64_t ld, const float *nrm32, const double *unit_alphabet, int M,
                              int64_t N, int64_t m, int64_t C, void *workspace, size_t workspace_bytes, void *stream);

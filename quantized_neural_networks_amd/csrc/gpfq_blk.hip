@@ -28,7 +28,8 @@
 // Layout: slot record t = [statistics of step t + Gram band of row t][X_{t-B}][Xq_{t-B}][Xq_{t+B} as float64],
 // zero-padded; a tile = the B records of a slot, streamed into the other LDS buffer by LDS-DMA during the slot -- one 1 KiB
 // piece at a time from inside the sweep's update phase (scalar addressing): issued back to back at the top of the slot the
-// pieces filled the vector-memory queue and stalled every sweep ~1000 cycles per slot.
+// pieces filled the vector-memory queue and stalled every sweep ~1000 cycles per slot.  (The classic form's eight-group rows take another tile: the same
+// rows wavefront-major, without the headers -- blk_rec_map, the one description of both formats.)
 //
 // Shapes: the instantiations the library ships are the rows of ONE table, kBlkInst below; blk_shape chooses among them by the rows'
 // length and the layer's width, blk_instance resolves a call to its row.  What bounds a slot: the sweeps (nine sample pairs on three of
@@ -36,6 +37,7 @@
 // (s_setprio) because it shares its SIMD with two sweep wavefronts, and the sweeps lower theirs as they progress through the
 // slot.  Symmetric alphabets take the SYM instantiation (BlkK::sym_a).  profiles/r02/blk_phase_stamps.txt has the per-phase
 // cycle counts (diagnostic build: GPFQ_DIAG="-DGPFQ_BLK_STAMPS").
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstring>
@@ -76,6 +78,65 @@ __host__ __device__ constexpr bool blk_row64(int G, int B) { return B > 1 && G >
 // (record skews against LDS bank conflicts were measured twice and bought nothing: DESIGN_HISTORY.md, "gpfq_blk.hip notes" 1)
 __host__ __device__ constexpr int64_t blk_rec_bytes(int64_t mp, int B, int G, bool CL = false) { return blk_hdr_bytes(B, CL) + (blk_row64(G, B) ? 16 : 12) * mp; }
 
+// ---- the record stream: ONE description (pre-passes, scaling pass, kernel, LDS carve-up, host sizing) ----
+// Two formats.  The classic one is the record of the layout note above, record by record, a tile = B records.  The eight-group rows of
+// kBlkInst (blk_own_rows) take a WAVEFRONT-MAJOR tile without headers: [unit U of the row][step s][X 128 B | Xq 128 B | Xq_{t+B} float64
+// 256 B], a unit being the 32 consecutive samples the eight k-lanes of a sweep wavefront read with one ds_read_b128 per row.  A sweep
+// wavefront's samples are one run of the row (kBlkInst's split), so its units are one run of the tile -- PW / 2 units x B steps x 512 bytes,
+// PW KiB where B = 4 -- and it streams exactly the bytes it reads itself: its rows of the next tile are valid behind its own dma_wait().
+// The record headers travel in the compact header stream alone (the decision wavefront's ring).  A tile of 1024 samples is 64 KiB.
+// kOwnRowsShip: two bits per form, bits 0-1 the classic form, bits 2-3 the cluster form's slices.  The low bit: the form's eight-group row
+// takes these tiles.  The high bit (needs the low one): the eight tile-sourced requests of a slot's top go out in front of the slot's
+// barrier (blk_sweep_role, kEarly).  -DGPFQ_BLK_OWN_ROWS=n builds another setting (records: profiles/own_rows/README.md).
+// What ships: both bits for the classic form; the cluster form's slices keep the classic records -- the layout is a property of the row --
+// because under the new ones the slice kernel spills nine more scalar registers (profiles/own_rows/blk_resource_usage.txt).
+constexpr int kOwnRowsShip = 3 + 4 * 0;
+#ifdef GPFQ_BLK_OWN_ROWS
+constexpr int kOwnRows = GPFQ_BLK_OWN_ROWS;
+#else
+constexpr int kOwnRows = kOwnRowsShip;
+#endif
+__host__ __device__ constexpr bool blk_own_rows(int G, bool CL = false) { return G == 8 && ((kOwnRows >> (CL ? 2 : 0)) & 1) != 0; }
+__host__ __device__ constexpr bool blk_own_early(int G, bool CL = false) { return blk_own_rows(G, CL) && ((kOwnRows >> (CL ? 3 : 1)) & 1) != 0; }
+struct BlkOwn {                                  // byte offsets inside a (unit, step) group and its size
+    static constexpr int kUnit = 32, kX = 0, kQ = 128, kD = 256, kStep = 512;
+    // Sample w (0 .. 31) of the unit in the float64 row of step s.  A k-lane's four samples are 32 bytes; the sweep reads the row of step
+    // lane & 3 (the matrix instruction's operand map), so a lane group of a ds_read_b128 holds four k-lanes of each of the four steps, whose
+    // groups lie kStep -- a whole number of turns round the 64 banks -- apart: the odd steps keep their k-lanes' 32-byte slots in the other
+    // half of the row (k-lane ^ 4), which leaves the two-way conflict the classic records have (their step pitch is half a turn) and not four.
+    __host__ __device__ static constexpr int d_off(int w, int s) { return kD + 32 * ((w / 4) ^ (4 * (s & 1))) + 8 * (w % 4); }
+};
+struct BlkRecMap {
+    int own;                    // 1: wavefront-major tiles
+    int hdr, mps;               // classic: header bytes; samples of a record row (of a slice's)
+    int64_t rec_bytes;          // classic: bytes of a record
+    int64_t tile_bytes;         // bytes of a tile of B steps
+    int64_t nrows;              // records whose rows the stream holds (classic: one more than the walk's slots need -- the DMA's over-read)
+    int64_t stream_bytes;       // bytes of a (slice's) record stream
+    // byte offset of sample i (row t - B: x, q; row t + B: d as float64, d32 as float32) of record t
+    __host__ __device__ int64_t grp(int64_t t, int i, int B) const { return (t / B) * tile_bytes + ((int64_t)(i / BlkOwn::kUnit) * B + t % B) * BlkOwn::kStep; }
+    __host__ __device__ int64_t x(int64_t t, int i, int B) const { return own ? grp(t, i, B) + BlkOwn::kX + 4 * (i % BlkOwn::kUnit) : t * rec_bytes + hdr + 4 * (int64_t)i; }
+    __host__ __device__ int64_t q(int64_t t, int i, int B) const { return own ? grp(t, i, B) + BlkOwn::kQ + 4 * (i % BlkOwn::kUnit) : t * rec_bytes + hdr + 4 * ((int64_t)mps + i); }
+    __host__ __device__ int64_t d(int64_t t, int i, int B) const { return own ? grp(t, i, B) + BlkOwn::d_off(i % BlkOwn::kUnit, (int)(t % B)) : t * rec_bytes + hdr + 8 * ((int64_t)mps + i); }
+    __host__ __device__ int64_t d32(int64_t t, int i) const { return t * rec_bytes + hdr + 8 * (int64_t)mps + 4 * (int64_t)i; }   // (classic only: blk_row64)
+};
+__host__ __device__ constexpr int64_t blk_tile_bytes(int64_t mp, int B, int G, bool CL = false)
+{
+    return blk_own_rows(G, CL) ? (mp / BlkOwn::kUnit) * B * BlkOwn::kStep : B * blk_rec_bytes(mp, B, G, CL);
+}
+// nblk blocks of the walk: slots 0 .. nblk
+__host__ __device__ inline BlkRecMap blk_rec_map(int64_t nblk, int mps, int B, int G, bool CL)
+{
+    BlkRecMap M;
+    M.own = blk_own_rows(G, CL) ? 1 : 0;
+    M.hdr = blk_hdr_bytes(B, CL); M.mps = mps;
+    M.rec_bytes = blk_rec_bytes(mps, B, G, CL);
+    M.tile_bytes = blk_tile_bytes(mps, B, G, CL);
+    M.nrows = (nblk + 1) * B + (M.own ? 0 : 1);
+    M.stream_bytes = M.own ? (nblk + 1) * M.tile_bytes : M.nrows * M.rec_bytes;
+    return M;
+}
+
 // ---- pre-pass ---------------------------------------------------------------------------------
 // One workgroup per slot record t: statistics of row t, its Gram band against rows t-1 .. t-(2B-1), float32 copies
 // of rows t-B, the float64 copy of Xq row t+B; zero-padded to mp samples.  One pass over the samples with all 3 + 4 (2B-1)
@@ -85,23 +146,20 @@ template <int B, bool R64, bool CL = false>
 __global__ void __launch_bounds__(256)
 gpfq_blk_prep_kernel(const float *__restrict__ X, const float *__restrict__ Xq, int64_t ld, int64_t N, int m, int mp,
                      const float *__restrict__ nrm32, char *__restrict__ recs, char *__restrict__ hdrs,
-                     const DevAlphabet *__restrict__ alpha, int sym, int nsl, int64_t slice_bytes)
+                     const DevAlphabet *__restrict__ alpha, int sym, int nsl, int64_t slice_bytes, BlkRecMap RM)
 {
     // (symmetric form, BlkK: the records hold f32(a32 Xq) in place of Xq; a32 comes from the device alphabet)
     const float sym_a = sym ? alpha->sym_a : 0.f;
     // (cluster form, nsl > 1: mp = nsl record rows of mp / nsl samples each, slice s's record stream slice_bytes behind slice s - 1's;
     //  the statistics and the Gram band are the whole row's and go into every slice's record)
-    constexpr int GREC = R64 ? 2 : 1;                         // (any G with this row format: the record size depends on nothing else)
     constexpr int ND = blk_band(B, CL), NV = 3 + 4 * ND;
     constexpr int DN = CL ? 2 * B : B;                        // the float64 row of a record: row t + DN (cluster form: two slots ahead)
     __shared__ double sm[4][((NV + 3) & ~3) + 1];
     const int64_t t = blockIdx.x;
     constexpr int hdr = blk_hdr_bytes(B, CL);
     const int mps = nsl > 1 ? mp / nsl : mp;                  // samples of a record row
-    char *rb = recs + t * blk_rec_bytes(mps, B, GREC, CL);
-    float  *ox = reinterpret_cast<float *>(rb + hdr);
-    float  *oq = ox + mps;
-    double *od = reinterpret_cast<double *>(rb + hdr + 8 * (int64_t)mps);
+    char *rb = recs + t * RM.rec_bytes;                       // (classic format: the record's header)
+    const bool rows = t < RM.nrows;                           // (wavefront-major tiles: no record behind the last slot's)
     const bool has_prev = t >= B && t - B < N, has_cur = t < N, has_next = t + DN < N;
     const float *px = X + (t - B) * ld, *pq = Xq + (t - B) * ld;
     const float *cx = X + t * ld, *cq = Xq + t * ld;
@@ -141,16 +199,17 @@ gpfq_blk_prep_kernel(const float *__restrict__ X, const float *__restrict__ Xq, 
 #pragma unroll
             for (int d = 1; d <= ND; ++d) { bx4[d - 1] = row(X, t - d); bq4[d - 1] = row(Xq, t - d); }
             const int sl = nsl > 1 ? i / mps : 0, il = i - sl * mps;      // slice and sample of the slice (mps is a multiple of four)
-            const int64_t so = (int64_t)sl * slice_bytes;
-            float *oxs = reinterpret_cast<float *>(reinterpret_cast<char *>(ox) + so), *oqs = reinterpret_cast<float *>(reinterpret_cast<char *>(oq) + so);
-            double *ods = reinterpret_cast<double *>(reinterpret_cast<char *>(od) + so);
-            *reinterpret_cast<float4 *>(oxs + il) = xp;
-            *reinterpret_cast<float4 *>(oqs + il) = sym_a != 0.f ? make_float4(__fmul_rn(sym_a, qp.x), __fmul_rn(sym_a, qp.y), __fmul_rn(sym_a, qp.z), __fmul_rn(sym_a, qp.w)) : qp;
-            if constexpr (R64) {
-                *reinterpret_cast<double2 *>(ods + il) = make_double2((double)qn.x, (double)qn.y);
-                *reinterpret_cast<double2 *>(ods + il + 2) = make_double2((double)qn.z, (double)qn.w);
-            } else {
-                *reinterpret_cast<float4 *>(reinterpret_cast<float *>(ods) + il) = qn;
+            char *rs = recs + (int64_t)sl * slice_bytes;
+            if (rows) {
+                *reinterpret_cast<float4 *>(rs + RM.x(t, il, B)) = xp;
+                *reinterpret_cast<float4 *>(rs + RM.q(t, il, B)) = sym_a != 0.f ? make_float4(__fmul_rn(sym_a, qp.x), __fmul_rn(sym_a, qp.y), __fmul_rn(sym_a, qp.z), __fmul_rn(sym_a, qp.w)) : qp;
+                if constexpr (R64) {
+                    double2 *od2 = reinterpret_cast<double2 *>(rs + RM.d(t, il, B));
+                    od2[0] = make_double2((double)qn.x, (double)qn.y);
+                    od2[1] = make_double2((double)qn.z, (double)qn.w);
+                } else {
+                    *reinterpret_cast<float4 *>(rs + RM.d32(t, il)) = qn;
+                }
             }
             float b1[ND], b2[ND];
 #pragma unroll
@@ -170,13 +229,13 @@ gpfq_blk_prep_kernel(const float *__restrict__ X, const float *__restrict__ Xq, 
         for (int i = threadIdx.x; i < mp; i += 256) {
             const bool in = i < m;
             const int sl = nsl > 1 ? i / mps : 0, il = i - sl * mps;
-            const int64_t so = (int64_t)sl * slice_bytes;
-            float *oxs = reinterpret_cast<float *>(reinterpret_cast<char *>(ox) + so), *oqs = reinterpret_cast<float *>(reinterpret_cast<char *>(oq) + so);
-            double *ods = reinterpret_cast<double *>(reinterpret_cast<char *>(od) + so);
-            oxs[il] = (has_prev && in) ? px[i] : 0.f;
-            oqs[il] = (has_prev && in) ? (sym_a != 0.f ? __fmul_rn(sym_a, pq[i]) : pq[i]) : 0.f;   // symmetric form: f32(a Xq), see BlkK::sym_a
-            if constexpr (R64) ods[il] = (double)((has_next && in) ? nq[i] : 0.f);
-            else reinterpret_cast<float *>(ods)[il] = (has_next && in) ? nq[i] : 0.f;
+            char *rs = recs + (int64_t)sl * slice_bytes;
+            if (rows) {
+                *reinterpret_cast<float *>(rs + RM.x(t, il, B)) = (has_prev && in) ? px[i] : 0.f;
+                *reinterpret_cast<float *>(rs + RM.q(t, il, B)) = (has_prev && in) ? (sym_a != 0.f ? __fmul_rn(sym_a, pq[i]) : pq[i]) : 0.f;   // symmetric form: f32(a Xq), see BlkK::sym_a
+                if constexpr (R64) *reinterpret_cast<double *>(rs + RM.d(t, il, B)) = (double)((has_next && in) ? nq[i] : 0.f);
+                else *reinterpret_cast<float *>(rs + RM.d32(t, il)) = (has_next && in) ? nq[i] : 0.f;
+            }
             if (has_cur && in) {
                 float b1[ND], b2[ND];
 #pragma unroll
@@ -213,14 +272,14 @@ gpfq_blk_prep_kernel(const float *__restrict__ X, const float *__restrict__ Xq, 
 #pragma unroll
         for (int d = 1; d <= ND; ++d) { e1 += total(5 + 4 * (d - 1)); e2 += total(6 + 4 * (d - 1)); }
         st.sE1 = 0x1p-23 * e1 * up * up; st.sE2 = 0x1p-23 * e2 * up * up;
-        for (int sl = 0; sl < (nsl > 1 ? nsl : 1); ++sl) *reinterpret_cast<BlkStats *>(rb + (int64_t)sl * slice_bytes) = st;
+        for (int sl = 0; sl < (nsl > 1 ? nsl : 1) && !RM.own; ++sl) *reinterpret_cast<BlkStats *>(rb + (int64_t)sl * slice_bytes) = st;
         *reinterpret_cast<BlkStats *>(hdrs + t * hdr) = st;
     } else if (threadIdx.x <= ND) {
         const int d = threadIdx.x;
         BandEntry e;
         e.H1 = total(3 + 4 * (d - 1)); e.H2 = total(4 + 4 * (d - 1));
         e.E1 = 0x1p-23 * total(5 + 4 * (d - 1)) * up; e.E2 = 0x1p-23 * total(6 + 4 * (d - 1)) * up;
-        for (int sl = 0; sl < (nsl > 1 ? nsl : 1); ++sl) *reinterpret_cast<BandEntry *>(rb + (int64_t)sl * slice_bytes + 64 + 32 * (d - 1)) = e;
+        for (int sl = 0; sl < (nsl > 1 ? nsl : 1) && !RM.own; ++sl) *reinterpret_cast<BandEntry *>(rb + (int64_t)sl * slice_bytes + 64 + 32 * (d - 1)) = e;
         *reinterpret_cast<BandEntry *>(hdrs + t * hdr + 64 + 32 * (d - 1)) = e;
     }
 }
@@ -237,9 +296,8 @@ template <int B, bool R64>
 __global__ void __launch_bounds__(256)
 gpfq_blk_prep_run_kernel(const float *__restrict__ X, const float *__restrict__ Xq, int64_t ld, int64_t N, int m, int mp, int64_t nrec, int RUN,
                          const float *__restrict__ nrm32, char *__restrict__ recs, char *__restrict__ hdrs,
-                         const DevAlphabet *__restrict__ alpha, int sym, unsigned *__restrict__ zero16)
+                         const DevAlphabet *__restrict__ alpha, int sym, unsigned *__restrict__ zero16, BlkRecMap RM)
 {
-    constexpr int GREC = R64 ? 2 : 1;
     constexpr int ND = blk_band(B), NV = 3 + 4 * ND, NP = (NV + 3) & ~3;
     constexpr int hdr = blk_hdr_bytes(B);
     __shared__ double sm[kPrepRunMax][4][NP + 1];
@@ -255,7 +313,7 @@ gpfq_blk_prep_run_kernel(const float *__restrict__ X, const float *__restrict__ 
     for (int k = threadIdx.x; k < RUN * 4 * (NP + 1); k += 256) (&sm[0][0][0])[k] = 0.0;     // (RUN: a launch parameter, <= kPrepRunMax)
     __syncthreads();
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int64_t rbytes = blk_rec_bytes(mp, B, GREC);
+    const int64_t rbytes = RM.rec_bytes;
     for (int i = 4 * threadIdx.x; i < mp; i += 1024) {
         auto row = [&](const float *base, int64_t r) -> float4 {
             if (r < 0 || r >= N || i >= m) return z4;
@@ -274,18 +332,16 @@ gpfq_blk_prep_run_kernel(const float *__restrict__ X, const float *__restrict__ 
             const int64_t t = t0 + r;
             // (the next record's three rows: requested before this record's arithmetic)
             const float4 xc1 = r + 1 < RUN ? row(X, t + 1) : z4, qc1 = r + 1 < RUN ? row(Xq, t + 1) : z4, qn1 = r + 1 < RUN ? row(Xq, t + 1 + B) : z4;
-            if (t < nrec) {
-                char *rb = recs + t * rbytes;
-                float *ox = reinterpret_cast<float *>(rb + hdr), *oq = ox + mp;
+            if (t < nrec && t < RM.nrows) {
                 const float4 xp = wx[B - 1], qp = wq[B - 1];      // rows t - B
-                *reinterpret_cast<float4 *>(ox + i) = xp;
-                *reinterpret_cast<float4 *>(oq + i) = sym_a != 0.f ? make_float4(__fmul_rn(sym_a, qp.x), __fmul_rn(sym_a, qp.y), __fmul_rn(sym_a, qp.z), __fmul_rn(sym_a, qp.w)) : qp;
+                *reinterpret_cast<float4 *>(recs + RM.x(t, i, B)) = xp;
+                *reinterpret_cast<float4 *>(recs + RM.q(t, i, B)) = sym_a != 0.f ? make_float4(__fmul_rn(sym_a, qp.x), __fmul_rn(sym_a, qp.y), __fmul_rn(sym_a, qp.z), __fmul_rn(sym_a, qp.w)) : qp;
                 if constexpr (R64) {
-                    double *od = reinterpret_cast<double *>(rb + hdr + 8 * (int64_t)mp);
-                    *reinterpret_cast<double2 *>(od + i) = make_double2((double)qn.x, (double)qn.y);
-                    *reinterpret_cast<double2 *>(od + i + 2) = make_double2((double)qn.z, (double)qn.w);
+                    double2 *od2 = reinterpret_cast<double2 *>(recs + RM.d(t, i, B));
+                    od2[0] = make_double2((double)qn.x, (double)qn.y);
+                    od2[1] = make_double2((double)qn.z, (double)qn.w);
                 } else {
-                    *reinterpret_cast<float4 *>(reinterpret_cast<float *>(rb + hdr + 8 * (int64_t)mp) + i) = qn;
+                    *reinterpret_cast<float4 *>(recs + RM.d32(t, i)) = qn;
                 }
             }
             if (own_norms) {
@@ -358,14 +414,14 @@ gpfq_blk_prep_run_kernel(const float *__restrict__ X, const float *__restrict__ 
 #pragma unroll
             for (int d = 1; d <= ND; ++d) { e1 += total(5 + 4 * (d - 1)); e2 += total(6 + 4 * (d - 1)); }
             st.sE1 = 0x1p-23 * e1 * up * up; st.sE2 = 0x1p-23 * e2 * up * up;
-            *reinterpret_cast<BlkStats *>(rb) = st;
+            if (!RM.own) *reinterpret_cast<BlkStats *>(rb) = st;
             *reinterpret_cast<BlkStats *>(hdrs + t * hdr) = st;
         } else {
             const int d = e;
             BandEntry be;
             be.H1 = total(3 + 4 * (d - 1)); be.H2 = total(4 + 4 * (d - 1));
             be.E1 = 0x1p-23 * total(5 + 4 * (d - 1)) * up; be.E2 = 0x1p-23 * total(6 + 4 * (d - 1)) * up;
-            *reinterpret_cast<BandEntry *>(rb + 64 + 32 * (d - 1)) = be;
+            if (!RM.own) *reinterpret_cast<BandEntry *>(rb + 64 + 32 * (d - 1)) = be;
             *reinterpret_cast<BandEntry *>(hdrs + t * hdr + 64 + 32 * (d - 1)) = be;
         }
     }
@@ -374,13 +430,16 @@ gpfq_blk_prep_run_kernel(const float *__restrict__ X, const float *__restrict__ 
 // Symmetric form, two-phase calls (gpfq_dense_layer_prepare / _run): the pre-pass ran before the alphabet existed and left Xq_{t-B} as it
 // is; this pass multiplies those rows by a32 in place (the same single float32 product the fused pre-pass forms).  grid (records, slices).
 __global__ void __launch_bounds__(256)
-gpfq_blk_scale_kernel(char *__restrict__ recs, int64_t rec_bytes, int hdr, int mps, int64_t slice_bytes, const DevAlphabet *__restrict__ alpha)
+gpfq_blk_scale_kernel(char *__restrict__ recs, BlkRecMap RM, int B, int64_t slice_bytes, const DevAlphabet *__restrict__ alpha)
 {
+    const int64_t t = blockIdx.x;
+    if (t >= RM.nrows) return;
     const float a = alpha->sym_a;
-    float4 *row = reinterpret_cast<float4 *>(recs + (int64_t)blockIdx.y * slice_bytes + (int64_t)blockIdx.x * rec_bytes + hdr + 4 * (int64_t)mps);
-    for (int i = threadIdx.x; i < mps / 4; i += 256) {
-        const float4 v = row[i];
-        row[i] = make_float4(__fmul_rn(a, v.x), __fmul_rn(a, v.y), __fmul_rn(a, v.z), __fmul_rn(a, v.w));
+    char *base = recs + (int64_t)blockIdx.y * slice_bytes;
+    for (int i = threadIdx.x; i < RM.mps / 4; i += 256) {
+        float4 *p = reinterpret_cast<float4 *>(base + RM.q(t, 4 * i, B));
+        const float4 v = *p;
+        *p = make_float4(__fmul_rn(a, v.x), __fmul_rn(a, v.y), __fmul_rn(a, v.z), __fmul_rn(a, v.w));
     }
 }
 
@@ -406,7 +465,7 @@ __host__ __device__ inline BlkLds blk_lds(int mp, int nb, int B, int nsw, int G,
 {
     BlkLds L;
     const int nw = blk_slots(nsw, nb);
-    L.tile_bytes = B * (int)blk_rec_bytes(mp, B, G, CL);
+    L.tile_bytes = (int)blk_tile_bytes(mp, B, G, CL);
     L.tile_pitch = (L.tile_bytes + 1023) & ~1023;               // the DMA moves whole 1 KiB pieces
     int o = 2 * L.tile_pitch;
     L.off_w = o;    o += 2 * nb * B * 4;    o = (o + 15) & ~15; // [2][NB][B] f32        weights of the block
@@ -715,13 +774,21 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
     constexpr int PU = G == 8 ? 2 : 1;
     static_assert(PW % PU == 0, "whole units per wavefront");
     auto pair_off = [](int p) { return PU * (p / PU) * KQ + p % PU; };
-    const int o_x  = HDR + 8 * (pbase + PU * kq);                 // float2 x   [pair]  (row t - B of record t)
-    int o_q = o_x + 4 * MP;                                       // float2 xq  [pair]
+    // (kOwn: the wavefront-major tile of blk_rec_map -- the wavefront's units are one run of it, from byte `wown` on; a unit's step is
+    //  BlkOwn::kStep bytes, a lane's sixteen bytes of a row sit at 16 kq, its 32 bytes of the float64 row at 32 kq.  SB: bytes from a step
+    //  of a unit to the next; UB: from a unit's row to the next unit's, float32 and float64)
+    constexpr bool kOwn = blk_own_rows(G, CL);
+    static_assert(!kOwn || (PU == 2 && KQ * 2 * PU == BlkOwn::kUnit && blk_row64(G, B)), "a unit is what the k-lanes read with one 16-byte request each");
+    constexpr int SB = kOwn ? BlkOwn::kStep : RB;
+    constexpr int UB32 = kOwn ? B * BlkOwn::kStep : 8 * PU * KQ, UB64 = kOwn ? B * BlkOwn::kStep : (blk_row64(G, B) ? 16 : 8) * PU * KQ;
+    const int wown = (2 * pbase / BlkOwn::kUnit) * B * BlkOwn::kStep;
+    const int o_x  = kOwn ? wown + BlkOwn::kX + 16 * kq : HDR + 8 * (pbase + PU * kq);   // float2 x   [pair]  (row t - B of record t)
+    int o_q = kOwn ? wown + BlkOwn::kQ + 16 * kq : o_x + 4 * MP;  // float2 xq  [pair]
     // (opaque to the compiler: it would fuse the x and xq reads of a pair -- 4 MP bytes apart -- into ONE ds_read2st64_b64, which the
     //  LDS serves as two 32-bank accesses in 8 cycles; two ds_read_b64 take 2 cycles each: MI355X_MICROARCH.md, LDS)
     asm volatile("" : "+v"(o_q));
     constexpr int DB = blk_row64(G, B) ? 16 : 8;                  // bytes of a sample pair of row t + B
-    const int o_d  = HDR + 8 * MP + DB * (pbase + PU * kq);      // double2 (float2) xqd[pair]  (row t + B)
+    const int o_d  = kOwn ? wown + BlkOwn::d_off(4 * kq, lane & 3) : HDR + 8 * MP + DB * (pbase + PU * kq);   // double2 (float2) xqd[pair]  (row t + B)
     using DRaw = std::conditional_t<blk_row64(G, B), double2, float2>;   // as it sits in the record; converted where it is consumed
     auto ld_d = [&](int off) -> DRaw { return lds_ld<DRaw>(lds, off); };
     auto to_d2 = [](const DRaw &v) -> double2 { return make_double2((double)v.x, (double)v.y); };
@@ -742,13 +809,17 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
     // (the texture addresser moves 64 bytes per clock: 66 KiB per slot), and so does the wavefront it shares its SIMD with --
     // spread out, the queue never fills and the transfers hide under the arithmetic (measured: 4.86 -> 4.51 ms at
     // 4096 x 4096 x 1024, and with the decision wavefront's priority raised 4.17).
+    // (kOwn: a wavefront streams its OWN run of the tile and nothing else -- PW / 2 units of B steps, in the order it uses them: piece k is
+    //  piece wown / 1024 + k of the tile, two steps of a unit; a four-pair wavefront has four, a six-pair one six)
+    constexpr int OWNP = (PW / PU) * B * BlkOwn::kStep >> 10;     // (kOwn) this wavefront's pieces per tile
+    static_assert(!kOwn || (PW / PU) * B * BlkOwn::kStep % 1024 == 0, "a wavefront's run of the tile is whole 1 KiB pieces");
     constexpr int NPIECES = (B * RB + 1023) >> 10;
-    constexpr int PER_MIN = NPIECES / NSW;               // every wavefront has at least this many pieces per tile
+    constexpr int PER_MIN = kOwn ? OWNP : NPIECES / NSW; // every wavefront has at least this many pieces per tile
     constexpr int PTS = PW >= 2 ? 2 : 1;                          // issue points per step of phase U (its first pairs)
     constexpr int PPP = PER_MIN / (PTS * B) > 0 ? PER_MIN / (PTS * B) : 1;   // pieces per issue point
     const unsigned lane16 = (unsigned)lane * 16u;
     auto issue_piece = [&](int b1, int k) {
-        const int pc = wave + NSW * k;
+        const int pc = kOwn ? (wown >> 10) + k : wave + NSW * k;
         glds16_s(K.recs + (CL ? cs.rec_off : (int64_t)0) + (int64_t)b1 * L.tile_bytes + ((int64_t)pc << 10), lane16,
                  ldsT_addr + (unsigned)(b1 & 1) * (unsigned)L.tile_pitch + ((unsigned)pc << 10));
     };
@@ -770,7 +841,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
             glds16_s(K.hdrs + (int64_t)b2 * B * HDR + ((int64_t)wave << 10), lane16,
                      lds_addr(lds_generic + L.off_hr) + (unsigned)buf * (unsigned)L.hr_pitch + ((unsigned)wave << 10));
     };
-    for (int k = 0; wave + NSW * k < NPIECES; ++k) issue_piece(0, k);
+    for (int k = 0; kOwn ? k < OWNP : wave + NSW * k < NPIECES; ++k) issue_piece(0, k);
     load_weights(0);
     load_headers(0, 0); load_headers(1, 1);
     dma_wait();
@@ -802,6 +873,16 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
     // (eight neuron groups, kPrio's low bit of the form) the slot top's issue priority raised in front of the slot's barrier: see the barrier
     constexpr int kPrioForm = CL ? (kPrio >> 2) & 3 : kPrio & 3;   // (the cluster form's slices have a setting of their own)
     constexpr bool kPrioUp = kTopSym && G == 8 && (kPrioForm & 1) != 0;
+    // (kEarly, wavefront-major tiles: the eight requests of a slot's top that read rows of the record tile -- this wavefront's own pieces,
+    //  landed behind its own dma_wait() -- go out in front of the slot's barrier, slot_rows_early; behind it the top requests the block's
+    //  (w, q) alone, slot_top_sym2_late.  rows_early(b1): the requests for slot b1's top.)
+    constexpr bool kEarly = kTopSym && blk_own_early(G, CL);
+    [[maybe_unused]] auto rows_early = [&](int b1) {
+        if constexpr (kEarly) {
+            const int tb1 = (b1 & 1) * L.tile_pitch;
+            slot_rows_early<SB, BlkOwn::kQ - BlkOwn::kX>(lds + tb1 + o_x, lds + tb1 + (lane & 3) * SB + o_d);
+        }
+    };
     // ... and the two LDS-DMA pieces a slot owes besides its record pieces -- the header piece of tile b + 2, the weight piece of block
     // b + 1 -- issued from inside the pair loop instead of between the slot's barrier and its first LDS request, where every wavefront
     // of the CU waits for the same thing and nothing hides their address arithmetic (kLateHdr, kLateW: see the pair loop).  With two
@@ -884,9 +965,11 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                     double t0 = u[n][0], t1 = u[n][1];
 #pragma unroll
                     for (int pp = 1; pp < PW; ++pp) { t0 = (p == pp) ? u[n][2 * pp] : t0; t1 = (p == pp) ? u[n][2 * pp + 1] : t1; }
+                    // (the pair's eight bytes of a row: kOwn -- unit p / PU of the wavefront's run, half p % PU of the lane's sixteen bytes)
+                    const int po = kOwn ? (p / PU) * UB32 + 8 * (p % PU) : 8 * pair_off(p);
                     for (int j = 0; j < S; ++j) {
-                        const int rb = nb_ + j * RB;
-                        const float2 x2 = lds_ld<float2>(lds, rb + o_x + 8 * pair_off(p)), q2 = lds_ld<float2>(lds, rb + o_q + 8 * pair_off(p));
+                        const int rb = nb_ + j * SB;
+                        const float2 x2 = lds_ld<float2>(lds, rb + o_x + po), q2 = lds_ld<float2>(lds, rb + o_q + po);
                         const float2 wq = lds_ld<float2>(lds, o_wq + cbq + (n * B + j) * 8);
                         if constexpr (SYM) {
                             t0 += (double)__fmaf_rn(wq.y, q2.x, __fmul_rn(wq.x, x2.x));
@@ -896,8 +979,8 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                             t1 += (double)__fsub_rn(__fmul_rn(wq.x, x2.y), __fmul_rn(wq.y, q2.y));
                         }
                     }
-                    const int rb = nb_ + S * RB;
-                    const float2 x2 = lds_ld<float2>(lds, rb + o_x + 8 * pair_off(p));
+                    const int rb = nb_ + S * SB;
+                    const float2 x2 = lds_ld<float2>(lds, rb + o_x + po);
                     float2 q2;
                     if constexpr (SYM) {                              // the record holds a32 * Xq_t: the row itself from memory (rare path)
                         const int i0 = 2 * (pbase + pair_off(p) + PU * kq);
@@ -906,7 +989,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                         q2.x = i0 < mrow ? xr[i0] : 0.f;
                         q2.y = i0 + 1 < mrow ? xr[i0 + 1] : 0.f;
                     } else {
-                        q2 = lds_ld<float2>(lds, rb + o_q + 8 * pair_off(p));
+                        q2 = lds_ld<float2>(lds, rb + o_q + po);
                     }
                     eu[n] = fma((double)q2.x, t0, eu[n]);
                     eu[n] = fma((double)q2.y, t1, eu[n]);
@@ -927,6 +1010,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
     // header on paper, made the slot's first wait for an LDS read a full lgkmcnt(0) where a count would do (scalar loads answer out of
     // order) and put a vmcnt(0) between the slot's first requests that waits for the LDS-DMA pieces issued just before them.
     if constexpr (kBatchTop) __builtin_amdgcn_s_waitcnt(0);
+    if constexpr (kEarly) rows_early(0);                          // (slot 0 enters through all twelve requests: these eight, then its top's four)
     for (int b = 0; b < nslots; ++b) {
         STAMP(st0);
         STAMP_DO(if (b) acc_t += st0 - st5;)   // from the barrier to the top of the next slot: control word, next operands
@@ -1065,7 +1149,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
             // (The slot's first requests stay BEHIND the wait for the slow path's control word: hoisted in front of it -- with the slow
             //  path inlined, round 4, or as an out-of-line call without a spill, round 5 -- the kernel is 10-20 % slower:
             //  DESIGN_HISTORY.md, "gpfq_blk.hip notes" 5; profiles/r05/blk_variants_ab.txt.)
-            const int rbm = tbase + (G == 8 ? lane & 3 : ng) * RB + o_d;  // (the matrix instruction's column j: the row of step lane & 3 -- which is ng where G = 4)
+            const int rbm = tbase + (G == 8 ? lane & 3 : ng) * SB + o_d;  // (the matrix instruction's column j: the row of step lane & 3 -- which is ng where G = 4)
             // Operand rows are requested PF pair-steps ahead of their use: one everywhere -- except in the seven-sweep-wavefront shapes (two
             // wavefronts per SIMD, 256 registers), where a pair-step's handful of instructions no longer covers an LDS round trip and the
             // sweep's own chain of them would become the slot: two (round 5).
@@ -1092,7 +1176,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
             float2 fwq[B][NL];
             XRow xbuf[PF], qbuf[PF];
             DRow dcur;
-            auto row_off = [&](int i, bool q) { return tbase + (i % B) * RB + (q ? o_q : o_x) + 8 * PU * (i / B) * KQ; };   // pair-step i = unit * B + step
+            auto row_off = [&](int i, bool q) { return tbase + (i % B) * SB + (q ? o_q : o_x) + UB32 * (i / B); };   // pair-step i = unit * B + step
             auto ld_drow = [&](int off) -> DRow {
                 if constexpr (PU == 2) return DRow{{lds_ld<double2>(lds, off), lds_ld<double2>(lds, off + 16)}};
                 else return lds_ld<double2>(lds, off);
@@ -1114,8 +1198,12 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                 nf4 w01[2], w23[2], x2n, q2n;
                 nd2 d01[2];
                 __builtin_amdgcn_s_setprio(2);
-                slot_top_sym2<RB>(w01, w23, x2n, q2n, d01, u[0][0], u[0][1], u[0][2], u[0][3], u[1][0], u[1][1], u[1][2], u[1][3],
-                                  lds + row_off(0, false), lds + row_off(0, true), lds + o_wq + pbq, lds + rbm);
+                if constexpr (kEarly) {
+                    slot_top_sym2_late(w01, w23, x2n, q2n, d01, u[0][0], u[0][1], u[0][2], u[0][3], u[1][0], u[1][1], u[1][2], u[1][3], lds + o_wq + pbq);
+                } else {
+                    slot_top_sym2<SB>(w01, w23, x2n, q2n, d01, u[0][0], u[0][1], u[0][2], u[0][3], u[1][0], u[1][1], u[1][2], u[1][3],
+                                      lds + row_off(0, false), lds + row_off(0, true), lds + o_wq + pbq, lds + rbm);
+                }
                 __builtin_amdgcn_s_waitcnt(0xC07F);            // (lgkmcnt(0) alone, for hipcc's waitcnt pass: see below)
                 __builtin_memcpy(&xbuf[0], &x2n, sizeof(XRow)); __builtin_memcpy(&qbuf[0], &q2n, sizeof(XRow));   // the rows of pair-step 2
                 if constexpr (kRows2) { xbuf[PF - 1] = lds_ld<XRow>(lds, row_off(3, false)); qbuf[PF - 1] = lds_ld<XRow>(lds, row_off(3, true)); }
@@ -1230,7 +1318,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                         else __builtin_amdgcn_s_setprio(0);
                     }
                 }
-                if (p > 0) dcur = ld_drow(rbm + DB * PU * p * KQ);               // (consumed under the NEXT pair's updates, or at the end)
+                if (p > 0) dcur = ld_drow(rbm + UB64 * p);               // (consumed under the NEXT pair's updates, or at the end)
 #pragma unroll
                 for (int st = 0; st < B; ++st) {
                     const int ips = p * B + st;                                  // this pair-step; its operands sit in buffer ips % PF
@@ -1304,7 +1392,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                 }
                 dprev = dcur;
             }
-            for (int k = PTS * B * PPP < PER_MIN ? PTS * B * PPP : PER_MIN; wave + NSW * k < NPIECES; ++k) issue_piece(bn, k);   // the rest
+            for (int k = PTS * B * PPP < PER_MIN ? PTS * B * PPP : PER_MIN; kOwn ? k < OWNP : wave + NSW * k < NPIECES; ++k) issue_piece(bn, k);   // the rest
             STAMP(st2);
 #pragma unroll
             for (int i = 0; i < NM; ++i) mfma_pair(NU - 1, i, dprev);
@@ -1400,7 +1488,7 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
                 }
             }
         }
-        for (int k = PTS * B * PPP < PER_MIN ? PTS * B * PPP : PER_MIN; wave + NSW * k < NPIECES; ++k) issue_piece(bn, k);   // the rest
+        for (int k = PTS * B * PPP < PER_MIN ? PTS * B * PPP : PER_MIN; kOwn ? k < OWNP : wave + NSW * k < NPIECES; ++k) issue_piece(bn, k);   // the rest
         STAMP(st2);
         // ---- phase D: this wavefront's share of <Xq_t, u> for the B rows of block b+1 ----
         if constexpr (kMfmaD) {
@@ -1507,7 +1595,14 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
         // (kPrioUp) The level of the next slot's top, set here: the control word's round trip, its test, the branch and the loop's scalar
         // control then run at one level in all the sweep wavefronts of a SIMD, whichever left the barrier first (the slow path too).
         if constexpr (kPrioUp) __builtin_amdgcn_s_setprio(2);
-        slot_barrier();
+        if constexpr (kEarly) {
+            // (the next slot's rows, requested here: slot_rows_early waits for this wavefront's LDS writes itself, so the barrier is the bare
+            //  instruction; the last slot has no next one)
+            if (b + 1 < nslots) { rows_early(b + 1); asm volatile("s_barrier" ::: "memory"); }
+            else slot_barrier();
+        } else {
+            slot_barrier();
+        }
         STAMP(st5);
         STAMP_DO(acc_dma += st1 - st0; acc_u += st2 - st1; acc_d += st3 - st2; acc_w += st4 - st3; acc_b += st5 - st4;)
 
@@ -1521,6 +1616,9 @@ __device__ __forceinline__ void blk_sweep_role(const BlkK &K, char *lds_generic,
         }
         if (__builtin_amdgcn_readfirstlane(ctl) >= 0) {
             slow_path(b, ctl);
+            if constexpr (kEarly) {
+                if (b + 1 < nslots) rows_early(b + 1);            // (the slow path ran through the rows' registers: requested again)
+            }
             if constexpr (kHoist) {
                 if (b + 1 < nslots) { preload_wq(b + 1); preload_rows(b + 1); }    // (the slow path has rewritten decisions of block b)
             }
@@ -1745,6 +1843,8 @@ __device__ __forceinline__ void blk_decision_role(const BlkK &K, char *lds_gener
     // behind the slot's stores instead (below).
     constexpr bool kHdrChain = NSW == 7;
     constexpr int BI = B > 1 ? B - 1 : 1, HDRB = blk_hdr_bytes(B, CL);
+    constexpr bool kOwnH = blk_own_rows(G, CL);
+    constexpr int HS = kOwnH ? HDRB : RB;
     // Only what the predicted dot products need: the bounds (E1, E2, cb, ca, Ea) are read from the tile in LDS while the chain
     // computes -- they are consumed by the certification after it, off the critical path.
     double2 g01 = make_double2(0.0, 0.0);                         // own step: (1/nrm^2, G)
@@ -1775,7 +1875,10 @@ __device__ __forceinline__ void blk_decision_role(const BlkK &K, char *lds_gener
     for (int b = 0; b < nslots; ++b) {
         STAMP(dt0);
         STAMP_DO(if (b) dacc_tail += dt0 - dt2;)   // after the barrier
-        const int tbase = (b & 1) * L.tile_pitch;
+        // The headers of tile b: in the tile itself -- or, where the tile holds none (kOwnH: blk_own_rows), in buffer b % 3 of the header
+        // ring, which is tile b's from two slots back until the sweeps overwrite it with tile b + 3's during slot b + 1.  hbase: step 0's,
+        // HS: bytes from a step's header to the next.
+        const int hbase = kOwnH ? L.off_hr + (hnext == 0 ? 2 : hnext - 1) * L.hr_pitch : (b & 1) * L.tile_pitch;
         const int cbq = (b & 1) * NB * B * 8;
         float  wc[B], qc[B];                                      // this block: weights, decisions (as float32 values)
         double D[B];
@@ -1828,7 +1931,7 @@ __device__ __forceinline__ void blk_decision_role(const BlkK &K, char *lds_gener
             if constexpr (CL) {
                 prefetch_headers(b % 3);                          // tile b's headers: buffer b % 3 of the ring
 #pragma unroll
-                for (int j = 0; j < B; ++j) hp2[j] = lds_ld<double2>(lds, tbase + sm * RB + 64 + 32 * (2 * B + sm - j - 1));
+                for (int j = 0; j < B; ++j) hp2[j] = lds_ld<double2>(lds, hbase + sm * HS + 64 + 32 * (2 * B + sm - j - 1));
             }
             if constexpr (kOwnFlush) {
                 if (flush_hi > flushed) {                         // (outputs of earlier slots: under the latency of the reads above)
@@ -1897,7 +2000,7 @@ __device__ __forceinline__ void blk_decision_role(const BlkK &K, char *lds_gener
 #pragma unroll
             for (int s = 0; s < B; ++s) A[s] = quad_bcast(Am, s);
             // the bounds of the own step, from the tile in LDS: requested now, consumed after the chain
-            const int rbm = tbase + sm * RB;
+            const int rbm = hbase + sm * HS;
             const double2 o23 = lds_ld<double2>(lds, rbm + 16);
             const double rEa = lds_ld<double>(lds, rbm + 32);
             const double2 o67 = lds_ld<double2>(lds, rbm + 48);   // (sE1, sE2): the quick certification's bound (below)
@@ -2123,7 +2226,7 @@ __device__ __forceinline__ void blk_decision_role(const BlkK &K, char *lds_gener
             double am[4];                                                        // (slow path only: not kept across the slots)
 #pragma unroll
             for (int q = 0; q < 4; ++q) am[q] = (IN_REGS && r + q * R < M) ? lds_ld<double>(lds, L.off_e + 8 * (2 + r + q * R)) : kNaN;
-            const int rb = tbase + s * RB;
+            const int rb = hbase + s * HS;
             const double2 r01 = lds_ld<double2>(lds, rb), r23 = lds_ld<double2>(lds, rb + 16), r45 = lds_ld<double2>(lds, rb + 32);
             const double rden = r01.x, rG = r01.y, rcb = r23.x, rca = r23.y, rEa = r45.x, nrm = r45.y;
             const bool rule1 = nrm < 1e-16;                                      // rule (i): literal 0
@@ -2244,7 +2347,7 @@ __device__ __forceinline__ void blk_decision_role(const BlkK &K, char *lds_gener
             const bool mine = active && stop == S;
             if (mine) {
                 const int64_t t = (int64_t)b * B + S;
-                const double nrm = lds_ld<double2>(lds, tbase + S * RB + 32).y;
+                const double nrm = lds_ld<double2>(lds, hbase + S * HS + 32).y;
                 float wS = 0.f;
 #pragma unroll
                 for (int s = 0; s < B; ++s) wS = (s == S) ? wc[s] : wS;
@@ -2553,10 +2656,10 @@ static BlkShape blk_shape(int64_t m, int64_t C, const Options &opt)
 // matrix instruction's partial sums, twice the operand reads -- blk_sweep_role, the kMfmaD note).  Option blk_groups forces one; left to
 // the shape it is kGroupsByShape: profiles/groups8/README.md has the measurement that decides it.
 constexpr int kGroupsByShape = 8;
+static bool blk_groups_shape(const BlkShape &sh) { return sh.G == 4 && sh.S == 32 && sh.B == 4 && sh.NW == 11 && sh.NL == 4; }   // (the shape alone: what sizes a workspace asks too)
 static int blk_groups(const BlkShape &sh, bool sym, const Options &opt)
 {
-    const bool applies = sym && sh.G == 4 && sh.S == 32 && sh.B == 4 && sh.NW == 11 && sh.NL == 4;
-    if (!applies) return 4;
+    if (!sym || !blk_groups_shape(sh)) return 4;
     return opt.blk_groups ? opt.blk_groups : kGroupsByShape;
 }
 
@@ -2580,9 +2683,15 @@ __global__ void gpfq_alphabet_device_kernel(DevAlphabet *out, const float *__res
 }
 
 // workspace: [records of slots 0..nblk, + one record of DMA over-read][compact headers of the same records, + 2 KiB of over-read]
+// (a shape's record area holds whichever format its call's row of kBlkInst takes -- blk_rec_map: the shape's own groups or, where
+//  blk_groups may resolve the shape to the eight-group row, that row's wavefront-major tiles -- so it is sized for the larger of the two,
+//  and the compact headers sit behind it at the same offset under either)
 static size_t blk_recs_bytes(int64_t nblk, const BlkShape &sh)          // (cluster form: of ONE slice)
 {
-    return ((size_t)((nblk + 1) * sh.B + 1) * (size_t)blk_rec_bytes(sh.mp, sh.B, sh.G, sh.NS != 0) + 255) & ~(size_t)255;
+    size_t need = (size_t)blk_rec_map(nblk, sh.mp, sh.B, sh.G, sh.NS != 0).stream_bytes;
+    if (blk_groups_shape(sh))
+        need = std::max(need, (size_t)blk_rec_map(nblk, sh.mp, sh.B, 8, sh.NS != 0).stream_bytes);
+    return (need + 255) & ~(size_t)255;
 }
 // cluster form: the exchange buffers, [cluster][2][slice][64 lanes][4 words]; clusters in whole groups of eight
 static int64_t blk_clusters(int64_t C, const BlkShape &sh) { return (((C + sh.NL * sh.G - 1) / (sh.NL * sh.G)) + 7) / 8 * 8; }
@@ -2648,6 +2757,41 @@ bool blk_supported(const PipeArgs &a)
     for (int k = 0; k < a.A.M; ++k) D.a[k] = a.A.a[k];
     if (!blk_uniform(D)) return false;      // (other alphabets keep the row-group kernels)
     return a.N + 64 < (1LL << 31) / 64;
+}
+
+// Two-phase calls (gpfq_dense_layer_prepare / _run): which row of kBlkInst the records of a prepared workspace were laid out for.  The two
+// calls take a snapshot of the options each; one that resolves the second call to another row -- another record format, another split --
+// would run a kernel on records it cannot read.  A small host-side table keyed by the workspace, the last kPreparedMax prepared ones:
+// the check costs the device nothing (a word in the workspace itself would have to be read by the kernel, in every instantiation's
+// prologue, or by the host, a synchronisation between the phases).  A workspace the table holds no note of is not checked (gpfq.h).
+constexpr int kPreparedMax = 64;
+struct PreparedRow { const void *ws; int row; };
+static std::mutex &prepared_mu() { static std::mutex m; return m; }
+static PreparedRow *prepared_rows() { static PreparedRow r[kPreparedMax] = {}; return r; }
+void blk_note_prepared(const PipeArgs &a)
+{
+    BlkShape sh;
+    const BlkInst *inst = blk_instance(a, &sh);
+    if (!inst) return;
+    std::lock_guard<std::mutex> g(prepared_mu());
+    PreparedRow *r = prepared_rows();
+    static int next = 0;
+    int at = -1;
+    for (int i = 0; i < kPreparedMax; ++i) if (r[i].ws == a.workspace) at = i;
+    if (at < 0) { at = next; next = (next + 1) % kPreparedMax; }
+    r[at] = {a.workspace, (int)(inst - kBlkInst)};
+}
+// false: the workspace was prepared for another row than this call resolves to (*prepared, *now: the two rows)
+bool blk_prepared_matches(const PipeArgs &a, int *prepared, int *now)
+{
+    BlkShape sh;
+    const BlkInst *inst = blk_instance(a, &sh);
+    if (!inst) return true;
+    std::lock_guard<std::mutex> g(prepared_mu());
+    const PreparedRow *r = prepared_rows();
+    for (int i = 0; i < kPreparedMax; ++i)
+        if (r[i].ws == a.workspace && a.workspace) { *prepared = r[i].row; *now = (int)(inst - kBlkInst); return *prepared == *now; }
+    return true;                                                  // (not in the table: prepared long ago -- the caller's word for it, as before)
 }
 
 constexpr size_t kAlphaBlock = 1024;        // the call's DevAlphabet, in front of the records (a host alphabet is stored there; a device alphabet is the caller's block)
@@ -2821,10 +2965,11 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
     char *const wbase = static_cast<char *>(a.workspace) + kAlphaBlock;
     const int sym_shape = blk_sym_a(a) != 0.f ? 1 : 0;
     const int sym_prep = a.phase == 0 ? sym_shape : 0;            // (two-phase calls: the scaling follows in phase 2)
+    // the records' format is the ROW's (blk_rec_map): the eight-group rows take wavefront-major tiles in the shape's record area
+    const BlkRecMap RM = blk_rec_map(nblk, sh.mp, sh.B, inst->G, inst->CLM != 0);
     if (a.phase == 2 && sym_shape) {
-        const int mps = sh.mp;
         hipLaunchKernelGGL(gpfq_blk_scale_kernel, dim3((unsigned)nrec, (unsigned)(sh.NS ? sh.NS : 1)), dim3(256), 0, stream, wbase,
-                           (int64_t)blk_rec_bytes(mps, sh.B, sh.G, sh.NS != 0), blk_hdr_bytes(sh.B, sh.NS != 0), mps, sh.NS ? (int64_t)blk_recs_bytes(nblk, sh) : (int64_t)0, alpha);
+                           RM, sh.B, sh.NS ? (int64_t)blk_recs_bytes(nblk, sh) : (int64_t)0, alpha);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -2853,12 +2998,12 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
     } else if (sh.NS) {                                            // cluster form: NS slices, one record stream each
         hipLaunchKernelGGL((gpfq_blk_prep_kernel<4, true, true>), dim3((unsigned)nrec), dim3(256), 0, stream, a.X, a.Xq, a.ld, a.N, (int)a.m, sh.mp * sh.NS,
                            nrm32, wbase, wbase + blk_hdrs_off(nblk, sh), alpha, sym,
-                           sh.NS, (int64_t)blk_recs_bytes(nblk, sh));
+                           sh.NS, (int64_t)blk_recs_bytes(nblk, sh), RM);
     } else if (run_form) {
         // (walks of fewer than 2048 steps: runs of records would be fewer workgroups than the chip has compute units, each a chain of eight
         //  records -- a Dense(128 -> 10) layer's pre-pass 0.08 ms longer; those keep one record per workgroup)
         // runs of 4 .. 16 records per workgroup (gpfq_blk_prep_run_kernel); the one-record form keeps the rows it cannot read 16 bytes at a time.
-        // The kernel holds four workgroups per compute unit (116 registers): 1024 at a time.  A workgroup is a chain of 1 + run round trips to
+        // The kernel holds four workgroups per compute unit (124 registers, of the 128 that allows): 1024 at a time.  A workgroup is a chain of 1 + run round trips to
         // memory, so the run length is the one in 4 .. 16 under which the launch is the fewest rounds x (1 + run) -- the SHORTEST run that
         // still fits one round where there is one (4101 records of the headline layer: runs of five, 821 workgroups).
         int run = 8;
@@ -2873,10 +3018,10 @@ hipError_t launch_blk(const PipeArgs &a, hipStream_t stream)
         auto *prun = sh.B == 4 ? (r64 ? gpfq_blk_prep_run_kernel<4, true> : gpfq_blk_prep_run_kernel<4, false>)
                                : (sh.B == 2 ? (r64 ? gpfq_blk_prep_run_kernel<2, true> : gpfq_blk_prep_run_kernel<2, false>) : gpfq_blk_prep_run_kernel<1, false>);
         hipLaunchKernelGGL(prun, dim3((unsigned)((nrec + run - 1) / run)), dim3(256), 0, stream, a.X, a.Xq, a.ld, a.N, (int)a.m, sh.mp, nrec, run,
-                           nrm32, wbase, wbase + blk_recs_bytes(nblk, sh), alpha, sym, zero16);
+                           nrm32, wbase, wbase + blk_recs_bytes(nblk, sh), alpha, sym, zero16, RM);
     } else {
         hipLaunchKernelGGL(prep, dim3((unsigned)nrec), dim3(256), 0, stream, a.X, a.Xq, a.ld, a.N, (int)a.m, sh.mp,
-                           nrm32, wbase, wbase + blk_recs_bytes(nblk, sh), alpha, sym, 1, (int64_t)0);
+                           nrm32, wbase, wbase + blk_recs_bytes(nblk, sh), alpha, sym, 1, (int64_t)0, RM);
     }
     e = hipGetLastError();
     if (e != hipSuccess || !do_run) return e;

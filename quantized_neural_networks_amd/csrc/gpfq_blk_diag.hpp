@@ -10,6 +10,9 @@
 //   -DGPFQ_BLK_PRIO=n    the issue priorities of the sweep wavefronts in the eight-group shapes (kPrioShip in gpfq_blk.hip is the shipped
 //                        setting): bits 0-1 the classic form, bits 2-3 the cluster slices; of a form's two bits the low one raises the slot
 //                        top's level in front of the slot's barrier, the high one staggers the level drops by the wavefront's age (kPrioSched)
+//   -DGPFQ_BLK_OWN_ROWS=n  the record tiles of the eight-group shapes (kOwnRowsShip in gpfq_blk.hip is the shipped setting; the switch is read
+//                        there, host and device): bits 0-1 the classic form, bits 2-3 the cluster slices; of a form's two bits the low one
+//                        takes the wavefront-major tiles, the high one requests a slot's tile-sourced rows in front of its barrier
 // The marginal-cost experiments of rounds 4-5 (every matrix / vector / LDS / DMA instruction issued twice, the barrier removed, pair splits
 // from the environment, the flush forced to one side) were removed in round 6; their numbers are in profiles/r04 and profiles/r05, their
 // code in the history (commit 1050215 and before).

@@ -561,8 +561,16 @@ static int dense_layer_impl(int phase, const float *X, const float *Xq, int64_t 
     pa.phase = phase;
     pa.workspace = static_cast<char *>(workspace) + onchip_stats_bytes(N);
     pa.fallback_count = static_cast<unsigned long long *>(workspace);
+    if (phase == 2) {
+        // the records in the workspace are the ones gpfq_dense_layer_prepare laid out: for the row of the kernel's table that THIS call resolves to?
+        int prepared = -1, now = -1;
+        if (!gpfq::blk_prepared_matches(pa, &prepared, &now))
+            return fail(GPFQ_ERR_INVALID_ARG, "%s: the workspace was prepared for row %d of the block kernel's table, this call resolves to row %d "
+                                              "(the options changed between gpfq_dense_layer_prepare and gpfq_dense_layer_run); nothing was computed", what, prepared, now);
+    }
     e = gpfq::launch_blk(pa, s);
     if (e != hipSuccess) return hip_fail(e, what);
+    if (phase == 1) gpfq::blk_note_prepared(pa);
     return (o.sync_errors && phase != 1) ? gpfq_call_status(workspace, stream) : GPFQ_OK;
 }
 

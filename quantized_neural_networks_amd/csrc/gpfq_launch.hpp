@@ -91,6 +91,8 @@ struct PipeArgs {
 hipError_t launch_alphabet_device(const float *median32, double alphabet_scalar, const AlphabetArg &unit, void *dev_alphabet, hipStream_t stream);
 bool blk_supported(const PipeArgs &a);
 bool blk_keras_out_supported(const PipeArgs &a);   // PipeArgs::o_st != 1 is taken (the 16-neuron four-step shapes; elsewhere neuron-major + one assembly pass)
+void blk_note_prepared(const PipeArgs &a);                     // gpfq_dense_layer_prepare: the row of the kernel's table a.workspace's records are laid out for
+bool blk_prepared_matches(const PipeArgs &a, int *prepared, int *now);   // gpfq_dense_layer_run: false when this call resolves to another row
 bool blk_instance_query(const PipeArgs &a, int32_t out[8]);   // the instantiation launch_blk would run: {G, S, B, NSW, SYM, NL, CLM, KOUT-capable}; false: none (gpfq_blk_instance)
 size_t blk_workspace_bytes(int64_t N, int64_t m, int64_t C, const Options &opt);   // (C: the cluster form's exchange buffers are per 16 neurons)
 hipError_t launch_blk(const PipeArgs &a, hipStream_t stream);

@@ -60,8 +60,10 @@ struct Options {
 // Reads every option once from the process-wide store (gpfq_capi.hip; relaxed atomics: a gpfq_set_option on another thread shows up
 // as the old or the new value of each key).  Every exported function that sizes or dispatches anything takes ONE snapshot at its top
 // and hands it down, so the support check, the workspace size and the launch of a call agree whatever another thread sets meanwhile.
-// gpfq_dense_layer_prepare and gpfq_dense_layer_run remain two calls with two snapshots: the pair does not verify that both saw the
-// same shape (that would be a new error path); a caller that splits a layer this way keeps the options still between the two.
+// gpfq_dense_layer_prepare and gpfq_dense_layer_run remain two calls with two snapshots; a caller that splits a layer this way keeps
+// the options still between the two.  Since the block kernel has two record formats the pair is checked: the run compares the row of the
+// kernel's table it resolves to with the one the workspace was prepared for and fails with GPFQ_ERR_INVALID_ARG when they differ
+// (gpfq_blk.hip: blk_note_prepared / blk_prepared_matches).
 Options options_snapshot();
 
 }  // namespace gpfq

@@ -394,6 +394,78 @@ __device__ __forceinline__ void slot_top_sym2(nf4 (&w01)[2], nf4 (&w23)[2], nf4 
                    "v159", "v160", "v161", "v162", "v163", "v164", "v165", "v166", "v167");
 #undef GPFQ_TOP2_PAIR_STEP
 }
+// slot_top_sym2 in two halves, for tiles in which a wavefront streams its own rows (gpfq_blk.hip, blk_own_rows): eight of the twelve
+// requests read rows of the record tile that this wavefront's own LDS-DMA pieces brought, valid behind its own dma_wait() -- so they go out
+// in FRONT of the slot's barrier (slot_rows_early), while the LDS is quiet, and only the four (w, q) requests, which read what the decision
+// wavefront wrote, stay behind it (slot_top_sym2_late).
+// slot_rows_early: waits for this wavefront's LDS writes of the slot (what slot_barrier's own wait is for: the caller follows it with a
+// bare s_barrier), then requests, in the order of their use, pair-step 0's rows into v[144:151], pair-step 1's into v[152:159], the unit's
+// 32 bytes of the first float64 row into v[128:135], pair-step 2's rows into v[136:143].  SB: bytes from a step's rows to the next step's;
+// the Xq row sits QO bytes behind the X row.  NOTHING is waited for: the registers are named in the clobber list and are no operand, so
+// the compiler never sees a register with a request in flight -- it keeps nothing of its own in v[128:167] across this statement or the
+// next, and what it computes in between (the control word's round trip, the loop's scalar control; lds_read_now ends with lgkmcnt(0), so
+// the rows have landed before anything else can run) must not touch them.  That is a property of ONE compiler's register allocation, not of
+// the language: profiles/own_rows/sweep_role_listing.txt holds that stretch of the listing (barrier -> slot top, the six-pair and the
+// four-pair role) as the shipped build compiles it, and is to be taken again after any edit of the stretch or change of compiler -- no
+// register of v[128:159] may be written there.  The slow path does touch them; the caller requests the rows again behind it.
+template <int SB, int QO>
+__device__ __forceinline__ void slot_rows_early(lchar *px, lchar *pd)
+{
+    static_assert(2 * SB + QO + 16 <= 65536, "the rows of pair-steps 1 and 2 are reached through the 16-bit offset field");
+    asm volatile("s_waitcnt lgkmcnt(0)\n\t"
+                 "ds_read_b128 v[144:147], %[ax]\n\tds_read_b128 v[148:151], %[ax] offset:%[q0]\n\t"
+                 "ds_read_b128 v[152:155], %[ax] offset:%[r1]\n\tds_read_b128 v[156:159], %[ax] offset:%[q1]\n\t"
+                 "ds_read_b128 v[128:131], %[ad]\n\tds_read_b128 v[132:135], %[ad] offset:16\n\t"
+                 "ds_read_b128 v[136:139], %[ax] offset:%[r2]\n\tds_read_b128 v[140:143], %[ax] offset:%[q2]"
+                 :: [ax] "v"((unsigned)(uintptr_t)px), [ad] "v"((unsigned)(uintptr_t)pd),
+                    [q0] "i"(QO), [r1] "i"(SB), [q1] "i"(SB + QO), [r2] "i"(2 * SB), [q2] "i"(2 * SB + QO)
+                 : "memory", "v128", "v129", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", "v139", "v140", "v141", "v142", "v143",
+                   "v144", "v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152", "v153", "v154", "v155", "v156", "v157", "v158", "v159");
+}
+// slot_top_sym2_late: the four (w, q) requests and slot_top_sym2's arithmetic of pair-steps 0 and 1 on the rows slot_rows_early brought.
+// The LDS answers in order, so the eight early requests have landed or are ahead in the queue: pair-step 0 waits for neuron 0's (w, q)
+// alone (three of the four still out), then for neuron 1's; pair-step 1 finds everything it reads in registers.  The float64 row and pair-step
+// 2's rows are outputs in the registers they landed in: the compiler first sees them behind the region's lgkmcnt(0).
+__device__ __forceinline__ void slot_top_sym2_late(nf4 (&w01)[2], nf4 (&w23)[2], nf4 &x2, nf4 &q2, nd2 (&d)[2],
+                                                   double &u00, double &u01, double &u02, double &u03, double &u10, double &u11, double &u12, double &u13,
+                                                   lchar *pwq)
+{
+#define GPFQ_TOP2_PAIR_STEP(W0, W1, XA, XAL, XAH, XB, XBL, XBH, QA, QB)                                            \
+    "v_pk_fma_f32 v[160:161], " W0 ", " QA ", v[160:161] op_sel:[1,0,0]\n\t"                                       \
+    "v_pk_fma_f32 v[162:163], " W0 ", " QB ", v[162:163] op_sel:[1,0,0]\n\t"                                       \
+    "v_pk_fma_f32 " XA ", " W1 ", " QA ", " XA " op_sel:[1,0,0]\n\t"                                               \
+    "v_pk_fma_f32 " XB ", " W1 ", " QB ", " XB " op_sel:[1,0,0]\n\t"                                               \
+    "v_cvt_f64_f32 " QA ", v160\n\tv_cvt_f64_f32 v[160:161], v161\n\t"                                             \
+    "v_cvt_f64_f32 v[164:165], " XAL "\n\tv_cvt_f64_f32 " XA ", " XAH "\n\t"                                       \
+    "v_cvt_f64_f32 " QB ", v162\n\tv_cvt_f64_f32 v[162:163], v163\n\t"                                             \
+    "v_cvt_f64_f32 v[166:167], " XBL "\n\tv_cvt_f64_f32 " XB ", " XBH "\n\t"                                       \
+    "v_add_f64 %[u01], %[u01], v[160:161]\n\tv_add_f64 %[u10], %[u10], v[164:165]\n\t"                             \
+    "v_add_f64 %[u11], %[u11], " XA "\n\tv_add_f64 %[u02], %[u02], " QB "\n\t"                                     \
+    "v_add_f64 %[u03], %[u03], v[162:163]\n\tv_add_f64 %[u12], %[u12], v[166:167]\n\t"                             \
+    "v_add_f64 %[u00], %[u00], " QA "\n\tv_add_f64 %[u13], %[u13], " XB "\n\t"
+    asm volatile("ds_read_b128 v[26:29], %[aw]\n\tds_read_b128 v[22:25], %[aw] offset:32\n\t"
+                 "ds_read_b128 %[w2], %[aw] offset:16\n\tds_read_b128 %[w3], %[aw] offset:48\n\t"
+                 // pair-step 0: the rows are in (eight requests ahead of these four); neuron 0's (w, q) is the first of the four, neuron 1's the second
+                 "s_waitcnt lgkmcnt(3)\n\tv_pk_mul_f32 v[160:161], v[144:145], v[26:27] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[162:163], v[146:147], v[26:27] op_sel_hi:[1,0]\n\t"
+                 "s_waitcnt lgkmcnt(2)\n\tv_pk_mul_f32 v[144:145], v[144:145], v[22:23] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[146:147], v[146:147], v[22:23] op_sel_hi:[1,0]\n\t"
+                 GPFQ_TOP2_PAIR_STEP("v[26:27]", "v[22:23]", "v[144:145]", "v144", "v145", "v[146:147]", "v146", "v147", "v[148:149]", "v[150:151]")
+                 // pair-step 1: rows and (w, q) are all in
+                 "v_pk_mul_f32 v[160:161], v[152:153], v[28:29] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[162:163], v[154:155], v[28:29] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[152:153], v[152:153], v[24:25] op_sel_hi:[1,0]\n\t"
+                 "v_pk_mul_f32 v[154:155], v[154:155], v[24:25] op_sel_hi:[1,0]\n\t"
+                 GPFQ_TOP2_PAIR_STEP("v[28:29]", "v[24:25]", "v[152:153]", "v152", "v153", "v[154:155]", "v154", "v155", "v[156:157]", "v[158:159]")
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&{v[26:29]}"(w01[0]), "=&{v[22:25]}"(w01[1]), [w2] "=&v"(w23[0]), [w3] "=&v"(w23[1]),
+                   "=&{v[128:131]}"(d[0]), "=&{v[132:135]}"(d[1]), "=&{v[136:139]}"(x2), "=&{v[140:143]}"(q2),
+                   [u00] "+v"(u00), [u01] "+v"(u01), [u02] "+v"(u02), [u03] "+v"(u03), [u10] "+v"(u10), [u11] "+v"(u11), [u12] "+v"(u12), [u13] "+v"(u13)
+                 : [aw] "v"((unsigned)(uintptr_t)pwq)
+                 : "memory", "v144", "v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152", "v153", "v154", "v155", "v156", "v157", "v158",
+                   "v159", "v160", "v161", "v162", "v163", "v164", "v165", "v166", "v167");
+#undef GPFQ_TOP2_PAIR_STEP
+}
 __device__ __forceinline__ int lds_read_now(lchar *p)
 {
     int v;
