@@ -593,6 +593,45 @@ int gpfq_quantize_rows_i8_from_amax(const float *x, int64_t B, int64_t ldx, int6
                                     float *scales, void *stream);
 
 /*
+ * The DepthwiseConv2D forward pass on the same footing: the kernel [kh][kw][Cin][mult] held as the packed rows
+ * of its matrix view [kh*kw][Cin*mult] (what deploy.export_packed writes): output channel j = c * mult + d has a row of kh*kw codes,
+ * pitch = gpfq_packed_row_bytes(kh*kw, bits).  Exact int32 sums on the packed int8 dot product; no matrix instruction.  Opt-in; bit
+ * for bit:
+ *
+ * gpfq_packed_depthwise_conv2d_forward_i8:
+ *   xq, ldq, scales: exactly those of gpfq_packed_conv2d_forward_i8 -- int8 NHWC images [H][W][Cin] at xq + i * ldq and one scale per
+ *   image, from gpfq_quantize_rows_i8, _split or _from_amax.  Geometry: TensorFlow's, by the same formulas (gpfq_patch_out_dim, floor
+ *   before and the rest after under SAME); a tap outside the image contributes 0.
+ *   With t = ky * kw + kx, the code of weight t of channel j, k = code - zero_code and w[t][j] = 2 k - (M - 1) for 0 <= k < M, else 0:
+ *   acc[i][oh][ow][j] = sum over t of xq[i][oh * sh + ky * rh - pad_top][ow * sw + kx * rw - pad_left][j / mult] * w[t][j], in int32;
+ *   p                 = ((double)acc * (double)scales[i]) * (radii[j] / (double)(M - 1)): two float64 products in that order;
+ *   v                 = (float)p + bias[j], a float32 add; (float)p without a bias;
+ *   y[i][oh][ow][j]   = (relu && v < 0) ? +0.0f : v: a NaN stays a NaN and -0.0f stays -0.0f.
+ *   radii [device] f64 [Cin*mult]; bias [device] f32 [Cin*mult] or NULL; y [device] f32 [n][OH][OW][Cin*mult], contiguous.
+ *   amax_bits may be NULL: no atomics then, and nothing else changes.  Otherwise [device] u32 [n], cleared asynchronously on `stream`,
+ *   and on completion amax_bits[i] = max over the stored y of image i of (bits(y) & 0x7fffffff), as gpfq_packed_conv2d_forward_i8_fused
+ *   leaves it -- taken inside a wavefront, then across the wavefronts of a workgroup in LDS: a workgroup issues at most ONE agent-scope
+ *   unsigned-max atomic without a return value per image its positions touch, and none where its maximum is 0.  amax_bits must not
+ *   overlap y or any input.
+ * So an image that is not finite gives an image of NaN and leaves every other image alone; output image i depends on input image i
+ * and scales[i] alone, not on n; and every call gives the same bits in y and amax_bits.  Whether mult == 1 and Cin is a multiple of
+ * 4 (and y 16-byte aligned) decides how the kernel gathers and stores (dwords and 16-byte stores, or byte by byte), never what it
+ * computes.
+ * The checks, status codes and early returns are gpfq_packed_conv2d_forward_i8_fused's with F = Cin * mult and the row length kh*kw
+ * (n = 0, an empty output: GPFQ_OK without a launch, amax_bits still cleared when n is positive; relu other than 0 or 1:
+ * GPFQ_ERR_INVALID_ARG), and: mult < 1 is GPFQ_ERR_INVALID_ARG; kh*kw > GPFQ_PACKED_DW_MAX_TAPS and Cin * mult at or beyond 2^31
+ * are GPFQ_ERR_UNSUPPORTED.
+ * At most two operations on `stream`: the clear (when amax_bits is given) and one launch.  No workgroup waits for another; no
+ * workspace, no scratch, no host synchronisation; the call can be captured into a graph.
+ */
+#define GPFQ_PACKED_DW_MAX_TAPS 64      /* = GPFQ_REFINE_PAIRS_MAX_K, the bound the pair refinement sets for these layers */
+int gpfq_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                            int64_t H, int64_t W, int64_t Cin, int64_t mult, int kh, int kw, int sh, int sw, int rh,
+                                            int rw, int same_padding, const uint8_t *packed, int bits, int zero_code,
+                                            const double *radii, int M, const float *bias, float *y, int relu, uint32_t *amax_bits,
+                                            void *stream);
+
+/*
  * Search over the alphabet scalar (a sequence as alphabet_scalar).  K candidate scalars s_0 .. s_{K-1}
  * (1 <= K <= GPFQ_SEARCH_MAX_CANDIDATES, each a finite positive number) are K * C independent columns of one walk with the unit
  * alphabet: candidate k of output channel j is column k * C + j (k-major: candidate k is a contiguous block of C columns).

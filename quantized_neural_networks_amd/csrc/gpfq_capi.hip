@@ -990,6 +990,26 @@ int gpfq_packed_dense_forward_i8_fused(const int8_t *xq, int64_t B, int64_t ldq,
                                  C, y, ldy, relu, amax_bits, stream);
 }
 
+// the geometry of the int8 image entries as their kernels take it (every field checked by the caller to fit an int): the output size
+// and TensorFlow's pads before
+static gpfq::ConvI8Shape conv_i8_shape(int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
+                                       int64_t oh, int64_t ow)
+{
+    gpfq::ConvI8Shape S;
+    S.H = (int)H; S.W = (int)W; S.Cin = (int)Cin; S.kh = kh; S.kw = kw; S.sh = sh; S.sw = sw; S.rh = rh; S.rw = rw;
+    S.OH = (int)oh; S.OW = (int)ow;
+    S.pad_top = S.pad_left = 0;
+    if (same_padding) {
+        // TF SAME: total = max((out-1)*stride + k_eff - in, 0), before = total / 2 (floor)
+        const int64_t keh = kh + (int64_t)(kh - 1) * (rh - 1), kew = kw + (int64_t)(kw - 1) * (rw - 1);
+        int64_t th = (oh - 1) * sh + keh - H; if (th < 0) th = 0;
+        int64_t tw = (ow - 1) * sw + kew - W; if (tw < 0) tw = 0;
+        S.pad_top = (int)(th / 2);
+        S.pad_left = (int)(tw / 2);
+    }
+    return S;
+}
+
 // both int8 Conv2D entries, as packed_dense_i8_entry
 static int packed_conv_i8_entry(const char *name, bool fused, const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
                                 int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
@@ -1032,17 +1052,7 @@ static int packed_conv_i8_entry(const char *name, bool fused, const int8_t *xq, 
     if (!xq || !scales || !packed || !radii || !y) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "packed must be 16-byte aligned");
-    gpfq::ConvI8Shape S;
-    S.H = (int)H; S.W = (int)W; S.Cin = (int)Cin; S.kh = kh; S.kw = kw; S.sh = sh; S.sw = sw; S.rh = rh; S.rw = rw;
-    S.OH = (int)oh; S.OW = (int)ow;
-    S.pad_top = S.pad_left = 0;
-    if (same_padding) {
-        // TF SAME: total = max((out-1)*stride + k_eff - in, 0), before = total / 2 (floor)
-        int64_t th = (oh - 1) * sh + keh - H; if (th < 0) th = 0;
-        int64_t tw = (ow - 1) * sw + kew - W; if (tw < 0) tw = 0;
-        S.pad_top = (int)(th / 2);
-        S.pad_left = (int)(tw / 2);
-    }
+    const gpfq::ConvI8Shape S = conv_i8_shape(H, W, Cin, kh, kw, sh, sw, rh, rw, same_padding, oh, ow);
     hipError_t e = fused ? gpfq::launch_packed_conv2d_forward_i8_fused(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y,
                                                                        relu, amax_bits, static_cast<hipStream_t>(stream))
                          : gpfq::launch_packed_conv2d_forward_i8(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y,
@@ -1066,6 +1076,54 @@ int gpfq_packed_conv2d_forward_i8_fused(const int8_t *xq, int64_t n, int64_t ldq
 {
     return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_fused", true, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw, rh, rw,
                                 same_padding, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
+}
+
+// the int8 DepthwiseConv2D entry: packed_conv_i8_entry's checks in its order, with F = Cin * mult and the row length kh * kw
+int gpfq_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                            int64_t H, int64_t W, int64_t Cin, int64_t mult, int kh, int kw, int sh, int sw, int rh,
+                                            int rw, int same_padding, const uint8_t *packed, int bits, int zero_code,
+                                            const double *radii, int M, const float *bias, float *y, int relu, uint32_t *amax_bits,
+                                            void *stream)
+{
+    const char *name = "gpfq_packed_depthwise_conv2d_forward_i8";
+    if (relu != 0 && relu != 1) return fail(GPFQ_ERR_INVALID_ARG, "relu=%d: must be 0 or 1", relu);
+    if (n < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size n=%lld", (long long)n);
+    if (H <= 0 || W <= 0 || Cin <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad image shape H=%lld W=%lld Cin=%lld", (long long)H, (long long)W, (long long)Cin);
+    if (mult < 1) return fail(GPFQ_ERR_INVALID_ARG, "depth multiplier mult=%lld: must be positive", (long long)mult);
+    if (kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || rh <= 0 || rw <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad kernel/stride/rate");
+    if (M < 2 || M > 64) return fail(GPFQ_ERR_INVALID_ARG, "the int8 forward pass takes linspace(-1, 1, M) of 2..64 members, got M=%d", M);
+    if ((int64_t)kh * kw > GPFQ_PACKED_DW_MAX_TAPS)
+        return fail(GPFQ_ERR_UNSUPPORTED, "kh*kw=%d*%d > GPFQ_PACKED_DW_MAX_TAPS=%d", kh, kw, GPFQ_PACKED_DW_MAX_TAPS);
+    int rc = packed_width_ok(bits, zero_code, M);
+    if (rc != GPFQ_OK) return rc;
+    if (bits != gpfq::packed_bits(M, zero_code))
+        return fail(GPFQ_ERR_INVALID_ARG, "bits=%d, but %d members%s pack to %d bits (gpfq_packed_bits)", bits, M,
+                    zero_code ? " and the literal zero" : "", gpfq::packed_bits(M, zero_code));
+    if (ldq % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld must be a multiple of 16", (long long)ldq);
+    const int64_t oh = gpfq_patch_out_dim(H, kh, sh, rh, same_padding), ow = gpfq_patch_out_dim(W, kw, sw, rw, same_padding);
+    if (n > 2147483647LL && amax_bits) return fail(GPFQ_ERR_UNSUPPORTED, "too many images for one clear of amax_bits");
+    if (n == 0 || oh == 0 || ow == 0) {             // an empty layer still leaves its images' cells cleared
+        if (amax_bits && n > 0) {
+            hipError_t e = gpfq::launch_amax_clear(amax_bits, n, static_cast<hipStream_t>(stream));
+            if (e != hipSuccess) return hip_fail(e, name);
+        }
+        return GPFQ_OK;
+    }
+    // what the kernel indexes with 32 bits: a place inside an image, a position, a tap's row and column, a channel
+    const int64_t limit = 1LL << 24, keh = kh + (int64_t)(kh - 1) * (rh - 1), kew = kw + (int64_t)(kw - 1) * (rw - 1);
+    if (H > limit || W > limit || sh > limit || sw > limit || keh > limit || kew > limit || H * W > 2147483647LL / Cin)
+        return fail(GPFQ_ERR_UNSUPPORTED, "image, stride or dilated kernel too large for one launch");
+    if (mult > 2147483647LL / Cin) return fail(GPFQ_ERR_UNSUPPORTED, "Cin*mult output channels: too many for one launch");
+    if (oh * ow > 0x7fff0000LL / n) return fail(GPFQ_ERR_UNSUPPORTED, "n*OH*OW output positions: too many for one launch");
+    if (gpfq::packed_dw_i8_blocks(n, oh, ow, Cin * mult) > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "layer too wide for one launch");
+    if (ldq < H * W * Cin) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld < H*W*Cin=%lld", (long long)ldq, (long long)(H * W * Cin));
+    if (!xq || !scales || !packed || !radii || !y) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "packed must be 16-byte aligned");
+    const gpfq::ConvI8Shape S = conv_i8_shape(H, W, Cin, kh, kw, sh, sw, rh, rw, same_padding, oh, ow);
+    hipError_t e = gpfq::launch_packed_depthwise_conv2d_forward_i8(xq, n, ldq, scales, S, (int)mult, packed, bits, zero_code, radii, M, bias, y,
+                                                                   relu, amax_bits, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
 }
 
 int gpfq_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii, const float *layer_median,

@@ -377,6 +377,14 @@ hipError_t launch_packed_conv2d_forward_i8_fused(const int8_t *xq, int64_t n, in
                                                  const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                                  const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits,
                                                  hipStream_t stream);
+// gpfq_packed_dw_i8.hip: the DepthwiseConv2D forward pass of the same images with the kernel
+// [kh*kw][Cin*mult] held as packed rows, on the packed int8 dot product.  S as above (S.Cin: the input channels); relu / amax_bits as
+// the fused launchers take them, with relu = 0 and amax_bits = NULL giving the kernel without the fused epilogue.
+// packed_dw_i8_blocks: the workgroups of that launch, for the entry's check.
+int64_t packed_dw_i8_blocks(int64_t n, int64_t OH, int64_t OW, int64_t C);
+hipError_t launch_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
+                                                     int mult, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                                     const float *bias, float *y, int relu, uint32_t *amax_bits, hipStream_t stream);
 // gpfq_search.hip (a sequence as alphabet_scalar): the K candidate scalars travel by value
 constexpr int kSearchMaxK = 16;
 struct SearchScalars {

@@ -5,7 +5,8 @@ bits per weight plus one radius per output channel, writes a whole network that 
 (``load_packed``): Conv2D / DepthwiseConv2D kernels are decoded on the device at load, Dense layers stay packed
 (``keras_shim.PackedDense``) and run from the codes (``gpfq_packed_dense_forward``).  With ``load_packed(..., packed_conv=True)``
 Conv2D layers stay packed as well (``keras_shim.PackedConv2D``; on int8 activations they run from the codes through
-``gpfq_packed_conv2d_forward_i8``).
+``gpfq_packed_conv2d_forward_i8``), and with ``packed_depthwise=True`` DepthwiseConv2D layers do (``keras_shim.PackedDepthwiseConv2D``,
+``gpfq_packed_depthwise_conv2d_forward_i8``).
 
     pack_kernel(Q, radii, unit_alphabet)   any on-alphabet kernel -> dict(codes, radii, alphabet, bits, zero_code, shape, depthwise)
     unpack_kernel(packed)                  the inverse: the kernel as float32, bit for bit (-0.0 reads back as 0.0)
@@ -138,6 +139,9 @@ def _check_int8_layer(layer, packed):
     if layer.fan_in > hip.GPFQ_PACKED_I8_MAX_N:
         raise ValueError(f"layer {layer.name}: activations=\"int8\" takes at most {hip.GPFQ_PACKED_I8_MAX_N} input features "
                          f"(GPFQ_PACKED_I8_MAX_N), the layer has {layer.fan_in}")
+    if isinstance(layer, keras_shim.PackedDepthwiseConv2D) and layer.fan_in > hip.GPFQ_PACKED_DW_MAX_TAPS:
+        raise ValueError(f"layer {layer.name}: activations=\"int8\" takes depthwise kernels of at most {hip.GPFQ_PACKED_DW_MAX_TAPS} taps "
+                         f"(GPFQ_PACKED_DW_MAX_TAPS), the layer has kh * kw = {layer.fan_in}")
 
 
 def fold_batchnorm(radii, bias, gamma, beta, mean, var, epsilon):
@@ -168,9 +172,9 @@ def _kind(layer):
 
 def _rows_of(shape, kind):
     """(rows per sample, floats per row) of a tensor of this static shape as the int8 quantizer of a `kind` layer cuts it: an image
-    is one row of a Conv2D layer, the last axis one row of a Dense layer."""
+    is one row of a Conv2D or DepthwiseConv2D layer, the last axis one row of a Dense layer."""
     dims = [int(v) for v in shape[1:]]
-    if kind == "Conv2D":
+    if kind in ("Conv2D", "DepthwiseConv2D"):
         return 1, int(np.prod(dims))
     return int(np.prod(dims[:-1])), dims[-1]
 
@@ -244,7 +248,8 @@ def plan_fusion(net, packed_at=None):
                    or None
         hands_to   the packed layer whose quantizer takes this layer's maxima, or None
 
-    packed_at: the positions in net.layers to plan for (default: the PackedDense / PackedConv2D layers whose activations are "int8").
+    packed_at: the positions in net.layers to plan for (default: the PackedDense / PackedConv2D / PackedDepthwiseConv2D layers
+    whose activations are "int8").
     A function of the layer classes, activations, static shapes and the graph alone: nothing runs on a device.  The rules, in order,
     per packed layer P: FOLD where P's activation is None / "linear" and its output has exactly one consumer,
     a BatchNormalization, and is not a network output; RELU where P's own activation is "relu" (nothing is folded then), or where the
@@ -254,11 +259,12 @@ def plan_fusion(net, packed_at=None):
     net = _shim_network(net)
     if packed_at is None:
         packed_at = [k for k, l in enumerate(net.layers)
-                     if isinstance(l, (keras_shim.PackedDense, keras_shim.PackedConv2D)) and l.activations == "int8"]
+                     if isinstance(l, (keras_shim.PackedDense, keras_shim.PackedConv2D, keras_shim.PackedDepthwiseConv2D))
+                     and l.activations == "int8"]
     nodes, outputs = _net_tables(net)
-    bad = [k for k in packed_at if nodes[k]["kind"] not in ("Dense", "Conv2D")]
+    bad = [k for k in packed_at if nodes[k]["kind"] not in ("Dense", "Conv2D", "DepthwiseConv2D")]
     if bad:
-        raise ValueError(f"plan_fusion: positions {bad} are not Dense or Conv2D layers")
+        raise ValueError(f"plan_fusion: positions {bad} are not Dense or Conv2D / DepthwiseConv2D layers")
     shapes = [(l.input_shape, l.output_shape) for l in net.layers]
     plan = _plan(nodes, outputs, packed_at, shapes)
     name = lambda k: None if k is None else net.layers[k].name
@@ -303,11 +309,11 @@ def _apply_fusion(net, packed_at):
     return net
 
 
-def load_packed(path, device=None, activations="float32", packed_conv=False, fuse=False):
+def load_packed(path, device=None, activations="float32", packed_conv=False, fuse=False, packed_depthwise=False):
     """Inverse of export_packed: a keras_shim network on ``device`` (default: the current GPU).  Dense layers that were exported
     packed come back as keras_shim.PackedDense (codes, radii and bias in device memory; the float kernel is never formed unless
     get_weights() or a batch beyond keras_shim.PACKED_TILED_MAX_BATCH asks for it); packed Conv2D / DepthwiseConv2D kernels are
-    decoded on the device.
+    decoded on the device unless the two switches below keep them.
 
     activations="int8": every PackedDense layer rounds its input to int8 per batch row and runs the exact-int32 forward pass at every
     batch size (keras_shim.PackedDense.activations; the float kernel is then formed by get_weights() alone).  Raises ValueError naming
@@ -315,8 +321,13 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
 
     packed_conv=True: every Conv2D layer that was exported packed stays packed too (keras_shim.PackedConv2D),
     with ``activations`` set on it: "int8" rounds every image to int8 with its own scale and runs gpfq_packed_conv2d_forward_i8, and
-    the same two checks apply with kh * kw * Cin as the row length; "float32" decodes at every call.  DepthwiseConv2D kernels are
-    decoded at load either way: their rows are kh * kw long, too short for the matrix instruction to matter.
+    the same two checks apply with kh * kw * Cin as the row length; "float32" decodes at every call.
+
+    packed_depthwise=True (independent of packed_conv): every DepthwiseConv2D layer that was exported packed stays packed
+    (keras_shim.PackedDepthwiseConv2D), with ``activations`` set on it: "int8" runs
+    gpfq_packed_depthwise_conv2d_forward_i8 -- no matrix instruction, the rows are kh * kw long -- under the same alphabet check, and a
+    ValueError names a layer of more than GPFQ_PACKED_DW_MAX_TAPS taps; "float32" decodes at every call.  Without it these kernels
+    are decoded at load.
 
     fuse=True (needs activations="int8"): what stands around the packed layers moves into them, by the plan
     of plan_fusion, recorded as ``net.fusion_plan``.  A BatchNormalization behind a linear packed layer is folded into the layer's
@@ -341,6 +352,8 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
         classes = {k: keras_shim.PackedDense for k in packed_at if arch["layers"][k]["cls"] == "Dense"}
         if packed_conv:
             classes.update({k: keras_shim.PackedConv2D for k in packed_at if arch["layers"][k]["cls"] == "Conv2D"})
+        if packed_depthwise:
+            classes.update({k: keras_shim.PackedDepthwiseConv2D for k in packed_at if arch["layers"][k]["cls"] == "DepthwiseConv2D"})
         if fuse:
             # the positions fused away, from the record alone (the fold and the ReLU need no shapes); the full plan follows the network
             nodes, outputs = _arch_tables(arch)

@@ -28,6 +28,7 @@ GPFQ_REFINE_GRAM_MAX_N = 25600     # longest walk the refinement sweeps on the G
 GPFQ_REFINE_PAIRS_MAX_K = 64       # longest walk of an (input channel, filter) pair refine_conv_pairs takes (include/gpfq.h)
 GPFQ_ERR_INVALID_ARG, GPFQ_ERR_UNSUPPORTED, GPFQ_ERR_WORKSPACE = -1, -2, -3
 GPFQ_PACKED_I8_MAX_N = 262144      # longest row of the int8 packed forward pass: its int32 sums cannot overflow (include/gpfq.h)
+GPFQ_PACKED_DW_MAX_TAPS = 64       # most taps kh * kw of the int8 packed DepthwiseConv2D forward pass (include/gpfq.h)
 
 # every symbol include/gpfq.h declares: (restype, argtypes)
 _i64, _int, _vp, _sz = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
@@ -79,6 +80,8 @@ SYMBOLS = {
     "gpfq_packed_conv2d_forward_i8_fused": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
                                                    _vp, _int, _int, _vp, _int, _vp, _i64, _vp, _int, _vp, _vp]),
     "gpfq_quantize_rows_i8_from_amax": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "gpfq_packed_depthwise_conv2d_forward_i8": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int,
+                                                       _int, _vp, _int, _int, _vp, _int, _vp, _vp, _int, _vp, _vp]),
     "gpfq_candidate_kernels": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dp, _int, _vp, _vp, _i64, _i64, _i64, _vp]),
     "gpfq_select_candidates_workspace_bytes": (_sz, [_int, _i64]),
     "gpfq_select_candidates": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _dp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
@@ -1556,21 +1559,14 @@ def packed_dense_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, N, bias=
     return out
 
 
-def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias=None, scales=None,
-                             out=None, relu=False, amax_out=None, amax=None):
-    """y f32 [n][OH][OW][F] of a Conv2D layer whose kernel [kh][kw][Cin][F] = kernel_shape is held as the packed rows of its matrix
-    view [kh*kw*Cin][F], on int8 images and exact int32 sums (gpfq_packed_conv2d_forward_i8; the contract is include/gpfq.h's, bit for
-    bit; TensorFlow's geometry).  x_or_xq: float32 NHWC x [n][H][W][Cin], each image quantized here with its own scale
-    (quantize_rows_i8 on the flattened images), or -- with `scales` f32 [n] -- ready int8 images [n][H][W][Cin], each contiguous, an
-    image pitch (stride(0)) that is a multiple of 16.  M: the size of the layer's unit alphabet, which must be linspace(-1, 1, M).
-    out: an optional contiguous [n][OH][OW][F] tensor.  relu / amax_out (a uint32 or int32 [n] tensor, one cell per image) / amax
-    (the maxima of a float x's images): as for packed_dense_forward_i8, through gpfq_packed_conv2d_forward_i8_fused.  No sync."""
-    kh, kw, Cin, F = (int(v) for v in kernel_shape)
-    kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
+def _i8_images(x_or_xq, kernel_shape, steps, scales, amax):
+    """The images of the two int8 image forward passes -> (xq, scales, n, H, W, image pitch): float32 NHWC images quantized here, each
+    with its own scale (quantize_rows_i8 on the flattened images, `amax` passed on), or -- with `scales` -- ready int8 images."""
+    kh, kw, Cin = kernel_shape[:3]
     if not isinstance(x_or_xq, torch.Tensor) or x_or_xq.dim() != 4 or x_or_xq.shape[3] != Cin:
-        raise GpfqError(f"x must be an NHWC tensor [n][H][W][{Cin}] for a kernel of shape {(kh, kw, Cin, F)}")
+        raise GpfqError(f"x must be an NHWC tensor [n][H][W][{Cin}] for a kernel of shape {tuple(kernel_shape)}")
     n, H, W = (int(v) for v in x_or_xq.shape[:3])
-    if min(H, W, Cin, kh, kw, sh, sw, rh, rw) <= 0:
+    if min(H, W, Cin, kh, kw, *steps) <= 0:
         raise GpfqError("image sides, kernel sides, strides and dilation must be positive")
     hwc = H * W * Cin
     if scales is None:
@@ -1587,21 +1583,42 @@ def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_
     _dev(scales, torch.float32, "scales")
     if scales.numel() != n or not scales.is_contiguous():
         raise GpfqError(f"scales must be a contiguous [{n}] tensor")
-    C = _packed_args(packed, bits, zero_code, radii, kh * kw * Cin)
-    if C != F:
-        raise GpfqError(f"radii has {C} entries, the kernel {F} filters")
+    return xq, scales, n, H, W, ldq
+
+
+def _i8_image_out(bias, out, shape, device):
+    """bias f32 [F] or None and out (or None: allocated) of the same two passes -> (bias pointer or None, out)."""
+    F = shape[3]
     if bias is not None:
         _dev(bias, torch.float32, "bias")
         if bias.numel() != F or not bias.is_contiguous():
             raise GpfqError(f"bias must be a contiguous [{F}] tensor")
-    OH, OW = patch_out_dim(H, kh, sh, rh, same), patch_out_dim(W, kw, sw, rw, same)
     if out is None:
-        out = torch.empty((n, OH, OW, F), dtype=torch.float32, device=xq.device)
+        out = torch.empty(shape, dtype=torch.float32, device=device)
     _dev(out, torch.float32, "out")
-    if tuple(out.shape) != (n, OH, OW, F) or not out.is_contiguous():
-        raise GpfqError(f"out {tuple(out.shape)} must be a contiguous [{n}][{OH}][{OW}][{F}] tensor")
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise GpfqError(f"out {tuple(out.shape)} must be a contiguous [{shape[0]}][{shape[1]}][{shape[2]}][{F}] tensor")
+    return (bias.data_ptr() if bias is not None else None), out
+
+
+def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias=None, scales=None,
+                             out=None, relu=False, amax_out=None, amax=None):
+    """y f32 [n][OH][OW][F] of a Conv2D layer whose kernel [kh][kw][Cin][F] = kernel_shape is held as the packed rows of its matrix
+    view [kh*kw*Cin][F], on int8 images and exact int32 sums (gpfq_packed_conv2d_forward_i8; the contract is include/gpfq.h's, bit for
+    bit; TensorFlow's geometry).  x_or_xq: float32 NHWC x [n][H][W][Cin], each image quantized here with its own scale
+    (quantize_rows_i8 on the flattened images), or -- with `scales` f32 [n] -- ready int8 images [n][H][W][Cin], each contiguous, an
+    image pitch (stride(0)) that is a multiple of 16.  M: the size of the layer's unit alphabet, which must be linspace(-1, 1, M).
+    out: an optional contiguous [n][OH][OW][F] tensor.  relu / amax_out (a uint32 or int32 [n] tensor, one cell per image) / amax
+    (the maxima of a float x's images): as for packed_dense_forward_i8, through gpfq_packed_conv2d_forward_i8_fused.  No sync."""
+    kh, kw, Cin, F = (int(v) for v in kernel_shape)
+    kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
+    xq, scales, n, H, W, ldq = _i8_images(x_or_xq, (kh, kw, Cin, F), (sh, sw, rh, rw), scales, amax)
+    C = _packed_args(packed, bits, zero_code, radii, kh * kw * Cin)
+    if C != F:
+        raise GpfqError(f"radii has {C} entries, the kernel {F} filters")
+    OH, OW = patch_out_dim(H, kh, sh, rh, same), patch_out_dim(W, kw, sw, rw, same)
+    bp, out = _i8_image_out(bias, out, (n, OH, OW, F), xq.device)
     fused, relu, ap = _fused_args(relu, amax_out, n)
-    bp = bias.data_ptr() if bias is not None else None
     with torch.cuda.device(xq.device):
         if fused:
             _check(load().gpfq_packed_conv2d_forward_i8_fused(xq.data_ptr(), n, ldq, scales.data_ptr(), H, W, Cin, kh, kw, sh, sw, rh, rw,
@@ -1613,4 +1630,28 @@ def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_
                                                         1 if same else 0, packed.data_ptr(), int(bits), int(zero_code), radii.data_ptr(),
                                                         int(M), bp, F, out.data_ptr(), _stream()),
                    "gpfq_packed_conv2d_forward_i8")
+    return out
+
+
+def packed_depthwise_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias=None,
+                                       scales=None, out=None, relu=False, amax_out=None, amax=None):
+    """y f32 [n][OH][OW][Cin*mult] of a DepthwiseConv2D layer whose kernel [kh][kw][Cin][mult] = kernel_shape is held as the packed rows
+    of its matrix view [kh*kw][Cin*mult], on int8 images and exact int32 sums (gpfq_packed_depthwise_conv2d_forward_i8; the contract
+    is include/gpfq.h's, bit for bit; TensorFlow's geometry; kh * kw <= GPFQ_PACKED_DW_MAX_TAPS).  Every other argument as for
+    packed_conv2d_forward_i8: float32 NHWC images are quantized here, each with its own scale (`amax`: their maxima), or ready int8
+    images come with `scales`; relu / amax_out (a uint32 or int32 [n] tensor) are the fused epilogue.  No sync."""
+    kh, kw, Cin, mult = (int(v) for v in kernel_shape)
+    kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
+    xq, scales, n, H, W, ldq = _i8_images(x_or_xq, (kh, kw, Cin, mult), (sh, sw, rh, rw), scales, amax)
+    C = _packed_args(packed, bits, zero_code, radii, kh * kw)
+    if C != Cin * mult:
+        raise GpfqError(f"radii has {C} entries, the kernel {Cin} x {mult} output channels")
+    OH, OW = patch_out_dim(H, kh, sh, rh, same), patch_out_dim(W, kw, sw, rw, same)
+    bp, out = _i8_image_out(bias, out, (n, OH, OW, C), xq.device)
+    _, relu, ap = _fused_args(relu, amax_out, n)
+    with torch.cuda.device(xq.device):
+        _check(load().gpfq_packed_depthwise_conv2d_forward_i8(xq.data_ptr(), n, ldq, scales.data_ptr(), H, W, Cin, mult, kh, kw, sh, sw, rh,
+                                                              rw, 1 if same else 0, packed.data_ptr(), int(bits), int(zero_code),
+                                                              radii.data_ptr(), int(M), bp, out.data_ptr(), relu, ap, _stream()),
+               "gpfq_packed_depthwise_conv2d_forward_i8")
     return out

@@ -545,6 +545,94 @@ class DepthwiseConv2D(Conv2D):
         return w, cin
 
 
+class PackedDepthwiseConv2D(DepthwiseConv2D, _FusedI8):
+    """A DepthwiseConv2D layer that holds its quantized kernel as packed low-bit codes (deploy.load_packed(...,
+    packed_depthwise=True)): only the codes, the radii and the bias live in device memory.  ``get_weights()``
+    decodes on demand; the weights cannot be set.
+
+    ``activations``: "float32" (the default) decodes the kernel at every call and runs the float32 grouped convolution exactly as
+    DepthwiseConv2D.call does; "int8" rounds every image of x to int8 with its own scale and runs
+    gpfq_packed_depthwise_conv2d_forward_i8 -- exact int32 sums, the float kernel is never formed (include/gpfq.h has the arithmetic;
+    the layer's alphabet must be linspace(-1, 1, M) and kh * kw at most GPFQ_PACKED_DW_MAX_TAPS, which deploy.load_packed checks).  A
+    property of the loaded layer, not of its configuration: config(), clone() and save_model() record the DepthwiseConv2D it decodes
+    to.  ``fused``, ``emit_amax``, ``amax_from``: _FusedI8."""
+
+    ACTIVATIONS = ("float32", "int8")
+
+    def __init__(self, kernel_size, strides=(1, 1), padding="valid", depth_multiplier=1, dilation_rate=(1, 1),
+                 activation=None, use_bias=True, input_shape=None, name=None):
+        super().__init__(kernel_size, strides, padding, depth_multiplier, dilation_rate, activation, use_bias, input_shape, name)
+        self.packed = None
+        self.activations = "float32"
+        self._init_fused()
+
+    def build(self, input_shape, device, rng):
+        Layer.build(self, input_shape, device, rng)
+        cin = int(input_shape[-1])
+        self.kernel_shape = self._kernel_shape(cin)
+        self.fan_in = self.kernel_shape[0] * self.kernel_shape[1]
+        self._weights = [torch.zeros(self._out_channels(cin), device=device)] if self.use_bias else []     # (the bias alone)
+
+    def set_packed(self, packed, bias=None):
+        """packed: a deploy.pack_kernel(..., depthwise=True) result for a [kh][kw][Cin][mult] kernel, on this layer's device."""
+        if tuple(packed["shape"]) != tuple(self.kernel_shape) or not packed["depthwise"]:
+            raise ValueError(f"packed kernel of shape {tuple(packed['shape'])} (depthwise: {bool(packed['depthwise'])}), layer {self.name} "
+                             f"expects a depthwise kernel of shape {tuple(self.kernel_shape)}")
+        self.packed = packed
+        if self.use_bias and bias is not None:
+            Layer.set_weights(self, [bias])
+
+    def _kernel(self):
+        from . import deploy
+        if self.packed is None:
+            raise RuntimeError(f"PackedDepthwiseConv2D layer {self.name} holds no packed kernel (deploy.load_packed installs one)")
+        return deploy.unpack_kernel(self.packed)
+
+    def get_weights(self):
+        return [self._kernel().cpu().numpy()] + Layer.get_weights(self)
+
+    def set_weights(self, weights):
+        raise NotImplementedError("a PackedDepthwiseConv2D layer holds codes, not floats: its weights cannot be set")
+
+    def clone(self):
+        """A DepthwiseConv2D layer of the same configuration (clone_model: fresh float weights, as for every other layer)."""
+        c = DepthwiseConv2D(**self.config())
+        c.name = self.name
+        return c
+
+    def route(self):
+        """Which way a call runs: "i8" (gpfq_packed_depthwise_conv2d_forward_i8) or "decode" (decode + the float32 convolution)."""
+        if self.activations not in self.ACTIVATIONS:
+            raise ValueError(f"PackedDepthwiseConv2D layer {self.name}: activations must be one of {self.ACTIVATIONS}, "
+                             f"got {self.activations!r}")
+        return "i8" if self.activations == "int8" else "decode"
+
+    def _torch_weight(self):
+        kh, kw, cin, mult = self.kernel_shape
+        return self._kernel().permute(2, 3, 0, 1).reshape(cin * mult, 1, kh, kw), cin      # (DepthwiseConv2D's grouped layout)
+
+    def _bias(self):
+        return self._weights[0] if self.use_bias else None
+
+    def call(self, x):
+        if self.route() == "decode":
+            self._need_i8("decode")
+            return Conv2D.call(self, x)                                     # (the kernel through _torch_weight, the bias through _bias)
+        from . import hip
+        if self.packed is None:
+            raise RuntimeError(f"PackedDepthwiseConv2D layer {self.name} holds no packed kernel (deploy.load_packed installs one)")
+        p = self.packed
+        radii, bias, relu, rest = self._fused_parts(self._bias())
+        x = x.contiguous()
+        n = int(x.shape[0])
+        amax_out = self._amax_out(n, x.device)
+        y = hip.packed_depthwise_conv2d_forward_i8(x, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]), self.kernel_shape,
+                                                   self.strides, self.dilation_rate, self.padding, bias=bias, relu=relu,
+                                                   amax_out=amax_out, amax=self._taken_maxima(x, n, x[0].numel() if n else 0))
+        self._remember(y, amax_out, y[0].numel() if n else 0)
+        return rest(y)
+
+
 class Flatten(Layer):
     def __init__(self, input_shape=None, name=None):
         super().__init__(name)
@@ -1020,6 +1108,8 @@ def _arch_arrays(model):
         #  kernel, load_model reads it)
         #  (and a layer fused away as the plain layer it stands for)
         cls = "Dense" if isinstance(l, PackedDense) else ("Conv2D" if isinstance(l, PackedConv2D) else l.__class__.__name__)
+        if isinstance(l, PackedDepthwiseConv2D):
+            cls = "DepthwiseConv2D"
         if isinstance(l, _FusedAway):
             cls = l._plain.__name__
         spec = dict(cls=cls, name=l.name, config=l.config())

@@ -54,15 +54,16 @@ def write_link(path, input_shape, specs, M, rng, dev, deploy, hip, ks):
     random biases and BatchNormalization statistics."""
     layers = [dict(cls=s["cls"], name=f"l{k}", config=s["config"]) for k, s in enumerate(specs)]
     arch = dict(input_shape=list(input_shape), layers=layers, functional=False)
-    packed_cls = {"Dense": ks.PackedDense, "Conv2D": ks.PackedConv2D}
+    packed_cls = {"Dense": ks.PackedDense, "Conv2D": ks.PackedConv2D, "DepthwiseConv2D": ks.PackedDepthwiseConv2D}
     net = ks._network_from_arch(arch, dev, {k: packed_cls[s["cls"]] for k, s in enumerate(specs) if s["cls"] in packed_cls})
     arrays = {"__arch__": np.frombuffer(json.dumps(arch).encode("utf-8"), dtype=np.uint8),
               "__packed__": np.frombuffer(json.dumps(dict(version=deploy.FORMAT_VERSION)).encode("utf-8"), dtype=np.uint8)}
     bits = hip.packed_bits(M, 0)
     for k, layer in enumerate(net.layers):
-        if isinstance(layer, (ks.PackedDense, ks.PackedConv2D)):
-            shape = tuple(layer.kernel_shape) if isinstance(layer, ks.PackedConv2D) else (layer.fan_in, layer.units)
-            R, C = int(np.prod(shape[:-1])), shape[-1]
+        if isinstance(layer, tuple(packed_cls.values())):
+            depthwise = isinstance(layer, ks.PackedDepthwiseConv2D)
+            shape = (layer.fan_in, layer.units) if isinstance(layer, ks.PackedDense) else tuple(layer.kernel_shape)
+            R, C = (shape[0] * shape[1], shape[2] * shape[3]) if depthwise else (int(np.prod(shape[:-1])), shape[-1])
             idx = torch.randint(0, M, (R, C), device=dev, dtype=torch.int8)
             arrays[f"p{k}_codes"] = hip.pack_codes(idx, bits, 0).cpu().numpy()
             arrays[f"p{k}_radii"] = rng.uniform(0.5, 1.5, C) / np.sqrt(R)
@@ -70,7 +71,7 @@ def write_link(path, input_shape, specs, M, rng, dev, deploy, hip, ks):
             arrays[f"p{k}_bits"] = np.int32(bits)
             arrays[f"p{k}_zero_code"] = np.int32(0)
             arrays[f"p{k}_shape"] = np.asarray(shape, dtype=np.int64)
-            arrays[f"p{k}_depthwise"] = np.int32(0)
+            arrays[f"p{k}_depthwise"] = np.int32(depthwise)
             arrays[f"w{k}_1"] = (0.1 * rng.standard_normal(C)).astype(np.float32)
         elif isinstance(layer, ks.BatchNormalization):
             C = int(layer._weights[0].shape[0])
@@ -107,7 +108,8 @@ def capture(fn, chain):
     return g
 
 
-def run(links, batches, args, dev, out, deploy, hip, ks, members=(3, 16)):
+def run(links, batches, args, dev, out, deploy, hip, ks, members=(3, 16), packed=dict(packed_conv=True)):
+    """packed: load_packed's switches for the layer kinds that stay packed in both networks."""
     fmt = lambda t: f"{1e3 * t[0] / args.chain:8.1f} ({1e3 * t[1] / args.chain:7.1f} ..{1e3 * t[2] / args.chain:8.1f})"
     tally = dict(win=0, loss=0, spread=0)
     with tempfile.TemporaryDirectory() as tmp:
@@ -115,8 +117,8 @@ def run(links, batches, args, dev, out, deploy, hip, ks, members=(3, 16)):
             for M in members:
                 rng = np.random.default_rng(len(label) + M)
                 path = write_link(os.path.join(tmp, "link.npz"), input_shape, specs, M, rng, dev, deploy, hip, ks)
-                loose = deploy.load_packed(path, device=dev, activations="int8", packed_conv=True)
-                fused = deploy.load_packed(path, device=dev, activations="int8", packed_conv=True, fuse=True)
+                loose = deploy.load_packed(path, device=dev, activations="int8", **packed)
+                fused = deploy.load_packed(path, device=dev, activations="int8", fuse=True, **packed)
                 plan = "; ".join(f"{e['layer']}: fold {e['folded']}, relu {e['relu']}, hands to {e['hands_to']}" for e in fused.fusion_plan)
                 out(f"{label}, M={M}   [{plan}]")
                 out("    rows     unfused us, median (min .. max)    fused us                           unfused again                      "
