@@ -632,6 +632,45 @@ int gpfq_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t
                                             void *stream);
 
 /*
+ * MaxPooling2D on the same route: the pooled float32 images and, in the same pass, what the next packed
+ * layer's quantizer needs of them.  Opt-in; bit for bit:
+ *
+ * gpfq_maxpool2d_forward_i8:
+ *   x [device] f32 [n][H][W][C], contiguous; y [device] f32 [n][OH][OW][C], contiguous.
+ *   Geometry: TensorFlow's, by the formulas of gpfq_packed_conv2d_forward_i8 with rate 1: OH = gpfq_patch_out_dim(H, ph, sh, 1,
+ *   same_padding), OW likewise; under SAME the total pad splits floor(total / 2) before and the rest after.  A tap outside the image
+ *   takes no part in its window: it is not a zero.
+ *   The pooled value of (i, oh, ow, c): the taps x[i][oh * sh + ky - pad_top][ow * sw + kx - pad_left][c] are visited with ky
+ *   ascending, then kx ascending; m is the first tap inside the image, and a later tap v replaces m when v > m or v is a NaN.  So a
+ *   window that holds a NaN gives a NaN (which payload is not stated), and among zeros of both signs the first one met stays -- what
+ *   F.max_pool2d gives.  y[i][oh][ow][c] is this value bit for bit.
+ *   Exactly one of amax_in and amax_out is given.
+ *   With amax_in ([device] u32 [n], only read): xq ([device] i8, image i at xq + i * ldq), its pad bytes up to roundup16(OH*OW*C) and
+ *   scales ([device] f32 [n]) are exactly what gpfq_quantize_rows_i8_from_amax(y, n, OH*OW*C, OH*OW*C, amax_in, xq, ldq, scales) leaves
+ *   -- a function of (x, amax_in) whatever the caller passes, as that entry's contract says -- formed from the registers that hold y,
+ *   not from memory.  ldq, alignment and pad rules are that entry's.  ONE launch, no atomics; amax_out must be NULL.
+ *   Behind a ReLU, and with windows that cover the image (sh <= ph, sw <= pw and, under VALID, (H - ph) % sh == 0 and
+ *   (W - pw) % sw == 0), the maxima of the images of x ARE those of the images of y: every element lies in a window, none is negative.
+ *   Without amax_in: xq and scales are not touched.  amax_out ([device] u32 [n]) is cleared asynchronously on `stream` and on
+ *   completion amax_out[i] = max over the stored y of image i of (bits(y) & 0x7fffffff), by the rule of the fused forward passes above:
+ *   the maximum is taken inside a wavefront first, which then issues at most one agent-scope unsigned-max atomic without a return
+ *   value per image it stored into, and none for a maximum of 0.  The caller then runs gpfq_quantize_rows_i8_from_amax on y.  Two
+ *   operations on `stream`: the clear and one launch.
+ *   Every call gives the same bits; image i of y, xq, scales and amax_out depends on image i of x (and amax_in[i]) alone, not on n.
+ *   Whether C is a multiple of 4 (and x and y 16-byte aligned) decides how the kernel reads and stores (16 bytes, or element by
+ *   element), never what it computes.
+ * GPFQ_ERR_INVALID_ARG, before any launch: H, W, C, ph, pw, sh or sw not positive; n negative; a NULL x or y; both or neither of
+ * amax_in and amax_out; with amax_in, a NULL xq or scales, ldq not a multiple of 16 or below OH*OW*C, xq not 16-byte aligned.
+ * GPFQ_ERR_UNSUPPORTED: ph*pw > GPFQ_POOL_MAX_TAPS; H*W*C or n*OH*OW*C at or beyond 2^31.  n = 0 or an empty output (OH or OW = 0)
+ * returns GPFQ_OK without a launch: nothing is written or cleared.  Asynchronous on `stream`, no workgroup waiting for another, without
+ * workspace, scratch or host synchronisation; the call can be captured into a graph.  x, y, amax_in, xq, scales and amax_out must
+ * not overlap.
+ */
+#define GPFQ_POOL_MAX_TAPS 64
+int gpfq_maxpool2d_forward_i8(const float *x, int64_t n, int64_t H, int64_t W, int64_t C, int ph, int pw, int sh, int sw, int same_padding,
+                              float *y, const uint32_t *amax_in, int8_t *xq, int64_t ldq, float *scales, uint32_t *amax_out, void *stream);
+
+/*
  * Search over the alphabet scalar (a sequence as alphabet_scalar).  K candidate scalars s_0 .. s_{K-1}
  * (1 <= K <= GPFQ_SEARCH_MAX_CANDIDATES, each a finite positive number) are K * C independent columns of one walk with the unit
  * alphabet: candidate k of output channel j is column k * C + j (k-major: candidate k is a contiguous block of C columns).

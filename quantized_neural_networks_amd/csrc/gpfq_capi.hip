@@ -1126,6 +1126,36 @@ int gpfq_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
 }
 
+// MaxPooling2D on the int8 route: the checks in the pattern of the image entries above, every one before any launch
+int gpfq_maxpool2d_forward_i8(const float *x, int64_t n, int64_t H, int64_t W, int64_t C, int ph, int pw, int sh, int sw, int same_padding,
+                              float *y, const uint32_t *amax_in, int8_t *xq, int64_t ldq, float *scales, uint32_t *amax_out, void *stream)
+{
+    const char *name = "gpfq_maxpool2d_forward_i8";
+    if (n < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size n=%lld", (long long)n);
+    if (H <= 0 || W <= 0 || C <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad image shape H=%lld W=%lld C=%lld", (long long)H, (long long)W, (long long)C);
+    if (ph <= 0 || pw <= 0 || sh <= 0 || sw <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad window/stride %dx%d / %dx%d", ph, pw, sh, sw);
+    if (!x || !y) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if ((amax_in != nullptr) == (amax_out != nullptr))
+        return fail(GPFQ_ERR_INVALID_ARG, "exactly one of amax_in (codes from supplied maxima) and amax_out (maxima for the quantizer) must be given");
+    if (amax_in) {
+        if (!xq || !scales) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+        if (ldq % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld must be a multiple of 16", (long long)ldq);
+        if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
+    }
+    if ((int64_t)ph * pw > GPFQ_POOL_MAX_TAPS)
+        return fail(GPFQ_ERR_UNSUPPORTED, "ph*pw=%d*%d > GPFQ_POOL_MAX_TAPS=%d", ph, pw, GPFQ_POOL_MAX_TAPS);
+    const int64_t lim = 2147483647LL;               // (each product below its own bound first: no overflow)
+    if (H > lim / W || H * W > lim / C) return fail(GPFQ_ERR_UNSUPPORTED, "H*W*C at or beyond 2^31: too large for one launch");
+    const int64_t oh = gpfq_patch_out_dim(H, ph, sh, 1, same_padding), ow = gpfq_patch_out_dim(W, pw, sw, 1, same_padding);
+    const int64_t L = oh * ow * C;                  // (oh <= H and ow <= W: below 2^31)
+    if (amax_in && ldq < L) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld < OH*OW*C=%lld", (long long)ldq, (long long)L);
+    if (n == 0 || L == 0) return GPFQ_OK;
+    if (L > lim / n) return fail(GPFQ_ERR_UNSUPPORTED, "n*OH*OW*C at or beyond 2^31: too large for one launch");
+    const gpfq::ConvI8Shape S = conv_i8_shape(H, W, C, ph, pw, sh, sw, 1, 1, same_padding, oh, ow);
+    hipError_t e = gpfq::launch_maxpool2d_forward_i8(x, n, S, y, amax_in, xq, ldq, scales, amax_out, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
+}
+
 int gpfq_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii, const float *layer_median,
                            const double *scalars, int K, double *radii, float *W_cand, int64_t ldo, int64_t c_lo, int64_t c_hi,
                            void *stream)

@@ -385,6 +385,11 @@ int64_t packed_dw_i8_blocks(int64_t n, int64_t OH, int64_t OW, int64_t C);
 hipError_t launch_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
                                                      int mult, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                                      const float *bias, float *y, int relu, uint32_t *amax_bits, hipStream_t stream);
+// gpfq_pool_i8.hip: MaxPooling2D of float32 NHWC images, and from the same registers either their int8 codes
+// and scales under the maxima amax_in (one launch) or, amax_in NULL, their maxima into the cleared amax_out.  S as above with
+// kh x kw the window, Cin the channels and rh = rw = 1; the entry has checked n * OH * OW * Cin < 2^31.
+hipError_t launch_maxpool2d_forward_i8(const float *x, int64_t n, const ConvI8Shape &S, float *y, const uint32_t *amax_in, int8_t *xq,
+                                       int64_t ldq, float *scales, uint32_t *amax_out, hipStream_t stream);
 // gpfq_search.hip (a sequence as alphabet_scalar): the K candidate scalars travel by value
 constexpr int kSearchMaxK = 16;
 struct SearchScalars {

@@ -179,11 +179,14 @@ def _rows_of(shape, kind):
     return int(np.prod(dims[:-1])), dims[-1]
 
 
-def _plan(nodes, outputs, packed_at, shapes=None):
+def _plan(nodes, outputs, packed_at, shapes=None, pools=False):
     """The fusion plan of a network given as tables (host only).  nodes: per position dict(kind, activation, inbound positions);
     outputs: the positions of the network's outputs; packed_at: the positions of the packed layers on the int8 route; shapes: per
     position (input shape, output shape), or None -- no links are made then.  Returns per packed position
-    dict(folded, relu, hands_to): positions or None; relu is the layer's own position where its own activation is the ReLU."""
+    dict(folded, relu, hands_to): positions or None; relu is the layer's own position where its own activation is the ReLU.
+    pools: the link may pass one MaxPooling2D, and every entry has its position (or None) under ``pool``, before hands_to; a
+    MaxPooling2D in front of a packed layer that no entry names has an entry of its own, dict(folded=None, relu=None, pool, hands_to),
+    under its own position -- without shapes (the row matches cannot be made) that is every pool whose consumers lead to one."""
     consumers = [[] for _ in nodes]
     for k, node in enumerate(nodes):
         for p in node["inbound"]:
@@ -194,11 +197,30 @@ def _plan(nodes, outputs, packed_at, shapes=None):
         """The one consumer of position pos, or None (several, none, or a network output)."""
         return consumers[pos][0] if pos not in outputs and len(consumers[pos]) == 1 else None
 
+    def reach(pos, a_pool):
+        """(the packed layer the output of pos reaches through single-consumer Flatten / Dropout layers -- and, a_pool, one
+        MaxPooling2D -- at most, the pool passed) or (None, None)."""
+        pool = None
+        while True:
+            c = sole(pos)
+            if c is None:
+                return None, None
+            kind = nodes[c]["kind"]
+            if kind in ("Flatten", "Dropout") or (a_pool and pool is None and kind == "MaxPooling2D"):
+                pool = c if kind == "MaxPooling2D" else pool
+                pos = c
+                continue
+            return (c, pool) if c in packed_at else (None, None)
+
+    def feeds(pool, c):
+        """The images a pool leaves are the rows of packed layer c one to one (on the pool's output shape)."""
+        return shapes is None or _rows_of(shapes[pool][1], "Conv2D") == _rows_of(shapes[c][0], nodes[c]["kind"])
+
     plan = {}
     for k in packed_at:
         act = nodes[k]["activation"]
         linear, own_relu = act in (None, "linear"), act == "relu"
-        entry = dict(folded=None, relu=None, hands_to=None)
+        entry = dict(folded=None, relu=None, pool=None, hands_to=None) if pools else dict(folded=None, relu=None, hands_to=None)
         out = k
         if linear:
             c = sole(out)
@@ -211,18 +233,20 @@ def _plan(nodes, outputs, packed_at, shapes=None):
             if c is not None and (nodes[c]["kind"] == "ReLU" or (nodes[c]["kind"] == "Activation" and nodes[c]["activation"] == "relu")):
                 entry["relu"] = out = c
         if (linear or own_relu) and shapes is not None:               # (another activation stays a torch op: nothing to hand on)
-            pos = out
-            while True:
-                c = sole(pos)
-                if c is None:
-                    break
-                if nodes[c]["kind"] in ("Flatten", "Dropout"):
-                    pos = c
-                    continue
-                if c in packed_at and _rows_of(shapes[k][1], nodes[k]["kind"]) == _rows_of(shapes[c][0], nodes[c]["kind"]):
-                    entry["hands_to"] = c
-                break
+            c, pool = reach(out, pools)
+            rows = _rows_of(shapes[k][1], nodes[k]["kind"])
+            if c is not None and pool is None and rows == _rows_of(shapes[c][0], nodes[c]["kind"]):
+                entry["hands_to"] = c
+            elif c is not None and pool is not None and rows == _rows_of(shapes[pool][0], "Conv2D") and feeds(pool, c):
+                entry["pool"], entry["hands_to"] = pool, c
         plan[k] = entry
+    if pools:
+        named = {e["pool"] for e in plan.values()}
+        for p, node in enumerate(nodes):
+            if node["kind"] == "MaxPooling2D" and p not in named:
+                c, _ = reach(p, False)
+                if c is not None and feeds(p, c):
+                    plan[p] = dict(folded=None, relu=None, pool=p, hands_to=c)
     return plan
 
 
@@ -238,7 +262,7 @@ def _net_tables(net):
     return nodes, outputs
 
 
-def plan_fusion(net, packed_at=None):
+def plan_fusion(net, packed_at=None, pools=False):
     """The plan of load_packed(..., fuse=True) for a keras_shim network (Sequential, or a functional Model): a list with one dict per
     packed layer on the int8 route, in layer order --
 
@@ -255,7 +279,16 @@ def plan_fusion(net, packed_at=None):
     a BatchNormalization, and is not a network output; RELU where P's own activation is "relu" (nothing is folded then), or where the
     group's output so far has exactly one consumer, a ReLU or Activation("relu"), and is not a network output; LINK where the group's
     output reaches, through single-consumer Flatten / Dropout layers at most, a packed layer whose rows are this layer's rows or
-    images one to one.  Any other activation stays a torch op and nothing is handed on."""
+    images one to one.  Any other activation stays a torch op and nothing is handed on.
+
+    pools=True (load_packed(..., fuse_pool=True)): the LINK walk also passes ONE MaxPooling2D that has a single
+    consumer and is not a network output, where the layer's images are the pool's and -- on the pool's output shape -- the pool's
+    images the rows of the packed layer behind it.  Every dict then has one more key, ``pool``: that MaxPooling2D's name, or None;
+    ``hands_to`` is the packed layer behind it, which takes the pool's codes, not this layer's maxima.  A MaxPooling2D whose single
+    consumer, through Flatten / Dropout layers at most, is a packed layer of the route, and that no packed layer's entry names (none
+    stands in front of it, or its activation or rows keep it from linking), is listed too, in layer order at its own position, as
+    dict(layer=None, folded=None, relu=None, pool=its name, hands_to=that layer).  With pools=False the dicts are exactly those
+    above, without the key."""
     net = _shim_network(net)
     if packed_at is None:
         packed_at = [k for k, l in enumerate(net.layers)
@@ -266,10 +299,13 @@ def plan_fusion(net, packed_at=None):
     if bad:
         raise ValueError(f"plan_fusion: positions {bad} are not Dense or Conv2D / DepthwiseConv2D layers")
     shapes = [(l.input_shape, l.output_shape) for l in net.layers]
-    plan = _plan(nodes, outputs, packed_at, shapes)
+    plan = _plan(nodes, outputs, packed_at, shapes, pools)
     name = lambda k: None if k is None else net.layers[k].name
-    return [dict(layer=name(k), folded=name(e["folded"]), relu=name(e["relu"]), hands_to=name(e["hands_to"]))
-            for k, e in sorted(plan.items())]
+    if not pools:
+        return [dict(layer=name(k), folded=name(e["folded"]), relu=name(e["relu"]), hands_to=name(e["hands_to"]))
+                for k, e in sorted(plan.items())]
+    return [dict(layer=name(k) if k in packed_at else None, folded=name(e["folded"]), relu=name(e["relu"]), pool=name(e["pool"]),
+                 hands_to=name(e["hands_to"])) for k, e in sorted(plan.items())]
 
 
 def _arch_tables(arch):
@@ -288,11 +324,18 @@ def _arch_tables(arch):
 _FUSED_AWAY = {"BatchNormalization": "FoldedBatchNormalization", "Activation": "FusedActivation", "ReLU": "FusedReLU"}
 
 
-def _apply_fusion(net, packed_at):
-    """Sets the fused state of the packed layers of a loaded network from its plan and records the plan as net.fusion_plan."""
+def _apply_fusion(net, packed_at, pools=False):
+    """Sets the fused state of the packed layers of a loaded network from its plan and records the plan as net.fusion_plan.  pools:
+    the plan with its pools -- a named pool is linked, the layer behind it takes its codes, a packed layer in front hands it maxima."""
     pos = {l.name: k for k, l in enumerate(net.layers)}
-    net.fusion_plan = plan_fusion(net, packed_at)
+    net.fusion_plan = plan_fusion(net, packed_at, pools) if pools else plan_fusion(net, packed_at)
     for e in net.fusion_plan:
+        if e.get("pool") is not None:
+            pool = net.layers[pos[e["pool"]]]
+            pool.linked = True
+            net.layers[pos[e["hands_to"]]].codes_from = pool
+        if e["layer"] is None:
+            continue
         layer = net.layers[pos[e["layer"]]]
         p = layer.packed
         radii = p["radii"].cpu().numpy()
@@ -304,12 +347,14 @@ def _apply_fusion(net, packed_at):
         to = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device=net.device, dtype=dt).contiguous()
         layer.fused = dict(radii=to(radii, torch.float64), bias=to(bias, torch.float32), relu=e["relu"] is not None)
         layer.emit_amax = e["hands_to"] is not None
-        if e["hands_to"] is not None:
+        if e.get("pool") is not None:
+            net.layers[pos[e["pool"]]].amax_from = layer
+        elif e["hands_to"] is not None:
             net.layers[pos[e["hands_to"]]].amax_from = layer
     return net
 
 
-def load_packed(path, device=None, activations="float32", packed_conv=False, fuse=False, packed_depthwise=False):
+def load_packed(path, device=None, activations="float32", packed_conv=False, fuse=False, packed_depthwise=False, fuse_pool=False):
     """Inverse of export_packed: a keras_shim network on ``device`` (default: the current GPU).  Dense layers that were exported
     packed come back as keras_shim.PackedDense (codes, radii and bias in device memory; the float kernel is never formed unless
     get_weights() or a batch beyond keras_shim.PACKED_TILED_MAX_BATCH asks for it); packed Conv2D / DepthwiseConv2D kernels are
@@ -335,7 +380,15 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
     kernel's epilogue; and a packed layer whose output feeds another one hands it the maxima its quantizer would search for.
     The layers folded or fused away keep their positions, names and weights and pass their input on (keras_shim.FoldedBatchNormalization,
     FusedActivation, FusedReLU): in a fused network the value at such a position, and at the packed layer's own, is the group's
-    output.  Everything but the fold is bit for bit what fuse=False computes; the fold differs by float32 roundings alone."""
+    output.  Everything but the fold is bit for bit what fuse=False computes; the fold differs by float32 roundings alone.
+
+    fuse_pool=True (needs fuse=True): the plan is plan_fusion(..., pools=True).  Every MaxPooling2D it names
+    is a keras_shim.QuantizingMaxPooling2D: one HIP pass (hip.maxpool2d_forward_i8) pools the float32 images AND leaves their int8
+    codes and scales, which the packed layer behind the pool takes in place of running its quantizer; a packed layer in front hands
+    the pool its maxima, and behind a fused ReLU, with windows that cover the image, the pool needs nothing else.  The value at every
+    position is bit for bit what fuse_pool=False computes."""
+    if fuse_pool and not fuse:
+        raise ValueError("fuse_pool=True hands a pool the maxima of the fused int8 layer before it and its codes to the one behind: it needs fuse=True")
     if activations not in keras_shim.PackedDense.ACTIVATIONS:
         raise ValueError(f"activations must be one of {keras_shim.PackedDense.ACTIVATIONS}, got {activations!r}")
     if fuse and activations != "int8":
@@ -362,6 +415,11 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
                 for k in (e["folded"], e["relu"]):
                     if k is not None and k not in fused_at:
                         classes[k] = getattr(keras_shim, _FUSED_AWAY[arch["layers"][k]["cls"]])
+            if fuse_pool:
+                # every pool the full plan can name (the row matches need the network's shapes: _apply_fusion links those that pass)
+                for e in _plan(nodes, outputs, fused_at, pools=True).values():
+                    if e["pool"] is not None:
+                        classes[e["pool"]] = keras_shim.QuantizingMaxPooling2D
         net = keras_shim._network_from_arch(arch, device, classes)
         for k, layer in enumerate(net.layers):
             if k in packed_at:
@@ -376,4 +434,4 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
                     layer.set_weights([unpack_kernel(packed)] + rest)
             elif layer._weights:
                 layer.set_weights([z[f"w{k}_{j}"] for j in range(len(layer._weights))])
-    return _apply_fusion(net, fused_at) if fuse else net
+    return _apply_fusion(net, fused_at, fuse_pool) if fuse else net

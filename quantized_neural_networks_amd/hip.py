@@ -29,6 +29,7 @@ GPFQ_REFINE_PAIRS_MAX_K = 64       # longest walk of an (input channel, filter) 
 GPFQ_ERR_INVALID_ARG, GPFQ_ERR_UNSUPPORTED, GPFQ_ERR_WORKSPACE = -1, -2, -3
 GPFQ_PACKED_I8_MAX_N = 262144      # longest row of the int8 packed forward pass: its int32 sums cannot overflow (include/gpfq.h)
 GPFQ_PACKED_DW_MAX_TAPS = 64       # most taps kh * kw of the int8 packed DepthwiseConv2D forward pass (include/gpfq.h)
+GPFQ_POOL_MAX_TAPS = 64            # most taps ph * pw of the int8 route's MaxPooling2D (include/gpfq.h)
 
 # every symbol include/gpfq.h declares: (restype, argtypes)
 _i64, _int, _vp, _sz = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
@@ -82,6 +83,7 @@ SYMBOLS = {
     "gpfq_quantize_rows_i8_from_amax": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "gpfq_packed_depthwise_conv2d_forward_i8": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int,
                                                        _int, _vp, _int, _int, _vp, _int, _vp, _vp, _int, _vp, _vp]),
+    "gpfq_maxpool2d_forward_i8": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "gpfq_candidate_kernels": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dp, _int, _vp, _vp, _i64, _i64, _i64, _vp]),
     "gpfq_select_candidates_workspace_bytes": (_sz, [_int, _i64]),
     "gpfq_select_candidates": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _dp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
@@ -1655,3 +1657,41 @@ def packed_depthwise_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, 
                                                               radii.data_ptr(), int(M), bp, out.data_ptr(), relu, ap, _stream()),
                "gpfq_packed_depthwise_conv2d_forward_i8")
     return out
+
+
+def maxpool2d_forward_i8(x, pool_size, strides, padding, amax=None):
+    """MaxPooling2D of float32 NHWC images x [n][H][W][C] together with the int8 codes of the pooled images
+    (gpfq_maxpool2d_forward_i8; the contract is include/gpfq.h's, bit for bit; TensorFlow's geometry; ph * pw <= GPFQ_POOL_MAX_TAPS)
+    -> (y f32 [n][OH][OW][C], xq i8 [n][roundup16(OH*OW*C)], scales f32 [n]): xq and scales are quantize_rows_i8's of the flattened
+    images of y.  amax: a uint32 or int32 [n] tensor of maxima of bits & 0x7fffffff to quantize under -- the pooled images' own, which
+    behind a ReLU and under windows that cover the image are the unpooled images' -- and the call is ONE launch, the codes formed from
+    the registers that hold y; without it the kernel leaves the pooled images' maxima and quantize_rows_i8(y, amax=...) follows: two
+    operations and a clear.  The same bits either way when the maxima are the pooled images' own.  No sync."""
+    _dev(x, torch.float32, "x")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise GpfqError(f"x must be a contiguous NHWC tensor [n][H][W][C], got {tuple(x.shape)}")
+    ph, pw, sh, sw, _, _, same = conv_geometry(pool_size, strides, (1, 1), padding)
+    n, H, W, C = (int(v) for v in x.shape)
+    if min(H, W, C, ph, pw, sh, sw) <= 0:
+        raise GpfqError("image sides, channels, window sides and strides must be positive")
+    OH, OW = patch_out_dim(H, ph, sh, 1, same), patch_out_dim(W, pw, sw, 1, same)
+    L = OH * OW * C
+    y = torch.empty((n, OH, OW, C), dtype=torch.float32, device=x.device)
+    if n == 0 or L == 0:                            # (nothing to pool: the quantizer's own rules for empty rows)
+        cells = amax if amax is not None else torch.zeros(n, dtype=torch.int32, device=x.device)
+        return (y,) + tuple(quantize_rows_i8(y.reshape(n, L), amax=cells))
+    entry = load().gpfq_maxpool2d_forward_i8
+    geometry = (n, H, W, C, ph, pw, sh, sw, 1 if same else 0)
+    if amax is None:
+        cells = torch.empty(n, dtype=torch.int32, device=x.device)
+        with torch.cuda.device(x.device):
+            _check(entry(x.data_ptr(), *geometry, y.data_ptr(), None, None, 0, None, cells.data_ptr(), _stream()), "gpfq_maxpool2d_forward_i8")
+        return (y,) + tuple(quantize_rows_i8(y.reshape(n, L), amax=cells))
+    ap = _amax_cells(amax, n, "amax")
+    ldq = (L + 15) // 16 * 16
+    xq = torch.empty((n, ldq), dtype=torch.int8, device=x.device)
+    scales = torch.empty(n, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(entry(x.data_ptr(), *geometry, y.data_ptr(), ap, xq.data_ptr(), ldq, scales.data_ptr(), None, _stream()),
+               "gpfq_maxpool2d_forward_i8")
+    return y, xq, scales

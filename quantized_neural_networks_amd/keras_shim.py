@@ -226,6 +226,14 @@ PACKED_FORWARD_MAX_BATCH = 4
 PACKED_TILED_MAX_BATCH = 128
 
 
+def _untouched(x, y, version):
+    """x is the tensor y (None: gone) as its producer wrote it at `version`: contiguous float32 over the same storage at the same
+    offset with the same element count, and no in-place operation since."""
+    return (y is not None and x.dtype == torch.float32 and x.is_contiguous() and x.device == y.device
+            and x.untyped_storage().data_ptr() == y.untyped_storage().data_ptr() and x.storage_offset() == y.storage_offset()
+            and x.numel() == y.numel() and x._version == version and y._version == version)
+
+
 class _FusedI8:
     """What deploy.load_packed(..., fuse=True) sets on a packed layer of the int8 route, and what the layer does
     with it.  Three pieces of state, all None / False on a layer loaded without ``fuse``:
@@ -247,6 +255,7 @@ class _FusedI8:
         self.fused = None
         self.emit_amax = False
         self.amax_from = None
+        self.codes_from = None                        # (the QuantizingMaxPooling2D in front: load_packed(..., fuse_pool=True))
         self._handoff = None                          # (weak reference to the output, its version, maxima i32 [rows], floats per row)
 
     def _fused_parts(self, bias):
@@ -270,13 +279,32 @@ class _FusedI8:
         if hand is None:
             return None
         ref, version, amax, per_row = hand
-        y = ref()
-        if (y is None or x.dtype != torch.float32 or not x.is_contiguous() or x.device != y.device
-                or x.untyped_storage().data_ptr() != y.untyped_storage().data_ptr() or x.storage_offset() != y.storage_offset()
-                or x.numel() != y.numel() or x._version != version or y._version != version
-                or rows != amax.numel() or row_len != per_row):
+        if not _untouched(x, ref(), version) or rows != amax.numel() or row_len != per_row:
             return None
         return amax
+
+    def _taken_codes(self, x, rows, row_len):
+        """(xq, scales) of the rows of x as the QuantizingMaxPooling2D in front left them, or None (quantize here): ``_taken_maxima``'s
+        proof against the pool's remembered output.  Flatten's reshape is a view -- the same storage, offset, element count and
+        version counter -- so the proof holds through it."""
+        hand = getattr(self.codes_from, "_codes", None) if self.codes_from is not None else None
+        if hand is None:
+            return None
+        ref, version, xq, scales, per_row = hand
+        if not _untouched(x, ref(), version) or rows != scales.numel() or row_len != per_row:
+            return None
+        return xq, scales
+
+    def _i8_input(self, x):
+        """The contiguous float32 images x of an image layer's int8 route -> (what its forward binding takes first, the keyword
+        arguments that go with it): the int8 images and scales the pool in front left (``_taken_codes``), or x and the producer's
+        maxima, if any, for the quantizer inside the binding."""
+        n = int(x.shape[0])
+        per = x[0].numel() if n else 0
+        codes = self._taken_codes(x, n, per)
+        if codes is not None:
+            return codes[0][:, :per].unflatten(1, tuple(x.shape[1:])), dict(scales=codes[1])
+        return x, dict(amax=self._taken_maxima(x, n, per))
 
     def _need_i8(self, route):
         if self.fused is not None and route != "i8":
@@ -360,8 +388,14 @@ class PackedDense(Dense, _FusedI8):
             radii, fbias, relu, rest = self._fused_parts(bias)
             x2 = x2.contiguous()
             amax_out = self._amax_out(x2.shape[0], x2.device)
+            codes = self._taken_codes(x2, x2.shape[0], self.fan_in)
+            if codes is not None:                                           # (the pool in front quantized its output: no quantizer here)
+                given = dict(scales=codes[1])
+                x2 = codes[0]
+            else:
+                given = dict(amax=self._taken_maxima(x2, x2.shape[0], self.fan_in))
             y = hip.packed_dense_forward_i8(x2, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]), self.fan_in, bias=fbias,
-                                            relu=relu, amax_out=amax_out, amax=self._taken_maxima(x2, x2.shape[0], self.fan_in))
+                                            relu=relu, amax_out=amax_out, **given)
             self._remember(y, amax_out, self.units)
             return rest(y.reshape(tuple(x.shape[:-1]) + (self.units,)))
         elif route != "matmul":
@@ -513,9 +547,10 @@ class PackedConv2D(Conv2D, _FusedI8):
         x = x.contiguous()
         n = int(x.shape[0])
         amax_out = self._amax_out(n, x.device)
+        x, given = self._i8_input(x)
         y = hip.packed_conv2d_forward_i8(x, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]), self.kernel_shape,
                                          self.strides, self.dilation_rate, self.padding, bias=bias, relu=relu, amax_out=amax_out,
-                                         amax=self._taken_maxima(x, n, x[0].numel() if n else 0))
+                                         **given)
         self._remember(y, amax_out, y[0].numel() if n else 0)
         return rest(y)
 
@@ -626,9 +661,10 @@ class PackedDepthwiseConv2D(DepthwiseConv2D, _FusedI8):
         x = x.contiguous()
         n = int(x.shape[0])
         amax_out = self._amax_out(n, x.device)
+        x, given = self._i8_input(x)
         y = hip.packed_depthwise_conv2d_forward_i8(x, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]), self.kernel_shape,
                                                    self.strides, self.dilation_rate, self.padding, bias=bias, relu=relu,
-                                                   amax_out=amax_out, amax=self._taken_maxima(x, n, x[0].numel() if n else 0))
+                                                   amax_out=amax_out, **given)
         self._remember(y, amax_out, y[0].numel() if n else 0)
         return rest(y)
 
@@ -674,6 +710,57 @@ class MaxPooling2D(_Pool2D):
             pl, pr = _same_pads(x.shape[3], self.pool_size[1], self.strides[1], 1)
             x = F.pad(x, (pl, pr, pt, pb), value=float("-inf"))
         return F.max_pool2d(x, self.pool_size, self.strides).permute(0, 2, 3, 1).contiguous()
+
+
+def pool_covers(H, W, pool_size, strides, padding):
+    """Every element of an H x W image lies in a window of this max pooling: no stride beyond its window side and, under "valid", no
+    leftover row or column.  With that, and no negative element, the maximum of the pooled image is the maximum of the image."""
+    (ph, pw), (sh, sw) = pool_size, strides
+    if sh > ph or sw > pw:
+        return False
+    return str(padding).lower() == "same" or (H >= ph and W >= pw and (H - ph) % sh == 0 and (W - pw) % sw == 0)
+
+
+class QuantizingMaxPooling2D(MaxPooling2D):
+    """A MaxPooling2D in front of a packed layer of the int8 route (deploy.load_packed(..., fuse=True, fuse_pool=True); DESIGN.md
+    section 11e): where the plan names it (``linked``) its call is hip.maxpool2d_forward_i8 -- the pooled float32 images, the value
+    and shape of a max pooling at this position, and with them the int8 codes and scales the consumer's quantizer would make, which the
+    consumer takes (_FusedI8._taken_codes) in place of quantizing.  A pool load_packed built of this class that the plan then left
+    out is a MaxPooling2D.  config(), clone() and save_model() give the MaxPooling2D.
+
+    ``amax_from``: the packed layer whose images this pool takes, or None.  The call is ONE launch where the input is, by
+    _FusedI8._taken_maxima's proof, that layer's untouched output with its maxima, that layer's ReLU is fused (no element is
+    negative) and the windows cover the image (pool_covers): the maxima of the pooled images are then the producer's.  Anything else
+    takes two operations -- the kernel leaves the pooled maxima, the from-amax quantizer follows -- with the same result."""
+
+    def __init__(self, pool_size=(2, 2), strides=None, padding="valid", name=None):
+        super().__init__(pool_size, strides, padding, name)
+        self.linked = False
+        self.amax_from = None
+        self._codes = None                            # (weak reference to the output, its version, xq, scales, floats per image)
+
+    def clone(self):
+        c = MaxPooling2D(**self.config())
+        c.name = self.name
+        return c
+
+    def _producer_maxima(self, x):
+        producer = self.amax_from
+        if producer is None or not (producer.fused or {}).get("relu"):
+            return None
+        if not pool_covers(int(x.shape[1]), int(x.shape[2]), self.pool_size, self.strides, self.padding):
+            return None
+        n = int(x.shape[0])
+        return _FusedI8._taken_maxima(self, x, n, x[0].numel() if n else 0)
+
+    def call(self, x):
+        if not self.linked:
+            return MaxPooling2D.call(self, x)
+        from . import hip
+        x = x.contiguous()
+        y, xq, scales = hip.maxpool2d_forward_i8(x, self.pool_size, self.strides, self.padding, amax=self._producer_maxima(x))
+        self._codes = (weakref.ref(y), y._version, xq, scales, y[0].numel() if y.shape[0] else 0)
+        return y
 
 
 class AveragePooling2D(_Pool2D):
@@ -1112,6 +1199,8 @@ def _arch_arrays(model):
             cls = "DepthwiseConv2D"
         if isinstance(l, _FusedAway):
             cls = l._plain.__name__
+        if isinstance(l, QuantizingMaxPooling2D):
+            cls = "MaxPooling2D"
         spec = dict(cls=cls, name=l.name, config=l.config())
         if functional:
             inbound = l.inbound_nodes[0].inbound_layers
