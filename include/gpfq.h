@@ -671,6 +671,33 @@ int gpfq_maxpool2d_forward_i8(const float *x, int64_t n, int64_t H, int64_t W, i
                               float *y, const uint32_t *amax_in, int8_t *xq, int64_t ldq, float *scales, uint32_t *amax_out, void *stream);
 
 /*
+ * A residual join on the same route: the sum of two float32 tensors, an optional ReLU, and what the packed
+ * layers that consume the sum need of it -- its int8 codes and scales, made once.  Opt-in; bit for bit:
+ *
+ * gpfq_add_forward_i8:
+ *   a, b [device] f32 [n][L], contiguous; y [device] f32 [n][L], contiguous.  Sample i is one row: one image of the consumer.
+ *   Per element: s = a + b, ONE float32 add; y = (relu && s < 0) ? +0.0f : s -- the fused epilogues' rule: a NaN stays a NaN (which
+ *   payload is not stated), -0.0f stays -0.0f.
+ *   amax_bits ([device] u32 [n]) is cleared asynchronously on `stream` and on completion amax_bits[i] = max over image i of
+ *   (bits(y) & 0x7fffffff), the cell the fused forward passes above leave: an Inf or a NaN puts it at or above 0x7f800000.  The
+ *   maximum is taken inside a workgroup of one chunk of gpfq_quantize_split_chunk() floats first, which then issues at most one
+ *   agent-scope unsigned-max atomic without a return value, and none for a maximum of 0.
+ *   xq ([device] i8, image i at xq + i * ldq), its pad bytes up to roundup16(L) and scales ([device] f32 [n]) are exactly what
+ *   gpfq_quantize_rows_i8(y, n, L, L, xq, ldq, scales) would leave; ldq, alignment and pad rules are that entry's.
+ *   Every call gives the same bits; image i of y, amax_bits, xq and scales depends on image i of a and b alone, not on n.  Whether
+ *   L is a multiple of 4 (and a, b and y 16-byte aligned) decides how the kernel reads and stores (16 bytes, or element by element),
+ *   never what it computes.
+ *   At most three operations on `stream`, ordered by the stream alone: the clear, the join, the from-amax quantizer on y.
+ * GPFQ_ERR_INVALID_ARG, before any launch: n negative; L not positive; relu not 0 or 1; a NULL a, b, y, amax_bits, xq or scales; ldq
+ * not a multiple of 16 or below L; xq not 16-byte aligned.  GPFQ_ERR_UNSUPPORTED: L at or beyond 2^31 chunks; n at or beyond 2^31.
+ * n = 0 returns GPFQ_OK without a launch: nothing is written or cleared.  Asynchronous on `stream`, no workgroup waiting for another,
+ * without workspace, scratch or host synchronisation; the call can be captured into a graph.  The outputs must not overlap each
+ * other or the inputs.
+ */
+int gpfq_add_forward_i8(const float *a, const float *b, int64_t n, int64_t L, int relu, float *y, uint32_t *amax_bits, int8_t *xq,
+                        int64_t ldq, float *scales, void *stream);
+
+/*
  * Search over the alphabet scalar (a sequence as alphabet_scalar).  K candidate scalars s_0 .. s_{K-1}
  * (1 <= K <= GPFQ_SEARCH_MAX_CANDIDATES, each a finite positive number) are K * C independent columns of one walk with the unit
  * alphabet: candidate k of output channel j is column k * C + j (k-major: candidate k is a contiguous block of C columns).

@@ -1156,6 +1156,22 @@ int gpfq_maxpool2d_forward_i8(const float *x, int64_t n, int64_t H, int64_t W, i
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
 }
 
+// a residual join on the int8 route: every check before any launch
+int gpfq_add_forward_i8(const float *a, const float *b, int64_t n, int64_t L, int relu, float *y, uint32_t *amax_bits, int8_t *xq,
+                        int64_t ldq, float *scales, void *stream)
+{
+    if (n < 0 || L <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad size n=%lld L=%lld", (long long)n, (long long)L);
+    if (relu != 0 && relu != 1) return fail(GPFQ_ERR_INVALID_ARG, "relu=%d must be 0 or 1", relu);
+    if (!a || !b || !y || !amax_bits || !xq || !scales) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (ldq % 16 != 0 || ldq < L) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld must be a multiple of 16 and at least L=%lld", (long long)ldq, (long long)L);
+    if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
+    if (L / gpfq::quantize_split_chunk() >= 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "image too long for one launch");
+    if (n > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "batch too long for one launch");
+    if (n == 0) return GPFQ_OK;
+    hipError_t e = gpfq::launch_add_forward_i8(a, b, n, L, relu, y, amax_bits, xq, ldq, scales, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_add_forward_i8");
+}
+
 int gpfq_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii, const float *layer_median,
                            const double *scalars, int K, double *radii, float *W_cand, int64_t ldo, int64_t c_lo, int64_t c_hi,
                            void *stream)

@@ -358,6 +358,7 @@ hipError_t launch_packed_dense_forward_i8_fused(const int8_t *xq, int64_t B, int
                                                 int64_t C, float *y, int64_t ldy, int relu, uint32_t *amax_bits, hipStream_t stream);
 // gpfq_quantize_split.hip (addendum): launch_quantize_rows_i8's result bit for bit with a row spread over
 // workgroups of quantize_split_chunk() floats each -- a clear of scales and three launches, scales holding the rows' maxima in between
+constexpr int64_t kQuantizeSplitChunk = 4096;     // what quantize_split_chunk() returns, for the kernels cut to the same chunks
 int64_t quantize_split_chunk();
 hipError_t launch_quantize_rows_i8_split(const float *x, int64_t B, int64_t ldx, int64_t N, int8_t *xq, int64_t ldq, float *scales,
                                          hipStream_t stream);
@@ -390,6 +391,10 @@ hipError_t launch_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n
 // kh x kw the window, Cin the channels and rh = rw = 1; the entry has checked n * OH * OW * Cin < 2^31.
 hipError_t launch_maxpool2d_forward_i8(const float *x, int64_t n, const ConvI8Shape &S, float *y, const uint32_t *amax_in, int8_t *xq,
                                        int64_t ldq, float *scales, uint32_t *amax_out, hipStream_t stream);
+// gpfq_add_i8.hip: y = a + b on [n][L] contiguous float32, an optional ReLU, the images' maxima into the
+// cleared amax_bits, then launch_quantize_rows_i8_from_amax on y: three stream operations.  The entry has checked the sizes.
+hipError_t launch_add_forward_i8(const float *a, const float *b, int64_t n, int64_t L, int relu, float *y, uint32_t *amax_bits, int8_t *xq,
+                                 int64_t ldq, float *scales, hipStream_t stream);
 // gpfq_search.hip (a sequence as alphabet_scalar): the K candidate scalars travel by value
 constexpr int kSearchMaxK = 16;
 struct SearchScalars {

@@ -32,6 +32,7 @@ constexpr int kSplitThreads = 256;
 constexpr int kSplitGroups = 4;                                     // groups of four floats per thread
 constexpr int64_t kSplitChunk = 4 * kSplitGroups * kSplitThreads;   // 4096 floats: 16 KiB of x, 4 KiB of xq per workgroup
 static_assert(kSplitChunk % 16 == 0, "a chunk ends on a 16-byte boundary of xq");
+static_assert(kSplitChunk == kQuantizeSplitChunk, "gpfq_launch.hpp states the chunk for the kernels cut to it");
 
 __device__ inline bool aligned16(const float *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

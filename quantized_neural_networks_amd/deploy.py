@@ -179,14 +179,21 @@ def _rows_of(shape, kind):
     return int(np.prod(dims[:-1])), dims[-1]
 
 
-def _plan(nodes, outputs, packed_at, shapes=None, pools=False):
+def _is_relu(node):
+    return node["kind"] == "ReLU" or (node["kind"] == "Activation" and node["activation"] == "relu")
+
+
+def _plan(nodes, outputs, packed_at, shapes=None, pools=False, adds=False):
     """The fusion plan of a network given as tables (host only).  nodes: per position dict(kind, activation, inbound positions);
     outputs: the positions of the network's outputs; packed_at: the positions of the packed layers on the int8 route; shapes: per
     position (input shape, output shape), or None -- no links are made then.  Returns per packed position
     dict(folded, relu, hands_to): positions or None; relu is the layer's own position where its own activation is the ReLU.
     pools: the link may pass one MaxPooling2D, and every entry has its position (or None) under ``pool``, before hands_to; a
     MaxPooling2D in front of a packed layer that no entry names has an entry of its own, dict(folded=None, relu=None, pool, hands_to),
-    under its own position -- without shapes (the row matches cannot be made) that is every pool whose consumers lead to one."""
+    under its own position -- without shapes (the row matches cannot be made) that is every pool whose consumers lead to one.
+    adds: every entry has the key ``add`` (None), before hands_to, and an Add of two inbound tensors with a packed consumer has an
+    entry of its own under its own position, dict(folded=None, relu, [pool=None,] add, hands_to=a tuple of positions) -- without
+    shapes (the inbound shapes and the row matches cannot be compared) that is every such Add with a packed direct consumer."""
     consumers = [[] for _ in nodes]
     for k, node in enumerate(nodes):
         for p in node["inbound"]:
@@ -220,7 +227,7 @@ def _plan(nodes, outputs, packed_at, shapes=None, pools=False):
     for k in packed_at:
         act = nodes[k]["activation"]
         linear, own_relu = act in (None, "linear"), act == "relu"
-        entry = dict(folded=None, relu=None, pool=None, hands_to=None) if pools else dict(folded=None, relu=None, hands_to=None)
+        entry = dict(folded=None, relu=None, **(dict(pool=None) if pools else {}), **(dict(add=None) if adds else {}), hands_to=None)
         out = k
         if linear:
             c = sole(out)
@@ -230,7 +237,7 @@ def _plan(nodes, outputs, packed_at, shapes=None, pools=False):
             entry["relu"] = k
         elif linear:
             c = sole(out)
-            if c is not None and (nodes[c]["kind"] == "ReLU" or (nodes[c]["kind"] == "Activation" and nodes[c]["activation"] == "relu")):
+            if c is not None and _is_relu(nodes[c]):
                 entry["relu"] = out = c
         if (linear or own_relu) and shapes is not None:               # (another activation stays a torch op: nothing to hand on)
             c, pool = reach(out, pools)
@@ -246,7 +253,21 @@ def _plan(nodes, outputs, packed_at, shapes=None, pools=False):
             if node["kind"] == "MaxPooling2D" and p not in named:
                 c, _ = reach(p, False)
                 if c is not None and feeds(p, c):
-                    plan[p] = dict(folded=None, relu=None, pool=p, hands_to=c)
+                    plan[p] = dict(folded=None, relu=None, pool=p, **(dict(add=None) if adds else {}), hands_to=c)
+    if adds:                                        # rule JOIN
+        for p, node in enumerate(nodes):
+            if node["kind"] != "Add" or len(node["inbound"]) != 2:
+                continue
+            if shapes is not None and tuple(shapes[p][0][0]) != tuple(shapes[p][0][1]):
+                continue
+            out, c = p, sole(p)
+            if c is not None and _is_relu(nodes[c]):
+                out = c
+            images = None if shapes is None else (1, _rows_of(shapes[p][1], "Conv2D")[1])
+            takers = tuple(c for c in sorted(set(consumers[out]))
+                           if c in packed_at and (shapes is None or _rows_of(shapes[c][0], nodes[c]["kind"]) == images))
+            if takers:
+                plan[p] = dict(folded=None, relu=out if out != p else None, **(dict(pool=None) if pools else {}), add=p, hands_to=takers)
     return plan
 
 
@@ -262,7 +283,7 @@ def _net_tables(net):
     return nodes, outputs
 
 
-def plan_fusion(net, packed_at=None, pools=False):
+def plan_fusion(net, packed_at=None, pools=False, adds=False):
     """The plan of load_packed(..., fuse=True) for a keras_shim network (Sequential, or a functional Model): a list with one dict per
     packed layer on the int8 route, in layer order --
 
@@ -288,7 +309,16 @@ def plan_fusion(net, packed_at=None, pools=False):
     consumer, through Flatten / Dropout layers at most, is a packed layer of the route, and that no packed layer's entry names (none
     stands in front of it, or its activation or rows keep it from linking), is listed too, in layer order at its own position, as
     dict(layer=None, folded=None, relu=None, pool=its name, hands_to=that layer).  With pools=False the dicts are exactly those
-    above, without the key."""
+    above, without the key.
+
+    adds=True (load_packed(..., fuse_add=True)): every dict has one more key, ``add`` (None on the entries
+    above), and rule JOIN lists residual joins.  JOIN applies to an Add with two inbound tensors of equal static shape.  If its output
+    has exactly one consumer, a ReLU or Activation("relu"), and is not a network output, that ReLU is fused and the value at its
+    position is the group's output.  Every direct consumer of the group's output that is a packed layer of the route and whose rows are
+    the group's samples one to one is handed the join's int8 codes; an Add with at least one such consumer is listed in layer order at
+    its own position, as dict(layer=None, folded=None, relu=the ReLU's name or None, [pool=None,] add=its name, hands_to=a tuple of
+    the consumers' names in layer order).  Other consumers -- the next Add, a GlobalAveragePooling2D -- read the float32 sum.  With
+    adds=False the dicts are exactly those above, without the key."""
     net = _shim_network(net)
     if packed_at is None:
         packed_at = [k for k, l in enumerate(net.layers)
@@ -299,13 +329,9 @@ def plan_fusion(net, packed_at=None, pools=False):
     if bad:
         raise ValueError(f"plan_fusion: positions {bad} are not Dense or Conv2D / DepthwiseConv2D layers")
     shapes = [(l.input_shape, l.output_shape) for l in net.layers]
-    plan = _plan(nodes, outputs, packed_at, shapes, pools)
-    name = lambda k: None if k is None else net.layers[k].name
-    if not pools:
-        return [dict(layer=name(k), folded=name(e["folded"]), relu=name(e["relu"]), hands_to=name(e["hands_to"]))
-                for k, e in sorted(plan.items())]
-    return [dict(layer=name(k) if k in packed_at else None, folded=name(e["folded"]), relu=name(e["relu"]), pool=name(e["pool"]),
-                 hands_to=name(e["hands_to"])) for k, e in sorted(plan.items())]
+    plan = _plan(nodes, outputs, packed_at, shapes, pools, adds)
+    name = lambda k: None if k is None else (tuple(name(j) for j in k) if isinstance(k, tuple) else net.layers[k].name)
+    return [dict(layer=name(k) if k in packed_at else None, **{key: name(v) for key, v in e.items()}) for k, e in sorted(plan.items())]
 
 
 def _arch_tables(arch):
@@ -324,12 +350,19 @@ def _arch_tables(arch):
 _FUSED_AWAY = {"BatchNormalization": "FoldedBatchNormalization", "Activation": "FusedActivation", "ReLU": "FusedReLU"}
 
 
-def _apply_fusion(net, packed_at, pools=False):
+def _apply_fusion(net, packed_at, pools=False, adds=False):
     """Sets the fused state of the packed layers of a loaded network from its plan and records the plan as net.fusion_plan.  pools:
-    the plan with its pools -- a named pool is linked, the layer behind it takes its codes, a packed layer in front hands it maxima."""
+    the plan with its pools -- a named pool is linked, the layer behind it takes its codes, a packed layer in front hands it maxima.
+    adds: the plan with its joins -- a named Add is linked and every layer of its hands_to takes its codes."""
     pos = {l.name: k for k, l in enumerate(net.layers)}
-    net.fusion_plan = plan_fusion(net, packed_at, pools) if pools else plan_fusion(net, packed_at)
+    net.fusion_plan = plan_fusion(net, packed_at, **(dict(pools=True) if pools else {}), **(dict(adds=True) if adds else {}))
     for e in net.fusion_plan:
+        if e.get("add") is not None:
+            join = net.layers[pos[e["add"]]]
+            join.linked = True
+            for c in e["hands_to"]:
+                net.layers[pos[c]].codes_from = join
+            continue
         if e.get("pool") is not None:
             pool = net.layers[pos[e["pool"]]]
             pool.linked = True
@@ -354,7 +387,8 @@ def _apply_fusion(net, packed_at, pools=False):
     return net
 
 
-def load_packed(path, device=None, activations="float32", packed_conv=False, fuse=False, packed_depthwise=False, fuse_pool=False):
+def load_packed(path, device=None, activations="float32", packed_conv=False, fuse=False, packed_depthwise=False, fuse_pool=False,
+                fuse_add=False):
     """Inverse of export_packed: a keras_shim network on ``device`` (default: the current GPU).  Dense layers that were exported
     packed come back as keras_shim.PackedDense (codes, radii and bias in device memory; the float kernel is never formed unless
     get_weights() or a batch beyond keras_shim.PACKED_TILED_MAX_BATCH asks for it); packed Conv2D / DepthwiseConv2D kernels are
@@ -386,7 +420,15 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
     is a keras_shim.QuantizingMaxPooling2D: one HIP pass (hip.maxpool2d_forward_i8) pools the float32 images AND leaves their int8
     codes and scales, which the packed layer behind the pool takes in place of running its quantizer; a packed layer in front hands
     the pool its maxima, and behind a fused ReLU, with windows that cover the image, the pool needs nothing else.  The value at every
-    position is bit for bit what fuse_pool=False computes."""
+    position is bit for bit what fuse_pool=False computes.
+
+    fuse_add=True (needs fuse=True): the plan is plan_fusion(..., adds=True).  Every Add it names is a
+    keras_shim.QuantizingAdd: one HIP kernel (hip.add_forward_i8) adds the two float32 tensors, applies the ReLU behind the Add
+    where the plan fuses it (that layer becomes a FusedActivation / FusedReLU) and leaves the images' maxima, and one quantizing pass
+    makes the int8 codes and scales that every packed consumer of the sum takes in place of running its own quantizer.  The value at
+    every position is bit for bit what fuse_add=False computes, the ReLU's value standing at the Add's position too."""
+    if fuse_add and not fuse:
+        raise ValueError("fuse_add=True hands the codes of a residual join to the fused int8 layers behind it: it needs fuse=True")
     if fuse_pool and not fuse:
         raise ValueError("fuse_pool=True hands a pool the maxima of the fused int8 layer before it and its codes to the one behind: it needs fuse=True")
     if activations not in keras_shim.PackedDense.ACTIVATIONS:
@@ -420,7 +462,18 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
                 for e in _plan(nodes, outputs, fused_at, pools=True).values():
                     if e["pool"] is not None:
                         classes[e["pool"]] = keras_shim.QuantizingMaxPooling2D
+            joins = {}
+            if fuse_add:
+                # every join the full plan can name, and its ReLU: fused away here, so applied by the join whether it is linked or not
+                joins = {e["add"]: e["relu"] for e in _plan(nodes, outputs, fused_at, adds=True).values() if e["add"] is not None}
+                for k, r in joins.items():
+                    classes[k] = keras_shim.QuantizingAdd
+                    if r is not None:
+                        classes[r] = getattr(keras_shim, _FUSED_AWAY[arch["layers"][r]["cls"]])
         net = keras_shim._network_from_arch(arch, device, classes)
+        if fuse:
+            for k, r in joins.items():
+                net.layers[k].relu = r is not None
         for k, layer in enumerate(net.layers):
             if k in packed_at:
                 packed = _read_packed(z, k, net.device)
@@ -434,4 +487,4 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
                     layer.set_weights([unpack_kernel(packed)] + rest)
             elif layer._weights:
                 layer.set_weights([z[f"w{k}_{j}"] for j in range(len(layer._weights))])
-    return _apply_fusion(net, fused_at, fuse_pool) if fuse else net
+    return _apply_fusion(net, fused_at, fuse_pool, fuse_add) if fuse else net

@@ -84,6 +84,7 @@ SYMBOLS = {
     "gpfq_packed_depthwise_conv2d_forward_i8": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int,
                                                        _int, _vp, _int, _int, _vp, _int, _vp, _vp, _int, _vp, _vp]),
     "gpfq_maxpool2d_forward_i8": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "gpfq_add_forward_i8": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp]),
     "gpfq_candidate_kernels": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dp, _int, _vp, _vp, _i64, _i64, _i64, _vp]),
     "gpfq_select_candidates_workspace_bytes": (_sz, [_int, _i64]),
     "gpfq_select_candidates": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _dp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
@@ -1694,4 +1695,30 @@ def maxpool2d_forward_i8(x, pool_size, strides, padding, amax=None):
     with torch.cuda.device(x.device):
         _check(entry(x.data_ptr(), *geometry, y.data_ptr(), ap, xq.data_ptr(), ldq, scales.data_ptr(), None, _stream()),
                "gpfq_maxpool2d_forward_i8")
+    return y, xq, scales
+
+
+def add_forward_i8(a, b, relu=False):
+    """The residual join a + b of two float32 tensors [n][...] of one shape, with the ReLU behind it where `relu`, together with the
+    int8 codes of the sum's images (gpfq_add_forward_i8; the contract is include/gpfq.h's, bit for bit) -> (y f32 of a's shape,
+    xq i8 [n][roundup16(L)], scales f32 [n]) with L the floats of one sample: xq and scales are quantize_rows_i8's of the flattened
+    images of y, made once for every packed layer that consumes y.  Three stream operations: a clear of n cells, the join kernel (which
+    leaves the images' maxima), the from-amax quantizer.  No sync."""
+    _dev(a, torch.float32, "a"); _dev(b, torch.float32, "b")
+    if relu not in (False, True, 0, 1):
+        raise GpfqError(f"relu must be a bool, got {relu!r}")
+    if a.dim() < 1 or a.shape != b.shape or a.device != b.device or not a.is_contiguous() or not b.is_contiguous():
+        raise GpfqError(f"a and b must be contiguous tensors of one shape [n][...] on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    n = int(a.shape[0])
+    L = a.shape[1:].numel()
+    y = torch.empty_like(a)
+    if n == 0 or L == 0:                            # (nothing to add: the quantizer's own rules for empty rows)
+        return (y,) + tuple(quantize_rows_i8(y.reshape(n, L)))
+    ldq = (L + 15) // 16 * 16
+    xq = torch.empty((n, ldq), dtype=torch.int8, device=a.device)
+    scales = torch.empty(n, dtype=torch.float32, device=a.device)
+    cells = torch.empty(n, dtype=torch.int32, device=a.device)
+    with torch.cuda.device(a.device):
+        _check(load().gpfq_add_forward_i8(a.data_ptr(), b.data_ptr(), n, L, int(bool(relu)), y.data_ptr(), cells.data_ptr(), xq.data_ptr(),
+                                          ldq, scales.data_ptr(), _stream()), "gpfq_add_forward_i8")
     return y, xq, scales

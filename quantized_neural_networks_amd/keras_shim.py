@@ -178,6 +178,36 @@ class Add(Layer):
         return y
 
 
+class QuantizingAdd(Add):
+    """A residual join in front of packed layers of the int8 route (deploy.load_packed(..., fuse=True, fuse_add=True); DESIGN.md
+    section 11f): where the plan names it (``linked``) and it is given exactly two float32 tensors of one shape on one GPU, its call is
+    hip.add_forward_i8 -- the sum, with the ReLU behind it where ``relu`` (that layer is then a FusedActivation / FusedReLU, and the
+    value at its position this one's), and with it the int8 codes and scales that every packed consumer's quantizer would make, which
+    the consumers take (_FusedI8._taken_codes) in place of quantizing.  Anything else is Add.call, followed by torch.relu where
+    ``relu``.  config(), clone() and save_model() give the Add."""
+
+    def __init__(self, name=None):
+        super().__init__(name)
+        self.linked = False
+        self.relu = False
+        self._codes = None                            # (weak reference to the output, its version, xq, scales, floats per image)
+
+    def clone(self):
+        c = Add(**self.config())
+        c.name = self.name
+        return c
+
+    def call(self, xs):
+        if (self.linked and len(xs) == 2 and all(isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_cuda for x in xs)
+                and xs[0].shape == xs[1].shape and xs[0].device == xs[1].device and xs[0].dim() >= 1):
+            from . import hip
+            y, xq, scales = hip.add_forward_i8(xs[0].contiguous(), xs[1].contiguous(), relu=self.relu)
+            self._codes = (weakref.ref(y), y._version, xq, scales, y[0].numel() if y.shape[0] else 0)
+            return y
+        y = Add.call(self, xs)
+        return torch.relu(y) if self.relu else y
+
+
 class GlobalAveragePooling2D(Layer):
     def compute_output_shape(self, s):
         return (s[0], s[3])
@@ -255,7 +285,7 @@ class _FusedI8:
         self.fused = None
         self.emit_amax = False
         self.amax_from = None
-        self.codes_from = None                        # (the QuantizingMaxPooling2D in front: load_packed(..., fuse_pool=True))
+        self.codes_from = None                        # (the QuantizingMaxPooling2D / QuantizingAdd in front: fuse_pool / fuse_add)
         self._handoff = None                          # (weak reference to the output, its version, maxima i32 [rows], floats per row)
 
     def _fused_parts(self, bias):
@@ -284,8 +314,8 @@ class _FusedI8:
         return amax
 
     def _taken_codes(self, x, rows, row_len):
-        """(xq, scales) of the rows of x as the QuantizingMaxPooling2D in front left them, or None (quantize here): ``_taken_maxima``'s
-        proof against the pool's remembered output.  Flatten's reshape is a view -- the same storage, offset, element count and
+        """(xq, scales) of the rows of x as the QuantizingMaxPooling2D or QuantizingAdd in front left them, or None (quantize here):
+        ``_taken_maxima``'s proof against that layer's remembered output.  Flatten's reshape is a view -- the same storage, offset, element count and
         version counter -- so the proof holds through it."""
         hand = getattr(self.codes_from, "_codes", None) if self.codes_from is not None else None
         if hand is None:
@@ -1201,6 +1231,8 @@ def _arch_arrays(model):
             cls = l._plain.__name__
         if isinstance(l, QuantizingMaxPooling2D):
             cls = "MaxPooling2D"
+        if isinstance(l, QuantizingAdd):
+            cls = "Add"
         spec = dict(cls=cls, name=l.name, config=l.config())
         if functional:
             inbound = l.inbound_nodes[0].inbound_layers
