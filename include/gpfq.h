@@ -698,6 +698,48 @@ int gpfq_add_forward_i8(const float *a, const float *b, int64_t n, int64_t L, in
                         int64_t ldq, float *scales, void *stream);
 
 /*
+ * Average pooling on the same route: the means as float32 images and what the packed layer behind the pool
+ * needs of them -- their int8 codes and scales.  Opt-in; bit for bit:
+ *
+ * A mean is a float64 sum of the float32 taps in the order stated below -- every sum starts as +0.0 and takes its taps one by one,
+ * each converted to float64 (exactly) and added with one float64 add -- then ONE float64 division by the number of taps and ONE
+ * rounding of the quotient to float32 (to nearest, ties to even).  A NaN or an Inf among the taps propagates by the IEEE rules
+ * (which NaN payload is not stated); nothing is clamped.  A mean of zeros of either sign is +0.0f.
+ *
+ * gpfq_global_avgpool_forward_i8 (GlobalAveragePooling2D):
+ *   x [device] f32 [n][H][W][C], contiguous; y [device] f32 [n][C], contiguous.  With P = H * W and the positions p = h * W + w,
+ *   channel c of image i has FOUR partial sums: S_w, w = 0 .. 3, is the sum over p = w, w + 4, w + 8, .. < P, ascending, of
+ *   x[i][p][c] (S_w = +0.0 where P <= w), and
+ *       y[i][c] = (float)((((S_0 + S_1) + S_2) + S_3) / (double)P).
+ * gpfq_avgpool2d_forward_i8 (AveragePooling2D):
+ *   x as above; y [device] f32 [n][OH][OW][C], contiguous.  The geometry is gpfq_maxpool2d_forward_i8's (TensorFlow's, rate 1).  The
+ *   taps x[i][oh * sh + ky - pad_top][ow * sw + kx - pad_left][c] are visited with ky ascending, then kx ascending, into ONE sum; a
+ *   tap outside the image takes no part, and the divisor is the number of taps inside the image -- below ph * pw in a border window
+ *   under SAME, what TensorFlow's AveragePooling2D divides by.
+ * Both:
+ *   amax_bits ([device] u32 [n]) is cleared asynchronously on `stream` and on completion amax_bits[i] = max over image i of
+ *   (bits(y) & 0x7fffffff), the cell the fused forward passes above leave: an Inf or a NaN puts it at or above 0x7f800000.  The
+ *   maximum is taken inside a workgroup first, which then issues at most one agent-scope unsigned-max atomic without a return value
+ *   per image it stored into, and none for a maximum of 0.
+ *   With L the floats of one image of y (C, or OH*OW*C): xq ([device] i8, image i at xq + i * ldq), its pad bytes up to roundup16(L)
+ *   and scales ([device] f32 [n]) are exactly what gpfq_quantize_rows_i8(y, n, L, L, xq, ldq, scales) would leave; ldq, alignment and
+ *   pad rules are that entry's.
+ *   Every call gives the same bits; image i of y, amax_bits, xq and scales depends on image i of x alone, not on n.  Whether C is a
+ *   multiple of 4 (and x and y 16-byte aligned) decides how the kernel reads and stores (16 bytes, or element by element), never
+ *   what it computes.
+ *   Three operations on `stream`, ordered by the stream alone: the clear, the pool, the from-amax quantizer on y.
+ * GPFQ_ERR_INVALID_ARG, before any launch: H, W, C (and ph, pw, sh, sw) not positive; n negative; a NULL x, y, amax_bits, xq or
+ * scales; ldq not a multiple of 16 or below L; xq not 16-byte aligned.  GPFQ_ERR_UNSUPPORTED: H*W*C at or beyond 2^31; n at or
+ * beyond 2^31; ph*pw > GPFQ_POOL_MAX_TAPS; n*OH*OW*C at or beyond 2^31.  n = 0 or an empty output (OH or OW = 0) returns GPFQ_OK
+ * without a launch: nothing is written or cleared.  Asynchronous on `stream`, no workgroup waiting for another, without workspace,
+ * scratch or host synchronisation; the call can be captured into a graph.  The outputs must not overlap each other or x.
+ */
+int gpfq_global_avgpool_forward_i8(const float *x, int64_t n, int64_t H, int64_t W, int64_t C, float *y, uint32_t *amax_bits, int8_t *xq,
+                                   int64_t ldq, float *scales, void *stream);
+int gpfq_avgpool2d_forward_i8(const float *x, int64_t n, int64_t H, int64_t W, int64_t C, int ph, int pw, int sh, int sw, int same_padding,
+                              float *y, uint32_t *amax_bits, int8_t *xq, int64_t ldq, float *scales, void *stream);
+
+/*
  * Search over the alphabet scalar (a sequence as alphabet_scalar).  K candidate scalars s_0 .. s_{K-1}
  * (1 <= K <= GPFQ_SEARCH_MAX_CANDIDATES, each a finite positive number) are K * C independent columns of one walk with the unit
  * alphabet: candidate k of output channel j is column k * C + j (k-major: candidate k is a contiguous block of C columns).

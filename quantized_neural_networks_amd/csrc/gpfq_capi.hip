@@ -1172,6 +1172,50 @@ int gpfq_add_forward_i8(const float *a, const float *b, int64_t n, int64_t L, in
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_add_forward_i8");
 }
 
+// both average pools on the int8 route: what they check alike, L the floats of one pooled image; every check before any launch
+static int avgpool_i8_args(int64_t n, int64_t H, int64_t W, int64_t C, const float *x, const float *y, const uint32_t *amax_bits,
+                           const int8_t *xq, int64_t ldq, const float *scales)
+{
+    if (n < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size n=%lld", (long long)n);
+    if (H <= 0 || W <= 0 || C <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad image shape H=%lld W=%lld C=%lld", (long long)H, (long long)W, (long long)C);
+    if (!x || !y || !amax_bits || !xq || !scales) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (ldq % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld must be a multiple of 16", (long long)ldq);
+    if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
+    const int64_t lim = 2147483647LL;               // (each product below its own bound first: no overflow)
+    if (H > lim / W || H * W > lim / C) return fail(GPFQ_ERR_UNSUPPORTED, "H*W*C at or beyond 2^31: too large for one launch");
+    if (n > lim) return fail(GPFQ_ERR_UNSUPPORTED, "batch too long for one launch");
+    return GPFQ_OK;
+}
+
+int gpfq_global_avgpool_forward_i8(const float *x, int64_t n, int64_t H, int64_t W, int64_t C, float *y, uint32_t *amax_bits, int8_t *xq,
+                                   int64_t ldq, float *scales, void *stream)
+{
+    int rc = avgpool_i8_args(n, H, W, C, x, y, amax_bits, xq, ldq, scales);
+    if (rc != GPFQ_OK) return rc;
+    if (ldq < C) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld < C=%lld", (long long)ldq, (long long)C);
+    if (n == 0) return GPFQ_OK;
+    hipError_t e = gpfq::launch_global_avgpool_forward_i8(x, n, H * W, C, y, amax_bits, xq, ldq, scales, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_global_avgpool_forward_i8");
+}
+
+int gpfq_avgpool2d_forward_i8(const float *x, int64_t n, int64_t H, int64_t W, int64_t C, int ph, int pw, int sh, int sw, int same_padding,
+                              float *y, uint32_t *amax_bits, int8_t *xq, int64_t ldq, float *scales, void *stream)
+{
+    int rc = avgpool_i8_args(n, H, W, C, x, y, amax_bits, xq, ldq, scales);
+    if (rc != GPFQ_OK) return rc;
+    if (ph <= 0 || pw <= 0 || sh <= 0 || sw <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad window/stride %dx%d / %dx%d", ph, pw, sh, sw);
+    if ((int64_t)ph * pw > GPFQ_POOL_MAX_TAPS)
+        return fail(GPFQ_ERR_UNSUPPORTED, "ph*pw=%d*%d > GPFQ_POOL_MAX_TAPS=%d", ph, pw, GPFQ_POOL_MAX_TAPS);
+    const int64_t oh = gpfq_patch_out_dim(H, ph, sh, 1, same_padding), ow = gpfq_patch_out_dim(W, pw, sw, 1, same_padding);
+    const int64_t L = oh * ow * C;                  // (oh <= H and ow <= W: below 2^31)
+    if (ldq < L) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld < OH*OW*C=%lld", (long long)ldq, (long long)L);
+    if (n == 0 || L == 0) return GPFQ_OK;
+    if (L > 2147483647LL / n) return fail(GPFQ_ERR_UNSUPPORTED, "n*OH*OW*C at or beyond 2^31: too large for one launch");
+    const gpfq::ConvI8Shape S = conv_i8_shape(H, W, C, ph, pw, sh, sw, 1, 1, same_padding, oh, ow);
+    hipError_t e = gpfq::launch_avgpool2d_forward_i8(x, n, S, y, amax_bits, xq, ldq, scales, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GPFQ_OK : hip_fail(e, "gpfq_avgpool2d_forward_i8");
+}
+
 int gpfq_candidate_kernels(const float *W, int64_t R, int64_t C, int64_t ld, const double *base_radii, const float *layer_median,
                            const double *scalars, int K, double *radii, float *W_cand, int64_t ldo, int64_t c_lo, int64_t c_hi,
                            void *stream)

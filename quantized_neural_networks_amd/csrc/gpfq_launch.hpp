@@ -395,6 +395,13 @@ hipError_t launch_maxpool2d_forward_i8(const float *x, int64_t n, const ConvI8Sh
 // cleared amax_bits, then launch_quantize_rows_i8_from_amax on y: three stream operations.  The entry has checked the sizes.
 hipError_t launch_add_forward_i8(const float *a, const float *b, int64_t n, int64_t L, int relu, float *y, uint32_t *amax_bits, int8_t *xq,
                                  int64_t ldq, float *scales, hipStream_t stream);
+// gpfq_avgpool_i8.hip: the means of [n][P][C] over P, or of the windows of S (kh x kw the window, Cin the
+// channels, rh = rw = 1), the images' maxima into the cleared amax_bits, then launch_quantize_rows_i8_from_amax on y: three stream
+// operations.  The entries have checked P * C < 2^31 and n * OH * OW * Cin < 2^31.
+hipError_t launch_global_avgpool_forward_i8(const float *x, int64_t n, int64_t P, int64_t C, float *y, uint32_t *amax_bits, int8_t *xq,
+                                            int64_t ldq, float *scales, hipStream_t stream);
+hipError_t launch_avgpool2d_forward_i8(const float *x, int64_t n, const ConvI8Shape &S, float *y, uint32_t *amax_bits, int8_t *xq,
+                                       int64_t ldq, float *scales, hipStream_t stream);
 // gpfq_search.hip (a sequence as alphabet_scalar): the K candidate scalars travel by value
 constexpr int kSearchMaxK = 16;
 struct SearchScalars {

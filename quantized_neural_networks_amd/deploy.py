@@ -183,7 +183,7 @@ def _is_relu(node):
     return node["kind"] == "ReLU" or (node["kind"] == "Activation" and node["activation"] == "relu")
 
 
-def _plan(nodes, outputs, packed_at, shapes=None, pools=False, adds=False):
+def _plan(nodes, outputs, packed_at, shapes=None, pools=False, adds=False, avgpools=False):
     """The fusion plan of a network given as tables (host only).  nodes: per position dict(kind, activation, inbound positions);
     outputs: the positions of the network's outputs; packed_at: the positions of the packed layers on the int8 route; shapes: per
     position (input shape, output shape), or None -- no links are made then.  Returns per packed position
@@ -193,7 +193,11 @@ def _plan(nodes, outputs, packed_at, shapes=None, pools=False, adds=False):
     under its own position -- without shapes (the row matches cannot be made) that is every pool whose consumers lead to one.
     adds: every entry has the key ``add`` (None), before hands_to, and an Add of two inbound tensors with a packed consumer has an
     entry of its own under its own position, dict(folded=None, relu, [pool=None,] add, hands_to=a tuple of positions) -- without
-    shapes (the inbound shapes and the row matches cannot be compared) that is every such Add with a packed direct consumer."""
+    shapes (the inbound shapes and the row matches cannot be compared) that is every such Add with a packed direct consumer.
+    avgpools: every entry has the key ``avgpool`` (None), before hands_to, and a GlobalAveragePooling2D or AveragePooling2D whose
+    output reaches a packed layer has an entry of its own under its own position, dict(folded=None, relu=None, [pool=None,]
+    [add=None,] avgpool, hands_to) -- without shapes (the row match cannot be made) that is every such pool."""
+    blank = dict(**(dict(pool=None) if pools else {}), **(dict(add=None) if adds else {}), **(dict(avgpool=None) if avgpools else {}))
     consumers = [[] for _ in nodes]
     for k, node in enumerate(nodes):
         for p in node["inbound"]:
@@ -227,7 +231,7 @@ def _plan(nodes, outputs, packed_at, shapes=None, pools=False, adds=False):
     for k in packed_at:
         act = nodes[k]["activation"]
         linear, own_relu = act in (None, "linear"), act == "relu"
-        entry = dict(folded=None, relu=None, **(dict(pool=None) if pools else {}), **(dict(add=None) if adds else {}), hands_to=None)
+        entry = dict(folded=None, relu=None, **blank, hands_to=None)
         out = k
         if linear:
             c = sole(out)
@@ -253,7 +257,7 @@ def _plan(nodes, outputs, packed_at, shapes=None, pools=False, adds=False):
             if node["kind"] == "MaxPooling2D" and p not in named:
                 c, _ = reach(p, False)
                 if c is not None and feeds(p, c):
-                    plan[p] = dict(folded=None, relu=None, pool=p, **(dict(add=None) if adds else {}), hands_to=c)
+                    plan[p] = dict(folded=None, relu=None, **dict(blank, pool=p), hands_to=c)
     if adds:                                        # rule JOIN
         for p, node in enumerate(nodes):
             if node["kind"] != "Add" or len(node["inbound"]) != 2:
@@ -267,7 +271,13 @@ def _plan(nodes, outputs, packed_at, shapes=None, pools=False, adds=False):
             takers = tuple(c for c in sorted(set(consumers[out]))
                            if c in packed_at and (shapes is None or _rows_of(shapes[c][0], nodes[c]["kind"]) == images))
             if takers:
-                plan[p] = dict(folded=None, relu=out if out != p else None, **(dict(pool=None) if pools else {}), add=p, hands_to=takers)
+                plan[p] = dict(folded=None, relu=out if out != p else None, **dict(blank, add=p), hands_to=takers)
+    if avgpools:                                    # rule AVG
+        for p, node in enumerate(nodes):
+            if node["kind"] in ("GlobalAveragePooling2D", "AveragePooling2D"):
+                c, _ = reach(p, False)
+                if c is not None and feeds(p, c):   # (the means of a sample are one row of a Dense layer, or one image of a conv layer)
+                    plan[p] = dict(folded=None, relu=None, **dict(blank, avgpool=p), hands_to=c)
     return plan
 
 
@@ -283,7 +293,7 @@ def _net_tables(net):
     return nodes, outputs
 
 
-def plan_fusion(net, packed_at=None, pools=False, adds=False):
+def plan_fusion(net, packed_at=None, pools=False, adds=False, avgpools=False):
     """The plan of load_packed(..., fuse=True) for a keras_shim network (Sequential, or a functional Model): a list with one dict per
     packed layer on the int8 route, in layer order --
 
@@ -318,7 +328,15 @@ def plan_fusion(net, packed_at=None, pools=False, adds=False):
     the group's samples one to one is handed the join's int8 codes; an Add with at least one such consumer is listed in layer order at
     its own position, as dict(layer=None, folded=None, relu=the ReLU's name or None, [pool=None,] add=its name, hands_to=a tuple of
     the consumers' names in layer order).  Other consumers -- the next Add, a GlobalAveragePooling2D -- read the float32 sum.  With
-    adds=False the dicts are exactly those above, without the key."""
+    adds=False the dicts are exactly those above, without the key.
+
+    avgpools=True (load_packed(..., fuse_avgpool=True)): every dict has one more key, ``avgpool`` (None on the
+    entries above), before hands_to, and rule AVG, after JOIN, lists average pools.  AVG applies to a GlobalAveragePooling2D or
+    AveragePooling2D whose output is not a network output and reaches, through single-consumer Flatten / Dropout layers at most, a
+    packed layer of the route whose rows are the pooled samples one to one (a Dense layer behind a global pool; for a windowed pool
+    the match pools=True makes).  Such a pool is listed in layer order at its own position, as dict(layer=None, folded=None,
+    relu=None, [pool=None,] [add=None,] avgpool=its name, hands_to=that layer).  With avgpools=False the dicts are exactly those
+    above, without the key."""
     net = _shim_network(net)
     if packed_at is None:
         packed_at = [k for k, l in enumerate(net.layers)
@@ -329,7 +347,7 @@ def plan_fusion(net, packed_at=None, pools=False, adds=False):
     if bad:
         raise ValueError(f"plan_fusion: positions {bad} are not Dense or Conv2D / DepthwiseConv2D layers")
     shapes = [(l.input_shape, l.output_shape) for l in net.layers]
-    plan = _plan(nodes, outputs, packed_at, shapes, pools, adds)
+    plan = _plan(nodes, outputs, packed_at, shapes, pools, adds, avgpools)
     name = lambda k: None if k is None else (tuple(name(j) for j in k) if isinstance(k, tuple) else net.layers[k].name)
     return [dict(layer=name(k) if k in packed_at else None, **{key: name(v) for key, v in e.items()}) for k, e in sorted(plan.items())]
 
@@ -350,13 +368,20 @@ def _arch_tables(arch):
 _FUSED_AWAY = {"BatchNormalization": "FoldedBatchNormalization", "Activation": "FusedActivation", "ReLU": "FusedReLU"}
 
 
-def _apply_fusion(net, packed_at, pools=False, adds=False):
+def _apply_fusion(net, packed_at, pools=False, adds=False, avgpools=False):
     """Sets the fused state of the packed layers of a loaded network from its plan and records the plan as net.fusion_plan.  pools:
     the plan with its pools -- a named pool is linked, the layer behind it takes its codes, a packed layer in front hands it maxima.
-    adds: the plan with its joins -- a named Add is linked and every layer of its hands_to takes its codes."""
+    adds: the plan with its joins -- a named Add is linked and every layer of its hands_to takes its codes.
+    avgpools: the plan with its average pools -- a named one is linked and the layer behind it takes its codes."""
     pos = {l.name: k for k, l in enumerate(net.layers)}
-    net.fusion_plan = plan_fusion(net, packed_at, **(dict(pools=True) if pools else {}), **(dict(adds=True) if adds else {}))
+    net.fusion_plan = plan_fusion(net, packed_at, **(dict(pools=True) if pools else {}), **(dict(adds=True) if adds else {}),
+                                  **(dict(avgpools=True) if avgpools else {}))
     for e in net.fusion_plan:
+        if e.get("avgpool") is not None:
+            pool = net.layers[pos[e["avgpool"]]]
+            pool.linked = True
+            net.layers[pos[e["hands_to"]]].codes_from = pool
+            continue
         if e.get("add") is not None:
             join = net.layers[pos[e["add"]]]
             join.linked = True
@@ -388,7 +413,7 @@ def _apply_fusion(net, packed_at, pools=False, adds=False):
 
 
 def load_packed(path, device=None, activations="float32", packed_conv=False, fuse=False, packed_depthwise=False, fuse_pool=False,
-                fuse_add=False):
+                fuse_add=False, fuse_avgpool=False):
     """Inverse of export_packed: a keras_shim network on ``device`` (default: the current GPU).  Dense layers that were exported
     packed come back as keras_shim.PackedDense (codes, radii and bias in device memory; the float kernel is never formed unless
     get_weights() or a batch beyond keras_shim.PACKED_TILED_MAX_BATCH asks for it); packed Conv2D / DepthwiseConv2D kernels are
@@ -426,7 +451,16 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
     keras_shim.QuantizingAdd: one HIP kernel (hip.add_forward_i8) adds the two float32 tensors, applies the ReLU behind the Add
     where the plan fuses it (that layer becomes a FusedActivation / FusedReLU) and leaves the images' maxima, and one quantizing pass
     makes the int8 codes and scales that every packed consumer of the sum takes in place of running its own quantizer.  The value at
-    every position is bit for bit what fuse_add=False computes, the ReLU's value standing at the Add's position too."""
+    every position is bit for bit what fuse_add=False computes, the ReLU's value standing at the Add's position too.
+
+    fuse_avgpool=True (needs fuse=True): the plan is plan_fusion(..., avgpools=True).  Every
+    GlobalAveragePooling2D / AveragePooling2D it names is a keras_shim.QuantizingGlobalAveragePooling2D / QuantizingAveragePooling2D:
+    one HIP kernel (hip.global_avgpool_forward_i8 / hip.avgpool2d_forward_i8) forms the means and leaves their maxima, and one
+    quantizing pass makes the int8 codes and scales that the packed layer behind the pool takes in place of running its own
+    quantizer.  The means are include/gpfq.h's -- a float64 sum in a stated order, one division, one rounding -- where
+    fuse_avgpool=False has torch's float32 reduction: the two differ by float32 roundings of the means, and by nothing else."""
+    if fuse_avgpool and not fuse:
+        raise ValueError("fuse_avgpool=True hands the codes of an average pool to the fused int8 layer behind it: it needs fuse=True")
     if fuse_add and not fuse:
         raise ValueError("fuse_add=True hands the codes of a residual join to the fused int8 layers behind it: it needs fuse=True")
     if fuse_pool and not fuse:
@@ -470,6 +504,11 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
                     classes[k] = keras_shim.QuantizingAdd
                     if r is not None:
                         classes[r] = getattr(keras_shim, _FUSED_AWAY[arch["layers"][r]["cls"]])
+            if fuse_avgpool:
+                # every average pool the full plan can name (the row matches need the network's shapes: _apply_fusion links those that pass)
+                for e in _plan(nodes, outputs, fused_at, avgpools=True).values():
+                    if e["avgpool"] is not None:
+                        classes[e["avgpool"]] = getattr(keras_shim, "Quantizing" + arch["layers"][e["avgpool"]]["cls"])
         net = keras_shim._network_from_arch(arch, device, classes)
         if fuse:
             for k, r in joins.items():
@@ -487,4 +526,4 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
                     layer.set_weights([unpack_kernel(packed)] + rest)
             elif layer._weights:
                 layer.set_weights([z[f"w{k}_{j}"] for j in range(len(layer._weights))])
-    return _apply_fusion(net, fused_at, fuse_pool, fuse_add) if fuse else net
+    return _apply_fusion(net, fused_at, fuse_pool, fuse_add, fuse_avgpool) if fuse else net

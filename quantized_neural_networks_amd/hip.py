@@ -85,6 +85,8 @@ SYMBOLS = {
                                                        _int, _vp, _int, _int, _vp, _int, _vp, _vp, _int, _vp, _vp]),
     "gpfq_maxpool2d_forward_i8": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "gpfq_add_forward_i8": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "gpfq_global_avgpool_forward_i8": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "gpfq_avgpool2d_forward_i8": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp]),
     "gpfq_candidate_kernels": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dp, _int, _vp, _vp, _i64, _i64, _i64, _vp]),
     "gpfq_select_candidates_workspace_bytes": (_sz, [_int, _i64]),
     "gpfq_select_candidates": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _dp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
@@ -1722,3 +1724,52 @@ def add_forward_i8(a, b, relu=False):
         _check(load().gpfq_add_forward_i8(a.data_ptr(), b.data_ptr(), n, L, int(bool(relu)), y.data_ptr(), cells.data_ptr(), xq.data_ptr(),
                                           ldq, scales.data_ptr(), _stream()), "gpfq_add_forward_i8")
     return y, xq, scales
+
+
+def _avgpool_i8(name, x, geometry, out_shape):
+    """What both average pools of the int8 route share: the outputs, the call, the empty cases."""
+    y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    n, L = int(x.shape[0]), y.shape[1:].numel()
+    if n == 0 or L == 0:                            # (nothing to pool: the quantizer's own rules for empty rows)
+        return (y,) + tuple(quantize_rows_i8(y.reshape(n, L)))
+    ldq = (L + 15) // 16 * 16
+    xq = torch.empty((n, ldq), dtype=torch.int8, device=x.device)
+    scales = torch.empty(n, dtype=torch.float32, device=x.device)
+    cells = torch.empty(n, dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(getattr(load(), name)(x.data_ptr(), *geometry, y.data_ptr(), cells.data_ptr(), xq.data_ptr(), ldq, scales.data_ptr(),
+                                     _stream()), name)
+    return y, xq, scales
+
+
+def _nhwc(x):
+    _dev(x, torch.float32, "x")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise GpfqError(f"x must be a contiguous NHWC tensor [n][H][W][C], got {tuple(x.shape)}")
+    n, H, W, C = (int(v) for v in x.shape)
+    if min(H, W, C) <= 0:
+        raise GpfqError("image sides and channels must be positive")
+    return n, H, W, C
+
+
+def global_avgpool_forward_i8(x):
+    """GlobalAveragePooling2D of float32 NHWC images x [n][H][W][C] together with the int8 codes of the means
+    (gpfq_global_avgpool_forward_i8; the contract is include/gpfq.h's, bit for bit: a float64 sum in a stated order, one division, one
+    rounding) -> (y f32 [n][C], xq i8 [n][roundup16(C)], scales f32 [n]): xq and scales are quantize_rows_i8's of y.  Three stream
+    operations: a clear of n cells, the pool (which leaves the rows' maxima), the from-amax quantizer.  No sync."""
+    n, H, W, C = _nhwc(x)
+    return _avgpool_i8("gpfq_global_avgpool_forward_i8", x, (n, H, W, C), (n, C))
+
+
+def avgpool2d_forward_i8(x, pool_size, strides, padding):
+    """AveragePooling2D of float32 NHWC images x [n][H][W][C] together with the int8 codes of the pooled images
+    (gpfq_avgpool2d_forward_i8; the contract is include/gpfq.h's, bit for bit; TensorFlow's geometry, under "same" the divisor of a
+    border window is the number of its taps inside the image; ph * pw <= GPFQ_POOL_MAX_TAPS) -> (y f32 [n][OH][OW][C],
+    xq i8 [n][roundup16(OH*OW*C)], scales f32 [n]): xq and scales are quantize_rows_i8's of the flattened images of y.  Three stream
+    operations, as global_avgpool_forward_i8.  No sync."""
+    n, H, W, C = _nhwc(x)
+    ph, pw, sh, sw, _, _, same = conv_geometry(pool_size, strides, (1, 1), padding)
+    if min(ph, pw, sh, sw) <= 0:
+        raise GpfqError("window sides and strides must be positive")
+    OH, OW = patch_out_dim(H, ph, sh, 1, same), patch_out_dim(W, pw, sw, 1, same)
+    return _avgpool_i8("gpfq_avgpool2d_forward_i8", x, (n, H, W, C, ph, pw, sh, sw, 1 if same else 0), (n, OH, OW, C))

@@ -216,6 +216,43 @@ class GlobalAveragePooling2D(Layer):
         return x.mean(dim=(1, 2))
 
 
+def _pooled_on_the_route(layer, x):
+    """A quantizing average pool's call on the int8 route: the plan named it and x is a float32 NHWC batch on a GPU."""
+    return layer.linked and isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_cuda and x.dim() == 4
+
+
+def _codes_of(y, xq, scales):
+    """What a layer that quantized its own output y remembers for the consumer's proof (_FusedI8._taken_codes)."""
+    return (weakref.ref(y), y._version, xq, scales, y[0].numel() if y.shape[0] else 0)
+
+
+class QuantizingGlobalAveragePooling2D(GlobalAveragePooling2D):
+    """A GlobalAveragePooling2D in front of a packed layer of the int8 route (deploy.load_packed(..., fuse=True, fuse_avgpool=True);
+    DESIGN.md section 11g): where the plan names it (``linked``) and it is given a float32 NHWC batch on a GPU, its call is
+    hip.global_avgpool_forward_i8 -- the means by include/gpfq.h's stated float64 sum (torch's x.mean differs from it by float32
+    roundings), and with them the int8 codes and scales the consumer's quantizer would make of them, which the consumer takes
+    (_FusedI8._taken_codes) in place of quantizing.  Anything else is GlobalAveragePooling2D.call.  config(), clone() and
+    save_model() give the GlobalAveragePooling2D."""
+
+    def __init__(self, name=None):
+        super().__init__(name)
+        self.linked = False
+        self._codes = None                            # (weak reference to the output, its version, xq, scales, floats per row)
+
+    def clone(self):
+        c = GlobalAveragePooling2D(**self.config())
+        c.name = self.name
+        return c
+
+    def call(self, x):
+        if not _pooled_on_the_route(self, x):
+            return GlobalAveragePooling2D.call(self, x)
+        from . import hip
+        y, xq, scales = hip.global_avgpool_forward_i8(x.contiguous())
+        self._codes = _codes_of(y, xq, scales)
+        return y
+
+
 class Dense(Layer):
     def __init__(self, units, activation=None, use_bias=True, input_shape=None, name=None):
         super().__init__(name)
@@ -285,7 +322,7 @@ class _FusedI8:
         self.fused = None
         self.emit_amax = False
         self.amax_from = None
-        self.codes_from = None                        # (the QuantizingMaxPooling2D / QuantizingAdd in front: fuse_pool / fuse_add)
+        self.codes_from = None                        # (the Quantizing pool or Add in front: fuse_pool / fuse_add / fuse_avgpool)
         self._handoff = None                          # (weak reference to the output, its version, maxima i32 [rows], floats per row)
 
     def _fused_parts(self, bias):
@@ -800,6 +837,29 @@ class AveragePooling2D(_Pool2D):
         return F.avg_pool2d(x.permute(0, 3, 1, 2), self.pool_size, self.strides).permute(0, 2, 3, 1).contiguous()
 
 
+class QuantizingAveragePooling2D(AveragePooling2D):
+    """An AveragePooling2D in front of a packed layer of the int8 route: QuantizingGlobalAveragePooling2D's rules with
+    hip.avgpool2d_forward_i8.  padding="same" stays refused, as by AveragePooling2D (the binding serves it; the shim does not)."""
+
+    def __init__(self, pool_size=(2, 2), strides=None, padding="valid", name=None):
+        super().__init__(pool_size, strides, padding, name)
+        self.linked = False
+        self._codes = None                            # (weak reference to the output, its version, xq, scales, floats per image)
+
+    def clone(self):
+        c = AveragePooling2D(**self.config())
+        c.name = self.name
+        return c
+
+    def call(self, x):
+        if self.padding.lower() == "same" or not _pooled_on_the_route(self, x):
+            return AveragePooling2D.call(self, x)
+        from . import hip
+        y, xq, scales = hip.avgpool2d_forward_i8(x.contiguous(), self.pool_size, self.strides, self.padding)
+        self._codes = _codes_of(y, xq, scales)
+        return y
+
+
 class ZeroPadding2D(Layer):
     def __init__(self, padding=(1, 1), name=None):
         super().__init__(name)
@@ -1233,6 +1293,8 @@ def _arch_arrays(model):
             cls = "MaxPooling2D"
         if isinstance(l, QuantizingAdd):
             cls = "Add"
+        if isinstance(l, (QuantizingGlobalAveragePooling2D, QuantizingAveragePooling2D)):
+            cls = type(l).__name__[len("Quantizing"):]
         spec = dict(cls=cls, name=l.name, config=l.config())
         if functional:
             inbound = l.inbound_nodes[0].inbound_layers
