@@ -593,6 +593,32 @@ int gpfq_quantize_rows_i8_from_amax(const float *x, int64_t B, int64_t ldx, int6
                                     float *scales, void *stream);
 
 /*
+ * gpfq_packed_conv2d_forward_i8_residual: the fused Conv2D pass with the shortcut of a residual join added in the kernel's epilogue
+ * (DESIGN.md section 11h).  Opt-in; bit for bit.  The arguments of gpfq_packed_conv2d_forward_i8_fused with `res` in front of relu.
+ *   res      [device] f32 [n][OH][OW][F], dense: the layout of y.
+ *   acc, p and v = (float)p + bias[j] ((float)p without a bias) are word for word the fused entry's.  Then s = v + res[i][oh][ow][j],
+ *   ONE float32 add, and y = (relu && s < 0) ? +0.0f : s.  A NaN or Inf of res propagates by IEEE and puts the image's cell at or
+ *   above 0x7f800000; nothing is clamped.
+ *   amax_bits: as for the fused entry, taken over the stored y; NULL: no atomics.  Here the maximum of an image is combined across
+ *   the four wavefronts of a workgroup in LDS first, and a workgroup issues at most ONE agent-scope unsigned-max atomic without a
+ *   return value per image it stored into, none where that maximum is 0.  The same bits at every call.
+ *   A float32 add is commutative, so y -- and with it amax_bits and the codes and scales gpfq_quantize_rows_i8_from_amax makes of
+ *   them -- is bit for bit what gpfq_packed_conv2d_forward_i8_fused(relu = 0, amax_bits = NULL) into a buffer t followed by
+ *   gpfq_add_forward_i8(t, res, relu) or gpfq_add_forward_i8(res, t, relu) leaves (a NaN in both operands aside: the conv's own output
+ *   is a NaN only where the image's scale is).
+ *   GPFQ_ERR_INVALID_ARG for a NULL res or for res overlapping y (a lane reads its shortcut before other lanes store); both are
+ *   checked where the other pointers are, behind the empty cases.  Every other check, status code and early return is the fused
+ *   entry's, the clear of amax_bits on n > 0 with an empty output included.  Up to two operations on `stream`: the clear (when
+ *   amax_bits is given) and one launch; no workgroup waits for another; no workspace, no scratch, no host synchronisation; the call
+ *   can be captured into a graph.
+ */
+int gpfq_packed_conv2d_forward_i8_residual(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                           int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw,
+                                           int same_padding, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                           const float *bias, int64_t F, float *y, const float *res, int relu, uint32_t *amax_bits,
+                                           void *stream);
+
+/*
  * The DepthwiseConv2D forward pass on the same footing: the kernel [kh][kw][Cin][mult] held as the packed rows
  * of its matrix view [kh*kw][Cin*mult] (what deploy.export_packed writes): output channel j = c * mult + d has a row of kh*kw codes,
  * pitch = gpfq_packed_row_bytes(kh*kw, bits).  Exact int32 sums on the packed int8 dot product; no matrix instruction.  Opt-in; bit

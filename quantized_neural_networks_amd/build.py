@@ -41,6 +41,7 @@ EXTRA_FLAGS = {"gpfq_pipe.hip": ["-fno-slp-vectorize"], "gpfq_blk.hip": ["-fno-s
 # "-DGPFQ_WIDE_STAMPS" to the several-wavefronts-per-neuron kernel of gpfq_wide.hip (printed from the kernel),
 # "-DGPFQ_S2_SKIP=n" leaves a phase of gpfq_gram_s2_kernel out (wrong sums: timing experiments only),
 # "-DGPFQ_CONV_I8_SKIP=n" one of gpfq_packed_conv_i8_kernel (the gather, the decode or the matrix instruction; the same),
+# "-DGPFQ_CONV_I8_RESIDUAL_LATE=1" makes every residual instantiation of it request its shortcut behind the last matrix instruction,
 # "-DGPFQ_ADD_I8_RAISE_CELL" gives gpfq_add_i8_kernel the load-then-atomic form of its one atomic (the same results, slower)
 # A diagnostic build lives beside the shipped library, in csrc/diag_<hash of the flags>/ (round 5): several variants can be built in the
 # CPU container, travel to the GPU box together and be timed there without a compiler run (the box's minutes are the scarce resource);

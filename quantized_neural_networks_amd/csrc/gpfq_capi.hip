@@ -1010,8 +1010,8 @@ static gpfq::ConvI8Shape conv_i8_shape(int64_t H, int64_t W, int64_t Cin, int kh
     return S;
 }
 
-// both int8 Conv2D entries, as packed_dense_i8_entry
-static int packed_conv_i8_entry(const char *name, bool fused, const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+// the three int8 Conv2D entries, as packed_dense_i8_entry; residual: the fused entry with the shortcut `res` of a residual join
+static int packed_conv_i8_entry(const char *name, bool fused, bool residual, const float *res, const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
                                 int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
                                 const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                 const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits, void *stream)
@@ -1053,6 +1053,15 @@ static int packed_conv_i8_entry(const char *name, bool fused, const int8_t *xq, 
     if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "packed must be 16-byte aligned");
     const gpfq::ConvI8Shape S = conv_i8_shape(H, W, Cin, kh, kw, sh, sw, rh, rw, same_padding, oh, ow);
+    if (residual) {
+        if (!res) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+        const uintptr_t bytes = (uintptr_t)(n * oh * ow * F) * sizeof(float), yb = reinterpret_cast<uintptr_t>(y),
+                        rb = reinterpret_cast<uintptr_t>(res);
+        if (yb < rb + bytes && rb < yb + bytes) return fail(GPFQ_ERR_INVALID_ARG, "res overlaps y: the kernel reads res after other lanes have stored y");
+        hipError_t e = gpfq::launch_packed_conv2d_forward_i8_residual(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y, res,
+                                                                      relu, amax_bits, static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
+    }
     hipError_t e = fused ? gpfq::launch_packed_conv2d_forward_i8_fused(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y,
                                                                        relu, amax_bits, static_cast<hipStream_t>(stream))
                          : gpfq::launch_packed_conv2d_forward_i8(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y,
@@ -1065,7 +1074,7 @@ int gpfq_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, cons
                                   const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                   const float *bias, int64_t F, float *y, void *stream)
 {
-    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8", false, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw, rh, rw, same_padding,
+    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8", false, false, nullptr, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw, rh, rw, same_padding,
                                 packed, bits, zero_code, radii, M, bias, F, y, 0, nullptr, stream);
 }
 
@@ -1074,8 +1083,18 @@ int gpfq_packed_conv2d_forward_i8_fused(const int8_t *xq, int64_t n, int64_t ldq
                                         int same_padding, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                         const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits, void *stream)
 {
-    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_fused", true, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw, rh, rw,
-                                same_padding, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
+    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_fused", true, false, nullptr, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw,
+                                rh, rw, same_padding, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
+}
+
+int gpfq_packed_conv2d_forward_i8_residual(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                           int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw,
+                                           int same_padding, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                           const float *bias, int64_t F, float *y, const float *res, int relu, uint32_t *amax_bits,
+                                           void *stream)
+{
+    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_residual", true, true, res, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw,
+                                rh, rw, same_padding, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
 }
 
 // the int8 DepthwiseConv2D entry: packed_conv_i8_entry's checks in its order, with F = Cin * mult and the row length kh * kw

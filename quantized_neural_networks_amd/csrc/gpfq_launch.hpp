@@ -378,6 +378,12 @@ hipError_t launch_packed_conv2d_forward_i8_fused(const int8_t *xq, int64_t n, in
                                                  const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                                  const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits,
                                                  hipStream_t stream);
+// the fused launch with the shortcut of a residual join added in the epilogue: y = relu(v + res), res in the
+// layout of y; at most two stream operations, the maxima by one atomic per workgroup and image
+hipError_t launch_packed_conv2d_forward_i8_residual(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
+                                                    const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                                    const float *bias, int64_t F, float *y, const float *res, int relu,
+                                                    uint32_t *amax_bits, hipStream_t stream);
 // gpfq_packed_dw_i8.hip: the DepthwiseConv2D forward pass of the same images with the kernel
 // [kh*kw][Cin*mult] held as packed rows, on the packed int8 dot product.  S as above (S.Cin: the input channels); relu / amax_bits as
 // the fused launchers take them, with relu = 0 and amax_bits = NULL giving the kernel without the fused epilogue.

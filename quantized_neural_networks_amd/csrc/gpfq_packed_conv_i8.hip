@@ -31,6 +31,26 @@
 //       maximum of the stored values' bit patterns of |y| for the next layer's quantizer.  With PlainStore (the unfused entry) none
 //       of the epilogue's code or arguments exists in the kernel.
 //
+//   gpfq_packed_conv_i8_kernel<BITS, MT, FAST, ResidualStore>   (gpfq_packed_conv2d_forward_i8_residual)
+//       The fused epilogue with the shortcut of a residual join added before the ReLU: y = relu(v + res), one float32 add on the
+//       value the lane already holds, in place of a second kernel that reads y back.  Its own in two places:
+//         The shortcut is REQUESTED BEFORE THE K WALK AND CONSUMED AFTER IT.  A lane's 4 MT results sit at filter l & 15, positions
+//         4 (l >> 4) + reg of each tile: their places in res are known before the first code is read.  The 4 MT loads are issued
+//         there, every one unconditional -- a position or filter past the end reads the last valid one instead and is never used --
+//         so that their latency lies under the walk and the epilogue adds from registers (4 MT VGPRs more, held across the loop).
+//         kResidualLate names the instantiations that issue them behind the last matrix instruction instead: MT = 4, at all three
+//         widths.  There the 16 values and the addresses formed for them at the top are 88 - 94 VGPRs and 4 wavefronts per SIMD
+//         where the late form has 72 and 5 (the fused epilogue: 54 - 62 and 6 - 7).  MT = 2 requests early at 56 - 58 VGPRs, 7
+//         wavefronts per SIMD at 2 and 8 bits where the late form would have 8; MT = 1 early at 8 of 8.  No instantiation uses
+//         scratch (the compiler's report: profiles/packed_residual_i8.txt).
+//         ONE ATOMIC PER WORKGROUP AND IMAGE.  The per-image maximum is formed inside the wavefront by shuffles as in the fused
+//         epilogue, then raised into the workgroup's LDS cell of that image (ds_max_u32; cell k: the k-th image from the
+//         workgroup's first, 64 MT cells since an image can be one position); after a barrier thread k issues the one bare
+//         agent-scope atomicMax of the workgroup for its k-th image, none for a maximum of 0.  The cells are cleared at the top of
+//         the kernel, with a barrier there while the wavefronts are still in step.  A wavefront past the last position skips the
+//         walk (no steps, nothing stored) and still meets both barriers: the early return is the other two policies'.  With
+//         amax_bits NULL there are no cells, no barriers and no atomics.
+//
 //   Tiers.  MT = 1, 2, 4 position tiles per wavefront on the fast path, from the position count alone (conv_tier below); the general
 //   path has MT = 1 only.
 #include <hip/hip_runtime.h>
@@ -48,6 +68,11 @@
 // leaves the gather of the A operands out, 2 the decode of the B operands, 3 the matrix instruction.  Wrong sums, the same loop.
 #ifndef GPFQ_CONV_I8_SKIP
 #define GPFQ_CONV_I8_SKIP 0
+#endif
+// The same kind of build (tools/packed_residual_probe.py): 1 makes every ResidualStore instantiation request its shortcut behind the
+// last matrix instruction, as MT = 4 does in the shipped library.  The same results.
+#ifndef GPFQ_CONV_I8_RESIDUAL_LATE
+#define GPFQ_CONV_I8_RESIDUAL_LATE 0
 #endif
 
 namespace gpfq {
@@ -93,10 +118,39 @@ gpfq_packed_conv_i8_kernel(const int8_t *__restrict__ xq, int64_t ldq, const flo
     const int r = lane & 15, h = lane >> 4;
     const int pblock = (int)(blockIdx.x / (unsigned)A.ftiles), ftile = (int)(blockIdx.x - (unsigned)pblock * (unsigned)A.ftiles);
     const int p0 = (pblock * kMfmaWaves + wave) * (16 * MT);         // this wavefront's first position
-    if (p0 >= A.P) return;                          // (wave-uniform; the kernel has no barrier)
+    if constexpr (!EPI::residual) {
+        if (p0 >= A.P) return;                      // (wave-uniform; the kernel has no barrier)
+    }
 
     const int64_t j = (int64_t)ftile * kMfmaChannels + r;
     const int plane = S.OH * S.OW;
+
+    // ResidualStore: the workgroup's cells, cleared while its wavefronts are in step, and the shortcut's values requested here
+    constexpr bool kResidualLate = MT == 4 || GPFQ_CONV_I8_RESIDUAL_LATE;      // (see the top)
+    constexpr int kCells = EPI::residual ? conv_block_positions(MT) : 1;
+    [[maybe_unused]] unsigned *wgmax = nullptr;
+    [[maybe_unused]] float rs[EPI::residual ? MT : 1][4];
+    [[maybe_unused]] auto request_shortcut = [&]() {
+        if constexpr (EPI::residual) {
+            const int64_t jc = j < F ? j : F - 1;
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int p = p0 + 16 * m + 4 * h + g;
+                    rs[m][g] = epi.res[(int64_t)(p < A.P ? p : A.P - 1) * F + jc];
+                }
+        }
+    };
+    if constexpr (EPI::residual) {
+        __shared__ unsigned cells[kCells];
+        wgmax = cells;
+        if (epi.amax) {                             // (uniform over the grid)
+            if (tid < kCells) cells[tid] = 0u;
+            __syncthreads();
+        }
+        if constexpr (!kResidualLate) request_shortcut();
+    }
 
     // the MT positions of this lane's A operands: the image and the tap (0, 0)'s place in it
     int ih0[MT], iw0[MT];
@@ -117,7 +171,8 @@ gpfq_packed_conv_i8_kernel(const int8_t *__restrict__ xq, int64_t ldq, const flo
     const DecodeBytes D = decode_bytes(zero_code, M);
     const unsigned tab = decode4(0x03020100u, D);   // the weights of the codes 0..3 (2 bits)
     const int groups = (int)(pitch / 16);
-    const int steps = (groups + kMfmaWaveGroups - 1) / kMfmaWaveGroups;
+    // (ResidualStore: a wavefront past the last position walks nothing -- wave-uniform -- and goes on to the barrier)
+    const int steps = (EPI::residual && p0 >= A.P) ? 0 : (groups + kMfmaWaveGroups - 1) / kMfmaWaveGroups;
     const uint4 *rowp = reinterpret_cast<const uint4 *>(packed + (j < F ? j : F - 1) * pitch);
     auto codes = [&](int step) {
         const int g = step * kMfmaWaveGroups + h;
@@ -214,6 +269,7 @@ gpfq_packed_conv_i8_kernel(const int8_t *__restrict__ xq, int64_t ldq, const flo
         const bool live = j < F;
         const double unit = live ? radii[j] / (double)(M - 1) : 0.0;
         const float bj = (live && bias) ? bias[j] : 0.f;
+        if constexpr (EPI::residual && kResidualLate) request_shortcut();
         unsigned top[MT][4];
 #pragma unroll
         for (int m = 0; m < MT; ++m)
@@ -225,6 +281,7 @@ gpfq_packed_conv_i8_kernel(const int8_t *__restrict__ xq, int64_t ldq, const flo
                     const double pr = ((double)acc[m][g] * (double)scales[p / plane]) * unit;
                     const float v = (float)pr;
                     float out = bias ? v + bj : v;
+                    if constexpr (EPI::residual) out = out + rs[m][g];  // (one float32 add: a NaN or Inf of res goes through)
                     if (epi.relu && out < 0.f) out = 0.f;               // (a NaN and -0.0 are not below zero: they stay)
                     y[(int64_t)p * F + j] = out;
                     top[m][g] = __float_as_uint(out) & 0x7fffffffu;
@@ -236,7 +293,8 @@ gpfq_packed_conv_i8_kernel(const int8_t *__restrict__ xq, int64_t ldq, const flo
         // wavefront, at most one atomic without a return value from lane 0 (raise_cell) -- none where the maximum is 0, which the
         // cleared cell already holds.
         const int pend = p0 + 16 * MT < A.P ? p0 + 16 * MT : A.P;
-        const int first = p0 / plane, last = (pend - 1) / plane;
+        const int first = p0 / plane, last = (pend - 1) / plane;    // (a wavefront past the last position: last < first)
+        [[maybe_unused]] const int wgfirst = (pblock * conv_block_positions(MT)) / plane;    // ResidualStore: the image of cell 0
         for (int i = first; i <= last; ++i) {       // (wave-uniform bounds)
             const int lo = i * plane, hi = lo + plane;
             unsigned t = 0u;
@@ -248,31 +306,37 @@ gpfq_packed_conv_i8_kernel(const int8_t *__restrict__ xq, int64_t ldq, const flo
                     if (p >= lo && p < hi) t = umax(t, top[m][g]);
                 }
             for (int sft = 32; sft >= 1; sft >>= 1) t = umax(t, (unsigned)__shfl_xor((int)t, sft, 64));
-            if (lane == 0 && t != 0u) raise_cell(epi.amax + i, t);
+            if constexpr (EPI::residual) {
+                if (lane == 0 && t != 0u) atomicMax(&wgmax[i - wgfirst], t);    // (LDS; i - wgfirst < 64 MT: one image per position at most)
+            } else {
+                if (lane == 0 && t != 0u) raise_cell(epi.amax + i, t);
+            }
+        }
+        if constexpr (EPI::residual) {
+            __syncthreads();
+            if (tid < kCells) {
+                const unsigned t = wgmax[tid];      // (nonzero only for an image the workgroup stored into: below n)
+                if (t != 0u) atomicMax(epi.amax + wgfirst + tid, t);    // one per workgroup and image: agent scope, no return value
+            }
         }
     }
 }
 
-template <int BITS, int MT, bool FAST, bool FUSED>
+template <int BITS, int MT, bool FAST, class EPI>
 hipError_t launch_conv_i8(const int8_t *xq, int64_t ldq, const float *scales, const ConvI8Args &A, const PackedLayer &L, int M, float *y,
-                          int relu, unsigned *amax, hipStream_t stream)
+                          const EPI &epi, hipStream_t stream)
 {
     const int64_t pblocks = ((int64_t)A.P + conv_block_positions(MT) - 1) / conv_block_positions(MT);
-    using EPI = std::conditional_t<FUSED, FusedStore, PlainStore>;
-    EPI epi;
-    if constexpr (FUSED) {
-        epi.relu = relu;
-        epi.amax = amax;
-    }
     hipLaunchKernelGGL((gpfq_packed_conv_i8_kernel<BITS, MT, FAST, EPI>), dim3((unsigned)(pblocks * A.ftiles)), dim3(kMfmaThreads), 0, stream,
                        xq, ldq, scales, A, L.packed, L.pitch, L.zero_code, L.radii, M, L.bias, L.C, y, epi);
     return hipGetLastError();
 }
 
-template <bool FUSED>
+// epi: the epilogue policy with its arguments -- PlainStore, FusedStore or ResidualStore; one set of tiers and paths for the three
+template <class EPI>
 hipError_t launch_conv_i8_any(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
                               const uint8_t *packed, int bits, int zero_code, const double *radii, int M, const float *bias,
-                              int64_t F, float *y, int relu, unsigned *amax, hipStream_t stream)
+                              int64_t F, float *y, const EPI &epi, hipStream_t stream)
 {
     ConvI8Args A;
     A.S = S;
@@ -288,9 +352,9 @@ hipError_t launch_conv_i8_any(const int8_t *xq, int64_t n, int64_t ldq, const fl
     return packed_dispatch(bits, fast ? conv_tier(A.P) : 1, [&](auto width, auto tier) {
         constexpr int BITS = decltype(width)::value, MT = decltype(tier)::value;
         if constexpr (MT == 1) {
-            if (!fast) return launch_conv_i8<BITS, 1, false, FUSED>(xq, ldq, scales, A, L, M, y, relu, amax, stream);
+            if (!fast) return launch_conv_i8<BITS, 1, false, EPI>(xq, ldq, scales, A, L, M, y, epi, stream);
         }
-        return launch_conv_i8<BITS, MT, true, FUSED>(xq, ldq, scales, A, L, M, y, relu, amax, stream);
+        return launch_conv_i8<BITS, MT, true, EPI>(xq, ldq, scales, A, L, M, y, epi, stream);
     });
 }
 
@@ -300,7 +364,7 @@ hipError_t launch_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t 
                                            const uint8_t *packed, int bits, int zero_code, const double *radii, int M, const float *bias,
                                            int64_t F, float *y, hipStream_t stream)
 {
-    return launch_conv_i8_any<false>(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y, 0, nullptr, stream);
+    return launch_conv_i8_any(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y, PlainStore{}, stream);
 }
 
 hipError_t launch_packed_conv2d_forward_i8_fused(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
@@ -312,7 +376,20 @@ hipError_t launch_packed_conv2d_forward_i8_fused(const int8_t *xq, int64_t n, in
         hipError_t e = launch_amax_clear(amax_bits, n, stream);
         if (e != hipSuccess) return e;
     }
-    return launch_conv_i8_any<true>(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
+    return launch_conv_i8_any(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y, FusedStore{relu, amax_bits}, stream);
+}
+
+hipError_t launch_packed_conv2d_forward_i8_residual(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
+                                                    const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                                    const float *bias, int64_t F, float *y, const float *res, int relu,
+                                                    uint32_t *amax_bits, hipStream_t stream)
+{
+    if (amax_bits) {
+        hipError_t e = launch_amax_clear(amax_bits, n, stream);
+        if (e != hipSuccess) return e;
+    }
+    return launch_conv_i8_any(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y, ResidualStore{relu, amax_bits, res},
+                              stream);
 }
 
 }  // namespace gpfq

@@ -2,7 +2,7 @@
 // int8 B operands of v_mfma_i32_16x16x64_i8 by register arithmetic.  The weight of code c is 2 (c - zero_code) - (M - 1) where
 // zero_code <= c < zero_code + M, else 0 (include/gpfq.h).  And what the two quantizers of the activations share (gpfq_packed_i8.hip:
 // a workgroup per row; gpfq_quantize_split.hip: a workgroup per chunk of a row): one element -> its int8.  And the two epilogues of
-// the forward kernels: the plain store, and the fused one of DESIGN.md section 11c.
+// the forward kernels: the plain store, the fused one of DESIGN.md section 11c, and the Conv2D kernel's residual one of section 11h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -23,12 +23,20 @@ __device__ inline int8_t quantize_one(float v, float inv)
 // What a forward kernel does with a value about to be stored, as its last template argument and -- by value
 // -- its last argument.  PlainStore is empty: the kernel compiled with it holds none of the fused epilogue's code.
 struct PlainStore {
-    static constexpr bool fused = false;
+    static constexpr bool fused = false, residual = false;
 };
 struct FusedStore {
-    static constexpr bool fused = true;
+    static constexpr bool fused = true, residual = false;
     int relu;                                       // 0 / 1: values below zero are stored as +0.0f
     unsigned *amax;                                 // cells for the rows' / images' maxima of bits(y) & 0x7fffffff, cleared; or NULL
+};
+// The Conv2D kernel alone: FusedStore with a residual operand added to the value before the ReLU, and the
+// maxima through one LDS cell per image of the workgroup, one bare atomic per workgroup and image.
+struct ResidualStore {
+    static constexpr bool fused = true, residual = true;
+    int relu;
+    unsigned *amax;
+    const float *res;                               // f32 [n][OH][OW][F], the layout of y
 };
 
 __device__ inline unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }

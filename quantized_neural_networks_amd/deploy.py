@@ -183,7 +183,7 @@ def _is_relu(node):
     return node["kind"] == "ReLU" or (node["kind"] == "Activation" and node["activation"] == "relu")
 
 
-def _plan(nodes, outputs, packed_at, shapes=None, pools=False, adds=False, avgpools=False):
+def _plan(nodes, outputs, packed_at, shapes=None, pools=False, adds=False, avgpools=False, residuals=False):
     """The fusion plan of a network given as tables (host only).  nodes: per position dict(kind, activation, inbound positions);
     outputs: the positions of the network's outputs; packed_at: the positions of the packed layers on the int8 route; shapes: per
     position (input shape, output shape), or None -- no links are made then.  Returns per packed position
@@ -196,8 +196,12 @@ def _plan(nodes, outputs, packed_at, shapes=None, pools=False, adds=False, avgpo
     shapes (the inbound shapes and the row matches cannot be compared) that is every such Add with a packed direct consumer.
     avgpools: every entry has the key ``avgpool`` (None), before hands_to, and a GlobalAveragePooling2D or AveragePooling2D whose
     output reaches a packed layer has an entry of its own under its own position, dict(folded=None, relu=None, [pool=None,]
-    [add=None,] avgpool, hands_to) -- without shapes (the row match cannot be made) that is every such pool."""
-    blank = dict(**(dict(pool=None) if pools else {}), **(dict(add=None) if adds else {}), **(dict(avgpool=None) if avgpools else {}))
+    [add=None,] avgpool, hands_to) -- without shapes (the row match cannot be made) that is every such pool.
+    residuals (with adds): every entry has the key ``residual`` (None), before hands_to, and the entry of a packed Conv2D that hosts
+    a join has (the Add's position, which of its two operands the shortcut is) there -- without shapes the operands' shapes are
+    not compared."""
+    blank = dict(**(dict(pool=None) if pools else {}), **(dict(add=None) if adds else {}), **(dict(avgpool=None) if avgpools else {}),
+                 **(dict(residual=None) if residuals else {}))
     consumers = [[] for _ in nodes]
     for k, node in enumerate(nodes):
         for p in node["inbound"]:
@@ -272,6 +276,34 @@ def _plan(nodes, outputs, packed_at, shapes=None, pools=False, adds=False, avgpo
                            if c in packed_at and (shapes is None or _rows_of(shapes[c][0], nodes[c]["kind"]) == images))
             if takers:
                 plan[p] = dict(folded=None, relu=out if out != p else None, **dict(blank, add=p), hands_to=takers)
+    if residuals:                                   # rule RES
+        # whose output the value at a position is: a packed image layer's group (every position of it), a listed or hosted join's
+        owner = {}
+        for k, e in plan.items():
+            if k in packed_at and nodes[k]["kind"] in ("Conv2D", "DepthwiseConv2D") and nodes[k]["activation"] in (None, "linear", "relu"):
+                owner.update({q: k for q in (k, e["folded"], e["relu"]) if q is not None})
+            elif e.get("add") == k:
+                owner.update({q: k for q in (k, e["relu"]) if q is not None})
+
+        def hosts(k, o):
+            """Packed Conv2D k can take a join on its output o: linear, no ReLU of its own, o the group's output."""
+            return (k in packed_at and nodes[k]["kind"] == "Conv2D" and nodes[k]["activation"] in (None, "linear")
+                    and plan[k]["relu"] is None and o == (plan[k]["folded"] if plan[k]["folded"] is not None else k))
+
+        for p, node in enumerate(nodes):
+            if node["kind"] != "Add" or len(node["inbound"]) != 2 or node["inbound"][0] == node["inbound"][1]:
+                continue
+            if shapes is not None and tuple(shapes[p][0][0]) != tuple(shapes[p][0][1]):
+                continue
+            found = None
+            for which in (0, 1):
+                o, other = node["inbound"][which], node["inbound"][1 - which]
+                k = owner.get(o)
+                if k is not None and hosts(k, o) and sole(o) == p and other < k and other in owner and (found is None or k > found[0]):
+                    found = (k, 1 - which)
+            if found is not None:
+                plan[found[0]]["residual"] = (p, found[1])
+                owner.setdefault(p, p)              # (a join JOIN does not list is a hosted Add all the same: a legal shortcut source)
     if avgpools:                                    # rule AVG
         for p, node in enumerate(nodes):
             if node["kind"] in ("GlobalAveragePooling2D", "AveragePooling2D"):
@@ -293,7 +325,7 @@ def _net_tables(net):
     return nodes, outputs
 
 
-def plan_fusion(net, packed_at=None, pools=False, adds=False, avgpools=False):
+def plan_fusion(net, packed_at=None, pools=False, adds=False, avgpools=False, residuals=False):
     """The plan of load_packed(..., fuse=True) for a keras_shim network (Sequential, or a functional Model): a list with one dict per
     packed layer on the int8 route, in layer order --
 
@@ -336,7 +368,21 @@ def plan_fusion(net, packed_at=None, pools=False, adds=False, avgpools=False):
     packed layer of the route whose rows are the pooled samples one to one (a Dense layer behind a global pool; for a windowed pool
     the match pools=True makes).  Such a pool is listed in layer order at its own position, as dict(layer=None, folded=None,
     relu=None, [pool=None,] [add=None,] avgpool=its name, hands_to=that layer).  With avgpools=False the dicts are exactly those
-    above, without the key."""
+    above, without the key.
+
+    residuals=True (needs adds=True; load_packed(..., fuse_residual=True)): every dict has one more key,
+    ``residual`` (None unless stated), before hands_to, and rule RES, after JOIN, moves residual joins into the epilogue of the
+    convolution in front of them.  RES applies to an Add with two inbound tensors of equal static shape, one of which is the output
+    of a packed Conv2D group of the route -- its BatchNormalization folded or not, no ReLU of its own, a linear activation -- that
+    has the Add as its only consumer and is not a network output: that layer is the HOST.  The other operand, the shortcut, must stand
+    earlier in layer order than the host and be a value whose producer remembers it: a position of a packed Conv2D /
+    DepthwiseConv2D group of the route, or of a join that JOIN lists or RES hosts (with its fused ReLU).  Where both operands
+    qualify as hosts -- a projection block -- the later one in layer order is the host.  The host's entry then has
+    residual=(the Add's name, the shortcut's place among the Add's operands: 0 or 1); the Add's own entry, its ReLU and hands_to stay
+    as JOIN states them, and a join JOIN does not list (no packed consumer) is hosted too, with no maxima wanted.  With
+    residuals=False the dicts are exactly those above, without the key."""
+    if residuals and not adds:
+        raise ValueError("plan_fusion: residuals=True hosts the joins rule JOIN knows: it needs adds=True")
     net = _shim_network(net)
     if packed_at is None:
         packed_at = [k for k, l in enumerate(net.layers)
@@ -347,9 +393,10 @@ def plan_fusion(net, packed_at=None, pools=False, adds=False, avgpools=False):
     if bad:
         raise ValueError(f"plan_fusion: positions {bad} are not Dense or Conv2D / DepthwiseConv2D layers")
     shapes = [(l.input_shape, l.output_shape) for l in net.layers]
-    plan = _plan(nodes, outputs, packed_at, shapes, pools, adds, avgpools)
+    plan = _plan(nodes, outputs, packed_at, shapes, pools, adds, avgpools, residuals)
     name = lambda k: None if k is None else (tuple(name(j) for j in k) if isinstance(k, tuple) else net.layers[k].name)
-    return [dict(layer=name(k) if k in packed_at else None, **{key: name(v) for key, v in e.items()}) for k, e in sorted(plan.items())]
+    named = lambda key, v: (name(v[0]), v[1]) if key == "residual" and v is not None else name(v)
+    return [dict(layer=name(k) if k in packed_at else None, **{key: named(key, v) for key, v in e.items()}) for k, e in sorted(plan.items())]
 
 
 def _arch_tables(arch):
@@ -368,14 +415,15 @@ def _arch_tables(arch):
 _FUSED_AWAY = {"BatchNormalization": "FoldedBatchNormalization", "Activation": "FusedActivation", "ReLU": "FusedReLU"}
 
 
-def _apply_fusion(net, packed_at, pools=False, adds=False, avgpools=False):
+def _apply_fusion(net, packed_at, pools=False, adds=False, avgpools=False, residuals=False):
     """Sets the fused state of the packed layers of a loaded network from its plan and records the plan as net.fusion_plan.  pools:
     the plan with its pools -- a named pool is linked, the layer behind it takes its codes, a packed layer in front hands it maxima.
     adds: the plan with its joins -- a named Add is linked and every layer of its hands_to takes its codes.
-    avgpools: the plan with its average pools -- a named one is linked and the layer behind it takes its codes."""
+    avgpools: the plan with its average pools -- a named one is linked and the layer behind it takes its codes.
+    residuals: the plan with its hosts -- a host knows its join and the layer that produces its shortcut, the join its host."""
     pos = {l.name: k for k, l in enumerate(net.layers)}
     net.fusion_plan = plan_fusion(net, packed_at, **(dict(pools=True) if pools else {}), **(dict(adds=True) if adds else {}),
-                                  **(dict(avgpools=True) if avgpools else {}))
+                                  **(dict(avgpools=True) if avgpools else {}), **(dict(residuals=True) if residuals else {}))
     for e in net.fusion_plan:
         if e.get("avgpool") is not None:
             pool = net.layers[pos[e["avgpool"]]]
@@ -405,6 +453,13 @@ def _apply_fusion(net, packed_at, pools=False, adds=False, avgpools=False):
         to = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device=net.device, dtype=dt).contiguous()
         layer.fused = dict(radii=to(radii, torch.float64), bias=to(bias, torch.float32), relu=e["relu"] is not None)
         layer.emit_amax = e["hands_to"] is not None
+        if e.get("residual") is not None:
+            join = net.layers[pos[e["residual"][0]]]
+            source = join.inbound_nodes[0].inbound_layers[e["residual"][1]]
+            while isinstance(source, keras_shim._FusedAway):        # (the value there is its group's output: the producer remembers it)
+                source = source.inbound_nodes[0].inbound_layers
+            if isinstance(join, keras_shim.QuantizingAdd) and hasattr(source, "_out"):
+                layer.residual, join.residual_host = dict(join=join, source=source), layer
         if e.get("pool") is not None:
             net.layers[pos[e["pool"]]].amax_from = layer
         elif e["hands_to"] is not None:
@@ -413,7 +468,7 @@ def _apply_fusion(net, packed_at, pools=False, adds=False, avgpools=False):
 
 
 def load_packed(path, device=None, activations="float32", packed_conv=False, fuse=False, packed_depthwise=False, fuse_pool=False,
-                fuse_add=False, fuse_avgpool=False):
+                fuse_add=False, fuse_avgpool=False, fuse_residual=False):
     """Inverse of export_packed: a keras_shim network on ``device`` (default: the current GPU).  Dense layers that were exported
     packed come back as keras_shim.PackedDense (codes, radii and bias in device memory; the float kernel is never formed unless
     get_weights() or a batch beyond keras_shim.PACKED_TILED_MAX_BATCH asks for it); packed Conv2D / DepthwiseConv2D kernels are
@@ -458,7 +513,17 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
     one HIP kernel (hip.global_avgpool_forward_i8 / hip.avgpool2d_forward_i8) forms the means and leaves their maxima, and one
     quantizing pass makes the int8 codes and scales that the packed layer behind the pool takes in place of running its own
     quantizer.  The means are include/gpfq.h's -- a float64 sum in a stated order, one division, one rounding -- where
-    fuse_avgpool=False has torch's float32 reduction: the two differ by float32 roundings of the means, and by nothing else."""
+    fuse_avgpool=False has torch's float32 reduction: the two differ by float32 roundings of the means, and by nothing else.
+
+    fuse_residual=True (needs fuse=True and fuse_add=True): the plan is plan_fusion(..., residuals=True).  A
+    PackedConv2D it names as the host of a join takes the shortcut from the layer that produced it -- under the proof of
+    _FusedI8, on that layer's remembered output -- and adds it in its kernel's epilogue (hip.packed_conv2d_forward_i8_residual),
+    with the Add's ReLU and, where the Add hands codes on, the maxima; the keras_shim.QuantizingAdd behind it, given exactly that
+    output and that shortcut, adds nothing and makes its codes from those maxima.  Where either proof fails the join is the
+    Add's, as with fuse_residual=False.  The value at the host's, its folded BatchNormalization's and the Add's positions is the
+    join's output; every value is bit for bit what fuse_residual=False computes there and behind."""
+    if fuse_residual and not (fuse and fuse_add):
+        raise ValueError("fuse_residual=True moves the joins of fuse_add=True into the fused int8 convolution in front: it needs fuse=True and fuse_add=True")
     if fuse_avgpool and not fuse:
         raise ValueError("fuse_avgpool=True hands the codes of an average pool to the fused int8 layer behind it: it needs fuse=True")
     if fuse_add and not fuse:
@@ -504,6 +569,11 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
                     classes[k] = keras_shim.QuantizingAdd
                     if r is not None:
                         classes[r] = getattr(keras_shim, _FUSED_AWAY[arch["layers"][r]["cls"]])
+            if fuse_residual:
+                # every join a host can take, JOIN's or not (one without a packed consumer keeps its ReLU layer: nothing fuses it)
+                for e in _plan(nodes, outputs, fused_at, adds=True, residuals=True).values():
+                    if e["residual"] is not None:
+                        classes.setdefault(e["residual"][0], keras_shim.QuantizingAdd)
             if fuse_avgpool:
                 # every average pool the full plan can name (the row matches need the network's shapes: _apply_fusion links those that pass)
                 for e in _plan(nodes, outputs, fused_at, avgpools=True).values():
@@ -526,4 +596,4 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
                     layer.set_weights([unpack_kernel(packed)] + rest)
             elif layer._weights:
                 layer.set_weights([z[f"w{k}_{j}"] for j in range(len(layer._weights))])
-    return _apply_fusion(net, fused_at, fuse_pool, fuse_add, fuse_avgpool) if fuse else net
+    return _apply_fusion(net, fused_at, fuse_pool, fuse_add, fuse_avgpool, fuse_residual) if fuse else net

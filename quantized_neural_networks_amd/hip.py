@@ -80,6 +80,8 @@ SYMBOLS = {
                                                   _vp]),
     "gpfq_packed_conv2d_forward_i8_fused": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
                                                    _vp, _int, _int, _vp, _int, _vp, _i64, _vp, _int, _vp, _vp]),
+    "gpfq_packed_conv2d_forward_i8_residual": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
+                                                      _vp, _int, _int, _vp, _int, _vp, _i64, _vp, _vp, _int, _vp, _vp]),
     "gpfq_quantize_rows_i8_from_amax": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "gpfq_packed_depthwise_conv2d_forward_i8": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int,
                                                        _int, _vp, _int, _int, _vp, _int, _vp, _vp, _int, _vp, _vp]),
@@ -1606,15 +1608,9 @@ def _i8_image_out(bias, out, shape, device):
     return (bias.data_ptr() if bias is not None else None), out
 
 
-def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias=None, scales=None,
-                             out=None, relu=False, amax_out=None, amax=None):
-    """y f32 [n][OH][OW][F] of a Conv2D layer whose kernel [kh][kw][Cin][F] = kernel_shape is held as the packed rows of its matrix
-    view [kh*kw*Cin][F], on int8 images and exact int32 sums (gpfq_packed_conv2d_forward_i8; the contract is include/gpfq.h's, bit for
-    bit; TensorFlow's geometry).  x_or_xq: float32 NHWC x [n][H][W][Cin], each image quantized here with its own scale
-    (quantize_rows_i8 on the flattened images), or -- with `scales` f32 [n] -- ready int8 images [n][H][W][Cin], each contiguous, an
-    image pitch (stride(0)) that is a multiple of 16.  M: the size of the layer's unit alphabet, which must be linspace(-1, 1, M).
-    out: an optional contiguous [n][OH][OW][F] tensor.  relu / amax_out (a uint32 or int32 [n] tensor, one cell per image) / amax
-    (the maxima of a float x's images): as for packed_dense_forward_i8, through gpfq_packed_conv2d_forward_i8_fused.  No sync."""
+def _packed_conv2d_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias, scales, out, relu,
+                      amax_out, amax, res=None, residual=False):
+    """What packed_conv2d_forward_i8 and packed_conv2d_forward_i8_residual share: the checks, the output, the call."""
     kh, kw, Cin, F = (int(v) for v in kernel_shape)
     kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
     xq, scales, n, H, W, ldq = _i8_images(x_or_xq, (kh, kw, Cin, F), (sh, sw, rh, rw), scales, amax)
@@ -1624,18 +1620,44 @@ def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_
     OH, OW = patch_out_dim(H, kh, sh, rh, same), patch_out_dim(W, kw, sw, rw, same)
     bp, out = _i8_image_out(bias, out, (n, OH, OW, F), xq.device)
     fused, relu, ap = _fused_args(relu, amax_out, n)
+    front = (xq.data_ptr(), n, ldq, scales.data_ptr(), H, W, Cin, kh, kw, sh, sw, rh, rw, 1 if same else 0, packed.data_ptr(), int(bits),
+             int(zero_code), radii.data_ptr(), int(M), bp, F, out.data_ptr())
+    if residual:
+        _dev(res, torch.float32, "res")
+        if tuple(res.shape) != tuple(out.shape) or not res.is_contiguous() or res.device != out.device:
+            raise GpfqError(f"res {tuple(res.shape)} must be a contiguous {tuple(out.shape)} tensor on the output's device")
+        entry, back = "gpfq_packed_conv2d_forward_i8_residual", (res.data_ptr(), relu, ap, _stream())
+    elif fused:
+        entry, back = "gpfq_packed_conv2d_forward_i8_fused", (relu, ap, _stream())
+    else:
+        entry, back = "gpfq_packed_conv2d_forward_i8", (_stream(),)
     with torch.cuda.device(xq.device):
-        if fused:
-            _check(load().gpfq_packed_conv2d_forward_i8_fused(xq.data_ptr(), n, ldq, scales.data_ptr(), H, W, Cin, kh, kw, sh, sw, rh, rw,
-                                                              1 if same else 0, packed.data_ptr(), int(bits), int(zero_code),
-                                                              radii.data_ptr(), int(M), bp, F, out.data_ptr(), relu, ap, _stream()),
-                   "gpfq_packed_conv2d_forward_i8_fused")
-        else:
-            _check(load().gpfq_packed_conv2d_forward_i8(xq.data_ptr(), n, ldq, scales.data_ptr(), H, W, Cin, kh, kw, sh, sw, rh, rw,
-                                                        1 if same else 0, packed.data_ptr(), int(bits), int(zero_code), radii.data_ptr(),
-                                                        int(M), bp, F, out.data_ptr(), _stream()),
-                   "gpfq_packed_conv2d_forward_i8")
+        _check(getattr(load(), entry)(*front, *back), entry)
     return out
+
+
+def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias=None, scales=None,
+                             out=None, relu=False, amax_out=None, amax=None):
+    """y f32 [n][OH][OW][F] of a Conv2D layer whose kernel [kh][kw][Cin][F] = kernel_shape is held as the packed rows of its matrix
+    view [kh*kw*Cin][F], on int8 images and exact int32 sums (gpfq_packed_conv2d_forward_i8; the contract is include/gpfq.h's, bit for
+    bit; TensorFlow's geometry).  x_or_xq: float32 NHWC x [n][H][W][Cin], each image quantized here with its own scale
+    (quantize_rows_i8 on the flattened images), or -- with `scales` f32 [n] -- ready int8 images [n][H][W][Cin], each contiguous, an
+    image pitch (stride(0)) that is a multiple of 16.  M: the size of the layer's unit alphabet, which must be linspace(-1, 1, M).
+    out: an optional contiguous [n][OH][OW][F] tensor.  relu / amax_out (a uint32 or int32 [n] tensor, one cell per image) / amax
+    (the maxima of a float x's images): as for packed_dense_forward_i8, through gpfq_packed_conv2d_forward_i8_fused.  No sync."""
+    return _packed_conv2d_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias, scales, out, relu,
+                             amax_out, amax)
+
+
+def packed_conv2d_forward_i8_residual(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, res, bias=None,
+                                      scales=None, out=None, relu=False, amax_out=None, amax=None):
+    """packed_conv2d_forward_i8 with the shortcut of a residual join added in the kernel's epilogue
+    (gpfq_packed_conv2d_forward_i8_residual; the contract is include/gpfq.h's, bit for bit): y = v + res, with
+    the ReLU behind the sum where `relu`, and amax_out the maxima of that y.  res: a contiguous float32 [n][OH][OW][F] tensor on the
+    output's device that does not overlap `out`.  Every other argument, and the result, as for packed_conv2d_forward_i8: y is bit for
+    bit what that call followed by add_forward_i8(y, res, relu) leaves, in one launch less and without the passes over y.  No sync."""
+    return _packed_conv2d_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias, scales, out, relu,
+                             amax_out, amax, res=res, residual=True)
 
 
 def packed_depthwise_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias=None,

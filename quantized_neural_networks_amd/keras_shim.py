@@ -184,28 +184,59 @@ class QuantizingAdd(Add):
     hip.add_forward_i8 -- the sum, with the ReLU behind it where ``relu`` (that layer is then a FusedActivation / FusedReLU, and the
     value at its position this one's), and with it the int8 codes and scales that every packed consumer's quantizer would make, which
     the consumers take (_FusedI8._taken_codes) in place of quantizing.  Anything else is Add.call, followed by torch.relu where
-    ``relu``.  config(), clone() and save_model() give the Add."""
+    ``relu``.  config(), clone() and save_model() give the Add.
+
+    ``residual_host`` (load_packed(..., fuse_residual=True)): the PackedConv2D whose kernel adds this join's
+    shortcut in its epilogue.  Given exactly that layer's untouched output and the shortcut it added (``_joined``), the call adds
+    nothing: it makes the codes from the host's maxima where it is ``linked`` and returns the host's output.  Anything else is the
+    call above."""
 
     def __init__(self, name=None):
         super().__init__(name)
         self.linked = False
         self.relu = False
+        self.residual_host = None
+        self.hosted_call = False
         self._codes = None                            # (weak reference to the output, its version, xq, scales, floats per image)
+        self._out = None                              # (weak reference to the output, its version: PackedConv2D._shortcut)
 
     def clone(self):
         c = Add(**self.config())
         c.name = self.name
         return c
 
+    def _hosted(self, xs):
+        """(the host's output y, its maxima or None) where xs are y, untouched, and the very shortcut the host added; else None."""
+        rec = getattr(self.residual_host, "_joined", None) if self.residual_host is not None else None
+        if rec is None or len(xs) != 2 or not all(isinstance(x, torch.Tensor) for x in xs):
+            return None
+        y, version, res, res_version, cells = rec[0](), rec[1], rec[2](), rec[3], rec[4]
+        for a, b in ((xs[0], xs[1]), (xs[1], xs[0])):
+            if res is not None and b is res and res._version == res_version and a is not res and _untouched(a, y, version):
+                return y, cells
+        return None
+
     def call(self, xs):
-        if (self.linked and len(xs) == 2 and all(isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_cuda for x in xs)
+        hosted = self._hosted(xs)
+        self.hosted_call = hosted is not None          # (the last call returned the host's output: nothing was added here)
+        if hosted is not None:
+            y, cells = hosted
+            if self.linked:
+                from . import hip
+                n = int(y.shape[0])
+                per = y[0].numel() if n else 0
+                xq, scales = hip.quantize_rows_i8(y.reshape(n, per), amax=cells)
+                self._codes = (weakref.ref(y), y._version, xq, scales, per)
+        elif (self.linked and len(xs) == 2 and all(isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_cuda for x in xs)
                 and xs[0].shape == xs[1].shape and xs[0].device == xs[1].device and xs[0].dim() >= 1):
             from . import hip
             y, xq, scales = hip.add_forward_i8(xs[0].contiguous(), xs[1].contiguous(), relu=self.relu)
             self._codes = (weakref.ref(y), y._version, xq, scales, y[0].numel() if y.shape[0] else 0)
-            return y
-        y = Add.call(self, xs)
-        return torch.relu(y) if self.relu else y
+        else:
+            y = Add.call(self, xs)
+            y = torch.relu(y) if self.relu else y
+        self._out = (weakref.ref(y), y._version) if isinstance(y, torch.Tensor) else None
+        return y
 
 
 class GlobalAveragePooling2D(Layer):
@@ -324,6 +355,7 @@ class _FusedI8:
         self.amax_from = None
         self.codes_from = None                        # (the Quantizing pool or Add in front: fuse_pool / fuse_add / fuse_avgpool)
         self._handoff = None                          # (weak reference to the output, its version, maxima i32 [rows], floats per row)
+        self._out = None                              # (weak reference to the output, its version)
 
     def _fused_parts(self, bias):
         """(radii, bias, relu fused, what is left of the activation as a torch op) of a call on the int8 route."""
@@ -338,6 +370,7 @@ class _FusedI8:
 
     def _remember(self, y, amax, per_row):
         self._handoff = (weakref.ref(y), y._version, amax, int(per_row)) if amax is not None else None
+        self._out = (weakref.ref(y), y._version)        # (for a host that takes this output as its shortcut: PackedConv2D._shortcut)
 
     def _taken_maxima(self, x, rows, row_len):
         """The producer's maxima for the rows of x, or None (the full quantizer).  x: the contiguous tensor about to be quantized."""
@@ -547,7 +580,10 @@ class PackedConv2D(Conv2D, _FusedI8):
     does; "int8" rounds every image of x to int8 with its own scale and runs gpfq_packed_conv2d_forward_i8 -- exact int32 sums, the
     float kernel is never formed (include/gpfq.h has the arithmetic; the layer's alphabet must be linspace(-1, 1, M), which
     deploy.load_packed checks).  A property of the loaded layer, not of its configuration: config(), clone() and save_model() record
-    the Conv2D it decodes to.  ``fused``, ``emit_amax``, ``amax_from``: _FusedI8."""
+    the Conv2D it decodes to.  ``fused``, ``emit_amax``, ``amax_from``: _FusedI8.  ``residual`` (load_packed(...,
+    fuse_residual=True)): the residual join behind this layer that its kernel performs in its epilogue
+    (hip.packed_conv2d_forward_i8_residual) where the shortcut can be proved to be its producer's untouched output (``_shortcut``);
+    the layer's output is then the join's."""
 
     ACTIVATIONS = ("float32", "int8")
 
@@ -557,6 +593,8 @@ class PackedConv2D(Conv2D, _FusedI8):
         self.packed = None
         self.activations = "float32"
         self._init_fused()
+        self.residual = None                         # (fuse_residual: dict(join=the QuantizingAdd this layer hosts, source=the shortcut's producer))
+        self._joined = None                           # (weak reference to y, its version, weak reference to res, its version, maxima or None)
 
     def build(self, input_shape, device, rng):
         Layer.build(self, input_shape, device, rng)
@@ -602,6 +640,20 @@ class PackedConv2D(Conv2D, _FusedI8):
     def _bias(self):
         return self._weights[0] if self.use_bias else None
 
+    def _shortcut(self, shape, device):
+        """The shortcut tensor of the residual join this layer hosts (``residual``), or None (the join stays
+        the Add's).  The proof is _FusedI8._taken_maxima's, on the producer's remembered output: alive, float32, contiguous, on this
+        device, of this call's output shape, and not modified in place since the producer wrote it."""
+        r = self.residual
+        hand = getattr(r["source"], "_out", None) if r is not None else None
+        if hand is None or self.activation not in (None, "linear") or (self.fused or {}).get("relu"):
+            return None
+        t, version = hand[0](), hand[1]
+        if (t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.device != device or tuple(t.shape) != tuple(shape)
+                or t._version != version):
+            return None
+        return t
+
     def call(self, x):
         if self.route() == "decode":
             self._need_i8("decode")
@@ -613,6 +665,19 @@ class PackedConv2D(Conv2D, _FusedI8):
         radii, bias, relu, rest = self._fused_parts(self._bias())
         x = x.contiguous()
         n = int(x.shape[0])
+        res = self._shortcut(self.compute_output_shape(tuple(x.shape)), x.device)
+        self._joined = None
+        if res is not None:
+            # the join in this kernel's epilogue: the Add's ReLU, and the maxima where the Add hands codes on
+            join = self.residual["join"]
+            cells = torch.empty(n, dtype=torch.int32, device=x.device) if join.linked and n > 0 else None
+            x, given = self._i8_input(x)
+            y = hip.packed_conv2d_forward_i8_residual(x, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]),
+                                                      self.kernel_shape, self.strides, self.dilation_rate, self.padding, res, bias=bias,
+                                                      relu=join.relu, amax_out=cells, **given)
+            self._joined = (weakref.ref(y), y._version, weakref.ref(res), res._version, cells)
+            self._remember(y, None, 0)
+            return y
         amax_out = self._amax_out(n, x.device)
         x, given = self._i8_input(x)
         y = hip.packed_conv2d_forward_i8(x, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]), self.kernel_shape,
