@@ -619,6 +619,29 @@ int gpfq_packed_conv2d_forward_i8_residual(const int8_t *xq, int64_t n, int64_t 
                                            void *stream);
 
 /*
+ * gpfq_packed_conv2d_forward_i8_staged: the staged form of the int8 Conv2D pass, for stem layers.  Opt-in; bit
+ * for bit gpfq_packed_conv2d_forward_i8_fused: the argument list, y and amax_bits of that entry, with its checks, status codes and
+ * empty cases; with relu = 0 and amax_bits = NULL it returns gpfq_packed_conv2d_forward_i8's result, so the one entry serves both.
+ *   Range: kh*kw*Cin <= GPFQ_PACKED_CONV_STAGED_MAX_K and, for the input window of four output rows by sixteen output columns,
+ *   (3 sh + (kh - 1) rh + 1) * (15 sw + (kw - 1) rw + 1) * Cin <= 32768 bytes; any Cin, multiples of 16 included.
+ *   gpfq_packed_conv2d_staged_supported says 1 / 0 for a shape (host arithmetic only, callable without a device; 0 also for bits other
+ *   than 2, 4, 8 or a size that is not positive); outside the range the entry returns GPFQ_ERR_UNSUPPORTED with a message naming the
+ *   bound, behind the empty cases and before any launch.
+ *   Readability: the kernel reads the images in aligned 4-byte words, so every image must be readable up to the next multiple of 4
+ *   of H*W*Cin.  Any buffer of n * ldq bytes satisfies this, and gpfq_quantize_rows_i8's output does.
+ *   With amax_bits a workgroup (one image, four output rows) issues at most ONE agent-scope unsigned-max atomic without a return
+ *   value, none where its maximum is 0.  Up to two operations on `stream`: the clear (when amax_bits is given) and one launch; no
+ *   workgroup waits for another; no workspace, no scratch, no host synchronisation; the call can be captured into a graph.
+ */
+#define GPFQ_PACKED_CONV_STAGED_MAX_K 256
+int gpfq_packed_conv2d_staged_supported(int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw,
+                                        int same_padding, int bits);
+int gpfq_packed_conv2d_forward_i8_staged(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                         int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw,
+                                         int same_padding, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                         const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits, void *stream);
+
+/*
  * The DepthwiseConv2D forward pass on the same footing: the kernel [kh][kw][Cin][mult] held as the packed rows
  * of its matrix view [kh*kw][Cin*mult] (what deploy.export_packed writes): output channel j = c * mult + d has a row of kh*kw codes,
  * pitch = gpfq_packed_row_bytes(kh*kw, bits).  Exact int32 sums on the packed int8 dot product; no matrix instruction.  Opt-in; bit

@@ -1011,7 +1011,7 @@ static gpfq::ConvI8Shape conv_i8_shape(int64_t H, int64_t W, int64_t Cin, int kh
 }
 
 // the three int8 Conv2D entries, as packed_dense_i8_entry; residual: the fused entry with the shortcut `res` of a residual join
-static int packed_conv_i8_entry(const char *name, bool fused, bool residual, const float *res, const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+static int packed_conv_i8_entry(const char *name, bool fused, bool residual, bool staged, const float *res, const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
                                 int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
                                 const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                 const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits, void *stream)
@@ -1041,6 +1041,10 @@ static int packed_conv_i8_entry(const char *name, bool fused, bool residual, con
         }
         return GPFQ_OK;
     }
+    if (staged && !gpfq::packed_conv_i8_staged_fits(Cin, kh, kw, sh, sw, rh, rw))
+        return fail(GPFQ_ERR_UNSUPPORTED, "the staged form takes kh*kw*Cin=%lld <= GPFQ_PACKED_CONV_STAGED_MAX_K=%d and a window of "
+                    "(3*sh+(kh-1)*rh+1)*(15*sw+(kw-1)*rw+1)*Cin <= 32768 bytes (gpfq_packed_conv2d_staged_supported)", (long long)K,
+                    GPFQ_PACKED_CONV_STAGED_MAX_K);
     // what the kernel indexes with 32 bits: a place inside an image, a position, a tap's row and column
     const int64_t limit = 1LL << 24, keh = kh + (int64_t)(kh - 1) * (rh - 1), kew = kw + (int64_t)(kw - 1) * (rw - 1);
     if (H > limit || W > limit || sh > limit || sw > limit || keh > limit || kew > limit || H * W > 2147483647LL / Cin)
@@ -1062,6 +1066,12 @@ static int packed_conv_i8_entry(const char *name, bool fused, bool residual, con
                                                                       relu, amax_bits, static_cast<hipStream_t>(stream));
         return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
     }
+    if (staged) {
+        if (gpfq::packed_conv_i8_staged_blocks(n, S, F) > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "layer too wide for one launch");
+        hipError_t e = gpfq::launch_packed_conv2d_forward_i8_staged(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y, relu,
+                                                                    amax_bits, static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
+    }
     hipError_t e = fused ? gpfq::launch_packed_conv2d_forward_i8_fused(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y,
                                                                        relu, amax_bits, static_cast<hipStream_t>(stream))
                          : gpfq::launch_packed_conv2d_forward_i8(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, y,
@@ -1074,7 +1084,7 @@ int gpfq_packed_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, cons
                                   const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                   const float *bias, int64_t F, float *y, void *stream)
 {
-    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8", false, false, nullptr, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw, rh, rw, same_padding,
+    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8", false, false, false, nullptr, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw, rh, rw, same_padding,
                                 packed, bits, zero_code, radii, M, bias, F, y, 0, nullptr, stream);
 }
 
@@ -1083,7 +1093,7 @@ int gpfq_packed_conv2d_forward_i8_fused(const int8_t *xq, int64_t n, int64_t ldq
                                         int same_padding, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                         const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits, void *stream)
 {
-    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_fused", true, false, nullptr, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw,
+    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_fused", true, false, false, nullptr, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw,
                                 rh, rw, same_padding, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
 }
 
@@ -1093,8 +1103,25 @@ int gpfq_packed_conv2d_forward_i8_residual(const int8_t *xq, int64_t n, int64_t 
                                            const float *bias, int64_t F, float *y, const float *res, int relu, uint32_t *amax_bits,
                                            void *stream)
 {
-    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_residual", true, true, res, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw,
+    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_residual", true, true, false, res, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw,
                                 rh, rw, same_padding, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
+}
+
+int gpfq_packed_conv2d_staged_supported(int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw,
+                                        int same_padding, int bits)
+{
+    (void)same_padding;                             // (the pads move the window, not its size)
+    if (H <= 0 || W <= 0 || (bits != 2 && bits != 4 && bits != 8)) return 0;
+    return gpfq::packed_conv_i8_staged_fits(Cin, kh, kw, sh, sw, rh, rw) ? 1 : 0;
+}
+
+int gpfq_packed_conv2d_forward_i8_staged(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                         int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw,
+                                         int same_padding, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                         const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits, void *stream)
+{
+    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_staged", true, false, true, nullptr, xq, n, ldq, scales, H, W, Cin, kh, kw,
+                                sh, sw, rh, rw, same_padding, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
 }
 
 // the int8 DepthwiseConv2D entry: packed_conv_i8_entry's checks in its order, with F = Cin * mult and the row length kh * kw

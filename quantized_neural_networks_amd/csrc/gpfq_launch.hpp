@@ -384,6 +384,17 @@ hipError_t launch_packed_conv2d_forward_i8_residual(const int8_t *xq, int64_t n,
                                                     const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                                     const float *bias, int64_t F, float *y, const float *res, int relu,
                                                     uint32_t *amax_bits, hipStream_t stream);
+// gpfq_packed_conv_i8_staged.hip: the same pass for kernels of kh kw Cin <= GPFQ_PACKED_CONV_STAGED_MAX_K, the
+// input window of a workgroup staged in LDS and the A operands held in registers across the filter tiles.  relu / amax_bits as the
+// fused launcher takes them, with relu = 0 and amax_bits = NULL giving the kernel without the fused epilogue.
+// packed_conv_i8_staged_fits: the two bounds of the form (host arithmetic); packed_conv_i8_staged_blocks: the workgroups of the
+// launch, for the entry's check.
+bool packed_conv_i8_staged_fits(int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw);
+int64_t packed_conv_i8_staged_blocks(int64_t n, const ConvI8Shape &S, int64_t F);
+hipError_t launch_packed_conv2d_forward_i8_staged(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
+                                                  const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                                  const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits,
+                                                  hipStream_t stream);
 // gpfq_packed_dw_i8.hip: the DepthwiseConv2D forward pass of the same images with the kernel
 // [kh*kw][Cin*mult] held as packed rows, on the packed int8 dot product.  S as above (S.Cin: the input channels); relu / amax_bits as
 // the fused launchers take them, with relu = 0 and amax_bits = NULL giving the kernel without the fused epilogue.

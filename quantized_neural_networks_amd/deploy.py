@@ -468,7 +468,7 @@ def _apply_fusion(net, packed_at, pools=False, adds=False, avgpools=False, resid
 
 
 def load_packed(path, device=None, activations="float32", packed_conv=False, fuse=False, packed_depthwise=False, fuse_pool=False,
-                fuse_add=False, fuse_avgpool=False, fuse_residual=False):
+                fuse_add=False, fuse_avgpool=False, fuse_residual=False, staged_conv=False):
     """Inverse of export_packed: a keras_shim network on ``device`` (default: the current GPU).  Dense layers that were exported
     packed come back as keras_shim.PackedDense (codes, radii and bias in device memory; the float kernel is never formed unless
     get_weights() or a batch beyond keras_shim.PACKED_TILED_MAX_BATCH asks for it); packed Conv2D / DepthwiseConv2D kernels are
@@ -521,7 +521,14 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
     with the Add's ReLU and, where the Add hands codes on, the maxima; the keras_shim.QuantizingAdd behind it, given exactly that
     output and that shortcut, adds nothing and makes its codes from those maxima.  Where either proof fails the join is the
     Add's, as with fuse_residual=False.  The value at the host's, its folded BatchNormalization's and the Add's positions is the
-    join's output; every value is bit for bit what fuse_residual=False computes there and behind."""
+    join's output; every value is bit for bit what fuse_residual=False computes there and behind.
+
+    staged_conv=True (needs activations="int8" and packed_conv=True): every PackedConv2D whose Cin is not a
+    multiple of 16 -- the stem layers, which the gather kernel serves byte by byte -- has ``staged`` set and runs the staged kernel
+    form where its shape is inside that form's range (keras_shim.PackedConv2D.conv_form).  The plan of fuse=True and the other
+    switches is untouched, and every value is bit for bit what staged_conv=False computes."""
+    if staged_conv and not (activations == "int8" and packed_conv):
+        raise ValueError("staged_conv=True chooses the kernel form of the int8 packed Conv2D layers: it needs activations=\"int8\" and packed_conv=True")
     if fuse_residual and not (fuse and fuse_add):
         raise ValueError("fuse_residual=True moves the joins of fuse_add=True into the fused int8 convolution in front: it needs fuse=True and fuse_add=True")
     if fuse_avgpool and not fuse:
@@ -592,6 +599,8 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
                         _check_int8_layer(layer, packed)
                     layer.set_packed(packed, rest[0] if rest else None)
                     layer.activations = activations
+                    if staged_conv and isinstance(layer, keras_shim.PackedConv2D):
+                        layer.staged = layer.kernel_shape[2] % 16 != 0
                 else:
                     layer.set_weights([unpack_kernel(packed)] + rest)
             elif layer._weights:

@@ -28,6 +28,7 @@ GPFQ_REFINE_GRAM_MAX_N = 25600     # longest walk the refinement sweeps on the G
 GPFQ_REFINE_PAIRS_MAX_K = 64       # longest walk of an (input channel, filter) pair refine_conv_pairs takes (include/gpfq.h)
 GPFQ_ERR_INVALID_ARG, GPFQ_ERR_UNSUPPORTED, GPFQ_ERR_WORKSPACE = -1, -2, -3
 GPFQ_PACKED_I8_MAX_N = 262144      # longest row of the int8 packed forward pass: its int32 sums cannot overflow (include/gpfq.h)
+GPFQ_PACKED_CONV_STAGED_MAX_K = 256  # longest kernel kh * kw * Cin of the staged int8 packed Conv2D forward pass (include/gpfq.h)
 GPFQ_PACKED_DW_MAX_TAPS = 64       # most taps kh * kw of the int8 packed DepthwiseConv2D forward pass (include/gpfq.h)
 GPFQ_POOL_MAX_TAPS = 64            # most taps ph * pw of the int8 route's MaxPooling2D (include/gpfq.h)
 
@@ -82,6 +83,9 @@ SYMBOLS = {
                                                    _vp, _int, _int, _vp, _int, _vp, _i64, _vp, _int, _vp, _vp]),
     "gpfq_packed_conv2d_forward_i8_residual": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
                                                       _vp, _int, _int, _vp, _int, _vp, _i64, _vp, _vp, _int, _vp, _vp]),
+    "gpfq_packed_conv2d_staged_supported": (_int, [_i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int]),
+    "gpfq_packed_conv2d_forward_i8_staged": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
+                                                    _vp, _int, _int, _vp, _int, _vp, _i64, _vp, _int, _vp, _vp]),
     "gpfq_quantize_rows_i8_from_amax": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "gpfq_packed_depthwise_conv2d_forward_i8": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int,
                                                        _int, _vp, _int, _int, _vp, _int, _vp, _vp, _int, _vp, _vp]),
@@ -1608,12 +1612,32 @@ def _i8_image_out(bias, out, shape, device):
     return (bias.data_ptr() if bias is not None else None), out
 
 
+CONV_I8_FORMS = (None, "gather", "staged")      # packed_conv2d_forward_i8(form=): None is "gather"
+
+
+def packed_conv2d_staged_supported(kernel_shape, strides, dilation, padding, H, W, bits):
+    """Whether the staged form of the int8 packed Conv2D forward pass takes a kernel [kh][kw][Cin][F] =
+    kernel_shape on H x W images (gpfq_packed_conv2d_staged_supported: host arithmetic, no device needed)."""
+    kh, kw, Cin = (int(v) for v in kernel_shape[:3])
+    kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
+    return bool(load().gpfq_packed_conv2d_staged_supported(int(H), int(W), Cin, kh, kw, sh, sw, rh, rw, 1 if same else 0, int(bits)))
+
+
 def _packed_conv2d_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias, scales, out, relu,
-                      amax_out, amax, res=None, residual=False):
+                      amax_out, amax, res=None, residual=False, form=None):
     """What packed_conv2d_forward_i8 and packed_conv2d_forward_i8_residual share: the checks, the output, the call."""
+    if form not in CONV_I8_FORMS:
+        raise GpfqError(f"form must be one of {CONV_I8_FORMS}, got {form!r}")
     kh, kw, Cin, F = (int(v) for v in kernel_shape)
     kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
+    ready = scales is not None
     xq, scales, n, H, W, ldq = _i8_images(x_or_xq, (kh, kw, Cin, F), (sh, sw, rh, rw), scales, amax)
+    if form == "staged" and ready and n > 0:
+        # the staged kernel reads aligned 4-byte words: the last image must be readable up to the next multiple of 4 of H W Cin
+        end = xq.storage_offset() + (n - 1) * (xq.stride(0) if n > 1 else 0) + (H * W * Cin + 3) // 4 * 4
+        if end > xq.untyped_storage().nbytes():
+            raise GpfqError(f"form=\"staged\" reads the last image up to byte {end} of xq's storage, which ends at "
+                            f"{xq.untyped_storage().nbytes()}")
     C = _packed_args(packed, bits, zero_code, radii, kh * kw * Cin)
     if C != F:
         raise GpfqError(f"radii has {C} entries, the kernel {F} filters")
@@ -1627,6 +1651,8 @@ def _packed_conv2d_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, 
         if tuple(res.shape) != tuple(out.shape) or not res.is_contiguous() or res.device != out.device:
             raise GpfqError(f"res {tuple(res.shape)} must be a contiguous {tuple(out.shape)} tensor on the output's device")
         entry, back = "gpfq_packed_conv2d_forward_i8_residual", (res.data_ptr(), relu, ap, _stream())
+    elif form == "staged":
+        entry, back = "gpfq_packed_conv2d_forward_i8_staged", (relu, ap, _stream())
     elif fused:
         entry, back = "gpfq_packed_conv2d_forward_i8_fused", (relu, ap, _stream())
     else:
@@ -1637,16 +1663,19 @@ def _packed_conv2d_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, 
 
 
 def packed_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias=None, scales=None,
-                             out=None, relu=False, amax_out=None, amax=None):
+                             out=None, relu=False, amax_out=None, amax=None, form=None):
     """y f32 [n][OH][OW][F] of a Conv2D layer whose kernel [kh][kw][Cin][F] = kernel_shape is held as the packed rows of its matrix
     view [kh*kw*Cin][F], on int8 images and exact int32 sums (gpfq_packed_conv2d_forward_i8; the contract is include/gpfq.h's, bit for
     bit; TensorFlow's geometry).  x_or_xq: float32 NHWC x [n][H][W][Cin], each image quantized here with its own scale
     (quantize_rows_i8 on the flattened images), or -- with `scales` f32 [n] -- ready int8 images [n][H][W][Cin], each contiguous, an
     image pitch (stride(0)) that is a multiple of 16.  M: the size of the layer's unit alphabet, which must be linspace(-1, 1, M).
     out: an optional contiguous [n][OH][OW][F] tensor.  relu / amax_out (a uint32 or int32 [n] tensor, one cell per image) / amax
-    (the maxima of a float x's images): as for packed_dense_forward_i8, through gpfq_packed_conv2d_forward_i8_fused.  No sync."""
+    (the maxima of a float x's images): as for packed_dense_forward_i8, through gpfq_packed_conv2d_forward_i8_fused.
+    form (CONV_I8_FORMS): None and "gather" are that call; "staged" runs gpfq_packed_conv2d_forward_i8_staged (DESIGN.md section
+    11i), the same bits for kernels inside packed_conv2d_staged_supported's range and a GpfqError outside it -- or where a ready
+    xq's storage ends before the next multiple of 4 of H*W*Cin of its last image.  No sync."""
     return _packed_conv2d_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias, scales, out, relu,
-                             amax_out, amax)
+                             amax_out, amax, form=form)
 
 
 def packed_conv2d_forward_i8_residual(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, res, bias=None,

@@ -583,7 +583,8 @@ class PackedConv2D(Conv2D, _FusedI8):
     the Conv2D it decodes to.  ``fused``, ``emit_amax``, ``amax_from``: _FusedI8.  ``residual`` (load_packed(...,
     fuse_residual=True)): the residual join behind this layer that its kernel performs in its epilogue
     (hip.packed_conv2d_forward_i8_residual) where the shortcut can be proved to be its producer's untouched output (``_shortcut``);
-    the layer's output is then the join's."""
+    the layer's output is then the join's.  ``staged`` (load_packed(..., staged_conv=True)): the int8 call
+    asks for the staged kernel form where ``conv_form`` finds the layer inside its range -- the same bits from another kernel."""
 
     ACTIVATIONS = ("float32", "int8")
 
@@ -593,6 +594,7 @@ class PackedConv2D(Conv2D, _FusedI8):
         self.packed = None
         self.activations = "float32"
         self._init_fused()
+        self.staged = False                          # (load_packed(..., staged_conv=True): ask for the staged kernel form)
         self.residual = None                         # (fuse_residual: dict(join=the QuantizingAdd this layer hosts, source=the shortcut's producer))
         self._joined = None                           # (weak reference to y, its version, weak reference to res, its version, maxima or None)
 
@@ -633,6 +635,15 @@ class PackedConv2D(Conv2D, _FusedI8):
         if self.activations not in self.ACTIVATIONS:
             raise ValueError(f"PackedConv2D layer {self.name}: activations must be one of {self.ACTIVATIONS}, got {self.activations!r}")
         return "i8" if self.activations == "int8" else "decode"
+
+    def conv_form(self, input_shape):
+        """The kernel form of an int8 call on inputs [n][H][W][Cin] = input_shape (hip.CONV_I8_FORMS): "staged" where ``staged`` is
+        set and the form takes this layer on such images (hip.packed_conv2d_staged_supported), else "gather"."""
+        from . import hip
+        if self.staged and self.packed is not None and hip.packed_conv2d_staged_supported(
+                self.kernel_shape, self.strides, self.dilation_rate, self.padding, input_shape[1], input_shape[2], self.packed["bits"]):
+            return "staged"
+        return "gather"
 
     def _torch_weight(self):
         return self._kernel().permute(3, 2, 0, 1), 1                        # OIHW, groups
@@ -679,10 +690,11 @@ class PackedConv2D(Conv2D, _FusedI8):
             self._remember(y, None, 0)
             return y
         amax_out = self._amax_out(n, x.device)
+        form = self.conv_form(tuple(x.shape))
         x, given = self._i8_input(x)
         y = hip.packed_conv2d_forward_i8(x, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]), self.kernel_shape,
                                          self.strides, self.dilation_rate, self.padding, bias=bias, relu=relu, amax_out=amax_out,
-                                         **given)
+                                         form=form, **given)
         self._remember(y, amax_out, y[0].numel() if n else 0)
         return rest(y)
 

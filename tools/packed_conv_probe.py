@@ -27,6 +27,14 @@ one graph) -> the Conv2D part of profiles/packed_chain.txt.  Producer -> consume
 at 56^2, 28^2, 14^2 and 7^2, a VGG-style conv(relu) -> conv pair, the CIFAR10 CNN's conv(relu) -> BN -> conv -- loaded with
 fuse=False and fuse=True and timed in alternation at 1, 8 and 32 images; the unfused network, captured twice, is the yardstick.
 
+--staged: the staged kernel form of DESIGN.md section 11i -> profiles/packed_conv_i8_staged.txt.  The stem layers it was built for --
+ResNet50's conv1, VGG16's conv1_1, a MobileNet stem, the CIFAR10 CNN's conv1 -- and two Cin % 16 == 0 shapes, which run the untouched
+gather unit either way; quantization and kernel together as in the layer table.  Four graphs alternate in one session: the gather
+form, the staged form (keras_shim.PackedConv2D.staged), F.conv2d on the resident float kernel, the gather form again -- so the file
+shows what the yardstick's own repeated runs differ by.  --parent-lib PATH takes the gather form from a libgpfq_hip.so built from the
+parent commit (its two graphs are captured with that library in place of this tree's); without it the gather form is this tree's,
+whose unit is the parent's source.  The staged and gather outputs are compared bit for bit.
+
 --ways i8,float: only these of the three ways (the layer table of profiles/packed_conv_i8_split.txt leaves decode out).
 --tree PATH: take the package (and its built library) from another checkout of this repository, e.g. the parent commit built in a
 scratch worktree: the same probe, alternating between two trees, is how a change to the layer call is measured.
@@ -36,8 +44,11 @@ scratch worktree: the same probe, alternating between two trees, is how a change
     python tools/packed_conv_probe.py --quantizer --out quantizer.txt
     python tools/packed_conv_probe.py --ways i8,float [--tree ../parent] --out layers.txt
     python tools/packed_conv_probe.py --pairs --out chain_conv.txt
+    python tools/packed_conv_probe.py --staged [--parent-lib ../parent/libgpfq_hip.so] --out profiles/packed_conv_i8_staged.txt
 """
 import argparse
+import contextlib
+import ctypes
 import os
 import sys
 
@@ -74,6 +85,8 @@ SHAPES = [
     ("cnn conv5 8^2 64 -> 128", 8, 64, 128, 3, 1),
     ("cnn conv6 8^2 128 -> 128", 8, 128, 128, 3, 1),
 ]
+STAGED_SHAPES = [SHAPES[6], ("vgg16 conv1_1 3x3 224^2 x 3 -> 64", 224, 3, 64, 3, 1), ("mobilenet stem 3x3/2 224^2 x 3 -> 32", 224, 3, 32, 3, 2),
+                 SHAPES[7], SHAPES[0], SHAPES[8]]
 PHASE_SHAPES = [SHAPES[0], SHAPES[3], SHAPES[4], SHAPES[6]]
 IMAGES = (1, 8, 32)
 WAYS = ("i8", "float", "decode")
@@ -209,6 +222,64 @@ def quantizer(args, dev, out):
         f"batch -> QUANTIZE_SPLIT_MIN_N = {first if first is not None else '2**62 (none: the default never splits)'}")
 
 
+@contextlib.contextmanager
+def library(lib):
+    """The binding's calls go to `lib` inside the block (None: they stay where they are)."""
+    hip.load()
+    own = hip._lib
+    if lib is not None:
+        hip._lib = lib
+    try:
+        yield
+    finally:
+        hip._lib = own
+
+
+def parent_library(path):
+    """A libgpfq_hip.so of another commit, with the argument types of the entries it has."""
+    lib = ctypes.CDLL(os.path.abspath(path))
+    for name, (res, argtypes) in hip.SYMBOLS.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, argtypes
+    return lib
+
+
+def staged(args, dev, out):
+    parent = parent_library(args.parent_lib) if args.parent_lib else None
+    out(f"# {torch.cuda.get_device_name(dev)}; device time per layer call (image quantization + kernel; F.conv2d for float): {args.chain} calls "
+        f"captured into one graph, {args.replays} timed replays per graph, four graphs alternating (gather, staged, float, gather again); "
+        f"median (min .. max); us; the gather form from {'the library of --parent-lib' if parent else 'this tree (the unit is untouched)'}")
+    for shape in (STAGED_SHAPES[:1] + STAGED_SHAPES[4:5] if args.quick else STAGED_SHAPES):
+        label, H, Cin, F, k, stride = shape
+        for M in (3, 16):
+            rng = np.random.default_rng(H + Cin + M)
+            (l_gather, l_float, l_staged), packed, bias = layers_of(rng, H, Cin, F, k, stride, M, dev)
+            l_staged.activations, l_staged.staged = "int8", True
+            form = l_staged.conv_form((1, H, H, Cin))
+            out(f"{label}, M={M} ({packed['bits']}-bit codes): K={k * k * Cin}; the staged layer runs form={form!r}")
+            out("    images   gather us, median (min .. max)        staged us                             float conv us                         "
+                "gather again us                       staged/gather   staged/float")
+            for n in IMAGES:
+                x = torch.relu(torch.randn((n, H, H, Cin), device=dev))
+                ys = {}
+
+                def way(w, layer):
+                    def fn():
+                        ys[w] = layer.call(x)
+                    return fn
+
+                with torch.no_grad():
+                    with library(parent):
+                        g0, g3 = capture(way("gather", l_gather), args.chain), capture(way("again", l_gather), args.chain)
+                    g1, g2 = capture(way("staged", l_staged), args.chain), capture(way("float", l_float), args.chain)
+                    res = timed([g0, g1, g2, g3], args.replays)
+                assert torch.equal(ys["gather"].view(torch.int32), ys["staged"].view(torch.int32))      # the same bits
+                out(f"    {n:6d}   " + "".join(f"{fmt(t, args.chain)}          " for t in res) +
+                    f"{res[1][0] / min(res[0][0], res[3][0]):6.2f}          {res[1][0] / res[2][0]:6.2f}")
+                del g0, g1, g2, g3
+
+
 def phases(args, dev, out):
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
     out(f"# library {os.path.relpath(hip.lib_path(), root)} (GPFQ_DIAG={os.environ.get('GPFQ_DIAG', '')!r}); 8 images; us per call, median (min .. max)")
@@ -245,6 +316,8 @@ def main():
     ap.add_argument("--phases", action="store_true", help="the int8 kernel and the image quantization alone (see the module's text)")
     ap.add_argument("--quantizer", action="store_true", help="the image quantization alone, form=\"row\" against form=\"split\"")
     ap.add_argument("--pairs", action="store_true", help="producer -> consumer links, fuse=False against fuse=True (see the module's text)")
+    ap.add_argument("--staged", action="store_true", help="the staged kernel form against the gather form and the float path")
+    ap.add_argument("--parent-lib", default=None, help="--staged: a libgpfq_hip.so built from the parent commit, for the gather form")
     ap.add_argument("--ways", default=",".join(WAYS), help="which of i8,float,decode the layer table times (i8 always)")
     ap.add_argument("--tree", default=None, help="another checkout of this repository to take the package and its library from")
     args = ap.parse_args()
@@ -266,6 +339,9 @@ def main():
         return
     if args.quantizer:
         quantizer(args, dev, out)
+        return
+    if args.staged:
+        staged(args, dev, out)
         return
     if args.pairs:
         import packed_chain_pairs as pairs
