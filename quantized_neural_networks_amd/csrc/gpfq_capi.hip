@@ -1010,11 +1010,21 @@ static gpfq::ConvI8Shape conv_i8_shape(int64_t H, int64_t W, int64_t Cin, int kh
     return S;
 }
 
-// the three int8 Conv2D entries, as packed_dense_i8_entry; residual: the fused entry with the shortcut `res` of a residual join
+// where the code-out entry stores in place of y: the maxima it quantizes under, the codes, the scales
+struct ConvCodesOut {
+    const uint32_t *amax_bits;
+    int8_t *yq;
+    int64_t ldyq;
+    float *scales;
+};
+
+// the int8 Conv2D entries, as packed_dense_i8_entry; residual: the fused entry with the shortcut `res` of a residual join; codes: the
+// fused entry with codes and scales in place of y (y and amax_bits NULL)
 static int packed_conv_i8_entry(const char *name, bool fused, bool residual, bool staged, const float *res, const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
                                 int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
                                 const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
-                                const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits, void *stream)
+                                const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits, void *stream,
+                                const ConvCodesOut *codes = nullptr)
 {
     if (relu != 0 && relu != 1) return fail(GPFQ_ERR_INVALID_ARG, "relu=%d: must be 0 or 1", relu);
     if (n < 0 || F < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size n=%lld F=%lld", (long long)n, (long long)F);
@@ -1039,8 +1049,18 @@ static int packed_conv_i8_entry(const char *name, bool fused, bool residual, boo
             hipError_t e = gpfq::launch_amax_clear(amax_bits, n, static_cast<hipStream_t>(stream));
             if (e != hipSuccess) return hip_fail(e, name);
         }
+        if (codes && n > 0) {                       // the composition's second half on rows of no column: the scales alone
+            if (!codes->amax_bits || !codes->scales) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+            if (n > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "too many images for one launch");
+            hipError_t e = gpfq::launch_quantize_rows_i8_from_amax(nullptr, n, 0, 0, codes->amax_bits, codes->yq, codes->ldyq, codes->scales,
+                                                                   static_cast<hipStream_t>(stream));
+            if (e != hipSuccess) return hip_fail(e, name);
+        }
         return GPFQ_OK;
     }
+    if (codes && !gpfq::packed_conv_i8_codes_fits(Cin, F))
+        return fail(GPFQ_ERR_UNSUPPORTED, "the code-out form takes Cin=%lld and F=%lld that are multiples of 16 "
+                    "(gpfq_packed_conv2d_codes_supported)", (long long)Cin, (long long)F);
     if (staged && !gpfq::packed_conv_i8_staged_fits(Cin, kh, kw, sh, sw, rh, rw))
         return fail(GPFQ_ERR_UNSUPPORTED, "the staged form takes kh*kw*Cin=%lld <= GPFQ_PACKED_CONV_STAGED_MAX_K=%d and a window of "
                     "(3*sh+(kh-1)*rh+1)*(15*sw+(kw-1)*rw+1)*Cin <= 32768 bytes (gpfq_packed_conv2d_staged_supported)", (long long)K,
@@ -1053,10 +1073,22 @@ static int packed_conv_i8_entry(const char *name, bool fused, bool residual, boo
     const int64_t ftiles = (F + 15) / 16, pblocks = (n * oh * ow + 63) / 64;
     if (ftiles > 2147483647LL / pblocks) return fail(GPFQ_ERR_UNSUPPORTED, "layer too wide for one launch");
     if (ldq < H * W * Cin) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld < H*W*Cin=%lld", (long long)ldq, (long long)(H * W * Cin));
-    if (!xq || !scales || !packed || !radii || !y) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (!xq || !scales || !packed || !radii || (!y && !codes)) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "packed must be 16-byte aligned");
     const gpfq::ConvI8Shape S = conv_i8_shape(H, W, Cin, kh, kw, sh, sw, rh, rw, same_padding, oh, ow);
+    if (codes) {
+        if (codes->ldyq % 16 != 0 || codes->ldyq < oh * ow * F)
+            return fail(GPFQ_ERR_INVALID_ARG, "code pitch ldyq=%lld must be a multiple of 16 and at least OH*OW*F=%lld", (long long)codes->ldyq,
+                        (long long)(oh * ow * F));
+        if (!codes->amax_bits || !codes->yq || !codes->scales) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+        if (reinterpret_cast<uintptr_t>(codes->yq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "yq must be 16-byte aligned");
+        if (gpfq::packed_conv_i8_codes_blocks(n, S, F) > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "layer too wide for one launch");
+        hipError_t e = gpfq::launch_packed_conv2d_forward_i8_codes(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias, F, relu,
+                                                                   codes->amax_bits, codes->yq, codes->ldyq, codes->scales,
+                                                                   static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
+    }
     if (residual) {
         if (!res) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
         const uintptr_t bytes = (uintptr_t)(n * oh * ow * F) * sizeof(float), yb = reinterpret_cast<uintptr_t>(y),
@@ -1105,6 +1137,26 @@ int gpfq_packed_conv2d_forward_i8_residual(const int8_t *xq, int64_t n, int64_t 
 {
     return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_residual", true, true, false, res, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw,
                                 rh, rw, same_padding, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
+}
+
+int gpfq_packed_conv2d_codes_supported(int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw, int same_padding,
+                                       int64_t F, int bits)
+{
+    (void)same_padding;                             // (the pads move the taps, not the form's range)
+    if (H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || rh <= 0 || rw <= 0 || (bits != 2 && bits != 4 && bits != 8)) return 0;
+    if (Cin > GPFQ_PACKED_I8_MAX_N || (int64_t)kh * kw > GPFQ_PACKED_I8_MAX_N || (int64_t)kh * kw * Cin > GPFQ_PACKED_I8_MAX_N) return 0;
+    return gpfq::packed_conv_i8_codes_fits(Cin, F) ? 1 : 0;
+}
+
+int gpfq_packed_conv2d_forward_i8_codes(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                        int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw,
+                                        int same_padding, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                        const float *bias, int64_t F, int relu, const uint32_t *out_amax_bits, int8_t *yq, int64_t ldyq,
+                                        float *out_scales, void *stream)
+{
+    const ConvCodesOut codes{out_amax_bits, yq, ldyq, out_scales};
+    return packed_conv_i8_entry("gpfq_packed_conv2d_forward_i8_codes", true, false, false, nullptr, xq, n, ldq, scales, H, W, Cin, kh, kw, sh, sw,
+                                rh, rw, same_padding, packed, bits, zero_code, radii, M, bias, F, nullptr, relu, nullptr, stream, &codes);
 }
 
 int gpfq_packed_conv2d_staged_supported(int64_t H, int64_t W, int64_t Cin, int kh, int kw, int sh, int sw, int rh, int rw,

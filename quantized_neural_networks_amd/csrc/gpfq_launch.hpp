@@ -395,6 +395,16 @@ hipError_t launch_packed_conv2d_forward_i8_staged(const int8_t *xq, int64_t n, i
                                                   const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                                   const float *bias, int64_t F, float *y, int relu, uint32_t *amax_bits,
                                                   hipStream_t stream);
+// gpfq_packed_conv_i8_codes.hip: the same pass for Cin and F multiples of 16 that stores, in place of y, the
+// int8 codes launch_quantize_rows_i8_from_amax would make of the fused launcher's y under out_amax_bits (only read), and out_scales:
+// one launch, no atomics.  packed_conv_i8_codes_fits: the form's range (host arithmetic); packed_conv_i8_codes_blocks: the
+// workgroups of the launch, for the entry's check.
+bool packed_conv_i8_codes_fits(int64_t Cin, int64_t F);
+int64_t packed_conv_i8_codes_blocks(int64_t n, const ConvI8Shape &S, int64_t F);
+hipError_t launch_packed_conv2d_forward_i8_codes(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
+                                                 const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
+                                                 const float *bias, int64_t F, int relu, const uint32_t *out_amax_bits, int8_t *yq,
+                                                 int64_t ldyq, float *out_scales, hipStream_t stream);
 // gpfq_packed_dw_i8.hip: the DepthwiseConv2D forward pass of the same images with the kernel
 // [kh*kw][Cin*mult] held as packed rows, on the packed int8 dot product.  S as above (S.Cin: the input channels); relu / amax_bits as
 // the fused launchers take them, with relu = 0 and amax_bits = NULL giving the kernel without the fused epilogue.

@@ -467,8 +467,42 @@ def _apply_fusion(net, packed_at, pools=False, adds=False, avgpools=False, resid
     return net
 
 
+def _code_producers(net):
+    """The PackedConv2D layers of a fused network that can hand their output on as int8 codes, by name: the
+    LINK entries of net.fusion_plan whose producer is a PackedConv2D with no pool in between and no residual join in its epilogue,
+    and whose output images are a multiple of 16 values long (the pitch of the consumer's int8 images)."""
+    by_name = {l.name: l for l in net.layers}
+    out = {}
+    for e in getattr(net, "fusion_plan", None) or []:
+        layer = by_name.get(e["layer"])
+        if (isinstance(layer, keras_shim.PackedConv2D) and isinstance(e["hands_to"], str) and e.get("pool") is None
+                and e.get("residual") is None and int(np.prod(layer.output_shape[1:])) % 16 == 0):
+            out[layer.name] = layer
+    return out
+
+
+def calibrate_code_amax(net, batches):
+    """{producer name: float} for load_packed(..., fuse=True, code_amax=...): for every PackedConv2D of ``net`` (loaded with fuse=True)
+    that can hand its output on as codes (LINK entries of net.fusion_plan with a PackedConv2D producer and no pool), the largest
+    finite maximum of |output| over all images of all ``batches`` (each an input batch of the network).  The maxima are the cells
+    the fused kernels leave for the next layer's quantizer anyway; they are read back once per batch."""
+    producers = _code_producers(net)
+    top = {name: 0 for name in producers}
+    for batch in batches:
+        net.predict_on_batch(batch)
+        cells = {name: l._handoff[2] for name, l in producers.items() if l._handoff is not None}
+        if not cells:
+            continue
+        host = torch.stack(list(cells.values())).cpu().numpy().view(np.uint32)          # the one read of the batch
+        for name, row in zip(cells, host):
+            finite = row[row < 0x7f800000]
+            if finite.size:
+                top[name] = max(top[name], int(finite.max()))
+    return {name: float(np.array([bits], dtype=np.uint32).view(np.float32)[0]) for name, bits in top.items()}
+
+
 def load_packed(path, device=None, activations="float32", packed_conv=False, fuse=False, packed_depthwise=False, fuse_pool=False,
-                fuse_add=False, fuse_avgpool=False, fuse_residual=False, staged_conv=False):
+                fuse_add=False, fuse_avgpool=False, fuse_residual=False, staged_conv=False, code_amax=None):
     """Inverse of export_packed: a keras_shim network on ``device`` (default: the current GPU).  Dense layers that were exported
     packed come back as keras_shim.PackedDense (codes, radii and bias in device memory; the float kernel is never formed unless
     get_weights() or a batch beyond keras_shim.PACKED_TILED_MAX_BATCH asks for it); packed Conv2D / DepthwiseConv2D kernels are
@@ -526,7 +560,17 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
     staged_conv=True (needs activations="int8" and packed_conv=True): every PackedConv2D whose Cin is not a
     multiple of 16 -- the stem layers, which the gather kernel serves byte by byte -- has ``staged`` set and runs the staged kernel
     form where its shape is inside that form's range (keras_shim.PackedConv2D.conv_form).  The plan of fuse=True and the other
-    switches is untouched, and every value is bit for bit what staged_conv=False computes."""
+    switches is untouched, and every value is bit for bit what staged_conv=False computes.
+
+    code_amax={producer name: maximum} (needs fuse=True): calibrated activation ranges.  Every named layer
+    must be a PackedConv2D that the plan links to a packed consumer with no pool in between (calibrate_code_amax lists them and
+    measures their maxima; any other name raises ValueError).  Such a layer stores no float32 output: one kernel
+    (hip.packed_conv2d_forward_i8_codes) writes the int8 codes of its output under the given maximum -- values beyond it clamp to
+    +-127 -- and the value at its position is that int8 tensor, which the consumer takes as its input codes under the proof of
+    _FusedI8.  The plan is untouched; the default None changes nothing.  The result is bit for bit what fuse=True alone computes
+    when each such link's quantizer is handed the same maximum."""
+    if code_amax is not None and not fuse:
+        raise ValueError("code_amax sets the range a fused int8 convolution quantizes its own output under: it needs fuse=True")
     if staged_conv and not (activations == "int8" and packed_conv):
         raise ValueError("staged_conv=True chooses the kernel form of the int8 packed Conv2D layers: it needs activations=\"int8\" and packed_conv=True")
     if fuse_residual and not (fuse and fuse_add):
@@ -605,4 +649,17 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
                     layer.set_weights([unpack_kernel(packed)] + rest)
             elif layer._weights:
                 layer.set_weights([z[f"w{k}_{j}"] for j in range(len(layer._weights))])
-    return _apply_fusion(net, fused_at, fuse_pool, fuse_add, fuse_avgpool, fuse_residual) if fuse else net
+    if not fuse:
+        return net
+    net = _apply_fusion(net, fused_at, fuse_pool, fuse_add, fuse_avgpool, fuse_residual)
+    if code_amax:
+        producers = _code_producers(net)
+        consumer = {e["layer"]: e["hands_to"] for e in net.fusion_plan}
+        by_name = {l.name: l for l in net.layers}
+        for name, value in code_amax.items():
+            if name not in producers:
+                raise ValueError(f"code_amax names {name!r}, which is not a PackedConv2D that hands its output to a packed layer with "
+                                 f"no pool in between (calibrate_code_amax lists those: {sorted(producers)})")
+            producers[name].code_amax = float(value)
+            by_name[consumer[name]].codes_from = producers[name]
+    return net

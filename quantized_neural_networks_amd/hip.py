@@ -86,6 +86,9 @@ SYMBOLS = {
     "gpfq_packed_conv2d_staged_supported": (_int, [_i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int]),
     "gpfq_packed_conv2d_forward_i8_staged": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
                                                     _vp, _int, _int, _vp, _int, _vp, _i64, _vp, _int, _vp, _vp]),
+    "gpfq_packed_conv2d_codes_supported": (_int, [_i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _i64, _int]),
+    "gpfq_packed_conv2d_forward_i8_codes": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int,
+                                                   _vp, _int, _int, _vp, _int, _vp, _i64, _int, _vp, _vp, _i64, _vp, _vp]),
     "gpfq_quantize_rows_i8_from_amax": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "gpfq_packed_depthwise_conv2d_forward_i8": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int,
                                                        _int, _vp, _int, _int, _vp, _int, _vp, _vp, _int, _vp, _vp]),
@@ -1687,6 +1690,66 @@ def packed_conv2d_forward_i8_residual(x_or_xq, packed, bits, zero_code, radii, M
     bit what that call followed by add_forward_i8(y, res, relu) leaves, in one launch less and without the passes over y.  No sync."""
     return _packed_conv2d_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias, scales, out, relu,
                              amax_out, amax, res=res, residual=True)
+
+
+def packed_conv2d_codes_supported(kernel_shape, strides, dilation, padding, H, W, bits):
+    """Whether the code-out form of the int8 packed Conv2D forward pass takes a kernel [kh][kw][Cin][F] =
+    kernel_shape on H x W images: Cin and F multiples of 16 (gpfq_packed_conv2d_codes_supported: host arithmetic, no device needed)."""
+    kh, kw, Cin, F = (int(v) for v in kernel_shape)
+    kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
+    return bool(load().gpfq_packed_conv2d_codes_supported(int(H), int(W), Cin, kh, kw, sh, sw, rh, rw, 1 if same else 0, F, int(bits)))
+
+
+def _code_amax_cells(out_amax, n, device):
+    """out_amax of packed_conv2d_forward_i8_codes -> the images' cells, int32 or uint32 [n] on the device: the bit patterns."""
+    if isinstance(out_amax, torch.Tensor):
+        if out_amax.dtype == torch.float32:
+            out_amax = _dev(out_amax, torch.float32, "out_amax").contiguous().view(torch.int32)
+        _amax_cells(out_amax, n, "out_amax")
+        return out_amax
+    return torch.full((n,), float(out_amax), dtype=torch.float32, device=device).view(torch.int32)
+
+
+def packed_conv2d_forward_i8_codes(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, out_amax, bias=None,
+                                   relu=False, scales=None, amax=None):
+    """(yq i8 [n][OH][OW][F], out_scales f32 [n]) of a packed Conv2D layer on the int8 route: the int8 codes and scales of its output
+    under the maxima out_amax -- what packed_conv2d_forward_i8(..., relu=relu) followed by quantize_rows_i8(y, amax=out_amax) leaves,
+    bit for bit, from ONE launch that never stores the float32 y (gpfq_packed_conv2d_forward_i8_codes; the contract is
+    include/gpfq.h's).  out_amax: a float (one maximum for every image), or a float32 tensor [n] of maxima, or
+    an int32 / uint32 tensor [n] of their bit patterns; values of the output beyond it are clamped to +-127.  The other arguments as
+    for packed_conv2d_forward_i8.  Where packed_conv2d_codes_supported is false (Cin or F not a multiple of 16) the two calls named
+    above run into a temporary y: the same bits.  yq's images are contiguous and its image pitch is a multiple of 16: it is what the
+    next layer's binding takes as a ready xq together with out_scales.  No sync."""
+    kh, kw, Cin, F = (int(v) for v in kernel_shape)
+    kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
+    xq, scales, n, H, W, ldq = _i8_images(x_or_xq, (kh, kw, Cin, F), (sh, sw, rh, rw), scales, amax)
+    cells = _code_amax_cells(out_amax, n, xq.device)
+    OH, OW = patch_out_dim(H, kh, sh, rh, same), patch_out_dim(W, kw, sw, rw, same)
+    per = OH * OW * F
+    if not packed_conv2d_codes_supported((kh, kw, Cin, F), (sh, sw), (rh, rw), padding, H, W, bits):
+        if xq.dim() == 2:                               # (float images quantized above: rows of roundup16(H W Cin) bytes)
+            xq = xq[:, :H * W * Cin].unflatten(1, (H, W, Cin))
+        y = packed_conv2d_forward_i8(xq, packed, bits, zero_code, radii, M, (kh, kw, Cin, F), (sh, sw), (rh, rw), padding, bias=bias,
+                                     scales=scales, relu=relu)
+        yq, out_scales = quantize_rows_i8(y.reshape(n, per), amax=cells)
+        return yq[:, :per].unflatten(1, (OH, OW, F)), out_scales
+    C = _packed_args(packed, bits, zero_code, radii, kh * kw * Cin)
+    if C != F:
+        raise GpfqError(f"radii has {C} entries, the kernel {F} filters")
+    if relu not in (False, True, 0, 1):
+        raise GpfqError(f"relu must be a bool, got {relu!r}")
+    if bias is not None:
+        _dev(bias, torch.float32, "bias")
+        if bias.numel() != F or not bias.is_contiguous():
+            raise GpfqError(f"bias must be a contiguous [{F}] tensor")
+    yq = torch.empty((n, OH, OW, F), dtype=torch.int8, device=xq.device)
+    out_scales = torch.empty(n, dtype=torch.float32, device=xq.device)
+    with torch.cuda.device(xq.device):
+        _check(load().gpfq_packed_conv2d_forward_i8_codes(
+            xq.data_ptr(), n, ldq, scales.data_ptr(), H, W, Cin, kh, kw, sh, sw, rh, rw, 1 if same else 0, packed.data_ptr(), int(bits),
+            int(zero_code), radii.data_ptr(), int(M), bias.data_ptr() if bias is not None else None, F, int(bool(relu)), cells.data_ptr(),
+            yq.data_ptr(), max(per, 16), out_scales.data_ptr(), _stream()), "gpfq_packed_conv2d_forward_i8_codes")
+    return yq, out_scales
 
 
 def packed_depthwise_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, bias=None,

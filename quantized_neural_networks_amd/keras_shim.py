@@ -324,10 +324,10 @@ PACKED_FORWARD_MAX_BATCH = 4
 PACKED_TILED_MAX_BATCH = 128
 
 
-def _untouched(x, y, version):
-    """x is the tensor y (None: gone) as its producer wrote it at `version`: contiguous float32 over the same storage at the same
-    offset with the same element count, and no in-place operation since."""
-    return (y is not None and x.dtype == torch.float32 and x.is_contiguous() and x.device == y.device
+def _untouched(x, y, version, dtype=torch.float32):
+    """x is the tensor y (None: gone) as its producer wrote it at `version`: contiguous float32 (`dtype`) over the same storage at the
+    same offset with the same element count, and no in-place operation since."""
+    return (y is not None and x.dtype == dtype and y.dtype == dtype and x.is_contiguous() and x.device == y.device
             and x.untyped_storage().data_ptr() == y.untyped_storage().data_ptr() and x.storage_offset() == y.storage_offset()
             and x.numel() == y.numel() and x._version == version and y._version == version)
 
@@ -386,8 +386,15 @@ class _FusedI8:
     def _taken_codes(self, x, rows, row_len):
         """(xq, scales) of the rows of x as the QuantizingMaxPooling2D or QuantizingAdd in front left them, or None (quantize here):
         ``_taken_maxima``'s proof against that layer's remembered output.  Flatten's reshape is a view -- the same storage, offset, element count and
-        version counter -- so the proof holds through it."""
+        version counter -- so the proof holds through it.  An int8 x is the code tensor of a PackedConv2D with ``code_amax`` (DESIGN.md
+        section 11j): the same proof against that producer's remembered codes, the dtype being int8 on both sides -- and where it
+        fails a TypeError, since bytes that are not provably the producer's codes have no scales and are never reinterpreted."""
         hand = getattr(self.codes_from, "_codes", None) if self.codes_from is not None else None
+        if x.dtype == torch.int8:
+            if hand is None or not _untouched(x, hand[0](), hand[1], torch.int8) or rows != hand[3].numel() or row_len != hand[4]:
+                raise TypeError(f"layer {self.name} was handed an int8 tensor that is not the untouched code output of the layer in "
+                                f"front of it (PackedConv2D.code_amax): int8 inputs are taken as codes under that proof alone")
+            return hand[2], hand[3]
         if hand is None:
             return None
         ref, version, xq, scales, per_row = hand
@@ -584,7 +591,10 @@ class PackedConv2D(Conv2D, _FusedI8):
     fuse_residual=True)): the residual join behind this layer that its kernel performs in its epilogue
     (hip.packed_conv2d_forward_i8_residual) where the shortcut can be proved to be its producer's untouched output (``_shortcut``);
     the layer's output is then the join's.  ``staged`` (load_packed(..., staged_conv=True)): the int8 call
-    asks for the staged kernel form where ``conv_form`` finds the layer inside its range -- the same bits from another kernel."""
+    asks for the staged kernel form where ``conv_form`` finds the layer inside its range -- the same bits from another kernel.
+    ``code_amax`` (load_packed(..., fuse=True, code_amax=...)): a calibrated maximum of this layer's output.
+    When set on a layer that hands its output to a packed layer, the int8 call is hip.packed_conv2d_forward_i8_codes and RETURNS THE
+    INT8 CODES of the output under that maximum; ``_codes`` remembers them with their scales for the consumer's proof."""
 
     ACTIVATIONS = ("float32", "int8")
 
@@ -594,6 +604,8 @@ class PackedConv2D(Conv2D, _FusedI8):
         self.packed = None
         self.activations = "float32"
         self._init_fused()
+        self.code_amax = None                        # (load_packed(..., code_amax=...): the maximum this layer's output is quantized under)
+        self._codes = None                            # (weak reference to the int8 output, its version, xq, scales, codes per image)
         self.staged = False                          # (load_packed(..., staged_conv=True): ask for the staged kernel form)
         self.residual = None                         # (fuse_residual: dict(join=the QuantizingAdd this layer hosts, source=the shortcut's producer))
         self._joined = None                           # (weak reference to y, its version, weak reference to res, its version, maxima or None)
@@ -689,6 +701,17 @@ class PackedConv2D(Conv2D, _FusedI8):
             self._joined = (weakref.ref(y), y._version, weakref.ref(res), res._version, cells)
             self._remember(y, None, 0)
             return y
+        self._codes = None
+        if self.code_amax is not None and self.emit_amax and n > 0:
+            # the hand-over in codes: the int8 tensor is this layer's output, and the consumer's whole input
+            x, given = self._i8_input(x)
+            yq, out_scales = hip.packed_conv2d_forward_i8_codes(x, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]),
+                                                                self.kernel_shape, self.strides, self.dilation_rate, self.padding,
+                                                                float(self.code_amax), bias=bias, relu=relu, **given)
+            per = yq[0].numel()
+            self._codes = (weakref.ref(yq), yq._version, yq.reshape(n, per), out_scales, per)
+            self._handoff = self._out = None
+            return yq
         amax_out = self._amax_out(n, x.device)
         form = self.conv_form(tuple(x.shape))
         x, given = self._i8_input(x)
