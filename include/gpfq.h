@@ -721,6 +721,48 @@ int gpfq_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t
                                             void *stream);
 
 /*
+ * gpfq_packed_depthwise_conv2d_forward_i8_codes: the DepthwiseConv2D pass that stores the NEXT layer's int8 codes, under maxima the
+ * caller supplies (calibrated activation ranges), in place of float32 y.  Opt-in; bit for bit.  The arguments
+ * of gpfq_packed_depthwise_conv2d_forward_i8 up to bias, then relu, then out_amax_bits, yq, ldyq, out_scales exactly as
+ * gpfq_packed_conv2d_forward_i8_codes takes them, with C = Cin * mult in the place of F:
+ *   out_amax_bits [device] u32 [n], only read: per image the bit pattern of the maximum to quantize under;
+ *   yq            [device] i8: the codes of image i at yq + i * ldyq, NHWC [OH][OW][C]; 16-byte aligned;
+ *   ldyq          a multiple of 16 and at least OH*OW*C; bytes of a row at or beyond OH*OW*C are not written;
+ *   out_scales    [device] f32 [n].
+ * Contract: yq and out_scales are exactly what this composition leaves in them,
+ *   1. gpfq_packed_depthwise_conv2d_forward_i8(xq .. bias, y, relu, amax_bits = NULL) into a float32 y [n][OH][OW][C];
+ *   2. gpfq_quantize_rows_i8_from_amax(y, B = n, ldx = N = OH*OW*C, out_amax_bits, yq, ldyq, out_scales),
+ * and no float32 y exists anywhere.  Spelled out per image i, a = out_amax_bits[i]:
+ *   a >= 0x7f800000:                        out_scales[i] = NaN,  every code of the image 0;
+ *   else amax = float-of-bits(a) < 2^-100:  out_scales[i] = 0.0f, every code of the image 0;
+ *   else inv = 127.0f / amax, out_scales[i] = amax / 127.0f (float32 divisions, correctly rounded) and
+ *        yq[i][oh][ow][j] = (int8) clamp(rintf(v * inv), -127, 127), one float32 product rounded half to even, on the float32
+ *        v = (relu && u < 0) ? +0.0f : u,  u = (float)p + bias[j] ((float)p without a bias),
+ *        p = ((double)acc * (double)scales[i]) * (radii[j] / (double)(M - 1)), acc the exact int32 sum of the depthwise entry.
+ *   So the clamp acts on values beyond amax (an infinite v gives +-127), and a NaN v under a finite maximum -- an image whose input
+ *   scale is NaN -- gives 0.  Image i of yq and out_scales[i] depend on image i of xq, scales[i] and out_amax_bits[i] alone, not on
+ *   n; every call gives the same bits.
+ * ONE launch, asynchronous on `stream`: no atomics, no workspace, no scratch, no host synchronisation; it can be captured into a
+ * graph.  Exactly one lane per image writes out_scales[i].  out_amax_bits, yq and out_scales must not overlap each other or any input.
+ * Range: mult == 1, Cin a multiple of 16 and kh*kw <= GPFQ_PACKED_DW_MAX_TAPS; any stride, rate and padding.
+ * gpfq_packed_depthwise_codes_supported says 1 / 0 for a shape (host arithmetic only, callable without a device; 0 also for bits
+ * other than 2, 4, 8 or a size that is not positive); outside the range the entry returns GPFQ_ERR_UNSUPPORTED, behind the empty
+ * cases and before any launch.
+ * Argument checks, status codes and empty cases are the depthwise entry's (y not being an argument).  In addition
+ * GPFQ_ERR_INVALID_ARG for ldyq not a multiple of 16 or below OH*OW*C, yq not 16-byte aligned, a NULL out_amax_bits, yq or
+ * out_scales, checked where the other pointers are.  The empty cases (n = 0, OH or OW = 0) return GPFQ_OK; with n > 0 the
+ * composition's second step still writes out_scales by the rule above (rows of no column: one launch, nothing of yq written), which
+ * needs out_amax_bits and out_scales not NULL.
+ */
+int gpfq_packed_depthwise_codes_supported(int64_t H, int64_t W, int64_t Cin, int64_t mult, int kh, int kw, int sh, int sw, int rh, int rw,
+                                          int same_padding, int bits);
+int gpfq_packed_depthwise_conv2d_forward_i8_codes(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                                  int64_t H, int64_t W, int64_t Cin, int64_t mult, int kh, int kw, int sh, int sw, int rh,
+                                                  int rw, int same_padding, const uint8_t *packed, int bits, int zero_code,
+                                                  const double *radii, int M, const float *bias, int relu,
+                                                  const uint32_t *out_amax_bits, int8_t *yq, int64_t ldyq, float *out_scales, void *stream);
+
+/*
  * MaxPooling2D on the same route: the pooled float32 images and, in the same pass, what the next packed
  * layer's quantizer needs of them.  Opt-in; bit for bit:
  *

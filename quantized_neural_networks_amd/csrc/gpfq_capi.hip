@@ -1176,14 +1176,14 @@ int gpfq_packed_conv2d_forward_i8_staged(const int8_t *xq, int64_t n, int64_t ld
                                 sh, sw, rh, rw, same_padding, packed, bits, zero_code, radii, M, bias, F, y, relu, amax_bits, stream);
 }
 
-// the int8 DepthwiseConv2D entry: packed_conv_i8_entry's checks in its order, with F = Cin * mult and the row length kh * kw
-int gpfq_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
-                                            int64_t H, int64_t W, int64_t Cin, int64_t mult, int kh, int kw, int sh, int sw, int rh,
-                                            int rw, int same_padding, const uint8_t *packed, int bits, int zero_code,
-                                            const double *radii, int M, const float *bias, float *y, int relu, uint32_t *amax_bits,
-                                            void *stream)
+// the int8 DepthwiseConv2D entries: packed_conv_i8_entry's checks in its order, with F = Cin * mult and the row length kh * kw; codes:
+// the entry with codes and scales in place of y (y and amax_bits NULL)
+static int packed_dw_i8_entry(const char *name, const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                              int64_t H, int64_t W, int64_t Cin, int64_t mult, int kh, int kw, int sh, int sw, int rh,
+                              int rw, int same_padding, const uint8_t *packed, int bits, int zero_code,
+                              const double *radii, int M, const float *bias, float *y, int relu, uint32_t *amax_bits,
+                              void *stream, const ConvCodesOut *codes = nullptr)
 {
-    const char *name = "gpfq_packed_depthwise_conv2d_forward_i8";
     if (relu != 0 && relu != 1) return fail(GPFQ_ERR_INVALID_ARG, "relu=%d: must be 0 or 1", relu);
     if (n < 0) return fail(GPFQ_ERR_INVALID_ARG, "negative size n=%lld", (long long)n);
     if (H <= 0 || W <= 0 || Cin <= 0) return fail(GPFQ_ERR_INVALID_ARG, "bad image shape H=%lld W=%lld Cin=%lld", (long long)H, (long long)W, (long long)Cin);
@@ -1205,8 +1205,18 @@ int gpfq_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t
             hipError_t e = gpfq::launch_amax_clear(amax_bits, n, static_cast<hipStream_t>(stream));
             if (e != hipSuccess) return hip_fail(e, name);
         }
+        if (codes && n > 0) {                       // the composition's second half on rows of no column: the scales alone
+            if (!codes->amax_bits || !codes->scales) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+            if (n > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "too many images for one launch");
+            hipError_t e = gpfq::launch_quantize_rows_i8_from_amax(nullptr, n, 0, 0, codes->amax_bits, codes->yq, codes->ldyq, codes->scales,
+                                                                   static_cast<hipStream_t>(stream));
+            if (e != hipSuccess) return hip_fail(e, name);
+        }
         return GPFQ_OK;
     }
+    if (codes && !gpfq::packed_dw_i8_codes_fits(Cin, mult, kh, kw))
+        return fail(GPFQ_ERR_UNSUPPORTED, "the code-out form takes mult=%lld == 1 and Cin=%lld that is a multiple of 16 "
+                    "(gpfq_packed_depthwise_codes_supported)", (long long)mult, (long long)Cin);
     // what the kernel indexes with 32 bits: a place inside an image, a position, a tap's row and column, a channel
     const int64_t limit = 1LL << 24, keh = kh + (int64_t)(kh - 1) * (rh - 1), kew = kw + (int64_t)(kw - 1) * (rw - 1);
     if (H > limit || W > limit || sh > limit || sw > limit || keh > limit || kew > limit || H * W > 2147483647LL / Cin)
@@ -1215,13 +1225,55 @@ int gpfq_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t
     if (oh * ow > 0x7fff0000LL / n) return fail(GPFQ_ERR_UNSUPPORTED, "n*OH*OW output positions: too many for one launch");
     if (gpfq::packed_dw_i8_blocks(n, oh, ow, Cin * mult) > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "layer too wide for one launch");
     if (ldq < H * W * Cin) return fail(GPFQ_ERR_INVALID_ARG, "image pitch ldq=%lld < H*W*Cin=%lld", (long long)ldq, (long long)(H * W * Cin));
-    if (!xq || !scales || !packed || !radii || !y) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+    if (!xq || !scales || !packed || !radii || (!y && !codes)) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
     if (reinterpret_cast<uintptr_t>(xq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "xq must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "packed must be 16-byte aligned");
     const gpfq::ConvI8Shape S = conv_i8_shape(H, W, Cin, kh, kw, sh, sw, rh, rw, same_padding, oh, ow);
+    if (codes) {
+        const int64_t C = Cin * mult;
+        if (codes->ldyq % 16 != 0 || codes->ldyq < oh * ow * C)
+            return fail(GPFQ_ERR_INVALID_ARG, "code pitch ldyq=%lld must be a multiple of 16 and at least OH*OW*C=%lld", (long long)codes->ldyq,
+                        (long long)(oh * ow * C));
+        if (!codes->amax_bits || !codes->yq || !codes->scales) return fail(GPFQ_ERR_INVALID_ARG, "NULL pointer");
+        if (reinterpret_cast<uintptr_t>(codes->yq) % 16 != 0) return fail(GPFQ_ERR_INVALID_ARG, "yq must be 16-byte aligned");
+        if (gpfq::packed_dw_i8_codes_blocks(n, oh, ow, C) > 2147483647LL) return fail(GPFQ_ERR_UNSUPPORTED, "layer too wide for one launch");
+        hipError_t e = gpfq::launch_packed_depthwise_conv2d_forward_i8_codes(xq, n, ldq, scales, S, packed, bits, zero_code, radii, M, bias,
+                                                                             relu, codes->amax_bits, codes->yq, codes->ldyq, codes->scales,
+                                                                             static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
+    }
     hipError_t e = gpfq::launch_packed_depthwise_conv2d_forward_i8(xq, n, ldq, scales, S, (int)mult, packed, bits, zero_code, radii, M, bias, y,
                                                                    relu, amax_bits, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? GPFQ_OK : hip_fail(e, name);
+}
+
+int gpfq_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                            int64_t H, int64_t W, int64_t Cin, int64_t mult, int kh, int kw, int sh, int sw, int rh,
+                                            int rw, int same_padding, const uint8_t *packed, int bits, int zero_code,
+                                            const double *radii, int M, const float *bias, float *y, int relu, uint32_t *amax_bits,
+                                            void *stream)
+{
+    return packed_dw_i8_entry("gpfq_packed_depthwise_conv2d_forward_i8", xq, n, ldq, scales, H, W, Cin, mult, kh, kw, sh, sw, rh, rw,
+                              same_padding, packed, bits, zero_code, radii, M, bias, y, relu, amax_bits, stream);
+}
+
+int gpfq_packed_depthwise_codes_supported(int64_t H, int64_t W, int64_t Cin, int64_t mult, int kh, int kw, int sh, int sw, int rh, int rw,
+                                          int same_padding, int bits)
+{
+    (void)same_padding;                             // (the pads move the taps, not the form's range)
+    if (H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || rh <= 0 || rw <= 0 || (bits != 2 && bits != 4 && bits != 8)) return 0;
+    return gpfq::packed_dw_i8_codes_fits(Cin, mult, kh, kw) ? 1 : 0;
+}
+
+int gpfq_packed_depthwise_conv2d_forward_i8_codes(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                                  int64_t H, int64_t W, int64_t Cin, int64_t mult, int kh, int kw, int sh, int sw, int rh,
+                                                  int rw, int same_padding, const uint8_t *packed, int bits, int zero_code,
+                                                  const double *radii, int M, const float *bias, int relu,
+                                                  const uint32_t *out_amax_bits, int8_t *yq, int64_t ldyq, float *out_scales, void *stream)
+{
+    const ConvCodesOut codes{out_amax_bits, yq, ldyq, out_scales};
+    return packed_dw_i8_entry("gpfq_packed_depthwise_conv2d_forward_i8_codes", xq, n, ldq, scales, H, W, Cin, mult, kh, kw, sh, sw, rh, rw,
+                              same_padding, packed, bits, zero_code, radii, M, bias, nullptr, relu, nullptr, stream, &codes);
 }
 
 // MaxPooling2D on the int8 route: the checks in the pattern of the image entries above, every one before any launch

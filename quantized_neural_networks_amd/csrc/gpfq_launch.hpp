@@ -413,6 +413,17 @@ int64_t packed_dw_i8_blocks(int64_t n, int64_t OH, int64_t OW, int64_t C);
 hipError_t launch_packed_depthwise_conv2d_forward_i8(const int8_t *xq, int64_t n, int64_t ldq, const float *scales, const ConvI8Shape &S,
                                                      int mult, const uint8_t *packed, int bits, int zero_code, const double *radii, int M,
                                                      const float *bias, float *y, int relu, uint32_t *amax_bits, hipStream_t stream);
+// gpfq_packed_dw_i8_codes.hip: the same pass for mult = 1 and Cin a multiple of 16 that stores, in place of y,
+// the int8 codes launch_quantize_rows_i8_from_amax would make of that launcher's y under out_amax_bits (only read), and out_scales: one
+// launch, no atomics.  packed_dw_i8_codes_fits: the form's range (host arithmetic); packed_dw_i8_codes_blocks: the workgroups of the
+// launch, for the entry's check.
+bool packed_dw_i8_codes_fits(int64_t Cin, int64_t mult, int kh, int kw);
+int64_t packed_dw_i8_codes_blocks(int64_t n, int64_t OH, int64_t OW, int64_t C);
+hipError_t launch_packed_depthwise_conv2d_forward_i8_codes(const int8_t *xq, int64_t n, int64_t ldq, const float *scales,
+                                                           const ConvI8Shape &S, const uint8_t *packed, int bits, int zero_code,
+                                                           const double *radii, int M, const float *bias, int relu,
+                                                           const uint32_t *out_amax_bits, int8_t *yq, int64_t ldyq, float *out_scales,
+                                                           hipStream_t stream);
 // gpfq_pool_i8.hip: MaxPooling2D of float32 NHWC images, and from the same registers either their int8 codes
 // and scales under the maxima amax_in (one launch) or, amax_in NULL, their maxima into the cleared amax_out.  S as above with
 // kh x kw the window, Cin the channels and rh = rw = 1; the entry has checked n * OH * OW * Cin < 2^31.

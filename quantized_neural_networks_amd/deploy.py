@@ -468,22 +468,22 @@ def _apply_fusion(net, packed_at, pools=False, adds=False, avgpools=False, resid
 
 
 def _code_producers(net):
-    """The PackedConv2D layers of a fused network that can hand their output on as int8 codes, by name: the
-    LINK entries of net.fusion_plan whose producer is a PackedConv2D with no pool in between and no residual join in its epilogue,
-    and whose output images are a multiple of 16 values long (the pitch of the consumer's int8 images)."""
+    """The PackedConv2D and PackedDepthwiseConv2D layers of a fused network that can hand their output on as int8 codes (DESIGN.md
+    sections 11j, 11k), by name: the LINK entries of net.fusion_plan whose producer is one of the two with no pool in between and no
+    residual join in its epilogue, and whose output images are a multiple of 16 values long (the pitch of the consumer's int8 images)."""
     by_name = {l.name: l for l in net.layers}
     out = {}
     for e in getattr(net, "fusion_plan", None) or []:
         layer = by_name.get(e["layer"])
-        if (isinstance(layer, keras_shim.PackedConv2D) and isinstance(e["hands_to"], str) and e.get("pool") is None
+        if (isinstance(layer, (keras_shim.PackedConv2D, keras_shim.PackedDepthwiseConv2D)) and isinstance(e["hands_to"], str) and e.get("pool") is None
                 and e.get("residual") is None and int(np.prod(layer.output_shape[1:])) % 16 == 0):
             out[layer.name] = layer
     return out
 
 
 def calibrate_code_amax(net, batches):
-    """{producer name: float} for load_packed(..., fuse=True, code_amax=...): for every PackedConv2D of ``net`` (loaded with fuse=True)
-    that can hand its output on as codes (LINK entries of net.fusion_plan with a PackedConv2D producer and no pool), the largest
+    """{producer name: float} for load_packed(..., fuse=True, code_amax=...): for every PackedConv2D or PackedDepthwiseConv2D of ``net``
+    (loaded with fuse=True) that can hand its output on as codes (LINK entries of net.fusion_plan with such a producer and no pool), the largest
     finite maximum of |output| over all images of all ``batches`` (each an input batch of the network).  The maxima are the cells
     the fused kernels leave for the next layer's quantizer anyway; they are read back once per batch."""
     producers = _code_producers(net)
@@ -562,10 +562,11 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
     form where its shape is inside that form's range (keras_shim.PackedConv2D.conv_form).  The plan of fuse=True and the other
     switches is untouched, and every value is bit for bit what staged_conv=False computes.
 
-    code_amax={producer name: maximum} (needs fuse=True): calibrated activation ranges.  Every named layer
-    must be a PackedConv2D that the plan links to a packed consumer with no pool in between (calibrate_code_amax lists them and
-    measures their maxima; any other name raises ValueError).  Such a layer stores no float32 output: one kernel
-    (hip.packed_conv2d_forward_i8_codes) writes the int8 codes of its output under the given maximum -- values beyond it clamp to
+    code_amax={producer name: maximum} (needs fuse=True; DESIGN.md sections 11j, 11k): calibrated activation ranges.  Every named layer
+    must be a PackedConv2D -- or, with packed_depthwise=True, a PackedDepthwiseConv2D -- that the plan links to a packed consumer with
+    no pool in between (calibrate_code_amax lists them and measures their maxima; any other name raises ValueError).  Such a layer
+    stores no float32 output: one kernel (hip.packed_conv2d_forward_i8_codes / hip.packed_depthwise_conv2d_forward_i8_codes) writes
+    the int8 codes of its output under the given maximum -- values beyond it clamp to
     +-127 -- and the value at its position is that int8 tensor, which the consumer takes as its input codes under the proof of
     _FusedI8.  The plan is untouched; the default None changes nothing.  The result is bit for bit what fuse=True alone computes
     when each such link's quantizer is handed the same maximum."""
@@ -658,7 +659,7 @@ def load_packed(path, device=None, activations="float32", packed_conv=False, fus
         by_name = {l.name: l for l in net.layers}
         for name, value in code_amax.items():
             if name not in producers:
-                raise ValueError(f"code_amax names {name!r}, which is not a PackedConv2D that hands its output to a packed layer with "
+                raise ValueError(f"code_amax names {name!r}, which is not a PackedConv2D or PackedDepthwiseConv2D that hands its output to a packed layer with "
                                  f"no pool in between (calibrate_code_amax lists those: {sorted(producers)})")
             producers[name].code_amax = float(value)
             by_name[consumer[name]].codes_from = producers[name]

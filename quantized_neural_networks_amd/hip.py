@@ -92,6 +92,9 @@ SYMBOLS = {
     "gpfq_quantize_rows_i8_from_amax": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "gpfq_packed_depthwise_conv2d_forward_i8": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int,
                                                        _int, _vp, _int, _int, _vp, _int, _vp, _vp, _int, _vp, _vp]),
+    "gpfq_packed_depthwise_codes_supported": (_int, [_i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int]),
+    "gpfq_packed_depthwise_conv2d_forward_i8_codes": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int,
+                                                             _int, _vp, _int, _int, _vp, _int, _vp, _int, _vp, _vp, _i64, _vp, _vp]),
     "gpfq_maxpool2d_forward_i8": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "gpfq_add_forward_i8": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp]),
     "gpfq_global_avgpool_forward_i8": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
@@ -1774,6 +1777,57 @@ def packed_depthwise_conv2d_forward_i8(x_or_xq, packed, bits, zero_code, radii, 
                                                               radii.data_ptr(), int(M), bp, out.data_ptr(), relu, ap, _stream()),
                "gpfq_packed_depthwise_conv2d_forward_i8")
     return out
+
+
+def packed_depthwise_codes_supported(kernel_shape, strides, dilation, padding, H, W, bits):
+    """Whether the code-out form of the int8 packed DepthwiseConv2D forward pass takes a kernel
+    [kh][kw][Cin][mult] = kernel_shape on H x W images: mult == 1, Cin a multiple of 16, kh * kw <= GPFQ_PACKED_DW_MAX_TAPS
+    (gpfq_packed_depthwise_codes_supported: host arithmetic, no device needed)."""
+    kh, kw, Cin, mult = (int(v) for v in kernel_shape)
+    kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
+    return bool(load().gpfq_packed_depthwise_codes_supported(int(H), int(W), Cin, mult, kh, kw, sh, sw, rh, rw, 1 if same else 0, int(bits)))
+
+
+def packed_depthwise_conv2d_forward_i8_codes(x_or_xq, packed, bits, zero_code, radii, M, kernel_shape, strides, dilation, padding, out_amax,
+                                             bias=None, relu=False, scales=None, amax=None):
+    """(yq i8 [n][OH][OW][Cin*mult], out_scales f32 [n]) of a packed DepthwiseConv2D layer on the int8 route: the int8 codes and scales
+    of its output under the maxima out_amax -- what packed_depthwise_conv2d_forward_i8(..., relu=relu) followed by
+    quantize_rows_i8(y, amax=out_amax) leaves, bit for bit, from ONE launch that never stores the float32 y
+    (gpfq_packed_depthwise_conv2d_forward_i8_codes; the contract is include/gpfq.h's).  out_amax and the other
+    arguments as for packed_conv2d_forward_i8_codes / packed_depthwise_conv2d_forward_i8.  Where packed_depthwise_codes_supported is
+    false (mult > 1, or Cin not a multiple of 16) the two calls named above run into a temporary y: the same bits.  yq's images are
+    contiguous and its image pitch is a multiple of 16: it is what the next layer's binding takes as a ready xq together with
+    out_scales.  No sync."""
+    kh, kw, Cin, mult = (int(v) for v in kernel_shape)
+    kh, kw, sh, sw, rh, rw, same = conv_geometry((kh, kw), strides, dilation, padding)
+    xq, scales, n, H, W, ldq = _i8_images(x_or_xq, (kh, kw, Cin, mult), (sh, sw, rh, rw), scales, amax)
+    cells = _code_amax_cells(out_amax, n, xq.device)
+    OH, OW = patch_out_dim(H, kh, sh, rh, same), patch_out_dim(W, kw, sw, rw, same)
+    C = Cin * mult
+    per = OH * OW * C
+    if not packed_depthwise_codes_supported((kh, kw, Cin, mult), (sh, sw), (rh, rw), padding, H, W, bits):
+        if xq.dim() == 2:                               # (float images quantized above: rows of roundup16(H W Cin) bytes)
+            xq = xq[:, :H * W * Cin].unflatten(1, (H, W, Cin))
+        y = packed_depthwise_conv2d_forward_i8(xq, packed, bits, zero_code, radii, M, (kh, kw, Cin, mult), (sh, sw), (rh, rw), padding,
+                                               bias=bias, scales=scales, relu=relu)
+        yq, out_scales = quantize_rows_i8(y.reshape(n, per), amax=cells)
+        return yq[:, :per].unflatten(1, (OH, OW, C)), out_scales
+    if _packed_args(packed, bits, zero_code, radii, kh * kw) != C:
+        raise GpfqError(f"radii has {radii.numel()} entries, the kernel {Cin} x {mult} output channels")
+    if relu not in (False, True, 0, 1):
+        raise GpfqError(f"relu must be a bool, got {relu!r}")
+    if bias is not None:
+        _dev(bias, torch.float32, "bias")
+        if bias.numel() != C or not bias.is_contiguous():
+            raise GpfqError(f"bias must be a contiguous [{C}] tensor")
+    yq = torch.empty((n, OH, OW, C), dtype=torch.int8, device=xq.device)
+    out_scales = torch.empty(n, dtype=torch.float32, device=xq.device)
+    with torch.cuda.device(xq.device):
+        _check(load().gpfq_packed_depthwise_conv2d_forward_i8_codes(
+            xq.data_ptr(), n, ldq, scales.data_ptr(), H, W, Cin, mult, kh, kw, sh, sw, rh, rw, 1 if same else 0, packed.data_ptr(), int(bits),
+            int(zero_code), radii.data_ptr(), int(M), bias.data_ptr() if bias is not None else None, int(bool(relu)), cells.data_ptr(),
+            yq.data_ptr(), max(per, 16), out_scales.data_ptr(), _stream()), "gpfq_packed_depthwise_conv2d_forward_i8_codes")
+    return yq, out_scales
 
 
 def maxpool2d_forward_i8(x, pool_size, strides, padding, amax=None):

@@ -392,8 +392,9 @@ class _FusedI8:
         hand = getattr(self.codes_from, "_codes", None) if self.codes_from is not None else None
         if x.dtype == torch.int8:
             if hand is None or not _untouched(x, hand[0](), hand[1], torch.int8) or rows != hand[3].numel() or row_len != hand[4]:
+                producer = type(self.codes_from).__name__ if self.codes_from is not None else "PackedConv2D"
                 raise TypeError(f"layer {self.name} was handed an int8 tensor that is not the untouched code output of the layer in "
-                                f"front of it (PackedConv2D.code_amax): int8 inputs are taken as codes under that proof alone")
+                                f"front of it ({producer}.code_amax): int8 inputs are taken as codes under that proof alone")
             return hand[2], hand[3]
         if hand is None:
             return None
@@ -757,7 +758,10 @@ class PackedDepthwiseConv2D(DepthwiseConv2D, _FusedI8):
     gpfq_packed_depthwise_conv2d_forward_i8 -- exact int32 sums, the float kernel is never formed (include/gpfq.h has the arithmetic;
     the layer's alphabet must be linspace(-1, 1, M) and kh * kw at most GPFQ_PACKED_DW_MAX_TAPS, which deploy.load_packed checks).  A
     property of the loaded layer, not of its configuration: config(), clone() and save_model() record the DepthwiseConv2D it decodes
-    to.  ``fused``, ``emit_amax``, ``amax_from``: _FusedI8."""
+    to.  ``fused``, ``emit_amax``, ``amax_from``: _FusedI8.  ``code_amax`` (load_packed(..., fuse=True, code_amax=...); DESIGN.md section
+    11k): a calibrated maximum of this layer's output.  When set on a layer that hands its output to a packed layer, the int8 call is
+    hip.packed_depthwise_conv2d_forward_i8_codes and RETURNS THE INT8 CODES of the output under that maximum; ``_codes`` remembers
+    them with their scales for the consumer's proof, exactly as PackedConv2D does."""
 
     ACTIVATIONS = ("float32", "int8")
 
@@ -767,6 +771,8 @@ class PackedDepthwiseConv2D(DepthwiseConv2D, _FusedI8):
         self.packed = None
         self.activations = "float32"
         self._init_fused()
+        self.code_amax = None                        # (load_packed(..., code_amax=...): the maximum this layer's output is quantized under)
+        self._codes = None                            # (weak reference to the int8 output, its version, xq, scales, codes per image)
 
     def build(self, input_shape, device, rng):
         Layer.build(self, input_shape, device, rng)
@@ -827,6 +833,17 @@ class PackedDepthwiseConv2D(DepthwiseConv2D, _FusedI8):
         radii, bias, relu, rest = self._fused_parts(self._bias())
         x = x.contiguous()
         n = int(x.shape[0])
+        self._codes = None
+        if self.code_amax is not None and self.emit_amax and n > 0:
+            # the hand-over in codes: the int8 tensor is this layer's output, and the consumer's whole input
+            x, given = self._i8_input(x)
+            yq, out_scales = hip.packed_depthwise_conv2d_forward_i8_codes(x, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]),
+                                                                          self.kernel_shape, self.strides, self.dilation_rate, self.padding,
+                                                                          float(self.code_amax), bias=bias, relu=relu, **given)
+            per = yq[0].numel()
+            self._codes = (weakref.ref(yq), yq._version, yq.reshape(n, per), out_scales, per)
+            self._handoff = self._out = None
+            return yq
         amax_out = self._amax_out(n, x.device)
         x, given = self._i8_input(x)
         y = hip.packed_depthwise_conv2d_forward_i8(x, p["codes"], p["bits"], p["zero_code"], radii, len(p["alphabet"]), self.kernel_shape,
